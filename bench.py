@@ -13,6 +13,7 @@ film (three buffers, one contiguous allocation) is gathered to rank 0 over RCCL 
 step ends when the whole frame is assembled on rank 0. Total work is fixed, so scaling is "strong".
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   (also writes the last step's film to DIR/*.npy)
   python bench.py --gpus N --steps K --warmup W            (starts the N ranks itself, one child process per GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
@@ -325,6 +326,34 @@ def self_launch(n):
     return 0
 
 
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20240607  # the pixel sample of a film larger than the budget is the same in every run
+
+
+def dump_outputs(out_dir, image, xyz):
+    """The assembled frame (rank 0's film buffers, [H, W, C] float64 each) as DIR/<name>.npy: film_pixels (sum of each
+    wavelength + filter weight), film_avgs (mean), film_vars (variance) -- or film_xyz for the XYZ film -- over the
+    pixels listed in pixel_index (row-major y * W + x). All pixels when they fit in DUMP_BUDGET_BYTES, else a seeded
+    random sample of them in ascending order, so two builds given the same arguments write comparable files."""
+    import numpy as np
+    import torch
+
+    names = ["film_xyz"] if xyz else ["film_pixels", "film_avgs", "film_vars"]
+    flat = [t.reshape(-1, t.shape[-1]) for t in image]
+    n_pixels = flat[0].shape[0]
+    per_pixel = 8 * (1 + sum(int(t.shape[1]) for t in flat))  # the index plus every channel, float64
+    keep = min(n_pixels, (DUMP_BUDGET_BYTES - 4096) // per_pixel)  # less room for the .npy headers
+    if keep == n_pixels:
+        index = np.arange(n_pixels, dtype=np.int64)
+    else:
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_pixels, size=keep, replace=False))
+    rows = torch.from_numpy(index).to(flat[0].device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "pixel_index.npy"), index.astype(np.float64))
+    for name, t in zip(names, flat):
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, rows).cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -343,12 +372,17 @@ def main():
     ap.add_argument("--film", default="spectral", choices=["spectral", "xyz"],
                     help="spectral = the reference's film (the headline metric); xyz = DRT_MODE_XYZ, a different mode, labelled as such")
     ap.add_argument("--checksum", action="store_true", help="add an order-independent checksum of the assembled frame to the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's assembled film to DIR/<name>.npy (float64; a fixed, seeded "
+                         "sample of pixels when the whole film exceeds %d MB)" % (DUMP_BUDGET_BYTES // 10**6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-oneshot", action="store_true", help="skip the one-shot (PCIe-inclusive) leg")
     ap.add_argument("--oneshot-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal only: all ranks use GPU 0 (needs --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # RCCL across processes needs dmabuf IPC on this driver
     wl_scene, wl_size, wl_spp, wl_depth, wl_label = WORKLOADS[args.workload]
@@ -600,6 +634,12 @@ def main():
                     fb.finish()
             torch.cuda.synchronize()
             out["frame_checksum"] = [int(t.view(torch.int64).sum().item()) for t in blocks[0].image]
+        if args.dump_outputs:
+            if world == 1:
+                for fb in blocks:
+                    fb.finish()
+            torch.cuda.synchronize()
+            dump_outputs(args.dump_outputs, blocks[0].image, xyz)
         if not args.no_cpu_baseline:
             # rank 0 only, after the timed region (the other ranks wait at the final barrier)
             out["cpu_baseline"] = cpu_baseline(lambda: load_workload_scene(wl_scene, W, H), W, H, args.depth)

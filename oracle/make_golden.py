@@ -1,6 +1,9 @@
 """Generate tests/golden/*.npz from the REAL reference path (oracle/_ref/libdrt_ref.so).
 
 Run in a container where /root/reference exists:  make -C oracle ref && python oracle/make_golden.py [render case ...]
+`python oracle/make_golden.py --records` instead rewrites tests/golden/reference_records.json and reference_arrays.npz: the
+reference's answers to the checks of tests/test_oracle_vs_reference.py and tests/test_reference_parser.py, recorded by running
+those tests against oracle/_ref (tests/reference_records.py).
 The fixtures are data only (inputs + the reference's outputs); they let the oracle be checked on
 machines where the reference cannot be built (the GPU box). Every array is float64/int32/uint64,
 loaded with numpy.load(allow_pickle=False).
@@ -245,6 +248,11 @@ def gen_renders(R, only=None):
 def main():
     os.makedirs(OUT, exist_ok=True)
     R = O.ref_lib()
+    if sys.argv[1:] == ["--records"]:
+        import subprocess
+        tests = [os.path.join(REPO, "tests", t) for t in ("test_oracle_vs_reference.py", "test_reference_parser.py")]
+        env = dict(os.environ, DRT_RECORD_REFERENCE="1")
+        raise SystemExit(subprocess.call([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider"] + tests, cwd=REPO, env=env))
     bundle = pydrt.load_scene(cases.scene_path("cornell_plane_light.scn"), 64, 64)
     R.ref_set_scene(C.byref(bundle.scene))
     if len(sys.argv) > 1:  # python oracle/make_golden.py <render case> ...: only those fixtures

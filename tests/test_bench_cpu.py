@@ -86,3 +86,37 @@ def test_committed_profiles_name_their_workloads_and_belong_to_this_build():
         assert pj["csrc_sha"] == bench.csrc_sha(), "%s was taken from other kernel sources: refresh the profiles" % name
     line = json.load(open(os.path.join(REPO, "profiles", "r03_bench_line.json")))
     assert line["roofline"]["frac"] is not None and "stale_profile" not in line["roofline"]
+
+
+def test_dump_outputs_writes_the_film_whole_or_as_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every pixel of a film that fits the budget; a seeded sample in ascending pixel order otherwise, the same
+    sample in every run, the files (float64, .npy headers included) within the budget."""
+    import numpy as np
+    import torch
+    H, W, S = 12, 10, 5
+    g = torch.Generator().manual_seed(3)
+    image = [torch.rand((H, W, c), dtype=torch.float64, generator=g) for c in (S + 1, S, S)]
+    whole = tmp_path / "whole"
+    bench.dump_outputs(str(whole), image, False)
+    assert sorted(os.listdir(whole)) == ["film_avgs.npy", "film_pixels.npy", "film_vars.npy", "pixel_index.npy"]
+    assert np.array_equal(np.load(whole / "pixel_index.npy"), np.arange(H * W, dtype=np.float64))
+    for name, t in zip(("film_pixels", "film_avgs", "film_vars"), image):
+        a = np.load(whole / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, t.reshape(-1, t.shape[-1]).numpy())
+    budget = 4096 + 8 * (1 + 3 * S + 1) * 37
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("sample%d" % k)
+        bench.dump_outputs(str(d), image, False)
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= budget
+        runs.append({f: np.load(d / f) for f in os.listdir(d)})
+    idx = runs[0]["pixel_index.npy"]
+    assert len(idx) == 37 and np.all(np.diff(idx) > 0) and idx.max() < H * W
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f])
+    rows = idx.astype(np.int64)
+    assert np.array_equal(runs[0]["film_vars.npy"], image[2].reshape(-1, S).numpy()[rows])
+    xyz = tmp_path / "xyz"
+    bench.dump_outputs(str(xyz), [torch.ones((H, W, 8), dtype=torch.float64)], True)
+    assert sorted(os.listdir(xyz)) == ["film_xyz.npy", "pixel_index.npy"]
