@@ -2342,3 +2342,101 @@ __global__ void drt_unit_kernel(int func, const double *__restrict__ in, uint32_
         default: break;
     }
 }
+
+/* Material-layer self-test (see drt_selftest_material in include/drt_hip.h): one record per thread against the context's own device
+ * scene. A record is a scene point; the kernel does to it what the trace and shade kernels do between them -- eval_coefficients,
+ * record_media_word, fresnel_rows, then bdsf_at_wavelength per wavelength on the rows the shade kernel reads -- or calls
+ * sample_direction. A record with no override reads the scene's own material table (sc.mats); one with an override reads
+ * `variants`: DRT_MAT_VARIANTS copies of that table in which every material lists one BDSF only (copies 0-6) or samples with
+ * another dir_func (copies 7-12), derived by the launcher the way build_device_scene derives the table. A record picks its table by
+ * pointing the SceneView at it. The launcher has checked every index a record carries before the launch. */
+enum
+{
+    DRT_MAT_EVALUATE = 0, /* in: position[3] normal[3] out[3] on_dot  surface incident transmit  bdsf override  incoming[3]  mode     (18)
+                             out: reflectance[S], EvalCoef.flags                                                               (S + 1) */
+    DRT_MAT_SAMPLE,       /* in: position[3] normal[3] out[3] on_dot  surface incident transmit  dir_func override  rng state bits (15)
+                             out: dir[3] recip_pdf, rng state after (bits), draws                                                  (6) */
+    DRT_MAT_COUNT
+};
+#define DRT_MAT_EVAL_IN 18
+#define DRT_MAT_SAMPLE_IN 15
+#define DRT_MAT_SAMPLE_OUT 6
+#define DRT_MAT_MODE_UNPAIRED 1u /* evaluate: record word 2 without its pair rows (PAIR_NONE): every Fresnel term from ir, tr, te */
+#define DRT_MAT_MODE_SIMPLE 2u   /* evaluate: bdsf_at_wavelength<true>, the shade kernel's instantiation without the Fresnel cases */
+#define DRT_MAT_VARIANTS (DRT_NUM_BDSFS + DRT_NUM_DIRFS) /* copies of the material table in `variants` */
+
+__global__ void drt_material_kernel(DevScene sc, const DevMaterial *__restrict__ variants, int func, const double *__restrict__ in,
+                                    uint32_t in_stride, double *__restrict__ out, uint32_t out_stride, uint64_t n)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *a = in + i * in_stride;
+    double *o = out + i * out_stride;
+    SceneView sv; /* the scene's tables in HBM, as the trace kernel sees a scene that does not fit LDS */
+    sv.surf = sc.surf;
+    sv.lights = sc.lights;
+    sv.surf_type = sc.surf_type;
+    sv.surf_mat = sc.surf_mat;
+    sv.light_type = sc.light_type;
+    sv.light_mat = sc.light_mat;
+    sv.bvh_nodes = sc.bvh_nodes;
+    sv.bvh_leaf = sc.bvh_leaf;
+    sv.n_surf = sc.n_surf;
+    sv.n_lights = sc.n_lights;
+    HitPoint ip;
+    ip.position = v3(a[0], a[1], a[2]);
+    ip.normal = v3(a[3], a[4], a[5]);
+    ip.out = v3(a[6], a[7], a[8]);
+    ip.on_dot = a[9];
+    ip.surface_mat = (uint32_t)a[10];
+    ip.incident_mat = (uint32_t)a[11];
+    ip.transmit_mat = (uint32_t)a[12];
+    ip.index = 0;
+    const int sel = (int)a[13]; /* -1: the material's own list / dir_func */
+    if (func == DRT_MAT_SAMPLE)
+    {
+        sv.mats = sel < 0 ? sc.mats : variants + (uint64_t)(DRT_NUM_BDSFS + sel) * sc.n_mat;
+        uint64_t rs = (uint64_t)__double_as_longlong(a[14]);
+        uint32_t draws = 0;
+        V3 dir;
+        double recip_pdf;
+        sample_direction(sc, sv, ip, rs, draws, dir, recip_pdf);
+        o[0] = dir.x; o[1] = dir.y; o[2] = dir.z;
+        o[3] = recip_pdf;
+        o[4] = __longlong_as_double((long long)rs);
+        o[5] = (double)draws;
+        return;
+    }
+    sv.mats = sel < 0 ? sc.mats : variants + (uint64_t)sel * sc.n_mat;
+    const uint32_t mode = (uint32_t)a[17];
+    const V3 incoming = v3(a[14], a[15], a[16]);
+    /* trace kernel: the scalars of the direction and the record words (drt_trace_kernel, "sampled continuation") */
+    const DevMaterial &mat = sv.mats[ip.surface_mat];
+    const EvalCoef e = eval_coefficients(sc, sv, ip, incoming);
+    uint64_t w2 = record_media_word(sc, sv, ip);
+    if (mode & DRT_MAT_MODE_UNPAIRED) w2 |= (uint64_t)PAIR_NONE << 48;
+    const uint32_t flags = e.flags | mat.vertex_flags;
+    /* shade kernel: the rows of the record, then the BDSF sum per wavelength (drt_shade_kernel, "the general BDSF list") */
+    uint32_t i_ir, i_tr, i_te;
+    bool paired;
+    fresnel_rows(w2, i_ir, i_tr, i_te, paired);
+    const uint32_t i_diffuse = (uint32_t)mat.diffuse_spd & 0xFFFFu, i_glossy = (uint32_t)mat.glossy_spd & 0xFFFFu;
+    const uint32_t i_mirror = (uint32_t)mat.mirror_spd & 0xFFFFu;
+    const bool simple = (mode & DRT_MAT_MODE_SIMPLE) != 0u;
+    for (uint32_t lam = 0; lam < sc.S; lam += 1)
+    {
+        const double diffuse = spd_at(sc.spds, sc.S, i_diffuse, lam), glossy = spd_at(sc.spds, sc.S, i_glossy, lam);
+        const double mirror = spd_at(sc.spds, sc.S, i_mirror, lam);
+        double r;
+        if (simple) r = bdsf_at_wavelength<true>(mat.bdsf_packed, mat.num_bdsfs, diffuse, glossy, mirror, 0.0, 0.0, 0.0, ip.on_dot, e.a_in,
+                                                 e.spec, e.mn_dot, e.ct_coef, flags, paired);
+        else
+        {
+            const double ir = spd_at(sc.spds, sc.S, i_ir, lam), tr = spd_at(sc.spds, sc.S, i_tr, lam), te = spd_at(sc.spds, sc.S, i_te, lam);
+            r = bdsf_at_wavelength<false>(mat.bdsf_packed, mat.num_bdsfs, diffuse, glossy, mirror, ir, tr, te, ip.on_dot, e.a_in, e.spec,
+                                          e.mn_dot, e.ct_coef, flags, paired);
+        }
+        o[lam] = r;
+    }
+    o[sc.S] = (double)e.flags;
+}

@@ -59,6 +59,8 @@ struct drt_context
     double      interval = 0.0;
 
     std::vector<void *> allocations; /* scene tables */
+    std::vector<DevMaterial> host_mats;        /* what d.mats holds (drt_selftest_material derives its override tables from it) */
+    DevMaterial *d_mat_variants = nullptr;     /* those tables, made on the first drt_selftest_material call */
     double *d_pixels = nullptr, *d_avgs = nullptr, *d_vars = nullptr; /* XYZ film mode: d_pixels is [n_pix][XYZ_FILM_WORDS], the others stay null */
     bool    xyz_mode = false;
     bool    own_film = false;
@@ -368,6 +370,16 @@ struct BvhBuilder
 
 static void shade_sets(uint32_t S, uint32_t *n_sets, uint32_t *tail_first, uint32_t *tail_count);
 
+/* what eval_coefficients must compute for a list holding BDSF b (DevMaterial.needs) */
+static uint32_t bdsf_needs(uint32_t b)
+{
+    if (b == DRT_BDSF_bp_glossy_bdsf) return NEED_GLOSSY;
+    if (b == DRT_BDSF_mirror_bdsf || b == DRT_BDSF_fs_conductor_bdsf || b == DRT_BDSF_fs_dielectric_reflectance_bdsf) return NEED_EQR;
+    if (b == DRT_BDSF_fs_dielectric_transmittance_bdsf) return NEED_EQT;
+    if (b == DRT_BDSF_ct_conductor_bdsf) return NEED_CT;
+    return 0u;
+}
+
 static int build_device_scene(drt_context *ctx, const drt_scene *scene, double reach)
 {
     const uint32_t S = scene->num_wavelengths;
@@ -521,10 +533,7 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
             if (b >= DRT_NUM_BDSFS) return fail(-2, "material %u: unknown bdsf id %u", i, b);
             dm.bdsfs[j] = b;
             dm.bdsf_packed |= (uint64_t)b << (4 * j);
-            if (b == DRT_BDSF_bp_glossy_bdsf) dm.needs |= NEED_GLOSSY;
-            if (b == DRT_BDSF_mirror_bdsf || b == DRT_BDSF_fs_conductor_bdsf || b == DRT_BDSF_fs_dielectric_reflectance_bdsf) dm.needs |= NEED_EQR;
-            if (b == DRT_BDSF_fs_dielectric_transmittance_bdsf) dm.needs |= NEED_EQT;
-            if (b == DRT_BDSF_ct_conductor_bdsf) dm.needs |= NEED_CT;
+            dm.needs |= bdsf_needs(b);
         }
         if (dm.num_bdsfs == 2 && dm.bdsfs[0] == DRT_BDSF_bp_diffuse_bdsf && dm.bdsfs[1] == DRT_BDSF_bp_glossy_bdsf) dm.vertex_flags = FLAG_PLASTIC;
         dm.pair_out = dm.pair_in = PAIR_NONE;
@@ -572,6 +581,7 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
     if ((rc = upload(ctx, lmat, &d.light_mat))) return rc;
     ctx->light0_em_spd = n_lights ? ((uint32_t)mats[lmat[0]].emission_spd & 0xFFFFu) : 0u; /* what the trace kernel writes into light 0's blocks */
     if ((rc = upload(ctx, mats, &d.mats))) return rc;
+    ctx->host_mats = mats;
     if ((rc = upload(ctx, spds, &d.spds))) return rc;
 
     ctx->cmf_rw = scene->cmf_rw; ctx->cmf_x = scene->cmf_x; ctx->cmf_y = scene->cmf_y; ctx->cmf_z = scene->cmf_z;
@@ -1939,6 +1949,104 @@ extern "C" int drt_selftest_unit(int device, int func, const double *in, uint32_
     HIP_TRY(hipMemcpy(din, in, n * in_stride * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dout, 0, n * out_stride * 8));
     hipLaunchKernelGGL(drt_unit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, func, din, in_stride, dout, out_stride, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout, n * out_stride * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    return 0;
+}
+
+/* Fresnel kind of a BDSF: 0 none, 1 dielectric, 2 conductor (build_device_scene's fresnel_kind, one function) */
+static int bdsf_fresnel_kind(uint32_t b)
+{
+    if (b == DRT_BDSF_fs_dielectric_reflectance_bdsf || b == DRT_BDSF_fs_dielectric_transmittance_bdsf) return 1;
+    if (b == DRT_BDSF_fs_conductor_bdsf || b == DRT_BDSF_ct_conductor_bdsf) return 2;
+    return 0;
+}
+
+/* the override tables of drt_material_kernel: the context's material table with every list replaced by one BDSF (copies 0-6) or
+ * every dir_func by another (copies 7-12). A one-function list needs what that function needs; its pair rows are kept only when the
+ * function is of the kind the rows were tabulated for (never read a dielectric's rel_sq row as a conductor's cA, cB), else PAIR_NONE. */
+static int material_variants(drt_context *ctx)
+{
+    if (ctx->d_mat_variants) return 0;
+    const uint32_t n_mat = ctx->dsc.n_mat;
+    std::vector<DevMaterial> v((size_t)DRT_MAT_VARIANTS * n_mat);
+    for (uint32_t k = 0; k < (uint32_t)DRT_MAT_VARIANTS; k += 1)
+        for (uint32_t m = 0; m < n_mat; m += 1)
+        {
+            DevMaterial dm = ctx->host_mats[m];
+            if (k < (uint32_t)DRT_NUM_BDSFS)
+            {
+                memset(dm.bdsfs, 0, sizeof(dm.bdsfs));
+                dm.bdsfs[0] = k;
+                dm.num_bdsfs = 1;
+                dm.bdsf_packed = k;
+                dm.needs = bdsf_needs(k);
+                dm.vertex_flags = 0;
+                const int rows = dm.pair_out == PAIR_NONE ? 0 : (dm.pair_out & PAIR_CONDUCTOR) ? 2 : 1;
+                if (rows == 0 || rows != bdsf_fresnel_kind(k)) dm.pair_out = dm.pair_in = PAIR_NONE;
+            }
+            else dm.dir_func = k - (uint32_t)DRT_NUM_BDSFS;
+            v[(size_t)k * n_mat + m] = dm;
+        }
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, v.size() * sizeof(DevMaterial)));
+    ctx->allocations.push_back(p);
+    HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
+    ctx->d_mat_variants = (DevMaterial *)p;
+    return 0;
+}
+
+extern "C" int drt_selftest_material(drt_context *ctx, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride,
+                                     uint64_t n)
+{
+    g_last_error.clear();
+    if (!ctx || !in || !out) return fail(-1, "null argument");
+    if (func < 0 || func >= DRT_MAT_COUNT) return fail(-1, "unknown material function %d", func);
+    const uint32_t S = ctx->dsc.S, n_mat = ctx->dsc.n_mat;
+    const uint32_t need_in = func == DRT_MAT_EVALUATE ? DRT_MAT_EVAL_IN : DRT_MAT_SAMPLE_IN;
+    const uint32_t need_out = func == DRT_MAT_EVALUATE ? S + 1u : DRT_MAT_SAMPLE_OUT;
+    if (in_stride < need_in || out_stride < need_out)
+        return fail(-1, "material function %d needs %u doubles in and %u out per record", func, need_in, need_out);
+    /* every index the kernel follows is checked here, so that no record makes it read outside the scene's tables */
+    auto index_ok = [](double x, double lo, double hi) { return x >= lo && x < hi && x == (double)(int64_t)x; };
+    for (uint64_t r = 0; r < n; r += 1)
+    {
+        const double *a = in + r * in_stride;
+        for (int k = 10; k < 13; k += 1)
+            if (!index_ok(a[k], 0.0, (double)n_mat)) return fail(-1, "record %llu: material index %g (the scene has %u)", (unsigned long long)r, a[k], n_mat);
+        const DevMaterial &sm = ctx->host_mats[(uint32_t)a[10]];
+        if (func == DRT_MAT_EVALUATE)
+        {
+            if (!index_ok(a[13], -1.0, (double)DRT_NUM_BDSFS)) return fail(-1, "record %llu: unknown bdsf id %g", (unsigned long long)r, a[13]);
+            if (!index_ok(a[17], 0.0, 4.0)) return fail(-1, "record %llu: unknown mode %g", (unsigned long long)r, a[17]);
+            if ((uint32_t)a[17] & DRT_MAT_MODE_SIMPLE)
+            {
+                bool fresnel = a[13] >= 0.0 ? bdsf_fresnel_kind((uint32_t)a[13]) != 0 : false;
+                for (uint32_t j = 0; a[13] < 0.0 && j < sm.num_bdsfs; j += 1) fresnel = fresnel || bdsf_fresnel_kind(sm.bdsfs[j]) != 0;
+                if (fresnel) return fail(-1, "record %llu: the SIMPLE instantiation has no Fresnel functions", (unsigned long long)r);
+            }
+        }
+        else
+        {
+            if (!index_ok(a[13], -1.0, (double)DRT_NUM_DIRFS)) return fail(-1, "record %llu: unknown dir_func id %g", (unsigned long long)r, a[13]);
+            if (a[13] < 0.0 && sm.dir_func >= (uint32_t)DRT_NUM_DIRFS)
+                return fail(-1, "record %llu: material %u has no direction sampler (dir_func %u)", (unsigned long long)r, (uint32_t)a[10], sm.dir_func);
+        }
+    }
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = material_variants(ctx);
+    if (rc) return rc;
+    double *din = nullptr, *dout = nullptr;
+    HIP_TRY(hipMalloc((void **)&din, n * in_stride * 8));
+    HIP_TRY(hipMalloc((void **)&dout, n * out_stride * 8));
+    HIP_TRY(hipMemcpy(din, in, n * in_stride * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dout, 0, n * out_stride * 8));
+    hipLaunchKernelGGL(drt_material_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ctx->dsc, ctx->d_mat_variants, func, din, in_stride,
+                       dout, out_stride, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, n * out_stride * 8, hipMemcpyDeviceToHost));

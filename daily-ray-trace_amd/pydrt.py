@@ -332,6 +332,8 @@ def hip_lib():
         L.drt_bvh_stats.argtypes = [C.POINTER(Scene)] + [C.POINTER(C.c_uint32)] * 4
         L.drt_selftest_unit.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                         C.c_uint64]
+        L.drt_selftest_material.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                            C.c_uint64]
         _hip = L
     return _hip
 
@@ -339,7 +341,7 @@ def hip_lib():
 HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy", "drt_bind_film", "drt_set_stream",
                "drt_render", "drt_synchronize", "drt_reset_film", "drt_film_device_ptrs", "drt_read_film", "drt_write_film",
                "drt_read_xyz", "drt_read_bgra", "drt_read_hit_indices", "drt_get_stats", "drt_batch_spp", "drt_render_tile", "drt_selftest_arith",
-               "drt_selftest_unit", "drt_bvh_stats",
+               "drt_selftest_unit", "drt_selftest_material", "drt_bvh_stats",
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi"]
 
@@ -517,6 +519,22 @@ def selftest_arith(op, a, b=None, device=0):
 _UNIT_OUT = {UNIT_LINE_SPHERE: 1, UNIT_LINE_PLANE: 1, UNIT_REFLECT: 3, UNIT_TRANSMIT: 3, UNIT_ROTATION_BETWEEN: 9,
              UNIT_SAMPLE_SPHERE: 4, UNIT_SAMPLE_DISC: 4, UNIT_GGX: 1, UNIT_GGX_ATT: 1, UNIT_FS_DIELECTRIC: 1, UNIT_FS_CONDUCTOR: 1,
              UNIT_SEED_AND_DRAW: 2, UNIT_BVH_BOX: 1}
+
+
+MAT_EVALUATE, MAT_SAMPLE = 0, 1
+MAT_MODE_UNPAIRED, MAT_MODE_SIMPLE = 1, 2
+
+
+def selftest_material(renderer, func, records):
+    """The material layer of `renderer`'s device scene over `records` ([n][k] doubles, layouts in include/drt_hip.h; u64 arguments as
+    their bit patterns): MAT_EVALUATE returns [n][S + 1] (reflectance, flags word), MAT_SAMPLE [n][6] (dir, 1/pdf, state bits, draws)."""
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    n, k = rec.shape
+    m = renderer.S + 1 if func == MAT_EVALUATE else 6
+    out = np.zeros((n, m), dtype=np.float64)
+    _check(hip_lib().drt_selftest_material(renderer.ctx, func, _ptr(rec, C.c_double), k, _ptr(out, C.c_double), m, n),
+           "drt_selftest_material")
+    return out
 
 
 def bvh_stats(bundle):

@@ -318,6 +318,27 @@ int drt_selftest_arith(int device, int op, const double *a, const double *b, dou
  *                                                          in o[3] d[3] lo[3] hi[3]            out lower bound of the entry distance, < 0: rejected */
 int drt_selftest_unit(int device, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
 
+/* Material-layer self-test: runs n records (`in_stride` doubles in, `out_stride` doubles out per record) against the device scene of
+ * ctx -- its materials, pair rows, diffuse * (1/PI) rows and refractive indices at trans_wl are the ones drt_create built -- through
+ * the very __device__ functions the trace and shade kernels call, in their order. A record is a surface point:
+ *     position[3] normal[3] out[3] on_dot  surface incident transmit          (13 doubles; material indices as whole numbers)
+ * followed by, per func:
+ *   0 evaluate: bdsf(), src/daily_ray_trace.c:215-229 with src/bdsf.c:105-186 -- eval_coefficients, record_media_word and fresnel_rows
+ *     as the trace kernel writes a vertex, then bdsf_at_wavelength per wavelength on the table rows the shade kernel reads.
+ *       in  +  bdsf  incoming[3]  mode                                         (18 doubles)
+ *          bdsf: -1 the surface material's own list, or one DRT_BDSF_* id that replaces it (needs derived from that list; the pair
+ *                rows are used only when the function is of the Fresnel kind they were tabulated for, else the record is unpaired)
+ *          mode: bit 0 unpaired (PAIR_NONE: every Fresnel term from ir, tr, te), bit 1 the SIMPLE instantiation (no Fresnel cases)
+ *       out reflectance[S], the EvalCoef flags word (bit 0 in == mirror direction, bit 1 in == refracted direction)   (S + 1)
+ *   1 sample: sample_direction, src/bdsf.c:188-292
+ *       in  +  dir_func  rng state (u64 bits)                                   (15 doubles)
+ *          dir_func: -1 the surface material's own sampler, or a DRT_DIRF_* id
+ *       out dir[3] recip_pdf, rng state after (u64 bits), rng draws taken      (6)
+ * Returns nonzero (drt_last_error) and runs nothing when a record is narrower than its function needs, out_stride is too small, a
+ * material index is not below num_materials, a bdsf / dir_func id is unknown (or the material's own dir_func is), or SIMPLE is asked of a
+ * list that holds a Fresnel function. Synchronises. */
+int drt_selftest_material(drt_context *ctx, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
+
 #ifdef __cplusplus
 }
 #endif
