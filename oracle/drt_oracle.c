@@ -461,12 +461,118 @@ static void bp_diffuse_bdsf(const drt_scene *sc, double *out, const point *p, v3
     for (uint32_t i = 0; i < S; i += 1) out[i] = out[i] * a;
 }
 
+/* ---- the glossy lobe's power in DEVICE mode: glibc's, glibc's with every (x, y) recorded, or a caller's table ------------ */
+/* Used by drt_oracle_render_tile() only; every other entry point (and REFERENCE mode) calls glibc's pow. Entries are keyed on
+ * the bit patterns of x and y (x may be -0: f64_max keeps it). Each render thread logs into its own pow_log; the table is
+ * read-only while a render runs. */
+typedef struct { uint64_t x, y; double v; } pow_entry;
+typedef struct { pow_entry *e; uint64_t n, cap, misses; } pow_log;
+
+static int g_pow_mode = DRT_ORACLE_POW_LIBM;
+static pow_entry *g_pow_table = NULL;   /* sorted by (x, y), unique keys */
+static uint64_t g_pow_table_n = 0;
+static pow_entry *g_pow_pairs = NULL;   /* what the last collecting render recorded: sorted, unique */
+static uint64_t g_pow_pairs_n = 0;
+static uint64_t g_pow_misses = 0;
+static __thread pow_log *t_pow = NULL;  /* set while render_rows runs */
+
+static uint64_t f64_bits(double d) { uint64_t u; memcpy(&u, &d, 8); return u; }
+static double bits_f64(uint64_t u) { double d; memcpy(&d, &u, 8); return d; }
+static int pow_key_cmp(const void *a, const void *b)
+{
+    const pow_entry *p = (const pow_entry *)a, *q = (const pow_entry *)b;
+    if (p->x != q->x) return p->x < q->x ? -1 : 1;
+    return (p->y > q->y) - (p->y < q->y);
+}
+/* sort + drop repeated keys; returns the new count */
+static uint64_t pow_sort_unique(pow_entry *e, uint64_t n)
+{
+    if (n < 2) return n;
+    qsort(e, (size_t)n, sizeof(pow_entry), pow_key_cmp);
+    uint64_t k = 1;
+    for (uint64_t i = 1; i < n; i += 1)
+        if (e[i].x != e[k - 1].x || e[i].y != e[k - 1].y) e[k++] = e[i];
+    return k;
+}
+static int pow_log_add(pow_log *l, double x, double y)
+{
+    if (l->n == l->cap)
+    {
+        l->n = pow_sort_unique(l->e, l->n);
+        if (l->cap == 0 || l->n * 2 > l->cap) /* less than half of it repeats: grow */
+        {
+            uint64_t cap = l->cap ? 2 * l->cap : 4096;
+            pow_entry *e = (pow_entry *)realloc(l->e, (size_t)cap * sizeof(pow_entry));
+            if (!e) return -1;
+            l->e = e;
+            l->cap = cap;
+        }
+    }
+    l->e[l->n].x = f64_bits(x);
+    l->e[l->n].y = f64_bits(y);
+    l->e[l->n].v = 0.0;
+    l->n += 1;
+    return 0;
+}
+static double glossy_pow(double x, double y)
+{
+    if (REFMODE || !t_pow || g_pow_mode == DRT_ORACLE_POW_LIBM) return pow(x, y);
+    if (g_pow_mode == DRT_ORACLE_POW_COLLECT)
+    {
+        if (pow_log_add(t_pow, x, y) != 0) t_pow->misses += 1; /* out of memory: the render reports it */
+        return pow(x, y);
+    }
+    pow_entry key = {f64_bits(x), f64_bits(y), 0.0};
+    const pow_entry *hit = g_pow_table_n ? (const pow_entry *)bsearch(&key, g_pow_table, (size_t)g_pow_table_n, sizeof(pow_entry), pow_key_cmp) : NULL;
+    if (hit) return hit->v;
+    t_pow->misses += 1; /* never glibc's value in its place: the render returns an error */
+    return NAN;
+}
+
+void drt_oracle_set_pow_mode(int mode) { g_pow_mode = mode; }
+int drt_oracle_get_pow_mode(void) { return g_pow_mode; }
+
+int drt_oracle_set_pow_table(const double *x, const double *y, const double *v, uint64_t n)
+{
+    pow_entry *e = n ? (pow_entry *)malloc((size_t)n * sizeof(pow_entry)) : NULL;
+    if (n && !e) return -1;
+    for (uint64_t i = 0; i < n; i += 1)
+    {
+        e[i].x = f64_bits(x[i]);
+        e[i].y = f64_bits(y[i]);
+        e[i].v = v[i];
+    }
+    if (n > 1) qsort(e, (size_t)n, sizeof(pow_entry), pow_key_cmp);
+    for (uint64_t i = 1; i < n; i += 1)
+        if (e[i].x == e[i - 1].x && e[i].y == e[i - 1].y)
+        {
+            free(e);
+            return -2; /* a key given twice */
+        }
+    free(g_pow_table);
+    g_pow_table = e;
+    g_pow_table_n = n;
+    return 0;
+}
+
+uint64_t drt_oracle_pow_pairs(double *x, double *y, uint64_t cap)
+{
+    for (uint64_t i = 0; i < g_pow_pairs_n && i < cap; i += 1)
+    {
+        x[i] = bits_f64(g_pow_pairs[i].x);
+        y[i] = bits_f64(g_pow_pairs[i].y);
+    }
+    return g_pow_pairs_n;
+}
+
+uint64_t drt_oracle_pow_misses(void) { return g_pow_misses; }
+
 static void bp_glossy_bdsf(const drt_scene *sc, double *out, const point *p, v3 in) /* :111-119 */
 {
     uint32_t S = sc->num_wavelengths;
     v3 bisector = v_normalise(v_sum(p->out, in));
     double nb = v_dot(p->normal, bisector);
-    double spec = pow((0.0 > nb) ? 0.0 : nb, p->surface_material->shininess); /* f64_max, src/utils.c:13-16 */
+    double spec = glossy_pow((0.0 > nb) ? 0.0 : nb, p->surface_material->shininess); /* f64_max, src/utils.c:13-16 */
     const double *g = spd_of(sc, p->surface_material->glossy_spd);
     for (uint32_t i = 0; i < S; i += 1) out[i] = g[i] * spec;
     double a = fabs(v_dot(p->normal, in));
@@ -912,6 +1018,7 @@ typedef struct
     int32_t *hits;
     uint32_t row_begin, row_end;
     drt_stats stats;
+    pow_log pow;
 } tile_job;
 
 static void *render_rows(void *arg)
@@ -922,6 +1029,7 @@ static void *render_rows(void *arg)
     double contribution[MAX_S + 1];
     double tmp0[MAX_S], tmp1[MAX_S];
     t_rng_draws = t_closest_scans = t_shadow_scans = t_shaded = 0;
+    t_pow = &job->pow;
     uint64_t paths = 0;
     uint32_t stride = p->row_stride ? p->row_stride : 1;
     for (uint32_t s = 0; s < p->spp; s += 1)
@@ -963,6 +1071,8 @@ static void *render_rows(void *arg)
     job->stats.shaded_vertices = t_shaded;
     job->stats.shadow_scans = t_shadow_scans;
     job->stats.rng_draws = t_rng_draws;
+    job->pow.n = pow_sort_unique(job->pow.e, job->pow.n);
+    t_pow = NULL;
     return NULL;
 }
 
@@ -989,6 +1099,31 @@ int drt_oracle_render_tile(const drt_scene *sc, const drt_camera *cam, const drt
         for (int t = 0; t < num_threads; t += 1) pthread_create(&threads[t], NULL, render_rows, &jobs[t]);
         for (int t = 0; t < num_threads; t += 1) pthread_join(threads[t], NULL);
     }
+    /* the power's log: the threads' pairs merged (sorted, unique); misses of the table or of memory fail the call */
+    uint64_t misses = 0, n_pairs = 0;
+    for (int t = 0; t < num_threads; t += 1)
+    {
+        misses += jobs[t].pow.misses;
+        n_pairs += jobs[t].pow.n;
+    }
+    g_pow_misses = misses;
+    if (g_pow_mode == DRT_ORACLE_POW_COLLECT) /* REFERENCE mode records nothing */
+    {
+        free(g_pow_pairs);
+        g_pow_pairs = n_pairs ? (pow_entry *)malloc((size_t)n_pairs * sizeof(pow_entry)) : NULL;
+        g_pow_pairs_n = 0;
+        if (n_pairs && !g_pow_pairs) misses += 1;
+        else
+        {
+            for (int t = 0; t < num_threads; t += 1)
+            {
+                if (jobs[t].pow.n) memcpy(g_pow_pairs + g_pow_pairs_n, jobs[t].pow.e, (size_t)jobs[t].pow.n * sizeof(pow_entry));
+                g_pow_pairs_n += jobs[t].pow.n;
+            }
+            g_pow_pairs_n = pow_sort_unique(g_pow_pairs, g_pow_pairs_n);
+        }
+    }
+    for (int t = 0; t < num_threads; t += 1) free(jobs[t].pow.e);
     if (stats)
     {
         memset(stats, 0, sizeof(*stats));
@@ -1003,7 +1138,7 @@ int drt_oracle_render_tile(const drt_scene *sc, const drt_camera *cam, const drt
     }
     free(threads);
     free(jobs);
-    return 0;
+    return misses ? -3 : 0;
 }
 
 /* spectrum_to_xyz, src/spectrum.c:49-70 */

@@ -28,7 +28,8 @@ extern "C" {
  *      sin/cos/pow come from libm. This is the mode checked against oracle/_ref (bit-exact).
  *  DRT_ORACLE_MATH_DEVICE: the same expressions in IEEE f64 only, with the path's own
  *      range-reduced sincos (spec below). This is the arithmetic the HIP kernels use, so
- *      hit indices and XYZ can be compared bit-for-bit with the GPU (pow excepted: libm vs ocml).
+ *      hit indices, films and XYZ can be compared bit-for-bit with the GPU once the glossy lobe's pow (libm vs the device's)
+ *      is taken from the device through DRT_ORACLE_POW_TABLE below.
  */
 enum
 {
@@ -38,13 +39,39 @@ enum
 void drt_oracle_set_math_mode(int mode);
 int  drt_oracle_get_math_mode(void);
 
+/*
+ * The glossy lobe's power, pow(max(0, n.b), shininess) in bp_glossy_bdsf -- the one call of pow() on the path. In DEVICE mode
+ * drt_oracle_render_tile() can take it from elsewhere than glibc, so that a film can be held to the device's bit for bit:
+ *  DRT_ORACLE_POW_LIBM:    glibc's pow (the default).
+ *  DRT_ORACLE_POW_COLLECT: glibc's pow, and every (x, y) it is called with is recorded; drt_oracle_pow_pairs() gives the
+ *                          pairs of the last such render, unique and sorted by the bit patterns of (x, y).
+ *  DRT_ORACLE_POW_TABLE:   the value is looked up, by the bit patterns of x and y, in the table of drt_oracle_set_pow_table().
+ *                          A pair that is not there is a miss: the value is NaN and drt_oracle_render_tile() returns -3.
+ * REFERENCE mode and every other entry point ignore the mode. Not to be changed while a render runs.
+ */
+enum
+{
+    DRT_ORACLE_POW_LIBM    = 0,
+    DRT_ORACLE_POW_COLLECT = 1,
+    DRT_ORACLE_POW_TABLE   = 2
+};
+void drt_oracle_set_pow_mode(int mode);
+int  drt_oracle_get_pow_mode(void);
+/* Copies the table ((x[i], y[i]) -> v[i]); 0 ok, -1 out of memory, -2 a key given twice. */
+int  drt_oracle_set_pow_table(const double *x, const double *y, const double *v, uint64_t n);
+/* Copies up to cap pairs into x / y; returns how many there are. */
+uint64_t drt_oracle_pow_pairs(double *x, double *y, uint64_t cap);
+/* Table misses (or, collecting, failed allocations) of the last drt_oracle_render_tile(). */
+uint64_t drt_oracle_pow_misses(void);
+
 /* ---- whole path ---------------------------------------------------------------------------- */
 
 /* CPU twin of drt_render_tile(): same arguments, same accumulate-into semantics
  * (src/daily_ray_trace.c:710-745). hit_indices (optional): [spp*tile_h*tile_w][max_depth] int32,
  * closest-hit surface index per find_ray_intersection call (-1 miss, -2 not reached), ordered
  * (sample, tile row, tile column). num_threads<=1: single thread (the reference's configuration);
- * >1: rows split across that many pthreads (per-path RNG makes the result identical). */
+ * >1: rows split across that many pthreads (per-path RNG makes the result identical).
+ * Returns 0, or -1 / -2 for bad arguments, -3 when the power's table missed (see DRT_ORACLE_POW_TABLE). */
 int drt_oracle_render_tile(const drt_scene *scene, const drt_camera *camera, const drt_params *params,
                            double *dst_pixels, double *dst_avgs, double *dst_vars,
                            int32_t *hit_indices, drt_stats *stats, int num_threads);

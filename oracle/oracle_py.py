@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(REPO, "daily-ray-trace_amd"))
 import pydrt  # noqa: E402  (struct definitions of the boundary only)
 
 MATH_REFERENCE, MATH_DEVICE = 0, 1
+POW_LIBM, POW_COLLECT, POW_TABLE = 0, 1, 2  # the glossy lobe's power in DEVICE mode (drt_oracle.h)
 f64p = C.POINTER(C.c_double)
 i32p = C.POINTER(C.c_int32)
 
@@ -55,6 +56,11 @@ def oracle_lib():
         S, Cm, P = C.POINTER(pydrt.Scene), C.POINTER(pydrt.Camera), C.POINTER(pydrt.Params)
         L.drt_oracle_render_tile.argtypes = [S, Cm, P, f64p, f64p, f64p, i32p, C.POINTER(pydrt.Stats), C.c_int]
         L.drt_oracle_sample_scene.argtypes = [S, Cm, P, C.c_uint32, C.c_uint32, C.c_uint32, f64p, f64p, i32p]
+        L.drt_oracle_set_pow_mode.argtypes = [C.c_int]
+        L.drt_oracle_set_pow_table.argtypes = [f64p, f64p, f64p, C.c_uint64]
+        L.drt_oracle_pow_pairs.restype = C.c_uint64
+        L.drt_oracle_pow_pairs.argtypes = [f64p, f64p, C.c_uint64]
+        L.drt_oracle_pow_misses.restype = C.c_uint64
         L.drt_oracle_spectrum_to_xyz.argtypes = [S, f64p, f64p]
         L.drt_oracle_film_to_xyz.argtypes = [S, f64p, C.c_uint64, f64p]
         L.drt_oracle_line_sphere.restype = C.c_double
@@ -96,23 +102,59 @@ def set_math_mode(mode):
     oracle_lib().drt_oracle_set_math_mode(mode)
 
 
-def oracle_render_tile(bundle, params, want_hits=False, num_threads=1, math_mode=None):
-    """CPU twin of drt_render_tile. Returns (pixels, avgs, vars, hits|None, Stats)."""
+class PowTableMiss(RuntimeError):
+    """drt_oracle_render_tile met a (x, y) that its power table does not hold (-3)."""
+
+
+def oracle_render_tile(bundle, params, want_hits=False, num_threads=1, math_mode=None, film=None, pow_collect=False, pow_table=None):
+    """CPU twin of drt_render_tile. Returns (pixels, avgs, vars, hits|None, Stats).
+    film: (pixels, avgs, vars) to accumulate into (copied; default zeros). pow_collect: record the glossy lobe's (x, y) pairs
+    (oracle_pow_pairs() gives them afterwards). pow_table: (xs, ys, values) to take the power from instead of glibc; a pair it
+    does not hold raises PowTableMiss. Both apply in DEVICE mode only and are switched off again on return."""
     L = oracle_lib()
     if math_mode is not None:
         set_math_mode(math_mode)
     n = int(params.tile_w) * int(params.tile_h)
     S = bundle.S
-    px = np.zeros((n, S + 1))
-    av = np.zeros((n, S))
-    va = np.zeros((n, S))
+    if film is None:
+        px, av, va = np.zeros((n, S + 1)), np.zeros((n, S)), np.zeros((n, S))
+    else:
+        px, av, va = (np.array(a, dtype=np.float64, order="C", copy=True) for a in film)
+        assert px.shape == (n, S + 1) and av.shape == (n, S) and va.shape == (n, S)
     hits = np.full((n * int(params.spp), int(params.max_depth)), -2, dtype=np.int32) if want_hits else None
     st = pydrt.Stats()
-    rc = L.drt_oracle_render_tile(C.byref(bundle.scene), C.byref(bundle.camera), C.byref(params), _ptr(px), _ptr(av),
-                                  _ptr(va), _ptr(hits, C.c_int32), C.byref(st), num_threads)
+    assert not (pow_collect and pow_table is not None)
+    if pow_table is not None:
+        xs, ys, vs = (np.ascontiguousarray(a, dtype=np.float64) for a in pow_table)
+        assert xs.shape == ys.shape == vs.shape
+        rc = L.drt_oracle_set_pow_table(_ptr(xs), _ptr(ys), _ptr(vs), xs.size)
+        if rc != 0:
+            raise RuntimeError("drt_oracle_set_pow_table failed: %d" % rc)
+        L.drt_oracle_set_pow_mode(POW_TABLE)
+    elif pow_collect:
+        L.drt_oracle_set_pow_mode(POW_COLLECT)
+    try:
+        rc = L.drt_oracle_render_tile(C.byref(bundle.scene), C.byref(bundle.camera), C.byref(params), _ptr(px), _ptr(av),
+                                      _ptr(va), _ptr(hits, C.c_int32), C.byref(st), num_threads)
+    finally:
+        L.drt_oracle_set_pow_mode(POW_LIBM)
+        if pow_table is not None:
+            L.drt_oracle_set_pow_table(None, None, None, 0)
+    if rc == -3:
+        raise PowTableMiss("drt_oracle_render_tile: %d lookups of the power's table missed" % L.drt_oracle_pow_misses())
     if rc != 0:
         raise RuntimeError("drt_oracle_render_tile failed: %d" % rc)
     return px, av, va, hits, st
+
+
+def oracle_pow_pairs():
+    """The unique (x, y) pairs the last collecting render passed to the glossy lobe's pow, sorted by their bit patterns."""
+    L = oracle_lib()
+    n = int(L.drt_oracle_pow_pairs(None, None, 0))
+    xs, ys = np.empty(n), np.empty(n)
+    if n:
+        L.drt_oracle_pow_pairs(_ptr(xs), _ptr(ys), n)
+    return xs, ys
 
 
 def oracle_film_to_xyz(bundle, pixels):

@@ -58,6 +58,46 @@ def load_case(name):
     return bundle, params
 
 
+def same_bits(a, b):
+    """equal, NaN for NaN (whatever its sign and payload: x86's and gfx950's default NaNs differ), and zeros of the same sign"""
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and np.array_equal(a, b, equal_nan=True) and \
+        np.array_equal(np.signbit(a) & ~np.isnan(a), np.signbit(b) & ~np.isnan(b))
+
+
+def first_difference(a, b):
+    """where and what the first element that is not same_bits is, for an assertion message"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape:
+        return "shapes %s and %s" % (a.shape, b.shape)
+    bad = ~((a == b) & (np.signbit(a) == np.signbit(b)) | (np.isnan(a) & np.isnan(b)))
+    idx = np.argwhere(bad)
+    if not len(idx):
+        return "none"
+    i = tuple(idx[0])
+    return "%d elements differ, first at %s: %r against %r" % (len(idx), i, float(a[i]), float(b[i]))
+
+
+def oracle_render_device_pow(bundle, params, want_hits=False, num_threads=1, film=None):
+    """The oracle's render in DEVICE arithmetic with the glossy lobe's power taken from the device (drt_pow_shininess through
+    drt_selftest_arith op 7) instead of glibc: what the HIP film must equal bit for bit. Pass 1 collects the (x, y) pairs of the
+    power with glibc's value, pass 2 renders again with the device's values of those pairs looked up; a pair it lacks is an error.
+    The power never steers a path, so both passes have the same hit log and statistics. Same return as oracle_render_tile."""
+    import oracle_py as O
+    kw = dict(want_hits=True, num_threads=num_threads, math_mode=O.MATH_DEVICE, film=film)
+    _, _, _, hits1, st1 = O.oracle_render_tile(bundle, params, pow_collect=True, **kw)
+    xs, ys = O.oracle_pow_pairs()
+    vals = pydrt.selftest_arith(7, xs, ys) if xs.size else np.zeros(0)
+    px, av, va, hits, st = O.oracle_render_tile(bundle, params, pow_table=(xs, ys, vals), **kw)
+    assert np.array_equal(hits1, hits), "the power changed a path's hit log"
+    assert stat_counts(st1) == stat_counts(st), "the power changed the path statistics"
+    return px, av, va, hits if want_hits else None, st
+
+
+def stat_counts(st):
+    return (st.paths, st.closest_hit_scans, st.shaded_vertices, st.shadow_scans, st.rng_draws)
+
+
 def rel_err(a, b):
     """max |a-b| / max|b| -- the scale-relative error used for film buffers."""
     scale = float(np.max(np.abs(b)))

@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 import cases
+from cases import same_bits
 import oracle_py as O
 import pydrt
 
@@ -242,11 +243,6 @@ def ulps(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     d = np.abs(a.view(np.int64) - b.view(np.int64))
     return np.where(np.isnan(a) & np.isnan(b), 0, d)
-
-
-def same_bits(a, b):
-    """equal, NaN for NaN (whatever its sign and payload), and zeros of the same sign"""
-    return np.array_equal(a, b, equal_nan=True) and np.array_equal(np.signbit(a) & ~np.isnan(a), np.signbit(b) & ~np.isnan(b))
 
 
 def oracle_evaluate(bundle, recs, dev_pow=True):
