@@ -568,7 +568,7 @@ __global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_b
             {
                 /* incoming = normalise(light_position - position), :320: the very expression (same operands, same operations) that gave
                  * the shadow ray its direction, :241 -- so it is jd, bit for bit, and the light's position need not stay live */
-                EvalCoef e = eval_coefficients(sc, sv, ip, jd);
+                EvalCoef e = eval_coefficients_by_material(sc, sv, ip, jd);
                 lflags = e.flags | FLAG_VISIBLE;
                 if (l == 0 && shaded < 8u) masks |= 0x10000u << shaded;
                 lrec[1] = (uint64_t)__double_as_longlong(light_c);
@@ -590,8 +590,8 @@ __global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_b
             uint64_t *vrec = records + (uint64_t)blk * tp.block_words + (uint64_t)(shaded & (REC_BLOCK_VERTICES - 1u)) * tp.vertex_words;
             V3 in;
             double dir_pdf;
-            sample_direction(sc, sv, ip, rs, n_draws, in, dir_pdf);
-            EvalCoef e = eval_coefficients(sc, sv, ip, in);
+            sample_direction_by_material(sc, sv, ip, rs, n_draws, in, dir_pdf);
+            EvalCoef e = eval_coefficients_by_material(sc, sv, ip, in);
             vrec[0] = mat.bdsf_packed;
             vrec[1] = (uint64_t)mat.num_bdsfs | ((uint64_t)(e.flags | mat.vertex_flags) << 8) | ((uint64_t)((uint32_t)mat.diffuse_spd & 0xFFFFu) << 16) |
                       ((uint64_t)((uint32_t)mat.glossy_spd & 0xFFFFu) << 32) | ((uint64_t)((uint32_t)mat.mirror_spd & 0xFFFFu) << 48);

@@ -505,9 +505,201 @@ __device__ __forceinline__ void fresnel_rows(uint64_t w2, uint32_t &i0, uint32_t
     i2 = (paired && !conductor) ? row : i_te;
 }
 
+/* What every evaluation and the sampler of one vertex share, whatever the direction (computed once per vertex, for the lanes whose
+ * material uses it): the mirror direction vec3_reflect(-out, n) (the EQR test, sample_specular_direction and the reflecting half of
+ * sample_reflect_or_transmit_direction, src/bdsf.c:123-151, :215-259) and the refracted direction vec3_transmit(-out, n, ir, tr) at
+ * trans_wl (the EQT test, sample_transmit_direction and the transmitting half, :163-168, :222-259). The same functions on the same
+ * operands as where they are used, so the same bits; the exact-equality flags then compare against the very register the sampler
+ * returned. */
+struct VertexDirs
+{
+    V3 refl, trans;
+};
+
+__device__ __forceinline__ bool dirs_need_refl(const DevMaterial &m)
+{
+    return (m.needs & NEED_EQR) || m.dir_func == DRT_DIRF_sample_specular_direction || m.dir_func == DRT_DIRF_sample_reflect_or_transmit_direction;
+}
+__device__ __forceinline__ bool dirs_need_trans(const DevMaterial &m)
+{
+    return (m.needs & NEED_EQT) || m.dir_func == DRT_DIRF_sample_transmit_direction || m.dir_func == DRT_DIRF_sample_reflect_or_transmit_direction;
+}
+
+__device__ __forceinline__ VertexDirs vertex_dirs(const DevScene &sc, const SceneView &sv, const HitPoint &ip)
+{
+    const DevMaterial &mat = sv.mats[ip.surface_mat];
+    VertexDirs vd;
+    vd.refl = v3(0.0, 0.0, 0.0);
+    vd.trans = v3(0.0, 0.0, 0.0);
+    const V3 w = v_reverse(ip.out);
+    if (dirs_need_refl(mat)) vd.refl = v_reflect(w, ip.normal);
+    if (dirs_need_trans(mat))
+    {
+        double ir = refract_at_trans_wl(sc, sv.mats[ip.incident_mat]);
+        double tr = refract_at_trans_wl(sc, sv.mats[ip.transmit_mat]);
+        vd.trans = v_transmit(w, ip.normal, ir, tr);
+    }
+    return vd;
+}
+
 /* The per-direction scalars of every BDSF in the material's list (src/bdsf.c:105-186):
- * what remains of bdsf(p, in) once the per-wavelength work is taken out. */
-__device__ __forceinline__ EvalCoef eval_coefficients(const DevScene &sc, const SceneView &sv, const HitPoint &ip, V3 in)
+ * what remains of bdsf(p, in) once the per-wavelength work is taken out. bp_glossy_bdsf's bisector and ct_conductor_bdsf's
+ * micro-normal are one expression, normalise(out + in), computed once for the lanes of either. */
+__device__ __forceinline__ EvalCoef eval_coefficients(const SceneView &sv, const HitPoint &ip, const VertexDirs &vd, V3 in)
+{
+    const DevMaterial &mat = sv.mats[ip.surface_mat];
+    EvalCoef e;
+    e.a_in = __builtin_fabs(v_dot(ip.normal, in)); /* bp_diffuse :108, bp_glossy :118 */
+    e.spec = 0.0;
+    e.mn_dot = 0.0;
+    e.ct_coef = 0.0;
+    e.flags = 0;
+    uint32_t needs = mat.needs;
+    V3 half = v3(0.0, 0.0, 0.0);
+    double n_half = 0.0;
+    if (needs & (NEED_GLOSSY | NEED_CT)) /* :113-114, :176-177 */
+    {
+        half = v_normalise(v_sum(ip.out, in));
+        n_half = v_dot(ip.normal, half);
+    }
+    if (needs & NEED_GLOSSY) e.spec = drt_pow_shininess((0.0 > n_half) ? 0.0 : n_half, mat.shininess); /* :115 */
+    if ((needs & NEED_EQR) && v_equal(in, vd.refl)) e.flags |= FLAG_EQR; /* :123-124, :136-137, :150-151 */
+    if ((needs & NEED_EQT) && v_equal(in, vd.trans)) e.flags |= FLAG_EQT; /* :163-168 */
+    if (needs & NEED_CT) /* :178-184 */
+    {
+        e.mn_dot = __builtin_fabs(n_half);
+        e.ct_coef = ggx_att(ip.out, ip.normal, half, mat.roughness) * (1.0 / (4.0 * ip.on_dot));
+    }
+    return e;
+}
+
+/* Direction samplers, src/bdsf.c:188-292; they return the reciprocal pdf.
+ * Written as phases that all lanes of a wave run together, whatever their materials, so that a wave whose lanes sample with
+ * different functions issues the costly steps once instead of once per function: the two draws, the one division and the sincos of
+ * cos_weighted_sample_hemisphere's disc, uniform_sample_hemisphere's sphere and sample_ct_direction's micro-normal, the rotation
+ * onto the normal and its product, and the final division of the disc, GGX and reflect-or-transmit samplers. Each lane picks its
+ * operands by select, so every lane still performs its own sampler's operations, in its order, on its operands. The disc's and the
+ * GGX sampler's rejection loops are one loop in which a lane repeats its own body until it accepts; the disc's z and the rotation of
+ * a rejected point are computed and dropped (the rotation matrix depends on the normal alone and is built once, before the loop). */
+__device__ __forceinline__ void sample_direction(const DevScene &sc, const SceneView &sv, const HitPoint &ip, const VertexDirs &vd, uint64_t &rs,
+                                                 uint32_t &draws, V3 &dir, double &recip_pdf)
+{
+    const DevMaterial &mat = sv.mats[ip.surface_mat];
+    const uint32_t df = mat.dir_func;
+    const bool disc = df == DRT_DIRF_cos_weighted_sample_hemisphere;  /* :200-213 */
+    const bool sphere = df == DRT_DIRF_uniform_sample_hemisphere;     /* :191-198 */
+    const bool ggx_mn = df == DRT_DIRF_sample_ct_direction;           /* :261-292 */
+    const bool coin = df == DRT_DIRF_sample_reflect_or_transmit_direction; /* :236-259 */
+    dir = v3(0.0, 0.0, 0.0);
+    recip_pdf = 0.0;
+    if (df == DRT_DIRF_sample_specular_direction) /* :215-220 */
+    {
+        dir = vd.refl;
+        recip_pdf = 1.0;
+    }
+    if (df == DRT_DIRF_sample_transmit_direction) /* :222-234 */
+    {
+        dir = vd.trans;
+        recip_pdf = 1.0;
+    }
+    double num = 0.0, den = 1.0; /* recip_pdf = num / den for the disc, GGX and reflect-or-transmit samplers */
+    if (coin)
+    {
+        const DevMaterial &im = sv.mats[ip.incident_mat];
+        const DevMaterial &tm = sv.mats[ip.transmit_mat];
+        /* value_at_wl(reflectance spectrum, 630) needs the Fresnel term at the two bracketing samples */
+        double inc_sin_sq = 1.0 - ip.on_dot * ip.on_dot;
+        double r0 = dielectric_reflectance(im.refract_i0, tm.refract_i0, ip.on_dot, inc_sin_sq);
+        double r1 = dielectric_reflectance(im.refract_i1, tm.refract_i1, ip.on_dot, inc_sin_sq);
+        double rd = drt_lerp(sc.trans_wl, sc.trans_w0, sc.trans_w1, r0, r1);
+        double f = drt_rng(rs, draws);
+        const bool reflect = f < rd;
+        dir = reflect ? vd.refl : vd.trans;
+        num = 1.0;
+        den = reflect ? rd : 1.0 - rd;
+    }
+    if (disc || sphere || ggx_mn)
+    {
+        const M33 r = rotation_between(v3(0.0, 0.0, 1.0), ip.normal);
+        const double rough = mat.roughness;
+        bool accepted;
+        double o_mn_dot = 0.0, d = 1.0;
+        do
+        {
+            /* draws: the disc's r_x, r_y (uniform_sample_disc, src/rng.c:25-51); the sphere's u, v (uniform_sample_sphere,
+             * src/rng.c:14-23); the GGX sampler's f, g */
+            const double u = drt_rng(rs, draws);
+            const double v = drt_rng(rs, draws);
+            /* the argument of the sincos and the one division before it */
+            const double o_x = 2.0 * u - 1.0;
+            const double o_y = 2.0 * v - 1.0;
+            const bool x_major = __builtin_fabs(o_x) > __builtin_fabs(o_y);
+            const double sqrt_u = __builtin_sqrt(sphere ? 1.0 - u * u : u);
+            const double q_num = ggx_mn ? rough * sqrt_u : (x_major ? o_y : o_x);
+            const double q_den = ggx_mn ? __builtin_sqrt(1.0 - u) : (x_major ? o_x : o_y);
+            const double q = q_num / q_den; /* the disc's o_y / o_x or o_x / o_y; the GGX sampler's tan_mn */
+            double t = x_major ? (DRT_PI / 4.0) * q : (DRT_PI / 2.0) - (DRT_PI / 4.0) * q;
+            if (!disc) t = (2.0 * DRT_PI) * v; /* the sphere's t, the GGX sampler's phi_mn */
+            double radius = x_major ? o_x : o_y; /* the disc's r */
+            double z = u;                        /* the sphere's z */
+            if (sphere) radius = sqrt_u;
+            if (ggx_mn)
+            {
+                const double cos_mn = 1.0 / __builtin_sqrt(1.0 + q * q);
+                radius = __builtin_sqrt(1.0 - cos_mn * cos_mn); /* sin_mn */
+                z = cos_mn;
+            }
+            double st, ct;
+            drt_sincos(t, st, ct);
+            V3 p = v3(radius * ct, radius * st, 0.0);
+            if (disc)
+            {
+                if (o_x == 0.0 && o_y == 0.0) p = v3(0.0, 0.0, 0.0);
+                const double qq = v_dot(p, p);
+                accepted = qq < 1.0;
+                z = __builtin_sqrt(1.0 - qq);
+            }
+            p.z = z;
+            V3 w = m_vmul(r, p);
+            dir = w;
+            if (sphere)
+            {
+                recip_pdf = 2.0 * DRT_PI;
+                accepted = true;
+            }
+            if (ggx_mn)
+            {
+                double sn_mn_dot = v_dot(ip.normal, w);
+                if (sn_mn_dot < 0.0)
+                {
+                    w = v_reverse(w);
+                    sn_mn_dot = -sn_mn_dot;
+                }
+                o_mn_dot = v_dot(ip.out, w);
+                dir = v_reflect(v_reverse(ip.out), w);
+                d = ggx(ip.normal, w, rough) * sn_mn_dot;
+                accepted = !(v_dot(dir, ip.normal) < 0.0);
+            }
+        } while (!accepted);
+        if (disc)
+        {
+            num = DRT_PI;
+            den = v_dot(ip.normal, dir);
+        }
+        if (ggx_mn)
+        {
+            num = 4.0 * o_mn_dot;
+            den = d;
+        }
+    }
+    if (disc || ggx_mn || coin) recip_pdf = num / den;
+}
+
+/* The same evaluation and samplers one material branch after the other, each computing what it needs itself. The bounce kernel
+ * (drt_bvh_kernels.h) keeps these: its shading sections sit between tree walks, so per-vertex directions would have to live across
+ * a walk, and with the shared phases above its scratch grows from 320 to 344 B per lane and config 5 loses 0.8 %.
+ * Same operations, same order, same bits as the shared forms. */
+__device__ __forceinline__ EvalCoef eval_coefficients_by_material(const DevScene &sc, const SceneView &sv, const HitPoint &ip, V3 in)
 {
     const DevMaterial &mat = sv.mats[ip.surface_mat];
     EvalCoef e;
@@ -543,7 +735,7 @@ __device__ __forceinline__ EvalCoef eval_coefficients(const DevScene &sc, const 
 }
 
 /* Direction samplers, src/bdsf.c:188-292; they return the reciprocal pdf */
-__device__ __forceinline__ void sample_direction(const DevScene &sc, const SceneView &sv, const HitPoint &ip, uint64_t &rs,
+__device__ __forceinline__ void sample_direction_by_material(const DevScene &sc, const SceneView &sv, const HitPoint &ip, uint64_t &rs,
                                                  uint32_t &draws, V3 &dir, double &recip_pdf)
 {
     const DevMaterial &mat = sv.mats[ip.surface_mat];
@@ -695,6 +887,14 @@ __device__ __forceinline__ void camera_ray(const DevCamera &cam, uint32_t scheme
 
 /* LDS carve-up (8-byte aligned): surfaces, lights, then u32 tables, then materials (see trace_lds_bytes in the launcher) */
 
+#ifdef DRT_BRANCH_STATS
+/* Measurement build only (-DDRT_BRANCH_STATS, never in the product): per wave-iteration that shades, which samplers and evaluator
+ * branches its lanes take. The last wave of a launch to finish prints the launch's totals and clears them. */
+#define DRT_BS_WORDS 16
+__device__ unsigned long long drt_branch_stats[DRT_BS_WORDS];
+__device__ unsigned int drt_branch_waves_done;
+#endif
+
 template <bool SCENE_IN_LDS, bool TAIL = false>
 __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene sc, DevCamera cam, TraceParams tp,
                                                                  uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
@@ -783,6 +983,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
     uint64_t chunk_next = 0, chunk_end = 0; /* wave-uniform */
 
     uint32_t n_scans = 0, n_shaded = 0, n_shadow = 0, n_draws = 0, n_paths = 0;
+#ifdef DRT_BRANCH_STATS
+    uint64_t bs[DRT_BS_WORDS] = {};
+#endif
 
     /* per-lane path state */
     bool alive = false;
@@ -922,6 +1125,10 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
             {
                 path_open_vertex(tp, wp, records, shaded, hdr, blk, tbl, spare, spare_tbl);
                 uint64_t *vrec = records + (uint64_t)blk * tp.block_words + (uint64_t)(shaded & (REC_BLOCK_VERTICES - 1u)) * tp.vertex_words;
+                /* the vertex's mirror and refracted directions, shared by the lights' evaluations, the sampler and the continuation's
+                 * evaluation. Computed before the light loop, so they are live across the shadow scans (after the first scan instead:
+                 * more scratch) */
+                const VertexDirs vd = vertex_dirs(sc, sv, ip);
                 /* direct_light_contribution, :272-332 -- light samples are drawn before the shadow test */
                 n_shaded += 1;
                 bool t_vis = false; /* light 0 as the tail arithmetic below wants it (the kernel carries tails only in one-light scenes) */
@@ -965,7 +1172,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                     if (visible)
                     {
                         V3 incoming = v_normalise(v_sub(light_position, ip.position));
-                        EvalCoef e = eval_coefficients(sc, sv, ip, incoming);
+                        EvalCoef e = eval_coefficients(sv, ip, vd, incoming);
                         lflags = e.flags | FLAG_VISIBLE;
                         if (l == 0 && shaded < 8u) vis0_mask |= 1u << shaded;
                         double c = attenuation * (light_pdf);
@@ -980,8 +1187,47 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 /* sampled continuation, :464-472 */
                 V3 in;
                 double dir_pdf;
-                sample_direction(sc, sv, ip, rs, n_draws, in, dir_pdf);
-                EvalCoef e = eval_coefficients(sc, sv, ip, in);
+#ifdef DRT_BRANCH_STATS
+                const uint32_t draws_before = n_draws;
+#endif
+                sample_direction(sc, sv, ip, vd, rs, n_draws, in, dir_pdf);
+                EvalCoef e = eval_coefficients(sv, ip, vd, in);
+#ifdef DRT_BRANCH_STATS
+                {
+                    /* counted by the first shading lane of the iteration; summed over lanes at the end */
+                    const uint32_t df = mat.dir_func;
+                    const bool in_loop = df == DRT_DIRF_cos_weighted_sample_hemisphere || df == DRT_DIRF_uniform_sample_hemisphere ||
+                                         df == DRT_DIRF_sample_ct_direction;
+                    const unsigned long long m_all = __ballot(1);
+                    const unsigned long long m_disc = __ballot(df == DRT_DIRF_cos_weighted_sample_hemisphere);
+                    const unsigned long long m_ggx = __ballot(df == DRT_DIRF_sample_ct_direction);
+                    const unsigned long long m_coin = __ballot(df == DRT_DIRF_sample_reflect_or_transmit_direction);
+                    const unsigned long long m_spec = __ballot(df == DRT_DIRF_sample_specular_direction);
+                    const unsigned long long m_loop = __ballot(in_loop);
+                    const unsigned long long m_again = __ballot(in_loop && n_draws - draws_before > 2u);
+                    const unsigned long long m_half = __ballot((mat.needs & (NEED_GLOSSY | NEED_CT)) != 0u);
+                    const unsigned long long m_eqt = __ballot((mat.needs & NEED_EQT) != 0u);
+                    if (lane == (uint32_t)(__ffsll((long long)m_all) - 1))
+                    {
+                        bs[0] += 1;
+                        bs[1] += __popcll(m_all);
+                        bs[2] += m_disc != 0ull;
+                        bs[3] += __popcll(m_disc);
+                        bs[4] += m_ggx != 0ull;
+                        bs[5] += __popcll(m_ggx);
+                        bs[6] += m_coin != 0ull;
+                        bs[7] += __popcll(m_coin);
+                        bs[8] += m_spec != 0ull;
+                        bs[9] += __popcll(m_spec);
+                        bs[10] += (m_disc != 0ull && m_ggx != 0ull && m_coin != 0ull && m_spec != 0ull);
+                        bs[11] += m_loop != 0ull;
+                        bs[12] += m_again != 0ull;
+                        bs[13] += m_half != 0ull;
+                        bs[14] += m_eqt != 0ull;
+                        bs[15] += (m_disc == m_all || m_ggx == m_all || m_coin == m_all || m_spec == m_all);
+                    }
+                }
+#endif
                 if (tail_ok)
                 {
                     if (mat.vertex_flags & FLAG_PLASTIC)
@@ -1094,6 +1340,24 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
         if (lane == 0 && v) atomicAdd(&counters[k], (unsigned long long)v);
     }
+#ifdef DRT_BRANCH_STATS
+    for (int k = 0; k < DRT_BS_WORDS; k += 1)
+    {
+        uint64_t v = bs[k];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+        if (lane == 0 && v) atomicAdd(&drt_branch_stats[k], (unsigned long long)v);
+    }
+    __threadfence();
+    if (lane == 0 && atomicAdd(&drt_branch_waves_done, 1u) + 1u == gridDim.x * (TRACE_BLOCK / 64u))
+    {
+        unsigned long long t[DRT_BS_WORDS];
+        for (int k = 0; k < DRT_BS_WORDS; k += 1) t[k] = atomicExch(&drt_branch_stats[k], 0ull);
+        printf("DRT_BRANCH_STATS iters %llu lanes %llu | disc %llu %llu | ggx %llu %llu | coin %llu %llu | spec %llu %llu | all4 %llu | "
+               "loop %llu again %llu | half %llu eqt %llu | uniform %llu\n",
+               t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15]);
+        drt_branch_waves_done = 0u;
+    }
+#endif
 }
 
 /* ---------------------------------------------------------------------------------------------- */
@@ -2400,7 +2664,7 @@ __global__ void drt_material_kernel(DevScene sc, const DevMaterial *__restrict__
         uint32_t draws = 0;
         V3 dir;
         double recip_pdf;
-        sample_direction(sc, sv, ip, rs, draws, dir, recip_pdf);
+        sample_direction(sc, sv, ip, vertex_dirs(sc, sv, ip), rs, draws, dir, recip_pdf);
         o[0] = dir.x; o[1] = dir.y; o[2] = dir.z;
         o[3] = recip_pdf;
         o[4] = __longlong_as_double((long long)rs);
@@ -2412,7 +2676,7 @@ __global__ void drt_material_kernel(DevScene sc, const DevMaterial *__restrict__
     const V3 incoming = v3(a[14], a[15], a[16]);
     /* trace kernel: the scalars of the direction and the record words (drt_trace_kernel, "sampled continuation") */
     const DevMaterial &mat = sv.mats[ip.surface_mat];
-    const EvalCoef e = eval_coefficients(sc, sv, ip, incoming);
+    const EvalCoef e = eval_coefficients(sv, ip, vertex_dirs(sc, sv, ip), incoming);
     uint64_t w2 = record_media_word(sc, sv, ip);
     if (mode & DRT_MAT_MODE_UNPAIRED) w2 |= (uint64_t)PAIR_NONE << 48;
     const uint32_t flags = e.flags | mat.vertex_flags;
