@@ -288,6 +288,7 @@ struct SceneView /* pointers into LDS (or HBM when the scene does not fit) */
     const DevMaterial *mats;
     const BvhNode     *bvh_nodes;
     const BvhLeafPrim *bvh_leaf;
+    const double      *rows = nullptr; /* LDS scenes: the surface table again, one SR_STRIDE-word row per surface, for the scans */
     uint32_t           n_surf, n_lights;
 };
 
@@ -301,6 +302,31 @@ __device__ __forceinline__ double surface_distance(const SceneView &sv, uint32_t
     if (type == DRT_GEO_SPHERE) return line_sphere(o, d, sf3(sv, SF_PX, i), sv.surf[SF_RADIUS * sv.n_surf + i]);
     return line_plane(o, d, sf3(sv, SF_PX, i), sf3(sv, SF_NX, i), sf3(sv, SF_UNX, i), sf3(sv, SF_VNX, i),
                       sv.surf[SF_ULEN * sv.n_surf + i], sv.surf[SF_VLEN * sv.n_surf + i]);
+}
+
+/* A surface as the LDS scans read it: its SF_COUNT fields and its type in one 128-byte row. The scan index is wave-uniform, so a
+ * row is one address and every field an immediate offset from it; the SoA table costs a vector register move per field read. */
+#define SR_STRIDE 16
+#define SR_TYPE 15 /* the row's last word: the surface type (DRT_GEO_*) */
+static_assert(SF_COUNT <= SR_TYPE, "a surface row holds the SF_COUNT fields and the type");
+__device__ __forceinline__ V3 row3(const double *r, int f) { return v3(r[f], r[f + 1], r[f + 2]); }
+__device__ __forceinline__ uint32_t row_type(const double *r) { return (uint32_t)__double_as_longlong(r[SR_TYPE]); }
+/* surface_distance on a row: the same intersector on the same numbers */
+__device__ __forceinline__ double row_distance(const double *r, uint32_t type, V3 o, V3 d)
+{
+    if (type == DRT_GEO_SPHERE) return line_sphere(o, d, row3(r, SF_PX), r[SF_RADIUS]);
+    return line_plane(o, d, row3(r, SF_PX), row3(r, SF_NX), row3(r, SF_UNX), row3(r, SF_VNX), r[SF_ULEN], r[SF_VLEN]);
+}
+/* surface i's type and distance, from its row (ROWS: the scene is in LDS) or from the SoA tables */
+template <bool ROWS>
+__device__ __forceinline__ uint32_t scan_type(const SceneView &sv, uint32_t i)
+{
+    return ROWS ? row_type(sv.rows + (size_t)i * SR_STRIDE) : sv.surf_type[i];
+}
+template <bool ROWS>
+__device__ __forceinline__ double scan_distance(const SceneView &sv, uint32_t i, uint32_t type, V3 o, V3 d)
+{
+    return ROWS ? row_distance(sv.rows + (size_t)i * SR_STRIDE, type, o, d) : surface_distance(sv, i, type, o, d);
 }
 
 #define BVH_STACK 32 /* levels of the deepest tree the builder hands out = entries a traversal stack can need */
@@ -403,6 +429,7 @@ __device__ __forceinline__ void bvh_children(const BvhNode &n, const Ray32 &r, f
 }
 
 /* points_mutually_visible, src/daily_ray_trace.c:238-270 */
+template <bool ROWS = false>
 __device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 p0, V3 p1)
 {
     V3 dir = v_normalise(v_sub(p1, p0));
@@ -411,9 +438,9 @@ __device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 
     bool visible = true;
     for (uint32_t i = 0; i < sv.n_surf; i += 1)
     {
-        uint32_t type = sv.surf_type[i];
+        uint32_t type = scan_type<ROWS>(sv, i);
         if (type != DRT_GEO_SPHERE && type != DRT_GEO_PLANE) continue;
-        double dist = surface_distance(sv, i, type, o, dir);
+        double dist = scan_distance<ROWS>(sv, i, type, o, dir);
         if (visible && dist < vis_dist) visible = false; /* the reference breaks here; later surfaces cannot undo it */
         if (!__any(visible)) break;
     }
@@ -429,6 +456,7 @@ struct HitPoint /* scene_point, src/daily_ray_trace.h:113-125 */
 };
 
 /* find_ray_intersection, src/daily_ray_trace.c:334-403 */
+template <bool ROWS = false>
 __device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const DevScene &sc, HitPoint &ip, V3 ro, V3 rd)
 {
     double min_dist = DRT_INF;
@@ -437,9 +465,9 @@ __device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const
     {
         for (uint32_t i = 0; i < sv.n_surf; i += 1)
         {
-            uint32_t type = sv.surf_type[i];
+            uint32_t type = scan_type<ROWS>(sv, i);
             if (type != DRT_GEO_SPHERE && type != DRT_GEO_PLANE) continue;
-            double dist = surface_distance(sv, i, type, ro, rd);
+            double dist = scan_distance<ROWS>(sv, i, type, ro, rd);
             if (dist < min_dist)
             {
                 min_dist = dist;
@@ -885,7 +913,8 @@ __device__ __forceinline__ void camera_ray(const DevCamera &cam, uint32_t scheme
 #define DRT_TRACE_WAVES_PER_SIMD 3 /* register budget: launch_bounds' 2nd argument is waves per SIMD */
 #endif
 
-/* LDS carve-up (8-byte aligned): surfaces, lights, then u32 tables, then materials (see trace_lds_bytes in the launcher) */
+/* LDS carve-up (8-byte aligned): the scans' surface rows, surfaces, lights, then u32 tables, then materials (see trace_lds_bytes in
+ * the launcher) */
 
 #ifdef DRT_BRANCH_STATS
 /* Measurement build only (-DDRT_BRANCH_STATS, never in the product): per wave-iteration that shades, which samplers and evaluator
@@ -908,7 +937,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
     if (SCENE_IN_LDS)
     {
         /* stage the SoA scene: coalesced HBM reads, one pass per table */
-        double *l_surf = lds_raw;
+        double *l_rows = lds_raw;
+        double *l_surf = l_rows + (size_t)SR_STRIDE * sc.n_surf;
+        for (uint32_t k = threadIdx.x; k < SR_STRIDE * sc.n_surf; k += TRACE_BLOCK)
+        {
+            const uint32_t i = k / SR_STRIDE, f = k % SR_STRIDE;
+            l_rows[k] = f < SF_COUNT ? sc.surf[f * sc.n_surf + i] : f == SR_TYPE ? __longlong_as_double((long long)sc.surf_type[i]) : 0.0;
+        }
         double *l_lights = l_surf + (size_t)SF_COUNT * sc.n_surf;
         uint32_t *l_u32 = (uint32_t *)(l_lights + (size_t)LF_COUNT * sc.n_lights);
         uint32_t n_u32 = 2 * sc.n_surf + 2 * sc.n_lights;
@@ -936,6 +971,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         sv.light_type = l_u32 + 2 * sc.n_surf;
         sv.light_mat = l_u32 + 2 * sc.n_surf + sc.n_lights;
         sv.mats = l_mats;
+        sv.rows = l_rows;
         sv.bvh_nodes = nullptr; /* a scene that fits LDS is scanned whole */
         sv.bvh_leaf = nullptr;
     }
@@ -1108,7 +1144,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         {
             /* ---- one iteration of cast_ray's loop, src/daily_ray_trace.c:446-474 ---- */
             HitPoint ip;
-            find_ray_intersection(sv, sc, ip, ro, rd);
+            find_ray_intersection<SCENE_IN_LDS>(sv, sc, ip, ro, rd);
             n_scans += 1;
             if (tp.record_hits) hits[((uint64_t)tp.hits_sample_offset * tp.n_pix + hit_row) * tp.max_depth + depth] = ip.index;
             const DevMaterial &mat = sv.mats[ip.surface_mat];
@@ -1166,7 +1202,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                         light_position = v_sum(v_sum(lpos, v_mul(lu, u)), v_mul(lv, v));
                     }
                     n_shadow += 1;
-                    bool visible = points_mutually_visible(sv, ip.position, light_position);
+                    bool visible = points_mutually_visible<SCENE_IN_LDS>(sv, ip.position, light_position);
                     uint64_t *lrec = vrec + REC_VERTEX_WORDS + (uint64_t)l * REC_LIGHT_WORDS;
                     uint32_t lflags = 0;
                     if (visible)

@@ -110,7 +110,7 @@ struct drt_context
 
 static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat)
 {
-    size_t b = (size_t)SF_COUNT * n_surf * 8 + (size_t)LF_COUNT * n_lights * 8;
+    size_t b = (size_t)(SR_STRIDE + SF_COUNT) * n_surf * 8 + (size_t)LF_COUNT * n_lights * 8;
     b += ((size_t)(2 * n_surf + 2 * n_lights) * 4 + 7) & ~(size_t)7;
     b += (size_t)n_mat * sizeof(DevMaterial);
     return b;
