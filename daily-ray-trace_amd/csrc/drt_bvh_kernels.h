@@ -67,14 +67,16 @@ struct PathStart
     uint64_t q, s_local, hit_row, slot;
     uint32_t x, y, sample;
 };
+template <bool LIST>
 __device__ __forceinline__ PathStart path_start(const TraceParams &tp, uint64_t pid)
 {
     PathStart ps;
     ps.q = pid / tp.n_samples; /* consecutive ids: the samples of one pixel */
     ps.s_local = pid - ps.q * tp.n_samples;
     ps.hit_row = ps.s_local * tp.n_pix + ps.q;
-    uint32_t j = (uint32_t)(ps.q / tp.tile_w);
-    uint32_t i = (uint32_t)(ps.q - (uint64_t)j * tp.tile_w);
+    const uint64_t t = LIST ? (uint64_t)tp.pixel_list[ps.q] : ps.q; /* the tile pixel */
+    uint32_t j = (uint32_t)(t / tp.tile_w);
+    uint32_t i = (uint32_t)(t - (uint64_t)j * tp.tile_w);
     ps.x = tp.x0 + i;
     ps.y = tp.y0 + j * tp.row_stride;
     ps.sample = tp.first_sample + (uint32_t)ps.s_local;
@@ -94,6 +96,7 @@ __device__ __forceinline__ uint64_t path_key(const TraceParams &tp, const PathSt
 #ifndef DRT_PRIMARY_WAVES_PER_SIMD
 #define DRT_PRIMARY_WAVES_PER_SIMD 6 /* 80 registers, 28 bytes of scratch: config 5 trace stage 506 -> 500 ms (5 and 8 waves: 501, 500) */
 #endif
+template <bool LIST = false>
 __global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt_primary_kernel(DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ headers,
                                                                     int32_t *__restrict__ hits, unsigned long long *__restrict__ counters,
                                                                     PrimaryHit *__restrict__ primary, uint64_t *__restrict__ queue,
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt
         const uint64_t pid = packet * 64u + lane;
         const bool valid = pid < tp.n_paths;
         V3 ro = v3(0, 0, 0), rd = v3(0, 0, 1);
-        PathStart ps = path_start(tp, valid ? pid : 0);
+        PathStart ps = path_start<LIST>(tp, valid ? pid : 0);
         uint64_t rs = 1;
         if (valid)
         {
@@ -355,6 +358,7 @@ __device__ __forceinline__ void bvh_walk(const SceneView &sv, int *stack, int *l
     }
 }
 
+template <bool LIST = false>
 __global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_bounce_kernel(
     DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ records, uint64_t *__restrict__ headers, int32_t *__restrict__ hits,
     unsigned long long *__restrict__ counters, unsigned long long *__restrict__ work_counter, const PrimaryHit *__restrict__ primary,
@@ -446,7 +450,7 @@ __global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_b
             {
                 /* the path's start, recomputed (same arithmetic as the primary kernel), and its first vertex from the queue */
                 const uint64_t pid = queue[my];
-                const PathStart ps = path_start(tp, pid);
+                const PathStart ps = path_start<LIST>(tp, pid);
                 hit_row = ps.hit_row;
                 rs = drt_splitmix64(path_key(tp, ps));
                 uint32_t camera_draws = 0; /* counted by the primary kernel */

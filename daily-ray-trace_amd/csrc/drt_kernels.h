@@ -184,6 +184,9 @@ struct TraceParams
     double       *tail_stage;            /* [n_pix * batch][tail_count] per-sample values the shade kernel's film phase reads; NULL: off */
     const double *spd_tail;              /* [n_spd][tail_count]: the SPD table's tail columns */
     uint32_t      tail_count, n_spd;
+    /* adaptive rounds (the LIST instantiations only): launch pixel q is tile pixel pixel_list[q]; n_pix counts the list's entries.
+     * Headers, records, the hit log and tail_stage stay indexed by q */
+    const uint32_t *pixel_list;
 };
 
 /* A wave's share of the pool. Waves take POOL_CHUNK blocks at a time from the global cursor and hand them to their lanes by
@@ -924,7 +927,7 @@ __device__ unsigned long long drt_branch_stats[DRT_BS_WORDS];
 __device__ unsigned int drt_branch_waves_done;
 #endif
 
-template <bool SCENE_IN_LDS, bool TAIL = false>
+template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
 __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene sc, DevCamera cam, TraceParams tp,
                                                                  uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
                                                                  int32_t *__restrict__ hits, unsigned long long *__restrict__ counters,
@@ -1097,8 +1100,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 uint64_t q = pid / tp.n_samples; /* consecutive ids: the samples of one pixel */
                 uint64_t s_local = pid - q * tp.n_samples;
                 hit_row = s_local * tp.n_pix + q;
-                uint32_t j = (uint32_t)(q / tp.tile_w);
-                uint32_t i = (uint32_t)(q - (uint64_t)j * tp.tile_w);
+                const uint64_t t = LIST ? (uint64_t)tp.pixel_list[q] : q; /* the tile pixel */
+                uint32_t j = (uint32_t)(t / tp.tile_w);
+                uint32_t i = (uint32_t)(t - (uint64_t)j * tp.tile_w);
                 uint32_t x = tp.x0 + i;
                 uint32_t y = tp.y0 + j * tp.row_stride;
                 uint32_t sample = tp.first_sample + (uint32_t)s_local;
@@ -1432,6 +1436,7 @@ struct ShadeParams
     uint32_t tail_period_mains, pad1;  /* split queue with a tail: main-pass items between two tail items (<= main items per group) */
     uint32_t items_per_group, n_items; /* work items: per group of `chunk` pixels, ceil(chunk/sub_pixels) main-pass items and, with a tail,
                                           one tail-pass item; items_per_group == 1: one item does the group's main pass and then its tail */
+    const uint32_t *pixel_list;        /* the LIST instantiations: launch pixel q's film rows are tile pixel pixel_list[q]'s */
 };
 
 __device__ __forceinline__ double word_as_double(uint64_t w) { return __longlong_as_double((long long)w); }
@@ -1570,7 +1575,7 @@ __device__ __forceinline__ double bdsf_at_wavelength(uint64_t list, uint32_t num
  * arithmetic in the same order. It is a work item of the shade kernel's queue, sharing the SIMDs with main-pass waves
  * (as a kernel of its own, at 4 to 8 waves per SIMD, it was 12-27 ms slower: measured).
  */
-template <bool SPDS_IN_LDS, bool XYZ, bool SIMPLE>
+template <bool SPDS_IN_LDS, bool XYZ, bool SIMPLE, bool LIST = false>
 __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const ShadeParams &sp, const double *lds, uint64_t *wave_lds, const uint64_t *__restrict__ records,
                                                  const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                                  double *__restrict__ film_avgs, double *__restrict__ film_vars, uint64_t chunk_base,
@@ -1816,9 +1821,10 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
         }
         __builtin_amdgcn_wave_barrier(); /* every lane is through the window before its headers are overwritten */
     }
-    double *px = film_pixels + pix_l * (uint64_t)(XYZ ? XYZ_FILM_WORDS : S + 1);
-    double *pa = XYZ ? nullptr : film_avgs + pix_l * (uint64_t)S;
-    double *pv = XYZ ? nullptr : film_vars + pix_l * (uint64_t)S;
+    const uint64_t pix_f = LIST ? (act ? (uint64_t)sp.pixel_list[pix_l] : 0u) : pix_l; /* its film row */
+    double *px = film_pixels + pix_f * (uint64_t)(XYZ ? XYZ_FILM_WORDS : S + 1);
+    double *pa = XYZ ? nullptr : film_avgs + pix_f * (uint64_t)S;
+    double *pv = XYZ ? nullptr : film_vars + pix_f * (uint64_t)S;
     const double *stage = sp.tail_stage + (pix_l * (uint64_t)sp.batch) * R + j;
     /* Phase B -- the film update (src/daily_ray_trace.c:732-743), the pixels' samples in order, all pixels in step */
     double f_sum = (act && !XYZ) ? px[lam] : 0.0, f_avg = (act && !XYZ) ? pa[lam] : 0.0, f_var = (act && !XYZ) ? pv[lam] : 0.0;
@@ -1870,7 +1876,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
 }
 
 
-template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE = false>
+template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE = false, bool LIST = false>
 __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAVES_SIMPLE : SHADE_WAVES_PER_SIMD_FOR(NSETS)) void drt_shade_kernel(DevScene sc, ShadeParams sp, const uint64_t *__restrict__ records,
                                                                  const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                                                  double *__restrict__ film_avgs, double *__restrict__ film_vars,
@@ -1960,9 +1966,10 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
 
         /* spectral film: the pixel's [S+1] / [S] / [S] rows; XYZ film: its XYZ_FILM_WORDS accumulators, and the batch's
          * spectral sum starts from zero and is folded into them at the end */
-        double *px = film_pixels + pix * (uint64_t)(XYZ ? XYZ_FILM_WORDS : S + 1);
-        double *pa = XYZ ? nullptr : film_avgs + pix * (uint64_t)S;
-        double *pv = XYZ ? nullptr : film_vars + pix * (uint64_t)S;
+        const uint64_t pix_f = LIST ? (uint64_t)sp.pixel_list[pix] : pix; /* its film row */
+        double *px = film_pixels + pix_f * (uint64_t)(XYZ ? XYZ_FILM_WORDS : S + 1);
+        double *pa = XYZ ? nullptr : film_avgs + pix_f * (uint64_t)S;
+        double *pv = XYZ ? nullptr : film_vars + pix_f * (uint64_t)S;
         double f_sum[NSETS], f_avg[NSETS], f_var[NSETS];
 #pragma unroll
         for (int k = 0; k < NSETS; k += 1)
@@ -2404,7 +2411,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
         }
       }
 
-        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, lane);
+        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, lane);
     }
 }
 

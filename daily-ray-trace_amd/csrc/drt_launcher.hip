@@ -5,6 +5,7 @@
  */
 #include "drt_kernels.h"
 #include "drt_bvh_kernels.h"
+#include "drt_adaptive_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -72,7 +73,7 @@ struct drt_context
     uint64_t  pool_blocks = 0;          /* blocks in d_records */
     uint32_t  worst_blocks_per_path = 0; /* what a path of max_depth vertices takes (table block included) */
     double    est_blocks_per_path = 0.0; /* measured on a sample of the tile when the context is created */
-    struct Batch { uint32_t first_sample, n_samples; uint64_t seq; uint32_t row0, rows, hits_sample_offset, stride; }; /* rows == 0: the whole tile */
+    struct Batch { uint32_t first_sample, n_samples; uint64_t seq; uint32_t row0, rows, hits_sample_offset, stride; const uint32_t *list; uint64_t list_len; }; /* rows == 0: the whole tile; list: the pixels of an adaptive round */
     std::vector<Batch> inflight;         /* kernel pairs enqueued since the last synchronisation (redone if the pool ran out) */
     uint64_t  next_seq = 1;
     uint64_t  redone_batches = 0, pool_peak = 0;
@@ -106,6 +107,16 @@ struct drt_context
     double trace_ms = 0.0, shade_ms = 0.0;
     uint64_t timed_pairs = 0; /* per sample pass over the tile (src/daily_ray_trace.c:746-756): min, max, running mean over the pairs */
     double min_sample_ms = 0.0, max_sample_ms = 0.0, avg_sample_ms = 0.0;
+
+    /* adaptive sampling (drt_render_adaptive): the film has had samples from drt_render / drt_write_film, or an adaptive render */
+    bool film_used = false, adaptive_done = false;
+    uint32_t *d_counts = nullptr;          /* [n_pix] samples per pixel */
+    uint32_t *d_alist[2] = {nullptr, nullptr}; /* the round's active pixels and the next round's (ping-pong) */
+    unsigned long long *d_keep = nullptr;  /* [ceil(n_pix / 64)] keep bits */
+    uint32_t *d_bkeep = nullptr;           /* [blocks of drt_converge_kernel + 1]: per block, then the active count */
+    uint32_t *h_active = nullptr;          /* pinned host word the active count is copied to: the copy stays asynchronous, so the
+                                              devices of a group are all given their round before any is waited for */
+    struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true; uint64_t redone = 0; } ad;
 };
 
 static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat)
@@ -671,11 +682,11 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
 
 static bool shade_simple(const drt_context *ctx) { return ctx->simple_bdsfs && ctx->spds_in_lds && ctx->shade_sets == 1; }
 
-template <int NSETS, bool XYZ>
+template <int NSETS, bool XYZ, bool LIST>
 static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams &sp, double *const film[3])
 {
 #define DRT_LAUNCH_SHADE(LDS, DARK, SIMPLE)                                                                                                       \
-    hipLaunchKernelGGL((drt_shade_kernel<NSETS, LDS, XYZ, DARK, SIMPLE>), dim3(grid), dim3(SHADE_BLOCK), ctx->shade_lds, ctx->stream, ctx->dsc, sp, \
+    hipLaunchKernelGGL((drt_shade_kernel<NSETS, LDS, XYZ, DARK, SIMPLE, LIST>), dim3(grid), dim3(SHADE_BLOCK), ctx->shade_lds, ctx->stream, ctx->dsc, sp, \
                        ctx->d_records, ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
     /* SIMPLE: scenes without a Fresnel function, one wavelength set per lane, tables in LDS (shade_simple()) */
     if (NSETS == 1 && shade_simple(ctx))
@@ -694,7 +705,8 @@ static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams 
 template <int NSETS>
 static int launch_shade_sets(drt_context *ctx, uint32_t grid, const ShadeParams &sp, double *const film[3])
 {
-    return ctx->xyz_mode ? launch_shade_mode<NSETS, true>(ctx, grid, sp, film) : launch_shade_mode<NSETS, false>(ctx, grid, sp, film);
+    if (sp.pixel_list) return launch_shade_mode<NSETS, false, true>(ctx, grid, sp, film); /* an adaptive round: spectral film only */
+    return ctx->xyz_mode ? launch_shade_mode<NSETS, true, false>(ctx, grid, sp, film) : launch_shade_mode<NSETS, false, false>(ctx, grid, sp, film);
 }
 
 /* How the S wavelengths map to lanes: n full 64-lane sets, plus (when the remainder is small) a packed tail pass */
@@ -774,7 +786,8 @@ static size_t pixels_bytes(const drt_context *ctx)
     return (size_t)ctx->n_pix * (ctx->xyz_mode ? (size_t)XYZ_FILM_WORDS : (size_t)ctx->dsc.S + 1) * 8;
 }
 
-static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0);
+static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0,
+                         const uint32_t *list = nullptr, uint64_t list_len = 0);
 
 /* waves of the trace-stage kernel that takes record blocks, for a launch of n_paths */
 static uint64_t trace_waves(const drt_context *ctx, uint64_t n_paths)
@@ -870,8 +883,8 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     if (ctx->bvh_pipeline)
     {
         int p_cu = 0, b_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p_cu, drt_primary_kernel, PRIMARY_BLOCK, 0));
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b_cu, drt_bounce_kernel, BOUNCE_BLOCK, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&p_cu, drt_primary_kernel<false>, PRIMARY_BLOCK, 0));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b_cu, drt_bounce_kernel<false>, BOUNCE_BLOCK, 0));
         if (const char *e = getenv("DRT_TRACE_BLOCKS_PER_CU")) b_cu = std::max(1, atoi(e));
         ctx->primary_grid_cap = prop.multiProcessorCount * std::max(1, p_cu);
         ctx->bounce_grid_cap = prop.multiProcessorCount * std::max(1, b_cu);
@@ -1066,6 +1079,12 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_xyz);
     (void)hipFree(ctx->d_bgra);
+    (void)hipFree(ctx->d_counts);
+    (void)hipFree(ctx->d_alist[0]);
+    (void)hipFree(ctx->d_alist[1]);
+    (void)hipFree(ctx->d_keep);
+    (void)hipFree(ctx->d_bkeep);
+    (void)hipHostFree(ctx->h_active);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -1155,7 +1174,8 @@ __global__ void drt_mark_pair_kernel(unsigned long long *totals, unsigned long l
 
 /* The trace stage of one kernel pair over samples [first_sample, first_sample + n) of every tile pixel: work queues and the
  * pool cursor reset, then drt_trace_kernel (scene in LDS) or drt_primary_kernel + drt_bounce_kernel (scene behind the hierarchy). */
-static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0, uint32_t rows, uint32_t stride)
+static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0, uint32_t rows, uint32_t stride,
+                         const uint32_t *list, uint64_t list_len)
 {
     const drt_params &p = ctx->params;
     TraceParams tp{};
@@ -1171,7 +1191,8 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
     tp.pixel_scheme = p.pixel_scheme;
     tp.record_hits = (p.flags & DRT_FLAG_RECORD_HITS) ? 1u : 0u;
     tp.seed = p.seed;
-    tp.n_pix = whole ? ctx->n_pix : (uint64_t)rows * p.tile_w;
+    tp.n_pix = list ? list_len : whole ? ctx->n_pix : (uint64_t)rows * p.tile_w; /* a list: its pixels, anywhere in the whole tile */
+    tp.pixel_list = list;
     tp.n_paths = tp.n_pix * n;
     tp.vertex_words = ctx->vertex_words;
     tp.block_words = ctx->block_words;
@@ -1201,12 +1222,22 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
         /* camera rays: a wave per 64 path ids; then the queued paths, one per lane */
         const uint64_t packets = (tp.n_paths + 63) / 64;
         const uint32_t pgrid = (uint32_t)std::min<uint64_t>((packets + PRIMARY_BLOCK / 64 - 1) / (PRIMARY_BLOCK / 64), (uint64_t)ctx->primary_grid_cap);
-        hipLaunchKernelGGL(drt_primary_kernel, dim3(pgrid), dim3(PRIMARY_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, tp, ctx->d_headers,
-                           ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, ctx->d_primary, ctx->d_queue, work + 2);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(drt_bounce_kernel, dim3(grid), dim3(BOUNCE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, tp, ctx->d_records,
-                           ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work, ctx->d_primary, ctx->d_queue, work + 2);
+#define DRT_LAUNCH_BVH(LIST)                                                                                                                    \
+        hipLaunchKernelGGL(drt_primary_kernel<LIST>, dim3(pgrid), dim3(PRIMARY_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, tp, ctx->d_headers, \
+                           ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, ctx->d_primary, ctx->d_queue, work + 2);                            \
+        HIP_TRY(hipGetLastError());                                                                                                             \
+        hipLaunchKernelGGL(drt_bounce_kernel<LIST>, dim3(grid), dim3(BOUNCE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, tp, ctx->d_records,    \
+                           ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work, ctx->d_primary, ctx->d_queue, work + 2)
+        if (list) { DRT_LAUNCH_BVH(true); }
+        else { DRT_LAUNCH_BVH(false); }
+#undef DRT_LAUNCH_BVH
     }
+    else if (list && ctx->trace_tail && tp.tail_stage)
+        hipLaunchKernelGGL((drt_trace_kernel<true, true, true>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
+                           ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
+    else if (list)
+        hipLaunchKernelGGL((drt_trace_kernel<true, false, true>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
+                           ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
     else if (ctx->trace_tail && tp.tail_stage)
         hipLaunchKernelGGL((drt_trace_kernel<true, true>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
                            ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
@@ -1218,15 +1249,16 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
 }
 
 /* One kernel pair: trace, shade + film, and the mark that tells the host whether the pair was complete. */
-static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0)
+static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0,
+                        const uint32_t *list = nullptr, uint64_t list_len = 0)
 {
     hipEvent_t ev[3];
     int rc = next_events(ctx, ev);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    if ((rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, row0, rows, stride))) return rc;
-    const uint64_t n_pix = rows ? (uint64_t)rows * ctx->params.tile_w : ctx->n_pix; /* pixels of this launch */
-    const uint64_t pix0 = rows ? (uint64_t)row0 * ctx->params.tile_w : 0;           /* its first pixel in the tile */
+    if ((rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, row0, rows, stride, list, list_len))) return rc;
+    const uint64_t n_pix = list ? list_len : rows ? (uint64_t)rows * ctx->params.tile_w : ctx->n_pix; /* pixels of this launch */
+    const uint64_t pix0 = (rows && !list) ? (uint64_t)row0 * ctx->params.tile_w : 0;                  /* its first pixel in the tile */
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
 
     unsigned long long *work = ctx->d_counters + DRT_NUM_COUNTERS;
@@ -1245,6 +1277,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     sp.tail_stage = ctx->d_tail_stage;
     sp.light0_em_spd = ctx->light0_em_spd;
     sp.tail_staged = (ctx->tail_all_staged && ctx->d_tail_stage) ? 1u : 0u;
+    sp.pixel_list = list;
     if (const char *e = getenv("DRT_DEBUG_SHADE_MODE")) sp.mode = (uint32_t)atoi(e); /* timing probe: 1 main pass only, 2 tail pass only */
     if (const char *e = getenv("DRT_DEBUG_TAIL_PHASE_A_OFF")) sp.tail_staged = (uint32_t)atoi(e) ? 1u : sp.tail_staged;
     sp.cmf_rw = ctx->cmf_rw; sp.cmf_x = ctx->cmf_x; sp.cmf_y = ctx->cmf_y; sp.cmf_z = ctx->cmf_z;
@@ -1315,7 +1348,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     HIP_TRY(hipEventRecord(ev[2], ctx->stream));
     ctx->ev_paths.resize(ctx->ev_used / 3, 0.0);
     ctx->ev_paths[ctx->ev_used / 3 - 1] = (double)n_pix * (double)n;
-    ctx->inflight.push_back({first_sample, n, seq, row0, rows, hits_sample_offset, stride});
+    ctx->inflight.push_back({first_sample, n, seq, row0, rows, hits_sample_offset, stride, list, list_len});
     return 0;
 }
 
@@ -1337,7 +1370,8 @@ static int redo_batches(drt_context *ctx, uint64_t last_good_seq)
         for (uint32_t done = 0; done < b.n_samples; done += safe)
         {
             /* (the hit log is indexed by sample offset within the caller's drt_render call: the batch remembers its own) */
-            int rc = enqueue_pair(ctx, b.first_sample + done, std::min(safe, b.n_samples - done), b.hits_sample_offset + done, b.row0, b.rows);
+            int rc = enqueue_pair(ctx, b.first_sample + done, std::min(safe, b.n_samples - done), b.hits_sample_offset + done, b.row0, b.rows, 0,
+                                  b.list, b.list_len);
             if (rc) return rc;
         }
     }
@@ -1382,9 +1416,18 @@ static int enqueue_blocks(drt_context *ctx, uint32_t first_sample, uint32_t num_
     return 0;
 }
 
+static int render_impl(drt_context *ctx, uint32_t first_sample, uint32_t num_samples);
+
 extern "C" int drt_render(drt_context *ctx, uint32_t first_sample, uint32_t num_samples)
 {
     if (!ctx) return fail(-1, "null context");
+    if (ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
+    ctx->film_used = true;
+    return render_impl(ctx, first_sample, num_samples);
+}
+
+static int render_impl(drt_context *ctx, uint32_t first_sample, uint32_t num_samples)
+{
     HIP_TRY(hipSetDevice(ctx->device));
     (void)hipGetLastError(); /* drop a stale error of an earlier, unrelated call: launches below are checked against a clean slate */
     const drt_params &p = ctx->params;
@@ -1462,6 +1505,7 @@ extern "C" int drt_reset_film(drt_context *ctx)
     if (ctx->d_vars) HIP_TRY(hipMemsetAsync(ctx->d_vars, 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->film_used = ctx->adaptive_done = false;
     ctx->trace_ms = ctx->shade_ms = 0.0;
     ctx->timed_pairs = 0;
     ctx->min_sample_ms = ctx->max_sample_ms = ctx->avg_sample_ms = 0.0;
@@ -1493,6 +1537,8 @@ extern "C" int drt_read_film(drt_context *ctx, double *pixels, double *avgs, dou
 extern "C" int drt_write_film(drt_context *ctx, const double *pixels, const double *avgs, const double *vars)
 {
     if (!ctx) return fail(-1, "null context");
+    if (ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
+    ctx->film_used = true;
     int rc = drt_synchronize(ctx);
     if (rc) return rc;
     const size_t S = ctx->dsc.S;
@@ -1592,6 +1638,223 @@ extern "C" int drt_get_stats(drt_context *ctx, drt_stats *out)
 }
 
 extern "C" uint32_t drt_batch_spp(drt_context *ctx) { return ctx ? ctx->batch_spp : 0; }
+
+/*
+ * Adaptive sampling ("Adaptive sampling"). Round 0 renders samples [0, min_spp) of every tile pixel through the dense
+ * path; each later round renders the next min(step, max_spp - n) samples of the pixels still active, in kernel pairs over ranges of
+ * the active list (the LIST instantiations). Every round ends with drt_converge_kernel (+ scan + scatter), which writes the counts
+ * and the next list, and one 4-byte read of the active count. A pixel rendered over samples 0 .. n-1 in order holds, bit for bit,
+ * the film a uniform n-sample render gives it.
+ */
+static int adaptive_check(drt_context *ctx, const drt_adaptive *a)
+{
+    if (!ctx || !a) return fail(-1, "null argument");
+    if (ctx->xyz_mode) return fail(-4, "adaptive sampling needs the spectral film (DRT_MODE_XYZ keeps no variance)");
+    if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "adaptive sampling does not record hit indices (DRT_FLAG_RECORD_HITS)");
+    if (ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
+    if (ctx->film_used) return fail(-7, "adaptive sampling needs a film without samples: drt_reset_film first");
+    if (a->min_spp < 2) return fail(-1, "min_spp %u: at least 2 (the variance needs two samples)", a->min_spp);
+    if (a->max_spp < a->min_spp) return fail(-1, "max_spp %u is below min_spp %u", a->max_spp, a->min_spp);
+    if (a->step < 1) return fail(-1, "step must be at least 1");
+    if (a->flags != 0) return fail(-1, "flags %u: none are defined", a->flags);
+    if (!std::isfinite(a->rel_error) || !(a->rel_error > 0.0)) return fail(-1, "rel_error %g: a finite number above 0", a->rel_error);
+    if (!std::isfinite(a->floor) || !(a->floor >= 0.0)) return fail(-1, "floor %g: a finite number, 0 or more", a->floor);
+    if (ctx->n_pix > 0xFFFFFFFFull) return fail(-1, "adaptive sampling lists pixels in 32 bits: the tile has %llu", (unsigned long long)ctx->n_pix);
+    return 0;
+}
+
+/* the convergence kernels over the round's n_in entries; the active count goes to d_bkeep[n_blocks] and from there, asynchronously, to
+ * the pinned word h_active (adaptive_finish_round reads it after its wait) */
+static int enqueue_converge(drt_context *ctx)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    const uint32_t n_blocks = (uint32_t)(((uint64_t)ad.n_in + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK);
+    ConvergeParams cp{};
+    cp.list_in = ad.first ? nullptr : ctx->d_alist[ad.cur];
+    cp.n_in = ad.n_in;
+    cp.n = ad.n;
+    cp.max_spp = ad.a.max_spp;
+    cp.cmf_rw = ctx->cmf_rw;
+    cp.cmf_y = ctx->cmf_y;
+    cp.interval = ctx->interval;
+    cp.rel_error = ad.a.rel_error;
+    cp.floor = ad.a.floor;
+    cp.counts = ctx->d_counts;
+    cp.keep_mask = ctx->d_keep;
+    cp.block_keep = ctx->d_bkeep;
+    cp.active = ctx->d_bkeep + n_blocks;
+    cp.list_out = ctx->d_alist[ad.first ? 0 : ad.cur ^ 1];
+    cp.overflow = (const uint32_t *)(ctx->d_counters + DRT_NUM_COUNTERS + 5);
+    hipLaunchKernelGGL(drt_converge_kernel, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, ctx->dsc, cp, ctx->d_avgs, ctx->d_vars);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(drt_converge_scan, dim3(1), dim3(CONVERGE_SCAN_BLOCK), 0, ctx->stream, cp, n_blocks);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(drt_converge_scatter, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, cp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_active, cp.active, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static void adaptive_free(drt_context *ctx)
+{
+    (void)hipFree(ctx->d_counts);
+    (void)hipFree(ctx->d_alist[0]);
+    (void)hipFree(ctx->d_alist[1]);
+    (void)hipFree(ctx->d_keep);
+    (void)hipFree(ctx->d_bkeep);
+    (void)hipHostFree(ctx->h_active);
+    ctx->d_counts = ctx->d_alist[0] = ctx->d_alist[1] = ctx->d_bkeep = ctx->h_active = nullptr;
+    ctx->d_keep = nullptr;
+}
+
+static int adaptive_alloc(drt_context *ctx)
+{
+    adaptive_free(ctx);
+    const uint64_t n_pix = ctx->n_pix;
+    HIP_TRY(hipMalloc((void **)&ctx->d_counts, n_pix * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&ctx->d_alist[0], n_pix * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&ctx->d_alist[1], n_pix * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&ctx->d_keep, (n_pix + 63) / 64 * sizeof(unsigned long long)));
+    HIP_TRY(hipMalloc((void **)&ctx->d_bkeep, ((n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK + 1) * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void **)&ctx->h_active, sizeof(uint32_t), hipHostMallocDefault));
+    return 0;
+}
+
+/* round 0: buffers, the dense render of samples [0, min_spp), the convergence kernels */
+static int adaptive_begin(drt_context *ctx, const drt_adaptive *a)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    (void)hipGetLastError();
+    ctx->adaptive_done = true; /* from here on the film holds (part of) an adaptive render */
+    drt_context::Adaptive &ad = ctx->ad;
+    ad = drt_context::Adaptive{};
+    ad.a = *a;
+    ad.a.rounds = ad.a.pixels_at_max = 0;
+    ad.a.paths = 0;
+    const uint64_t n_pix = ctx->n_pix;
+    if (!ctx->d_counts || !ctx->d_alist[0] || !ctx->d_alist[1] || !ctx->d_keep || !ctx->d_bkeep || !ctx->h_active)
+    {
+        /* all or none: a call that failed half way leaves no buffer behind that a later call would take for the whole set */
+        const int rc = adaptive_alloc(ctx);
+        if (rc) adaptive_free(ctx);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(ctx->d_counts, 0, n_pix * sizeof(uint32_t), ctx->stream));
+    ad.first = true;
+    ad.n_in = (uint32_t)n_pix;
+    ad.k = a->min_spp;
+    ad.n = a->min_spp;
+    int rc = render_impl(ctx, 0, a->min_spp);
+    if (rc) return rc;
+    return enqueue_converge(ctx);
+}
+
+/* a later round: samples [n, n + k) of the ad.active pixels of list d_alist[cur], in kernel pairs over ranges of the list. A pair
+ * takes up to five eighths of the paths the record pool is sized for (the pixels still active are the ones with the long paths: a
+ * pair that runs out anyway is rendered again by redo_batches), its pixels all the round's samples where they fit; pairs of equal size */
+static int adaptive_enqueue_round(drt_context *ctx)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    ad.first = false;
+    ad.n_in = ad.active;
+    ad.k = std::min(ad.a.step, ad.a.max_spp - ad.n);
+    const uint32_t first = ad.n;
+    ad.n += ad.k;
+    const uint64_t budget = std::max<uint64_t>(1, ctx->n_pix * (uint64_t)ctx->batch_spp * 5 / 8);
+    const uint32_t m_fit = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ad.k, budget), 4096);
+    const uint32_t n_sp = (ad.k + m_fit - 1) / m_fit, m = (ad.k + n_sp - 1) / n_sp;   /* samples per pair */
+    const uint64_t p_fit = std::max<uint64_t>(1, budget / m);
+    const uint64_t n_pp = (ad.n_in + p_fit - 1) / p_fit, P = (ad.n_in + n_pp - 1) / n_pp; /* pixels per pair */
+    const uint32_t *list = ctx->d_alist[ad.cur];
+    for (uint64_t off = 0; off < ad.n_in; off += P)
+    {
+        const uint64_t len = std::min<uint64_t>(P, ad.n_in - off);
+        for (uint32_t at = 0; at < ad.k; at += m)
+        {
+            const uint32_t ns = std::min(m, ad.k - at);
+            int rc = enqueue_pair(ctx, first + at, ns, 0, 0, 0, ns, list + off, len);
+            if (rc) return rc;
+        }
+    }
+    return enqueue_converge(ctx);
+}
+
+/* the round's one wait; a round whose record pool ran out is rendered again (drt_synchronize) and its convergence kernels rerun */
+static int adaptive_finish_round(drt_context *ctx)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint64_t redone = ctx->redone_batches;
+    int rc = drt_synchronize(ctx);
+    if (rc) return rc;
+    if (ctx->redone_batches != redone)
+    {
+        if ((rc = enqueue_converge(ctx))) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    ad.active = *ctx->h_active;
+    ad.a.rounds += 1;
+    ad.a.paths += (uint64_t)ad.n_in * (ad.first ? ad.a.min_spp : ad.k);
+    if (ad.n == ad.a.max_spp) ad.a.pixels_at_max += ad.n_in;
+    if (!ad.first) ad.cur ^= 1;
+    else ad.cur = 0;
+    return 0;
+}
+
+/* test knob DRT_ADAPTIVE_ROUNDS=k: stop after k rounds, the pixels still active left in the list drt_read_active_list reads */
+static uint32_t adaptive_round_cap()
+{
+    const char *e = getenv("DRT_ADAPTIVE_ROUNDS");
+    return e ? (uint32_t)std::max(0, atoi(e)) : 0u;
+}
+
+static bool adaptive_goes_on(const drt_context *ctx, uint32_t cap)
+{
+    return ctx->ad.active > 0 && !(cap && ctx->ad.a.rounds >= cap);
+}
+
+extern "C" int drt_render_adaptive(drt_context *ctx, drt_adaptive *a)
+{
+    g_last_error.clear();
+    int rc = adaptive_check(ctx, a);
+    if (rc) return rc;
+    const uint32_t cap = adaptive_round_cap();
+    if ((rc = adaptive_begin(ctx, a))) return rc;
+    if ((rc = adaptive_finish_round(ctx))) return rc;
+    while (adaptive_goes_on(ctx, cap))
+    {
+        if ((rc = adaptive_enqueue_round(ctx))) return rc;
+        if ((rc = adaptive_finish_round(ctx))) return rc;
+    }
+    a->rounds = ctx->ad.a.rounds;
+    a->pixels_at_max = ctx->ad.a.pixels_at_max;
+    a->paths = ctx->ad.a.paths;
+    return 0;
+}
+
+extern "C" int drt_read_active_list(drt_context *ctx, uint32_t *list, uint32_t capacity, uint32_t *count)
+{
+    if (!ctx || !count || (!list && capacity)) return fail(-1, "null argument");
+    if (!ctx->adaptive_done || !ctx->d_counts) return fail(-4, "no adaptive render: the list comes from drt_render_adaptive");
+    int rc = drt_synchronize(ctx);
+    if (rc) return rc;
+    const uint32_t n = ctx->ad.active;
+    if (n > capacity) return fail(-1, "the active list holds %u entries, the buffer %u", n, capacity);
+    if (n) HIP_TRY(hipMemcpy(list, ctx->d_alist[ctx->ad.cur], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *count = n;
+    return 0;
+}
+
+extern "C" int drt_read_sample_counts(drt_context *ctx, uint32_t *counts)
+{
+    if (!ctx || !counts) return fail(-1, "null argument");
+    if (!ctx->adaptive_done || !ctx->d_counts) return fail(-4, "no adaptive render: the counts come from drt_render_adaptive");
+    int rc = drt_synchronize(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(counts, ctx->d_counts, ctx->n_pix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
 
 static double wall_ms()
 {
@@ -1825,6 +2088,10 @@ extern "C" int drt_group_write_film(drt_group *g, const double *pixels, const do
 {
     int rc = drt_group_synchronize(g);
     if (rc) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && c->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
+    for (drt_context *c : g->ctx)
+        if (c) c->film_used = true;
     if ((rc = group_copy(g, const_cast<double *>(pixels), 0, true))) return rc;
     if ((rc = group_copy(g, const_cast<double *>(avgs), 1, true))) return rc;
     return group_copy(g, const_cast<double *>(vars), 2, true);
@@ -1874,6 +2141,65 @@ extern "C" int drt_group_get_stats(drt_group *g, drt_stats *out)
         out->min_sample_ms = std::max(out->min_sample_ms, st.min_sample_ms);
         out->max_sample_ms = std::max(out->max_sample_ms, st.max_sample_ms);
         out->avg_sample_ms = std::max(out->avg_sample_ms, st.avg_sample_ms);
+    }
+    return 0;
+}
+
+/* every device its own rounds on its own rows, side by side: a round is enqueued on all of them before any is waited for */
+extern "C" int drt_group_render_adaptive(drt_group *g, drt_adaptive *a)
+{
+    g_last_error.clear();
+    if (!g || !a) return fail(-1, "null argument");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = adaptive_check(c, a))) return rc;
+    const uint32_t cap = adaptive_round_cap();
+    std::vector<char> running(g->ctx.size(), 0); /* a round of this device is in flight */
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k])
+        {
+            if ((rc = adaptive_begin(g->ctx[k], a))) return rc;
+            running[k] = 1;
+        }
+    for (;;)
+    {
+        for (size_t k = 0; k < g->ctx.size(); k += 1)
+            if (running[k] && (rc = adaptive_finish_round(g->ctx[k]))) return rc;
+        bool any = false;
+        for (size_t k = 0; k < g->ctx.size(); k += 1)
+        {
+            running[k] = g->ctx[k] && adaptive_goes_on(g->ctx[k], cap);
+            if (running[k] && (rc = adaptive_enqueue_round(g->ctx[k]))) return rc;
+            any = any || running[k];
+        }
+        if (!any) break;
+    }
+    a->rounds = 0;
+    a->pixels_at_max = 0;
+    a->paths = 0;
+    for (drt_context *c : g->ctx)
+        if (c)
+        {
+            a->rounds = std::max(a->rounds, c->ad.a.rounds);
+            a->pixels_at_max += c->ad.a.pixels_at_max;
+            a->paths += c->ad.a.paths;
+        }
+    return 0;
+}
+
+extern "C" int drt_group_read_sample_counts(drt_group *g, uint32_t *counts)
+{
+    if (!g || !counts) return fail(-1, "null argument");
+    const size_t n = g->ctx.size();
+    const size_t row_bytes = (size_t)g->tile_w * sizeof(uint32_t);
+    for (size_t k = 0; k < n; k += 1)
+    {
+        drt_context *c = g->ctx[k];
+        if (!c) continue;
+        if (!c->adaptive_done || !c->d_counts) return fail(-4, "no adaptive render: the counts come from drt_group_render_adaptive");
+        int rc = drt_synchronize(c);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpy2D((char *)counts + k * row_bytes, n * row_bytes, c->d_counts, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
     }
     return 0;
 }

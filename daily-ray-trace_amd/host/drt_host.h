@@ -77,8 +77,9 @@ typedef struct
     f64 wavelength_interval;
 } spd_file_header;
 
-/* Host extras that the reference has no field for (device choice, RNG seed, batch size);
- * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME. */
+/* Host extras that the reference has no field for (device choice, RNG seed, batch size, adaptive sampling);
+ * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
+ * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR. */
 typedef struct
 {
     int32_t  device;
@@ -90,6 +91,10 @@ typedef struct
     uint32_t n_devices;      /* > 0: render on devices[0..n_devices) at once, image rows dealt cyclically (drt_group_*); */
     int32_t  devices[16];    /* 0: the single `device` above. DRT_DEVICES="0,1,2,3" or "all" (every visible device) */
     uint32_t all_devices;
+    /* adaptive sampling (drt_group_render_adaptive) when adaptive != 0: num_pixel_samples is max_spp; the .spd filter column holds
+     * each pixel's sample count. Not combined with checkpoints or resuming. */
+    uint32_t adaptive, adaptive_min_spp, adaptive_step;
+    double   adaptive_error, adaptive_floor;
 } drt_host_options;
 
 /* Fills *config from the text of a config.cfg. Unknown keys are fatal (exit(-1)), like the reference.

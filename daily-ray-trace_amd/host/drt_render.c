@@ -9,6 +9,8 @@
  */
 #include "drt_host.h"
 
+#include <errno.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -111,6 +113,23 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     if (!ctx) rc = -1;
     if (!rc && !(opt && opt->quiet) && drt_group_size(ctx) > 1) printf("Rendering on %u devices\n", drt_group_size(ctx));
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
+    if (!rc && opt && opt->adaptive)
+    {
+        /* adaptive sampling: rounds until every pixel has converged or holds num_pixel_samples (= max_spp) samples */
+        drt_adaptive a;
+        memset(&a, 0, sizeof(a));
+        a.min_spp = opt->adaptive_min_spp;
+        a.max_spp = p.spp;
+        a.step = opt->adaptive_step;
+        a.rel_error = opt->adaptive_error;
+        a.floor = opt->adaptive_floor;
+        rc = drt_group_render_adaptive(ctx, &a);
+        if (!rc) done = p.spp;
+        if (!rc && !opt->quiet)
+            printf("Adaptive: %u rounds, %llu of %llu paths traced (%.1f%%), %u of %llu pixels at %u samples\n", a.rounds,
+                   (unsigned long long)a.paths, (unsigned long long)p.spp * num_pixels, 100.0 * (f64)a.paths / ((f64)p.spp * (f64)num_pixels),
+                   a.pixels_at_max, (unsigned long long)num_pixels, p.spp);
+    }
     u32 step = (opt && opt->checkpoint_spp) ? opt->checkpoint_spp : p.spp;
     while (!rc && done < p.spp)
     {
@@ -185,6 +204,64 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     return (w0 || w1 || w2) ? -2 : 0;
 }
 
+/* a whole-string number from the environment: 0 and *out set, -1 (and a message naming the variable) when it does not parse */
+static int env_double(const char *name, double *out)
+{
+    const char *e = getenv(name);
+    char *end = NULL;
+    errno = 0;
+    double v = strtod(e, &end);
+    if (!*e || *end || errno) { fprintf(stderr, "render_image: %s=\"%s\" is not a number\n", name, e); return -1; }
+    *out = v;
+    return 0;
+}
+
+static int env_u32(const char *name, u32 *out)
+{
+    const char *e = getenv(name);
+    char *end = NULL;
+    errno = 0;
+    unsigned long long v = strtoull(e, &end, 10);
+    if (!*e || *end || errno || e[0] == '-' || v > 0xFFFFFFFFull) { fprintf(stderr, "render_image: %s=\"%s\" is not a whole number\n", name, e); return -1; }
+    *out = (u32)v;
+    return 0;
+}
+
+/* DRT_ADAPTIVE_*: parsed and checked here, before any device call. DRT_ADAPTIVE_ERROR=<rel_error> turns adaptive sampling on;
+ * DRT_ADAPTIVE_MIN_SPP (default min(16, num_pixel_samples)), DRT_ADAPTIVE_STEP (default min_spp), DRT_ADAPTIVE_FLOOR (default 0). */
+static int adaptive_options(const config_arguments *config, drt_host_options *opt)
+{
+    static const char *const names[] = { "DRT_ADAPTIVE_MIN_SPP", "DRT_ADAPTIVE_STEP", "DRT_ADAPTIVE_FLOOR" };
+    if (!getenv("DRT_ADAPTIVE_ERROR"))
+    {
+        for (int k = 0; k < 3; k += 1)
+            if (getenv(names[k])) { fprintf(stderr, "render_image: %s is set but DRT_ADAPTIVE_ERROR is not\n", names[k]); return -1; }
+        return 0;
+    }
+    const u32 max_spp = config->num_pixel_samples;
+    opt->adaptive = 1;
+    if (env_double("DRT_ADAPTIVE_ERROR", &opt->adaptive_error)) return -1;
+    if (!isfinite(opt->adaptive_error) || !(opt->adaptive_error > 0.0))
+    { fprintf(stderr, "render_image: DRT_ADAPTIVE_ERROR=%s: a finite number above 0\n", getenv("DRT_ADAPTIVE_ERROR")); return -1; }
+    opt->adaptive_min_spp = max_spp < 16 ? max_spp : 16;
+    if (getenv("DRT_ADAPTIVE_MIN_SPP") && env_u32("DRT_ADAPTIVE_MIN_SPP", &opt->adaptive_min_spp)) return -1;
+    if (opt->adaptive_min_spp < 2 || opt->adaptive_min_spp > max_spp)
+    {
+        fprintf(stderr, "render_image: DRT_ADAPTIVE_MIN_SPP=%u: from 2 to num_pixel_samples (%u)\n", opt->adaptive_min_spp, max_spp);
+        return -1;
+    }
+    opt->adaptive_step = opt->adaptive_min_spp;
+    if (getenv("DRT_ADAPTIVE_STEP") && env_u32("DRT_ADAPTIVE_STEP", &opt->adaptive_step)) return -1;
+    if (opt->adaptive_step < 1) { fprintf(stderr, "render_image: DRT_ADAPTIVE_STEP=%u: at least 1\n", opt->adaptive_step); return -1; }
+    opt->adaptive_floor = 0.0;
+    if (getenv("DRT_ADAPTIVE_FLOOR") && env_double("DRT_ADAPTIVE_FLOOR", &opt->adaptive_floor)) return -1;
+    if (!isfinite(opt->adaptive_floor) || !(opt->adaptive_floor >= 0.0))
+    { fprintf(stderr, "render_image: DRT_ADAPTIVE_FLOOR=%s: a finite number, 0 or more\n", getenv("DRT_ADAPTIVE_FLOOR")); return -1; }
+    if (getenv("DRT_CHECKPOINT_SPP")) { fprintf(stderr, "render_image: DRT_ADAPTIVE_ERROR cannot be combined with DRT_CHECKPOINT_SPP\n"); return -1; }
+    if (getenv("DRT_RESUME")) { fprintf(stderr, "render_image: DRT_ADAPTIVE_ERROR cannot be combined with DRT_RESUME\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -209,5 +286,6 @@ void render_image(config_arguments *config)
     if ((e = getenv("DRT_BATCH_SPP"))) opt.batch_spp = (u32)atoi(e);
     if ((e = getenv("DRT_CHECKPOINT_SPP"))) opt.checkpoint_spp = (u32)atoi(e);
     if ((e = getenv("DRT_RESUME"))) opt.resume = (u32)atoi(e);
+    if (adaptive_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

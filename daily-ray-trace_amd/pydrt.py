@@ -81,6 +81,20 @@ class Stats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class Adaptive(C.Structure):
+    """drt_adaptive (include/drt_hip.h): the inputs of an adaptive render and, after it, rounds / pixels_at_max / paths."""
+    _fields_ = [("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("step", C.c_uint32), ("flags", C.c_uint32),
+                ("rel_error", C.c_double), ("floor", C.c_double), ("rounds", C.c_uint32), ("pixels_at_max", C.c_uint32),
+                ("paths", C.c_uint64)]
+
+
+def make_adaptive(min_spp, max_spp, step, rel_error, floor=0.0):
+    a = Adaptive()
+    a.min_spp, a.max_spp, a.step, a.flags = min_spp, max_spp, step, 0
+    a.rel_error, a.floor = rel_error, floor
+    return a
+
+
 def make_params(width, height, spp, max_depth, seed=1, x0=0, y0=0, tile_w=None, tile_h=None, row_stride=1,
                 first_sample=0, pixel_scheme=FILM_SAMPLE_RANDOM, mode=MODE_SPECTRAL, device=0, batch_spp=0, flags=0):
     p = Params()
@@ -323,6 +337,11 @@ def hip_lib():
         L.drt_write_film.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.drt_read_hit_indices.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_uint64]
         L.drt_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
+        L.drt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Adaptive)]
+        L.drt_read_sample_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.drt_read_active_list.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+        L.drt_group_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Adaptive)]
+        L.drt_group_read_sample_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.drt_batch_spp.restype = C.c_uint32
         L.drt_batch_spp.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
@@ -343,7 +362,9 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_read_xyz", "drt_read_bgra", "drt_read_hit_indices", "drt_get_stats", "drt_batch_spp", "drt_render_tile", "drt_selftest_arith",
                "drt_selftest_unit", "drt_selftest_material", "drt_bvh_stats",
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
-               "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi"]
+               "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
+               "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
+               "drt_read_active_list"]
 
 
 def _check(rc, what):
@@ -443,6 +464,24 @@ class Renderer:
         _check(self.L.drt_get_stats(self.ctx, C.byref(st)), "drt_get_stats")
         return st
 
+    def render_adaptive(self, min_spp, max_spp, step, rel_error, floor=0.0):
+        """Adaptive sampling (drt_render_adaptive): returns {"rounds", "pixels_at_max", "paths"}."""
+        a = make_adaptive(min_spp, max_spp, step, rel_error, floor)
+        _check(self.L.drt_render_adaptive(self.ctx, C.byref(a)), "drt_render_adaptive")
+        return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths}
+
+    def read_sample_counts(self):
+        out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
+        _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
+        return out
+
+    def read_active_list(self):
+        """the tile pixels still active after the last adaptive round (DRT_ADAPTIVE_ROUNDS stops a render early), ascending"""
+        out = np.empty(self.n_pixels, dtype=np.uint32)
+        n = C.c_uint32()
+        _check(self.L.drt_read_active_list(self.ctx, _ptr(out, C.c_uint32), self.n_pixels, C.byref(n)), "drt_read_active_list")
+        return out[:n.value].copy()
+
 
 class Group:
     """drt_group_*: one host thread, several GPUs; the tile's rows dealt cyclically over `devices` (None: all visible)."""
@@ -482,6 +521,17 @@ class Group:
         st = Stats()
         _check(self.L.drt_group_get_stats(self.g, C.byref(st)), "drt_group_get_stats")
         return st
+
+    def render_adaptive(self, min_spp, max_spp, step, rel_error, floor=0.0):
+        """drt_group_render_adaptive: returns {"rounds", "pixels_at_max", "paths"} (rounds: the most any device ran)."""
+        a = make_adaptive(min_spp, max_spp, step, rel_error, floor)
+        _check(self.L.drt_group_render_adaptive(self.g, C.byref(a)), "drt_group_render_adaptive")
+        return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths}
+
+    def read_sample_counts(self):
+        out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
+        _check(self.L.drt_group_read_sample_counts(self.g, _ptr(out, C.c_uint32)), "drt_group_read_sample_counts")
+        return out
 
     def close(self):
         if self.g:

@@ -288,6 +288,37 @@ int drt_render_tile_multi(const drt_scene *scene, const drt_camera *camera, cons
                           const int32_t *devices, uint32_t n_devices,
                           double *dst_pixels, double *dst_avgs, double *dst_vars, drt_stats *stats);
 
+/*
+ * Adaptive sampling: stop sampling pixels whose film has converged. Round 0 renders samples [0, min_spp) of every tile pixel; each
+ * later round the next min(step, max_spp - n) samples of every pixel still active (all of them hold the same n). After a round each
+ * pixel rendered in it is tested on its own film (c = n samples; rw, cy the rows cmf_rw, cmf_y; avg, var its film rows):
+ *     N = interval * sum_i cy[i] rw[i]
+ *     Y = (sum_i cy[i] avg[i] rw[i]) * (interval / N),  E = (sum_i cy[i] sqrt(var[i] / (c (c - 1))) rw[i]) * (interval / N)
+ *     active next round  <=>  n < max_spp  &&  !(E <= rel_error * max(|Y|, floor))
+ * (sums sequential over ascending i, no contraction; a NaN stays active until max_spp). A pixel that ends with n_p samples holds,
+ * bit for bit, the film a uniform n_p-sample render gives it; the filter column of the film is its count.
+ */
+typedef struct drt_adaptive
+{
+    uint32_t min_spp, max_spp, step, flags; /* min_spp >= 2, max_spp >= min_spp, step >= 1; flags: 0 (reserved) */
+    double   rel_error, floor;              /* finite, rel_error > 0, floor >= 0 */
+    uint32_t rounds, pixels_at_max;         /* out */
+    uint64_t paths;                         /* out: samples rendered, summed over pixels */
+} drt_adaptive;                             /* 48 bytes */
+/* Synchronous. Needs a film without samples (a fresh context, or drt_reset_film after drt_render / drt_write_film), DRT_MODE_SPECTRAL and
+ * no DRT_FLAG_RECORD_HITS; refuses (nonzero, drt_last_error, nothing rendered) otherwise or on inputs out of range. Afterwards
+ * drt_render, drt_write_film and another adaptive call are refused until drt_reset_film. drt_get_stats counts every round. */
+int drt_render_adaptive(drt_context *ctx, drt_adaptive *a);
+/* Samples per pixel of the last adaptive render, [tile_h*tile_w]. Synchronises. */
+int drt_read_sample_counts(drt_context *ctx, uint32_t *counts);
+/* The pixels (tile indices, ascending) still active after the last round of the last adaptive render -- none once it has run to the
+ * end; the test knob DRT_ADAPTIVE_ROUNDS=k stops a render after k rounds. *count gets their number; capacity smaller than that is an
+ * error. Synchronises. */
+int drt_read_active_list(drt_context *ctx, uint32_t *list, uint32_t capacity, uint32_t *count);
+/* The group forms: every device runs its own rounds on its rows; film and counts are the same for any device list. */
+int drt_group_render_adaptive(drt_group *g, drt_adaptive *a);
+int drt_group_read_sample_counts(drt_group *g, uint32_t *counts); /* whole tile, image order */
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */
