@@ -907,10 +907,105 @@ __device__ __forceinline__ void camera_ray(const DevCamera &cam, uint32_t scheme
     }
 }
 
+/* Path ids without a 64-bit division per path. A wave hands out consecutive ids, so it keeps the (pixel, sample) pair of the next
+ * id it will hand out -- PathPos, wave-uniform, from one 64-bit division per draw from the work counter -- and a lane that takes
+ * the id `r` places further on (r <= 64) gets its pair from that one by 32-bit arithmetic. The same integers as id / n_samples
+ * and id % n_samples for every id and every n_samples >= 1. */
+struct PathPos
+{
+    uint64_t q; /* id / n_samples: the launch pixel */
+    uint32_t s; /* id % n_samples: the sample within the launch */
+};
+__device__ __forceinline__ PathPos path_pos_of_id(uint64_t id, uint32_t n_samples)
+{
+    PathPos p;
+    p.q = id / n_samples;
+    p.s = (uint32_t)(id - p.q * n_samples);
+    return p;
+}
+__device__ __forceinline__ PathPos path_pos_step(PathPos p, uint32_t r, uint32_t n_samples)
+{
+    const uint32_t room = n_samples - p.s; /* >= 1: ids left in pixel p.q from p on */
+    if (r < room) p.s += r;
+    else
+    {
+        const uint32_t over = r - room; /* < 64: ids past the end of pixel p.q; neither sum can wrap, whatever n_samples is */
+        uint32_t dq = 0u;
+        if (over >= n_samples) dq = over / n_samples; /* only where a pixel has fewer than 64 samples */
+        p.q += 1u + dq;
+        p.s = over - dq * n_samples;
+    }
+    return p;
+}
+/* tile pixel t = j * tile_w + i. A tile of up to 2^32 pixels takes the 32-bit division; the 64-bit form stays for larger ones */
+__device__ __forceinline__ void tile_pixel_ij(uint64_t t, uint32_t tile_w, uint32_t &i, uint32_t &j)
+{
+    if (t <= 0xFFFFFFFFull)
+    {
+        const uint32_t t32 = (uint32_t)t;
+        j = t32 / tile_w;
+        i = t32 - j * tile_w;
+    }
+    else
+    {
+        j = (uint32_t)(t / tile_w);
+        i = (uint32_t)(t - (uint64_t)j * tile_w);
+    }
+}
+
 /* ---------------------------------------------------------------------------------------------- */
 /* The trace kernel                                                                                */
 
 #define TRACE_BLOCK 256
+
+/* Launch constants of the trace kernel. A kernel's by-value arguments are all loaded at its entry and stay in scalar registers for
+ * as long as anything reads them: three structures and five pointers are more than a wave has, and what does not fit is parked in
+ * the lanes of a vector register, moved there and back by vector instructions. So the arguments are read as arguments in the
+ * prologue ONLY. What the loop reads at every vertex or scan step is copied to locals there and stays scalar; everything else --
+ * the camera, the tile and its seed, the hit log, the pool's and the tail's bookkeeping, the scene's few scalars -- is read where
+ * it is used, by scalar loads from the kernarg segment (the arguments' own memory): no vector instruction and no vector register.
+ * trace_const() hides the address from the compiler at each use, so that a read is neither hoisted out of the loop nor kept in
+ * registers from one use to the next. DRT_TRACE_CONST selects the two alternatives that were measured against it:
+ * 0 reads the arguments themselves, 1 a copy at the front of the workgroup's LDS. */
+struct TraceConst /* the kernel's argument list, in its order: the kernarg segment has this very layout */
+{
+    DevScene    sc;
+    DevCamera   cam;
+    TraceParams tp;
+    uint64_t           *records, *headers;
+    int32_t            *hits;
+    unsigned long long *counters, *work_counter;
+};
+static_assert(sizeof(DevScene) % 8 == 0 && sizeof(DevCamera) % 8 == 0 && sizeof(TraceParams) % 8 == 0,
+              "TraceConst mirrors the kernarg segment only while every argument ends on an 8-byte boundary");
+#ifndef DRT_TRACE_CONST
+#define DRT_TRACE_CONST 2
+#endif
+#if DRT_TRACE_CONST == 1
+#define TRACE_CONST_BYTES ((sizeof(TraceConst) + 127u) & ~(size_t)127u) /* whole 128-byte rows: the surface rows behind it keep their alignment */
+#else
+#define TRACE_CONST_BYTES ((size_t)0)
+#endif
+/* A wave-uniform value, re-read from its register at this point of the program. The tail loops test `j >= TR` for j = 0..7; left
+ * alone, the compiler evaluates the eight tests once ahead of the path loop and keeps the eight lane masks, 16 scalar registers,
+ * alive (and spilled) across all of it. Pinned at each loop, the tests are eight scalar compares where they are needed. */
+__device__ __forceinline__ uint32_t pinned_scalar(uint32_t v)
+{
+    asm volatile("" : "+s"(v));
+    return v;
+}
+__device__ __forceinline__ const TraceConst &trace_const(const double *lds)
+{
+#if DRT_TRACE_CONST == 2
+    uint32_t off = 0;
+    asm volatile("" : "+s"(off));
+    return *(const TraceConst *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+#else
+    uint32_t off = 0;
+    asm volatile("" : "+v"(off));
+    return *(const TraceConst *)((const char *)lds + off);
+#endif
+}
 #define DRT_TRACE_TAIL_MAX 8u /* tail wavelengths the trace kernel carries at most (the launcher's rule: S mod 64 <= 8) */
 #ifndef DRT_TRACE_WAVES_PER_SIMD
 #define DRT_TRACE_WAVES_PER_SIMD 3 /* register budget: launch_bounds' 2nd argument is waves per SIMD */
@@ -928,19 +1023,44 @@ __device__ unsigned int drt_branch_waves_done;
 #endif
 
 template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
-__global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene sc, DevCamera cam, TraceParams tp,
+__global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
                                                                  uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
-                                                                 int32_t *__restrict__ hits, unsigned long long *__restrict__ counters,
-                                                                 unsigned long long *__restrict__ work_counter)
+                                                                 int32_t *__restrict__ k_hits, unsigned long long *__restrict__ k_counters,
+                                                                 unsigned long long *__restrict__ k_work_counter)
 {
     extern __shared__ double lds_raw[];
+    /* the k_ arguments are read in this prologue only (see TraceConst): the loop reads LC, or the locals made here */
+#if DRT_TRACE_CONST == 1
+    if (threadIdx.x == 0)
+    {
+        TraceConst *c = (TraceConst *)lds_raw;
+        c->sc = k_sc;
+        c->cam = k_cam;
+        c->tp = k_tp;
+        c->hits = k_hits;
+        c->counters = k_counters;
+        c->work_counter = k_work_counter;
+    }
+#endif
+#if DRT_TRACE_CONST == 0
+    const TraceConst k_all = {k_sc, k_cam, k_tp, records, headers, k_hits, k_counters, k_work_counter};
+#define LC k_all
+#else
+#define LC trace_const(lds_raw)
+#endif
     SceneView sv;
+    double *l_spd_tail = nullptr, *tail_state = nullptr;
+    uint32_t TR, max_depth, vertex_words, block_words;
+    bool tail_on, record_hits;
+    {
+    const DevScene &sc = k_sc;
+    const TraceParams &tp = k_tp;
     sv.n_surf = sc.n_surf;
     sv.n_lights = sc.n_lights;
     if (SCENE_IN_LDS)
     {
         /* stage the SoA scene: coalesced HBM reads, one pass per table */
-        double *l_rows = lds_raw;
+        double *l_rows = lds_raw + TRACE_CONST_BYTES / 8;
         double *l_surf = l_rows + (size_t)SR_STRIDE * sc.n_surf;
         for (uint32_t k = threadIdx.x; k < SR_STRIDE * sc.n_surf; k += TRACE_BLOCK)
         {
@@ -989,6 +1109,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         sv.mats = sc.mats;
         sv.bvh_nodes = sc.bvh_nodes;
         sv.bvh_leaf = sc.bvh_leaf;
+        __syncthreads(); /* the launch constants */
     }
 
     /*
@@ -1004,9 +1125,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
      * out of LDS with one light and a tail of at most 8 wavelengths (DRT_TRACE_TAIL=0 turns it off, the parity tests' A/B).
      * Same operations in the same order as drt_shade_kernel's (src/daily_ray_trace.c:440-472, :615).
      */
-    const uint32_t TR = tp.tail_count;
-    const bool tail_on = TAIL && SCENE_IN_LDS && tp.tail_stage != nullptr; /* TAIL: an instantiation of its own, so that scenes that cannot use it run the kernel without any of this */
-    double *l_spd_tail = nullptr, *tail_state = nullptr;
+    TR = tp.tail_count;
+    tail_on = TAIL && SCENE_IN_LDS && tp.tail_stage != nullptr; /* TAIL: an instantiation of its own, so that scenes that cannot use it run the kernel without any of this */
     if (tail_on)
     {
         l_spd_tail = (double *)(sv.mats + sc.n_mat); /* behind the LDS copy of the materials, the last of the scene's tables */
@@ -1014,12 +1134,20 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         tail_state = l_spd_tail + (size_t)tp.n_spd * TR + (size_t)(threadIdx.x >> 6) * (2u * TR * 64u) + (threadIdx.x & 63u);
         __syncthreads();
     }
+    /* what every iteration reads, in scalar registers */
+    max_depth = tp.max_depth;
+    vertex_words = tp.vertex_words;
+    block_words = tp.block_words;
+    record_hits = tp.record_hits != 0u;
+    if (*tp.overflow) return; /* an earlier launch ran out of record blocks: the host renders from there again */
+    }
+    /* ---- from here on no k_ argument: a single use of one in the loop brings its scalar register, and the spill, back ---- */
     bool tail_ok = false; /* per lane: the path's tail wavelengths are being carried here */
     const uint32_t lane = threadIdx.x & 63u;
     /* per-wave work queue: a wave draws chunks of consecutive path ids from the global counter and
      * deals them to its idle lanes by ballot + prefix count */
-    const uint64_t CHUNK = tp.chunk;
     uint64_t chunk_next = 0, chunk_end = 0; /* wave-uniform */
+    PathPos chunk_pos = {0, 0};             /* wave-uniform: pixel and sample of path id chunk_next */
 
     uint32_t n_scans = 0, n_shaded = 0, n_shadow = 0, n_draws = 0, n_paths = 0;
 #ifdef DRT_BRANCH_STATS
@@ -1029,7 +1157,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
     /* per-lane path state */
     bool alive = false;
     bool exhausted = false; /* wave-uniform: no more work to draw */
-    uint64_t pid = 0, rs = 1, hit_row = 0; /* hit_row: the path's row in the hit log, ordered (sample, pixel) */
+    uint64_t rs = 1, hit_row = 0; /* hit_row: the path's row in the hit log, ordered (sample, pixel) */
     uint32_t depth = 0, shaded = 0;
     uint32_t vis0_mask = 0;    /* bit v: light 0 is visible from shaded vertex v (< 8); header bits 24-31 */
     uint32_t plastic_mask = 0; /* bit v: shaded vertex v (< 16) has the two-lobe plastic list; header bits 48-63, read by the shade kernel's tail pass */
@@ -1038,7 +1166,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
     uint32_t blk = 0, tbl = 0;              /* the pool block of the current four vertices; the path's table block (deep paths) */
     uint32_t spare = ~0u, spare_tbl = ~0u; /* a block (and, for deep paths, a table block) held ready: see path_spare_block */
     WavePool wp = {0u, 0u, 0u};
-    if (*tp.overflow) return; /* an earlier launch ran out of record blocks: the host renders from there again */
 
     for (;;)
     {
@@ -1049,19 +1176,21 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
             uint32_t want = (uint32_t)__popcll(idle_mask);
             uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull)); /* prefix count among idle lanes */
             uint64_t avail = chunk_end - chunk_next;
+            const uint32_t n_samples = LC.tp.n_samples;
+            /* a lane that starts a path takes the id `ahead` places after the one `from` stands for */
+            PathPos from = chunk_pos;
+            uint32_t ahead = rank;
             if (avail < want)
             {
                 /* hand out what is left of the chunk first, then draw a new chunk */
-                if (!alive && rank < avail)
-                {
-                    pid = chunk_next + rank;
-                    alive = true;
-                }
+                if (!alive && rank < avail) alive = true; /* id chunk_next + rank */
                 uint32_t taken = (uint32_t)avail;
+                const TraceConst &c = LC;
+                const uint64_t CHUNK = c.tp.chunk, n_paths_all = c.tp.n_paths;
                 unsigned long long base = 0;
-                if (lane == 0) base = atomicAdd(work_counter, (unsigned long long)CHUNK);
+                if (lane == 0) base = atomicAdd(c.work_counter, (unsigned long long)CHUNK);
                 base = __shfl(base, 0);
-                if (base >= tp.n_paths)
+                if (base >= n_paths_all)
                 {
                     exhausted = true;
                     chunk_next = chunk_end = 0;
@@ -1069,46 +1198,45 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 else
                 {
                     chunk_next = base;
-                    chunk_end = (base + CHUNK < tp.n_paths) ? base + CHUNK : tp.n_paths;
+                    chunk_end = (base + CHUNK < n_paths_all) ? base + CHUNK : n_paths_all;
+                    chunk_pos = path_pos_of_id(base, n_samples); /* the one 64-bit division: per draw, not per path */
                     uint64_t avail2 = chunk_end - chunk_next;
-                    bool fresh = false;
                     if (!alive && rank >= taken && (uint64_t)(rank - taken) < avail2)
                     {
-                        pid = chunk_next + (rank - taken);
-                        alive = true;
-                        fresh = true;
+                        alive = true; /* id chunk_next + (rank - taken) */
+                        from = chunk_pos;
+                        ahead = rank - taken;
                     }
                     uint32_t used = (want - taken < avail2) ? (want - taken) : (uint32_t)avail2;
                     chunk_next += used;
-                    (void)fresh;
+                    chunk_pos = path_pos_step(chunk_pos, used, n_samples);
                 }
                 /* lanes that got a path in either step start it below */
             }
             else
             {
-                if (!alive)
-                {
-                    pid = chunk_next + rank;
-                    alive = true;
-                }
+                if (!alive) alive = true; /* id chunk_next + rank */
                 chunk_next += want;
+                chunk_pos = path_pos_step(chunk_pos, want, n_samples);
             }
             /* start the newly assigned paths: lanes that were idle in idle_mask and are alive now */
             bool started = alive && ((idle_mask >> lane) & 1ull);
             if (started)
             {
-                uint64_t q = pid / tp.n_samples; /* consecutive ids: the samples of one pixel */
-                uint64_t s_local = pid - q * tp.n_samples;
-                hit_row = s_local * tp.n_pix + q;
-                const uint64_t t = LIST ? (uint64_t)tp.pixel_list[q] : q; /* the tile pixel */
-                uint32_t j = (uint32_t)(t / tp.tile_w);
-                uint32_t i = (uint32_t)(t - (uint64_t)j * tp.tile_w);
-                uint32_t x = tp.x0 + i;
-                uint32_t y = tp.y0 + j * tp.row_stride;
-                uint32_t sample = tp.first_sample + (uint32_t)s_local;
-                uint64_t key = tp.seed + (((uint64_t)sample * (uint64_t)tp.height + (uint64_t)y) * (uint64_t)tp.width + (uint64_t)x);
+                const TraceConst &c = LC;
+                const PathPos me = path_pos_step(from, ahead, n_samples);
+                const uint64_t q = me.q; /* consecutive ids: the samples of one pixel */
+                const uint64_t s_local = me.s;
+                if (record_hits) hit_row = s_local * c.tp.n_pix + q;
+                const uint64_t t = LIST ? (uint64_t)c.tp.pixel_list[q] : q; /* the tile pixel */
+                uint32_t i, j;
+                tile_pixel_ij(t, c.tp.tile_w, i, j);
+                uint32_t x = c.tp.x0 + i;
+                uint32_t y = c.tp.y0 + j * c.tp.row_stride;
+                uint32_t sample = c.tp.first_sample + (uint32_t)s_local;
+                uint64_t key = c.tp.seed + (((uint64_t)sample * (uint64_t)c.tp.height + (uint64_t)y) * (uint64_t)c.tp.width + (uint64_t)x);
                 rs = drt_splitmix64(key);
-                camera_ray(cam, tp.pixel_scheme, x, y, rs, n_draws, ro, rd);
+                camera_ray(c.cam, c.tp.pixel_scheme, x, y, rs, n_draws, ro, rd);
                 depth = 0;
                 shaded = 0;
                 plastic_mask = 0;
@@ -1116,30 +1244,31 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 tail_ok = tail_on;
                 if (tail_on)
                 {
+                    const uint32_t tr = pinned_scalar(TR);
 #pragma unroll
                     for (uint32_t j = 0; j < DRT_TRACE_TAIL_MAX; j += 1)
                     {
-                        if (j >= TR) break;
+                        if (j >= tr) break;
                         tail_state[(2u * j) * 64u] = 1.0;      /* throughput, const_spectrum(throughput, 1.0), :440 */
                         tail_state[(2u * j + 1u) * 64u] = 0.0; /* dst */
                     }
                 }
-                uint64_t slot = q * (uint64_t)tp.batch + s_local;
+                uint64_t slot = q * (uint64_t)c.tp.batch + s_local;
                 hdr = headers + slot * REC_HEADER_WORDS;
                 /* vignette: dot(ray_direction, forward) of the PRIMARY ray, src/daily_ray_trace.c:614 */
-                hdr[1] = (uint64_t)__double_as_longlong(v_dot(rd, cam.forward) * 1.0);
+                hdr[1] = (uint64_t)__double_as_longlong(v_dot(rd, c.cam.forward) * 1.0);
                 n_paths += 1;
-                if (tp.record_hits)
+                if (record_hits)
                 {
-                    int32_t *h = hits + ((uint64_t)tp.hits_sample_offset * tp.n_pix + hit_row) * tp.max_depth;
-                    for (uint32_t d = 0; d < tp.max_depth; d += 1) h[d] = -2;
+                    int32_t *h = c.hits + ((uint64_t)c.tp.hits_sample_offset * c.tp.n_pix + hit_row) * max_depth;
+                    for (uint32_t d = 0; d < max_depth; d += 1) h[d] = -2;
                 }
             }
         }
         if (!__any(alive)) break;
 
         /* a spare record block for the lanes whose path may open one at this iteration's vertex (the whole wave takes part) */
-        if (!path_spare_block(tp, wp, alive, shaded, spare, spare_tbl, lane))
+        if (!path_spare_block(LC.tp, wp, alive, shaded, spare, spare_tbl, lane))
         {
             hdr[0] = (uint64_t)HDR_TERM_NOT_DONE << 16;
             alive = false;
@@ -1148,9 +1277,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         {
             /* ---- one iteration of cast_ray's loop, src/daily_ray_trace.c:446-474 ---- */
             HitPoint ip;
-            find_ray_intersection<SCENE_IN_LDS>(sv, sc, ip, ro, rd);
+            find_ray_intersection<SCENE_IN_LDS>(sv, LC.sc, ip, ro, rd);
             n_scans += 1;
-            if (tp.record_hits) hits[((uint64_t)tp.hits_sample_offset * tp.n_pix + hit_row) * tp.max_depth + depth] = ip.index;
+            if (record_hits)
+            {
+                const TraceConst &c = LC;
+                c.hits[((uint64_t)c.tp.hits_sample_offset * c.tp.n_pix + hit_row) * max_depth + depth] = ip.index;
+            }
             const DevMaterial &mat = sv.mats[ip.surface_mat];
             bool terminal = false;
             uint32_t term = 0, term_spd = 0;
@@ -1163,12 +1296,12 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
             }
             else
             {
-                path_open_vertex(tp, wp, records, shaded, hdr, blk, tbl, spare, spare_tbl);
-                uint64_t *vrec = records + (uint64_t)blk * tp.block_words + (uint64_t)(shaded & (REC_BLOCK_VERTICES - 1u)) * tp.vertex_words;
+                path_open_vertex(LC.tp, wp, records, shaded, hdr, blk, tbl, spare, spare_tbl);
+                uint64_t *vrec = records + (uint64_t)blk * block_words + (uint64_t)(shaded & (REC_BLOCK_VERTICES - 1u)) * vertex_words;
                 /* the vertex's mirror and refracted directions, shared by the lights' evaluations, the sampler and the continuation's
                  * evaluation. Computed before the light loop, so they are live across the shadow scans (after the first scan instead:
                  * more scratch) */
-                const VertexDirs vd = vertex_dirs(sc, sv, ip);
+                const VertexDirs vd = vertex_dirs(LC.sc, sv, ip);
                 /* direct_light_contribution, :272-332 -- light samples are drawn before the shadow test */
                 n_shaded += 1;
                 bool t_vis = false; /* light 0 as the tail arithmetic below wants it (the kernel carries tails only in one-light scenes) */
@@ -1230,7 +1363,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
 #ifdef DRT_BRANCH_STATS
                 const uint32_t draws_before = n_draws;
 #endif
-                sample_direction(sc, sv, ip, vd, rs, n_draws, in, dir_pdf);
+                sample_direction(LC.sc, sv, ip, vd, rs, n_draws, in, dir_pdf);
                 EvalCoef e = eval_coefficients(sv, ip, vd, in);
 #ifdef DRT_BRANCH_STATS
                 {
@@ -1278,10 +1411,11 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                         const double *row_e = l_spd_tail + t_em * TR;
                         /* (a constant trip count, so that the compiler unrolls: the wavelengths' chains of dependent f64 operations then
                          *  run side by side instead of one after the other) */
+                        const uint32_t tr = pinned_scalar(TR);
 #pragma unroll
                         for (uint32_t j = 0; j < DRT_TRACE_TAIL_MAX; j += 1)
                         {
-                            if (j >= TR) break;
+                            if (j >= tr) break;
                             const double diffuse_pi = row_d[j], glossy = row_g[j];
                             double throughput = tail_state[(2u * j) * 64u], dst = tail_state[(2u * j + 1u) * 64u];
                             double contribution = 0.0;
@@ -1308,10 +1442,11 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                          * (src/bdsf.c:121-132) -- as bdsf_at_wavelength() in drt_shade_kernel */
                         const double *row_m = l_spd_tail + ((uint32_t)mat.mirror_spd & 0xFFFFu) * TR;
                         const double *row_e = l_spd_tail + t_em * TR;
+                        const uint32_t tr = pinned_scalar(TR);
 #pragma unroll
                         for (uint32_t j = 0; j < DRT_TRACE_TAIL_MAX; j += 1)
                         {
-                            if (j >= TR) break;
+                            if (j >= tr) break;
                             const double mirror = row_m[j];
                             double throughput = tail_state[(2u * j) * 64u], dst = tail_state[(2u * j + 1u) * 64u];
                             double contribution = 0.0;
@@ -1337,7 +1472,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 vrec[0] = mat.bdsf_packed;
                 vrec[1] = (uint64_t)mat.num_bdsfs | ((uint64_t)(e.flags | mat.vertex_flags) << 8) | ((uint64_t)((uint32_t)mat.diffuse_spd & 0xFFFFu) << 16) |
                           ((uint64_t)((uint32_t)mat.glossy_spd & 0xFFFFu) << 32) | ((uint64_t)((uint32_t)mat.mirror_spd & 0xFFFFu) << 48);
-                vrec[2] = record_media_word(sc, sv, ip);
+                vrec[2] = record_media_word(LC.sc, sv, ip);
                 vrec[3] = (uint64_t)__double_as_longlong(ip.on_dot);
                 vrec[4] = (uint64_t)__double_as_longlong(dir_pdf);
                 store_coef(vrec + 5, e);
@@ -1347,19 +1482,20 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 ro = ip.position;
             }
             depth += 1;
-            if (terminal || depth >= tp.max_depth)
+            if (terminal || depth >= max_depth)
             {
                 uint32_t staged = 0;
                 if (tail_ok)
                 {
                     /* the sample's value at the tail wavelengths: emission of what the path ended on, vignette (:452-457, :615) */
                     const double vignette = __longlong_as_double((long long)hdr[1]);
-                    double *st = tp.tail_stage + (uint64_t)(hdr - headers) / REC_HEADER_WORDS * TR;
+                    double *st = LC.tp.tail_stage + (uint64_t)(hdr - headers) / REC_HEADER_WORDS * TR;
                     const double *row_t = l_spd_tail + (term_spd & 0xFFFFu) * TR;
+                    const uint32_t tr = pinned_scalar(TR);
 #pragma unroll
                     for (uint32_t j = 0; j < DRT_TRACE_TAIL_MAX; j += 1)
                     {
-                        if (j >= TR) break;
+                        if (j >= tr) break;
                         double dst = tail_state[(2u * j + 1u) * 64u];
                         if (term == 1) dst = dst + tail_state[(2u * j) * 64u] * row_t[j];
                         st[j] = dst * vignette;
@@ -1374,6 +1510,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
 
     /* statistics: wave reduction, one atomic per wave and counter */
     uint64_t vals[6] = {n_paths, n_scans, n_shaded, n_shadow, n_draws, wp.taken};
+    unsigned long long *counters = LC.counters;
     for (int k = 0; k < 6; k += 1)
     {
         uint64_t v = vals[k];
@@ -1398,6 +1535,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         drt_branch_waves_done = 0u;
     }
 #endif
+#undef LC
 }
 
 /* ---------------------------------------------------------------------------------------------- */
@@ -2515,6 +2653,34 @@ __global__ void drt_xyz_finish_kernel(DevScene sc, uint32_t cmf_rw, uint32_t cmf
     n *= interval;
     const double *f = film + p * (uint64_t)XYZ_FILM_WORDS;
     for (int c = 0; c < 3; c += 1) xyz[3 * p + c] = ((f[c] + f[4 + c]) / f[3]) * (interval / n);
+}
+
+/* Path-id self-test (see drt_selftest_path_ids in include/drt_hip.h): a wave per draw. It walks `total` consecutive ids from
+ * bases[draw] as the trace kernel's refill does -- the base by path_pos_of_id, steps[k] ids handed to the first lanes by
+ * path_pos_step, the wave's position moved on by the same -- and writes (pixel, sample, i, j) per id. */
+__global__ void drt_path_id_kernel(const uint64_t *__restrict__ bases, const uint32_t *__restrict__ steps, uint32_t n_steps, uint32_t total,
+                                   uint32_t n_samples, uint32_t tile_w, uint64_t *__restrict__ out)
+{
+    const uint32_t lane = threadIdx.x;
+    PathPos pos = path_pos_of_id(bases[blockIdx.x], n_samples);
+    uint32_t next = 0;
+    for (uint32_t k = 0; k < n_steps; k += 1)
+    {
+        const uint32_t n = steps[k]; /* 1..64, their sum == total: checked by the host */
+        if (lane < n)
+        {
+            const PathPos me = path_pos_step(pos, lane, n_samples);
+            uint32_t i, j;
+            tile_pixel_ij(me.q, tile_w, i, j);
+            uint64_t *o = out + ((uint64_t)blockIdx.x * total + next + lane) * 4u;
+            o[0] = me.q;
+            o[1] = me.s;
+            o[2] = i;
+            o[3] = j;
+        }
+        pos = path_pos_step(pos, n, n_samples);
+        next += n;
+    }
 }
 
 /* arithmetic self-test (see drt_selftest_arith in include/drt_hip.h) */

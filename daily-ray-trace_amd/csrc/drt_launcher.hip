@@ -121,7 +121,8 @@ struct drt_context
 
 static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat)
 {
-    size_t b = (size_t)(SR_STRIDE + SF_COUNT) * n_surf * 8 + (size_t)LF_COUNT * n_lights * 8;
+    size_t b = TRACE_CONST_BYTES; /* the launch constants, in front (DRT_TRACE_CONST == 1 only) */
+    b += (size_t)(SR_STRIDE + SF_COUNT) * n_surf * 8 + (size_t)LF_COUNT * n_lights * 8;
     b += ((size_t)(2 * n_surf + 2 * n_lights) * 4 + 7) & ~(size_t)7;
     b += (size_t)n_mat * sizeof(DevMaterial);
     return b;
@@ -2224,6 +2225,37 @@ extern "C" int drt_render_tile_multi(const drt_scene *scene, const drt_camera *c
     } while (0);
     drt_group_destroy(g);
     return rc;
+}
+
+extern "C" int drt_selftest_path_ids(int device, const uint64_t *bases, uint32_t n_draws, const uint32_t *steps, uint32_t n_steps, uint32_t n_samples,
+                                     uint32_t tile_w, uint64_t *out)
+{
+    g_last_error.clear();
+    if (!bases || !steps || !out || n_draws == 0 || n_steps == 0 || n_samples == 0 || tile_w == 0) return fail(-1, "drt_selftest_path_ids: empty argument");
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n_steps; k += 1)
+    {
+        if (steps[k] == 0 || steps[k] > 64) return fail(-1, "drt_selftest_path_ids: step %u is %u, not in 1..64", k, steps[k]);
+        total += steps[k];
+    }
+    if (total > (1u << 20) || total * n_draws > (1u << 24)) return fail(-1, "drt_selftest_path_ids: too many ids");
+    HIP_TRY(hipSetDevice(device));
+    uint64_t *d_bases = nullptr, *d_out = nullptr;
+    uint32_t *d_steps = nullptr;
+    const size_t out_bytes = (size_t)total * n_draws * 4 * 8;
+    HIP_TRY(hipMalloc((void **)&d_bases, (size_t)n_draws * 8));
+    HIP_TRY(hipMalloc((void **)&d_steps, (size_t)n_steps * 4));
+    HIP_TRY(hipMalloc((void **)&d_out, out_bytes));
+    HIP_TRY(hipMemcpy(d_bases, bases, (size_t)n_draws * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_steps, steps, (size_t)n_steps * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(drt_path_id_kernel, dim3(n_draws), dim3(64), 0, 0, d_bases, d_steps, n_steps, (uint32_t)total, n_samples, tile_w, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    (void)hipFree(d_bases);
+    (void)hipFree(d_steps);
+    (void)hipFree(d_out);
+    return 0;
 }
 
 extern "C" int drt_selftest_arith(int device, int op, const double *a, const double *b, double *out, uint64_t n)

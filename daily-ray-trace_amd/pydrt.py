@@ -348,6 +348,9 @@ def hip_lib():
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
         L.drt_selftest_arith.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(C.c_double), C.c_uint64]
+        if hasattr(L, "drt_selftest_path_ids"):  # (an older build named by DRT_HIP_LIB for an A/B run has none; build() checks HIP_SYMBOLS)
+            L.drt_selftest_path_ids.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.POINTER(C.c_uint64)]
         L.drt_bvh_stats.argtypes = [C.POINTER(Scene)] + [C.POINTER(C.c_uint32)] * 4
         L.drt_selftest_unit.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                         C.c_uint64]
@@ -360,7 +363,7 @@ def hip_lib():
 HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy", "drt_bind_film", "drt_set_stream",
                "drt_render", "drt_synchronize", "drt_reset_film", "drt_film_device_ptrs", "drt_read_film", "drt_write_film",
                "drt_read_xyz", "drt_read_bgra", "drt_read_hit_indices", "drt_get_stats", "drt_batch_spp", "drt_render_tile", "drt_selftest_arith",
-               "drt_selftest_unit", "drt_selftest_material", "drt_bvh_stats",
+               "drt_selftest_unit", "drt_selftest_material", "drt_selftest_path_ids", "drt_bvh_stats",
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
@@ -561,6 +564,17 @@ def selftest_arith(op, a, b=None, device=0):
     out = np.empty(2 * n if op == 2 else n, dtype=np.float64)
     _check(hip_lib().drt_selftest_arith(device, op, _ptr(a, C.c_double), _ptr(b, C.c_double), _ptr(out, C.c_double), n),
            "drt_selftest_arith")
+    return out
+
+
+def selftest_path_ids(bases, steps, n_samples, tile_w, device=0):
+    """The trace kernel's path-id arithmetic on the device: for each base id, the ids base .. base + sum(steps) - 1 handed out
+    steps[k] at a time. Returns uint64 [len(bases)][sum(steps)][4]: pixel, sample, i, j (include/drt_hip.h)."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint64)
+    steps = np.ascontiguousarray(steps, dtype=np.uint32)
+    out = np.zeros((bases.size, int(steps.sum()), 4), dtype=np.uint64)
+    _check(hip_lib().drt_selftest_path_ids(device, _ptr(bases, C.c_uint64), bases.size, _ptr(steps, C.c_uint32), steps.size, n_samples,
+                                           tile_w, _ptr(out, C.c_uint64)), "drt_selftest_path_ids")
     return out
 
 

@@ -329,6 +329,13 @@ int drt_bvh_stats(const drt_scene *scene, uint32_t *nodes, uint32_t *leaf_surfac
  * 1 a/b, 2 sincos(a) -> out[2*i], out[2*i+1], 3 pow(a,b), 4 rng stream from key a (as u64 bits). */
 int drt_selftest_arith(int device, int op, const double *a, const double *b, double *out, uint64_t n);
 
+/* Path-id self-test: the trace kernel's decomposition of a path id into (launch pixel, sample in the launch) and of a tile pixel into
+ * (i, j), run the way its refill runs it. Each of the n_draws waves starts at path id bases[w] (one 64-bit division, as at a draw
+ * from the work counter) and hands out steps[0], steps[1], ... consecutive ids (each 1..64) by 32-bit arithmetic only. out holds four
+ * words per id, draw after draw: id / n_samples, id % n_samples, and (id / n_samples) % tile_w, (id / n_samples) / tile_w. */
+int drt_selftest_path_ids(int device, const uint64_t *bases, uint32_t n_draws, const uint32_t *steps, uint32_t n_steps, uint32_t n_samples,
+                          uint32_t tile_w, uint64_t *out);
+
 /* Device-function self-test: runs ONE of the path's device functions -- the very __device__ function the trace / shade
  * kernels call -- over n records (`in_stride` doubles in, `out_stride` doubles out per record), so that the edge cases of
  * the reference's functions (tangent / parallel / on-boundary rays, antiparallel rotation, disc centre, total internal

@@ -1,34 +1,165 @@
 #!/usr/bin/env python3
-"""Per-kernel register / scratch / occupancy figures of libdrt_hip.so's kernels, from hipcc's own resource remarks
-(-Rpass-analysis=kernel-resource-usage). Compiles csrc/drt_launcher.hip to an object in /tmp; extra arguments are passed on
-(e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring] [-D...]"""
+"""Per-kernel register / spill / scratch / occupancy figures of libdrt_hip.so's kernels, from the compiler's own output: the device
+assembly of csrc/drt_launcher.hip (the Makefile's flags plus -S -gline-tables-only) and the kernel metadata at its end. Extra
+arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring] [--loops] [-D...]
+
+Columns: VGPRs, SGPRs, `sspill` / `vspill` = the metadata's .sgpr_spill_count / .vgpr_spill_count, scratch bytes per lane, static
+LDS, occupancy (waves per SIMD, from the VGPR count), `valu` = vector ALU instructions in the kernel's text, `lanemv` = how many of
+them are SPILL LANE MOVES. On gfx9 a spilled scalar register is parked in a lane of a reserved vector register: v_writelane_b32
+stores it, v_readlane_b32 with a constant lane brings it back, and both issue in the vector pipe. Counted are every v_writelane_b32,
+and every v_readlane_b32 with a constant lane whose source is a register some v_writelane_b32 of the kernel writes (a kernel's own
+v_readlane with a variable lane, or on a register it never writes lanes of, is its algorithm and not a spill).
+--loops adds, per kernel, both counts by loop depth as the assembly's loop annotations nest the basic blocks."""
 import os
 import re
 import subprocess
 import sys
+import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "daily-ray-trace_amd")
-args = [a for a in sys.argv[1:] if a.startswith("-")]
-flt = [a for a in sys.argv[1:] if not a.startswith("-")]
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-std=c++17",
-       "-I" + os.path.join(REPO, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(PKG, "csrc", "drt_launcher.hip"),
-       "-o", "/tmp/drt_resources.o"] + args
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
-cur = None
-rows = {}
-for line in out.splitlines():
-    m = re.search(r"remark: +(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|TotalSGPRs|LDS Size \[bytes/block\]): (.*?) \[-Rpass", line)
-    if not m:
-        continue
-    k, v = m.group(1), m.group(2)
-    if k == "Function Name":
-        cur = subprocess.run(["c++filt", v], capture_output=True, text=True).stdout.strip().split("(")[0]
-        rows[cur] = {}
-    elif cur:
-        rows[cur][k.split(" ")[0]] = v
-print("%-60s %6s %6s %8s %6s %5s" % ("kernel", "VGPRs", "SGPRs", "scratch", "LDS", "occ"))
-for name, r in rows.items():
-    if flt and not any(f in name for f in flt):
-        continue
-    print("%-60s %6s %6s %8s %6s %5s" % (name[:60], r.get("VGPRs"), r.get("TotalSGPRs"), r.get("ScratchSize"), r.get("LDS"), r.get("Occupancy")))
+HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+# the Makefile's HIPFLAGS (warnings aside)
+FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-std=c++17", "-I" + os.path.join(REPO, "include")]
+
+# vector ALU mnemonics: v_* except the few that are not issued to the VALU
+_NOT_VALU = ("v_nop", "v_interp")
+
+
+def device_asm(extra=()):
+    """The gfx950 assembly of csrc/drt_launcher.hip as text."""
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "drt.s")
+        cmd = [HIPCC] + FLAGS + ["--cuda-device-only", "-S", "-gline-tables-only", os.path.join(PKG, "csrc", "drt_launcher.hip"), "-o", out] + list(extra)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])
+        return open(out, encoding="utf-8", errors="replace").read()
+
+
+def _demangle(names):
+    r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True)
+    plain = r.stdout.splitlines() if r.returncode == 0 else list(names)
+    return {m: p.split("(")[0].replace("void ", "") for m, p in zip(names, plain)}
+
+
+def _metadata(asm):
+    """{mangled name: {field: value}} from the .amdhsa.kernels list of the amdgpu_metadata block."""
+    kernels, cur = {}, None
+    start = asm.find("amdhsa.kernels:")
+    if start < 0:
+        return kernels
+    fields = {}
+    for line in asm[start:].splitlines()[1:]:
+        if line.startswith("amdhsa.") or line.startswith("..."):
+            break
+        m = re.match(r"^  - (\.\w+):\s*(.*)$", line)  # first key of a kernel's map
+        if m:
+            if fields.get(".name"):
+                kernels[fields[".name"]] = fields
+            fields = {m.group(1): m.group(2).strip()}
+            continue
+        m = re.match(r"^    (\.\w+):\s*(.*)$", line)
+        if m:
+            fields[m.group(1)] = m.group(2).strip().strip("'")
+    if fields.get(".name"):
+        kernels[fields[".name"]] = fields
+    return kernels
+
+
+def _body_stats(body):
+    """Vector-ALU instructions and spill lane moves of one kernel's text, in all and by loop depth."""
+    depth, hdr = 0, None
+    rows = []  # (depth, mnemonic, operands)
+    for line in body:
+        t = line.strip()
+        if re.match(r"^\.?LBB\d+_\d+:", t) or re.match(r"^; %bb\.\d+", t):
+            depth, hdr = 0, None  # a basic block: its loop annotations are on the label's line and the comment lines after it
+        if t.startswith(";") or t.startswith(".LBB"):
+            m = re.search(r"This (?:Inner )?Loop Header: Depth=(\d+)", t)
+            if m:
+                hdr = int(m.group(1))
+                depth = hdr
+            elif hdr is None:
+                m = re.search(r"in Loop: Header=\S+ Depth=(\d+)", t)
+                if m:
+                    depth = int(m.group(1))
+            continue
+        m = re.match(r"^(v_\w+)\s*(.*?)(?:\s*;.*)?$", t)
+        if m and not m.group(1).startswith(_NOT_VALU):
+            rows.append((depth, m.group(1), m.group(2)))
+    parked = set()
+    for _, op, args in rows:
+        if op == "v_writelane_b32":
+            parked.add(args.split(",")[0].strip())
+    valu, moves, writes, reads = {}, {}, 0, 0
+    for d, op, args in rows:
+        valu[d] = valu.get(d, 0) + 1
+        a = [x.strip() for x in args.split(",")]
+        spill = False
+        if op == "v_writelane_b32":
+            spill = True
+            writes += 1
+        elif op == "v_readlane_b32" and len(a) == 3 and a[1] in parked and re.fullmatch(r"\d+|0x[0-9a-fA-F]+", a[2]):
+            spill = True
+            reads += 1
+        if spill:
+            moves[d] = moves.get(d, 0) + 1
+    return {"valu": sum(valu.values()), "lane_moves": writes + reads, "lane_writes": writes, "lane_reads": reads,
+            "parked_in": sorted(parked, key=lambda r: int(r[1:]) if r[1:].isdigit() else 0),
+            "by_depth": {d: (valu[d], moves.get(d, 0)) for d in sorted(valu)}}
+
+
+def kernel_stats(extra=(), asm=None):
+    """{demangled kernel name: figures}; see the module's docstring for what they are."""
+    asm = asm if asm is not None else device_asm(extra)
+    meta = _metadata(asm)
+    lines = asm.splitlines()
+    names = _demangle(list(meta))
+    out = {}
+    label = {}
+    for n, l in enumerate(lines):
+        if l.startswith("_Z") or l.startswith("drt_"):
+            label.setdefault(l.split(":")[0], n)
+    for mangled, md in meta.items():
+        a = label.get(mangled)
+        if a is None:
+            continue
+        b = a
+        while b < len(lines) and not lines[b].startswith(".Lfunc_end") and ".amdhsa_kernel" not in lines[b]:
+            b += 1
+        body = lines[a + 1:b]
+        st = _body_stats(body)
+        occ = None
+        for l in lines[b:b + 400]:
+            m = re.search(r";\s*Occupancy:\s*(\d+)", l)
+            if m:
+                occ = int(m.group(1))
+                break
+        st.update({"vgprs": int(md.get(".vgpr_count", 0)), "sgprs": int(md.get(".sgpr_count", 0)),
+                   "sgpr_spill_count": int(md.get(".sgpr_spill_count", 0)), "vgpr_spill_count": int(md.get(".vgpr_spill_count", 0)),
+                   "scratch": int(md.get(".private_segment_fixed_size", 0)), "lds": int(md.get(".group_segment_fixed_size", 0)), "occupancy": occ})
+        out[names[mangled]] = st
+    return out
+
+
+def main(argv):
+    loops = "--loops" in argv
+    argv = [a for a in argv if a != "--loops"]
+    args = [a for a in argv if a.startswith("-")]
+    flt = [a for a in argv if not a.startswith("-")]
+    rows = kernel_stats(args)
+    print("%-60s %5s %5s %6s %6s %7s %6s %4s %6s %6s" % ("kernel", "VGPRs", "SGPRs", "sspill", "vspill", "scratch", "LDS", "occ", "valu", "lanemv"))
+    for name, r in rows.items():
+        if flt and not any(f in name for f in flt):
+            continue
+        print("%-60s %5d %5d %6d %6d %7d %6d %4s %6d %6d" % (name[:60], r["vgprs"], r["sgprs"], r["sgpr_spill_count"], r["vgpr_spill_count"], r["scratch"],
+                                                          r["lds"], r["occupancy"], r["valu"], r["lane_moves"]))
+        if loops:
+            print("    lane moves: %d v_writelane, %d v_readlane, parked in %s" % (r["lane_writes"], r["lane_reads"], " ".join(r["parked_in"]) or "-"))
+            for d, (v, m) in r["by_depth"].items():
+                print("    loop depth %d: %5d vector instructions, %4d spill lane moves" % (d, v, m))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
