@@ -8,6 +8,12 @@
  *   drt_converge_scan     one block: exclusive offsets of the blocks' kept entries, and the total (the next round's active count)
  *   drt_converge_scatter  the kept entries to list_out at block offset + wave offset + prefix count: ascending tile order stays
  * All three do nothing when the round's record pool ran out (the host renders those samples again and re-enqueues them).
+ *
+ * A pixel's count is its filter sum (the film's column S: +1.0 per sample), read where it is needed: the test uses c = the pixel's own
+ * count, and rerunning the kernels after a redone pair records the same counts again. drt_render_adaptive_continue starts from a film
+ * it did not render: drt_adopt_counts_kernel checks every tile pixel's filter sum and takes it as the count, the three kernels above
+ * test every pixel on the rows it holds, and drt_contract_kernel reduces the counts of the pixels that stay active to the three words
+ * the allotment contract is decided on.
  */
 #pragma once
 
@@ -22,7 +28,7 @@ struct ConvergeParams
 {
     const uint32_t *list_in; /* [n_in] tile pixels of the round; NULL: entry e is tile pixel e */
     uint32_t n_in;
-    uint32_t n, max_spp;     /* samples every listed pixel holds after this round; the cap */
+    uint32_t max_spp;        /* the cap (a listed pixel's count after this round is its filter sum) */
     uint32_t cmf_rw, cmf_y;  /* SPD rows of the white table and y-bar */
     double   interval, rel_error, floor;
     uint32_t *counts;        /* [tile pixels] samples per pixel */
@@ -31,7 +37,16 @@ struct ConvergeParams
     uint32_t *active;        /* the next round's active count */
     uint32_t *list_out;      /* [n_in at most] */
     const uint32_t *overflow;
+    const double *pixels;    /* the film's sums, [tile pixels][S + 1]: column S is the pixel's count */
+    uint32_t *at_max;        /* += listed pixels whose count is max_spp or more (each is listed for the last time then) */
 };
+
+/* words of the report drt_adopt_counts_kernel and drt_contract_kernel leave (the host presets BAD and MIN to 0xFFFFFFFF, the rest to 0) */
+#define ADOPT_BAD 0 /* the first tile pixel whose filter sum is not a whole number in [2, 2^32) */
+#define ADOPT_MIN 1 /* over the active list: the smallest count, */
+#define ADOPT_MAX 2 /* the largest, */
+#define ADOPT_REM 3 /* and whether some max_spp - count is not a multiple of step */
+#define ADOPT_WORDS 4
 
 /* the lanes of one wave agree on their LDS slab: every lane's writes come before any lane's reads that follow (LDS operations of one
  * wave run in order; the fence keeps the compiler from moving them across) */
@@ -67,7 +82,8 @@ __global__ __launch_bounds__(CONVERGE_BLOCK) void drt_converge_kernel(DevScene s
     double N = 0.0;
     for (uint32_t i = 0; i < S; i += 1) N += (cy[i] * rw[i]);
     N *= cp.interval;
-    const double c = (double)cp.n;
+    const double c = valid ? cp.pixels[(size_t)pixel * (S + 1) + S] : 2.0; /* the pixel's count: what its rows were averaged over */
+    const uint32_t n = (uint32_t)c;
     const double d = c * (c - 1.0);
     double Y = 0.0, E = 0.0;
     double *rows = s_rows[wave];
@@ -114,11 +130,13 @@ __global__ __launch_bounds__(CONVERGE_BLOCK) void drt_converge_kernel(DevScene s
     E = E * (cp.interval / N);
     const double aY = fabs(Y);
     const double m = aY >= cp.floor ? aY : cp.floor;
-    const bool keep = valid && cp.n < cp.max_spp && !(E <= cp.rel_error * m); /* a NaN stays */
-    if (valid) cp.counts[pixel] = cp.n;
+    const bool keep = valid && n < cp.max_spp && !(E <= cp.rel_error * m); /* a NaN stays */
+    if (valid) cp.counts[pixel] = n;
     const unsigned long long mask = __ballot(keep);
+    const unsigned long long full = __ballot(valid && n >= cp.max_spp);
     if (lane == 0)
     {
+        if (full) atomicAdd(cp.at_max, (uint32_t)__popcll(full));
         if (e < cp.n_in) cp.keep_mask[e / 64u] = mask;
         s_kept[wave] = (uint32_t)__popcll(mask);
     }
@@ -175,5 +193,46 @@ __global__ __launch_bounds__(CONVERGE_BLOCK) void drt_converge_scatter(ConvergeP
     {
         at += (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
         cp.list_out[at] = cp.list_in ? cp.list_in[e] : (uint32_t)e;
+    }
+}
+
+/* Every tile pixel's count from its filter sum; report[ADOPT_BAD] = the first pixel whose sum is no count (a count is a whole number in
+ * [2, 2^32): the variance needs two samples). One atomic per wave that holds such a pixel. */
+__global__ __launch_bounds__(CONVERGE_BLOCK) void drt_adopt_counts_kernel(const double *__restrict__ pixels, uint32_t S, uint32_t n_pix,
+                                                                          uint32_t *__restrict__ counts, uint32_t *report)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * CONVERGE_BLOCK + threadIdx.x;
+    const bool valid = p < n_pix;
+    const double f = valid ? pixels[(size_t)p * (S + 1) + S] : 2.0;
+    const bool ok = f >= 2.0 && f < 4294967296.0 && f == __builtin_floor(f); /* a NaN fails the first comparison */
+    if (valid) counts[p] = ok ? (uint32_t)f : 0u;
+    const unsigned long long bad = __ballot(valid && !ok);
+    if (bad && (threadIdx.x & 63u) == 0) atomicMin(report + ADOPT_BAD, (uint32_t)(p + (uint32_t)__builtin_ctzll(bad)));
+}
+
+/* The allotment contract's three words over the active list the convergence kernels have just written: wave reductions, then one
+ * atomic per word and wave. The list's length is read on the device (*n_active); the grid covers the longest list there can be. */
+__global__ __launch_bounds__(CONVERGE_BLOCK) void drt_contract_kernel(const uint32_t *__restrict__ list, const uint32_t *__restrict__ n_active,
+                                                                      const uint32_t *__restrict__ counts, uint32_t max_spp, uint32_t step,
+                                                                      uint32_t *report, const uint32_t *overflow)
+{
+    if (*overflow) return;
+    const uint64_t e = (uint64_t)blockIdx.x * CONVERGE_BLOCK + threadIdx.x;
+    const bool valid = e < *n_active;
+    const uint32_t n = valid ? counts[list[e]] : 0u;
+    uint32_t lo = valid ? n : 0xFFFFFFFFu, hi = valid ? n : 0u;
+    for (int off = 32; off > 0; off >>= 1)
+    {
+        const uint32_t l2 = (uint32_t)__shfl_xor((int)lo, off), h2 = (uint32_t)__shfl_xor((int)hi, off);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    const unsigned long long rem = __ballot(valid && (max_spp - n) % step != 0u); /* an active pixel has n < max_spp */
+    const unsigned long long any = __ballot(valid);
+    if ((threadIdx.x & 63u) == 0 && any)
+    {
+        atomicMin(report + ADOPT_MIN, lo);
+        atomicMax(report + ADOPT_MAX, hi);
+        if (rem) atomicOr(report + ADOPT_REM, 1u);
     }
 }

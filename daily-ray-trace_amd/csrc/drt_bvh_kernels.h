@@ -80,6 +80,7 @@ __device__ __forceinline__ PathStart path_start(const TraceParams &tp, uint64_t 
     ps.x = tp.x0 + i;
     ps.y = tp.y0 + j * tp.row_stride;
     ps.sample = tp.first_sample + (uint32_t)ps.s_local;
+    if (LIST) ps.sample += tp.sample_base[t];
     ps.slot = ps.q * (uint64_t)tp.batch + ps.s_local;
     return ps;
 }

@@ -185,8 +185,10 @@ struct TraceParams
     const double *spd_tail;              /* [n_spd][tail_count]: the SPD table's tail columns */
     uint32_t      tail_count, n_spd;
     /* adaptive rounds (the LIST instantiations only): launch pixel q is tile pixel pixel_list[q]; n_pix counts the list's entries.
-     * Headers, records, the hit log and tail_stage stay indexed by q */
+     * Headers, records, the hit log and tail_stage stay indexed by q. Tile pixel t's samples start at sample_base[t] (the count it holds
+     * before the round, [tile pixels]); first_sample is then the pair's offset inside the round */
     const uint32_t *pixel_list;
+    const uint32_t *sample_base;
 };
 
 /* A wave's share of the pool. Waves take POOL_CHUNK blocks at a time from the global cursor and hand them to their lanes by
@@ -1234,6 +1236,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 uint32_t x = c.tp.x0 + i;
                 uint32_t y = c.tp.y0 + j * c.tp.row_stride;
                 uint32_t sample = c.tp.first_sample + (uint32_t)s_local;
+                if (LIST) sample += c.tp.sample_base[t];
                 uint64_t key = c.tp.seed + (((uint64_t)sample * (uint64_t)c.tp.height + (uint64_t)y) * (uint64_t)c.tp.width + (uint64_t)x);
                 rs = drt_splitmix64(key);
                 camera_ray(c.cam, c.tp.pixel_scheme, x, y, rs, n_draws, ro, rd);
@@ -1574,7 +1577,8 @@ struct ShadeParams
     uint32_t tail_period_mains, pad1;  /* split queue with a tail: main-pass items between two tail items (<= main items per group) */
     uint32_t items_per_group, n_items; /* work items: per group of `chunk` pixels, ceil(chunk/sub_pixels) main-pass items and, with a tail,
                                           one tail-pass item; items_per_group == 1: one item does the group's main pass and then its tail */
-    const uint32_t *pixel_list;        /* the LIST instantiations: launch pixel q's film rows are tile pixel pixel_list[q]'s */
+    const uint32_t *pixel_list;        /* the LIST instantiations: launch pixel q's film rows are tile pixel pixel_list[q]'s, and its */
+    const uint32_t *sample_base;       /* first sample of this launch is sample_base[pixel_list[q]] + first_sample ([tile pixels]) */
 };
 
 __device__ __forceinline__ double word_as_double(uint64_t w) { return __longlong_as_double((long long)w); }
@@ -1965,12 +1969,13 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
     double *pv = XYZ ? nullptr : film_vars + pix_f * (uint64_t)S;
     const double *stage = sp.tail_stage + (pix_l * (uint64_t)sp.batch) * R + j;
     /* Phase B -- the film update (src/daily_ray_trace.c:732-743), the pixels' samples in order, all pixels in step */
+    const uint32_t first = LIST ? sp.first_sample + (act ? sp.sample_base[pix_f] : 0u) : sp.first_sample; /* per lane group */
     double f_sum = (act && !XYZ) ? px[lam] : 0.0, f_avg = (act && !XYZ) ? pa[lam] : 0.0, f_var = (act && !XYZ) ? pv[lam] : 0.0;
 #pragma unroll 4
     for (uint32_t k = 0; k < sp.n_samples; k += 1)
     {
         const double contribution = act ? stage[(uint64_t)k * R] : 0.0;
-        const double denom = (double)(sp.first_sample + k + 1);
+        const double denom = (double)(first + k + 1);
         f_sum = f_sum + contribution;
         if (!XYZ)
         {
@@ -2108,6 +2113,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
         double *px = film_pixels + pix_f * (uint64_t)(XYZ ? XYZ_FILM_WORDS : S + 1);
         double *pa = XYZ ? nullptr : film_avgs + pix_f * (uint64_t)S;
         double *pv = XYZ ? nullptr : film_vars + pix_f * (uint64_t)S;
+        const uint32_t first = LIST ? sp.first_sample + sp.sample_base[pix_f] : sp.first_sample; /* wave-uniform: one scalar per pixel */
         double f_sum[NSETS], f_avg[NSETS], f_var[NSETS];
 #pragma unroll
         for (int k = 0; k < NSETS; k += 1)
@@ -2475,7 +2481,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                     throughput[k] = throughput[k] * reflectance; /* :469 */
                 }
             }
-            const double denom = (double)(sp.first_sample + s0 + s + 1);
+            const double denom = (double)(first + s0 + s + 1);
             if (DARK) dark = false; /* (a sample that gets this far may leave something in the accumulators) */
 #pragma unroll
             for (int k = 0; k < NSETS; k += 1)

@@ -114,9 +114,11 @@ struct drt_context
     uint32_t *d_alist[2] = {nullptr, nullptr}; /* the round's active pixels and the next round's (ping-pong) */
     unsigned long long *d_keep = nullptr;  /* [ceil(n_pix / 64)] keep bits */
     uint32_t *d_bkeep = nullptr;           /* [blocks of drt_converge_kernel + 1]: per block, then the active count */
-    uint32_t *h_active = nullptr;          /* pinned host word the active count is copied to: the copy stays asynchronous, so the
-                                              devices of a group are all given their round before any is waited for */
-    struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true; uint64_t redone = 0; } ad;
+    uint32_t *d_ainfo = nullptr;           /* [1 + ADOPT_WORDS]: pixels at max_spp so far, then the report of the adoption kernels */
+    uint32_t *h_active = nullptr;          /* pinned host words the active count, then d_ainfo, are copied to: the copies stay asynchronous,
+                                              so the devices of a group are all given their round before any is waited for */
+    /* n: the count all active pixels hold (same); !same: they hold different counts, each max_spp - count a multiple of step */
+    struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
 static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat)
@@ -1194,6 +1196,7 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
     tp.seed = p.seed;
     tp.n_pix = list ? list_len : whole ? ctx->n_pix : (uint64_t)rows * p.tile_w; /* a list: its pixels, anywhere in the whole tile */
     tp.pixel_list = list;
+    tp.sample_base = list ? ctx->d_counts : nullptr;
     tp.n_paths = tp.n_pix * n;
     tp.vertex_words = ctx->vertex_words;
     tp.block_words = ctx->block_words;
@@ -1279,6 +1282,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     sp.light0_em_spd = ctx->light0_em_spd;
     sp.tail_staged = (ctx->tail_all_staged && ctx->d_tail_stage) ? 1u : 0u;
     sp.pixel_list = list;
+    sp.sample_base = list ? ctx->d_counts : nullptr;
     if (const char *e = getenv("DRT_DEBUG_SHADE_MODE")) sp.mode = (uint32_t)atoi(e); /* timing probe: 1 main pass only, 2 tail pass only */
     if (const char *e = getenv("DRT_DEBUG_TAIL_PHASE_A_OFF")) sp.tail_staged = (uint32_t)atoi(e) ? 1u : sp.tail_staged;
     sp.cmf_rw = ctx->cmf_rw; sp.cmf_x = ctx->cmf_x; sp.cmf_y = ctx->cmf_y; sp.cmf_z = ctx->cmf_z;
@@ -1643,17 +1647,19 @@ extern "C" uint32_t drt_batch_spp(drt_context *ctx) { return ctx ? ctx->batch_sp
 /*
  * Adaptive sampling ("Adaptive sampling"). Round 0 renders samples [0, min_spp) of every tile pixel through the dense
  * path; each later round renders the next min(step, max_spp - n) samples of the pixels still active, in kernel pairs over ranges of
- * the active list (the LIST instantiations). Every round ends with drt_converge_kernel (+ scan + scatter), which writes the counts
- * and the next list, and one 4-byte read of the active count. A pixel rendered over samples 0 .. n-1 in order holds, bit for bit,
+ * the active list (the LIST instantiations), every pixel from the count it holds (d_counts). Every round ends with drt_converge_kernel
+ * (+ scan + scatter), which takes the counts from the film's filter sums and writes the next list, and one read of two words: the
+ * active count and the pixels at max_spp so far. A pixel rendered over samples 0 .. n-1 in order holds, bit for bit,
  * the film a uniform n-sample render gives it.
  */
-static int adaptive_check(drt_context *ctx, const drt_adaptive *a)
+static int adaptive_check(drt_context *ctx, const drt_adaptive *a, bool held = false) /* held: drt_render_adaptive_continue, on the film as it is */
 {
     if (!ctx || !a) return fail(-1, "null argument");
     if (ctx->xyz_mode) return fail(-4, "adaptive sampling needs the spectral film (DRT_MODE_XYZ keeps no variance)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "adaptive sampling does not record hit indices (DRT_FLAG_RECORD_HITS)");
-    if (ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
-    if (ctx->film_used) return fail(-7, "adaptive sampling needs a film without samples: drt_reset_film first");
+    if (!held && ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
+    if (!held && ctx->film_used) return fail(-7, "adaptive sampling needs a film without samples: drt_reset_film first");
+    if (held && !ctx->adaptive_done && !ctx->film_used) return fail(-7, "the film holds no samples to continue from: drt_render_adaptive renders from the start");
     if (a->min_spp < 2) return fail(-1, "min_spp %u: at least 2 (the variance needs two samples)", a->min_spp);
     if (a->max_spp < a->min_spp) return fail(-1, "max_spp %u is below min_spp %u", a->max_spp, a->min_spp);
     if (a->step < 1) return fail(-1, "step must be at least 1");
@@ -1673,7 +1679,6 @@ static int enqueue_converge(drt_context *ctx)
     ConvergeParams cp{};
     cp.list_in = ad.first ? nullptr : ctx->d_alist[ad.cur];
     cp.n_in = ad.n_in;
-    cp.n = ad.n;
     cp.max_spp = ad.a.max_spp;
     cp.cmf_rw = ctx->cmf_rw;
     cp.cmf_y = ctx->cmf_y;
@@ -1684,8 +1689,10 @@ static int enqueue_converge(drt_context *ctx)
     cp.keep_mask = ctx->d_keep;
     cp.block_keep = ctx->d_bkeep;
     cp.active = ctx->d_bkeep + n_blocks;
-    cp.list_out = ctx->d_alist[ad.first ? 0 : ad.cur ^ 1];
+    cp.list_out = ctx->d_alist[ad.cur ^ 1];
     cp.overflow = (const uint32_t *)(ctx->d_counters + DRT_NUM_COUNTERS + 5);
+    cp.pixels = ctx->d_pixels;
+    cp.at_max = ctx->d_ainfo;
     hipLaunchKernelGGL(drt_converge_kernel, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, ctx->dsc, cp, ctx->d_avgs, ctx->d_vars);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(drt_converge_scan, dim3(1), dim3(CONVERGE_SCAN_BLOCK), 0, ctx->stream, cp, n_blocks);
@@ -1693,6 +1700,7 @@ static int enqueue_converge(drt_context *ctx)
     hipLaunchKernelGGL(drt_converge_scatter, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, cp);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ctx->h_active, cp.active, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_active + 1, ctx->d_ainfo, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     return 0;
 }
 
@@ -1703,8 +1711,9 @@ static void adaptive_free(drt_context *ctx)
     (void)hipFree(ctx->d_alist[1]);
     (void)hipFree(ctx->d_keep);
     (void)hipFree(ctx->d_bkeep);
+    (void)hipFree(ctx->d_ainfo);
     (void)hipHostFree(ctx->h_active);
-    ctx->d_counts = ctx->d_alist[0] = ctx->d_alist[1] = ctx->d_bkeep = ctx->h_active = nullptr;
+    ctx->d_counts = ctx->d_alist[0] = ctx->d_alist[1] = ctx->d_bkeep = ctx->d_ainfo = ctx->h_active = nullptr;
     ctx->d_keep = nullptr;
 }
 
@@ -1717,7 +1726,25 @@ static int adaptive_alloc(drt_context *ctx)
     HIP_TRY(hipMalloc((void **)&ctx->d_alist[1], n_pix * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&ctx->d_keep, (n_pix + 63) / 64 * sizeof(unsigned long long)));
     HIP_TRY(hipMalloc((void **)&ctx->d_bkeep, ((n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_active, sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipMalloc((void **)&ctx->d_ainfo, (1 + ADOPT_WORDS) * sizeof(uint32_t)));
+    HIP_TRY(hipHostMalloc((void **)&ctx->h_active, (2 + ADOPT_WORDS) * sizeof(uint32_t), hipHostMallocDefault));
+    return 0;
+}
+
+/* the buffers of an adaptive render; the count of pixels at max_spp starts from zero */
+static int adaptive_buffers(drt_context *ctx)
+{
+    if (!ctx->d_counts || !ctx->d_alist[0] || !ctx->d_alist[1] || !ctx->d_keep || !ctx->d_bkeep || !ctx->d_ainfo || !ctx->h_active)
+    {
+        /* all or none: a call that failed half way leaves no buffer behind that a later call would take for the whole set */
+        const int rc = adaptive_alloc(ctx);
+        if (rc) adaptive_free(ctx);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(ctx->d_ainfo, 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_ainfo + 1 + ADOPT_BAD, 0xFF, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_ainfo + 1 + ADOPT_MIN, 0xFF, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->d_ainfo + 1 + ADOPT_MAX, 0, 2 * sizeof(uint32_t), ctx->stream));
     return 0;
 }
 
@@ -1733,24 +1760,20 @@ static int adaptive_begin(drt_context *ctx, const drt_adaptive *a)
     ad.a.rounds = ad.a.pixels_at_max = 0;
     ad.a.paths = 0;
     const uint64_t n_pix = ctx->n_pix;
-    if (!ctx->d_counts || !ctx->d_alist[0] || !ctx->d_alist[1] || !ctx->d_keep || !ctx->d_bkeep || !ctx->h_active)
-    {
-        /* all or none: a call that failed half way leaves no buffer behind that a later call would take for the whole set */
-        const int rc = adaptive_alloc(ctx);
-        if (rc) adaptive_free(ctx);
-        if (rc) return rc;
-    }
+    int rc = adaptive_buffers(ctx);
+    if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_counts, 0, n_pix * sizeof(uint32_t), ctx->stream));
     ad.first = true;
+    ad.cur = 1; /* the first list goes to d_alist[0] */
     ad.n_in = (uint32_t)n_pix;
     ad.k = a->min_spp;
     ad.n = a->min_spp;
-    int rc = render_impl(ctx, 0, a->min_spp);
-    if (rc) return rc;
+    if ((rc = render_impl(ctx, 0, a->min_spp))) return rc;
     return enqueue_converge(ctx);
 }
 
-/* a later round: samples [n, n + k) of the ad.active pixels of list d_alist[cur], in kernel pairs over ranges of the list. A pair
+/* a later round: the next k samples of the ad.active pixels of list d_alist[cur] -- each from the count it holds, d_counts -- in kernel
+ * pairs over ranges of the list. k: min(step, max_spp - n) while all active pixels hold n samples, step otherwise (the contract). A pair
  * takes up to five eighths of the paths the record pool is sized for (the pixels still active are the ones with the long paths: a
  * pair that runs out anyway is rendered again by redo_batches), its pixels all the round's samples where they fit; pairs of equal size */
 static int adaptive_enqueue_round(drt_context *ctx)
@@ -1758,9 +1781,8 @@ static int adaptive_enqueue_round(drt_context *ctx)
     drt_context::Adaptive &ad = ctx->ad;
     ad.first = false;
     ad.n_in = ad.active;
-    ad.k = std::min(ad.a.step, ad.a.max_spp - ad.n);
-    const uint32_t first = ad.n;
-    ad.n += ad.k;
+    ad.k = ad.same ? std::min(ad.a.step, ad.a.max_spp - ad.n) : ad.a.step;
+    if (ad.same) ad.n += ad.k;
     const uint64_t budget = std::max<uint64_t>(1, ctx->n_pix * (uint64_t)ctx->batch_spp * 5 / 8);
     const uint32_t m_fit = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ad.k, budget), 4096);
     const uint32_t n_sp = (ad.k + m_fit - 1) / m_fit, m = (ad.k + n_sp - 1) / n_sp;   /* samples per pair */
@@ -1773,7 +1795,7 @@ static int adaptive_enqueue_round(drt_context *ctx)
         for (uint32_t at = 0; at < ad.k; at += m)
         {
             const uint32_t ns = std::min(m, ad.k - at);
-            int rc = enqueue_pair(ctx, first + at, ns, 0, 0, 0, ns, list + off, len);
+            int rc = enqueue_pair(ctx, at, ns, 0, 0, 0, ns, list + off, len);
             if (rc) return rc;
         }
     }
@@ -1797,9 +1819,8 @@ static int adaptive_finish_round(drt_context *ctx)
     ad.active = *ctx->h_active;
     ad.a.rounds += 1;
     ad.a.paths += (uint64_t)ad.n_in * (ad.first ? ad.a.min_spp : ad.k);
-    if (ad.n == ad.a.max_spp) ad.a.pixels_at_max += ad.n_in;
-    if (!ad.first) ad.cur ^= 1;
-    else ad.cur = 0;
+    ad.a.pixels_at_max = ctx->h_active[1];
+    ad.cur ^= 1;
     return 0;
 }
 
@@ -1831,6 +1852,150 @@ extern "C" int drt_render_adaptive(drt_context *ctx, drt_adaptive *a)
     a->rounds = ctx->ad.a.rounds;
     a->pixels_at_max = ctx->ad.a.pixels_at_max;
     a->paths = ctx->ad.a.paths;
+    return 0;
+}
+
+/*
+ * drt_render_adaptive_continue: adaptive sampling on the film the context holds. In three steps, so that a group takes each of them on
+ * all its devices before the next: continue_adopt (every tile pixel's count from its filter sum, checked), continue_test (every pixel
+ * tested on its own rows, the first active list, the contract's three words over it), continue_accept (the context becomes an adaptive
+ * render's; the rounds follow as in drt_render_adaptive). Until continue_accept nothing is rendered and no film bit changes, and a
+ * refusal puts the context's earlier list back (continue_refuse).
+ */
+struct ContinueReport { uint32_t active = 0, lo = 0xFFFFFFFFu, hi = 0, rem = 0; };
+
+static int continue_adopt(drt_context *ctx)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    (void)hipGetLastError();
+    int rc = drt_synchronize(ctx); /* the film complete: samples of an earlier drt_render that ran out of records are rendered again here */
+    if (rc) return rc;
+    if ((rc = adaptive_buffers(ctx))) return rc;
+    const uint32_t n_blocks = (uint32_t)((ctx->n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK);
+    hipLaunchKernelGGL(drt_adopt_counts_kernel, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, ctx->d_pixels, ctx->dsc.S,
+                       (uint32_t)ctx->n_pix, ctx->d_counts, ctx->d_ainfo + 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_active + 2, ctx->d_ainfo + 1, ADOPT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static int continue_test(drt_context *ctx, const drt_adaptive *a)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint32_t bad = ctx->h_active[2 + ADOPT_BAD];
+    if (bad != 0xFFFFFFFFu)
+    {
+        double f = 0.0;
+        HIP_TRY(hipMemcpy(&f, ctx->d_pixels + (size_t)bad * (ctx->dsc.S + 1) + ctx->dsc.S, sizeof(f), hipMemcpyDeviceToHost));
+        return fail(-7, "tile pixel %u (column %u, row %u of the tile) holds the filter sum %g: a sample count is a whole number from 2 to 2^32 - 1",
+                    bad, bad % ctx->params.tile_w, bad / ctx->params.tile_w, f);
+    }
+    drt_context::Adaptive &ad = ctx->ad;
+    const int cur = ctx->adaptive_done ? ad.cur : 1; /* the list an earlier call left stays where it is until this call is accepted */
+    ad.a = *a;
+    ad.a.rounds = ad.a.pixels_at_max = 0;
+    ad.a.paths = 0;
+    ad.cur = cur;
+    ad.first = true;
+    ad.n_in = (uint32_t)ctx->n_pix;
+    int rc = enqueue_converge(ctx);
+    if (rc) return rc;
+    const uint32_t n_blocks = (uint32_t)((ctx->n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK);
+    hipLaunchKernelGGL(drt_contract_kernel, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, ctx->d_alist[cur ^ 1], ctx->d_bkeep + n_blocks,
+                       ctx->d_counts, a->max_spp, a->step, ctx->d_ainfo + 1, (const uint32_t *)(ctx->d_counters + DRT_NUM_COUNTERS + 5));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_active + 2, ctx->d_ainfo + 1, ADOPT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static int continue_report(drt_context *ctx, ContinueReport *r)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    r->active += ctx->h_active[0];
+    r->lo = std::min(r->lo, ctx->h_active[2 + ADOPT_MIN]);
+    r->hi = std::max(r->hi, ctx->h_active[2 + ADOPT_MAX]);
+    r->rem |= ctx->h_active[2 + ADOPT_REM];
+    return 0;
+}
+
+/* the refusal's hint -- not on the way of a render, so on the host: the greatest common divisor of the active pixels' max_spp - count */
+static int continue_gcd(drt_context *ctx, uint32_t max_spp, uint32_t *g)
+{
+    const uint32_t n = ctx->h_active[0];
+    if (!n) return 0;
+    std::vector<uint32_t> counts(ctx->n_pix), list(n);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpy(counts.data(), ctx->d_counts, ctx->n_pix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(list.data(), ctx->d_alist[ctx->ad.cur ^ 1], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint32_t t : list)
+    {
+        uint32_t x = max_spp - counts[t], y = *g;
+        while (y) { const uint32_t r = x % y; x = y; y = r; }
+        *g = x;
+    }
+    return 0;
+}
+
+static int continue_refuse(const ContinueReport &r, const drt_adaptive *a, uint32_t g)
+{
+    std::string steps;
+    for (uint32_t d = 1; d <= g && steps.size() < 60; d += 1)
+        if (g % d == 0) steps += (steps.empty() ? "" : ", ") + std::to_string(d);
+    if (g > 1 && steps.size() >= 60) steps += ", ... (the divisors of " + std::to_string(g) + ")";
+    return fail(-7, "the %u active pixels hold from %u to %u samples and max_spp %u less the count is not a multiple of step %u for all of them: "
+                "a round renders the same number of samples of every active pixel, so step must be one of %s",
+                r.active, r.lo, r.hi, a->max_spp, a->step, steps.c_str());
+}
+
+static void continue_accept(drt_context *ctx, const ContinueReport &r)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    ctx->adaptive_done = true;
+    ad.active = ctx->h_active[0];
+    ad.a.pixels_at_max = ctx->h_active[1];
+    ad.cur ^= 1;
+    ad.first = false;
+    ad.same = r.lo == r.hi;
+    ad.n = r.lo;
+    ad.k = 0;
+}
+
+static bool continue_goes_on(const drt_context *ctx, uint32_t max_rounds)
+{
+    return ctx->ad.active > 0 && !(max_rounds && ctx->ad.a.rounds >= max_rounds);
+}
+
+extern "C" int drt_render_adaptive_continue(drt_context *ctx, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active)
+{
+    g_last_error.clear();
+    int rc = adaptive_check(ctx, a, true);
+    if (rc) return rc;
+    const drt_context::Adaptive before = ctx->ad;
+    ContinueReport r;
+    if ((rc = continue_adopt(ctx)) || (rc = continue_test(ctx, a)) || (rc = continue_report(ctx, &r)))
+    {
+        ctx->ad = before;
+        return rc;
+    }
+    if (r.active && r.lo != r.hi && r.rem)
+    {
+        uint32_t g = 0;
+        rc = continue_gcd(ctx, a->max_spp, &g);
+        ctx->ad = before;
+        return rc ? rc : continue_refuse(r, a, g);
+    }
+    continue_accept(ctx, r);
+    while (continue_goes_on(ctx, max_rounds))
+    {
+        if ((rc = adaptive_enqueue_round(ctx))) return rc;
+        if ((rc = adaptive_finish_round(ctx))) return rc;
+    }
+    a->rounds = ctx->ad.a.rounds;
+    a->pixels_at_max = ctx->ad.a.pixels_at_max;
+    a->paths = ctx->ad.a.paths;
+    if (still_active) *still_active = ctx->ad.active;
     return 0;
 }
 
@@ -2185,6 +2350,64 @@ extern "C" int drt_group_render_adaptive(drt_group *g, drt_adaptive *a)
             a->pixels_at_max += c->ad.a.pixels_at_max;
             a->paths += c->ad.a.paths;
         }
+    return 0;
+}
+
+/* parameters checked, films adopted and the contract decided over the whole tile on all devices before any device renders */
+extern "C" int drt_group_render_adaptive_continue(drt_group *g, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active)
+{
+    g_last_error.clear();
+    if (!g || !a) return fail(-1, "null argument");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = adaptive_check(c, a, true))) return rc;
+    std::vector<drt_context::Adaptive> before;
+    for (drt_context *c : g->ctx) before.push_back(c ? c->ad : drt_context::Adaptive{});
+    auto put_back = [&]() { for (size_t k = 0; k < g->ctx.size(); k += 1) if (g->ctx[k]) g->ctx[k]->ad = before[k]; };
+    ContinueReport r;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = continue_adopt(c))) { put_back(); return rc; }
+    for (drt_context *c : g->ctx)
+        if (c && (rc = continue_test(c, a))) { put_back(); return rc; }
+    for (drt_context *c : g->ctx)
+        if (c && (rc = continue_report(c, &r))) { put_back(); return rc; }
+    if (r.active && r.lo != r.hi && r.rem)
+    {
+        uint32_t d = 0;
+        for (drt_context *c : g->ctx)
+            if (c && !rc) rc = continue_gcd(c, a->max_spp, &d);
+        put_back();
+        return rc ? rc : continue_refuse(r, a, d);
+    }
+    for (drt_context *c : g->ctx)
+        if (c) continue_accept(c, r);
+    std::vector<char> running(g->ctx.size(), 0);
+    for (;;)
+    {
+        bool any = false;
+        for (size_t k = 0; k < g->ctx.size(); k += 1)
+        {
+            running[k] = g->ctx[k] && continue_goes_on(g->ctx[k], max_rounds);
+            if (running[k] && (rc = adaptive_enqueue_round(g->ctx[k]))) return rc;
+            any = any || running[k];
+        }
+        if (!any) break;
+        for (size_t k = 0; k < g->ctx.size(); k += 1)
+            if (running[k] && (rc = adaptive_finish_round(g->ctx[k]))) return rc;
+    }
+    a->rounds = 0;
+    a->pixels_at_max = 0;
+    a->paths = 0;
+    uint32_t left = 0;
+    for (drt_context *c : g->ctx)
+        if (c)
+        {
+            a->rounds = std::max(a->rounds, c->ad.a.rounds);
+            a->pixels_at_max += c->ad.a.pixels_at_max;
+            a->paths += c->ad.a.paths;
+            left += c->ad.active;
+        }
+    if (still_active) *still_active = left;
     return 0;
 }
 

@@ -17,6 +17,11 @@
  * first wavelength, interval), seed, max_cast_depth, pixel scheme and a hash of the scene file -- and with the files (headers,
  * sizes, filter sum of every pixel = the manifest's sample count, mean = sum / n on a spread of pixels); anything else
  * restarts from sample 0 with a message saying why.
+ *
+ * An ADAPTIVE render's checkpoint (drt_host_write_outputs_adaptive) is the same set under a version-3 manifest: version 2's fields,
+ * `samples` the largest count of any pixel, and one `adaptive` line with the parameters it was rendered with. Every pixel holds its
+ * own count, its filter sum. drt_host_load_checkpoint_adaptive accepts version 3 and version 2 (a uniform checkpoint is a valid
+ * start) and checks each pixel on its own count; the uniform loader accepts version 2 only.
  */
 #include "drt_host.h"
 
@@ -84,6 +89,7 @@ typedef struct
     unsigned version, samples, width, height, wavelengths, generation, max_depth, pixel_scheme;
     unsigned long long seed, scene;
     double min_wl, interval;
+    drt_host_adaptive_line adaptive; /* version 3 */
 } manifest;
 
 static int read_manifest(const char *mpath, manifest *m)
@@ -94,8 +100,12 @@ static int read_manifest(const char *mpath, manifest *m)
     int got = fscanf(mf, "drt-checkpoint %u samples %u width %u height %u wavelengths %u seed %llu generation %u max_depth %u pixel_scheme %u min_wl %lf interval %lf scene %llx",
                      &m->version, &m->samples, &m->width, &m->height, &m->wavelengths, &m->seed, &m->generation, &m->max_depth, &m->pixel_scheme,
                      &m->min_wl, &m->interval, &m->scene);
+    int line = 1;
+    if (got == 12 && m->version == 3)
+        line = fscanf(mf, " adaptive min_spp %u max_spp %u step %u rel_error %lf floor %lf", &m->adaptive.min_spp, &m->adaptive.max_spp,
+                      &m->adaptive.step, &m->adaptive.rel_error, &m->adaptive.floor) == 5;
     fclose(mf);
-    return (got == 12 && m->version == 2 && m->generation <= 1) ? 0 : -2;
+    return (got == 12 && line && (m->version == 2 || m->version == 3) && m->generation <= 1) ? 0 : -2;
 }
 
 /* one of the reference's outputs under its own name: a hard link to `same_as` when given and possible, else written out */
@@ -109,9 +119,9 @@ static int publish(const char *path, const char *same_as, u32 width, u32 height,
     return 0;
 }
 
-int drt_host_write_outputs(const config_arguments *config, u32 width, u32 height, u32 S, f64 min_wl, f64 interval,
-                           const f64 *dst_pixels, const f64 *dst_avgs, const f64 *dst_vars, int with_raw_variance,
-                           u32 samples_done, u64 seed)
+static int write_outputs(const config_arguments *config, u32 width, u32 height, u32 S, f64 min_wl, f64 interval,
+                         const f64 *dst_pixels, const f64 *dst_avgs, const f64 *dst_vars, int with_raw_variance,
+                         u32 samples_done, u64 seed, const drt_host_adaptive_line *adaptive)
 {
     g_ckpt_error[0] = 0;
     u64 num_pixels = (u64)width * height;
@@ -136,10 +146,13 @@ int drt_host_write_outputs(const config_arguments *config, u32 width, u32 height
         tmp_name(mtmp, sizeof(mtmp), mpath);
         FILE *f = fopen(mtmp, "w");
         if (!f) return refuse("could not write %s", mtmp);
-        int ok = fprintf(f, "drt-checkpoint 2\nsamples %u\nwidth %u\nheight %u\nwavelengths %u\nseed %llu\ngeneration %d\nmax_depth %u\npixel_scheme %u\n"
+        int ok = fprintf(f, "drt-checkpoint %d\nsamples %u\nwidth %u\nheight %u\nwavelengths %u\nseed %llu\ngeneration %d\nmax_depth %u\npixel_scheme %u\n"
                             "min_wl %.17g\ninterval %.17g\nscene %llx\n",
-                         samples_done, width, height, S, (unsigned long long)seed, g, config->max_cast_depth, (unsigned)config->pixel_scheme, min_wl, interval,
+                         adaptive ? 3 : 2, samples_done, width, height, S, (unsigned long long)seed, g, config->max_cast_depth, (unsigned)config->pixel_scheme, min_wl, interval,
                          (unsigned long long)scene_hash(config->input_scene)) > 0;
+        if (adaptive)
+            ok = fprintf(f, "adaptive min_spp %u max_spp %u step %u rel_error %.17g floor %.17g\n", adaptive->min_spp, adaptive->max_spp, adaptive->step,
+                         adaptive->rel_error, adaptive->floor) > 0 && ok;
         ok = (fflush(f) == 0) && ok;
         ok = (fsync(fileno(f)) == 0) && ok;
         ok = (fclose(f) == 0) && ok;
@@ -173,6 +186,25 @@ int drt_host_write_outputs(const config_arguments *config, u32 width, u32 height
     return 0;
 }
 
+int drt_host_write_outputs(const config_arguments *config, u32 width, u32 height, u32 S, f64 min_wl, f64 interval,
+                           const f64 *dst_pixels, const f64 *dst_avgs, const f64 *dst_vars, int with_raw_variance,
+                           u32 samples_done, u64 seed)
+{
+    return write_outputs(config, width, height, S, min_wl, interval, dst_pixels, dst_avgs, dst_vars, with_raw_variance, samples_done, seed, NULL);
+}
+
+int drt_host_write_outputs_adaptive(const config_arguments *config, u32 width, u32 height, u32 S, f64 min_wl, f64 interval,
+                                    const f64 *dst_pixels, const f64 *dst_avgs, const f64 *dst_vars, int with_raw_variance,
+                                    u64 seed, const drt_host_adaptive_line *adaptive)
+{
+    /* `samples`: the largest count */
+    f64 most = 0.0;
+    for (u64 px = 0; px < (u64)width * height; px += 1)
+        if (dst_pixels[px * (S + 1) + S] > most) most = dst_pixels[px * (S + 1) + S];
+    if (!(most < 4294967296.0)) return refuse("a pixel holds %g samples", most);
+    return write_outputs(config, width, height, S, min_wl, interval, dst_pixels, dst_avgs, dst_vars, with_raw_variance, (u32)most, seed, adaptive);
+}
+
 static long file_size(const char *path)
 {
     FILE *f = fopen(path, "rb");
@@ -183,8 +215,9 @@ static long file_size(const char *path)
     return n;
 }
 
-int drt_host_load_checkpoint(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
-                             f64 *dst_avgs, f64 *dst_vars, u32 *samples_done)
+/* adaptive: every pixel on its own count, from 2 to the job's num_pixel_samples, and a version-3 manifest is welcome */
+static int load_checkpoint(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
+                           f64 *dst_avgs, f64 *dst_vars, u32 *samples_done, int adaptive, drt_host_adaptive_line *line)
 {
     g_ckpt_error[0] = 0;
     *samples_done = 0;
@@ -193,7 +226,7 @@ int drt_host_load_checkpoint(const config_arguments *config, u32 width, u32 heig
     manifest m;
     int mrc = read_manifest(mpath, &m);
     if (mrc == -1) return refuse("no checkpoint manifest %s", mpath);
-    if (mrc) return refuse("%s is not a checkpoint manifest of this version", mpath);
+    if (mrc || (!adaptive && m.version != 2)) return refuse("%s is not a checkpoint manifest of this version", mpath);
     const u32 n = m.samples;
     if (m.width != width || m.height != height || m.wavelengths != S)
         return refuse("checkpoint is %ux%u with %u wavelengths, the job %ux%u with %u", m.width, m.height, m.wavelengths, width, height, S);
@@ -226,19 +259,42 @@ int drt_host_load_checkpoint(const config_arguments *config, u32 width, u32 heig
         free(px);
     }
     /* every pixel's filter sum is the sample count (the filter value is 1.0, src/daily_ray_trace.c:616) */
-    for (u64 px = 0; px < num_pixels; px += 1)
+    f64 most = 0.0;
+    for (u64 px = 0; px < num_pixels && adaptive; px += 1)
+    {
+        const f64 c = dst_pixels[px * (S + 1) + S];
+        if (!(c >= 2.0 && c <= (f64)config->num_pixel_samples && c == floor(c)))
+            return refuse("%s holds %g samples at pixel %llu: a whole number from 2 to num_pixel_samples (%u)", paths[0], c, (unsigned long long)px, config->num_pixel_samples);
+        if (c > most) most = c;
+    }
+    if (adaptive && most != (f64)n) return refuse("%s holds at most %g samples in a pixel, the manifest says %u", paths[0], most, n);
+    for (u64 px = 0; px < num_pixels && !adaptive; px += 1)
         if (dst_pixels[px * (S + 1) + S] != (f64)n) return refuse("%s holds %g samples at pixel %llu, the manifest says %u", paths[0], dst_pixels[px * (S + 1) + S], (unsigned long long)px, n);
     /* the mean must be the mean of THESE sums: mean = sum / n to rounding, on a spread of pixels */
     const u64 stride = num_pixels > 4096 ? num_pixels / 4096 : 1;
     for (u64 px = 0; px < num_pixels; px += stride)
         for (u32 i = 0; i < S; i += 1)
         {
+            const f64 n_px = dst_pixels[px * (S + 1) + S]; /* the pixel's own count (every pixel's, in a uniform checkpoint) */
             f64 sum = dst_pixels[px * (S + 1) + i], mean = dst_avgs[px * S + i];
-            f64 tol = 1e-9 * (fabs(sum) / n) + 1e-300;
-            if (!(fabs(mean - sum / n) <= tol) && isfinite(sum))
-                return refuse("%s does not belong to %s (pixel %llu: mean %g, sum / %u = %g)", paths[1], paths[0], (unsigned long long)px, mean, n, sum / n);
+            f64 tol = 1e-9 * (fabs(sum) / n_px) + 1e-300;
+            if (!(fabs(mean - sum / n_px) <= tol) && isfinite(sum))
+                return refuse("%s does not belong to %s (pixel %llu: mean %g, sum / %u = %g)", paths[1], paths[0], (unsigned long long)px, mean, (u32)n_px, sum / n_px);
             if (dst_vars[px * S + i] < 0.0) return refuse("%s holds a negative variance sum", paths[2]);
         }
     *samples_done = n;
+    if (line) *line = m.adaptive; /* zeros from a version-2 manifest */
     return 0;
+}
+
+int drt_host_load_checkpoint(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
+                             f64 *dst_avgs, f64 *dst_vars, u32 *samples_done)
+{
+    return load_checkpoint(config, width, height, S, seed, dst_pixels, dst_avgs, dst_vars, samples_done, 0, NULL);
+}
+
+int drt_host_load_checkpoint_adaptive(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
+                                      f64 *dst_avgs, f64 *dst_vars, u32 *largest_count, drt_host_adaptive_line *line)
+{
+    return load_checkpoint(config, width, height, S, seed, dst_pixels, dst_avgs, dst_vars, largest_count, 1, line);
 }

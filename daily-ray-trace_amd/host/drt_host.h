@@ -79,7 +79,7 @@ typedef struct
 
 /* Host extras that the reference has no field for (device choice, RNG seed, batch size, adaptive sampling);
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
- * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR. */
+ * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME. */
 typedef struct
 {
     int32_t  device;
@@ -92,10 +92,15 @@ typedef struct
     int32_t  devices[16];    /* 0: the single `device` above. DRT_DEVICES="0,1,2,3" or "all" (every visible device) */
     uint32_t all_devices;
     /* adaptive sampling (drt_group_render_adaptive) when adaptive != 0: num_pixel_samples is max_spp; the .spd filter column holds
-     * each pixel's sample count. Not combined with checkpoints or resuming. */
+     * each pixel's sample count. Not combined with checkpoint_spp or resume: an adaptive render has checkpoints of its own, */
     uint32_t adaptive, adaptive_min_spp, adaptive_step;
     double   adaptive_error, adaptive_floor;
+    uint32_t adaptive_checkpoint_rounds; /* written after every this many rendering rounds (0: none), */
+    uint32_t adaptive_resume;            /* and continues from one (or from a uniform render's), every pixel from the count it holds */
 } drt_host_options;
+
+/* the `adaptive` line of a version-3 checkpoint manifest: what the film was rendered with so far */
+typedef struct { uint32_t min_spp, max_spp, step; double rel_error, floor; } drt_host_adaptive_line;
 
 /* Fills *config from the text of a config.cfg. Unknown keys are fatal (exit(-1)), like the reference.
  * Paths may use '\' or '/'. */
@@ -166,6 +171,15 @@ int drt_host_write_outputs(const config_arguments *config, u32 width, u32 height
  * (buffers then hold garbage: clear them) with the reason in drt_host_checkpoint_error(). */
 int drt_host_load_checkpoint(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
                              f64 *dst_avgs, f64 *dst_vars, u32 *samples_done);
+/* The adaptive forms. Writing: the same set under a version-3 manifest (`samples` = the largest count of any pixel, one `adaptive`
+ * line). Loading: a version-3 or a version-2 manifest; every pixel's filter sum a whole number from 2 to the job's num_pixel_samples,
+ * the largest the manifest's `samples`, and mean = sum / the pixel's own count on a spread of pixels. *line (may be NULL) gets the
+ * manifest's adaptive line, zeros from version 2. */
+int drt_host_write_outputs_adaptive(const config_arguments *config, u32 width, u32 height, u32 S, f64 min_wl, f64 interval,
+                                    const f64 *dst_pixels, const f64 *dst_avgs, const f64 *dst_vars, int with_raw_variance,
+                                    u64 seed, const drt_host_adaptive_line *adaptive);
+int drt_host_load_checkpoint_adaptive(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
+                                      f64 *dst_avgs, f64 *dst_vars, u32 *largest_count, drt_host_adaptive_line *line);
 const char *drt_host_checkpoint_error(void);
 
 /* .spd -> BMP post-process (spd_file_to_bmp, src/win32_main.c:115-121). cmf: [4][S] rows rw, x, y, z. */

@@ -113,7 +113,63 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     if (!ctx) rc = -1;
     if (!rc && !(opt && opt->quiet) && drt_group_size(ctx) > 1) printf("Rendering on %u devices\n", drt_group_size(ctx));
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
-    if (!rc && opt && opt->adaptive)
+    if (!rc && opt && opt->adaptive && (opt->adaptive_checkpoint_rounds || opt->adaptive_resume))
+    {
+        /* An adaptive render that can be taken up again: samples [0, min_spp) of every pixel as a uniform render, then
+         * drt_group_render_adaptive_continue in slices of adaptive_checkpoint_rounds rounds -- the same render as drt_group_render_adaptive
+         * (include/drt_hip.h) -- with a checkpoint after each slice. A resumed run adopts the checkpoint's film instead of rendering the
+         * first samples, every pixel at the count it holds; continuing with a tighter DRT_ADAPTIVE_ERROR or more num_pixel_samples
+         * gives the film of one render with those. */
+        const drt_host_adaptive_line line = { opt->adaptive_min_spp, p.spp, opt->adaptive_step, opt->adaptive_error, opt->adaptive_floor };
+        u32 rounds = 0, at_max = 0, largest = 0;
+        u64 paths = 0;
+        int resumed = 0;
+        if (opt->adaptive_resume)
+        {
+            if (drt_host_load_checkpoint_adaptive(config, width, height, S, seed, dst_pixels, dst_avgs, dst_vars, &largest, NULL) == 0)
+            {
+                u64 held = 0;
+                for (u64 px = 0; px < num_pixels; px += 1) held += (u64)dst_pixels[px * (S + 1) + S];
+                resumed = 1;
+                if (!opt->quiet) printf("Resuming an adaptive render: %llu pixels hold %llu samples, %u at most\n", (unsigned long long)num_pixels, (unsigned long long)held, largest);
+                rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
+            }
+            else fprintf(stderr, "render_image: not resuming (%s), starting at sample 0\n", drt_host_checkpoint_error());
+        }
+        if (!rc && !resumed)
+        {
+            rc = drt_group_render(ctx, 0, opt->adaptive_min_spp);
+            rounds = 1;
+            paths = (u64)opt->adaptive_min_spp * num_pixels;
+        }
+        for (u32 left = 1; !rc && left;)
+        {
+            drt_adaptive a;
+            memset(&a, 0, sizeof(a));
+            a.min_spp = 2; /* not used by the continuation */
+            a.max_spp = p.spp;
+            a.step = opt->adaptive_step;
+            a.rel_error = opt->adaptive_error;
+            a.floor = opt->adaptive_floor;
+            if ((rc = drt_group_render_adaptive_continue(ctx, &a, opt->adaptive_checkpoint_rounds, &left))) break;
+            rounds += a.rounds;
+            paths += a.paths;
+            at_max = a.pixels_at_max;
+            if (left) /* a checkpoint: the final write below uses the same code */
+            {
+                if ((rc = drt_group_read_film(ctx, dst_pixels, dst_avgs, dst_vars))) break;
+                if (drt_host_write_outputs_adaptive(config, width, height, S, scene->min_wavelength, scene->wavelength_interval, dst_pixels, dst_avgs, dst_vars, 1, seed, &line))
+                    fprintf(stderr, "render_image: checkpoint write failed: %s\n", drt_host_checkpoint_error());
+                if (!opt->quiet) printf("Adaptive checkpoint after %u rounds, %u pixels active\n", rounds, left);
+            }
+        }
+        if (!rc) done = p.spp;
+        if (!rc && !opt->quiet)
+            printf("Adaptive: %u rounds, %llu of %llu paths traced (%.1f%%), %u of %llu pixels at %u samples\n", rounds,
+                   (unsigned long long)paths, (unsigned long long)p.spp * num_pixels, 100.0 * (f64)paths / ((f64)p.spp * (f64)num_pixels),
+                   at_max, (unsigned long long)num_pixels, p.spp);
+    }
+    else if (!rc && opt && opt->adaptive)
     {
         /* adaptive sampling: rounds until every pixel has converged or holds num_pixel_samples (= max_spp) samples */
         drt_adaptive a;
@@ -183,7 +239,14 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
                (f64)stats.shaded_vertices / (f64)stats.paths, (f64)stats.paths / (stats.total_ms * 1e3));
     }
 
-    int wrc = drt_host_write_outputs(config, width, height, S, scene->min_wavelength, scene->wavelength_interval, dst_pixels, dst_avgs, dst_vars,
+    int wrc;
+    if (opt && opt->adaptive && opt->adaptive_checkpoint_rounds)
+    {
+        const drt_host_adaptive_line line = { opt->adaptive_min_spp, p.spp, opt->adaptive_step, opt->adaptive_error, opt->adaptive_floor };
+        wrc = drt_host_write_outputs_adaptive(config, width, height, S, scene->min_wavelength, scene->wavelength_interval, dst_pixels, dst_avgs, dst_vars, 1, seed, &line);
+    }
+    else
+        wrc = drt_host_write_outputs(config, width, height, S, scene->min_wavelength, scene->wavelength_interval, dst_pixels, dst_avgs, dst_vars,
                                      (opt && opt->checkpoint_spp) ? 1 : 0, done, seed);
     if (wrc) fprintf(stderr, "render_image: %s\n", drt_host_checkpoint_error());
     int w0 = wrc, w1 = 0, w2 = 0;
@@ -228,13 +291,15 @@ static int env_u32(const char *name, u32 *out)
 }
 
 /* DRT_ADAPTIVE_*: parsed and checked here, before any device call. DRT_ADAPTIVE_ERROR=<rel_error> turns adaptive sampling on;
- * DRT_ADAPTIVE_MIN_SPP (default min(16, num_pixel_samples)), DRT_ADAPTIVE_STEP (default min_spp), DRT_ADAPTIVE_FLOOR (default 0). */
+ * DRT_ADAPTIVE_MIN_SPP (default min(16, num_pixel_samples)), DRT_ADAPTIVE_STEP (default min_spp), DRT_ADAPTIVE_FLOOR (default 0);
+ * DRT_ADAPTIVE_CHECKPOINT_ROUNDS=k (a whole number, 1 or more) writes a checkpoint after every k rendering rounds, DRT_ADAPTIVE_RESUME=1
+ * continues from one. */
 static int adaptive_options(const config_arguments *config, drt_host_options *opt)
 {
-    static const char *const names[] = { "DRT_ADAPTIVE_MIN_SPP", "DRT_ADAPTIVE_STEP", "DRT_ADAPTIVE_FLOOR" };
+    static const char *const names[] = { "DRT_ADAPTIVE_MIN_SPP", "DRT_ADAPTIVE_STEP", "DRT_ADAPTIVE_FLOOR", "DRT_ADAPTIVE_CHECKPOINT_ROUNDS", "DRT_ADAPTIVE_RESUME" };
     if (!getenv("DRT_ADAPTIVE_ERROR"))
     {
-        for (int k = 0; k < 3; k += 1)
+        for (int k = 0; k < 5; k += 1)
             if (getenv(names[k])) { fprintf(stderr, "render_image: %s is set but DRT_ADAPTIVE_ERROR is not\n", names[k]); return -1; }
         return 0;
     }
@@ -257,6 +322,12 @@ static int adaptive_options(const config_arguments *config, drt_host_options *op
     if (getenv("DRT_ADAPTIVE_FLOOR") && env_double("DRT_ADAPTIVE_FLOOR", &opt->adaptive_floor)) return -1;
     if (!isfinite(opt->adaptive_floor) || !(opt->adaptive_floor >= 0.0))
     { fprintf(stderr, "render_image: DRT_ADAPTIVE_FLOOR=%s: a finite number, 0 or more\n", getenv("DRT_ADAPTIVE_FLOOR")); return -1; }
+    if (getenv("DRT_ADAPTIVE_CHECKPOINT_ROUNDS"))
+    {
+        if (env_u32("DRT_ADAPTIVE_CHECKPOINT_ROUNDS", &opt->adaptive_checkpoint_rounds)) return -1;
+        if (opt->adaptive_checkpoint_rounds < 1) { fprintf(stderr, "render_image: DRT_ADAPTIVE_CHECKPOINT_ROUNDS=0: at least 1\n"); return -1; }
+    }
+    if (getenv("DRT_ADAPTIVE_RESUME") && env_u32("DRT_ADAPTIVE_RESUME", &opt->adaptive_resume)) return -1;
     if (getenv("DRT_CHECKPOINT_SPP")) { fprintf(stderr, "render_image: DRT_ADAPTIVE_ERROR cannot be combined with DRT_CHECKPOINT_SPP\n"); return -1; }
     if (getenv("DRT_RESUME")) { fprintf(stderr, "render_image: DRT_ADAPTIVE_ERROR cannot be combined with DRT_RESUME\n"); return -1; }
     return 0;

@@ -342,6 +342,8 @@ def hip_lib():
         L.drt_read_active_list.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         L.drt_group_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Adaptive)]
         L.drt_group_read_sample_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.drt_render_adaptive_continue.argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.POINTER(C.c_uint32)]
+        L.drt_group_render_adaptive_continue.argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.POINTER(C.c_uint32)]
         L.drt_batch_spp.restype = C.c_uint32
         L.drt_batch_spp.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
@@ -367,7 +369,7 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
-               "drt_read_active_list"]
+               "drt_read_active_list", "drt_render_adaptive_continue", "drt_group_render_adaptive_continue"]
 
 
 def _check(rc, what):
@@ -473,6 +475,14 @@ class Renderer:
         _check(self.L.drt_render_adaptive(self.ctx, C.byref(a)), "drt_render_adaptive")
         return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths}
 
+    def render_adaptive_continue(self, max_spp, step, rel_error, floor=0.0, max_rounds=0):
+        """Adaptive sampling continued on the film the context holds (drt_render_adaptive_continue), every pixel from its own count;
+        max_rounds = 0: to the end. Returns {"rounds", "pixels_at_max", "paths", "still_active"}: rounds and paths of this call."""
+        a = make_adaptive(2, max_spp, step, rel_error, floor)  # (min_spp is not used: the smallest the checks accept)
+        left = C.c_uint32()
+        _check(self.L.drt_render_adaptive_continue(self.ctx, C.byref(a), max_rounds, C.byref(left)), "drt_render_adaptive_continue")
+        return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths, "still_active": left.value}
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -530,6 +540,13 @@ class Group:
         a = make_adaptive(min_spp, max_spp, step, rel_error, floor)
         _check(self.L.drt_group_render_adaptive(self.g, C.byref(a)), "drt_group_render_adaptive")
         return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths}
+
+    def render_adaptive_continue(self, max_spp, step, rel_error, floor=0.0, max_rounds=0):
+        """drt_group_render_adaptive_continue: as Renderer.render_adaptive_continue (rounds: the most any device ran; still_active: all devices')."""
+        a = make_adaptive(2, max_spp, step, rel_error, floor)
+        left = C.c_uint32()
+        _check(self.L.drt_group_render_adaptive_continue(self.g, C.byref(a), max_rounds, C.byref(left)), "drt_group_render_adaptive_continue")
+        return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths, "still_active": left.value}
 
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)

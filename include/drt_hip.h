@@ -319,6 +319,32 @@ int drt_read_active_list(drt_context *ctx, uint32_t *list, uint32_t capacity, ui
 int drt_group_render_adaptive(drt_group *g, drt_adaptive *a);
 int drt_group_read_sample_counts(drt_group *g, uint32_t *counts); /* whole tile, image order */
 
+/*
+ * Continue adaptive sampling on the film the context HOLDS: whatever drt_render, drt_write_film, drt_render_adaptive or an earlier
+ * call of this function left there. The rule above holds per pixel, with the pixel's own count n_p where it says n: pixel p's count is
+ * its filter sum, c = n_p in E, p is active iff n_p < max_spp && !(E <= rel_error * max(|Y|, floor)), and an active pixel's next
+ * allotment is min(step, max_spp - n_p). First every pixel is tested on its own rows (nothing is rendered); then rounds as in
+ * drt_render_adaptive over the pixels that stay active, each rendering samples [n_p, n_p + min(step, max_spp - n_p)) of pixel p.
+ * max_rounds = 0: until no pixel is active; k: return after at most k rendering rounds. a->min_spp is not used (checked as in
+ * drt_render_adaptive, nothing more). A pixel with n_p >= max_spp is finished.
+ * Out: a->rounds rendering rounds run by THIS call, a->paths samples rendered by this call, a->pixels_at_max tile pixels with
+ * n_p >= max_spp at return; *still_active (may be NULL) the length of the active list at return.
+ * Afterwards the context is in the state an adaptive render leaves (drt_read_sample_counts, drt_read_active_list, drt_read_film and
+ * drt_read_bgra work; drt_render and drt_write_film are refused until drt_reset_film), and the call may be repeated, with the same
+ * or other parameters. Continuing with a rel_error and floor no larger and a max_spp no smaller than before (same step, same grid of
+ * counts) gives the film and the counts of one drt_render_adaptive call with the new parameters; drt_render(0, m) followed by this
+ * call those of drt_render_adaptive with min_spp = m.
+ * Refused (nonzero, drt_last_error, nothing rendered, no film bit changed): DRT_MODE_XYZ, DRT_FLAG_RECORD_HITS, inputs out of range, a
+ * film without samples, a filter sum that is not a whole number in [2, 2^32) (the message names the first such tile pixel), and the
+ * allotment contract: a round renders the same number of samples of every active pixel, so after the first test either all active
+ * pixels hold the same count (the rounds are then drt_render_adaptive's, a partial last round included) or every active pixel's
+ * max_spp - n_p is a multiple of step (every round then renders step samples of each). The rounds keep either property. The message of
+ * that refusal lists the values of step that would do. In the group form the contract is decided over the whole tile, and parameters,
+ * films and contract are checked on all devices before any device renders; film, counts and report are the same for any device list.
+ */
+int drt_render_adaptive_continue(drt_context *ctx, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active);
+int drt_group_render_adaptive_continue(drt_group *g, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */
