@@ -6,6 +6,7 @@
 #include "drt_kernels.h"
 #include "drt_bvh_kernels.h"
 #include "drt_adaptive_kernels.h"
+#include "drt_denoise_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -118,6 +119,13 @@ struct drt_context
     uint32_t *h_active = nullptr;          /* pinned host words the active count, then d_ainfo, are copied to: the copies stay asynchronous,
                                               so the devices of a group are all given their round before any is waited for */
     /* n: the count all active pixels hold (same); !same: they hold different counts, each max_spp - count a multiple of step */
+    /* the denoiser (drt_denoise_film): its result and work buffers, kept from call to call, and the film they were made from */
+    uint64_t film_gen = 0;                 /* counts what changes the film: kernel pairs, drt_write_film, drt_reset_film, drt_bind_film */
+    uint64_t dn_gen = 0;                   /* film_gen at the last drt_denoise_film */
+    bool     dn_valid = false;
+    double  *d_dn_mean = nullptr, *d_dn_var = nullptr, *d_dn_guide = nullptr, *d_dn_weights = nullptr, *d_dn_wsum = nullptr;
+    uint32_t *d_dn_unusable = nullptr;
+    uint32_t dn_window_cap = 0;            /* window entries per pixel d_dn_weights holds */
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -1087,6 +1095,12 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_alist[1]);
     (void)hipFree(ctx->d_keep);
     (void)hipFree(ctx->d_bkeep);
+    (void)hipFree(ctx->d_dn_mean);
+    (void)hipFree(ctx->d_dn_var);
+    (void)hipFree(ctx->d_dn_guide);
+    (void)hipFree(ctx->d_dn_weights);
+    (void)hipFree(ctx->d_dn_wsum);
+    (void)hipFree(ctx->d_dn_unusable);
     (void)hipHostFree(ctx->h_active);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -1105,6 +1119,7 @@ extern "C" int drt_bind_film(drt_context *ctx, void *d_pixels, void *d_avgs, voi
         (void)hipFree(ctx->d_vars);
         ctx->own_film = false;
     }
+    ctx->film_gen += 1;
     ctx->d_pixels = (double *)d_pixels;
     ctx->d_avgs = (double *)d_avgs;
     ctx->d_vars = (double *)d_vars;
@@ -1259,6 +1274,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     hipEvent_t ev[3];
     int rc = next_events(ctx, ev);
     if (rc) return rc;
+    ctx->film_gen += 1;
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     if ((rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, row0, rows, stride, list, list_len))) return rc;
     const uint64_t n_pix = list ? list_len : rows ? (uint64_t)rows * ctx->params.tile_w : ctx->n_pix; /* pixels of this launch */
@@ -1511,6 +1527,7 @@ extern "C" int drt_reset_film(drt_context *ctx)
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->film_used = ctx->adaptive_done = false;
+    ctx->film_gen += 1;
     ctx->trace_ms = ctx->shade_ms = 0.0;
     ctx->timed_pairs = 0;
     ctx->min_sample_ms = ctx->max_sample_ms = ctx->avg_sample_ms = 0.0;
@@ -1544,6 +1561,7 @@ extern "C" int drt_write_film(drt_context *ctx, const double *pixels, const doub
     if (!ctx) return fail(-1, "null context");
     if (ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
     ctx->film_used = true;
+    ctx->film_gen += 1;
     int rc = drt_synchronize(ctx);
     if (rc) return rc;
     const size_t S = ctx->dsc.S;
@@ -2257,7 +2275,11 @@ extern "C" int drt_group_write_film(drt_group *g, const double *pixels, const do
     for (drt_context *c : g->ctx)
         if (c && c->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
     for (drt_context *c : g->ctx)
-        if (c) c->film_used = true;
+        if (c)
+        {
+            c->film_used = true;
+            c->film_gen += 1;
+        }
     if ((rc = group_copy(g, const_cast<double *>(pixels), 0, true))) return rc;
     if ((rc = group_copy(g, const_cast<double *>(avgs), 1, true))) return rc;
     return group_copy(g, const_cast<double *>(vars), 2, true);
@@ -2426,6 +2448,253 @@ extern "C" int drt_group_read_sample_counts(drt_group *g, uint32_t *counts)
         HIP_TRY(hipMemcpy2D((char *)counts + k * row_bytes, n * row_bytes, c->d_counts, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
     }
     return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* The variance-guided denoiser (kernels in drt_denoise_kernels.h)           */
+
+/* the parameter ranges: no device call before these have passed */
+static int denoise_check(const drt_denoise *d)
+{
+    if (!d) return fail(-1, "null argument");
+    if (d->radius > DENOISE_MAX_RADIUS) return fail(-1, "denoise: radius = %u: from 0 to %d", d->radius, DENOISE_MAX_RADIUS);
+    if (d->patch > DENOISE_MAX_PATCH) return fail(-1, "denoise: patch = %u: from 0 to %d", d->patch, DENOISE_MAX_PATCH);
+    if (d->flags != 0) return fail(-1, "denoise: flags = %u: 0 (reserved)", d->flags);
+    if (!std::isfinite(d->k) || !(d->k > 0.0)) return fail(-1, "denoise: k = %g: a finite number above 0", d->k);
+    if (!std::isfinite(d->alpha) || !(d->alpha >= 0.0)) return fail(-1, "denoise: alpha = %g: a finite number, 0 or more", d->alpha);
+    return 0;
+}
+
+static int denoise_check_film(uint32_t mode, uint32_t row_stride, uint32_t S)
+{
+    if (mode == DRT_MODE_XYZ) return fail(-4, "denoise: needs the spectral film (DRT_MODE_XYZ keeps no mean and no variance)");
+    if (row_stride != 1) return fail(-4, "denoise: row_stride = %u: a pixel's neighbours are not in this film (row_stride must be 1; a group gathers the film, drt_group_denoise)", row_stride);
+    if (S == 0 || S > DENOISE_MAX_S) return fail(-4, "denoise: %u wavelengths: from 1 to %d", S, DENOISE_MAX_S);
+    return 0;
+}
+
+static size_t denoise_halo_bytes(const drt_denoise *d)
+{
+    const size_t side = DENOISE_TILE + 2 * (size_t)(d->radius + d->patch);
+    return side * side * DENOISE_LDS_FIELDS * sizeof(double);
+}
+
+/* the three kernels on `stream`, timed; dp holds every pointer. The current device is the buffers'. */
+static int denoise_enqueue(hipStream_t stream, const DenoiseParams &dp, const drt_denoise *d, double *kernel_ms)
+{
+    const uint64_t n_pix = (uint64_t)dp.tile_w * dp.tile_h;
+    const size_t halo = denoise_halo_bytes(d);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(drt_denoise_weight_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)halo));
+    hipEvent_t ev[2];
+    HIP_TRY(hipEventCreate(&ev[0]));
+    HIP_TRY(hipEventCreate(&ev[1]));
+    hipError_t e = hipMemsetAsync(dp.unusable, 0, sizeof(uint32_t), stream);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess)
+    {
+        hipLaunchKernelGGL(drt_denoise_guide_kernel, dim3((uint32_t)((n_pix + DENOISE_BLOCK - 1) / DENOISE_BLOCK)), dim3(DENOISE_BLOCK), 0, stream, dp);
+        hipLaunchKernelGGL(drt_denoise_weight_kernel, dim3((dp.tile_w + DENOISE_TILE - 1) / DENOISE_TILE, (dp.tile_h + DENOISE_TILE - 1) / DENOISE_TILE),
+                           dim3(DENOISE_TILE, DENOISE_TILE), halo, stream, dp);
+        hipLaunchKernelGGL(drt_denoise_apply_kernel, dim3((dp.tile_w + DENOISE_APPLY_SIDE - 1) / DENOISE_APPLY_SIDE, (dp.tile_h + DENOISE_APPLY_SIDE - 1) / DENOISE_APPLY_SIDE),
+                           dim3(DENOISE_BLOCK), 0, stream, dp);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (e != hipSuccess) return fail(-100 - (int)e, "denoise kernels: %s", hipGetErrorString(e));
+    if (kernel_ms) *kernel_ms = (double)ms;
+    return 0;
+}
+
+static void denoise_fill(DenoiseParams *dp, const drt_denoise *d, uint32_t S, uint32_t tile_w, uint32_t tile_h, double interval)
+{
+    memset(dp, 0, sizeof(*dp));
+    dp->S = S;
+    dp->tile_w = tile_w;
+    dp->tile_h = tile_h;
+    dp->radius = d->radius;
+    dp->patch = d->patch;
+    dp->n_window = (2 * d->radius + 1) * (2 * d->radius + 1);
+    dp->interval = interval;
+    dp->k2 = d->k * d->k;
+    dp->alpha = d->alpha;
+}
+
+extern "C" int drt_denoise_film(drt_context *ctx, drt_denoise *d)
+{
+    if (!ctx || !d) return fail(-1, "null argument");
+    int rc = denoise_check(d);
+    if (rc) return rc;
+    if ((rc = denoise_check_film(ctx->xyz_mode ? DRT_MODE_XYZ : DRT_MODE_SPECTRAL, ctx->params.row_stride, ctx->dsc.S))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = drt_synchronize(ctx))) return rc; /* the complete film first (see drt_read_xyz) */
+    ctx->dn_valid = false;
+    const uint32_t S = ctx->dsc.S;
+    const size_t n_pix = ctx->n_pix;
+    DenoiseParams dp;
+    denoise_fill(&dp, d, S, ctx->params.tile_w, ctx->params.tile_h, ctx->interval);
+    if (!ctx->d_dn_mean) HIP_TRY(hipMalloc((void **)&ctx->d_dn_mean, n_pix * S * 8));
+    if (!ctx->d_dn_var) HIP_TRY(hipMalloc((void **)&ctx->d_dn_var, n_pix * S * 8));
+    if (!ctx->d_dn_guide) HIP_TRY(hipMalloc((void **)&ctx->d_dn_guide, n_pix * DENOISE_GUIDE_WORDS * 8));
+    if (!ctx->d_dn_wsum) HIP_TRY(hipMalloc((void **)&ctx->d_dn_wsum, n_pix * 8));
+    if (!ctx->d_dn_unusable) HIP_TRY(hipMalloc((void **)&ctx->d_dn_unusable, sizeof(uint32_t)));
+    if (ctx->dn_window_cap < dp.n_window)
+    {
+        (void)hipFree(ctx->d_dn_weights);
+        ctx->d_dn_weights = nullptr;
+        ctx->dn_window_cap = 0;
+        HIP_TRY(hipMalloc((void **)&ctx->d_dn_weights, n_pix * dp.n_window * 8));
+        ctx->dn_window_cap = dp.n_window;
+    }
+    dp.rw = ctx->dsc.spds + (size_t)ctx->cmf_rw * S;
+    dp.cx = ctx->dsc.spds + (size_t)ctx->cmf_x * S;
+    dp.cy = ctx->dsc.spds + (size_t)ctx->cmf_y * S;
+    dp.cz = ctx->dsc.spds + (size_t)ctx->cmf_z * S;
+    dp.pixels = ctx->d_pixels;
+    dp.avgs = ctx->d_avgs;
+    dp.vars = ctx->d_vars;
+    dp.guide = ctx->d_dn_guide;
+    dp.weights = ctx->d_dn_weights;
+    dp.wsum = ctx->d_dn_wsum;
+    dp.mean = ctx->d_dn_mean;
+    dp.var = ctx->d_dn_var;
+    dp.unusable = ctx->d_dn_unusable;
+    if ((rc = denoise_enqueue(ctx->stream, dp, d, &d->kernel_ms))) return rc;
+    HIP_TRY(hipMemcpy(&d->unusable, ctx->d_dn_unusable, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    ctx->dn_gen = ctx->film_gen;
+    ctx->dn_valid = true;
+    return 0;
+}
+
+static int denoise_current(drt_context *ctx)
+{
+    if (!ctx->dn_valid) return fail(-4, "no denoised film: drt_denoise_film first");
+    if (ctx->dn_gen != ctx->film_gen) return fail(-4, "the film has changed since drt_denoise_film: denoise it again");
+    return 0;
+}
+
+extern "C" int drt_read_denoised(drt_context *ctx, double *mean, double *var)
+{
+    if (!ctx) return fail(-1, "null context");
+    int rc = denoise_current(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)ctx->n_pix * ctx->dsc.S * 8;
+    if (mean) HIP_TRY(hipMemcpy(mean, ctx->d_dn_mean, bytes, hipMemcpyDeviceToHost));
+    if (var) HIP_TRY(hipMemcpy(var, ctx->d_dn_var, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_denoised_bgra(drt_context *ctx, uint8_t *bgra)
+{
+    if (!ctx || !bgra) return fail(-1, "null argument");
+    int rc = denoise_current(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    /* the conversion drt_read_bgra(ctx, 1, ...) applies to the running mean, on the denoised mean */
+    hipLaunchKernelGGL(drt_film_bgra_kernel, dim3((uint32_t)((ctx->n_pix + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x,
+                       ctx->cmf_y, ctx->cmf_z, ctx->interval, ctx->n_pix, (const double *)ctx->d_dn_mean, 1, ctx->d_bgra);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* One-shot on host buffers of a whole film, on the current device: rows = the four colour-matching rows on that device. */
+static int denoise_host_film(const double *const d_rows[4], uint32_t S, uint32_t tile_w, uint32_t tile_h, double interval, drt_denoise *d,
+                             const double *pixels, const double *avgs, const double *vars, double *mean, double *var)
+{
+    const size_t n_pix = (size_t)tile_w * tile_h;
+    DenoiseParams dp;
+    denoise_fill(&dp, d, S, tile_w, tile_h, interval);
+    const size_t sizes[9] = {n_pix * (S + 1) * 8, n_pix * S * 8, n_pix * S * 8, n_pix * S * 8, n_pix * S * 8, n_pix * DENOISE_GUIDE_WORDS * 8,
+                             n_pix * dp.n_window * 8, n_pix * 8, sizeof(uint32_t)};
+    void *buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int rc = 0;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 9 && e == hipSuccess; k += 1) e = hipMalloc(&buf[k], sizes[k]);
+    const void *src[3] = {pixels, avgs, vars};
+    for (int k = 0; k < 3 && e == hipSuccess; k += 1) e = hipMemcpy(buf[k], src[k], sizes[k], hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(-100 - (int)e, "denoise: film buffers on the device: %s", hipGetErrorString(e));
+    if (!rc)
+    {
+        dp.rw = d_rows[0];
+        dp.cx = d_rows[1];
+        dp.cy = d_rows[2];
+        dp.cz = d_rows[3];
+        dp.pixels = (const double *)buf[0];
+        dp.avgs = (const double *)buf[1];
+        dp.vars = (const double *)buf[2];
+        dp.mean = (double *)buf[3];
+        dp.var = (double *)buf[4];
+        dp.guide = (double *)buf[5];
+        dp.weights = (double *)buf[6];
+        dp.wsum = (double *)buf[7];
+        dp.unusable = (uint32_t *)buf[8];
+        rc = denoise_enqueue(nullptr, dp, d, &d->kernel_ms);
+    }
+    if (!rc)
+    {
+        if (mean) e = hipMemcpy(mean, buf[3], sizes[3], hipMemcpyDeviceToHost);
+        if (var && e == hipSuccess) e = hipMemcpy(var, buf[4], sizes[4], hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&d->unusable, buf[8], sizeof(uint32_t), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(-100 - (int)e, "denoise: reading the result: %s", hipGetErrorString(e));
+    }
+    for (int k = 0; k < 9; k += 1) (void)hipFree(buf[k]);
+    return rc;
+}
+
+extern "C" int drt_denoise_buffers(const drt_scene *scene, const drt_params *params, drt_denoise *d, const double *pixels, const double *avgs,
+                                   const double *vars, double *mean, double *var)
+{
+    g_last_error.clear();
+    if (!scene || !params || !d || !pixels || !avgs || !vars) return fail(-1, "null argument");
+    int rc = denoise_check(d);
+    if (rc) return rc;
+    const uint32_t S = scene->num_wavelengths;
+    if ((rc = denoise_check_film(params->mode, params->row_stride, S))) return rc;
+    if (params->tile_w == 0 || params->tile_h == 0) return fail(-1, "denoise: an empty tile");
+    const uint32_t rows[4] = {scene->cmf_rw, scene->cmf_x, scene->cmf_y, scene->cmf_z};
+    for (int k = 0; k < 4; k += 1)
+        if (rows[k] >= scene->num_spds || !scene->spds) return fail(-1, "denoise: colour-matching row %u of %u SPDs", rows[k], scene->num_spds);
+    HIP_TRY(hipSetDevice(params->device));
+    double *d_cmf = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_cmf, (size_t)4 * S * 8));
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; k += 1)
+        e = hipMemcpy(d_cmf + (size_t)k * S, scene->spds + (size_t)rows[k] * S, (size_t)S * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = fail(-100 - (int)e, "denoise: colour-matching rows on the device: %s", hipGetErrorString(e));
+    const double *d_rows[4] = {d_cmf, d_cmf + S, d_cmf + 2 * (size_t)S, d_cmf + 3 * (size_t)S};
+    if (!rc) rc = denoise_host_film(d_rows, S, params->tile_w, params->tile_h, scene->wavelength_interval, d, pixels, avgs, vars, mean, var);
+    (void)hipFree(d_cmf);
+    return rc;
+}
+
+/* Row-cyclic devices hold no neighbours of their own rows: the group gathers the film (drt_group_read_film) and its first device
+ * filters it whole, so the bits are those of one context for any device list. */
+extern "C" int drt_group_denoise(drt_group *g, drt_denoise *d, double *mean, double *var)
+{
+    if (!g || !d) return fail(-1, "null argument");
+    int rc = denoise_check(d);
+    if (rc) return rc;
+    drt_context *first = nullptr;
+    for (drt_context *c : g->ctx)
+        if (c && !first) first = c;
+    if (!first) return fail(-1, "denoise: an empty group");
+    /* (a context of a group of n devices has row_stride n x the group's: what counts is the group's own) */
+    if ((rc = denoise_check_film(g->xyz_mode ? DRT_MODE_XYZ : DRT_MODE_SPECTRAL, first->params.row_stride / (uint32_t)g->ctx.size(), g->S))) return rc;
+    const size_t n_pix = (size_t)g->tile_w * g->tile_h, S = g->S;
+    std::vector<double> px(n_pix * (S + 1)), av(n_pix * S), va(n_pix * S);
+    if ((rc = drt_group_read_film(g, px.data(), av.data(), va.data()))) return rc;
+    HIP_TRY(hipSetDevice(first->device));
+    const double *d_rows[4] = {first->dsc.spds + (size_t)first->cmf_rw * S, first->dsc.spds + (size_t)first->cmf_x * S,
+                               first->dsc.spds + (size_t)first->cmf_y * S, first->dsc.spds + (size_t)first->cmf_z * S};
+    return denoise_host_film(d_rows, g->S, g->tile_w, g->tile_h, first->interval, d, px.data(), av.data(), va.data(), mean, var);
 }
 
 extern "C" int drt_render_tile_multi(const drt_scene *scene, const drt_camera *camera, const drt_params *params,

@@ -79,7 +79,8 @@ typedef struct
 
 /* Host extras that the reference has no field for (device choice, RNG seed, batch size, adaptive sampling);
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
- * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME. */
+ * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
+ * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD. */
 typedef struct
 {
     int32_t  device;
@@ -97,6 +98,11 @@ typedef struct
     double   adaptive_error, adaptive_floor;
     uint32_t adaptive_checkpoint_rounds; /* written after every this many rendering rounds (0: none), */
     uint32_t adaptive_resume;            /* and continues from one (or from a uniform render's), every pixel from the count it holds */
+    /* the variance-guided denoiser (drt_group_denoise) when denoise != 0: the finished film, uniform, adaptive or resumed, is filtered
+     * into two more .spd files (the average file's header); the three standard outputs stay byte for byte what they are without it */
+    uint32_t denoise, denoise_radius, denoise_patch;
+    double   denoise_k, denoise_alpha;
+    char     denoise_spd[256], denoise_var_spd[256];
 } drt_host_options;
 
 /* the `adaptive` line of a version-3 checkpoint manifest: what the film was rendered with so far */

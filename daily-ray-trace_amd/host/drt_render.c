@@ -23,6 +23,15 @@ static f64 now_ms(void)
     return (f64)ts.tv_sec * 1000.0 + (f64)ts.tv_nsec * 1e-6;
 }
 
+/* a .spd without a filter column, written under a temporary name and moved into place */
+static int publish_spd(const char *path, u32 width, u32 height, u32 S, f64 min_wl, f64 interval, const f64 *data)
+{
+    char tmp[300];
+    if (snprintf(tmp, sizeof(tmp), "%s.tmp", path) >= (int)sizeof(tmp)) return -1;
+    if (drt_host_write_spd(tmp, width, height, S, 0, min_wl, interval, data) != 0) return -1;
+    return rename(tmp, path) == 0 ? 0 : -1;
+}
+
 int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_stats *stats_out)
 {
     u32 width = config->output_width, height = config->output_height;
@@ -202,6 +211,24 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     }
     if (!rc) rc = drt_group_read_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc) rc = drt_group_get_stats(ctx, &stats);
+    /* the denoised film, while the devices still hold the scene's tables (the film itself is not changed) */
+    f64 *dn_mean = NULL, *dn_var = NULL;
+    if (!rc && opt && opt->denoise)
+    {
+        drt_denoise dn;
+        memset(&dn, 0, sizeof(dn));
+        dn.radius = opt->denoise_radius;
+        dn.patch = opt->denoise_patch;
+        dn.k = opt->denoise_k;
+        dn.alpha = opt->denoise_alpha;
+        dn_mean = (f64 *)malloc(num_pixels * S * sizeof(f64));
+        dn_var = (f64 *)malloc(num_pixels * S * sizeof(f64));
+        if (!dn_mean || !dn_var) rc = -3;
+        if (!rc) rc = drt_group_denoise(ctx, &dn, dn_mean, dn_var);
+        if (!rc && !opt->quiet)
+            printf("Denoised: radius %u, patch %u, k %g, alpha %g: %.3f ms on the device, %u pixels passed through\n", dn.radius, dn.patch, dn.k,
+                   dn.alpha, dn.kernel_ms, dn.unusable);
+    }
     /* the .bmp pixels come from the film while it is still on the device (drt_read_bgra: the same bytes as converting the
      * .spd files on the host, host/drt_bmp.c, without reading 1.7 GB back from disk) */
     u8 *bgra[3] = { NULL, NULL, NULL };
@@ -219,6 +246,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     {
         fprintf(stderr, "render_image: the HIP launcher failed (%d): %s\n", rc, drt_last_error());
         for (int k = 0; k < 3; k += 1) free(bgra[k]);
+        free(dn_var);
+        free(dn_mean);
         free(dst_vars);
         free(dst_avgs);
         free(dst_pixels);
@@ -250,6 +279,13 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
                                      (opt && opt->checkpoint_spp) ? 1 : 0, done, seed);
     if (wrc) fprintf(stderr, "render_image: %s\n", drt_host_checkpoint_error());
     int w0 = wrc, w1 = 0, w2 = 0;
+    if (!w0 && dn_mean)
+    {
+        /* both under the average file's header (no filter column), each by temporary name + rename */
+        w1 = publish_spd(opt->denoise_spd, width, height, S, scene->min_wavelength, scene->wavelength_interval, dn_mean);
+        if (!w1) w2 = publish_spd(opt->denoise_var_spd, width, height, S, scene->min_wavelength, scene->wavelength_interval, dn_var);
+        if (w1 || w2) fprintf(stderr, "render_image: could not write the denoised .spd outputs\n");
+    }
     /* post-process like the reference's main(): each film -> linear RGB -> BMP (src/win32_main.c:150-152) */
     if (!(w0 || w1 || w2))
     {
@@ -259,6 +295,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         if (bad) fprintf(stderr, "render_image: could not write one of the .bmp outputs\n");
     }
     for (int k = 0; k < 3; k += 1) free(bgra[k]);
+    free(dn_var);
+    free(dn_mean);
     if (stats_out) *stats_out = stats;
     free(dst_vars);
     free(dst_avgs);
@@ -333,6 +371,44 @@ static int adaptive_options(const config_arguments *config, drt_host_options *op
     return 0;
 }
 
+/* DRT_DENOISE_*: parsed and checked here, before any device call. DRT_DENOISE_K=<k> turns the denoiser on; DRT_DENOISE_RADIUS (default 5),
+ * DRT_DENOISE_PATCH (1), DRT_DENOISE_ALPHA (1); the outputs go to DRT_DENOISE_SPD (default <output_spd>.denoised.spd) and
+ * DRT_DENOISE_VAR_SPD (default <variance_spd>.denoised.spd). */
+static int denoise_options(const config_arguments *config, drt_host_options *opt)
+{
+    static const char *const names[] = { "DRT_DENOISE_RADIUS", "DRT_DENOISE_PATCH", "DRT_DENOISE_ALPHA", "DRT_DENOISE_SPD", "DRT_DENOISE_VAR_SPD" };
+    if (!getenv("DRT_DENOISE_K"))
+    {
+        for (int k = 0; k < 5; k += 1)
+            if (getenv(names[k])) { fprintf(stderr, "render_image: %s is set but DRT_DENOISE_K is not\n", names[k]); return -1; }
+        return 0;
+    }
+    opt->denoise = 1;
+    if (env_double("DRT_DENOISE_K", &opt->denoise_k)) return -1;
+    if (!isfinite(opt->denoise_k) || !(opt->denoise_k > 0.0))
+    { fprintf(stderr, "render_image: DRT_DENOISE_K=%s: a finite number above 0\n", getenv("DRT_DENOISE_K")); return -1; }
+    opt->denoise_radius = 5;
+    if (getenv("DRT_DENOISE_RADIUS") && env_u32("DRT_DENOISE_RADIUS", &opt->denoise_radius)) return -1;
+    if (opt->denoise_radius > 10) { fprintf(stderr, "render_image: DRT_DENOISE_RADIUS=%u: from 0 to 10\n", opt->denoise_radius); return -1; }
+    opt->denoise_patch = 1;
+    if (getenv("DRT_DENOISE_PATCH") && env_u32("DRT_DENOISE_PATCH", &opt->denoise_patch)) return -1;
+    if (opt->denoise_patch > 3) { fprintf(stderr, "render_image: DRT_DENOISE_PATCH=%u: from 0 to 3\n", opt->denoise_patch); return -1; }
+    opt->denoise_alpha = 1.0;
+    if (getenv("DRT_DENOISE_ALPHA") && env_double("DRT_DENOISE_ALPHA", &opt->denoise_alpha)) return -1;
+    if (!isfinite(opt->denoise_alpha) || !(opt->denoise_alpha >= 0.0))
+    { fprintf(stderr, "render_image: DRT_DENOISE_ALPHA=%s: a finite number, 0 or more\n", getenv("DRT_DENOISE_ALPHA")); return -1; }
+    const char *e = getenv("DRT_DENOISE_SPD");
+    int n = e ? snprintf(opt->denoise_spd, sizeof(opt->denoise_spd), "%s", e)
+              : snprintf(opt->denoise_spd, sizeof(opt->denoise_spd), "%s.denoised.spd", config->output_spd);
+    if (n <= 0 || n >= (int)sizeof(opt->denoise_spd)) { fprintf(stderr, "render_image: DRT_DENOISE_SPD: a path of 1 to %d characters\n", (int)sizeof(opt->denoise_spd) - 1); return -1; }
+    e = getenv("DRT_DENOISE_VAR_SPD");
+    n = e ? snprintf(opt->denoise_var_spd, sizeof(opt->denoise_var_spd), "%s", e)
+          : snprintf(opt->denoise_var_spd, sizeof(opt->denoise_var_spd), "%s.denoised.spd", config->variance_spd);
+    if (n <= 0 || n >= (int)sizeof(opt->denoise_var_spd)) { fprintf(stderr, "render_image: DRT_DENOISE_VAR_SPD: a path of 1 to %d characters\n", (int)sizeof(opt->denoise_var_spd) - 1); return -1; }
+    if (strcmp(opt->denoise_spd, opt->denoise_var_spd) == 0) { fprintf(stderr, "render_image: DRT_DENOISE_SPD and DRT_DENOISE_VAR_SPD name the same file\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -358,5 +434,6 @@ void render_image(config_arguments *config)
     if ((e = getenv("DRT_CHECKPOINT_SPP"))) opt.checkpoint_spp = (u32)atoi(e);
     if ((e = getenv("DRT_RESUME"))) opt.resume = (u32)atoi(e);
     if (adaptive_options(config, &opt) != 0) exit(-1);
+    if (denoise_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

@@ -95,6 +95,19 @@ def make_adaptive(min_spp, max_spp, step, rel_error, floor=0.0):
     return a
 
 
+class Denoise(C.Structure):
+    """drt_denoise (include/drt_hip.h): the inputs of the variance-guided denoiser and, after it, unusable / kernel_ms."""
+    _fields_ = [("radius", C.c_uint32), ("patch", C.c_uint32), ("flags", C.c_uint32), ("unusable", C.c_uint32),
+                ("k", C.c_double), ("alpha", C.c_double), ("kernel_ms", C.c_double)]
+
+
+def make_denoise(radius=5, patch=1, k=1.0, alpha=1.0):
+    d = Denoise()
+    d.radius, d.patch, d.flags, d.unusable = radius, patch, 0, 0
+    d.k, d.alpha, d.kernel_ms = k, alpha, 0.0
+    return d
+
+
 def make_params(width, height, spp, max_depth, seed=1, x0=0, y0=0, tile_w=None, tile_h=None, row_stride=1,
                 first_sample=0, pixel_scheme=FILM_SAMPLE_RANDOM, mode=MODE_SPECTRAL, device=0, batch_spp=0, flags=0):
     p = Params()
@@ -344,6 +357,12 @@ def hip_lib():
         L.drt_group_read_sample_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.drt_render_adaptive_continue.argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.POINTER(C.c_uint32)]
         L.drt_group_render_adaptive_continue.argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.POINTER(C.c_uint32)]
+        if hasattr(L, "drt_denoise_film"):  # (as drt_selftest_path_ids below)
+            L.drt_denoise_film.argtypes = [C.c_void_p, C.POINTER(Denoise)]
+            L.drt_read_denoised.argtypes = [C.c_void_p, f64p, f64p]
+            L.drt_read_denoised_bgra.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
+            L.drt_denoise_buffers.argtypes = [C.POINTER(Scene), C.POINTER(Params), C.POINTER(Denoise), f64p, f64p, f64p, f64p, f64p]
+            L.drt_group_denoise.argtypes = [C.c_void_p, C.POINTER(Denoise), f64p, f64p]
         L.drt_batch_spp.restype = C.c_uint32
         L.drt_batch_spp.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
@@ -369,7 +388,8 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
-               "drt_read_active_list", "drt_render_adaptive_continue", "drt_group_render_adaptive_continue"]
+               "drt_read_active_list", "drt_render_adaptive_continue", "drt_group_render_adaptive_continue",
+               "drt_denoise_film", "drt_read_denoised", "drt_read_denoised_bgra", "drt_denoise_buffers", "drt_group_denoise"]
 
 
 def _check(rc, what):
@@ -483,6 +503,26 @@ class Renderer:
         _check(self.L.drt_render_adaptive_continue(self.ctx, C.byref(a), max_rounds, C.byref(left)), "drt_render_adaptive_continue")
         return {"rounds": a.rounds, "pixels_at_max": a.pixels_at_max, "paths": a.paths, "still_active": left.value}
 
+    def denoise(self, radius=5, patch=1, k=1.0, alpha=1.0):
+        """Variance-guided denoising of the film the context holds (drt_denoise_film), into buffers of the context's own: the film
+        itself does not change. Returns {"unusable", "kernel_ms"}; read_denoised() / read_denoised_bgra() fetch the result."""
+        d = make_denoise(radius, patch, k, alpha)
+        _check(self.L.drt_denoise_film(self.ctx, C.byref(d)), "drt_denoise_film")
+        return {"unusable": d.unusable, "kernel_ms": d.kernel_ms}
+
+    def read_denoised(self):
+        """(mean', var') of the last denoise(), [n][S] each"""
+        mean = np.empty((self.n_pixels, self.S), dtype=np.float64)
+        var = np.empty((self.n_pixels, self.S), dtype=np.float64)
+        _check(self.L.drt_read_denoised(self.ctx, _ptr(mean, C.c_double), _ptr(var, C.c_double)), "drt_read_denoised")
+        return mean, var
+
+    def read_denoised_bgra(self):
+        """BMP pixel bytes [n][4] of the denoised mean (the conversion of read_bgra(1))"""
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_denoised_bgra(self.ctx, _ptr(out, C.c_uint8)), "drt_read_denoised_bgra")
+        return out
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -553,6 +593,14 @@ class Group:
         _check(self.L.drt_group_read_sample_counts(self.g, _ptr(out, C.c_uint32)), "drt_group_read_sample_counts")
         return out
 
+    def denoise(self, radius=5, patch=1, k=1.0, alpha=1.0):
+        """drt_group_denoise: the group's film gathered and filtered on its first device. Returns (mean', var', {"unusable", "kernel_ms"})."""
+        d = make_denoise(radius, patch, k, alpha)
+        mean = np.empty((self.n_pixels, self.S), dtype=np.float64)
+        var = np.empty((self.n_pixels, self.S), dtype=np.float64)
+        _check(self.L.drt_group_denoise(self.g, C.byref(d), _ptr(mean, C.c_double), _ptr(var, C.c_double)), "drt_group_denoise")
+        return mean, var, {"unusable": d.unusable, "kernel_ms": d.kernel_ms}
+
     def close(self):
         if self.g:
             self.L.drt_group_destroy(self.g)
@@ -572,6 +620,21 @@ def render_tile(bundle, params):
                            _ptr(av, C.c_double), _ptr(va, C.c_double), C.byref(st))
     _check(rc, "drt_render_tile")
     return px, av, va, st
+
+
+def denoise_buffers(bundle, params, pixels, avgs, vars_, radius=5, patch=1, k=1.0, alpha=1.0):
+    """One-shot drt_denoise_buffers on host buffers of a whole tile_w x tile_h film (a stored .spd triplet, say), on params.device.
+    Returns (mean', var', {"unusable", "kernel_ms"})."""
+    n, S = int(params.tile_w) * int(params.tile_h), bundle.S
+    px = np.ascontiguousarray(pixels, dtype=np.float64).reshape(n, S + 1)
+    av = np.ascontiguousarray(avgs, dtype=np.float64).reshape(n, S)
+    va = np.ascontiguousarray(vars_, dtype=np.float64).reshape(n, S)
+    d = make_denoise(radius, patch, k, alpha)
+    mean = np.empty((n, S), dtype=np.float64)
+    var = np.empty((n, S), dtype=np.float64)
+    _check(hip_lib().drt_denoise_buffers(C.byref(bundle.scene), C.byref(params), C.byref(d), _ptr(px, C.c_double), _ptr(av, C.c_double),
+                                         _ptr(va, C.c_double), _ptr(mean, C.c_double), _ptr(var, C.c_double)), "drt_denoise_buffers")
+    return mean, var, {"unusable": d.unusable, "kernel_ms": d.kernel_ms}
 
 
 def selftest_arith(op, a, b=None, device=0):

@@ -345,6 +345,40 @@ int drt_group_read_sample_counts(drt_group *g, uint32_t *counts); /* whole tile,
 int drt_render_adaptive_continue(drt_context *ctx, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active);
 int drt_group_render_adaptive_continue(drt_group *g, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active);
 
+/*
+ * Variance-guided denoising of the spectral film. The film holds, per pixel and wavelength, a running mean and a sum of squared
+ * deviations, and in its filter column the sample count c: what is left after a render is noise of known size. The filter is a
+ * non-local mean over a (2 radius + 1)^2 window whose weights compare (2 patch + 1)^2 patches of the pixels' XYZ against the
+ * variance of that XYZ, gated by the centre pair's own distance; DESIGN.md section 5b states the rule, which uses + - * / sqrt
+ * only, and tests/denoise_rule.py restates it in numpy: the device's result equals that bit for bit. A pixel is usable when its count
+ * is a whole number in [2, 2^32) and its guide values are finite; an unusable pixel passes through (mean' = mean, var' = var / (c (c - 1)))
+ * and weighs nothing anywhere else.
+ *   mean'[p][i] = sum_q w(p,q) avg[q][i] / W,   var'[p][i] = sum_q w(p,q)^2 (var[q][i] / (c_q (c_q - 1))) / W^2,   W = sum_q w(p,q)
+ */
+typedef struct drt_denoise
+{
+    uint32_t radius, patch, flags; /* radius 0..10, patch 0..3; flags: 0 (reserved). Suggested: 5, 1 */
+    uint32_t unusable;             /* out: pixels that passed through */
+    double   k, alpha;             /* finite, k > 0, alpha >= 0. Suggested: 1, 1 */
+    double   kernel_ms;            /* out: HIP-event time of the three kernels */
+} drt_denoise;                     /* 40 bytes */
+/* Filters the film the context holds -- after drt_render, drt_write_film or either adaptive call -- into two buffers of the context's
+ * own. Synchronises first. Changes no film bit, no count and no render state: drt_render continues afterwards as if it had not been
+ * called. Refused with nothing done: parameters out of range (checked before any device call), DRT_MODE_XYZ, row_stride != 1. */
+int drt_denoise_film(drt_context *ctx, drt_denoise *d);
+/* The result of the last drt_denoise_film, [tile_h*tile_w][S] each; either pointer may be NULL. An error before a drt_denoise_film, and
+ * after anything has changed the film since (drt_render, drt_write_film, drt_reset_film, drt_bind_film, an adaptive call). */
+int drt_read_denoised(drt_context *ctx, double *mean, double *var);
+/* The denoised mean as .bmp pixel bytes: the conversion of drt_read_bgra(ctx, 1, ...) applied to mean'. Same errors. */
+int drt_read_denoised_bgra(drt_context *ctx, uint8_t *bgra);
+/* One-shot on host buffers of a whole tile_w x tile_h film (also the post-process of a stored .spd triplet), on params->device; of
+ * params only tile_w, tile_h, row_stride, mode and device are read. d is in-out. mean or var may be NULL. */
+int drt_denoise_buffers(const drt_scene *scene, const drt_params *params, drt_denoise *d, const double *pixels, const double *avgs,
+                        const double *vars, double *mean, double *var);
+/* Row-cyclic devices hold no neighbours of their own rows: the group gathers its film as drt_group_read_film does and runs the one-shot
+ * form on its first device. Same bits for any device list. */
+int drt_group_denoise(drt_group *g, drt_denoise *d, double *mean, double *var);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */
