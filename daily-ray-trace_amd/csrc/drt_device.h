@@ -226,6 +226,35 @@ __device__ __forceinline__ double line_plane(V3 o, V3 d, V3 pp, V3 pn, V3 un, V3
     return DRT_INF;
 }
 
+/* line_plane for a caller that uses the distance in ONE comparison only, `dist < limit` (strict), and only where `want` holds: the
+ * closest-hit scan (limit = the nearest distance so far, want = true) and the shadow scan (limit = the distance to the light,
+ * want = the lane is still visible). Same operations in the same order up to l; the rectangle test -- hit point, j = i - pp, j.u,
+ * j.v, about half of the function -- runs only for lanes with want && 0 <= l < limit, and the compiler puts it behind one branch
+ * that a wave without such a lane skips. Every other lane gets DRT_INF. For the caller's comparison that is what line_plane gives:
+ *   - !want: the caller does not look at the distance.
+ *   - l < 0 or l NaN (l >= 0.0 is false for both): line_plane returns DRT_INF itself.
+ *   - l >= limit, or limit NaN: line_plane returns l or DRT_INF; l < limit is false and DRT_INF < limit is false for every limit.
+ *   - l = -0 (a quotient that underflows, or a zero numerator over a negative dn): -0 >= 0.0 is true, and -0 < limit as 0 < limit;
+ *     the lane goes on to the rectangle test as in line_plane and returns the same -0 or DRT_INF.
+ *   - otherwise the rectangle test is line_plane's, on the same l: the same bits come back.
+ * So (result < limit) == (want && line_plane(...) < limit) always, and where that is true the result is line_plane's, bit for bit.
+ * No floating-point operation is added or changed. The four rectangle comparisons are joined by `&`: all four operands are computed
+ * anyway and a comparison has no side effect, so the value is the short-circuit form's, in one exec region instead of three. */
+__device__ __forceinline__ double line_plane_limited(V3 o, V3 d, V3 pp, V3 pn, V3 un, V3 vn, double ul, double vl, double limit, bool want)
+{
+    double dn = v_dot(d, pn);
+    if (dn == 0.0) return DRT_INF;
+    V3 o_to_p = v_sub(pp, o);
+    double l = v_dot(o_to_p, pn) / dn;
+    if (!(want && l >= 0.0 && l < limit)) return DRT_INF;
+    V3 i = v_sum(o, v_mul(d, l));
+    V3 j = v_sub(i, pp);
+    double ju = v_dot(j, un);
+    double jv = v_dot(j, vn);
+    if ((0.0 <= ju) & (ju <= ul) & (0.0 <= jv) & (jv <= vl)) return l;
+    return DRT_INF;
+}
+
 /* ---- pow(x, y) as bp_glossy_bdsf uses it (src/bdsf.c:116): x in [0, 1], y the material's shininess ------------------------ */
 /* For an integer shininess (what scenes carry: 100, 32, ...) by repeated squaring in double-double arithmetic: the value carried is
  * hi + lo with |lo| <= ulp(hi) / 2, every product is exact to 2^-104, so after the <= 20 products of an exponent below 1024 the

@@ -328,11 +328,49 @@ __device__ __forceinline__ uint32_t scan_type(const SceneView &sv, uint32_t i)
 {
     return ROWS ? row_type(sv.rows + (size_t)i * SR_STRIDE) : sv.surf_type[i];
 }
-template <bool ROWS>
-__device__ __forceinline__ double scan_distance(const SceneView &sv, uint32_t i, uint32_t type, V3 o, V3 d)
+/* row_distance for a scan that only asks `dist < limit`, and only of lanes with `want`: a plane's rectangle test runs where it can
+ * matter (see line_plane_limited). A sphere is tested as ever: its square root is already skipped by a wave without a hit. */
+__device__ __forceinline__ double row_distance_limited(const double *r, uint32_t type, V3 o, V3 d, double limit, bool want)
 {
-    return ROWS ? row_distance(sv.rows + (size_t)i * SR_STRIDE, type, o, d) : surface_distance(sv, i, type, o, d);
+    if (type == DRT_GEO_SPHERE) return line_sphere(o, d, row3(r, SF_PX), r[SF_RADIUS]);
+    return line_plane_limited(o, d, row3(r, SF_PX), row3(r, SF_NX), row3(r, SF_UNX), row3(r, SF_VNX), r[SF_ULEN], r[SF_VLEN], limit, want);
 }
+/* The scans use a distance in one strict comparison with `limit`, for lanes with `want` only; the row scans say so to the plane
+ * test, the SoA scan (scenes outside LDS, where the hierarchy does the pruning) computes every distance in full. */
+template <bool ROWS>
+__device__ __forceinline__ double scan_distance(const SceneView &sv, uint32_t i, uint32_t type, V3 o, V3 d, double limit, bool want)
+{
+    return ROWS ? row_distance_limited(sv.rows + (size_t)i * SR_STRIDE, type, o, d, limit, want) : surface_distance(sv, i, type, o, d);
+}
+
+#ifdef DRT_BRANCH_STATS
+/* Measurement build only: one plane step of a row scan, as the wave takes it. Returns 1 when no lane of the wave needs the rectangle
+ * test, i.e. when the branch behind line_plane_limited's division is taken by the whole wave. Recomputes dn and l the same way. */
+__device__ __forceinline__ uint32_t scan_plane_step_skipped(const double *r, V3 o, V3 d, double limit, bool want)
+{
+    const V3 pp = row3(r, SF_PX), pn = row3(r, SF_NX);
+    const double dn = v_dot(d, pn);
+    const double l = v_dot(v_sub(pp, o), pn) / dn;
+    return __any(dn != 0.0 && want && l >= 0.0 && l < limit) ? 0u : 1u;
+}
+#define DRT_SCAN_STATS_PARAM , uint64_t *scan_stats = nullptr
+#define DRT_SCAN_STATS_ARG(p) , (p)
+/* counted by the first active lane of the step; the kernel sums over lanes at its end. scan_stats[0]: plane steps, [1]: skipped */
+#define DRT_SCAN_STATS_STEP(rowp, o, d, limit, want)                                                                  \
+    if (ROWS && scan_stats && type == DRT_GEO_PLANE)                                                                    \
+    {                                                                                                                   \
+        const uint32_t skipped_ = scan_plane_step_skipped((rowp), (o), (d), (limit), (want));                          \
+        if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((long long)__ballot(1)) - 1))                                    \
+        {                                                                                                               \
+            scan_stats[0] += 1;                                                                                         \
+            scan_stats[1] += skipped_;                                                                                  \
+        }                                                                                                               \
+    }
+#else
+#define DRT_SCAN_STATS_PARAM
+#define DRT_SCAN_STATS_ARG(p)
+#define DRT_SCAN_STATS_STEP(rowp, o, d, limit, want)
+#endif
 
 #define BVH_STACK 32 /* levels of the deepest tree the builder hands out = entries a traversal stack can need */
 
@@ -435,7 +473,7 @@ __device__ __forceinline__ void bvh_children(const BvhNode &n, const Ray32 &r, f
 
 /* points_mutually_visible, src/daily_ray_trace.c:238-270 */
 template <bool ROWS = false>
-__device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 p0, V3 p1)
+__device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 p0, V3 p1 DRT_SCAN_STATS_PARAM)
 {
     V3 dir = v_normalise(v_sub(p1, p0));
     V3 o = v_sum(p0, v_mul(dir, DRT_VIS_FUDGE));
@@ -445,7 +483,9 @@ __device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 
     {
         uint32_t type = scan_type<ROWS>(sv, i);
         if (type != DRT_GEO_SPHERE && type != DRT_GEO_PLANE) continue;
-        double dist = scan_distance<ROWS>(sv, i, type, o, dir);
+        DRT_SCAN_STATS_STEP(sv.rows + (size_t)i * SR_STRIDE, o, dir, vis_dist, visible)
+        /* a lane that is no longer visible asks nothing of the remaining surfaces */
+        double dist = scan_distance<ROWS>(sv, i, type, o, dir, vis_dist, visible);
         if (visible && dist < vis_dist) visible = false; /* the reference breaks here; later surfaces cannot undo it */
         if (!__any(visible)) break;
     }
@@ -462,7 +502,7 @@ struct HitPoint /* scene_point, src/daily_ray_trace.h:113-125 */
 
 /* find_ray_intersection, src/daily_ray_trace.c:334-403 */
 template <bool ROWS = false>
-__device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const DevScene &sc, HitPoint &ip, V3 ro, V3 rd)
+__device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const DevScene &sc, HitPoint &ip, V3 ro, V3 rd DRT_SCAN_STATS_PARAM)
 {
     double min_dist = DRT_INF;
     int index = -1;
@@ -472,7 +512,8 @@ __device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const
         {
             uint32_t type = scan_type<ROWS>(sv, i);
             if (type != DRT_GEO_SPHERE && type != DRT_GEO_PLANE) continue;
-            double dist = scan_distance<ROWS>(sv, i, type, ro, rd);
+            DRT_SCAN_STATS_STEP(sv.rows + (size_t)i * SR_STRIDE, ro, rd, min_dist, true)
+            double dist = scan_distance<ROWS>(sv, i, type, ro, rd, min_dist, true);
             if (dist < min_dist)
             {
                 min_dist = dist;
@@ -1019,7 +1060,7 @@ __device__ __forceinline__ const TraceConst &trace_const(const double *lds)
 #ifdef DRT_BRANCH_STATS
 /* Measurement build only (-DDRT_BRANCH_STATS, never in the product): per wave-iteration that shades, which samplers and evaluator
  * branches its lanes take. The last wave of a launch to finish prints the launch's totals and clears them. */
-#define DRT_BS_WORDS 16
+#define DRT_BS_WORDS 20 /* [16], [17]: plane steps of the closest-hit scans and how many the whole wave skipped; [18], [19]: of the shadow scans */
 __device__ unsigned long long drt_branch_stats[DRT_BS_WORDS];
 __device__ unsigned int drt_branch_waves_done;
 #endif
@@ -1280,7 +1321,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         {
             /* ---- one iteration of cast_ray's loop, src/daily_ray_trace.c:446-474 ---- */
             HitPoint ip;
-            find_ray_intersection<SCENE_IN_LDS>(sv, LC.sc, ip, ro, rd);
+            find_ray_intersection<SCENE_IN_LDS>(sv, LC.sc, ip, ro, rd DRT_SCAN_STATS_ARG(bs + 16));
             n_scans += 1;
             if (record_hits)
             {
@@ -1342,7 +1383,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                         light_position = v_sum(v_sum(lpos, v_mul(lu, u)), v_mul(lv, v));
                     }
                     n_shadow += 1;
-                    bool visible = points_mutually_visible<SCENE_IN_LDS>(sv, ip.position, light_position);
+                    bool visible = points_mutually_visible<SCENE_IN_LDS>(sv, ip.position, light_position DRT_SCAN_STATS_ARG(bs + 18));
                     uint64_t *lrec = vrec + REC_VERTEX_WORDS + (uint64_t)l * REC_LIGHT_WORDS;
                     uint32_t lflags = 0;
                     if (visible)
@@ -1533,8 +1574,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
         unsigned long long t[DRT_BS_WORDS];
         for (int k = 0; k < DRT_BS_WORDS; k += 1) t[k] = atomicExch(&drt_branch_stats[k], 0ull);
         printf("DRT_BRANCH_STATS iters %llu lanes %llu | disc %llu %llu | ggx %llu %llu | coin %llu %llu | spec %llu %llu | all4 %llu | "
-               "loop %llu again %llu | half %llu eqt %llu | uniform %llu\n",
-               t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15]);
+               "loop %llu again %llu | half %llu eqt %llu | uniform %llu | closest plane steps %llu skipped %llu | shadow plane steps %llu skipped %llu\n",
+               t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15], t[16], t[17], t[18], t[19]);
         drt_branch_waves_done = 0u;
     }
 #endif
@@ -2750,6 +2791,7 @@ enum
     DRT_UNIT_FS_CONDUCTOR,      /* in: ir tr te cos                        out: R                         src/bdsf.c:78-101      */
     DRT_UNIT_SEED_AND_DRAW,     /* in: path key (u64 bits)                 out: state (bits), first rng() src/rng.c:1-12, SURVEY 8a-R */
     DRT_UNIT_BVH_BOX,           /* in: o[3] d[3] lo[3] hi[3] (box in f32 values) out: the f32 slab test's entry bound, or < 0 = box rejected (bvh_box_entry) */
+    DRT_UNIT_LINE_PLANE_LIMITED, /* in: LINE_PLANE's 18, limit, want (0 = false) out: line_plane_limited: t where want && t < limit, else +inf */
     DRT_UNIT_COUNT
 };
 
@@ -2816,6 +2858,14 @@ __global__ void drt_unit_kernel(int func, const double *__restrict__ in, uint32_
                 n.hi[0][k] = (float)a[9 + k];
             }
             o[0] = (double)bvh_box_entry(n, 0, bvh_ray32(V(0), V(3)));
+            break;
+        }
+        case DRT_UNIT_LINE_PLANE_LIMITED:
+        {
+            /* as the row scans call it: the constants of DRT_UNIT_LINE_PLANE, the scan's limit and the lane's `want` */
+            V3 u = V(12), v = V(15);
+            double ul = v_length(u), vl = v_length(v);
+            o[0] = line_plane_limited(V(0), V(3), V(6), V(9), v_div(u, ul), v_div(v, vl), ul, vl, a[18], a[19] != 0.0);
             break;
         }
         default: break;

@@ -2787,8 +2787,8 @@ extern "C" int drt_selftest_unit(int device, int func, const double *in, uint32_
     if (func < 0 || func >= DRT_UNIT_COUNT) return fail(-1, "unknown unit function %d", func);
     if (!in || !out || in_stride == 0 || out_stride == 0) return fail(-1, "null argument");
     /* what each function reads and writes per record: a caller with narrower records would make the kernel read past its buffers */
-    static const uint32_t need_in[DRT_UNIT_COUNT] = {10, 18, 6, 8, 6, 1, 1, 7, 10, 3, 4, 1, 12};
-    static const uint32_t need_out[DRT_UNIT_COUNT] = {1, 1, 3, 3, 9, 4, 4, 1, 1, 1, 1, 2, 1};
+    static const uint32_t need_in[DRT_UNIT_COUNT] = {10, 18, 6, 8, 6, 1, 1, 7, 10, 3, 4, 1, 12, 20};
+    static const uint32_t need_out[DRT_UNIT_COUNT] = {1, 1, 3, 3, 9, 4, 4, 1, 1, 1, 1, 2, 1, 1};
     if (in_stride < need_in[func] || out_stride < need_out[func])
         return fail(-1, "unit function %d needs %u doubles in and %u out per record", func, need_in[func], need_out[func]);
     if (n == 0) return 0;

@@ -413,7 +413,9 @@ int drt_selftest_path_ids(int device, const uint64_t *bases, uint32_t n_draws, c
  *  10 fs_conductor_reflectance  src/bdsf.c:78-101        in ir tr te cos (one wavelength)    out R
  *  11 seed_rng + rng            src/rng.c:1-12 (8a-R)    in path key (u64 bits)              out state (u64 bits), first rng()
  *  12 the hierarchy's f32 box test (prunes the scan of src/daily_ray_trace.c:340-364; no reference counterpart)
- *                                                          in o[3] d[3] lo[3] hi[3]            out lower bound of the entry distance, < 0: rejected */
+ *                                                          in o[3] d[3] lo[3] hi[3]            out lower bound of the entry distance, < 0: rejected
+ *  13 line_plane_limited, the plane test of the LDS row scans (csrc/drt_device.h; the reference's function cut short where the scan's
+ *     one comparison `t < limit` cannot come out true)    in func 1's 18, limit, want (0 = false)  out t where want and t < limit, else +inf */
 int drt_selftest_unit(int device, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
 
 /* Material-layer self-test: runs n records (`in_stride` doubles in, `out_stride` doubles out per record) against the device scene of

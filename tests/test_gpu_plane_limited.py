@@ -1,0 +1,167 @@
+"""The plane test of the LDS row scans, line_plane_limited (csrc/drt_device.h), one record at a time on the device through
+drt_selftest_unit, against line_plane on the same record.
+
+A scan uses a surface's distance in one strict comparison, `dist < limit`, and only for lanes with `want` (the closest-hit scan:
+limit = the nearest distance so far, want = true; the shadow scan: limit = the distance to the light, want = still visible).
+line_plane_limited leaves out the rectangle test where that comparison cannot come out true. What it owes the scans, for EVERY record:
+
+    (out < limit) == (want and line_plane < limit)
+    where that holds, out has line_plane's bits; everywhere else out is +inf.
+
+Records: the 1000 plane records of tests/golden/unit_geometry.npz (whose line_plane is the compiled reference's answer) and
+hand-made ones (line_plane checked against the oracle): a ray parallel to the plane (dn = 0), l = +0 and l = -0, a NaN direction,
+quotients that underflow to +0, to -0 and to a subnormal, hits on the rectangle's edges and corners and one ulp outside, a plane
+behind the ray. Limits, for each record: +inf, 0, the record's own l = ((pp - o) . n) / (d . n) -- whatever the rectangle test then
+says -- and its two neighbouring doubles, also -0 and NaN. Every (record, limit) with want true and with want false.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import oracle_py as O
+import pydrt
+
+INF_BITS = np.float64(np.inf).view(np.uint64)
+
+
+def _dot(a, b):
+    """v_dot's order of operations (no fused multiply-add): the same bits as on the device"""
+    return a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]
+
+
+def quotient(rec):
+    """l as line_plane computes it, before any test: NaN or +-inf where dn = 0"""
+    o, d, pp, pn = rec[:, 0:3], rec[:, 3:6], rec[:, 6:9], rec[:, 9:12]
+    with np.errstate(all="ignore"):
+        return _dot(pp - o, pn) / _dot(d, pn)
+
+
+def hand_made():
+    pp, pn, pu, pv = [-0.5, -0.5, 0], [0, 0, 1], [1, 0, 0], [0, 1, 0]
+    plane = pp + pn + pu + pv
+    nan = float("nan")
+    rows = [
+        [0, 0, 1, 1, 0, 0] + plane,               # parallel: dn = 0, numerator not 0
+        [0, 0, 0, 1, 0, 0] + plane,               # parallel and in the plane: 0 / 0
+        [0, 0, 0, 0, 0, 1] + plane,               # on the plane: the numerator is (-0 + -0) + 0 = +0, so l = +0
+        [0, 0, 0, 0, 0, -1] + plane,              # on the plane, dn < 0: l = +0 / -1 = -0
+        [0.25, 0.25, 0, 0.3, 0.1, 2] + plane,     # on the plane, slanted
+        [0.25, 0.25, 0, 0.3, 0.1, -2] + plane,
+        [0, 0, 1, nan, nan, nan] + plane,         # NaN direction (total internal reflection)
+        [0, 0, 1, 0, nan, -1] + plane,            # one NaN component, multiplied by a zero of the normal
+        [0, 0, 1e-300, 0, 0, -1e30] + plane,      # quotient underflows to +0
+        [0, 0, 1e-300, 0, 0, 1e30] + plane,       # quotient underflows to -0: counts as >= 0, the hit point is o itself
+        [0, 0, -1e-300, 0, 0, 1e30] + plane,      # +0 from the other side
+        [0, 0, 1e-300, 0, 0, -1e10] + plane,      # subnormal quotient
+        [0, 0, 1e-300, 0, 0, 1e10] + plane,       # negative subnormal: behind
+        [0.9, 0.9, 1e-300, 0, 0, 1e30] + plane,   # -0, outside the rectangle
+        [0, 0, 1, 0, 0, 1] + plane,               # plane behind the ray
+        [0, 0, -3, 0, 0, 1] + plane,              # from below
+        [0, 0, 1, 0.2, -0.1, -4] + plane,         # l < 1, direction not normalised
+    ]
+    # hits on the rectangle's edges and corners (inclusive bounds), one ulp and a little outside
+    for (x, y) in ((-0.5, -0.5), (0.5, 0.5), (0.5, -0.5), (-0.5, 0.5), (0.5, 0), (0, 0.5), (-0.5, 0), (0, -0.5),
+                   (np.nextafter(0.5, 1), 0), (np.nextafter(-0.5, -1), 0), (0, np.nextafter(0.5, 1)), (0, np.nextafter(-0.5, -1)),
+                   (0.5000001, 0), (0, -0.5000001)):
+        rows.append([x, y, 1, 0, 0, -1] + plane)
+        rows.append([x, y, 2, 0, 0, -0.5] + plane)
+    # a slanted plane with edges of unequal length, and one whose edge has length 0 (u / |u| is NaN: nothing is ever hit)
+    slanted = [1, 2, 3] + [0, 0.6, 0.8] + [2, 0, 0] + [0, 2.4, -1.8]
+    for o, d in (([2, 3, 9], [0, -0.6, -0.8]), ([1, 2, 9], [0, 0, -1]), ([3, 2, 9], [0, 0, -1]), ([2, 3, 2], [0.1, 0.6, 0.8]),
+                 ([3.0000001, 2, 9], [0, 0, -1])):
+        rows.append(o + d + slanted)
+    rows.append([0, 0, 1, 0, 0, -1] + pp + pn + [0, 0, 0] + pv)
+    return np.array(rows, dtype=np.float64)
+
+
+def limits_for(l):
+    """[n][7]: the limits each record meets"""
+    with np.errstate(all="ignore"):
+        return np.stack([np.full_like(l, np.inf), np.zeros_like(l), l, np.nextafter(l, -np.inf), np.nextafter(l, np.inf),
+                         np.full_like(l, -0.0), np.full_like(l, np.nan)], axis=1)
+
+
+def check(rec, lp):
+    """the contract above for every (record, limit, want); lp = line_plane of each record, on the device"""
+    l = quotient(rec)
+    lim = limits_for(l)
+    n, k = lim.shape
+    # where line_plane hits, it returns the quotient itself: the limits `l` and its neighbours really are at the boundary
+    hit = np.isfinite(lp)
+    assert np.array_equal(lp[hit].view(np.uint64), l[hit].view(np.uint64))
+    for want in (1.0, 0.0):
+        full = np.hstack([np.repeat(rec, k, axis=0), lim.reshape(-1, 1), np.full((n * k, 1), want)])
+        out = pydrt.selftest_unit(pydrt.UNIT_LINE_PLANE_LIMITED, full)[:, 0]
+        limit = full[:, 18]
+        base = np.repeat(lp, k)
+        with np.errstate(invalid="ignore"):
+            expect = (want != 0.0) & (base < limit)
+            got = out < limit
+        bad = np.nonzero(got != expect)[0]
+        assert bad.size == 0, "want %g: (out < limit) differs from (want and line_plane < limit) for %d of %d, first: record %s limit %r line_plane %r out %r" % (
+            want, bad.size, n * k, full[bad[0], :18].tolist(), limit[bad[0]], base[bad[0]], out[bad[0]])
+        ob, bb = out.view(np.uint64), base.view(np.uint64)
+        assert np.array_equal(ob[expect], bb[expect]), "want %g: a distance below the limit is not line_plane's, bit for bit" % want
+        assert np.all(ob[~expect] == INF_BITS), "want %g: a distance the scan cannot use is not +inf" % want
+        if want:
+            assert expect.any() and (~expect).any()
+        else:
+            assert not expect.any()
+    return l
+
+
+@pytest.mark.gpu
+def test_limited_plane_test_on_the_reference_records(golden_dir):
+    g = np.load(os.path.join(golden_dir, "unit_geometry.npz"), allow_pickle=False)
+    rec = np.hstack([g["pl_o"], g["pl_d"], g["pl_p"], g["pl_n"], g["pl_u"], g["pl_v"]])
+    lp = pydrt.selftest_unit(pydrt.UNIT_LINE_PLANE, rec)[:, 0]
+    assert np.array_equal(lp, g["pl_t"])  # the compiled reference's answers
+    l = check(rec, lp)
+    # the fixture has what the limits are about: hits, misses of the rectangle with l >= 0, planes behind, parallel rays
+    with np.errstate(invalid="ignore"):
+        assert np.isfinite(lp).any() and (np.isinf(lp) & (l >= 0.0)).any() and (l < 0.0).any() and (~np.isfinite(l)).any()
+
+
+@pytest.mark.gpu
+def test_limited_plane_test_on_hand_made_records():
+    rec = hand_made()
+    L = O.oracle_lib()
+    want = np.array([L.drt_oracle_line_plane(O._v3(r[0:3]), O._v3(r[3:6]), O._v3(r[6:9]), O._v3(r[9:12]), O._v3(r[12:15]), O._v3(r[15:18]))
+                     for r in rec])
+    lp = pydrt.selftest_unit(pydrt.UNIT_LINE_PLANE, rec)[:, 0]
+    assert np.array_equal(lp.view(np.uint64), want.view(np.uint64))  # NaN-free: line_plane returns l or +inf
+    l = check(rec, lp)
+    neg_zero = np.float64(-0.0).view(np.uint64)
+    # the cases the records were made for are really there
+    assert (lp.view(np.uint64) == neg_zero).any() and ((lp == 0.0) & ~np.signbit(lp)).any()  # -0 and +0 returned as hits
+    assert np.isnan(l).any() and np.isinf(l).any()                                            # NaN direction, 0 / 0, x / 0
+    assert ((l != 0.0) & (np.abs(l) < 2.3e-308)).any()                                        # subnormal quotients
+    with np.errstate(invalid="ignore"):
+        assert (np.isinf(lp) & (l == 0.0)).any() and (np.isinf(lp) & (l > 0.0)).any() and (l < 0.0).any()
+
+
+@pytest.mark.gpu
+def test_unit_entry_refuses_narrow_records():
+    with pytest.raises(RuntimeError):
+        pydrt.selftest_unit(pydrt.UNIT_LINE_PLANE_LIMITED, np.zeros((4, 18)))
+
+
+def test_unit_tables_agree():
+    """the kernel's enum, the launcher's record widths, the header's list and the Python ids describe the same functions"""
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    kernels = open(os.path.join(repo, "daily-ray-trace_amd", "csrc", "drt_kernels.h")).read()
+    enum = re.search(r"enum\s*\{\s*(DRT_UNIT_LINE_SPHERE = 0,.*?)DRT_UNIT_COUNT", kernels, re.S).group(1)
+    names = re.findall(r"^\s*(DRT_UNIT_\w+)", enum, re.M)
+    launcher = open(os.path.join(repo, "daily-ray-trace_amd", "csrc", "drt_launcher.hip")).read()
+    need_in = [int(x) for x in re.search(r"need_in\[DRT_UNIT_COUNT\] = \{([^}]*)\}", launcher).group(1).split(",")]
+    need_out = [int(x) for x in re.search(r"need_out\[DRT_UNIT_COUNT\] = \{([^}]*)\}", launcher).group(1).split(",")]
+    assert len(names) == len(need_in) == len(need_out) == len(pydrt._UNIT_OUT)
+    for i, name in enumerate(names):
+        assert getattr(pydrt, name[len("DRT_"):]) == i, name
+        assert pydrt._UNIT_OUT[i] == need_out[i], name
+    assert names[-1] == "DRT_UNIT_LINE_PLANE_LIMITED" and names[-2] == "DRT_UNIT_BVH_BOX"
+    assert need_in[-1] == need_in[names.index("DRT_UNIT_LINE_PLANE")] + 2 and need_out[-1] == 1
+    header = open(os.path.join(repo, "include", "drt_hip.h")).read()
+    assert re.search(r"^ \*\s+%d line_plane_limited" % (len(names) - 1), header, re.M)
