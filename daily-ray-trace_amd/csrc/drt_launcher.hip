@@ -7,6 +7,7 @@
 #include "drt_bvh_kernels.h"
 #include "drt_adaptive_kernels.h"
 #include "drt_denoise_kernels.h"
+#include "drt_feature_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -126,6 +127,17 @@ struct drt_context
     double  *d_dn_mean = nullptr, *d_dn_var = nullptr, *d_dn_guide = nullptr, *d_dn_weights = nullptr, *d_dn_wsum = nullptr;
     uint32_t *d_dn_unusable = nullptr;
     uint32_t dn_window_cap = 0;            /* window entries per pixel d_dn_weights holds */
+    /* first-hit features (drt_render_features): what the colour table is made from, the result, and the film it took its counts from */
+    std::vector<drt_material> ft_mats;     /* the scene's materials and SPD rows as the caller gave them */
+    std::vector<double> ft_spds;
+    uint32_t ft_n_spd = 0, ft_S = 0;
+    double  *d_ft_mean = nullptr, *d_ft_m2 = nullptr, *d_ft_colour = nullptr;
+    int32_t *d_ft_ids = nullptr;
+    uint32_t *d_ft_counts = nullptr, *d_ft_report = nullptr;
+    unsigned long long *d_ft_info = nullptr;
+    hipEvent_t ft_ev[2] = {nullptr, nullptr};
+    bool     ft_valid = false, ft_from_film = false;
+    uint64_t ft_gen = 0;                   /* film_gen at the last drt_render_features */
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -836,6 +848,10 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     }
     int rc = build_device_scene(ctx, scene, reach);
     if (rc) return rc;
+    ctx->ft_mats.assign(scene->materials, scene->materials + scene->num_materials);
+    ctx->ft_n_spd = scene->num_spds;
+    ctx->ft_S = scene->num_wavelengths;
+    ctx->ft_spds.assign(scene->spds, scene->spds + (size_t)scene->num_spds * scene->num_wavelengths);
 
     DevCamera &c = ctx->dcam;
     c.forward = hv(camera->forward); c.right = hv(camera->right); c.up = hv(camera->up);
@@ -1101,6 +1117,15 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_dn_weights);
     (void)hipFree(ctx->d_dn_wsum);
     (void)hipFree(ctx->d_dn_unusable);
+    (void)hipFree(ctx->d_ft_mean);
+    (void)hipFree(ctx->d_ft_m2);
+    (void)hipFree(ctx->d_ft_colour);
+    (void)hipFree(ctx->d_ft_ids);
+    (void)hipFree(ctx->d_ft_counts);
+    (void)hipFree(ctx->d_ft_report);
+    (void)hipFree(ctx->d_ft_info);
+    for (hipEvent_t e : ctx->ft_ev)
+        if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(ctx->h_active);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -2695,6 +2720,235 @@ extern "C" int drt_group_denoise(drt_group *g, drt_denoise *d, double *mean, dou
     const double *d_rows[4] = {first->dsc.spds + (size_t)first->cmf_rw * S, first->dsc.spds + (size_t)first->cmf_x * S,
                                first->dsc.spds + (size_t)first->cmf_y * S, first->dsc.spds + (size_t)first->cmf_z * S};
     return denoise_host_film(d_rows, g->S, g->tile_w, g->tile_h, first->interval, d, px.data(), av.data(), va.data(), mean, var);
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* First-hit feature buffers (kernels in drt_feature_kernels.h)              */
+
+static size_t feature_lds_bytes(uint32_t n_surf)
+{
+    return (size_t)(SR_STRIDE + SF_COUNT) * n_surf * 8 + (((size_t)2 * n_surf * 4 + 7) & ~(size_t)7);
+}
+
+/* [num_materials][3], the rule's "material colour": sums sequential over ascending wavelength, no contraction (the host is built
+ * with -ffp-contract=off, like the kernels) */
+static int feature_colour_table(const drt_context *ctx, std::vector<double> *table)
+{
+    const uint32_t S = ctx->ft_S;
+    const double *spds = ctx->ft_spds.data();
+    const double *rw = spds + (size_t)ctx->cmf_rw * S;
+    const double *cmf[3] = {spds + (size_t)ctx->cmf_x * S, spds + (size_t)ctx->cmf_y * S, spds + (size_t)ctx->cmf_z * S};
+    double N = 0.0;
+    for (uint32_t i = 0; i < S; i += 1) N += (cmf[1][i] * rw[i]);
+    N *= ctx->interval;
+    const double scale = ctx->interval / N;
+    const std::vector<double> zeros(S, 0.0);
+    std::vector<double> r(S);
+    table->assign(ctx->ft_mats.size() * 3, 0.0);
+    for (size_t m = 0; m < ctx->ft_mats.size(); m += 1)
+    {
+        const drt_material &mat = ctx->ft_mats[m];
+        const int32_t idx[4] = {mat.emission_spd, mat.diffuse_spd, mat.glossy_spd, mat.mirror_spd};
+        const double *row[4];
+        for (int k = 0; k < 4; k += 1)
+        {
+            if (idx[k] >= 0 && (uint32_t)idx[k] >= ctx->ft_n_spd) return fail(-1, "features: material %zu names SPD %d of %u", m, idx[k], ctx->ft_n_spd);
+            row[k] = idx[k] >= 0 ? spds + (size_t)idx[k] * S : zeros.data();
+        }
+        for (uint32_t i = 0; i < S; i += 1) r[i] = mat.is_emissive ? row[0][i] : (row[1][i] + row[2][i]) + row[3][i];
+        for (int k = 0; k < 3; k += 1)
+        {
+            double acc = 0.0;
+            for (uint32_t i = 0; i < S; i += 1) acc += (cmf[k][i] * r[i] * rw[i]);
+            (*table)[m * 3 + k] = acc * scale;
+        }
+    }
+    return 0;
+}
+
+static int features_check(const drt_features *f)
+{
+    if (f->flags != 0) return fail(-1, "features: flags = %u: 0 (reserved)", f->flags);
+    if (f->n_samples && (uint64_t)f->first_sample + f->n_samples > 0xFFFFFFFFull)
+        return fail(-1, "features: first_sample %u + %u samples: sample numbers are 32 bits", f->first_sample, f->n_samples);
+    return 0;
+}
+
+/* The film complete, the buffers there, and with n_samples = 0 every pixel's count from its filter sum. Refuses before anything is
+ * rendered; the film, the adaptive counts and the render state stay as they are. */
+static int features_prepare(drt_context *ctx, const drt_features *f)
+{
+    if (f->n_samples == 0 && ctx->xyz_mode)
+        return fail(-4, "features: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)");
+    if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "features: a tile of %llu pixels", (unsigned long long)ctx->n_pix);
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = drt_synchronize(ctx);
+    if (rc) return rc;
+    ctx->ft_valid = false;
+    const size_t n_pix = (size_t)ctx->n_pix;
+    if (!ctx->d_ft_mean) HIP_TRY(hipMalloc((void **)&ctx->d_ft_mean, n_pix * DRT_FEATURE_CHANNELS * 8));
+    if (!ctx->d_ft_m2) HIP_TRY(hipMalloc((void **)&ctx->d_ft_m2, n_pix * DRT_FEATURE_CHANNELS * 8));
+    if (!ctx->d_ft_ids) HIP_TRY(hipMalloc((void **)&ctx->d_ft_ids, n_pix * sizeof(int32_t)));
+    if (!ctx->d_ft_info) HIP_TRY(hipMalloc((void **)&ctx->d_ft_info, FEATURE_INFO_WORDS * sizeof(unsigned long long)));
+    if (!ctx->d_ft_colour) HIP_TRY(hipMalloc((void **)&ctx->d_ft_colour, std::max<size_t>(ctx->ft_mats.size(), 1) * 3 * 8));
+    for (hipEvent_t &e : ctx->ft_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    if (f->n_samples == 0)
+    {
+        if (!ctx->d_ft_counts) HIP_TRY(hipMalloc((void **)&ctx->d_ft_counts, n_pix * sizeof(uint32_t)));
+        if (!ctx->d_ft_report) HIP_TRY(hipMalloc((void **)&ctx->d_ft_report, 2 * sizeof(uint32_t)));
+        uint32_t report[2] = {0xFFFFFFFFu, 0u};
+        HIP_TRY(hipMemcpyAsync(ctx->d_ft_report, report, sizeof(report), hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(drt_feature_counts_kernel, dim3((uint32_t)((n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+                           ctx->d_pixels, ctx->dsc.S, (uint32_t)n_pix, ctx->d_ft_counts, ctx->d_ft_report);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(report, ctx->d_ft_report, sizeof(report), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (report[0] != 0xFFFFFFFFu)
+        {
+            double sum = 0.0;
+            HIP_TRY(hipMemcpy(&sum, ctx->d_pixels + (size_t)report[0] * (ctx->dsc.S + 1) + ctx->dsc.S, sizeof(sum), hipMemcpyDeviceToHost));
+            return fail(-7, "features: tile pixel %u (column %u, row %u of the tile) holds the filter sum %g: with n_samples = 0 a pixel's sample count is its filter sum, a whole number from 1 to 2^32 - 1 (an empty film has none: give n_samples)",
+                        report[0], report[0] % ctx->params.tile_w, report[0] / ctx->params.tile_w, sum);
+        }
+        if ((uint64_t)f->first_sample + report[1] > 0xFFFFFFFFull)
+            return fail(-1, "features: first_sample %u + %u samples: sample numbers are 32 bits", f->first_sample, report[1]);
+    }
+    return 0;
+}
+
+static int features_enqueue(drt_context *ctx, const drt_features *f)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::vector<double> table;
+    int rc = feature_colour_table(ctx, &table);
+    if (rc) return rc;
+    if (!table.empty()) HIP_TRY(hipMemcpy(ctx->d_ft_colour, table.data(), table.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(ctx->d_ft_info, 0, FEATURE_INFO_WORDS * sizeof(unsigned long long), ctx->stream));
+    const drt_params &p = ctx->params;
+    FeatureParams fp{};
+    fp.width = p.width; fp.height = p.height; fp.x0 = p.x0; fp.y0 = p.y0;
+    fp.tile_w = p.tile_w; fp.tile_h = p.tile_h; fp.row_stride = p.row_stride;
+    fp.n_samples = f->n_samples;
+    fp.first_sample = f->first_sample;
+    fp.pixel_scheme = p.pixel_scheme;
+    fp.seed = p.seed;
+    fp.n_pix = ctx->n_pix;
+    fp.counts = f->n_samples ? nullptr : ctx->d_ft_counts;
+    fp.colour = ctx->d_ft_colour;
+    fp.mean = ctx->d_ft_mean;
+    fp.m2 = ctx->d_ft_m2;
+    fp.ids = ctx->d_ft_ids;
+    fp.info = ctx->d_ft_info;
+    const uint32_t grid = (uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK);
+    HIP_TRY(hipEventRecord(ctx->ft_ev[0], ctx->stream));
+    if (ctx->scene_in_lds)
+        hipLaunchKernelGGL(drt_feature_kernel, dim3(grid), dim3(FEATURE_BLOCK), feature_lds_bytes(ctx->dsc.n_surf), ctx->stream, ctx->dsc, ctx->dcam, fp);
+    else
+        hipLaunchKernelGGL(drt_feature_bvh_kernel, dim3(grid), dim3(FEATURE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, fp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->ft_ev[1], ctx->stream));
+    return 0;
+}
+
+/* waits for the kernel; adds this context's share to the report (kernel_ms: the slowest context's) */
+static int features_finish(drt_context *ctx, drt_features *f)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(-100 - (int)e, "feature kernel: %s", hipGetErrorString(e));
+    unsigned long long info[FEATURE_INFO_WORDS] = {0, 0};
+    HIP_TRY(hipMemcpy(info, ctx->d_ft_info, sizeof(info), hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ft_ev[0], ctx->ft_ev[1]));
+    f->empty_pixels += (uint32_t)info[0];
+    f->rays += info[1];
+    f->kernel_ms = std::max(f->kernel_ms, (double)ms);
+    ctx->ft_gen = ctx->film_gen;
+    ctx->ft_from_film = f->n_samples == 0;
+    ctx->ft_valid = true;
+    return 0;
+}
+
+extern "C" int drt_render_features(drt_context *ctx, drt_features *f)
+{
+    if (!ctx || !f) return fail(-1, "null argument");
+    int rc = features_check(f);
+    if (rc) return rc;
+    if ((rc = features_prepare(ctx, f))) return rc;
+    if ((rc = features_enqueue(ctx, f))) return rc;
+    f->empty_pixels = 0;
+    f->rays = 0;
+    f->kernel_ms = 0.0;
+    return features_finish(ctx, f);
+}
+
+static int features_current(drt_context *ctx)
+{
+    if (!ctx->ft_valid) return fail(-4, "no feature buffers: drt_render_features first");
+    if (ctx->ft_from_film && ctx->ft_gen != ctx->film_gen)
+        return fail(-4, "the film has changed since drt_render_features took its counts from it (n_samples = 0): render the features again");
+    return 0;
+}
+
+extern "C" int drt_read_features(drt_context *ctx, double *mean, double *m2, int32_t *ids)
+{
+    if (!ctx) return fail(-1, "null context");
+    int rc = features_current(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)ctx->n_pix * DRT_FEATURE_CHANNELS * 8;
+    if (mean) HIP_TRY(hipMemcpy(mean, ctx->d_ft_mean, bytes, hipMemcpyDeviceToHost));
+    if (m2) HIP_TRY(hipMemcpy(m2, ctx->d_ft_m2, bytes, hipMemcpyDeviceToHost));
+    if (ids) HIP_TRY(hipMemcpy(ids, ctx->d_ft_ids, (size_t)ctx->n_pix * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_feature_bgra(drt_context *ctx, int which, double lo, double hi, uint8_t *bgra)
+{
+    if (!ctx || !bgra) return fail(-1, "null argument");
+    if (which < 0 || which > 2) return fail(-1, "features: which = %d: 0 normal, 1 depth, 2 coverage", which);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !(hi > lo)) return fail(-1, "features: lo = %g, hi = %g: finite numbers, lo below hi", lo, hi);
+    int rc = features_current(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    hipLaunchKernelGGL(drt_feature_bgra_kernel, dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+                       (const double *)ctx->d_ft_mean, ctx->n_pix, which, lo, hi, ctx->d_bgra);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* every device its own rows, side by side: parameters and films checked on all of them before any renders */
+extern "C" int drt_group_render_features(drt_group *g, drt_features *f, double *mean, double *m2, int32_t *ids)
+{
+    g_last_error.clear();
+    if (!g || !f) return fail(-1, "null argument");
+    int rc = features_check(f);
+    if (rc) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = features_prepare(c, f))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = features_enqueue(c, f))) return rc;
+    f->empty_pixels = 0;
+    f->rays = 0;
+    f->kernel_ms = 0.0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = features_finish(c, f))) return rc;
+    const size_t n = g->ctx.size();
+    for (size_t k = 0; k < n; k += 1)
+    {
+        drt_context *c = g->ctx[k];
+        if (!c) continue;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t row8 = (size_t)g->tile_w * DRT_FEATURE_CHANNELS * 8, row4 = (size_t)g->tile_w * sizeof(int32_t);
+        if (mean) HIP_TRY(hipMemcpy2D((char *)mean + k * row8, n * row8, c->d_ft_mean, row8, row8, g->rows[k], hipMemcpyDeviceToHost));
+        if (m2) HIP_TRY(hipMemcpy2D((char *)m2 + k * row8, n * row8, c->d_ft_m2, row8, row8, g->rows[k], hipMemcpyDeviceToHost));
+        if (ids) HIP_TRY(hipMemcpy2D((char *)ids + k * row4, n * row4, c->d_ft_ids, row4, row4, g->rows[k], hipMemcpyDeviceToHost));
+    }
+    return 0;
 }
 
 extern "C" int drt_render_tile_multi(const drt_scene *scene, const drt_camera *camera, const drt_params *params,

@@ -121,3 +121,32 @@ int drt_host_spd_file_to_bmp(const char *spd_path, const char *bmp_path, const f
     free(pixels);
     return rc;
 }
+
+/* drt_read_feature_bgra's byte rule: t = (v - lo) / (hi - lo) clamped to [0, 1], byte = (u8)(t * 255.0 + 0.5), a NaN gives 0 */
+static u8 feature_byte(f64 v, f64 lo, f64 hi)
+{
+    f64 t = (v - lo) / (hi - lo);
+    t = t < 0.0 ? 0.0 : t;
+    t = t > 1.0 ? 1.0 : t;
+    return t == t ? (u8)(t * 255.0 + 0.5) : (u8)0;
+}
+
+void drt_host_feature_bgra(const f64 *mean, u64 n, int which, f64 lo, f64 hi, u8 *bgra)
+{
+    for (u64 p = 0; p < n; p += 1)
+    {
+        const f64 *m = mean + p * DRT_FEATURE_CHANNELS;
+        u8 r, g, b;
+        if (which == 0)
+        {
+            r = feature_byte(m[0], lo, hi);
+            g = feature_byte(m[1], lo, hi);
+            b = feature_byte(m[2], lo, hi);
+        }
+        else r = g = b = feature_byte(m[which == 1 ? 3 : 4], lo, hi);
+        bgra[p * 4 + 0] = b;
+        bgra[p * 4 + 1] = g;
+        bgra[p * 4 + 2] = r;
+        bgra[p * 4 + 3] = 255;
+    }
+}

@@ -103,6 +103,11 @@ typedef struct
     uint32_t denoise, denoise_radius, denoise_patch;
     double   denoise_k, denoise_alpha;
     char     denoise_spd[256], denoise_var_spd[256];
+    /* the first-hit feature buffers (drt_group_render_features, every pixel at the count its film holds) when features != 0: mean and m2 as
+     * two 8-"wavelength" .spd files without a filter column, and <output_spd>.normal.bmp / .depth.bmp / .coverage.bmp; the three standard
+     * outputs and the denoiser's files stay byte for byte what they are without it */
+    uint32_t features;
+    char     features_spd[256], features_m2_spd[256];
 } drt_host_options;
 
 /* the `adaptive` line of a version-3 checkpoint manifest: what the film was rendered with so far */
@@ -192,6 +197,8 @@ const char *drt_host_checkpoint_error(void);
 void drt_host_spectrum_to_rgb(const f64 *cmf, u32 S, f64 interval, const f64 *spd, f64 rgb[3]);
 int  drt_host_write_bmp(const char *path, u32 width, u32 height, const f64 *rgb);
 int  drt_host_write_bmp_bgra(const char *path, u32 width, u32 height, const u8 *bgra);
+/* One feature of a [n][8] feature mean as BMP pixel bytes: drt_read_feature_bgra's rule (include/drt_hip.h) on the host. */
+void drt_host_feature_bgra(const f64 *mean, u64 n, int which, f64 lo, f64 hi, u8 *bgra);
 int  drt_host_spd_file_to_bmp(const char *spd_path, const char *bmp_path, const f64 *cmf);
 
 #ifdef __cplusplus

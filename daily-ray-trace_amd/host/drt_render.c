@@ -229,6 +229,19 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
             printf("Denoised: radius %u, patch %u, k %g, alpha %g: %.3f ms on the device, %u pixels passed through\n", dn.radius, dn.patch, dn.k,
                    dn.alpha, dn.kernel_ms, dn.unusable);
     }
+    /* the first-hit feature buffers of the finished film, every pixel at the count it holds (the film itself is not changed) */
+    f64 *ft_mean = NULL, *ft_m2 = NULL;
+    if (!rc && opt && opt->features)
+    {
+        drt_features ft;
+        memset(&ft, 0, sizeof(ft));
+        ft_mean = (f64 *)malloc(num_pixels * DRT_FEATURE_CHANNELS * sizeof(f64));
+        ft_m2 = (f64 *)malloc(num_pixels * DRT_FEATURE_CHANNELS * sizeof(f64));
+        if (!ft_mean || !ft_m2) rc = -3;
+        if (!rc) rc = drt_group_render_features(ctx, &ft, ft_mean, ft_m2, NULL);
+        if (!rc && !opt->quiet)
+            printf("Features: %llu camera rays, %.3f ms on the device, %u pixels see nothing\n", (unsigned long long)ft.rays, ft.kernel_ms, ft.empty_pixels);
+    }
     /* the .bmp pixels come from the film while it is still on the device (drt_read_bgra: the same bytes as converting the
      * .spd files on the host, host/drt_bmp.c, without reading 1.7 GB back from disk) */
     u8 *bgra[3] = { NULL, NULL, NULL };
@@ -246,6 +259,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     {
         fprintf(stderr, "render_image: the HIP launcher failed (%d): %s\n", rc, drt_last_error());
         for (int k = 0; k < 3; k += 1) free(bgra[k]);
+        free(ft_m2);
+        free(ft_mean);
         free(dn_var);
         free(dn_mean);
         free(dst_vars);
@@ -286,8 +301,40 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         if (!w1) w2 = publish_spd(opt->denoise_var_spd, width, height, S, scene->min_wavelength, scene->wavelength_interval, dn_var);
         if (w1 || w2) fprintf(stderr, "render_image: could not write the denoised .spd outputs\n");
     }
+    int w3 = 0;
+    if (!(w0 || w1 || w2) && ft_mean)
+    {
+        /* mean and m2 as 8-"wavelength" files without a filter column, then the three pictures of the mean; depth from its smallest
+         * to its largest value over the pixels that see anything */
+        static const char *const suffix[3] = { "normal", "depth", "coverage" };
+        w3 = publish_spd(opt->features_spd, width, height, DRT_FEATURE_CHANNELS, scene->min_wavelength, scene->wavelength_interval, ft_mean);
+        if (!w3) w3 = publish_spd(opt->features_m2_spd, width, height, DRT_FEATURE_CHANNELS, scene->min_wavelength, scene->wavelength_interval, ft_m2);
+        f64 zlo = 0.0, zhi = 0.0;
+        int seen = 0;
+        for (u64 px = 0; px < num_pixels; px += 1)
+        {
+            const f64 *m = ft_mean + px * DRT_FEATURE_CHANNELS;
+            if (!(m[4] > 0.0)) continue;
+            if (!seen || m[3] < zlo) zlo = m[3];
+            if (!seen || m[3] > zhi) zhi = m[3];
+            seen = 1;
+        }
+        if (!seen || !(zhi > zlo) || !isfinite(zlo) || !isfinite(zhi)) { zlo = 0.0; zhi = 1.0; }
+        u8 *fb = (u8 *)malloc(num_pixels * 4 + 4);
+        if (!fb) w3 = -1;
+        for (int k = 0; !w3 && k < 3; k += 1)
+        {
+            char path[300], tmp[304];
+            if (snprintf(path, sizeof(path), "%s.%s.bmp", config->output_spd, suffix[k]) >= (int)sizeof(path)) { w3 = -1; break; }
+            snprintf(tmp, sizeof(tmp), "%s.tmp", path);
+            drt_host_feature_bgra(ft_mean, num_pixels, k, k == 0 ? -1.0 : k == 1 ? zlo : 0.0, k == 1 ? zhi : 1.0, fb);
+            if (drt_host_write_bmp_bgra(tmp, width, height, fb) != 0 || rename(tmp, path) != 0) w3 = -1;
+        }
+        free(fb);
+        if (w3) fprintf(stderr, "render_image: could not write the feature outputs\n");
+    }
     /* post-process like the reference's main(): each film -> linear RGB -> BMP (src/win32_main.c:150-152) */
-    if (!(w0 || w1 || w2))
+    if (!(w0 || w1 || w2 || w3))
     {
         int bad = 0;
         for (int k = 0; k < 3; k += 1)
@@ -295,6 +342,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         if (bad) fprintf(stderr, "render_image: could not write one of the .bmp outputs\n");
     }
     for (int k = 0; k < 3; k += 1) free(bgra[k]);
+    free(ft_m2);
+    free(ft_mean);
     free(dn_var);
     free(dn_mean);
     if (stats_out) *stats_out = stats;
@@ -302,7 +351,7 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     free(dst_avgs);
     free(dst_pixels);
     drt_host_free_scene(hs);
-    return (w0 || w1 || w2) ? -2 : 0;
+    return (w0 || w1 || w2 || w3) ? -2 : 0;
 }
 
 /* a whole-string number from the environment: 0 and *out set, -1 (and a message naming the variable) when it does not parse */
@@ -409,6 +458,33 @@ static int denoise_options(const config_arguments *config, drt_host_options *opt
     return 0;
 }
 
+/* DRT_FEATURES*: parsed and checked here, before any device call. DRT_FEATURES=1 turns the first-hit feature buffers on (0: off, anything
+ * else is refused); the two .spd outputs go to DRT_FEATURES_SPD (default <output_spd>.features.spd) and DRT_FEATURES_M2_SPD (default
+ * <variance_spd>.features.spd). */
+static int features_options(const config_arguments *config, drt_host_options *opt)
+{
+    static const char *const names[] = { "DRT_FEATURES_SPD", "DRT_FEATURES_M2_SPD" };
+    const char *e = getenv("DRT_FEATURES");
+    if (e && strcmp(e, "0") != 0 && strcmp(e, "1") != 0) { fprintf(stderr, "render_image: DRT_FEATURES=\"%s\": 0 or 1\n", e); return -1; }
+    if (!e || e[0] == '0')
+    {
+        for (int k = 0; k < 2; k += 1)
+            if (getenv(names[k])) { fprintf(stderr, "render_image: %s is set but DRT_FEATURES is not 1\n", names[k]); return -1; }
+        return 0;
+    }
+    opt->features = 1;
+    e = getenv("DRT_FEATURES_SPD");
+    int n = e ? snprintf(opt->features_spd, sizeof(opt->features_spd), "%s", e)
+              : snprintf(opt->features_spd, sizeof(opt->features_spd), "%s.features.spd", config->output_spd);
+    if (n <= 0 || n >= (int)sizeof(opt->features_spd)) { fprintf(stderr, "render_image: DRT_FEATURES_SPD: a path of 1 to %d characters\n", (int)sizeof(opt->features_spd) - 1); return -1; }
+    e = getenv("DRT_FEATURES_M2_SPD");
+    n = e ? snprintf(opt->features_m2_spd, sizeof(opt->features_m2_spd), "%s", e)
+          : snprintf(opt->features_m2_spd, sizeof(opt->features_m2_spd), "%s.features.spd", config->variance_spd);
+    if (n <= 0 || n >= (int)sizeof(opt->features_m2_spd)) { fprintf(stderr, "render_image: DRT_FEATURES_M2_SPD: a path of 1 to %d characters\n", (int)sizeof(opt->features_m2_spd) - 1); return -1; }
+    if (strcmp(opt->features_spd, opt->features_m2_spd) == 0) { fprintf(stderr, "render_image: DRT_FEATURES_SPD and DRT_FEATURES_M2_SPD name the same file\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -435,5 +511,6 @@ void render_image(config_arguments *config)
     if ((e = getenv("DRT_RESUME"))) opt.resume = (u32)atoi(e);
     if (adaptive_options(config, &opt) != 0) exit(-1);
     if (denoise_options(config, &opt) != 0) exit(-1);
+    if (features_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

@@ -108,6 +108,23 @@ def make_denoise(radius=5, patch=1, k=1.0, alpha=1.0):
     return d
 
 
+FEATURE_CHANNELS = 8  # DRT_FEATURE_CHANNELS: normal x y z, depth, coverage, albedo X Y Z
+FEATURE_NORMAL, FEATURE_DEPTH, FEATURE_COVERAGE = 0, 1, 2  # read_feature_bgra(which)
+
+
+class Features(C.Structure):
+    """drt_features (include/drt_hip.h): the inputs of a first-hit feature pass and, after it, empty_pixels / rays / kernel_ms."""
+    _fields_ = [("n_samples", C.c_uint32), ("first_sample", C.c_uint32), ("flags", C.c_uint32), ("empty_pixels", C.c_uint32),
+                ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+def make_features(n_samples=0, first_sample=0):
+    f = Features()
+    f.n_samples, f.first_sample, f.flags, f.empty_pixels = n_samples, first_sample, 0, 0
+    f.rays, f.kernel_ms = 0, 0.0
+    return f
+
+
 def make_params(width, height, spp, max_depth, seed=1, x0=0, y0=0, tile_w=None, tile_h=None, row_stride=1,
                 first_sample=0, pixel_scheme=FILM_SAMPLE_RANDOM, mode=MODE_SPECTRAL, device=0, batch_spp=0, flags=0):
     p = Params()
@@ -363,6 +380,11 @@ def hip_lib():
             L.drt_read_denoised_bgra.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
             L.drt_denoise_buffers.argtypes = [C.POINTER(Scene), C.POINTER(Params), C.POINTER(Denoise), f64p, f64p, f64p, f64p, f64p]
             L.drt_group_denoise.argtypes = [C.c_void_p, C.POINTER(Denoise), f64p, f64p]
+        if hasattr(L, "drt_render_features"):  # (as drt_selftest_path_ids below)
+            L.drt_render_features.argtypes = [C.c_void_p, C.POINTER(Features)]
+            L.drt_read_features.argtypes = [C.c_void_p, f64p, f64p, i32p]
+            L.drt_read_feature_bgra.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint8)]
+            L.drt_group_render_features.argtypes = [C.c_void_p, C.POINTER(Features), f64p, f64p, i32p]
         L.drt_batch_spp.restype = C.c_uint32
         L.drt_batch_spp.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
@@ -389,7 +411,8 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
                "drt_read_active_list", "drt_render_adaptive_continue", "drt_group_render_adaptive_continue",
-               "drt_denoise_film", "drt_read_denoised", "drt_read_denoised_bgra", "drt_denoise_buffers", "drt_group_denoise"]
+               "drt_denoise_film", "drt_read_denoised", "drt_read_denoised_bgra", "drt_denoise_buffers", "drt_group_denoise",
+               "drt_render_features", "drt_read_features", "drt_read_feature_bgra", "drt_group_render_features"]
 
 
 def _check(rc, what):
@@ -523,6 +546,29 @@ class Renderer:
         _check(self.L.drt_read_denoised_bgra(self.ctx, _ptr(out, C.c_uint8)), "drt_read_denoised_bgra")
         return out
 
+    def render_features(self, n_samples=0, first_sample=0, flags=0):
+        """First-hit feature buffers (drt_render_features) into buffers of the context's own: n_samples of every pixel from
+        first_sample on, or (0) each pixel's count from the held film's filter column. The film and the render state do not
+        change. Returns {"empty_pixels", "rays", "kernel_ms"}; read_features() / read_feature_bgra() fetch the result."""
+        f = make_features(n_samples, first_sample)
+        f.flags = flags
+        _check(self.L.drt_render_features(self.ctx, C.byref(f)), "drt_render_features")
+        return {"empty_pixels": f.empty_pixels, "rays": f.rays, "kernel_ms": f.kernel_ms}
+
+    def read_features(self):
+        """(mean [n][8], m2 [n][8], ids [n] int32) of the last render_features()"""
+        mean = np.empty((self.n_pixels, FEATURE_CHANNELS), dtype=np.float64)
+        m2 = np.empty((self.n_pixels, FEATURE_CHANNELS), dtype=np.float64)
+        ids = np.empty(self.n_pixels, dtype=np.int32)
+        _check(self.L.drt_read_features(self.ctx, _ptr(mean, C.c_double), _ptr(m2, C.c_double), _ptr(ids, C.c_int32)), "drt_read_features")
+        return mean, m2, ids
+
+    def read_feature_bgra(self, which, lo, hi):
+        """BMP pixel bytes [n][4] of the mean normal (FEATURE_NORMAL: x, y, z to R, G, B), depth or coverage (grey), [lo, hi] to 0..255"""
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_feature_bgra(self.ctx, int(which), float(lo), float(hi), _ptr(out, C.c_uint8)), "drt_read_feature_bgra")
+        return out
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -600,6 +646,16 @@ class Group:
         var = np.empty((self.n_pixels, self.S), dtype=np.float64)
         _check(self.L.drt_group_denoise(self.g, C.byref(d), _ptr(mean, C.c_double), _ptr(var, C.c_double)), "drt_group_denoise")
         return mean, var, {"unusable": d.unusable, "kernel_ms": d.kernel_ms}
+
+    def render_features(self, n_samples=0, first_sample=0):
+        """drt_group_render_features: every device its own rows. Returns (mean, m2, ids, {"empty_pixels", "rays", "kernel_ms"}), image order."""
+        f = make_features(n_samples, first_sample)
+        mean = np.empty((self.n_pixels, FEATURE_CHANNELS), dtype=np.float64)
+        m2 = np.empty((self.n_pixels, FEATURE_CHANNELS), dtype=np.float64)
+        ids = np.empty(self.n_pixels, dtype=np.int32)
+        _check(self.L.drt_group_render_features(self.g, C.byref(f), _ptr(mean, C.c_double), _ptr(m2, C.c_double), _ptr(ids, C.c_int32)),
+               "drt_group_render_features")
+        return mean, m2, ids, {"empty_pixels": f.empty_pixels, "rays": f.rays, "kernel_ms": f.kernel_ms}
 
     def close(self):
         if self.g:

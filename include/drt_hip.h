@@ -379,6 +379,49 @@ int drt_denoise_buffers(const drt_scene *scene, const drt_params *params, drt_de
  * form on its first device. Same bits for any device list. */
 int drt_group_denoise(drt_group *g, drt_denoise *d, double *mean, double *var);
 
+/*
+ * First-hit feature buffers: what a pixel looks at. Per tile pixel p with count c_p, and for sample s = first_sample .. first_sample + c_p - 1
+ * in ascending order: the path's own camera ray (the RNG seeded with the path key of (x, y, s), then the draws the render takes, in its
+ * order), its closest hit as the render finds it (fudged origin, facing normal after the flip), and of that the vector phi of
+ * DRT_FEATURE_CHANNELS doubles:
+ *     phi[0..2] the hit normal,  phi[3] the depth (position - aperture_position) . forward,  phi[4] 1,  phi[5..7] the XYZ of the surface material
+ *     a miss (a NaN ray misses): phi[0..4] = 0, phi[5..7] the XYZ of the escape material
+ * A material's XYZ is that of its emission when it is emissive, else of (diffuse + glossy) + mirror (an SPD index of -1 reads as zeros),
+ * channel k with colour-matching row ck being (sum_i ck[i] r[i] rw[i]) * (interval / N), N as in drt_adaptive above. Every channel is
+ * updated the way the film is (src/daily_ray_trace.c:736-743): d = phi - m; m = m + d / (double)(s - first_sample + 1); M2 = M2 + d * (phi - m).
+ * Results: mean [tile_h*tile_w][DRT_FEATURE_CHANNELS], m2 likewise (not divided, like the film's variance: mean[..][4] is the coverage),
+ * ids [tile_h*tile_w], the closest-hit surface index of sample first_sample (-1 for a miss). DESIGN.md section 5c states the rule, which
+ * uses + - * / sqrt only, and tests/feature_rule.py restates it: the device's result equals that bit for bit.
+ */
+#define DRT_FEATURE_CHANNELS 8
+typedef struct drt_features
+{
+    uint32_t n_samples;    /* >0: that many samples of every pixel; 0: each pixel's count from the held film's filter column */
+    uint32_t first_sample;
+    uint32_t flags;        /* 0 (reserved) */
+    uint32_t empty_pixels; /* out: pixels whose coverage is 0 */
+    uint64_t rays;         /* out: camera rays cast, summed over pixels */
+    double   kernel_ms;    /* out: HIP-event time */
+} drt_features;            /* 32 bytes */
+/* Synchronises, then fills three buffers of the context's own. Changes no film bit, no count and no render state: drt_render and the
+ * adaptive calls go on afterwards as if it had not been called. n_samples > 0 works in both film modes and on an empty film. n_samples = 0
+ * needs DRT_MODE_SPECTRAL and a film whose every filter sum is a whole number in [1, 2^32). Refused with nothing done: nonzero flags,
+ * first_sample + count beyond 2^32 - 1, and with n_samples = 0 the XYZ film and a filter sum that is no count (the message names the
+ * first such tile pixel). */
+int drt_render_features(drt_context *ctx, drt_features *f);
+/* The result of the last drt_render_features; any pointer may be NULL. An error before a drt_render_features, and -- when that call took
+ * its counts from the film (n_samples = 0) -- after anything has changed the film since (drt_render, drt_write_film, drt_reset_film,
+ * drt_bind_film, an adaptive call). */
+int drt_read_features(drt_context *ctx, double *mean, double *m2, int32_t *ids);
+/* One feature of the mean as .bmp pixel bytes, [tile_h*tile_w][4] = B, G, R, 255 in drt_read_bgra's row order: which = 0 the normal
+ * (x, y, z to R, G, B), 1 the depth, 2 the coverage (both grey). t = (v - lo) / (hi - lo); t = t < 0 ? 0 : t; t = t > 1 ? 1 : t;
+ * byte = (uint8_t)(t * 255.0 + 0.5); a NaN gives 0. Refused: hi <= lo, or either not finite; drt_read_features' errors. */
+int drt_read_feature_bgra(drt_context *ctx, int which, double lo, double hi, uint8_t *bgra);
+/* Features need no neighbours: every device renders its own rows, and the host buffers (whole tile, any may be NULL) come back in image
+ * order. Same bits for any device list. With n_samples = 0 every device checks its film before any device renders. kernel_ms is the
+ * slowest device's. */
+int drt_group_render_features(drt_group *g, drt_features *f, double *mean, double *m2, int32_t *ids);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */

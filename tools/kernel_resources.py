@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / scratch / occupancy figures of libdrt_hip.so's kernels, from the compiler's own output: the device
 assembly of csrc/drt_launcher.hip (the Makefile's flags plus -S -gline-tables-only) and the kernel metadata at its end. Extra
-arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring] [--loops] [-D...]
+arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring | group] [--loops] [-D...]
+A filter that names a group (GROUPS below: `features`) stands for the group's kernels.
 
 Columns: VGPRs, SGPRs, `sspill` / `vspill` = the metadata's .sgpr_spill_count / .vgpr_spill_count, scratch bytes per lane, static
 LDS, occupancy (waves per SIMD, from the VGPR count), `valu` = vector ALU instructions in the kernel's text, `lanemv` = how many of
@@ -21,6 +22,9 @@ PKG = os.path.join(REPO, "daily-ray-trace_amd")
 HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
 # the Makefile's HIPFLAGS (warnings aside)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-std=c++17", "-I" + os.path.join(REPO, "include")]
+
+# a filter word that is a key here selects the kernels whose names hold one of the substrings
+GROUPS = {"features": ("drt_feature_kernel", "drt_feature_bvh_kernel", "drt_feature_counts_kernel", "drt_feature_bgra_kernel")}
 
 # vector ALU mnemonics: v_* except the few that are not issued to the VALU
 _NOT_VALU = ("v_nop", "v_interp")
@@ -147,7 +151,7 @@ def main(argv):
     loops = "--loops" in argv
     argv = [a for a in argv if a != "--loops"]
     args = [a for a in argv if a.startswith("-")]
-    flt = [a for a in argv if not a.startswith("-")]
+    flt = [s for a in argv if not a.startswith("-") for s in GROUPS.get(a, (a,))]
     rows = kernel_stats(args)
     print("%-60s %5s %5s %6s %6s %7s %6s %4s %6s %6s" % ("kernel", "VGPRs", "SGPRs", "sspill", "vspill", "scratch", "LDS", "occ", "valu", "lanemv"))
     for name, r in rows.items():
