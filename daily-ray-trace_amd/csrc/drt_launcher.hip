@@ -8,6 +8,7 @@
 #include "drt_adaptive_kernels.h"
 #include "drt_denoise_kernels.h"
 #include "drt_feature_kernels.h"
+#include "drt_matte_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -138,6 +139,14 @@ struct drt_context
     hipEvent_t ft_ev[2] = {nullptr, nullptr};
     bool     ft_valid = false, ft_from_film = false;
     uint64_t ft_gen = 0;                   /* film_gen at the last drt_render_features */
+    /* ID mattes (drt_render_mattes): the result and the film it took its counts from; d_ft_counts and d_ft_report are shared */
+    int32_t *d_mt_ids = nullptr, *d_mt_list = nullptr;
+    uint32_t *d_mt_counts = nullptr, *d_mt_tail = nullptr;
+    double  *d_mt_cover = nullptr;
+    unsigned long long *d_mt_info = nullptr;
+    hipEvent_t mt_ev[2] = {nullptr, nullptr};
+    bool     mt_valid = false, mt_from_film = false;
+    uint64_t mt_gen = 0;                   /* film_gen at the last drt_render_mattes */
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -1125,6 +1134,14 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_ft_report);
     (void)hipFree(ctx->d_ft_info);
     for (hipEvent_t e : ctx->ft_ev)
+        if (e) (void)hipEventDestroy(e);
+    (void)hipFree(ctx->d_mt_ids);
+    (void)hipFree(ctx->d_mt_list);
+    (void)hipFree(ctx->d_mt_counts);
+    (void)hipFree(ctx->d_mt_tail);
+    (void)hipFree(ctx->d_mt_cover);
+    (void)hipFree(ctx->d_mt_info);
+    for (hipEvent_t e : ctx->mt_ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(ctx->h_active);
     for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
@@ -2774,6 +2791,32 @@ static int features_check(const drt_features *f)
     return 0;
 }
 
+/* n_samples = 0: every tile pixel's count from its filter sum into d_ft_counts, which the feature and the matte pass share (each reads
+ * it only in the kernel of the same call). The stream must be idle. */
+static int film_counts(drt_context *ctx, const char *who, uint32_t first_sample)
+{
+    const size_t n_pix = (size_t)ctx->n_pix;
+    if (!ctx->d_ft_counts) HIP_TRY(hipMalloc((void **)&ctx->d_ft_counts, n_pix * sizeof(uint32_t)));
+    if (!ctx->d_ft_report) HIP_TRY(hipMalloc((void **)&ctx->d_ft_report, 2 * sizeof(uint32_t)));
+    uint32_t report[2] = {0xFFFFFFFFu, 0u};
+    HIP_TRY(hipMemcpyAsync(ctx->d_ft_report, report, sizeof(report), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(drt_feature_counts_kernel, dim3((uint32_t)((n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+                       ctx->d_pixels, ctx->dsc.S, (uint32_t)n_pix, ctx->d_ft_counts, ctx->d_ft_report);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(report, ctx->d_ft_report, sizeof(report), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (report[0] != 0xFFFFFFFFu)
+    {
+        double sum = 0.0;
+        HIP_TRY(hipMemcpy(&sum, ctx->d_pixels + (size_t)report[0] * (ctx->dsc.S + 1) + ctx->dsc.S, sizeof(sum), hipMemcpyDeviceToHost));
+        return fail(-7, "%s: tile pixel %u (column %u, row %u of the tile) holds the filter sum %g: with n_samples = 0 a pixel's sample count is its filter sum, a whole number from 1 to 2^32 - 1 (an empty film has none: give n_samples)",
+                    who, report[0], report[0] % ctx->params.tile_w, report[0] / ctx->params.tile_w, sum);
+    }
+    if ((uint64_t)first_sample + report[1] > 0xFFFFFFFFull)
+        return fail(-1, "%s: first_sample %u + %u samples: sample numbers are 32 bits", who, first_sample, report[1]);
+    return 0;
+}
+
 /* The film complete, the buffers there, and with n_samples = 0 every pixel's count from its filter sum. Refuses before anything is
  * rendered; the film, the adaptive counts and the render state stay as they are. */
 static int features_prepare(drt_context *ctx, const drt_features *f)
@@ -2793,27 +2836,7 @@ static int features_prepare(drt_context *ctx, const drt_features *f)
     if (!ctx->d_ft_colour) HIP_TRY(hipMalloc((void **)&ctx->d_ft_colour, std::max<size_t>(ctx->ft_mats.size(), 1) * 3 * 8));
     for (hipEvent_t &e : ctx->ft_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    if (f->n_samples == 0)
-    {
-        if (!ctx->d_ft_counts) HIP_TRY(hipMalloc((void **)&ctx->d_ft_counts, n_pix * sizeof(uint32_t)));
-        if (!ctx->d_ft_report) HIP_TRY(hipMalloc((void **)&ctx->d_ft_report, 2 * sizeof(uint32_t)));
-        uint32_t report[2] = {0xFFFFFFFFu, 0u};
-        HIP_TRY(hipMemcpyAsync(ctx->d_ft_report, report, sizeof(report), hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(drt_feature_counts_kernel, dim3((uint32_t)((n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
-                           ctx->d_pixels, ctx->dsc.S, (uint32_t)n_pix, ctx->d_ft_counts, ctx->d_ft_report);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(report, ctx->d_ft_report, sizeof(report), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (report[0] != 0xFFFFFFFFu)
-        {
-            double sum = 0.0;
-            HIP_TRY(hipMemcpy(&sum, ctx->d_pixels + (size_t)report[0] * (ctx->dsc.S + 1) + ctx->dsc.S, sizeof(sum), hipMemcpyDeviceToHost));
-            return fail(-7, "features: tile pixel %u (column %u, row %u of the tile) holds the filter sum %g: with n_samples = 0 a pixel's sample count is its filter sum, a whole number from 1 to 2^32 - 1 (an empty film has none: give n_samples)",
-                        report[0], report[0] % ctx->params.tile_w, report[0] / ctx->params.tile_w, sum);
-        }
-        if ((uint64_t)f->first_sample + report[1] > 0xFFFFFFFFull)
-            return fail(-1, "features: first_sample %u + %u samples: sample numbers are 32 bits", f->first_sample, report[1]);
-    }
+    if (f->n_samples == 0 && (rc = film_counts(ctx, "features", f->first_sample))) return rc;
     return 0;
 }
 
@@ -2947,6 +2970,211 @@ extern "C" int drt_group_render_features(drt_group *g, drt_features *f, double *
         if (mean) HIP_TRY(hipMemcpy2D((char *)mean + k * row8, n * row8, c->d_ft_mean, row8, row8, g->rows[k], hipMemcpyDeviceToHost));
         if (m2) HIP_TRY(hipMemcpy2D((char *)m2 + k * row8, n * row8, c->d_ft_m2, row8, row8, g->rows[k], hipMemcpyDeviceToHost));
         if (ids) HIP_TRY(hipMemcpy2D((char *)ids + k * row4, n * row4, c->d_ft_ids, row4, row4, g->rows[k], hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* ID mattes (kernels in drt_matte_kernels.h)                                */
+
+#define MATTE_MAX_IDS 4096u
+#define MATTE_WORDS (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS) /* ids and counts per pixel */
+
+static int mattes_check(const drt_mattes *m)
+{
+    if (m->flags != 0) return fail(-1, "mattes: flags = %u: 0 (reserved)", m->flags);
+    if (m->n_samples && (uint64_t)m->first_sample + m->n_samples > 0xFFFFFFFFull)
+        return fail(-1, "mattes: first_sample %u + %u samples: sample numbers are 32 bits", m->first_sample, m->n_samples);
+    return 0;
+}
+
+/* As features_prepare: refuses before anything is rendered; the film, the adaptive counts, the render state and the feature buffers
+ * stay as they are. */
+static int mattes_prepare(drt_context *ctx, const drt_mattes *m)
+{
+    if (m->n_samples == 0 && ctx->xyz_mode)
+        return fail(-4, "mattes: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)");
+    if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "mattes: a tile of %llu pixels", (unsigned long long)ctx->n_pix);
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = drt_synchronize(ctx);
+    if (rc) return rc;
+    ctx->mt_valid = false;
+    const size_t n_pix = (size_t)ctx->n_pix;
+    if (!ctx->d_mt_ids) HIP_TRY(hipMalloc((void **)&ctx->d_mt_ids, n_pix * MATTE_WORDS * sizeof(int32_t)));
+    if (!ctx->d_mt_counts) HIP_TRY(hipMalloc((void **)&ctx->d_mt_counts, n_pix * MATTE_WORDS * sizeof(uint32_t)));
+    if (!ctx->d_mt_tail) HIP_TRY(hipMalloc((void **)&ctx->d_mt_tail, n_pix * 4 * sizeof(uint32_t)));
+    if (!ctx->d_mt_info) HIP_TRY(hipMalloc((void **)&ctx->d_mt_info, MATTE_INFO_WORDS * sizeof(unsigned long long)));
+    for (hipEvent_t &e : ctx->mt_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    if (m->n_samples == 0 && (rc = film_counts(ctx, "mattes", m->first_sample))) return rc;
+    return 0;
+}
+
+static int mattes_enqueue(drt_context *ctx, const drt_mattes *m)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemsetAsync(ctx->d_mt_info, 0, MATTE_INFO_WORDS * sizeof(unsigned long long), ctx->stream));
+    const drt_params &p = ctx->params;
+    MatteParams mp{};
+    FeatureParams &fp = mp.fp;
+    fp.width = p.width; fp.height = p.height; fp.x0 = p.x0; fp.y0 = p.y0;
+    fp.tile_w = p.tile_w; fp.tile_h = p.tile_h; fp.row_stride = p.row_stride;
+    fp.n_samples = m->n_samples;
+    fp.first_sample = m->first_sample;
+    fp.pixel_scheme = p.pixel_scheme;
+    fp.seed = p.seed;
+    fp.n_pix = ctx->n_pix;
+    fp.counts = m->n_samples ? nullptr : ctx->d_ft_counts;
+    mp.ids = ctx->d_mt_ids;
+    mp.counts = ctx->d_mt_counts;
+    mp.tail = ctx->d_mt_tail;
+    mp.info = ctx->d_mt_info;
+    const uint32_t grid = (uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK);
+    HIP_TRY(hipEventRecord(ctx->mt_ev[0], ctx->stream));
+    if (ctx->scene_in_lds)
+        hipLaunchKernelGGL(drt_matte_kernel, dim3(grid), dim3(FEATURE_BLOCK), feature_lds_bytes(ctx->dsc.n_surf), ctx->stream, ctx->dsc, ctx->dcam, mp);
+    else
+        hipLaunchKernelGGL(drt_matte_bvh_kernel, dim3(grid), dim3(FEATURE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, mp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ctx->mt_ev[1], ctx->stream));
+    return 0;
+}
+
+/* waits for the kernel; adds this context's share to the report (kernel_ms: the slowest context's) */
+static int mattes_finish(drt_context *ctx, drt_mattes *m)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(-100 - (int)e, "matte kernel: %s", hipGetErrorString(e));
+    unsigned long long info[MATTE_INFO_WORDS] = {0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(info, ctx->d_mt_info, sizeof(info), hipMemcpyDeviceToHost));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->mt_ev[0], ctx->mt_ev[1]));
+    m->empty_pixels += (uint32_t)info[0];
+    m->overflow_pixels[0] += (uint32_t)info[1];
+    m->overflow_pixels[1] += (uint32_t)info[2];
+    m->rays += info[3];
+    m->kernel_ms = std::max(m->kernel_ms, (double)ms);
+    ctx->mt_gen = ctx->film_gen;
+    ctx->mt_from_film = m->n_samples == 0;
+    ctx->mt_valid = true;
+    return 0;
+}
+
+static void mattes_clear_out(drt_mattes *m)
+{
+    m->empty_pixels = 0;
+    m->overflow_pixels[0] = m->overflow_pixels[1] = 0;
+    m->rays = 0;
+    m->kernel_ms = 0.0;
+}
+
+extern "C" int drt_render_mattes(drt_context *ctx, drt_mattes *m)
+{
+    if (!ctx || !m) return fail(-1, "null argument");
+    int rc = mattes_check(m);
+    if (rc) return rc;
+    if ((rc = mattes_prepare(ctx, m))) return rc;
+    if ((rc = mattes_enqueue(ctx, m))) return rc;
+    mattes_clear_out(m);
+    return mattes_finish(ctx, m);
+}
+
+static int mattes_current(drt_context *ctx)
+{
+    if (!ctx->mt_valid) return fail(-4, "no matte buffers: drt_render_mattes first");
+    if (ctx->mt_from_film && ctx->mt_gen != ctx->film_gen)
+        return fail(-4, "the film has changed since drt_render_mattes took its counts from it (n_samples = 0): render the mattes again");
+    return 0;
+}
+
+extern "C" int drt_read_mattes(drt_context *ctx, int32_t *ids, uint32_t *counts, uint32_t *tail)
+{
+    if (!ctx) return fail(-1, "null context");
+    int rc = mattes_current(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n_pix = (size_t)ctx->n_pix;
+    if (ids) HIP_TRY(hipMemcpy(ids, ctx->d_mt_ids, n_pix * MATTE_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (counts) HIP_TRY(hipMemcpy(counts, ctx->d_mt_counts, n_pix * MATTE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (tail) HIP_TRY(hipMemcpy(tail, ctx->d_mt_tail, n_pix * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+static int matte_layer_check(int layer)
+{
+    if (layer != DRT_MATTE_SURFACE && layer != DRT_MATTE_MATERIAL) return fail(-1, "mattes: layer = %d: 0 surfaces, 1 materials", layer);
+    return 0;
+}
+
+extern "C" int drt_read_matte(drt_context *ctx, int layer, const int32_t *id_list, uint32_t n_ids, double *coverage)
+{
+    /* what the arguments alone decide comes first, before the context is looked at */
+    int rc = matte_layer_check(layer);
+    if (rc) return rc;
+    if (n_ids == 0 || n_ids > MATTE_MAX_IDS) return fail(-1, "mattes: n_ids = %u: 1 to %u ids", n_ids, MATTE_MAX_IDS);
+    if (!id_list || !coverage) return fail(-1, "null argument");
+    for (uint32_t k = 0; k < n_ids; k += 1)
+        if (id_list[k] < DRT_MATTE_ID_MISS) return fail(-1, "mattes: id_list[%u] = %d: -1 (a miss) or the index of a %s", k, id_list[k], layer == DRT_MATTE_SURFACE ? "surface" : "material");
+    if (!ctx) return fail(-1, "null context");
+    const uint32_t limit = layer == DRT_MATTE_SURFACE ? ctx->dsc.n_surf : ctx->dsc.n_mat;
+    for (uint32_t k = 0; k < n_ids; k += 1)
+        if (id_list[k] >= 0 && (uint32_t)id_list[k] >= limit)
+            return fail(-1, "mattes: id_list[%u] = %d: the scene has %u %s", k, id_list[k], limit, layer == DRT_MATTE_SURFACE ? "surfaces" : "materials");
+    if ((rc = mattes_current(ctx))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->d_mt_list) HIP_TRY(hipMalloc((void **)&ctx->d_mt_list, MATTE_MAX_IDS * sizeof(int32_t)));
+    if (!ctx->d_mt_cover) HIP_TRY(hipMalloc((void **)&ctx->d_mt_cover, (size_t)ctx->n_pix * sizeof(double)));
+    HIP_TRY(hipMemcpy(ctx->d_mt_list, id_list, n_ids * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(drt_matte_select_kernel, dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+                       (const int32_t *)ctx->d_mt_ids, (const uint32_t *)ctx->d_mt_counts, (const uint32_t *)ctx->d_mt_tail, ctx->n_pix, layer,
+                       (const int32_t *)ctx->d_mt_list, n_ids, ctx->d_mt_cover);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(coverage, ctx->d_mt_cover, (size_t)ctx->n_pix * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_matte_bgra(drt_context *ctx, int layer, uint8_t *bgra)
+{
+    if (!ctx || !bgra) return fail(-1, "null argument");
+    int rc = matte_layer_check(layer);
+    if (rc) return rc;
+    if ((rc = mattes_current(ctx))) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    hipLaunchKernelGGL(drt_matte_bgra_kernel, dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+                       (const int32_t *)ctx->d_mt_ids, (const uint32_t *)ctx->d_mt_counts, (const uint32_t *)ctx->d_mt_tail, ctx->n_pix, layer, ctx->d_bgra);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* every device its own rows, side by side: parameters and films checked on all of them before any renders */
+extern "C" int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids, uint32_t *counts, uint32_t *tail)
+{
+    g_last_error.clear();
+    if (!g || !m) return fail(-1, "null argument");
+    int rc = mattes_check(m);
+    if (rc) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = mattes_prepare(c, m))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = mattes_enqueue(c, m))) return rc;
+    mattes_clear_out(m);
+    for (drt_context *c : g->ctx)
+        if (c && (rc = mattes_finish(c, m))) return rc;
+    const size_t n = g->ctx.size();
+    for (size_t k = 0; k < n; k += 1)
+    {
+        drt_context *c = g->ctx[k];
+        if (!c) continue;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t row = (size_t)g->tile_w * MATTE_WORDS * 4, row_tail = (size_t)g->tile_w * 4 * 4;
+        if (ids) HIP_TRY(hipMemcpy2D((char *)ids + k * row, n * row, c->d_mt_ids, row, row, g->rows[k], hipMemcpyDeviceToHost));
+        if (counts) HIP_TRY(hipMemcpy2D((char *)counts + k * row, n * row, c->d_mt_counts, row, row, g->rows[k], hipMemcpyDeviceToHost));
+        if (tail) HIP_TRY(hipMemcpy2D((char *)tail + k * row_tail, n * row_tail, c->d_mt_tail, row_tail, row_tail, g->rows[k], hipMemcpyDeviceToHost));
     }
     return 0;
 }

@@ -131,6 +131,33 @@ static u8 feature_byte(f64 v, f64 lo, f64 hi)
     return t == t ? (u8)(t * 255.0 + 0.5) : (u8)0;
 }
 
+/* drt_read_matte_bgra's rule on the host: the same + * / in the same order, uncontracted, so the same bytes */
+static f64 matte_palette(int32_t id, int c)
+{
+    u32 h = (u32)(id + 1) * 0x9E3779B1u;
+    h ^= h >> 16;
+    return (f64)(64u + ((h >> (8 * c)) & 127u));
+}
+
+void drt_host_matte_bgra(const int32_t *ids, const u32 *counts, const u32 *tail, u64 n, int layer, u8 *bgra)
+{
+    for (u64 p = 0; p < n; p += 1)
+    {
+        const u64 at = (p * DRT_MATTE_LAYERS + (u64)layer) * DRT_MATTE_SLOTS;
+        const f64 c_p = (f64)tail[p * 4];
+        f64 v[3] = { 0.0, 0.0, 0.0 };
+        for (int k = 0; k < DRT_MATTE_SLOTS; k += 1)
+        {
+            const f64 share = (f64)counts[at + k] / c_p;
+            for (int c = 0; c < 3; c += 1) v[c] = v[c] + share * matte_palette(ids[at + k], c);
+        }
+        bgra[p * 4 + 0] = (u8)(v[2] + 0.5);
+        bgra[p * 4 + 1] = (u8)(v[1] + 0.5);
+        bgra[p * 4 + 2] = (u8)(v[0] + 0.5);
+        bgra[p * 4 + 3] = 255;
+    }
+}
+
 void drt_host_feature_bgra(const f64 *mean, u64 n, int which, f64 lo, f64 hi, u8 *bgra)
 {
     for (u64 p = 0; p < n; p += 1)

@@ -80,7 +80,7 @@ typedef struct
 /* Host extras that the reference has no field for (device choice, RNG seed, batch size, adaptive sampling);
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
- * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD. */
+ * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES. */
 typedef struct
 {
     int32_t  device;
@@ -108,6 +108,11 @@ typedef struct
      * outputs and the denoiser's files stay byte for byte what they are without it */
     uint32_t features;
     char     features_spd[256], features_m2_spd[256];
+    /* the ID mattes (drt_group_render_mattes, every pixel at the count its film holds) when mattes != 0: <output_spd>.surface_id.spd and
+     * .material_id.spd, 12 channels per pixel ((double)id_0, count_0 / c, ..., id_5, count_5 / c in rank order, an empty slot -1, 0),
+     * the previews <output_spd>.surface_id.bmp and .material_id.bmp, and <output_spd>.mattes.txt, which names every surface and
+     * material; every other output stays byte for byte what it is without it */
+    uint32_t mattes;
 } drt_host_options;
 
 /* the `adaptive` line of a version-3 checkpoint manifest: what the film was rendered with so far */
@@ -199,6 +204,8 @@ int  drt_host_write_bmp(const char *path, u32 width, u32 height, const f64 *rgb)
 int  drt_host_write_bmp_bgra(const char *path, u32 width, u32 height, const u8 *bgra);
 /* One feature of a [n][8] feature mean as BMP pixel bytes: drt_read_feature_bgra's rule (include/drt_hip.h) on the host. */
 void drt_host_feature_bgra(const f64 *mean, u64 n, int which, f64 lo, f64 hi, u8 *bgra);
+/* One layer of the ID mattes ([n][2][6] ids and counts, [n][4] tail) as BMP pixel bytes: drt_read_matte_bgra's rule on the host. */
+void drt_host_matte_bgra(const int32_t *ids, const u32 *counts, const u32 *tail, u64 n, int layer, u8 *bgra);
 int  drt_host_spd_file_to_bmp(const char *spd_path, const char *bmp_path, const f64 *cmf);
 
 #ifdef __cplusplus

@@ -32,6 +32,53 @@ static int publish_spd(const char *path, u32 width, u32 height, u32 S, f64 min_w
     return rename(tmp, path) == 0 ? 0 : -1;
 }
 
+#define MATTE_CHANNELS (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS) /* ids and counts per pixel; also the doubles per pixel of a layer's .spd */
+
+/* The ID mattes' files, each by temporary name + rename: <base>.surface_id.spd and <base>.material_id.spd (12 channels per pixel:
+ * (double)id_k, count_k / c in rank order), the two previews beside them, and <base>.mattes.txt with the names behind the ids. */
+static int publish_mattes(const char *base, const drt_host_scene *hs, u32 width, u32 height, const int32_t *ids, const u32 *counts, const u32 *tail)
+{
+    static const char *const layer_name[DRT_MATTE_LAYERS] = { "surface_id", "material_id" };
+    const drt_scene *scene = drt_host_scene_data(hs);
+    const u64 num_pixels = (u64)width * height;
+    char path[300], tmp[304];
+    f64 *chan = (f64 *)malloc(num_pixels * MATTE_CHANNELS * sizeof(f64));
+    u8 *fb = (u8 *)malloc(num_pixels * 4 + 4);
+    int bad = (!chan || !fb) ? -1 : 0;
+    for (int y = 0; !bad && y < DRT_MATTE_LAYERS; y += 1)
+    {
+        for (u64 px = 0; px < num_pixels; px += 1)
+        {
+            const u64 at = (px * DRT_MATTE_LAYERS + (u64)y) * DRT_MATTE_SLOTS;
+            const f64 c = (f64)tail[px * 4];
+            for (int k = 0; k < DRT_MATTE_SLOTS; k += 1)
+            {
+                chan[px * MATTE_CHANNELS + 2 * k] = (f64)ids[at + k];
+                chan[px * MATTE_CHANNELS + 2 * k + 1] = (f64)counts[at + k] / c;
+            }
+        }
+        if (snprintf(path, sizeof(path), "%s.%s.spd", base, layer_name[y]) >= (int)sizeof(path)) { bad = -1; break; }
+        if (publish_spd(path, width, height, MATTE_CHANNELS, scene->min_wavelength, scene->wavelength_interval, chan) != 0) { bad = -1; break; }
+        snprintf(path, sizeof(path), "%s.%s.bmp", base, layer_name[y]);
+        snprintf(tmp, sizeof(tmp), "%s.tmp", path);
+        drt_host_matte_bgra(ids, counts, tail, num_pixels, y, fb);
+        if (drt_host_write_bmp_bgra(tmp, width, height, fb) != 0 || rename(tmp, path) != 0) bad = -1;
+    }
+    free(fb);
+    free(chan);
+    if (bad) return bad;
+    if (snprintf(path, sizeof(path), "%s.mattes.txt", base) >= (int)sizeof(path)) return -1;
+    snprintf(tmp, sizeof(tmp), "%s.tmp", path);
+    FILE *f = fopen(tmp, "w");
+    if (!f) return -1;
+    for (u32 i = 0; i < scene->num_surfaces; i += 1)
+        fprintf(f, "surface %u %s material %u\n", i, drt_host_surface_name(hs, i), scene->surfaces[i].material);
+    for (u32 i = 0; i < scene->num_materials; i += 1) fprintf(f, "material %u %s\n", i, drt_host_material_name(hs, i));
+    bad = ferror(f);
+    if (fclose(f) != 0 || bad) return -1;
+    return rename(tmp, path) == 0 ? 0 : -1;
+}
+
 int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_stats *stats_out)
 {
     u32 width = config->output_width, height = config->output_height;
@@ -242,6 +289,22 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         if (!rc && !opt->quiet)
             printf("Features: %llu camera rays, %.3f ms on the device, %u pixels see nothing\n", (unsigned long long)ft.rays, ft.kernel_ms, ft.empty_pixels);
     }
+    /* the ID mattes of the finished film, likewise */
+    int32_t *mt_ids = NULL;
+    u32 *mt_counts = NULL, *mt_tail = NULL;
+    if (!rc && opt && opt->mattes)
+    {
+        drt_mattes mt;
+        memset(&mt, 0, sizeof(mt));
+        mt_ids = (int32_t *)malloc(num_pixels * MATTE_CHANNELS * sizeof(int32_t));
+        mt_counts = (u32 *)malloc(num_pixels * MATTE_CHANNELS * sizeof(u32));
+        mt_tail = (u32 *)malloc(num_pixels * 4 * sizeof(u32));
+        if (!mt_ids || !mt_counts || !mt_tail) rc = -3;
+        if (!rc) rc = drt_group_render_mattes(ctx, &mt, mt_ids, mt_counts, mt_tail);
+        if (!rc && !opt->quiet)
+            printf("Mattes: %llu camera rays, %.3f ms on the device, %u pixels see nothing, %u / %u see more than %d surfaces / materials\n",
+                   (unsigned long long)mt.rays, mt.kernel_ms, mt.empty_pixels, mt.overflow_pixels[0], mt.overflow_pixels[1], DRT_MATTE_SLOTS);
+    }
     /* the .bmp pixels come from the film while it is still on the device (drt_read_bgra: the same bytes as converting the
      * .spd files on the host, host/drt_bmp.c, without reading 1.7 GB back from disk) */
     u8 *bgra[3] = { NULL, NULL, NULL };
@@ -259,6 +322,9 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     {
         fprintf(stderr, "render_image: the HIP launcher failed (%d): %s\n", rc, drt_last_error());
         for (int k = 0; k < 3; k += 1) free(bgra[k]);
+        free(mt_tail);
+        free(mt_counts);
+        free(mt_ids);
         free(ft_m2);
         free(ft_mean);
         free(dn_var);
@@ -333,8 +399,14 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         free(fb);
         if (w3) fprintf(stderr, "render_image: could not write the feature outputs\n");
     }
+    int w4 = 0;
+    if (!(w0 || w1 || w2 || w3) && mt_ids)
+    {
+        w4 = publish_mattes(config->output_spd, hs, width, height, mt_ids, mt_counts, mt_tail);
+        if (w4) fprintf(stderr, "render_image: could not write the matte outputs\n");
+    }
     /* post-process like the reference's main(): each film -> linear RGB -> BMP (src/win32_main.c:150-152) */
-    if (!(w0 || w1 || w2 || w3))
+    if (!(w0 || w1 || w2 || w3 || w4))
     {
         int bad = 0;
         for (int k = 0; k < 3; k += 1)
@@ -342,6 +414,9 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         if (bad) fprintf(stderr, "render_image: could not write one of the .bmp outputs\n");
     }
     for (int k = 0; k < 3; k += 1) free(bgra[k]);
+    free(mt_tail);
+    free(mt_counts);
+    free(mt_ids);
     free(ft_m2);
     free(ft_mean);
     free(dn_var);
@@ -351,7 +426,7 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     free(dst_avgs);
     free(dst_pixels);
     drt_host_free_scene(hs);
-    return (w0 || w1 || w2 || w3) ? -2 : 0;
+    return (w0 || w1 || w2 || w3 || w4) ? -2 : 0;
 }
 
 /* a whole-string number from the environment: 0 and *out set, -1 (and a message naming the variable) when it does not parse */
@@ -485,6 +560,16 @@ static int features_options(const config_arguments *config, drt_host_options *op
     return 0;
 }
 
+/* DRT_MATTES: parsed and checked here, before any device call. 1 turns the ID mattes on, 0 is off, anything else is refused. (The
+ * program renders the spectral film only, so the counts the mattes need are always there.) */
+static int mattes_options(drt_host_options *opt)
+{
+    const char *e = getenv("DRT_MATTES");
+    if (e && strcmp(e, "0") != 0 && strcmp(e, "1") != 0) { fprintf(stderr, "render_image: DRT_MATTES=\"%s\": 0 or 1\n", e); return -1; }
+    opt->mattes = e && e[0] == '1';
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -512,5 +597,6 @@ void render_image(config_arguments *config)
     if (adaptive_options(config, &opt) != 0) exit(-1);
     if (denoise_options(config, &opt) != 0) exit(-1);
     if (features_options(config, &opt) != 0) exit(-1);
+    if (mattes_options(&opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

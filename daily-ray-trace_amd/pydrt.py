@@ -125,6 +125,29 @@ def make_features(n_samples=0, first_sample=0):
     return f
 
 
+MATTE_SLOTS, MATTE_LAYERS, MATTE_ID_MISS = 6, 2, -1  # DRT_MATTE_SLOTS, DRT_MATTE_LAYERS, DRT_MATTE_ID_MISS
+MATTE_SURFACE, MATTE_MATERIAL = 0, 1  # the layers
+
+
+class Mattes(C.Structure):
+    """drt_mattes (include/drt_hip.h): the inputs of an ID-matte pass and, after it, empty_pixels / overflow_pixels / rays / kernel_ms."""
+    _fields_ = [("n_samples", C.c_uint32), ("first_sample", C.c_uint32), ("flags", C.c_uint32), ("empty_pixels", C.c_uint32),
+                ("overflow_pixels", C.c_uint32 * 2), ("rays", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+def make_mattes(n_samples=0, first_sample=0):
+    m = Mattes()
+    m.n_samples, m.first_sample, m.flags, m.empty_pixels = n_samples, first_sample, 0, 0
+    m.overflow_pixels[0] = m.overflow_pixels[1] = 0
+    m.rays, m.kernel_ms = 0, 0.0
+    return m
+
+
+def _mattes_report(m):
+    return {"empty_pixels": m.empty_pixels, "overflow_pixels": (m.overflow_pixels[0], m.overflow_pixels[1]), "rays": m.rays,
+            "kernel_ms": m.kernel_ms}
+
+
 def make_params(width, height, spp, max_depth, seed=1, x0=0, y0=0, tile_w=None, tile_h=None, row_stride=1,
                 first_sample=0, pixel_scheme=FILM_SAMPLE_RANDOM, mode=MODE_SPECTRAL, device=0, batch_spp=0, flags=0):
     p = Params()
@@ -385,6 +408,13 @@ def hip_lib():
             L.drt_read_features.argtypes = [C.c_void_p, f64p, f64p, i32p]
             L.drt_read_feature_bgra.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint8)]
             L.drt_group_render_features.argtypes = [C.c_void_p, C.POINTER(Features), f64p, f64p, i32p]
+        if hasattr(L, "drt_render_mattes"):
+            u32p = C.POINTER(C.c_uint32)
+            L.drt_render_mattes.argtypes = [C.c_void_p, C.POINTER(Mattes)]
+            L.drt_read_mattes.argtypes = [C.c_void_p, i32p, u32p, u32p]
+            L.drt_read_matte.argtypes = [C.c_void_p, C.c_int, i32p, C.c_uint32, f64p]
+            L.drt_read_matte_bgra.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]
+            L.drt_group_render_mattes.argtypes = [C.c_void_p, C.POINTER(Mattes), i32p, u32p, u32p]
         L.drt_batch_spp.restype = C.c_uint32
         L.drt_batch_spp.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
@@ -412,7 +442,8 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
                "drt_read_active_list", "drt_render_adaptive_continue", "drt_group_render_adaptive_continue",
                "drt_denoise_film", "drt_read_denoised", "drt_read_denoised_bgra", "drt_denoise_buffers", "drt_group_denoise",
-               "drt_render_features", "drt_read_features", "drt_read_feature_bgra", "drt_group_render_features"]
+               "drt_render_features", "drt_read_features", "drt_read_feature_bgra", "drt_group_render_features",
+               "drt_render_mattes", "drt_read_mattes", "drt_read_matte", "drt_read_matte_bgra", "drt_group_render_mattes"]
 
 
 def _check(rc, what):
@@ -569,6 +600,36 @@ class Renderer:
         _check(self.L.drt_read_feature_bgra(self.ctx, int(which), float(lo), float(hi), _ptr(out, C.c_uint8)), "drt_read_feature_bgra")
         return out
 
+    def render_mattes(self, n_samples=0, first_sample=0, flags=0):
+        """ID mattes (drt_render_mattes) into buffers of the context's own: n_samples of every pixel from first_sample on, or (0)
+        each pixel's count from the held film's filter column. The film, the render state and the feature buffers do not change.
+        Returns {"empty_pixels", "overflow_pixels", "rays", "kernel_ms"}; read_mattes() / read_matte() / read_matte_bgra() fetch the result."""
+        m = make_mattes(n_samples, first_sample)
+        m.flags = flags
+        _check(self.L.drt_render_mattes(self.ctx, C.byref(m)), "drt_render_mattes")
+        return _mattes_report(m)
+
+    def read_mattes(self):
+        """(ids [n][2][6] int32, counts [n][2][6] uint32, tail [n][4] uint32 = c_p, misses, other per layer) of the last render_mattes()"""
+        ids = np.empty((self.n_pixels, MATTE_LAYERS, MATTE_SLOTS), dtype=np.int32)
+        counts = np.empty((self.n_pixels, MATTE_LAYERS, MATTE_SLOTS), dtype=np.uint32)
+        tail = np.empty((self.n_pixels, 4), dtype=np.uint32)
+        _check(self.L.drt_read_mattes(self.ctx, _ptr(ids, C.c_int32), _ptr(counts, C.c_uint32), _ptr(tail, C.c_uint32)), "drt_read_mattes")
+        return ids, counts, tail
+
+    def read_matte(self, layer, id_list):
+        """coverage [n]: the share of every pixel's samples whose id in the layer is in id_list (MATTE_ID_MISS: the misses)"""
+        lst = np.ascontiguousarray(id_list, dtype=np.int32).reshape(-1)
+        out = np.empty(self.n_pixels, dtype=np.float64)
+        _check(self.L.drt_read_matte(self.ctx, int(layer), _ptr(lst, C.c_int32), len(lst), _ptr(out, C.c_double)), "drt_read_matte")
+        return out
+
+    def read_matte_bgra(self, layer):
+        """BMP pixel bytes [n][4] of a layer's preview: every slot's palette colour weighted by its share"""
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_matte_bgra(self.ctx, int(layer), _ptr(out, C.c_uint8)), "drt_read_matte_bgra")
+        return out
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -656,6 +717,16 @@ class Group:
         _check(self.L.drt_group_render_features(self.g, C.byref(f), _ptr(mean, C.c_double), _ptr(m2, C.c_double), _ptr(ids, C.c_int32)),
                "drt_group_render_features")
         return mean, m2, ids, {"empty_pixels": f.empty_pixels, "rays": f.rays, "kernel_ms": f.kernel_ms}
+
+    def render_mattes(self, n_samples=0, first_sample=0):
+        """drt_group_render_mattes: every device its own rows. Returns (ids, counts, tail, report) as Renderer.read_mattes(), image order."""
+        m = make_mattes(n_samples, first_sample)
+        ids = np.empty((self.n_pixels, MATTE_LAYERS, MATTE_SLOTS), dtype=np.int32)
+        counts = np.empty((self.n_pixels, MATTE_LAYERS, MATTE_SLOTS), dtype=np.uint32)
+        tail = np.empty((self.n_pixels, 4), dtype=np.uint32)
+        _check(self.L.drt_group_render_mattes(self.g, C.byref(m), _ptr(ids, C.c_int32), _ptr(counts, C.c_uint32), _ptr(tail, C.c_uint32)),
+               "drt_group_render_mattes")
+        return ids, counts, tail, _mattes_report(m)
 
     def close(self):
         if self.g:

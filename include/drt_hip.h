@@ -422,6 +422,56 @@ int drt_read_feature_bgra(drt_context *ctx, int which, double lo, double hi, uin
  * slowest device's. */
 int drt_group_render_features(drt_group *g, drt_features *f, double *mean, double *m2, int32_t *ids);
 
+/*
+ * ID mattes: which surface, and which material, a pixel shows, and how much of each. The samples are the feature pass's: per tile pixel p
+ * with count c_p, sample s = first_sample .. first_sample + c_p - 1 in ascending order, the path's own camera ray and its closest hit. A
+ * hit has a surface id, the closest-hit index, and a material id, that surface's material index; a miss (a NaN ray misses) has neither.
+ * Two layers, DRT_MATTE_SURFACE and DRT_MATTE_MATERIAL, each of DRT_MATTE_SLOTS slots of (id, count), all empty at the start. A miss adds
+ * 1 to `misses` (one number for both layers). A hit does in each layer, with that layer's id: a slot that holds the id gets count + 1;
+ * else the lowest empty slot takes (id, 1); else other[layer] gets + 1. So the order of the samples matters only to a pixel that sees
+ * more than DRT_MATTE_SLOTS ids. After the last sample each layer's slots are ranked by count descending, then id ascending, the empty
+ * ones last as (DRT_MATTE_ID_MISS, 0). For every pixel and layer sum(counts) + other + misses == c_p.
+ * Results: ids [tile_h*tile_w][DRT_MATTE_LAYERS][DRT_MATTE_SLOTS], counts likewise, tail [tile_h*tile_w][4] = c_p, misses, the surface
+ * layer's other, the material layer's other. DESIGN.md section 5d states the rule and tests/matte_rule.py restates it: integers only,
+ * and the device's result equals that.
+ */
+#define DRT_MATTE_SLOTS   6
+#define DRT_MATTE_ID_MISS (-1)
+enum { DRT_MATTE_SURFACE = 0, DRT_MATTE_MATERIAL = 1, DRT_MATTE_LAYERS = 2 };
+typedef struct drt_mattes
+{
+    uint32_t n_samples;          /* >0: that many samples of every pixel; 0: each pixel's count from the held film's filter column */
+    uint32_t first_sample;
+    uint32_t flags;              /* 0 (reserved) */
+    uint32_t empty_pixels;       /* out: pixels with misses == c_p */
+    uint32_t overflow_pixels[2]; /* out: pixels with other > 0, per layer */
+    uint64_t rays;               /* out: camera rays cast, summed over pixels */
+    double   kernel_ms;          /* out: HIP-event time */
+} drt_mattes;                    /* 40 bytes */
+/* Synchronises, then fills three buffers of the context's own. Changes no film bit, no count, no render state and no feature buffer:
+ * drt_render and the adaptive calls go on afterwards as if it had not been called. n_samples > 0 works in both film modes and on an empty
+ * film. n_samples = 0 needs DRT_MODE_SPECTRAL and a film whose every filter sum is a whole number in [1, 2^32). Refused with nothing
+ * done: nonzero flags, first_sample + count beyond 2^32 - 1, and with n_samples = 0 the XYZ film and a filter sum that is no count (the
+ * message names the first such tile pixel). */
+int drt_render_mattes(drt_context *ctx, drt_mattes *m);
+/* The result of the last drt_render_mattes; any pointer may be NULL. An error before a drt_render_mattes, and -- when that call took its
+ * counts from the film (n_samples = 0) -- after anything has changed the film since (drt_render, drt_write_film, drt_reset_film,
+ * drt_bind_film, an adaptive call). */
+int drt_read_mattes(drt_context *ctx, int32_t *ids, uint32_t *counts, uint32_t *tail);
+/* One matte, [tile_h*tile_w]: coverage[p] = (double)(sum of count_k over the layer's slots whose id is in id_list) / (double)c_p, the sum
+ * taken in integers; DRT_MATTE_ID_MISS in the list adds misses. Refused: layer not 0 or 1, n_ids of 0 or above 4096, an id below -1, an
+ * id not below the scene's surface count (layer 0) or material count (layer 1); drt_read_mattes' errors. */
+int drt_read_matte(drt_context *ctx, int layer, const int32_t *id_list, uint32_t n_ids, double *coverage);
+/* A preview of one layer as .bmp pixel bytes, [tile_h*tile_w][4] = B, G, R, 255 in drt_read_bgra's row order. An id's colour:
+ * h = (uint32_t)(id + 1) * 0x9E3779B1u; h ^= h >> 16; (R, G, B) = 64 + (h & 127), 64 + ((h >> 8) & 127), 64 + ((h >> 16) & 127). Per channel
+ * v = sum over the ranked slots, from +0, of ((double)count_k / (double)c_p) * (double)colour(id_k); byte = (uint8_t)(v + 0.5), which is
+ * 191 at most. Misses and `other` add nothing. Refused: layer not 0 or 1; drt_read_mattes' errors. */
+int drt_read_matte_bgra(drt_context *ctx, int layer, uint8_t *bgra);
+/* As drt_group_render_features: every device renders its own rows, and the host buffers (whole tile, any may be NULL) come back in image
+ * order. Same bits for any device list. Every device is checked before any device renders. The out fields are summed over the devices;
+ * kernel_ms is the slowest device's. */
+int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids, uint32_t *counts, uint32_t *tail);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */
