@@ -9,6 +9,7 @@
 #include "drt_denoise_kernels.h"
 #include "drt_feature_kernels.h"
 #include "drt_matte_kernels.h"
+#include "drt_ray_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,6 +24,7 @@
 
 static thread_local std::string g_last_error;
 
+#define RAY_STAGING_RAYS (1u << 20) /* host-mode ray queries go through device buffers of this many rays, chunk by chunk */
 #define DRT_DEFAULT_MAX_BATCH 256 /* samples per kernel pair when the caller leaves batch_spp = 0 */
 
 /* d_counters, in 8-byte words: [0, DRT_NUM_COUNTERS) the statistics of complete kernel pairs; then the WORK words of the pair in
@@ -147,6 +149,13 @@ struct drt_context
     hipEvent_t mt_ev[2] = {nullptr, nullptr};
     bool     mt_valid = false, mt_from_film = false;
     uint64_t mt_gen = 0;                   /* film_gen at the last drt_render_mattes */
+    /* ray queries (drt_cast_rays, drt_test_visibility, drt_cast_pixels): the staging buffers of host mode, made when first needed */
+    uint64_t ray_chunk = RAY_STAGING_RAYS; /* rays per host-mode launch (DRT_RAY_CHUNK: a test knob, read here at creation) */
+    int      ray_grid_cap = 1;
+    double  *d_ray_a = nullptr, *d_ray_b = nullptr;
+    drt_ray_hit *d_ray_hits = nullptr;
+    uint8_t *d_ray_visible = nullptr;
+    uint32_t *d_ray_xy = nullptr, *d_ray_samples = nullptr;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -916,6 +925,9 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     if (per_cu < 1) per_cu = 1;
     if (const char *e = getenv("DRT_TRACE_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(e)); /* tuning knob */
     ctx->trace_grid_cap = prop.multiProcessorCount * per_cu;
+    ctx->ray_grid_cap = prop.multiProcessorCount * 4; /* the ray-query kernels loop over ray blocks: a few workgroups per CU */
+    if (const char *e = getenv("DRT_RAY_CHUNK")) /* test knob: host-mode ray queries in chunks this small */
+        ctx->ray_chunk = std::max<uint64_t>(1, std::min<uint64_t>(RAY_STAGING_RAYS, strtoull(e, nullptr, 0)));
     if (ctx->bvh_pipeline)
     {
         int p_cu = 0, b_cu = 0;
@@ -1141,6 +1153,12 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_mt_tail);
     (void)hipFree(ctx->d_mt_cover);
     (void)hipFree(ctx->d_mt_info);
+    (void)hipFree(ctx->d_ray_a);
+    (void)hipFree(ctx->d_ray_b);
+    (void)hipFree(ctx->d_ray_hits);
+    (void)hipFree(ctx->d_ray_visible);
+    (void)hipFree(ctx->d_ray_xy);
+    (void)hipFree(ctx->d_ray_samples);
     for (hipEvent_t e : ctx->mt_ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(ctx->h_active);
@@ -3177,6 +3195,266 @@ extern "C" int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids
         if (tail) HIP_TRY(hipMemcpy2D((char *)tail + k * row_tail, n * row_tail, c->d_mt_tail, row_tail, row_tail, g->rows[k], hipMemcpyDeviceToHost));
     }
     return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Ray queries (kernels in drt_ray_kernels.h)                               */
+
+enum { RAYS_CLOSEST = 0, RAYS_VISIBLE = 1, RAYS_PIXELS = 2 };
+static const char *const ray_call_name[3] = {"drt_cast_rays", "drt_test_visibility", "drt_cast_pixels"};
+
+/* the caller's arrays of one query list (or of one device's share of it); which of them a call uses depends on its kind */
+struct RayArgs
+{
+    const double *a = nullptr, *b = nullptr; /* origins and dirs, p0 and p1 */
+    drt_ray_hit *hits = nullptr;
+    uint8_t *visible = nullptr;
+    const uint32_t *xy = nullptr, *samples = nullptr;
+    double *out_a = nullptr, *out_b = nullptr; /* drt_cast_pixels: the rays cast, either may be null */
+};
+
+static RayArgs ray_args_from(const RayArgs &r, uint64_t first)
+{
+    RayArgs s;
+    s.a = r.a ? r.a + first * 3 : nullptr;
+    s.b = r.b ? r.b + first * 3 : nullptr;
+    s.hits = r.hits ? r.hits + first : nullptr;
+    s.visible = r.visible ? r.visible + first : nullptr;
+    s.xy = r.xy ? r.xy + first * 2 : nullptr;
+    s.samples = r.samples ? r.samples + first : nullptr;
+    s.out_a = r.out_a ? r.out_a + first * 3 : nullptr;
+    s.out_b = r.out_b ? r.out_b + first * 3 : nullptr;
+    return s;
+}
+
+/* Everything that can be refused, before any device call. *nothing: the list is empty, a successful no-op. */
+static int rays_check(int kind, uint32_t width, uint32_t height, const RayArgs &r, uint64_t n, uint32_t flags, bool *nothing)
+{
+    const char *who = ray_call_name[kind];
+    *nothing = false;
+    if (flags & ~DRT_RAYS_DEVICE) return fail(-1, "%s: flags = %u: 0 or DRT_RAYS_DEVICE", who, flags);
+    if (n == 0)
+    {
+        *nothing = true;
+        return 0;
+    }
+    if (kind == RAYS_CLOSEST)
+    {
+        if (!r.a) return fail(-1, "%s: origins is null", who);
+        if (!r.b) return fail(-1, "%s: dirs is null", who);
+        if (!r.hits) return fail(-1, "%s: hits is null", who);
+    }
+    else if (kind == RAYS_VISIBLE)
+    {
+        if (!r.a) return fail(-1, "%s: p0 is null", who);
+        if (!r.b) return fail(-1, "%s: p1 is null", who);
+        if (!r.visible) return fail(-1, "%s: visible is null", who);
+    }
+    else
+    {
+        if (!r.xy) return fail(-1, "%s: xy is null", who);
+        if (!r.samples) return fail(-1, "%s: samples is null", who);
+        if (!r.hits) return fail(-1, "%s: hits is null", who);
+    }
+    if ((flags & DRT_RAYS_DEVICE) && n > (1ull << 31)) return fail(-1, "%s: n = %llu: 2^31 rays at most in device mode", who, (unsigned long long)n);
+    if (kind == RAYS_PIXELS && !(flags & DRT_RAYS_DEVICE)) /* (device mode: the host cannot read xy; the kernel gives such a query a NaN ray, a miss) */
+        for (uint64_t i = 0; i < n; i += 1)
+            if (r.xy[i * 2] >= width || r.xy[i * 2 + 1] >= height)
+                return fail(-1, "%s: xy[%llu] = (%u, %u): outside the %u x %u image", who, (unsigned long long)i, r.xy[i * 2], r.xy[i * 2 + 1], width, height);
+    return 0;
+}
+
+/* one launch over device arrays, on the context's stream */
+static int rays_launch(drt_context *ctx, int kind, const RayArgs &d, uint64_t n)
+{
+    RayParams rp{};
+    rp.n = n;
+    rp.a = d.a; rp.b = d.b; rp.hits = d.hits; rp.visible = d.visible;
+    rp.xy = d.xy; rp.samples = d.samples; rp.out_a = d.out_a; rp.out_b = d.out_b;
+    rp.width = ctx->params.width; rp.height = ctx->params.height;
+    rp.pixel_scheme = ctx->params.pixel_scheme;
+    rp.seed = ctx->params.seed;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n + RAY_BLOCK - 1) / RAY_BLOCK, (uint64_t)std::max(1, ctx->ray_grid_cap));
+    const size_t lds = feature_lds_bytes(ctx->dsc.n_surf);
+    hipStream_t st = ctx->stream;
+    if (ctx->scene_in_lds)
+    {
+        if (kind == RAYS_CLOSEST) hipLaunchKernelGGL(drt_ray_closest_kernel<false>, dim3(grid), dim3(RAY_BLOCK), lds, st, ctx->dsc, ctx->dcam, rp);
+        else if (kind == RAYS_PIXELS) hipLaunchKernelGGL(drt_ray_closest_kernel<true>, dim3(grid), dim3(RAY_BLOCK), lds, st, ctx->dsc, ctx->dcam, rp);
+        else hipLaunchKernelGGL(drt_ray_visible_kernel, dim3(grid), dim3(RAY_BLOCK), lds, st, ctx->dsc, rp);
+    }
+    else
+    {
+        if (kind == RAYS_CLOSEST) hipLaunchKernelGGL(drt_ray_closest_bvh_kernel<false>, dim3(grid), dim3(RAY_BLOCK), 0, st, ctx->dsc, ctx->dcam, rp);
+        else if (kind == RAYS_PIXELS) hipLaunchKernelGGL(drt_ray_closest_bvh_kernel<true>, dim3(grid), dim3(RAY_BLOCK), 0, st, ctx->dsc, ctx->dcam, rp);
+        else hipLaunchKernelGGL(drt_ray_visible_bvh_kernel, dim3(grid), dim3(RAY_BLOCK), 0, st, ctx->dsc, rp);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+static int ray_staging(T **p, size_t count)
+{
+    if (!*p) HIP_TRY(hipMalloc((void **)p, count * sizeof(T)));
+    return 0;
+}
+
+/* Host mode: the list in chunks of ctx->ray_chunk rays through the staging buffers, all on the context's stream and in its order, so
+ * a buffer is reused only after the kernel and the copies of the chunk before. Enqueues only; rays_host_finish waits. */
+static int rays_host_enqueue(drt_context *ctx, int kind, const RayArgs &h, uint64_t n)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t cap = (size_t)ctx->ray_chunk;
+    int rc = 0;
+    RayArgs d;
+    if (kind != RAYS_PIXELS)
+    {
+        if ((rc = ray_staging(&ctx->d_ray_a, cap * 3)) || (rc = ray_staging(&ctx->d_ray_b, cap * 3))) return rc;
+        d.a = ctx->d_ray_a;
+        d.b = ctx->d_ray_b;
+    }
+    else
+    {
+        if ((rc = ray_staging(&ctx->d_ray_xy, cap * 2)) || (rc = ray_staging(&ctx->d_ray_samples, cap))) return rc;
+        d.xy = ctx->d_ray_xy;
+        d.samples = ctx->d_ray_samples;
+        if (h.out_a)
+        {
+            if ((rc = ray_staging(&ctx->d_ray_a, cap * 3))) return rc;
+            d.out_a = ctx->d_ray_a;
+        }
+        if (h.out_b)
+        {
+            if ((rc = ray_staging(&ctx->d_ray_b, cap * 3))) return rc;
+            d.out_b = ctx->d_ray_b;
+        }
+    }
+    if (kind == RAYS_VISIBLE)
+    {
+        if ((rc = ray_staging(&ctx->d_ray_visible, cap))) return rc;
+        d.visible = ctx->d_ray_visible;
+    }
+    else
+    {
+        if ((rc = ray_staging(&ctx->d_ray_hits, cap))) return rc;
+        d.hits = ctx->d_ray_hits;
+    }
+    hipStream_t st = ctx->stream;
+    for (uint64_t first = 0; first < n; first += cap)
+    {
+        const size_t m = (size_t)std::min<uint64_t>(cap, n - first);
+        const RayArgs c = ray_args_from(h, first);
+        if (kind != RAYS_PIXELS)
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->d_ray_a, c.a, m * 24, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->d_ray_b, c.b, m * 24, hipMemcpyHostToDevice, st));
+        }
+        else
+        {
+            HIP_TRY(hipMemcpyAsync(ctx->d_ray_xy, c.xy, m * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(ctx->d_ray_samples, c.samples, m * 4, hipMemcpyHostToDevice, st));
+        }
+        if ((rc = rays_launch(ctx, kind, d, m))) return rc;
+        if (kind == RAYS_VISIBLE) HIP_TRY(hipMemcpyAsync(c.visible, ctx->d_ray_visible, m, hipMemcpyDeviceToHost, st));
+        else HIP_TRY(hipMemcpyAsync(c.hits, ctx->d_ray_hits, m * sizeof(drt_ray_hit), hipMemcpyDeviceToHost, st));
+        if (kind == RAYS_PIXELS && c.out_a) HIP_TRY(hipMemcpyAsync(c.out_a, ctx->d_ray_a, m * 24, hipMemcpyDeviceToHost, st));
+        if (kind == RAYS_PIXELS && c.out_b) HIP_TRY(hipMemcpyAsync(c.out_b, ctx->d_ray_b, m * 24, hipMemcpyDeviceToHost, st));
+    }
+    return 0;
+}
+
+static int rays_host_finish(drt_context *ctx, int kind)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(-100 - (int)e, "%s: %s", ray_call_name[kind], hipGetErrorString(e));
+    return 0;
+}
+
+static int rays_call(drt_context *ctx, int kind, const RayArgs &r, uint64_t n, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "%s: ctx is null", ray_call_name[kind]);
+    bool nothing = false;
+    int rc = rays_check(kind, ctx->params.width, ctx->params.height, r, n, flags, &nothing);
+    if (rc || nothing) return rc;
+    if (flags & DRT_RAYS_DEVICE)
+    {
+        HIP_TRY(hipSetDevice(ctx->device));
+        return rays_launch(ctx, kind, r, n);
+    }
+    if ((rc = rays_host_enqueue(ctx, kind, r, n))) return rc;
+    return rays_host_finish(ctx, kind);
+}
+
+extern "C" int drt_cast_rays(drt_context *ctx, const double *origins, const double *dirs, uint64_t n, drt_ray_hit *hits, uint32_t flags)
+{
+    RayArgs r;
+    r.a = origins; r.b = dirs; r.hits = hits;
+    return rays_call(ctx, RAYS_CLOSEST, r, n, flags);
+}
+
+extern "C" int drt_test_visibility(drt_context *ctx, const double *p0, const double *p1, uint64_t n, uint8_t *visible, uint32_t flags)
+{
+    RayArgs r;
+    r.a = p0; r.b = p1; r.visible = visible;
+    return rays_call(ctx, RAYS_VISIBLE, r, n, flags);
+}
+
+extern "C" int drt_cast_pixels(drt_context *ctx, const uint32_t *xy, const uint32_t *samples, uint64_t n, double *origins, double *dirs,
+                               drt_ray_hit *hits, uint32_t flags)
+{
+    RayArgs r;
+    r.xy = xy; r.samples = samples; r.out_a = origins; r.out_b = dirs; r.hits = hits;
+    return rays_call(ctx, RAYS_PIXELS, r, n, flags);
+}
+
+/* The list in contiguous shares, one per device that holds a context, results in list order. Every context holds the same scene, camera,
+ * image size and seed, so the bits are one context's. Checked once, before any launch; every device is given its share before any is
+ * waited for. */
+static int rays_group_call(drt_group *g, int kind, const RayArgs &r, uint64_t n)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "%s: the group is null", ray_call_name[kind]);
+    std::vector<drt_context *> live;
+    for (drt_context *c : g->ctx)
+        if (c) live.push_back(c);
+    if (live.empty()) return fail(-1, "%s: the group holds no context", ray_call_name[kind]);
+    bool nothing = false;
+    int rc = 0;
+    for (drt_context *c : live)
+        if ((rc = rays_check(kind, c->params.width, c->params.height, r, n, 0, &nothing)) || nothing) return rc;
+    const uint64_t k = live.size();
+    for (uint64_t d = 0; d < k; d += 1)
+    {
+        const uint64_t first = n / k * d + std::min<uint64_t>(d, n % k), count = n / k + (d < n % k ? 1 : 0);
+        if (count && (rc = rays_host_enqueue(live[d], kind, ray_args_from(r, first), count))) return rc;
+    }
+    for (drt_context *c : live)
+        if ((rc = rays_host_finish(c, kind))) return rc;
+    return 0;
+}
+
+extern "C" int drt_group_cast_rays(drt_group *g, const double *origins, const double *dirs, uint64_t n, drt_ray_hit *hits)
+{
+    RayArgs r;
+    r.a = origins; r.b = dirs; r.hits = hits;
+    return rays_group_call(g, RAYS_CLOSEST, r, n);
+}
+
+extern "C" int drt_group_test_visibility(drt_group *g, const double *p0, const double *p1, uint64_t n, uint8_t *visible)
+{
+    RayArgs r;
+    r.a = p0; r.b = p1; r.visible = visible;
+    return rays_group_call(g, RAYS_VISIBLE, r, n);
+}
+
+extern "C" int drt_group_cast_pixels(drt_group *g, const uint32_t *xy, const uint32_t *samples, uint64_t n, double *origins, double *dirs, drt_ray_hit *hits)
+{
+    RayArgs r;
+    r.xy = xy; r.samples = samples; r.out_a = origins; r.out_b = dirs; r.hits = hits;
+    return rays_group_call(g, RAYS_PIXELS, r, n);
 }
 
 extern "C" int drt_render_tile_multi(const drt_scene *scene, const drt_camera *camera, const drt_params *params,

@@ -80,7 +80,8 @@ typedef struct
 /* Host extras that the reference has no field for (device choice, RNG seed, batch size, adaptive sampling);
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
- * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES. */
+ * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK. */
+#define DRT_HOST_MAX_PICKS 64
 typedef struct
 {
     int32_t  device;
@@ -113,6 +114,10 @@ typedef struct
      * the previews <output_spd>.surface_id.bmp and .material_id.bmp, and <output_spd>.mattes.txt, which names every surface and
      * material; every other output stays byte for byte what it is without it */
     uint32_t mattes;
+    /* DRT_PICK: what is under these pixels (drt_group_cast_pixels after the render): one `pick` line per entry on stdout; every output
+     * file stays byte for byte what it is without it */
+    uint32_t n_picks;
+    uint32_t pick_xy[DRT_HOST_MAX_PICKS][2], pick_sample[DRT_HOST_MAX_PICKS];
 } drt_host_options;
 
 /* the `adaptive` line of a version-3 checkpoint manifest: what the film was rendered with so far */

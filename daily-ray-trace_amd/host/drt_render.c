@@ -305,6 +305,11 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
             printf("Mattes: %llu camera rays, %.3f ms on the device, %u pixels see nothing, %u / %u see more than %d surfaces / materials\n",
                    (unsigned long long)mt.rays, mt.kernel_ms, mt.empty_pixels, mt.overflow_pixels[0], mt.overflow_pixels[1], DRT_MATTE_SLOTS);
     }
+    /* DRT_PICK: the closest hit of each entry's camera ray (nothing on the devices changes) */
+    drt_ray_hit pick_hits[DRT_HOST_MAX_PICKS];
+    u32 n_picks = (opt && !rc) ? opt->n_picks : 0;
+    if (n_picks) rc = drt_group_cast_pixels(ctx, &opt->pick_xy[0][0], opt->pick_sample, n_picks, NULL, NULL, pick_hits);
+    if (rc) n_picks = 0;
     /* the .bmp pixels come from the film while it is still on the device (drt_read_bgra: the same bytes as converting the
      * .spd files on the host, host/drt_bmp.c, without reading 1.7 GB back from disk) */
     u8 *bgra[3] = { NULL, NULL, NULL };
@@ -347,6 +352,16 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         printf("Paths: %llu  closest-hit scans/path: %.3f  shaded vertices/path: %.3f  Mpaths/s (device): %.2f\n",
                (unsigned long long)stats.paths, (f64)stats.closest_hit_scans / (f64)stats.paths,
                (f64)stats.shaded_vertices / (f64)stats.paths, (f64)stats.paths / (stats.total_ms * 1e3));
+    }
+
+    for (u32 k = 0; k < n_picks; k += 1)
+    {
+        const drt_ray_hit *h = &pick_hits[k];
+        if (h->index < 0) printf("pick %u %u %u miss\n", opt->pick_xy[k][0], opt->pick_xy[k][1], opt->pick_sample[k]);
+        else
+            printf("pick %u %u %u surface %d %s material %u %s distance %.17g position %.17g %.17g %.17g\n", opt->pick_xy[k][0], opt->pick_xy[k][1],
+                   opt->pick_sample[k], h->index, drt_host_surface_name(hs, (u32)h->index), h->surface_material,
+                   drt_host_material_name(hs, h->surface_material), h->distance, h->position[0], h->position[1], h->position[2]);
     }
 
     int wrc;
@@ -570,6 +585,55 @@ static int mattes_options(drt_host_options *opt)
     return 0;
 }
 
+/* DRT_PICK="x,y[,sample][;x,y[,sample]...]": parsed and checked here, before any device call. Whole decimal numbers, the sample 0 when
+ * left out, DRT_HOST_MAX_PICKS entries at most, every pixel inside the output_width x output_height image. */
+static int pick_number(const char **c, u32 *out)
+{
+    if (**c < '0' || **c > '9') return -1;
+    char *end;
+    errno = 0;
+    unsigned long long v = strtoull(*c, &end, 10);
+    if (errno || v > 0xFFFFFFFFull) return -1;
+    *out = (u32)v;
+    *c = end;
+    return 0;
+}
+
+static int pick_options(const config_arguments *config, drt_host_options *opt)
+{
+    const char *e = getenv("DRT_PICK");
+    opt->n_picks = 0;
+    if (!e) return 0;
+    const char *c = e;
+    for (;;)
+    {
+        u32 x, y, sample = 0;
+        if (opt->n_picks == DRT_HOST_MAX_PICKS) { fprintf(stderr, "render_image: DRT_PICK: %d entries at most\n", DRT_HOST_MAX_PICKS); return -1; }
+        if (pick_number(&c, &x) || *c != ',') break;
+        c += 1;
+        if (pick_number(&c, &y)) break;
+        if (*c == ',')
+        {
+            c += 1;
+            if (pick_number(&c, &sample)) break;
+        }
+        if (x >= (u32)config->output_width || y >= (u32)config->output_height)
+        {
+            fprintf(stderr, "render_image: DRT_PICK: pixel (%u, %u) is outside the %u x %u image\n", x, y, (u32)config->output_width, (u32)config->output_height);
+            return -1;
+        }
+        opt->pick_xy[opt->n_picks][0] = x;
+        opt->pick_xy[opt->n_picks][1] = y;
+        opt->pick_sample[opt->n_picks] = sample;
+        opt->n_picks += 1;
+        if (*c == 0) return 0;
+        if (*c != ';') break;
+        c += 1;
+    }
+    fprintf(stderr, "render_image: DRT_PICK=\"%s\": x,y[,sample] entries of whole numbers, separated by ';' (stopped at character %d)\n", e, (int)(c - e));
+    return -1;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -598,5 +662,6 @@ void render_image(config_arguments *config)
     if (denoise_options(config, &opt) != 0) exit(-1);
     if (features_options(config, &opt) != 0) exit(-1);
     if (mattes_options(&opt) != 0) exit(-1);
+    if (pick_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

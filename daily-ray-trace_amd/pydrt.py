@@ -143,6 +143,50 @@ def make_mattes(n_samples=0, first_sample=0):
     return m
 
 
+RAYS_DEVICE = 1  # DRT_RAYS_DEVICE
+
+
+class RayHit(C.Structure):
+    """drt_ray_hit (include/drt_hip.h): a closest hit as find_ray_intersection gives it, plus the distance. 104 bytes."""
+    _fields_ = [("position", f64x3), ("normal", f64x3), ("out", f64x3), ("on_dot", C.c_double), ("distance", C.c_double),
+                ("index", C.c_int32), ("surface_material", C.c_uint32), ("incident_material", C.c_uint32),
+                ("transmit_material", C.c_uint32)]
+
+
+# the same layout as a numpy record: what cast_rays / cast_pixels return in host mode
+RAY_HIT_DTYPE = np.dtype([("position", "<f8", 3), ("normal", "<f8", 3), ("out", "<f8", 3), ("on_dot", "<f8"), ("distance", "<f8"),
+                          ("index", "<i4"), ("surface_material", "<u4"), ("incident_material", "<u4"), ("transmit_material", "<u4")])
+assert RAY_HIT_DTYPE.itemsize == C.sizeof(RayHit) == 104
+
+
+def _is_tensor(a):
+    return "torch" in sys.modules and isinstance(a, sys.modules["torch"].Tensor)
+
+
+def _rays_f64(a, name):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s: an [n][3] array" % name)
+    return a
+
+
+def _rays_tensor(t, name, device):
+    torch = sys.modules["torch"]
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s: a contiguous [n][3] float64 tensor" % name)
+    if t.device.type != "cuda" or t.device.index != device:
+        raise ValueError("%s: a tensor on the context's device (cuda:%d)" % (name, device))
+    return t
+
+
+def _pixels_u32(xy, samples):
+    xy = np.ascontiguousarray(xy, dtype=np.uint32)
+    samples = np.ascontiguousarray(samples, dtype=np.uint32).reshape(-1)
+    if xy.ndim != 2 or xy.shape[1] != 2 or xy.shape[0] != samples.shape[0]:
+        raise ValueError("xy: an [n][2] array, samples: [n]")
+    return xy, samples
+
+
 def _mattes_report(m):
     return {"empty_pixels": m.empty_pixels, "overflow_pixels": (m.overflow_pixels[0], m.overflow_pixels[1]), "rays": m.rays,
             "kernel_ms": m.kernel_ms}
@@ -408,6 +452,14 @@ def hip_lib():
             L.drt_read_features.argtypes = [C.c_void_p, f64p, f64p, i32p]
             L.drt_read_feature_bgra.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_uint8)]
             L.drt_group_render_features.argtypes = [C.c_void_p, C.POINTER(Features), f64p, f64p, i32p]
+        if hasattr(L, "drt_cast_rays"):
+            vp = C.c_void_p  # host or device memory
+            L.drt_cast_rays.argtypes = [C.c_void_p, vp, vp, C.c_uint64, vp, C.c_uint32]
+            L.drt_test_visibility.argtypes = [C.c_void_p, vp, vp, C.c_uint64, vp, C.c_uint32]
+            L.drt_cast_pixels.argtypes = [C.c_void_p, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint32]
+            L.drt_group_cast_rays.argtypes = [C.c_void_p, vp, vp, C.c_uint64, vp]
+            L.drt_group_test_visibility.argtypes = [C.c_void_p, vp, vp, C.c_uint64, vp]
+            L.drt_group_cast_pixels.argtypes = [C.c_void_p, vp, vp, C.c_uint64, vp, vp, vp]
         if hasattr(L, "drt_render_mattes"):
             u32p = C.POINTER(C.c_uint32)
             L.drt_render_mattes.argtypes = [C.c_void_p, C.POINTER(Mattes)]
@@ -443,7 +495,9 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_read_active_list", "drt_render_adaptive_continue", "drt_group_render_adaptive_continue",
                "drt_denoise_film", "drt_read_denoised", "drt_read_denoised_bgra", "drt_denoise_buffers", "drt_group_denoise",
                "drt_render_features", "drt_read_features", "drt_read_feature_bgra", "drt_group_render_features",
-               "drt_render_mattes", "drt_read_mattes", "drt_read_matte", "drt_read_matte_bgra", "drt_group_render_mattes"]
+               "drt_render_mattes", "drt_read_mattes", "drt_read_matte", "drt_read_matte_bgra", "drt_group_render_mattes",
+               "drt_cast_rays", "drt_test_visibility", "drt_cast_pixels", "drt_group_cast_rays", "drt_group_test_visibility",
+               "drt_group_cast_pixels"]
 
 
 def _check(rc, what):
@@ -630,6 +684,70 @@ class Renderer:
         _check(self.L.drt_read_matte_bgra(self.ctx, int(layer), _ptr(out, C.c_uint8)), "drt_read_matte_bgra")
         return out
 
+    def cast_rays(self, origins, dirs):
+        """Closest hits of caller-supplied rays (drt_cast_rays). numpy arrays [n][3]: host mode, returns a RAY_HIT_DTYPE record array
+        [n]. Contiguous float64 torch tensors on the context's device: device mode, enqueued on the context's stream without waiting;
+        returns a uint8 tensor [n][104] (view it as RAY_HIT_DTYPE after .cpu().numpy())."""
+        if _is_tensor(origins) or _is_tensor(dirs):
+            torch = sys.modules["torch"]
+            dev = int(self.params.device)
+            o, d = _rays_tensor(origins, "origins", dev), _rays_tensor(dirs, "dirs", dev)
+            if o.shape != d.shape:
+                raise ValueError("origins and dirs: the same shape")
+            hits = torch.empty((o.shape[0], 104), dtype=torch.uint8, device=o.device)
+            _check(self.L.drt_cast_rays(self.ctx, o.data_ptr(), d.data_ptr(), o.shape[0], hits.data_ptr(), RAYS_DEVICE), "drt_cast_rays")
+            return hits
+        o, d = _rays_f64(origins, "origins"), _rays_f64(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs: the same shape")
+        hits = np.zeros(o.shape[0], dtype=RAY_HIT_DTYPE)
+        _check(self.L.drt_cast_rays(self.ctx, o.ctypes.data, d.ctypes.data, o.shape[0], hits.ctypes.data, 0), "drt_cast_rays")
+        return hits
+
+    def test_visibility(self, p0, p1):
+        """points_mutually_visible of caller-supplied pairs (drt_test_visibility): uint8 [n], 1 visible. numpy arrays: host mode;
+        torch tensors on the context's device: device mode, a uint8 tensor, enqueued without waiting."""
+        if _is_tensor(p0) or _is_tensor(p1):
+            torch = sys.modules["torch"]
+            dev = int(self.params.device)
+            a, b = _rays_tensor(p0, "p0", dev), _rays_tensor(p1, "p1", dev)
+            if a.shape != b.shape:
+                raise ValueError("p0 and p1: the same shape")
+            vis = torch.empty(a.shape[0], dtype=torch.uint8, device=a.device)
+            _check(self.L.drt_test_visibility(self.ctx, a.data_ptr(), b.data_ptr(), a.shape[0], vis.data_ptr(), RAYS_DEVICE), "drt_test_visibility")
+            return vis
+        a, b = _rays_f64(p0, "p0"), _rays_f64(p1, "p1")
+        if a.shape != b.shape:
+            raise ValueError("p0 and p1: the same shape")
+        vis = np.zeros(a.shape[0], dtype=np.uint8)
+        _check(self.L.drt_test_visibility(self.ctx, a.ctypes.data, b.ctypes.data, a.shape[0], vis.ctypes.data, 0), "drt_test_visibility")
+        return vis
+
+    def cast_pixels(self, xy, samples):
+        """The path's own camera ray of pixel xy[i] = (x, y) of the whole image and sample samples[i], and its closest hit
+        (drt_cast_pixels). Returns (origins [n][3], dirs [n][3], hits). numpy arrays: host mode; int32 / uint32-valued torch tensors
+        (dtype int32, values below 2^31) on the context's device: device mode, tensors back, enqueued without waiting."""
+        if _is_tensor(xy) or _is_tensor(samples):
+            torch = sys.modules["torch"]
+            dev = int(self.params.device)
+            for t, name in ((xy, "xy"), (samples, "samples")):
+                if t.dtype != torch.int32 or not t.is_contiguous() or t.device.type != "cuda" or t.device.index != dev:
+                    raise ValueError("%s: a contiguous int32 tensor on the context's device (cuda:%d)" % (name, dev))
+            if xy.dim() != 2 or xy.shape[1] != 2 or samples.dim() != 1 or samples.shape[0] != xy.shape[0]:
+                raise ValueError("xy: an [n][2] tensor, samples: [n]")
+            n = xy.shape[0]
+            o = torch.empty((n, 3), dtype=torch.float64, device=xy.device)
+            d = torch.empty((n, 3), dtype=torch.float64, device=xy.device)
+            hits = torch.empty((n, 104), dtype=torch.uint8, device=xy.device)
+            _check(self.L.drt_cast_pixels(self.ctx, xy.data_ptr(), samples.data_ptr(), n, o.data_ptr(), d.data_ptr(), hits.data_ptr(), RAYS_DEVICE),
+                   "drt_cast_pixels")
+            return o, d, hits
+        xy, samples = _pixels_u32(xy, samples)
+        n = xy.shape[0]
+        o, d, hits = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, dtype=RAY_HIT_DTYPE)
+        _check(self.L.drt_cast_pixels(self.ctx, xy.ctypes.data, samples.ctypes.data, n, o.ctypes.data, d.ctypes.data, hits.ctypes.data, 0), "drt_cast_pixels")
+        return o, d, hits
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -727,6 +845,33 @@ class Group:
         _check(self.L.drt_group_render_mattes(self.g, C.byref(m), _ptr(ids, C.c_int32), _ptr(counts, C.c_uint32), _ptr(tail, C.c_uint32)),
                "drt_group_render_mattes")
         return ids, counts, tail, _mattes_report(m)
+
+    def cast_rays(self, origins, dirs):
+        """drt_group_cast_rays: the list in contiguous shares, one per device; a RAY_HIT_DTYPE record array in list order."""
+        o, d = _rays_f64(origins, "origins"), _rays_f64(dirs, "dirs")
+        if o.shape != d.shape:
+            raise ValueError("origins and dirs: the same shape")
+        hits = np.zeros(o.shape[0], dtype=RAY_HIT_DTYPE)
+        _check(self.L.drt_group_cast_rays(self.g, o.ctypes.data, d.ctypes.data, o.shape[0], hits.ctypes.data), "drt_group_cast_rays")
+        return hits
+
+    def test_visibility(self, p0, p1):
+        """drt_group_test_visibility: uint8 [n] in list order."""
+        a, b = _rays_f64(p0, "p0"), _rays_f64(p1, "p1")
+        if a.shape != b.shape:
+            raise ValueError("p0 and p1: the same shape")
+        vis = np.zeros(a.shape[0], dtype=np.uint8)
+        _check(self.L.drt_group_test_visibility(self.g, a.ctypes.data, b.ctypes.data, a.shape[0], vis.ctypes.data), "drt_group_test_visibility")
+        return vis
+
+    def cast_pixels(self, xy, samples):
+        """drt_group_cast_pixels: (origins, dirs, hits) in list order."""
+        xy, samples = _pixels_u32(xy, samples)
+        n = xy.shape[0]
+        o, d, hits = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, dtype=RAY_HIT_DTYPE)
+        _check(self.L.drt_group_cast_pixels(self.g, xy.ctypes.data, samples.ctypes.data, n, o.ctypes.data, d.ctypes.data, hits.ctypes.data),
+               "drt_group_cast_pixels")
+        return o, d, hits
 
     def close(self):
         if self.g:

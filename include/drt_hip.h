@@ -472,6 +472,49 @@ int drt_read_matte_bgra(drt_context *ctx, int layer, uint8_t *bgra);
  * kernel_ms is the slowest device's. */
 int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids, uint32_t *counts, uint32_t *tail);
 
+/*
+ * Ray queries: the two questions the whole path is built on, asked of the resident scene for rays the caller supplies. The reference's
+ * find_ray_intersection (src/daily_ray_trace.c:334-403) and points_mutually_visible (:238-270) are the rule, and the oracle's
+ * restatement of them is what the device's answers equal bit for bit; DESIGN.md section 5e.
+ *
+ * A query reads the scene tables and the camera only: it changes no film bit, count, statistic, hit log, record pool, feature or matte
+ * buffer and no film generation count, and may be issued between two drt_render calls. n = 0 is a successful no-op. Refused with a
+ * message in drt_last_error() and no device call: a null required pointer when n > 0, flags other than DRT_RAYS_DEVICE, n above 2^31 in
+ * device mode, and (host mode) a pixel outside the image. Host mode (flags = 0: all pointers are host memory) goes through staging
+ * buffers of about a million rays, chunk by chunk, and synchronises the context's stream before it returns. Device mode
+ * (DRT_RAYS_DEVICE) enqueues one launch on the context's stream (drt_set_stream) and returns without waiting: drt_synchronize or the
+ * caller's own stream order completes it. There the host cannot read xy: a pixel outside the image gets a NaN ray, which misses.
+ * In a context whose scene is behind the hierarchy (DRT_PATH_BVH) the box tests' error budget covers origins within the extent the
+ * hierarchy was built for (the scene and the camera); origins far outside it are not held to the rule.
+ */
+typedef struct drt_ray_hit /* scene_point, src/daily_ray_trace.h:113-125, plus the distance */
+{
+    double   position[3], normal[3], out[3]; /* moved origin + dir * distance; the facing normal after the flip (:388-394); -dir */
+    double   on_dot;                         /* normal . out, as :379 and :393 compute it */
+    double   distance;                       /* min_dist: measured from the origin AFTER it was moved by vis_fudge (:339) */
+    int32_t  index;                          /* closest-hit surface index, -1: a miss */
+    uint32_t surface_material, incident_material, transmit_material; /* :381-395: a sphere entered from inside swaps the two media, a plane does not */
+} drt_ray_hit;                               /* 104 bytes, no padding. A miss: index -1, surface_material the escape material, the rest +0 / 0 */
+
+#define DRT_RAYS_DEVICE 1u /* all pointers are device memory on the context's device */
+
+/* find_ray_intersection (src/daily_ray_trace.c:334-403) of ray i = (origins[i], dirs[i]), each [n][3]: the origin is moved by vis_fudge
+ * along dirs[i] as given (no normalisation, :339), the comparison is a strict < over ascending surfaces (:340-364). A NaN direction misses. */
+int drt_cast_rays(drt_context *ctx, const double *origins, const double *dirs, uint64_t n, drt_ray_hit *hits, uint32_t flags);
+/* points_mutually_visible (src/daily_ray_trace.c:238-270) of (p0[i], p1[i]), each [n][3]: visible[i] is 1 or 0. The direction is normalised
+ * (:241), the origin moved by the fudge (:242), the limit |p1 - o| - fudge (:243). p0 == p1 gives a NaN direction and the reference's answer to it. */
+int drt_test_visibility(drt_context *ctx, const double *p0, const double *p1, uint64_t n, uint8_t *visible, uint32_t flags);
+/* Query i is pixel (xy[2i], xy[2i+1]) of the whole width x height image (not only the context's tile) and sample samples[i]: the path's
+ * own camera ray (sample_scene's ray set-up, src/daily_ray_trace.c:550-607, seeded with the path key), written to origins / dirs where
+ * those are not null, and its closest hit as drt_cast_rays gives it. hits[i].index is drt_read_hit_indices' column 0 of that path. */
+int drt_cast_pixels(drt_context *ctx, const uint32_t *xy, const uint32_t *samples, uint64_t n, double *origins, double *dirs, drt_ray_hit *hits,
+                    uint32_t flags);
+/* Host pointers only. The list is split into contiguous shares, one per device; results come back in list order; everything is checked
+ * before any launch. Same bits as one context for any device list. */
+int drt_group_cast_rays(drt_group *g, const double *origins, const double *dirs, uint64_t n, drt_ray_hit *hits);
+int drt_group_test_visibility(drt_group *g, const double *p0, const double *p1, uint64_t n, uint8_t *visible);
+int drt_group_cast_pixels(drt_group *g, const uint32_t *xy, const uint32_t *samples, uint64_t n, double *origins, double *dirs, drt_ray_hit *hits);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */
