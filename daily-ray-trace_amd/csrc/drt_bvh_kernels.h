@@ -84,6 +84,12 @@ __device__ __forceinline__ PathStart path_start(const TraceParams &tp, uint64_t 
     ps.slot = ps.q * (uint64_t)tp.batch + ps.s_local;
     return ps;
 }
+/* the tile pixel of the path's launch pixel once more: only ray mode asks for it (a bound table in host mode is numbered by tile pixel) */
+template <bool LIST>
+__device__ __forceinline__ uint64_t path_tile_pixel(const TraceParams &tp, const PathStart &ps)
+{
+    return LIST ? (uint64_t)tp.pixel_list[ps.q] : ps.q;
+}
 __device__ __forceinline__ uint64_t path_key(const TraceParams &tp, const PathStart &ps)
 {
     return tp.seed + (((uint64_t)ps.sample * (uint64_t)tp.height + (uint64_t)ps.y) * (uint64_t)tp.width + (uint64_t)ps.x);
@@ -97,11 +103,13 @@ __device__ __forceinline__ uint64_t path_key(const TraceParams &tp, const PathSt
 #ifndef DRT_PRIMARY_WAVES_PER_SIMD
 #define DRT_PRIMARY_WAVES_PER_SIMD 6 /* 80 registers, 28 bytes of scratch: config 5 trace stage 506 -> 500 ms (5 and 8 waves: 501, 500) */
 #endif
-template <bool LIST = false>
-__global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt_primary_kernel(DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ headers,
-                                                                    int32_t *__restrict__ hits, unsigned long long *__restrict__ counters,
-                                                                    PrimaryHit *__restrict__ primary, uint64_t *__restrict__ queue,
-                                                                    unsigned long long *__restrict__ queue_count)
+/* the kernel's body: drt_primary_kernel's (RAYS = false, rt not read) and, with the first ray and the header's factor from a bound ray
+ * table, drt_primary_rays_kernel's */
+template <bool LIST, bool RAYS>
+__device__ __forceinline__ void primary_paths(DevScene sc, DevCamera cam, TraceParams tp, uint64_t *headers,
+                                              int32_t *hits, unsigned long long *counters,
+                                              PrimaryHit *primary, uint64_t *queue,
+                                              unsigned long long *queue_count, const DevRayTable &rt)
 {
     __shared__ int s_stack[PRIMARY_BLOCK / 64][BVH_LDS_STACK];
     SceneView sv;
@@ -124,10 +132,12 @@ __global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt
         V3 ro = v3(0, 0, 0), rd = v3(0, 0, 1);
         PathStart ps = path_start<LIST>(tp, valid ? pid : 0);
         uint64_t rs = 1;
+        double weight = 1.0;
         if (valid)
         {
             rs = drt_splitmix64(path_key(tp, ps));
-            camera_ray(cam, tp.pixel_scheme, ps.x, ps.y, rs, n_draws, ro, rd);
+            if (RAYS) weight = table_ray(rt, tp.width, path_tile_pixel<LIST>(tp, ps), ps.x, ps.y, ps.sample, ro, rd); /* no draw before cast_ray */
+            else camera_ray(cam, tp.pixel_scheme, ps.x, ps.y, rs, n_draws, ro, rd);
             n_paths += 1;
             n_scans += 1;
         }
@@ -195,7 +205,7 @@ __global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt
             const uint32_t smat = index >= 0 ? sv.surf_mat[index] : sc.escape_mat;
             const DevMaterial &mat = sv.mats[smat];
             uint64_t *hdr = headers + ps.slot * REC_HEADER_WORDS;
-            hdr[1] = (uint64_t)__double_as_longlong(v_dot(rd, cam.forward) * 1.0); /* vignette, :614 */
+            hdr[1] = (uint64_t)__double_as_longlong((RAYS ? weight : v_dot(rd, cam.forward)) * 1.0); /* vignette, :614 */
             if (tp.record_hits)
             {
                 int32_t *h = hits + ((uint64_t)tp.hits_sample_offset * tp.n_pix + ps.hit_row) * tp.max_depth;
@@ -232,6 +242,25 @@ __global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
         if (lane == 0 && v) atomicAdd(&counters[slot_of[k]], (unsigned long long)v);
     }
+}
+
+template <bool LIST = false>
+__global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt_primary_kernel(DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ headers,
+                                                                    int32_t *__restrict__ hits, unsigned long long *__restrict__ counters,
+                                                                    PrimaryHit *__restrict__ primary, uint64_t *__restrict__ queue,
+                                                                    unsigned long long *__restrict__ queue_count)
+{
+    const DevRayTable no_table = {nullptr, nullptr, nullptr, 0u, 0u, 0u, 0u};
+    primary_paths<LIST, false>(sc, cam, tp, headers, hits, counters, primary, queue, queue_count, no_table);
+}
+
+template <bool LIST = false>
+__global__ __launch_bounds__(PRIMARY_BLOCK, DRT_PRIMARY_WAVES_PER_SIMD) void drt_primary_rays_kernel(DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ headers,
+                                                                    int32_t *__restrict__ hits, unsigned long long *__restrict__ counters,
+                                                                    PrimaryHit *__restrict__ primary, uint64_t *__restrict__ queue,
+                                                                    unsigned long long *__restrict__ queue_count, DevRayTable rt)
+{
+    primary_paths<LIST, true>(sc, cam, tp, headers, hits, counters, primary, queue, queue_count, rt);
 }
 
 /* ---------------------------------------------------------------------------------------------- */
@@ -359,11 +388,13 @@ __device__ __forceinline__ void bvh_walk(const SceneView &sv, int *stack, int *l
     }
 }
 
-template <bool LIST = false>
-__global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_bounce_kernel(
-    DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ records, uint64_t *__restrict__ headers, int32_t *__restrict__ hits,
-    unsigned long long *__restrict__ counters, unsigned long long *__restrict__ work_counter, const PrimaryHit *__restrict__ primary,
-    const uint64_t *__restrict__ queue, const unsigned long long *__restrict__ queue_count)
+/* the kernel's body: drt_bounce_kernel's (RAYS = false, rt not read) and drt_bounce_rays_kernel's, which takes a path's first ray from
+ * the bound ray table where the other recomputes the camera's */
+template <bool LIST, bool RAYS>
+__device__ __forceinline__ void bounce_paths(
+    DevScene sc, DevCamera cam, TraceParams tp, uint64_t *records, uint64_t *headers, int32_t *hits,
+    unsigned long long *counters, unsigned long long *work_counter, const PrimaryHit *primary,
+    const uint64_t *queue, const unsigned long long *queue_count, const DevRayTable &rt)
 {
     __shared__ int s_stack[BOUNCE_BLOCK / 64][BVH_LDS_STACK * 64];
     __shared__ int s_leaf_queue[BOUNCE_BLOCK / 64][BVH_QUEUE_WORDS];
@@ -456,7 +487,8 @@ __global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_b
                 rs = drt_splitmix64(path_key(tp, ps));
                 uint32_t camera_draws = 0; /* counted by the primary kernel */
                 V3 ro, rd;
-                camera_ray(cam, tp.pixel_scheme, ps.x, ps.y, rs, camera_draws, ro, rd);
+                if (RAYS) (void)table_ray(rt, tp.width, path_tile_pixel<LIST>(tp, ps), ps.x, ps.y, ps.sample, ro, rd);
+                else camera_ray(cam, tp.pixel_scheme, ps.x, ps.y, rs, camera_draws, ro, rd);
                 hdr = headers + ps.slot * REC_HEADER_WORDS;
                 const PrimaryHit ph = primary[ps.slot];
                 hit_point_from_scan(sv, sc, ip, v_sum(ro, v_mul(rd, DRT_VIS_FUDGE)), rd, ph.min_dist, ph.index);
@@ -624,4 +656,23 @@ __global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_b
         for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
         if (lane == 0 && v) atomicAdd(&counters[k], (unsigned long long)v);
     }
+}
+
+template <bool LIST = false>
+__global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_bounce_kernel(
+    DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ records, uint64_t *__restrict__ headers, int32_t *__restrict__ hits,
+    unsigned long long *__restrict__ counters, unsigned long long *__restrict__ work_counter, const PrimaryHit *__restrict__ primary,
+    const uint64_t *__restrict__ queue, const unsigned long long *__restrict__ queue_count)
+{
+    const DevRayTable no_table = {nullptr, nullptr, nullptr, 0u, 0u, 0u, 0u};
+    bounce_paths<LIST, false>(sc, cam, tp, records, headers, hits, counters, work_counter, primary, queue, queue_count, no_table);
+}
+
+template <bool LIST = false>
+__global__ __launch_bounds__(BOUNCE_BLOCK, DRT_BOUNCE_WAVES_PER_SIMD) void drt_bounce_rays_kernel(
+    DevScene sc, DevCamera cam, TraceParams tp, uint64_t *__restrict__ records, uint64_t *__restrict__ headers, int32_t *__restrict__ hits,
+    unsigned long long *__restrict__ counters, unsigned long long *__restrict__ work_counter, const PrimaryHit *__restrict__ primary,
+    const uint64_t *__restrict__ queue, const unsigned long long *__restrict__ queue_count, DevRayTable rt)
+{
+    bounce_paths<LIST, true>(sc, cam, tp, records, headers, hits, counters, work_counter, primary, queue, queue_count, rt);
 }

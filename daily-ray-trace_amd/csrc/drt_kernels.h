@@ -121,6 +121,18 @@ struct DevCamera
     double aperture_radius, focal_depth, pixel_width, pixel_height;
 };
 
+/* A bound ray table (drt_bind_rays): one primary ray and one weight per pixel and layer, read where the camera kernels call
+ * camera_ray and store the vignette. `tiled`: the arrays hold the rows of the context's own tile, [n_layers][tile pixels], and
+ * entry t_offset + t belongs to the launch's tile pixel t (host mode: the launcher's copy); otherwise they are the caller's
+ * whole-image arrays [n_layers][height][width] (device mode). layer_stride is the entries of one layer either way. */
+struct DevRayTable
+{
+    const double *origins, *dirs; /* [entries][3] */
+    const double *weights;        /* [entries], or NULL: every weight is 1.0 */
+    uint64_t      layer_stride, t_offset;
+    uint32_t      n_layers, tiled;
+};
+
 /* ---------------------------------------------------------------------------------------------- */
 /* Vertex records (trace -> shade). All 8-byte words; self-contained, so the shade kernel never  */
 /* looks a material up: the trace kernel resolves it into a packed BDSF list + SPD indices.        */
@@ -950,6 +962,20 @@ __device__ __forceinline__ void camera_ray(const DevCamera &cam, uint32_t scheme
     }
 }
 
+/* Ray mode's replacement of camera_ray and of the vignette factor (src/daily_ray_trace.c:577-607, :614): the ray of image pixel
+ * (x, y) (tile pixel t of the launch) and absolute sample `sample` is entry (sample % n_layers) of that pixel, taken as it stands --
+ * no draw, no normalisation -- and the returned weight stands where dot(ray_direction, forward) stood. */
+__device__ __forceinline__ double table_ray(const DevRayTable &rt, uint32_t width, uint64_t t, uint32_t x, uint32_t y, uint32_t sample,
+                                            V3 &ro, V3 &rd)
+{
+    const uint32_t l = sample % rt.n_layers;
+    const uint64_t r = (uint64_t)l * rt.layer_stride + (rt.tiled ? rt.t_offset + t : (uint64_t)y * (uint64_t)width + (uint64_t)x);
+    const double *o = rt.origins + 3u * r, *d = rt.dirs + 3u * r;
+    ro = v3(o[0], o[1], o[2]);
+    rd = v3(d[0], d[1], d[2]);
+    return rt.weights ? rt.weights[r] : 1.0;
+}
+
 /* Path ids without a 64-bit division per path. A wave hands out consecutive ids, so it keeps the (pixel, sample) pair of the next
  * id it will hand out -- PathPos, wave-uniform, from one 64-bit division per draw from the work counter -- and a lane that takes
  * the id `r` places further on (r <= 64) gets its pair from that one by 32-bit arithmetic. The same integers as id / n_samples
@@ -1021,6 +1047,13 @@ struct TraceConst /* the kernel's argument list, in its order: the kernarg segme
 };
 static_assert(sizeof(DevScene) % 8 == 0 && sizeof(DevCamera) % 8 == 0 && sizeof(TraceParams) % 8 == 0,
               "TraceConst mirrors the kernarg segment only while every argument ends on an 8-byte boundary");
+/* the ray-mode entry points take the table as one more argument behind these: the same segment, one structure longer */
+struct TraceRaysConst
+{
+    TraceConst  k;
+    DevRayTable rt;
+};
+static_assert(sizeof(TraceConst) % 8 == 0 && sizeof(DevRayTable) % 8 == 0, "the table follows the last pointer without padding");
 #ifndef DRT_TRACE_CONST
 #define DRT_TRACE_CONST 2
 #endif
@@ -1065,11 +1098,13 @@ __device__ unsigned long long drt_branch_stats[DRT_BS_WORDS];
 __device__ unsigned int drt_branch_waves_done;
 #endif
 
-template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
-__global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
-                                                                 uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
-                                                                 int32_t *__restrict__ k_hits, unsigned long long *__restrict__ k_counters,
-                                                                 unsigned long long *__restrict__ k_work_counter)
+/* The kernel's body, shared by the camera entry points (drt_trace_kernel, RAYS = false: k_rt is not read) and the ray-mode ones
+ * (drt_trace_rays_kernel): they differ in the path's first ray and in the factor the header carries, nothing else. */
+template <bool SCENE_IN_LDS, bool TAIL, bool LIST, bool RAYS>
+__device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
+                                            uint64_t *records, uint64_t *headers,
+                                            int32_t *k_hits, unsigned long long *k_counters,
+                                            unsigned long long *k_work_counter, const DevRayTable &k_rt)
 {
     extern __shared__ double lds_raw[];
     /* the k_ arguments are read in this prologue only (see TraceConst): the loop reads LC, or the locals made here */
@@ -1090,6 +1125,11 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
 #define LC k_all
 #else
 #define LC trace_const(lds_raw)
+#endif
+#if DRT_TRACE_CONST == 2
+#define LC_RT (((const TraceRaysConst &)trace_const(lds_raw)).rt) /* read where a path starts, like the camera */
+#else
+#define LC_RT k_rt
 #endif
     SceneView sv;
     double *l_spd_tail = nullptr, *tail_state = nullptr;
@@ -1280,7 +1320,9 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 if (LIST) sample += c.tp.sample_base[t];
                 uint64_t key = c.tp.seed + (((uint64_t)sample * (uint64_t)c.tp.height + (uint64_t)y) * (uint64_t)c.tp.width + (uint64_t)x);
                 rs = drt_splitmix64(key);
-                camera_ray(c.cam, c.tp.pixel_scheme, x, y, rs, n_draws, ro, rd);
+                double weight = 1.0;
+                if (RAYS) weight = table_ray(LC_RT, c.tp.width, t, x, y, sample, ro, rd); /* no draw before cast_ray */
+                else camera_ray(c.cam, c.tp.pixel_scheme, x, y, rs, n_draws, ro, rd);
                 depth = 0;
                 shaded = 0;
                 plastic_mask = 0;
@@ -1300,7 +1342,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
                 uint64_t slot = q * (uint64_t)c.tp.batch + s_local;
                 hdr = headers + slot * REC_HEADER_WORDS;
                 /* vignette: dot(ray_direction, forward) of the PRIMARY ray, src/daily_ray_trace.c:614 */
-                hdr[1] = (uint64_t)__double_as_longlong(v_dot(rd, c.cam.forward) * 1.0);
+                hdr[1] = (uint64_t)__double_as_longlong((RAYS ? weight : v_dot(rd, c.cam.forward)) * 1.0);
                 n_paths += 1;
                 if (record_hits)
                 {
@@ -1580,6 +1622,28 @@ __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_tra
     }
 #endif
 #undef LC
+#undef LC_RT
+}
+
+template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
+__global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
+                                                                 uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
+                                                                 int32_t *__restrict__ k_hits, unsigned long long *__restrict__ k_counters,
+                                                                 unsigned long long *__restrict__ k_work_counter)
+{
+    const DevRayTable no_table = {nullptr, nullptr, nullptr, 0u, 0u, 0u, 0u};
+    trace_paths<SCENE_IN_LDS, TAIL, LIST, false>(k_sc, k_cam, k_tp, records, headers, k_hits, k_counters, k_work_counter, no_table);
+}
+
+/* Ray mode (drt_bind_rays): the same kernel with the table behind its arguments. The camera argument stays, unread, so that the
+ * segment keeps TraceConst's layout. */
+template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
+__global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_rays_kernel(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
+                                                                 uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
+                                                                 int32_t *__restrict__ k_hits, unsigned long long *__restrict__ k_counters,
+                                                                 unsigned long long *__restrict__ k_work_counter, DevRayTable k_rt)
+{
+    trace_paths<SCENE_IN_LDS, TAIL, LIST, true>(k_sc, k_cam, k_tp, records, headers, k_hits, k_counters, k_work_counter, k_rt);
 }
 
 /* ---------------------------------------------------------------------------------------------- */

@@ -156,6 +156,10 @@ struct drt_context
     drt_ray_hit *d_ray_hits = nullptr;
     uint8_t *d_ray_visible = nullptr;
     uint32_t *d_ray_xy = nullptr, *d_ray_samples = nullptr;
+    /* ray films (drt_bind_rays): the table the ray-mode kernels read, and the device copies of the tile's rows that host mode made */
+    bool        rays_bound = false;
+    DevRayTable rt{};
+    double     *d_rt_origins = nullptr, *d_rt_dirs = nullptr, *d_rt_weights = nullptr;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -1159,6 +1163,9 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_ray_visible);
     (void)hipFree(ctx->d_ray_xy);
     (void)hipFree(ctx->d_ray_samples);
+    (void)hipFree(ctx->d_rt_origins);
+    (void)hipFree(ctx->d_rt_dirs);
+    (void)hipFree(ctx->d_rt_weights);
     for (hipEvent_t e : ctx->mt_ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(ctx->h_active);
@@ -1296,33 +1303,44 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
         tp.chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, 64), ctx->bvh_pipeline ? 256 : 1024); /* queued paths all cost alike: small draws (config 5: 827 ms at 64-256, 855 at 1024) */
         if (ctx->trace_chunk_override) tp.chunk = ctx->trace_chunk_override;
     }
+    /* a bound ray table: the same launches through the ray-mode entry points, the table behind their arguments. A launch over rows
+     * [row0, ...) of the tile numbers its pixels from there; a list's pixels are numbered in the whole tile */
+    DevRayTable rt = ctx->rt;
+    rt.t_offset = (list || whole) ? 0 : (uint64_t)row0 * p.tile_w;
+    const bool rays = ctx->rays_bound;
     if (ctx->bvh_pipeline)
     {
         /* camera rays: a wave per 64 path ids; then the queued paths, one per lane */
         const uint64_t packets = (tp.n_paths + 63) / 64;
         const uint32_t pgrid = (uint32_t)std::min<uint64_t>((packets + PRIMARY_BLOCK / 64 - 1) / (PRIMARY_BLOCK / 64), (uint64_t)ctx->primary_grid_cap);
-#define DRT_LAUNCH_BVH(LIST)                                                                                                                    \
-        hipLaunchKernelGGL(drt_primary_kernel<LIST>, dim3(pgrid), dim3(PRIMARY_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, tp, ctx->d_headers, \
-                           ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, ctx->d_primary, ctx->d_queue, work + 2);                            \
-        HIP_TRY(hipGetLastError());                                                                                                             \
-        hipLaunchKernelGGL(drt_bounce_kernel<LIST>, dim3(grid), dim3(BOUNCE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, tp, ctx->d_records,    \
-                           ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work, ctx->d_primary, ctx->d_queue, work + 2)
+#define DRT_BVH_ARGS_P ctx->dsc, ctx->dcam, tp, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, ctx->d_primary, ctx->d_queue, work + 2
+#define DRT_BVH_ARGS_B ctx->dsc, ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work, ctx->d_primary, ctx->d_queue, work + 2
+#define DRT_LAUNCH_BVH(LIST)                                                                                                              \
+        if (rays) hipLaunchKernelGGL(drt_primary_rays_kernel<LIST>, dim3(pgrid), dim3(PRIMARY_BLOCK), 0, ctx->stream, DRT_BVH_ARGS_P, rt); \
+        else hipLaunchKernelGGL(drt_primary_kernel<LIST>, dim3(pgrid), dim3(PRIMARY_BLOCK), 0, ctx->stream, DRT_BVH_ARGS_P);               \
+        HIP_TRY(hipGetLastError());                                                                                                       \
+        if (rays) hipLaunchKernelGGL(drt_bounce_rays_kernel<LIST>, dim3(grid), dim3(BOUNCE_BLOCK), 0, ctx->stream, DRT_BVH_ARGS_B, rt);    \
+        else hipLaunchKernelGGL(drt_bounce_kernel<LIST>, dim3(grid), dim3(BOUNCE_BLOCK), 0, ctx->stream, DRT_BVH_ARGS_B)
         if (list) { DRT_LAUNCH_BVH(true); }
         else { DRT_LAUNCH_BVH(false); }
 #undef DRT_LAUNCH_BVH
+#undef DRT_BVH_ARGS_P
+#undef DRT_BVH_ARGS_B
     }
-    else if (list && ctx->trace_tail && tp.tail_stage)
-        hipLaunchKernelGGL((drt_trace_kernel<true, true, true>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
-                           ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
-    else if (list)
-        hipLaunchKernelGGL((drt_trace_kernel<true, false, true>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
-                           ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
-    else if (ctx->trace_tail && tp.tail_stage)
-        hipLaunchKernelGGL((drt_trace_kernel<true, true>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
-                           ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
     else
-        hipLaunchKernelGGL((drt_trace_kernel<true, false>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, ctx->dsc,
-                           ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work);
+    {
+#define DRT_TRACE_ARGS ctx->dsc, ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work
+#define DRT_LAUNCH_TRACE(TAIL, LIST)                                                                                                                       \
+        if (rays) hipLaunchKernelGGL((drt_trace_rays_kernel<true, TAIL, LIST>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, DRT_TRACE_ARGS, rt); \
+        else hipLaunchKernelGGL((drt_trace_kernel<true, TAIL, LIST>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, DRT_TRACE_ARGS)
+        const bool tail = ctx->trace_tail && tp.tail_stage;
+        if (list && tail) { DRT_LAUNCH_TRACE(true, true); }
+        else if (list) { DRT_LAUNCH_TRACE(false, true); }
+        else if (tail) { DRT_LAUNCH_TRACE(true, false); }
+        else { DRT_LAUNCH_TRACE(false, false); }
+#undef DRT_LAUNCH_TRACE
+#undef DRT_TRACE_ARGS
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1713,7 +1731,8 @@ extern "C" int drt_get_stats(drt_context *ctx, drt_stats *out)
     out->record_block_bytes = ctx->block_words * 8;
     out->redone_launches = (uint32_t)ctx->redone_batches;
     out->launches = (uint32_t)std::min<uint64_t>(ctx->timed_pairs, 0xFFFFFFFFull);
-    out->path_flags = (ctx->bvh_pipeline ? DRT_PATH_BVH : 0u) | ((ctx->trace_tail && ctx->d_tail_stage) ? DRT_PATH_TRACE_TAIL : 0u);
+    out->path_flags = (ctx->bvh_pipeline ? DRT_PATH_BVH : 0u) | ((ctx->trace_tail && ctx->d_tail_stage) ? DRT_PATH_TRACE_TAIL : 0u) |
+                      (ctx->rays_bound ? DRT_PATH_RAYS : 0u);
     out->min_sample_ms = ctx->min_sample_ms;
     out->max_sample_ms = ctx->max_sample_ms;
     out->avg_sample_ms = ctx->avg_sample_ms;
@@ -2839,6 +2858,7 @@ static int film_counts(drt_context *ctx, const char *who, uint32_t first_sample)
  * rendered; the film, the adaptive counts and the render state stay as they are. */
 static int features_prepare(drt_context *ctx, const drt_features *f)
 {
+    if (ctx->rays_bound) return fail(-7, "features: they are made from the camera's rays, and a ray table is bound (drt_bind_rays with NULL unbinds it)");
     if (f->n_samples == 0 && ctx->xyz_mode)
         return fail(-4, "features: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)");
     if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "features: a tile of %llu pixels", (unsigned long long)ctx->n_pix);
@@ -3010,6 +3030,7 @@ static int mattes_check(const drt_mattes *m)
  * stay as they are. */
 static int mattes_prepare(drt_context *ctx, const drt_mattes *m)
 {
+    if (ctx->rays_bound) return fail(-7, "mattes: they are made from the camera's rays, and a ray table is bound (drt_bind_rays with NULL unbinds it)");
     if (m->n_samples == 0 && ctx->xyz_mode)
         return fail(-4, "mattes: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)");
     if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "mattes: a tile of %llu pixels", (unsigned long long)ctx->n_pix);
@@ -3376,6 +3397,8 @@ static int rays_call(drt_context *ctx, int kind, const RayArgs &r, uint64_t n, u
 {
     g_last_error.clear();
     if (!ctx) return fail(-1, "%s: ctx is null", ray_call_name[kind]);
+    if (kind == RAYS_PIXELS && ctx->rays_bound)
+        return fail(-7, "%s: it asks for the camera's rays, and a ray table is bound (drt_bind_rays with NULL unbinds it)", ray_call_name[kind]);
     bool nothing = false;
     int rc = rays_check(kind, ctx->params.width, ctx->params.height, r, n, flags, &nothing);
     if (rc || nothing) return rc;
@@ -3421,6 +3444,9 @@ static int rays_group_call(drt_group *g, int kind, const RayArgs &r, uint64_t n)
     for (drt_context *c : g->ctx)
         if (c) live.push_back(c);
     if (live.empty()) return fail(-1, "%s: the group holds no context", ray_call_name[kind]);
+    for (drt_context *c : live)
+        if (kind == RAYS_PIXELS && c->rays_bound)
+            return fail(-7, "%s: it asks for the camera's rays, and a ray table is bound (drt_group_bind_rays with NULL unbinds it)", ray_call_name[kind]);
     bool nothing = false;
     int rc = 0;
     for (drt_context *c : live)
@@ -3455,6 +3481,145 @@ extern "C" int drt_group_cast_pixels(drt_group *g, const uint32_t *xy, const uin
     RayArgs r;
     r.xy = xy; r.samples = samples; r.out_a = origins; r.out_b = dirs; r.hits = hits;
     return rays_group_call(g, RAYS_PIXELS, r, n);
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Ray films: the first ray from a table (include/drt_hip.h)                           */
+
+/* what makes a call a refusal before anything is touched; t == NULL (unbind) has only the film's state to pass */
+static int bind_rays_check(const drt_context *ctx, const drt_ray_table *t, const char *name, bool group)
+{
+    if (t)
+    {
+        if (!t->origins || !t->dirs) return fail(-1, "%s: %s is null", name, !t->origins ? "origins" : "dirs");
+        if (t->n_layers == 0) return fail(-1, "%s: n_layers is 0 (a table has at least one layer)", name);
+        if (t->flags & ~DRT_RAYS_DEVICE) return fail(-1, "%s: unknown flags 0x%x", name, t->flags);
+        if (group && (t->flags & DRT_RAYS_DEVICE)) return fail(-1, "%s: host pointers only (DRT_RAYS_DEVICE is per context: drt_bind_rays)", name);
+    }
+    if (ctx->film_used || ctx->adaptive_done)
+        return fail(-7, "%s: the film holds samples, and the first ray cannot change under them: drt_reset_film first", name);
+    return 0;
+}
+
+/* A binding made ready but not yet in force: the table the kernels will read and, in host mode, the device copies behind it. Making it
+ * can fail (memory, a copy); putting it in force cannot, so a group makes every context's ready before it changes any. */
+struct PendingRays
+{
+    DevRayTable rt{};
+    double     *d_new[3] = {nullptr, nullptr, nullptr};
+    bool        bound = false;
+};
+
+static void bind_rays_drop(drt_context *ctx, PendingRays &pr)
+{
+    (void)hipSetDevice(ctx->device);
+    for (double *&d : pr.d_new)
+    {
+        (void)hipFree(d);
+        d = nullptr;
+    }
+}
+
+static int bind_rays_prepare(drt_context *ctx, const drt_ray_table *t, PendingRays &pr, const char *name)
+{
+    const drt_params &p = ctx->params;
+    HIP_TRY(hipSetDevice(ctx->device));
+    pr.bound = t != nullptr;
+    if (!t) return 0;
+    DevRayTable &rt = pr.rt;
+    rt.n_layers = t->n_layers;
+    if (t->flags & DRT_RAYS_DEVICE)
+    {
+        rt.origins = t->origins; rt.dirs = t->dirs; rt.weights = t->weights;
+        rt.layer_stride = (uint64_t)p.width * p.height;
+        rt.tiled = 0u;
+        return 0;
+    }
+    /* the tile's rows of every layer, packed [n_layers][tile_h][tile_w]: tile pixel (i, j) is image pixel (x0 + i, y0 + j * row_stride) */
+    const uint64_t n_tile = ctx->n_pix, entries = n_tile * t->n_layers;
+    const double *src[3] = {t->origins, t->dirs, t->weights};
+    for (int a = 0; a < 3; a += 1)
+    {
+        if (!src[a]) continue;
+        const size_t per = a < 2 ? 3 : 1;
+        const size_t count = (size_t)entries * per;
+        double *rows = (double *)malloc(std::max<size_t>(count, 1) * sizeof(double));
+        if (!rows)
+        {
+            bind_rays_drop(ctx, pr);
+            return fail(-3, "%s: out of host memory for %llu table entries", name, (unsigned long long)entries);
+        }
+        for (uint64_t l = 0; l < t->n_layers; l += 1)
+            for (uint32_t j = 0; j < p.tile_h; j += 1)
+            {
+                const uint64_t from = ((l * p.height + (uint64_t)p.y0 + (uint64_t)j * p.row_stride) * p.width + p.x0) * per;
+                memcpy(rows + (l * n_tile + (uint64_t)j * p.tile_w) * per, src[a] + from, (size_t)p.tile_w * per * sizeof(double));
+            }
+        hipError_t e = hipMalloc((void **)&pr.d_new[a], std::max<size_t>(count, 1) * sizeof(double));
+        if (e == hipSuccess && count) e = hipMemcpy(pr.d_new[a], rows, count * sizeof(double), hipMemcpyHostToDevice);
+        free(rows);
+        if (e != hipSuccess)
+        {
+            (void)hipGetLastError();
+            bind_rays_drop(ctx, pr);
+            return fail(-100 - (int)e, "%s: %s", name, hipGetErrorString(e));
+        }
+    }
+    rt.origins = pr.d_new[0]; rt.dirs = pr.d_new[1]; rt.weights = pr.d_new[2];
+    rt.layer_stride = n_tile;
+    rt.tiled = 1u;
+    return 0;
+}
+
+/* cannot fail. No render is in flight (the film holds no samples), so the old copies can go; a query enqueued in device mode does not
+ * read them */
+static void bind_rays_commit(drt_context *ctx, PendingRays &pr)
+{
+    (void)hipSetDevice(ctx->device);
+    (void)hipFree(ctx->d_rt_origins);
+    (void)hipFree(ctx->d_rt_dirs);
+    (void)hipFree(ctx->d_rt_weights);
+    ctx->d_rt_origins = pr.d_new[0]; ctx->d_rt_dirs = pr.d_new[1]; ctx->d_rt_weights = pr.d_new[2];
+    pr.d_new[0] = pr.d_new[1] = pr.d_new[2] = nullptr;
+    ctx->rt = pr.rt;
+    ctx->rays_bound = pr.bound;
+}
+
+extern "C" int drt_bind_rays(drt_context *ctx, const drt_ray_table *t)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "drt_bind_rays: ctx is null");
+    int rc = bind_rays_check(ctx, t, "drt_bind_rays", false);
+    if (rc) return rc;
+    PendingRays pr;
+    if ((rc = bind_rays_prepare(ctx, t, pr, "drt_bind_rays"))) return rc;
+    bind_rays_commit(ctx, pr);
+    return 0;
+}
+
+extern "C" int drt_group_bind_rays(drt_group *g, const drt_ray_table *t)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_bind_rays: the group is null");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = bind_rays_check(c, t, "drt_group_bind_rays", true))) return rc;
+    /* every device's copy is made before any context changes: a device that fails leaves the whole group as it was */
+    PendingRays pending[64]; /* a group holds 64 devices at most (drt_group_create) */
+    const size_t n = g->ctx.size();
+    for (size_t k = 0; k < n && !rc; k += 1)
+        if (g->ctx[k]) rc = bind_rays_prepare(g->ctx[k], t, pending[k], "drt_group_bind_rays");
+    if (rc)
+    {
+        const std::string keep = g_last_error;
+        for (size_t k = 0; k < n; k += 1)
+            if (g->ctx[k]) bind_rays_drop(g->ctx[k], pending[k]);
+        g_last_error = keep;
+        return rc;
+    }
+    for (size_t k = 0; k < n; k += 1)
+        if (g->ctx[k]) bind_rays_commit(g->ctx[k], pending[k]);
+    return 0;
 }
 
 extern "C" int drt_render_tile_multi(const drt_scene *scene, const drt_camera *camera, const drt_params *params,

@@ -73,6 +73,18 @@ static void sync_parent(const char *path)
 }
 
 /* FNV-1a over the scene file's bytes (0 when it cannot be read): a resumed run must be the same scene */
+/* The projection the job renders through (drt_host_checkpoint_projection; 0: the scene's camera). It is part of what a film was rendered
+ * FROM, so it goes into the manifest's scene fingerprint: a checkpoint taken under one projection is refused under another, as one of
+ * another scene file is. With the camera the fingerprint is the scene file's alone, as it always was. */
+static u32 g_projection = 0;
+static f64 g_ortho_width = 0.0;
+
+void drt_host_checkpoint_projection(u32 projection, f64 ortho_width)
+{
+    g_projection = projection;
+    g_ortho_width = projection == DRT_HOST_PROJECTION_ORTHO ? ortho_width : 0.0;
+}
+
 static u64 scene_hash(const char *path)
 {
     FILE *f = fopen(path, "rb");
@@ -81,6 +93,13 @@ static u64 scene_hash(const char *path)
     int c;
     while ((c = fgetc(f)) != EOF) h = (h ^ (u64)(unsigned char)c) * 0x100000001b3ull;
     fclose(f);
+    if (g_projection)
+    {
+        unsigned char tag[12];
+        memcpy(tag, &g_projection, 4);
+        memcpy(tag + 4, &g_ortho_width, 8);
+        for (int k = 0; k < 12; k += 1) h = (h ^ (u64)tag[k]) * 0x100000001b3ull;
+    }
     return h ? h : 1;
 }
 
@@ -235,7 +254,7 @@ static int load_checkpoint(const config_arguments *config, u32 width, u32 height
     if (m.pixel_scheme != (unsigned)config->pixel_scheme) return refuse("checkpoint was rendered with pixel scheme %u, the job uses %u", m.pixel_scheme, (unsigned)config->pixel_scheme);
     if (m.min_wl != config->min_wl || m.interval != config->wl_interval)
         return refuse("checkpoint is on the wavelength grid %g + k %g, the job on %g + k %g", m.min_wl, m.interval, config->min_wl, config->wl_interval);
-    if (m.scene != scene_hash(config->input_scene)) return refuse("checkpoint was rendered from another scene file than %s is now", config->input_scene);
+    if (m.scene != scene_hash(config->input_scene)) return refuse("checkpoint was rendered from another scene file than %s is now, or through another projection (DRT_PROJECTION, DRT_ORTHO_WIDTH)", config->input_scene);
     if (n == 0) return refuse("checkpoint holds no samples");
     const u64 num_pixels = (u64)width * height;
     generation_paths(config, (int)m.generation, paths);

@@ -118,7 +118,15 @@ typedef struct
      * file stays byte for byte what it is without it */
     uint32_t n_picks;
     uint32_t pick_xy[DRT_HOST_MAX_PICKS][2], pick_sample[DRT_HOST_MAX_PICKS];
+    /* DRT_PROJECTION: the scene through another projection than the configured camera's (a ray table bound before the first sample,
+     * drt_group_bind_rays): 0 the camera, DRT_HOST_PROJECTION_EQUIRECT, DRT_HOST_PROJECTION_ORTHO with ortho_width (DRT_ORTHO_WIDTH).
+     * Checkpoints, resuming and the adaptive forms work as with the camera; not combined with features, mattes or picks, which ask
+     * for the camera's rays */
+    uint32_t projection;
+    double   ortho_width;
 } drt_host_options;
+#define DRT_HOST_PROJECTION_EQUIRECT 1u
+#define DRT_HOST_PROJECTION_ORTHO 2u
 
 /* the `adaptive` line of a version-3 checkpoint manifest: what the film was rendered with so far */
 typedef struct { uint32_t min_spp, max_spp, step; double rel_error, floor; } drt_host_adaptive_line;
@@ -170,6 +178,16 @@ void drt_host_blackbody_spectrum(f64 min_wl, f64 wl_interval, u32 num_samples, f
 void drt_host_init_camera(drt_camera *camera, const f64 position[3], const f64 target[3], f64 roll, f64 fov,
                           f64 fdepth, f64 flength, f64 aperture, u32 width_px, u32 height_px);
 
+/* Ray tables for drt_bind_rays (include/drt_hip.h), one layer, [height][width][3] each, row 0 at the bottom as the film's rows are.
+ * Both return 0, or -1 (nothing written) for a null pointer, an empty image or a film_width that is not a finite number above 0.
+ * equirect: every origin is the camera's aperture_position; pixel (x, y) looks along longitude ((x + 0.5) / width - 0.5) * 2 pi (towards
+ * `right`) and latitude ((y + 0.5) / height - 0.5) * pi (towards `up`) about `forward`, as a unit vector: the centre of an image of odd
+ * width and height looks along `forward`.
+ * ortho: every direction is `forward` as it stands; the origins lie on the rectangle of film_width x film_width * height / width,
+ * spanned by `right` and `up`, whose centre is the aperture_position, at the pixels' centres. */
+int drt_host_rays_equirect(const drt_camera *camera, u32 width, u32 height, f64 *origins, f64 *dirs);
+int drt_host_rays_ortho(const drt_camera *camera, u32 width, u32 height, f64 film_width, f64 *origins, f64 *dirs);
+
 /* Name tables expanded from include/bdsf_list.h (same role as bdsf_name_list / dir_func_name_list). */
 extern const char *bdsf_name_list[];
 extern const u32   num_bdsfs_defined;
@@ -201,6 +219,10 @@ int drt_host_write_outputs_adaptive(const config_arguments *config, u32 width, u
                                     u64 seed, const drt_host_adaptive_line *adaptive);
 int drt_host_load_checkpoint_adaptive(const config_arguments *config, u32 width, u32 height, u32 S, u64 seed, f64 *dst_pixels,
                                       f64 *dst_avgs, f64 *dst_vars, u32 *largest_count, drt_host_adaptive_line *line);
+/* The projection of the job that writes or loads checkpoints from here on (drt_host_options.projection and ortho_width; 0: the camera).
+ * It enters the manifest's scene fingerprint, so a checkpoint rendered through the camera or another projection is not resumed under
+ * this one. render_image_ex sets it from its options. */
+void drt_host_checkpoint_projection(u32 projection, f64 ortho_width);
 const char *drt_host_checkpoint_error(void);
 
 /* .spd -> BMP post-process (spd_file_to_bmp, src/win32_main.c:115-121). cmf: [4][S] rows rw, x, y, z. */

@@ -137,6 +137,7 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
      * (opt->resume) reloads those files, takes the number of samples done from the filter sum, and continues --
      * bit-identical to an uninterrupted run, because sample k always uses the same per-path seeds.
      */
+    drt_host_checkpoint_projection(opt ? opt->projection : 0, opt ? opt->ortho_width : 0.0); /* a checkpoint belongs to its projection */
     drt_stats stats;
     memset(&stats, 0, sizeof(stats));
     u32 done = 0;
@@ -168,6 +169,26 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     drt_group *ctx = drt_group_create(scene, drt_host_camera_data(hs), &p, devices, n_devices);
     if (!ctx) rc = -1;
     if (!rc && !(opt && opt->quiet) && drt_group_size(ctx) > 1) printf("Rendering on %u devices\n", drt_group_size(ctx));
+    /* DRT_PROJECTION: the first rays from a table, bound while the film is still without samples (a resumed film is written after it) */
+    if (!rc && opt && opt->projection)
+    {
+        f64 *ray_o = (f64 *)malloc(num_pixels * 3 * sizeof(f64)), *ray_d = (f64 *)malloc(num_pixels * 3 * sizeof(f64));
+        if (!ray_o || !ray_d) rc = -3;
+        if (!rc)
+            rc = opt->projection == DRT_HOST_PROJECTION_EQUIRECT ? drt_host_rays_equirect(drt_host_camera_data(hs), width, height, ray_o, ray_d)
+                                                                 : drt_host_rays_ortho(drt_host_camera_data(hs), width, height, opt->ortho_width, ray_o, ray_d);
+        if (!rc)
+        {
+            drt_ray_table table;
+            memset(&table, 0, sizeof(table));
+            table.origins = ray_o;
+            table.dirs = ray_d;
+            table.n_layers = 1;
+            rc = drt_group_bind_rays(ctx, &table);
+        }
+        free(ray_d);
+        free(ray_o);
+    }
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc && opt && opt->adaptive && (opt->adaptive_checkpoint_rounds || opt->adaptive_resume))
     {
@@ -634,6 +655,34 @@ static int pick_options(const config_arguments *config, drt_host_options *opt)
     return -1;
 }
 
+/* DRT_PROJECTION=equirect | ortho (with DRT_ORTHO_WIDTH=<w>, the rectangle's width in scene units): parsed and checked here, before any
+ * device call, after the options it cannot be combined with. */
+static int projection_options(drt_host_options *opt)
+{
+    const char *e = getenv("DRT_PROJECTION"), *w = getenv("DRT_ORTHO_WIDTH");
+    opt->projection = 0;
+    if (!e)
+    {
+        if (w) { fprintf(stderr, "render_image: DRT_ORTHO_WIDTH is set but DRT_PROJECTION is not ortho\n"); return -1; }
+        return 0;
+    }
+    if (strcmp(e, "equirect") == 0) opt->projection = DRT_HOST_PROJECTION_EQUIRECT;
+    else if (strcmp(e, "ortho") == 0) opt->projection = DRT_HOST_PROJECTION_ORTHO;
+    else { fprintf(stderr, "render_image: DRT_PROJECTION=\"%s\": equirect or ortho\n", e); return -1; }
+    if (opt->projection == DRT_HOST_PROJECTION_ORTHO)
+    {
+        if (!w) { fprintf(stderr, "render_image: DRT_PROJECTION=ortho needs DRT_ORTHO_WIDTH\n"); return -1; }
+        if (env_double("DRT_ORTHO_WIDTH", &opt->ortho_width)) return -1;
+        if (!isfinite(opt->ortho_width) || !(opt->ortho_width > 0.0))
+        { fprintf(stderr, "render_image: DRT_ORTHO_WIDTH=%s: a finite number above 0\n", w); return -1; }
+    }
+    else if (w) { fprintf(stderr, "render_image: DRT_ORTHO_WIDTH is set but DRT_PROJECTION is not ortho\n"); return -1; }
+    if (opt->features) { fprintf(stderr, "render_image: DRT_PROJECTION cannot be combined with DRT_FEATURES, which asks for the camera's rays\n"); return -1; }
+    if (opt->mattes) { fprintf(stderr, "render_image: DRT_PROJECTION cannot be combined with DRT_MATTES, which asks for the camera's rays\n"); return -1; }
+    if (opt->n_picks) { fprintf(stderr, "render_image: DRT_PROJECTION cannot be combined with DRT_PICK, which asks for the camera's rays\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -663,5 +712,6 @@ void render_image(config_arguments *config)
     if (features_options(config, &opt) != 0) exit(-1);
     if (mattes_options(&opt) != 0) exit(-1);
     if (pick_options(config, &opt) != 0) exit(-1);
+    if (projection_options(&opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

@@ -522,6 +522,55 @@ void drt_host_init_camera(drt_camera *camera, const f64 position[3], const f64 t
 }
 
 /* ------------------------------------------------------------------------------------------ */
+/* Ray tables for drt_bind_rays: projections the reference's camera_ray does not have           */
+
+int drt_host_rays_equirect(const drt_camera *camera, u32 width, u32 height, f64 *origins, f64 *dirs)
+{
+    if (!camera || !origins || !dirs || width == 0 || height == 0) return -1;
+    for (u32 y = 0; y < height; y += 1)
+    {
+        const f64 lat = (((f64)y + 0.5) / (f64)height - 0.5) * (f64)PI;
+        const f64 sl = sin(lat), cl = cos(lat);
+        for (u32 x = 0; x < width; x += 1)
+        {
+            const f64 lon = (((f64)x + 0.5) / (f64)width - 0.5) * (2.0 * (f64)PI);
+            const f64 a = cl * cos(lon), b = cl * sin(lon);
+            f64 d[3];
+            for (int k = 0; k < 3; k += 1) d[k] = (a * camera->forward[k] + b * camera->right[k]) + sl * camera->up[k];
+            const f64 len = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+            const u64 r = ((u64)y * width + x) * 3;
+            for (int k = 0; k < 3; k += 1)
+            {
+                origins[r + k] = camera->aperture_position[k];
+                dirs[r + k] = d[k] / len;
+            }
+        }
+    }
+    return 0;
+}
+
+int drt_host_rays_ortho(const drt_camera *camera, u32 width, u32 height, f64 film_width, f64 *origins, f64 *dirs)
+{
+    if (!camera || !origins || !dirs || width == 0 || height == 0 || !isfinite(film_width) || !(film_width > 0.0)) return -1;
+    const f64 film_height = film_width * (f64)height / (f64)width;
+    for (u32 y = 0; y < height; y += 1)
+    {
+        const f64 v = (((f64)y + 0.5) / (f64)height - 0.5) * film_height;
+        for (u32 x = 0; x < width; x += 1)
+        {
+            const f64 u = (((f64)x + 0.5) / (f64)width - 0.5) * film_width;
+            const u64 r = ((u64)y * width + x) * 3;
+            for (int k = 0; k < 3; k += 1)
+            {
+                origins[r + k] = (camera->aperture_position[k] + u * camera->right[k]) + v * camera->up[k];
+                dirs[r + k] = camera->forward[k];
+            }
+        }
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------------------------------ */
 /* Scene build                                                                                  */
 
 struct drt_host_scene

@@ -21,7 +21,7 @@ MODE_SPECTRAL, MODE_XYZ = 0, 1
 FLAG_RECORD_HITS = 1
 BATCH_RESIDENT = 0xFFFFFFFF  # make_params(batch_spp=...): launches sized for a context kept across frames
 FLAG_FILM_ZERO = 2
-PATH_BVH, PATH_TRACE_TAIL = 1, 2  # Stats.path_flags
+PATH_BVH, PATH_TRACE_TAIL, PATH_RAYS = 1, 2, 4  # Stats.path_flags
 
 # names and order of include/bdsf_list.h
 BDSF_NAMES = ["bp_diffuse_bdsf", "bp_glossy_bdsf", "mirror_bdsf", "fs_conductor_bdsf",
@@ -159,6 +159,78 @@ RAY_HIT_DTYPE = np.dtype([("position", "<f8", 3), ("normal", "<f8", 3), ("out", 
 assert RAY_HIT_DTYPE.itemsize == C.sizeof(RayHit) == 104
 
 
+class RayTable(C.Structure):
+    """drt_ray_table (include/drt_hip.h): the first rays of a ray film, [n_layers][height][width] over the whole image. 32 bytes."""
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p), ("weights", C.c_void_p), ("n_layers", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(RayTable) == 32
+
+
+def _ray_table(origins, dirs, weights, width, height, device):
+    """(RayTable, what must stay referenced) from numpy arrays [L][h][w][3] / [h][w][3] (host mode) or float64 torch tensors of those
+    shapes on cuda:<device> (device mode); weights [L][h][w] / [h][w] or None."""
+    t = RayTable()
+    if _is_tensor(origins) or _is_tensor(dirs) or _is_tensor(weights):
+        torch = sys.modules["torch"]
+        arrs = [origins, dirs] + ([weights] if weights is not None else [])
+        for a, name in zip(arrs, ("origins", "dirs", "weights")):
+            if not _is_tensor(a) or a.dtype != torch.float64 or not a.is_contiguous():
+                raise ValueError("%s: a contiguous float64 tensor (device mode takes tensors only)" % name)
+            if a.device.type != "cuda" or a.device.index != device:
+                raise ValueError("%s: a tensor on the context's device (cuda:%d)" % (name, device))
+        shape = lambda a: tuple(a.shape)
+        ptr = lambda a: a.data_ptr()
+        t.flags = RAYS_DEVICE
+    else:
+        arrs = [np.ascontiguousarray(origins, dtype=np.float64), np.ascontiguousarray(dirs, dtype=np.float64)]
+        if weights is not None:
+            arrs.append(np.ascontiguousarray(weights, dtype=np.float64))
+        shape = lambda a: a.shape
+        ptr = lambda a: a.ctypes.data
+        t.flags = 0
+    o = shape(arrs[0])
+    if len(o) == 3:
+        o = (1,) + o
+    if len(o) != 4 or o[0] < 1 or o[1:] != (height, width, 3):
+        raise ValueError("origins: [n_layers][%d][%d][3] or [%d][%d][3]" % (height, width, height, width))
+    d = shape(arrs[1])
+    if (d if len(d) == 4 else (1,) + d) != o:
+        raise ValueError("dirs: the shape of origins")
+    if weights is not None:
+        w = shape(arrs[2])
+        if (w if len(w) == 3 else (1,) + w) != o[:3]:
+            raise ValueError("weights: [n_layers][%d][%d] or [%d][%d]" % (height, width, height, width))
+    t.origins, t.dirs = ptr(arrs[0]), ptr(arrs[1])
+    t.weights = ptr(arrs[2]) if weights is not None else None
+    t.n_layers = o[0]
+    return t, arrs
+
+
+def _camera_of(bundle_or_camera):
+    return bundle_or_camera.camera if hasattr(bundle_or_camera, "camera") else bundle_or_camera
+
+
+def equirect_rays(camera, width, height):
+    """drt_host_rays_equirect (host/drt_host.h): (origins, dirs), each [height][width][3], of an equirectangular capture about the
+    camera's aperture position. `camera`: a Camera or a SceneBundle."""
+    cam = _camera_of(camera)
+    o, d = np.empty((height, width, 3)), np.empty((height, width, 3))
+    if host_lib().drt_host_rays_equirect(C.byref(cam), width, height, _ptr(o, C.c_double), _ptr(d, C.c_double)) != 0:
+        raise ValueError("equirect_rays: an image of at least one pixel")
+    return o, d
+
+
+def ortho_rays(camera, width, height, film_width):
+    """drt_host_rays_ortho (host/drt_host.h): (origins, dirs), each [height][width][3]: parallel rays along the camera's forward from a
+    rectangle film_width wide through its aperture position."""
+    cam = _camera_of(camera)
+    o, d = np.empty((height, width, 3)), np.empty((height, width, 3))
+    if host_lib().drt_host_rays_ortho(C.byref(cam), width, height, float(film_width), _ptr(o, C.c_double), _ptr(d, C.c_double)) != 0:
+        raise ValueError("ortho_rays: an image of at least one pixel and a finite film_width above 0")
+    return o, d
+
+
 def _is_tensor(a):
     return "torch" in sys.modules and isinstance(a, sys.modules["torch"].Tensor)
 
@@ -244,6 +316,9 @@ def host_lib():
         L.drt_host_blackbody_spectrum.argtypes = [C.c_double, C.c_double, C.c_uint32, C.c_double, C.POINTER(C.c_double)]
         L.drt_host_init_camera.argtypes = [C.POINTER(Camera), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
                                            C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32]
+        f64p = C.POINTER(C.c_double)
+        L.drt_host_rays_equirect.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, f64p, f64p]
+        L.drt_host_rays_ortho.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_double, f64p, f64p]
         _host = L
     return _host
 
@@ -468,6 +543,9 @@ def hip_lib():
             L.drt_read_matte_bgra.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]
             L.drt_group_render_mattes.argtypes = [C.c_void_p, C.POINTER(Mattes), i32p, u32p, u32p]
         L.drt_batch_spp.restype = C.c_uint32
+        if hasattr(L, "drt_bind_rays"):
+            L.drt_bind_rays.argtypes = [C.c_void_p, C.POINTER(RayTable)]
+            L.drt_group_bind_rays.argtypes = [C.c_void_p, C.POINTER(RayTable)]
         L.drt_batch_spp.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
@@ -497,7 +575,7 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_render_features", "drt_read_features", "drt_read_feature_bgra", "drt_group_render_features",
                "drt_render_mattes", "drt_read_mattes", "drt_read_matte", "drt_read_matte_bgra", "drt_group_render_mattes",
                "drt_cast_rays", "drt_test_visibility", "drt_cast_pixels", "drt_group_cast_rays", "drt_group_test_visibility",
-               "drt_group_cast_pixels"]
+               "drt_group_cast_pixels", "drt_bind_rays", "drt_group_bind_rays"]
 
 
 def _check(rc, what):
@@ -748,6 +826,19 @@ class Renderer:
         _check(self.L.drt_cast_pixels(self.ctx, xy.ctypes.data, samples.ctypes.data, n, o.ctypes.data, d.ctypes.data, hits.ctypes.data, 0), "drt_cast_pixels")
         return o, d, hits
 
+    def bind_rays(self, origins, dirs=None, weights=None):
+        """A ray film (drt_bind_rays): from now on the path of image pixel (x, y), sample s starts with origins[s % L][y][x],
+        dirs[s % L][y][x] and is weighted by weights[s % L][y][x] (None: 1.0). numpy arrays [L][h][w][3] or [h][w][3] over the WHOLE
+        image: host mode, the tile's rows are copied. float64 torch tensors on the context's device: device mode, used in place and
+        kept referenced until the next bind_rays. bind_rays(None) goes back to the camera. The film must hold no samples."""
+        if origins is None:
+            _check(self.L.drt_bind_rays(self.ctx, None), "drt_bind_rays")
+            self._ray_arrays = None
+            return
+        t, keep = _ray_table(origins, dirs, weights, int(self.params.width), int(self.params.height), int(self.params.device))
+        _check(self.L.drt_bind_rays(self.ctx, C.byref(t)), "drt_bind_rays")
+        self._ray_arrays = keep if t.flags & RAYS_DEVICE else None
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -872,6 +963,16 @@ class Group:
         _check(self.L.drt_group_cast_pixels(self.g, xy.ctypes.data, samples.ctypes.data, n, o.ctypes.data, d.ctypes.data, hits.ctypes.data),
                "drt_group_cast_pixels")
         return o, d, hits
+
+    def bind_rays(self, origins, dirs=None, weights=None):
+        """drt_group_bind_rays: as Renderer.bind_rays with numpy arrays (host mode only); every device copies its own rows."""
+        if origins is None:
+            _check(self.L.drt_group_bind_rays(self.g, None), "drt_group_bind_rays")
+            return
+        if _is_tensor(origins) or _is_tensor(dirs) or _is_tensor(weights):
+            raise ValueError("Group.bind_rays: numpy arrays (a group takes host pointers only)")
+        t, _ = _ray_table(origins, dirs, weights, int(self.params.width), int(self.params.height), 0)
+        _check(self.L.drt_group_bind_rays(self.g, C.byref(t)), "drt_group_bind_rays")
 
     def close(self):
         if self.g:

@@ -207,7 +207,8 @@ typedef struct drt_stats
 enum
 {
     DRT_PATH_BVH        = 1u, /* the scene is behind the bounding-volume hierarchy: drt_primary_kernel + drt_bounce_kernel trace it */
-    DRT_PATH_TRACE_TAIL = 2u  /* the trace kernel carries every path's tail wavelengths (all-plastic scenes); the shade kernel's tail pass only updates the film */
+    DRT_PATH_TRACE_TAIL = 2u, /* the trace kernel carries every path's tail wavelengths (all-plastic scenes); the shade kernel's tail pass only updates the film */
+    DRT_PATH_RAYS       = 4u  /* a ray table is bound (drt_bind_rays): the ray-mode entry points of those kernels run; set while bound, and only then */
 };
 
 typedef struct drt_context drt_context;
@@ -514,6 +515,44 @@ int drt_cast_pixels(drt_context *ctx, const uint32_t *xy, const uint32_t *sample
 int drt_group_cast_rays(drt_group *g, const double *origins, const double *dirs, uint64_t n, drt_ray_hit *hits);
 int drt_group_test_visibility(drt_group *g, const double *p0, const double *p1, uint64_t n, uint8_t *visible);
 int drt_group_cast_pixels(drt_group *g, const uint32_t *xy, const uint32_t *samples, uint64_t n, double *origins, double *dirs, drt_ray_hit *hits);
+
+/*
+ * Ray films: the path's FIRST ray as an input. A context bound to a ray table renders, per image pixel and sample, the spectral radiance
+ * that arrives along a ray the caller supplies, where sample_scene makes one from the pinhole / thin-lens camera
+ * (src/daily_ray_trace.c:577-607, camera_ray :550-607) and weighs it by the vignette (:614). Everything below the first ray -- cast_ray,
+ * the RNG keys, the film update, the shade kernel -- is unchanged; DESIGN.md section 5f.
+ *
+ * The table has n_layers >= 1 layers over the WHOLE width x height image (not only the context's tile):
+ *     origins[n_layers][height][width][3], dirs[n_layers][height][width][3], weights[n_layers][height][width] (NULL: every weight 1.0).
+ * For image pixel (x, y) and absolute sample index s (first_sample, and in adaptive rounds the pixel's own count, included):
+ *     l = s % n_layers,  r = (l * height + y) * width + x   (64-bit);
+ *     the RNG is seeded from the path key seed + ((s * height + y) * width + x) as always, and NO draw is taken before cast_ray;
+ *     ray_origin = origins[r], ray_direction = dirs[r] as given (no normalisation, as drt_cast_rays); cast_ray runs unchanged;
+ *     the contribution is multiplied by weights[r] * 1.0 where :614-615 multiply by vignette_factor * pixel_filter_value.
+ * A NaN direction misses: the pixel gets what an escaping ray leaves. A NaN weight makes its own pixel NaN and no other.
+ *
+ * flags = 0 (host mode): the arrays are host memory; the context copies the rows of its own tile (x0, y0, tile_w, tile_h, row_stride) of
+ * every layer to its device before the call returns, and the caller's arrays are free afterwards. DRT_RAYS_DEVICE: the arrays are
+ * whole-image arrays on the context's device, used in place -- no copy, no wait -- and must outlive the binding.
+ * t == NULL unbinds: the context renders through its camera again.
+ *
+ * Binding and unbinding need a film without samples (a fresh context, or after drt_reset_film). Otherwise, and for null origins or dirs,
+ * n_layers == 0, flags other than DRT_RAYS_DEVICE, or device mode in the group form, the call is refused with a message in
+ * drt_last_error(): nothing is changed, no film bit included. While a table is bound drt_render, the adaptive calls, the film reads and
+ * writes, the XYZ mode, the hit log, the denoiser, drt_cast_rays and drt_test_visibility work as before; drt_render_features,
+ * drt_render_mattes, drt_cast_pixels and their group forms are refused, since they ask for the camera's rays. drt_stats.path_flags
+ * carries DRT_PATH_RAYS while a table is bound. As for the ray queries, in a DRT_PATH_BVH context the box tests' error budget covers origins
+ * within the extent the hierarchy was built for (the scene and the context's camera).
+ */
+typedef struct drt_ray_table
+{
+    const double *origins, *dirs, *weights; /* weights may be NULL */
+    uint32_t      n_layers, flags;          /* flags: 0 or DRT_RAYS_DEVICE */
+} drt_ray_table;                            /* 32 bytes */
+int drt_bind_rays(drt_context *ctx, const drt_ray_table *t);   /* t == NULL: back to the camera */
+/* Host pointers only: every device copies its own rows. All contexts are checked, and every device's copy is made, before any context
+ * is changed: a call that fails on one device leaves the whole group as it was. */
+int drt_group_bind_rays(drt_group *g, const drt_ray_table *t);
 
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
