@@ -10,6 +10,7 @@
 #include "drt_feature_kernels.h"
 #include "drt_matte_kernels.h"
 #include "drt_ray_kernels.h"
+#include "drt_update_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -160,6 +161,27 @@ struct drt_context
     bool        rays_bound = false;
     DevRayTable rt{};
     double     *d_rt_origins = nullptr, *d_rt_dirs = nullptr, *d_rt_weights = nullptr;
+    /* scene updates (drt_update_surfaces, drt_set_camera; drt_update_kernels.h): the caller's raw surfaces on both sides, the host's
+     * tree, and what the three kernels read. Everything on the device is made at the first update. */
+    std::vector<drt_surface> h_surfaces;   /* as drt_create got them, with every host-mode update written in */
+    bool      h_stale = false;             /* a device-mode update has gone into d_raw only: read it back before the host decides anything */
+    std::vector<BvhNode>  h_nodes;         /* hierarchy contexts: the tree's links (its boxes are the device's business after an update) */
+    std::vector<uint32_t> h_order;         /* ... and the surface in every leaf slot */
+    double    cam_reach = 0.0, extent = 0.0; /* the camera's share of the extent; the extent in use (hierarchy contexts) */
+    bool      extent_known = true;
+    bool      upd_ready = false;
+    drt_surface *d_raw = nullptr, *h_stage = nullptr; /* the device copy; the pinned buffer host mode goes through */
+    int32_t  *d_light_slot = nullptr;
+    double   *d_boxes = nullptr;
+    uint32_t *d_leaf_parent = nullptr;
+    uint2    *d_levels = nullptr;
+    std::vector<uint32_t> level_first;     /* level l, deepest first, is d_levels[level_first[l] .. level_first[l + 1]) */
+    unsigned long long *d_upd_status = nullptr;
+    hipEvent_t upd_ev[3] = {nullptr, nullptr, nullptr}; /* the last update's kernels: start, end; the pinned buffer is free again */
+    bool      upd_timed = false, stage_busy = false;
+    bool      upd_check = false, upd_violation = false; /* device mode: the status word is to be read at the next synchronisation; what it said */
+    uint32_t  updates = 0, refits = 0;
+    double    upd_ms = 0.0;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -679,6 +701,9 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
         }
         if ((rc = upload(ctx, bb.nodes, &d.bvh_nodes))) return rc;
         if ((rc = upload(ctx, leaf, &d.bvh_leaf))) return rc;
+        ctx->h_nodes = bb.nodes;
+        ctx->h_order = bb.order;
+        ctx->extent = bb.extent;
     }
     if (!ctx->scene_in_lds) ctx->trace_lds = 0;
     ctx->spds_in_lds = (size_t)d.n_spd * S * 8 <= 64 * 1024;
@@ -847,6 +872,27 @@ static uint64_t blocks_worst_case(const drt_context *ctx, uint64_t n_paths)
     return (uint64_t)((double)n_paths * ctx->worst_blocks_per_path * (1.0 + 64.0 / POOL_CHUNK)) + trace_waves(ctx, n_paths) * (POOL_CHUNK + 2 * 64) + 1;
 }
 
+/* ray origins that are not on a surface are on the camera: its aperture and its film */
+static double camera_reach(const drt_camera *camera)
+{
+    double reach = 0.0;
+    for (int k = 0; k < 3; k += 1)
+    {
+        const double a = camera->aperture_position[k], f = camera->film_bottom_left[k];
+        reach = std::max(reach, std::fabs(a) + 2.0 * std::fabs(f - a) + std::fabs(camera->aperture_radius));
+    }
+    return reach;
+}
+
+static void set_device_camera(drt_context *ctx, const drt_camera *camera)
+{
+    DevCamera &c = ctx->dcam;
+    c.forward = hv(camera->forward); c.right = hv(camera->right); c.up = hv(camera->up);
+    c.aperture_position = hv(camera->aperture_position); c.film_bottom_left = hv(camera->film_bottom_left);
+    c.aperture_radius = camera->aperture_radius; c.focal_depth = camera->focal_depth;
+    c.pixel_width = camera->pixel_width; c.pixel_height = camera->pixel_height;
+}
+
 static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camera *camera, const drt_params *params)
 {
     if (!scene || !camera || !params) return fail(-1, "null argument");
@@ -861,25 +907,17 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
-    /* ray origins that are not on a surface are on the camera: its aperture and its film */
-    double reach = 0.0;
-    for (int k = 0; k < 3; k += 1)
-    {
-        const double a = camera->aperture_position[k], f = camera->film_bottom_left[k];
-        reach = std::max(reach, std::fabs(a) + 2.0 * std::fabs(f - a) + std::fabs(camera->aperture_radius));
-    }
+    const double reach = camera_reach(camera);
     int rc = build_device_scene(ctx, scene, reach);
     if (rc) return rc;
+    ctx->cam_reach = reach;
+    ctx->h_surfaces.assign(scene->surfaces, scene->surfaces + scene->num_surfaces);
     ctx->ft_mats.assign(scene->materials, scene->materials + scene->num_materials);
     ctx->ft_n_spd = scene->num_spds;
     ctx->ft_S = scene->num_wavelengths;
     ctx->ft_spds.assign(scene->spds, scene->spds + (size_t)scene->num_spds * scene->num_wavelengths);
 
-    DevCamera &c = ctx->dcam;
-    c.forward = hv(camera->forward); c.right = hv(camera->right); c.up = hv(camera->up);
-    c.aperture_position = hv(camera->aperture_position); c.film_bottom_left = hv(camera->film_bottom_left);
-    c.aperture_radius = camera->aperture_radius; c.focal_depth = camera->focal_depth;
-    c.pixel_width = camera->pixel_width; c.pixel_height = camera->pixel_height;
+    set_device_camera(ctx, camera);
 
     const uint32_t S = scene->num_wavelengths;
     ctx->n_pix = (uint64_t)params->tile_w * params->tile_h;
@@ -1166,6 +1204,15 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_rt_origins);
     (void)hipFree(ctx->d_rt_dirs);
     (void)hipFree(ctx->d_rt_weights);
+    (void)hipFree(ctx->d_raw);
+    (void)hipHostFree(ctx->h_stage);
+    (void)hipFree(ctx->d_light_slot);
+    (void)hipFree(ctx->d_boxes);
+    (void)hipFree(ctx->d_leaf_parent);
+    (void)hipFree(ctx->d_levels);
+    (void)hipFree(ctx->d_upd_status);
+    for (hipEvent_t e : ctx->upd_ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->mt_ev)
         if (e) (void)hipEventDestroy(e);
     (void)hipHostFree(ctx->h_active);
@@ -1570,9 +1617,30 @@ static int render_impl(drt_context *ctx, uint32_t first_sample, uint32_t num_sam
     return 0;
 }
 
+static int synchronize_impl(drt_context *ctx);
+
+/* A device-mode update whose surfaces took the extent to 2^27 or beyond (the one condition the host cannot check before the call
+ * returns) fails every synchronising call from then on, until a later update or drt_set_camera brings the extent back. */
 extern "C" int drt_synchronize(drt_context *ctx)
 {
     if (!ctx) return fail(-1, "null context");
+    int rc = synchronize_impl(ctx);
+    if (rc) return rc;
+    if (ctx->upd_check)
+    {
+        unsigned long long word = 0;
+        HIP_TRY(hipMemcpy(&word, ctx->d_upd_status + 1, sizeof(word), hipMemcpyDeviceToHost));
+        ctx->upd_violation = word != 0ull;
+        ctx->upd_check = false;
+    }
+    if (ctx->upd_violation)
+        return fail(-2, "drt_update_surfaces: the updated surfaces' coordinates reach 2^27 or beyond, and the hierarchy's f32 box test holds up to 2^27: "
+                        "what was rendered since is not held to the rule; update the surfaces again");
+    return 0;
+}
+
+static int synchronize_impl(drt_context *ctx)
+{
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     int rc = collect_timings(ctx);
@@ -1596,7 +1664,7 @@ extern "C" int drt_reset_film(drt_context *ctx)
 {
     if (!ctx) return fail(-1, "null context");
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = drt_synchronize(ctx);
+    int rc = synchronize_impl(ctx); /* (not drt_synchronize: a film is reset before the update that mends a refused extent) */
     if (rc) return rc;
     const size_t S = ctx->dsc.S;
     HIP_TRY(hipMemsetAsync(ctx->d_pixels, 0, pixels_bytes(ctx), ctx->stream));
@@ -2310,6 +2378,18 @@ extern "C" int drt_group_synchronize(drt_group *g)
         if (c)
         {
             int rc = drt_synchronize(c);
+            if (rc) return rc;
+        }
+    return 0;
+}
+
+extern "C" int drt_group_reset_film(drt_group *g)
+{
+    if (!g) return fail(-1, "null group");
+    for (drt_context *c : g->ctx)
+        if (c)
+        {
+            int rc = drt_reset_film(c);
             if (rc) return rc;
         }
     return 0;
@@ -3619,6 +3699,412 @@ extern "C" int drt_group_bind_rays(drt_group *g, const drt_ray_table *t)
     }
     for (size_t k = 0; k < n; k += 1)
         if (g->ctx[k]) bind_rays_commit(g->ctx[k], pending[k]);
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Scene updates: the camera and the surfaces of a live context (include/drt_hip.h)   */
+
+#define DRT_SURFACES_FLAGS (DRT_SURFACES_DEVICE | DRT_SURFACES_REBUILD)
+
+/* the largest |coordinate| of the surfaces' boxes, as BvhBuilder::build takes it */
+static double surfaces_extent(const drt_surface *s, size_t n)
+{
+    double extent = 0.0;
+    for (size_t i = 0; i < n; i += 1)
+    {
+        if (s[i].type != DRT_GEO_SPHERE && s[i].type != DRT_GEO_PLANE) continue;
+        double lo[3], hi[3];
+        prim_bounds(s[i], lo, hi);
+        for (int k = 0; k < 3; k += 1)
+        {
+            if (std::fabs(lo[k]) < 1e299) extent = std::max(extent, std::fabs(lo[k]));
+            if (std::fabs(hi[k]) < 1e299) extent = std::max(extent, std::fabs(hi[k]));
+        }
+    }
+    return extent;
+}
+
+/* what the leaf and refit kernels need to know of a tree: where every leaf slot hangs, and the inner nodes level by level */
+struct TreeMaps
+{
+    std::vector<uint32_t> leaf_parent;
+    std::vector<uint2>    entries;
+    std::vector<uint32_t> level_first;
+};
+
+static void tree_maps(const std::vector<BvhNode> &nodes, size_t n_leaf, TreeMaps *m)
+{
+    m->leaf_parent.assign(std::max<size_t>(n_leaf, 1), 0u);
+    std::vector<std::vector<uint2>> level; /* level[d]: the inner nodes d levels below the root */
+    std::vector<std::pair<uint32_t, uint32_t>> todo(1, {0u, 0u});
+    while (!todo.empty())
+    {
+        const uint32_t x = todo.back().first, depth = todo.back().second;
+        todo.pop_back();
+        for (uint32_t c = 0; c < 2; c += 1)
+        {
+            const BvhNode &nd = nodes[x];
+            if (nd.count[c] > 0) m->leaf_parent[(size_t)(-2 - nd.child[c]) >> 3] = x * 2u + c;
+            else if (nd.count[c] == 0)
+            {
+                if (level.size() < depth + 2) level.resize(depth + 2);
+                uint2 e;
+                e.x = (uint32_t)nd.child[c];
+                e.y = x * 2u + c;
+                level[depth + 1].push_back(e);
+                todo.push_back({(uint32_t)nd.child[c], depth + 1});
+            }
+        }
+    }
+    m->entries.clear();
+    m->level_first.assign(1, 0u);
+    for (size_t d = level.size(); d-- > 1;)
+    {
+        if (level[d].empty()) continue;
+        m->entries.insert(m->entries.end(), level[d].begin(), level[d].end());
+        m->level_first.push_back((uint32_t)m->entries.size());
+    }
+}
+
+/* the maps of ctx->h_nodes to the device (the allocations are sized for any one-surface-per-leaf tree over the same surfaces) */
+static int update_upload_maps(drt_context *ctx)
+{
+    TreeMaps m;
+    tree_maps(ctx->h_nodes, ctx->h_order.size(), &m);
+    const size_t n_leaf = std::max<size_t>(ctx->h_order.size(), 1);
+    if (!ctx->d_leaf_parent) HIP_TRY(hipMalloc((void **)&ctx->d_leaf_parent, n_leaf * sizeof(uint32_t)));
+    if (!ctx->d_levels) HIP_TRY(hipMalloc((void **)&ctx->d_levels, std::max<size_t>(ctx->h_nodes.size(), 1) * sizeof(uint2)));
+    HIP_TRY(hipMemcpy(ctx->d_leaf_parent, m.leaf_parent.data(), n_leaf * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (!m.entries.empty()) HIP_TRY(hipMemcpy(ctx->d_levels, m.entries.data(), m.entries.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    ctx->level_first = m.level_first;
+    return 0;
+}
+
+/* everything an update needs on the device, made at the first one. Changes nothing a render reads. */
+static int update_prepare(drt_context *ctx)
+{
+    if (ctx->upd_ready) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n = ctx->h_surfaces.size(), bytes = std::max<size_t>(n, 1) * sizeof(drt_surface);
+    if (!ctx->d_raw)
+    {
+        HIP_TRY(hipMalloc((void **)&ctx->d_raw, bytes));
+        if (n) HIP_TRY(hipMemcpy(ctx->d_raw, ctx->h_surfaces.data(), n * sizeof(drt_surface), hipMemcpyHostToDevice));
+    }
+    if (!ctx->h_stage) HIP_TRY(hipHostMalloc((void **)&ctx->h_stage, bytes, hipHostMallocDefault));
+    if (!ctx->d_light_slot)
+    {
+        /* the light list is the emissive surfaces in surface order (build_device_scene); types and materials do not change */
+        std::vector<int32_t> slot(std::max<size_t>(n, 1), -1);
+        int32_t l = 0;
+        for (size_t i = 0; i < n; i += 1)
+            if (ctx->ft_mats[ctx->h_surfaces[i].material].is_emissive) slot[i] = l++;
+        HIP_TRY(hipMalloc((void **)&ctx->d_light_slot, slot.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(ctx->d_light_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    if (!ctx->d_upd_status) HIP_TRY(hipMalloc((void **)&ctx->d_upd_status, UPD_STATUS_WORDS * sizeof(unsigned long long)));
+    for (hipEvent_t &e : ctx->upd_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    if (ctx->use_bvh)
+    {
+        if (!ctx->d_boxes) HIP_TRY(hipMalloc((void **)&ctx->d_boxes, std::max<size_t>(n, 1) * 6 * sizeof(double)));
+        int rc = update_upload_maps(ctx);
+        if (rc) return rc;
+    }
+    ctx->upd_ready = true;
+    return 0;
+}
+
+/* the three kernels, on the context's stream: every table derived again from ALL raw surfaces and the camera's reach */
+static int update_enqueue(drt_context *ctx)
+{
+    HIP_TRY(hipEventRecord(ctx->upd_ev[0], ctx->stream));
+    const uint32_t n = ctx->dsc.n_surf;
+    if (n > 0)
+    {
+        HIP_TRY(hipMemsetAsync(ctx->d_upd_status, 0, UPD_STATUS_WORDS * sizeof(unsigned long long), ctx->stream));
+        UpdateTables t;
+        t.raw = (const double *)ctx->d_raw;
+        t.surf = const_cast<double *>(ctx->dsc.surf);
+        t.lights = const_cast<double *>(ctx->dsc.lights);
+        t.light_slot = ctx->d_light_slot;
+        t.boxes = ctx->use_bvh ? ctx->d_boxes : nullptr;
+        t.status = ctx->d_upd_status;
+        hipLaunchKernelGGL(drt_surface_derive_kernel, dim3((n + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, ctx->stream, ctx->dsc, t);
+        HIP_TRY(hipGetLastError());
+        const uint32_t n_leaf = (uint32_t)ctx->h_order.size();
+        if (ctx->use_bvh && n_leaf > 0)
+        {
+            LeafTables lt;
+            lt.raw = t.raw;
+            lt.boxes = ctx->d_boxes;
+            lt.leaf_parent = ctx->d_leaf_parent;
+            lt.leaf = const_cast<BvhLeafPrim *>(ctx->dsc.bvh_leaf);
+            lt.nodes = const_cast<BvhNode *>(ctx->dsc.bvh_nodes);
+            lt.status = ctx->d_upd_status;
+            hipLaunchKernelGGL(drt_bvh_leaf_kernel, dim3((n_leaf + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, ctx->stream, lt, n_leaf, ctx->cam_reach);
+            HIP_TRY(hipGetLastError());
+            for (size_t l = 0; l + 1 < ctx->level_first.size(); l += 1) /* deepest level first; a kernel boundary between two levels */
+            {
+                const uint32_t first = ctx->level_first[l], cnt = ctx->level_first[l + 1] - first;
+                hipLaunchKernelGGL(drt_bvh_refit_kernel, dim3((cnt + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, ctx->stream, lt.nodes, ctx->d_levels + first, cnt);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+    }
+    HIP_TRY(hipEventRecord(ctx->upd_ev[1], ctx->stream));
+    ctx->upd_timed = true;
+    ctx->updates += 1;
+    if (ctx->use_bvh) ctx->refits += 1;
+    /* what describes the old scene is stale */
+    ctx->ft_valid = ctx->mt_valid = false;
+    return 0;
+}
+
+static int update_film_check(const drt_context *ctx, const char *name)
+{
+    if (ctx->film_used || ctx->adaptive_done)
+        return fail(-7, "%s: the film holds samples, and one film would mix two scenes: drt_reset_film first", name);
+    return 0;
+}
+
+/* a host-mode update that has passed every check, and (DRT_SURFACES_REBUILD) the tree it will install */
+struct PendingUpdate
+{
+    BvhBuilder bb;
+    bool       rebuild = false;
+    double     extent = 0.0;
+};
+
+/* the host copy again after device-mode updates (type and material words are the host's own: device mode does not copy them) */
+static int update_read_back(drt_context *ctx)
+{
+    if (!ctx->h_stale) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!ctx->h_surfaces.empty())
+        HIP_TRY(hipMemcpy(ctx->h_surfaces.data(), ctx->d_raw, ctx->h_surfaces.size() * sizeof(drt_surface), hipMemcpyDeviceToHost));
+    ctx->h_stale = false;
+    return 0;
+}
+
+/* everything a host-mode call can be refused for; changes nothing */
+static int update_check(drt_context *ctx, const drt_surface *surfaces, uint32_t first, uint32_t count, uint32_t flags, const char *name, bool group,
+                        PendingUpdate *pu)
+{
+    const size_t n = ctx->h_surfaces.size();
+    if (flags & ~DRT_SURFACES_FLAGS) return fail(-1, "%s: unknown flags 0x%x", name, flags);
+    if ((flags & DRT_SURFACES_DEVICE) && (flags & DRT_SURFACES_REBUILD))
+        return fail(-1, "%s: DRT_SURFACES_REBUILD builds the hierarchy on the host and needs host surfaces", name);
+    if (group && (flags & DRT_SURFACES_DEVICE)) return fail(-1, "%s: host pointers only (DRT_SURFACES_DEVICE is per context: drt_update_surfaces)", name);
+    if ((uint64_t)first + count > n) return fail(-1, "%s: surfaces [%u, %llu) of %zu", name, first, (unsigned long long)first + count, n);
+    if (count > 0 && !surfaces) return fail(-1, "%s: surfaces is null", name);
+    if (count == 0) return 0; /* a no-op, whatever the film holds */
+    int rc = update_film_check(ctx, name);
+    if (rc) return rc;
+    if (flags & DRT_SURFACES_DEVICE) return 0;
+    if ((rc = update_read_back(ctx))) return rc;
+    for (uint32_t i = 0; i < count; i += 1)
+    {
+        const drt_surface &was = ctx->h_surfaces[first + i];
+        if (surfaces[i].type != was.type) return fail(-2, "%s: surface %u: type %u, was %u (an update keeps every surface's type)", name, first + i, surfaces[i].type, was.type);
+        if (surfaces[i].material != was.material)
+            return fail(-2, "%s: surface %u: material %u, was %u (an update keeps every surface's material)", name, first + i, surfaces[i].material, was.material);
+    }
+    if (!ctx->use_bvh) return 0;
+    std::vector<drt_surface> all = ctx->h_surfaces;
+    std::copy(surfaces, surfaces + count, all.begin() + first);
+    pu->rebuild = (flags & DRT_SURFACES_REBUILD) != 0u;
+    if (pu->rebuild)
+    {
+        drt_scene sc{};
+        sc.num_surfaces = (uint32_t)n;
+        sc.surfaces = all.data();
+        pu->bb.build(&sc, ctx->cam_reach);
+        pu->extent = pu->bb.extent;
+        if (pu->bb.max_depth > BVH_STACK)
+            return fail(-2, "%s: BVH of %zu surfaces is %d levels deep, the traversal stack holds %d", name, pu->bb.prims.size(), pu->bb.max_depth, BVH_STACK);
+        if (pu->bb.nodes.size() != ctx->h_nodes.size() || pu->bb.order.size() != ctx->h_order.size())
+            return fail(-2, "%s: the rebuilt hierarchy has %zu nodes, the context's %zu", name, pu->bb.nodes.size(), ctx->h_nodes.size());
+    }
+    else pu->extent = std::max(ctx->cam_reach, surfaces_extent(all.data(), n));
+    if (!(pu->extent < UPDATE_EXTENT_LIMIT))
+        return fail(-2, "%s: scene or camera coordinates reach %g: the hierarchy's f32 box test holds up to 2^27", name, pu->extent);
+    return 0;
+}
+
+/* the caller's records into the pinned buffer: can fail, and changes nothing a render reads */
+static int update_stage(drt_context *ctx, const drt_surface *surfaces, uint32_t count)
+{
+    int rc = update_prepare(ctx);
+    if (rc) return rc;
+    if (ctx->stage_busy) HIP_TRY(hipEventSynchronize(ctx->upd_ev[2])); /* the last update's copy out of it */
+    ctx->stage_busy = false;
+    memcpy(ctx->h_stage, surfaces, (size_t)count * sizeof(drt_surface));
+    return 0;
+}
+
+static int update_commit(drt_context *ctx, uint32_t first, uint32_t count, PendingUpdate *pu)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    std::copy(ctx->h_stage, ctx->h_stage + count, ctx->h_surfaces.begin() + first);
+    HIP_TRY(hipMemcpyAsync(ctx->d_raw + first, ctx->h_stage, (size_t)count * sizeof(drt_surface), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->upd_ev[2], ctx->stream));
+    ctx->stage_busy = true;
+    if (pu->rebuild)
+    {
+        /* nodes and leaf order into the same allocations; the kernels below fill in every box and every leaf's numbers */
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        std::vector<BvhLeafPrim> leaf(std::max<size_t>(pu->bb.order.size(), 1));
+        memset(leaf.data(), 0, leaf.size() * sizeof(BvhLeafPrim));
+        for (size_t k = 0; k < pu->bb.order.size(); k += 1)
+        {
+            leaf[k].index = pu->bb.order[k];
+            leaf[k].type = ctx->h_surfaces[pu->bb.order[k]].type;
+            leaf[k].reach32 = INFINITY;
+        }
+        HIP_TRY(hipMemcpy(const_cast<BvhNode *>(ctx->dsc.bvh_nodes), pu->bb.nodes.data(), pu->bb.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(const_cast<BvhLeafPrim *>(ctx->dsc.bvh_leaf), leaf.data(), leaf.size() * sizeof(BvhLeafPrim), hipMemcpyHostToDevice));
+        ctx->h_nodes = pu->bb.nodes;
+        ctx->h_order = pu->bb.order;
+        int rc = update_upload_maps(ctx);
+        if (rc) return rc;
+    }
+    int rc = update_enqueue(ctx);
+    if (rc) return rc;
+    if (pu->rebuild) ctx->refits = 0;
+    ctx->extent = pu->extent;
+    ctx->extent_known = true;
+    ctx->upd_check = ctx->upd_violation = false; /* the host has checked the extent itself */
+    return 0;
+}
+
+extern "C" int drt_update_surfaces(drt_context *ctx, const drt_surface *surfaces, uint32_t first, uint32_t count, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "drt_update_surfaces: ctx is null");
+    PendingUpdate pu;
+    int rc = update_check(ctx, surfaces, first, count, flags, "drt_update_surfaces", false, &pu);
+    if (rc || count == 0) return rc;
+    if (flags & DRT_SURFACES_DEVICE)
+    {
+        if ((rc = update_prepare(ctx))) return rc;
+        /* the 13 doubles behind the type and material words, record by record, in stream order */
+        HIP_TRY(hipMemcpy2DAsync((char *)(ctx->d_raw + first) + 8, sizeof(drt_surface), (const char *)surfaces + 8, sizeof(drt_surface), sizeof(drt_surface) - 8, count,
+                                 hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->h_stale = true;
+        if ((rc = update_enqueue(ctx))) return rc;
+        ctx->extent_known = !ctx->use_bvh;
+        ctx->upd_check = ctx->use_bvh;
+        ctx->upd_violation = false;
+        return 0;
+    }
+    if ((rc = update_stage(ctx, surfaces, count))) return rc;
+    return update_commit(ctx, first, count, &pu);
+}
+
+static int set_camera_check(drt_context *ctx, const drt_camera *camera, const char *name)
+{
+    if (!camera) return fail(-1, "%s: camera is null", name);
+    int rc = update_film_check(ctx, name);
+    if (rc) return rc;
+    const double reach = camera_reach(camera);
+    if (ctx->use_bvh && !(reach < UPDATE_EXTENT_LIMIT))
+        return fail(-2, "%s: scene or camera coordinates reach %g: the hierarchy's f32 box test holds up to 2^27", name, reach);
+    return 0;
+}
+
+static int set_camera_commit(drt_context *ctx, const drt_camera *camera)
+{
+    set_device_camera(ctx, camera); /* kernels take it by value: what is enqueued already keeps the old one */
+    ctx->cam_reach = camera_reach(camera);
+    if (!ctx->use_bvh)
+    {
+        ctx->updates += 1;
+        ctx->upd_timed = false;
+        ctx->upd_ms = 0.0;
+        ctx->ft_valid = ctx->mt_valid = false;
+        return 0;
+    }
+    /* the camera's reach is part of the extent, and the extent is in every leaf's padding */
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = update_enqueue(ctx);
+    if (rc) return rc;
+    ctx->extent_known = false;
+    ctx->upd_check = ctx->h_stale; /* the host's own surfaces were checked when they came */
+    ctx->upd_violation = false;
+    return 0;
+}
+
+extern "C" int drt_set_camera(drt_context *ctx, const drt_camera *camera)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "drt_set_camera: ctx is null");
+    int rc = set_camera_check(ctx, camera, "drt_set_camera");
+    if (rc) return rc;
+    if (ctx->use_bvh && (rc = update_prepare(ctx))) return rc;
+    return set_camera_commit(ctx, camera);
+}
+
+extern "C" int drt_get_update_report(drt_context *ctx, drt_update_report *out)
+{
+    g_last_error.clear();
+    if (!ctx || !out) return fail(-1, "drt_get_update_report: null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->upd_timed)
+    {
+        float ms = 0.0f;
+        HIP_TRY(hipEventSynchronize(ctx->upd_ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->upd_ev[0], ctx->upd_ev[1]));
+        ctx->upd_ms = (double)ms;
+        ctx->upd_timed = false;
+    }
+    if (ctx->use_bvh && !ctx->extent_known)
+    {
+        unsigned long long bits = 0;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpy(&bits, ctx->d_upd_status, sizeof(bits), hipMemcpyDeviceToHost));
+        double surfaces = 0.0;
+        memcpy(&surfaces, &bits, sizeof(surfaces));
+        ctx->extent = std::max(ctx->cam_reach, surfaces);
+        ctx->extent_known = true;
+    }
+    out->updates = ctx->updates;
+    out->refits_since_build = ctx->refits;
+    out->extent = ctx->use_bvh ? ctx->extent : 0.0;
+    out->kernel_ms = ctx->upd_ms;
+    return 0;
+}
+
+extern "C" int drt_group_set_camera(drt_group *g, const drt_camera *camera)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_set_camera: the group is null");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = set_camera_check(c, camera, "drt_group_set_camera"))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && c->use_bvh && (rc = update_prepare(c))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = set_camera_commit(c, camera))) return rc;
+    return 0;
+}
+
+extern "C" int drt_group_update_surfaces(drt_group *g, const drt_surface *surfaces, uint32_t first, uint32_t count, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_update_surfaces: the group is null");
+    int rc = 0;
+    /* every context is checked, and every device's staging copy is made, before any context changes */
+    std::vector<PendingUpdate> pending(g->ctx.size());
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = update_check(g->ctx[k], surfaces, first, count, flags, "drt_group_update_surfaces", true, &pending[k]))) return rc;
+    if (count == 0) return 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = update_stage(c, surfaces, count))) return rc;
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = update_commit(g->ctx[k], first, count, &pending[k]))) return rc;
     return 0;
 }
 

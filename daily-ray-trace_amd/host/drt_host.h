@@ -80,7 +80,8 @@ typedef struct
 /* Host extras that the reference has no field for (device choice, RNG seed, batch size, adaptive sampling);
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
- * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK. */
+ * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK,
+ * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE. */
 #define DRT_HOST_MAX_PICKS 64
 typedef struct
 {
@@ -124,6 +125,11 @@ typedef struct
      * for the camera's rays */
     uint32_t projection;
     double   ortho_width;
+    /* DRT_TURNTABLE=n: n frames from ONE context or group, frame k through drt_host_turntable_camera(k, n): per frame one drt_reset_film,
+     * one drt_set_camera and the render the configuration asks for (uniform or adaptive); frame k writes the three standard outputs with
+     * .%04u before the extension. Not combined with checkpoints, resuming, DRT_PROJECTION or the post-passes (denoiser, features, mattes,
+     * picks). 0: off, and everything as without it */
+    uint32_t turntable;
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u
@@ -177,6 +183,11 @@ void drt_host_blackbody_spectrum(f64 min_wl, f64 wl_interval, u32 num_samples, f
 /* init_camera: fills *camera from position/target/roll/fov/fdepth/flength/aperture and the image size. */
 void drt_host_init_camera(drt_camera *camera, const f64 position[3], const f64 target[3], f64 roll, f64 fov,
                           f64 fdepth, f64 flength, f64 aperture, u32 width_px, u32 height_px);
+/* The camera of frame k of an n-frame turntable (DRT_TURNTABLE, drt_set_camera): the scene's own camera with its position turned by
+ * 360 k / n degrees about the axis through its target along the up direction drt_host_init_camera starts from, (0, 1, 0), made by
+ * drt_host_init_camera itself. k = 0 is the scene's camera bit for bit. Returns 0, or -1 (nothing written) for a null pointer, n = 0 or
+ * an empty image. */
+int drt_host_turntable_camera(const drt_host_scene *s, u32 width_px, u32 height_px, u32 k, u32 n, drt_camera *out);
 
 /* Ray tables for drt_bind_rays (include/drt_hip.h), one layer, [height][width][3] each, row 0 at the bottom as the film's rows are.
  * Both return 0, or -1 (nothing written) for a null pointer, an empty image or a film_width that is not a finite number above 0.

@@ -79,8 +79,142 @@ static int publish_mattes(const char *base, const drt_host_scene *hs, u32 width,
     return rename(tmp, path) == 0 ? 0 : -1;
 }
 
+/* "out.spd" -> "out.0003.spd" (no extension: the number goes at the end); -1 when the name does not fit the field */
+static int frame_path(char dst[64], const char *src, u32 frame)
+{
+    if (!src[0]) { dst[0] = 0; return 0; }
+    const char *dot = strrchr(src, '.'), *slash = strrchr(src, '/');
+    if (dot && slash && dot < slash) dot = NULL;
+    const int stem = dot ? (int)(dot - src) : (int)strlen(src);
+    return snprintf(dst, 64, "%.*s.%04u%s", stem, src, frame, dot ? dot : "") < 64 ? 0 : -1;
+}
+
+/* DRT_TURNTABLE=n: n frames from one group, the second and every later one at the price of a drt_set_camera instead of a drt_group_create */
+static int render_turntable(config_arguments *config, const drt_host_options *opt, drt_stats *stats_out)
+{
+    const u32 width = config->output_width, height = config->output_height, frames = opt->turntable;
+    spd_tables_csvs csvs;
+    csvs.white = config->white_spd;  csvs.cmf_x = config->cmf_x;      csvs.cmf_y = config->cmf_y;
+    csvs.cmf_z = config->cmf_z;      csvs.rgb_red = config->red_spd;  csvs.rgb_green = config->green_spd;
+    csvs.rgb_blue = config->blue_spd; csvs.rgb_cyan = config->cyan_spd; csvs.rgb_magenta = config->magenta_spd;
+    csvs.rgb_yellow = config->yellow_spd;
+    char spectra_dir[128];
+    snprintf(spectra_dir, sizeof(spectra_dir), "%s", config->white_spd);
+    char *slash = strrchr(spectra_dir, '/');
+    if (slash) *slash = 0; else snprintf(spectra_dir, sizeof(spectra_dir), "spectra");
+    for (u32 k = 0; k < frames; k += 1)
+    {
+        config_arguments fc = *config;
+        if (frame_path(fc.output_spd, config->output_spd, k) || frame_path(fc.average_spd, config->average_spd, k) ||
+            frame_path(fc.variance_spd, config->variance_spd, k) || frame_path(fc.output_bmp, config->output_bmp, k) ||
+            frame_path(fc.average_bmp, config->average_bmp, k) || frame_path(fc.variance_bmp, config->variance_bmp, k))
+        {
+            fprintf(stderr, "render_image: DRT_TURNTABLE: an output name with .%04u before its extension is longer than 63 characters\n", k);
+            return -1;
+        }
+    }
+    drt_host_scene *hs = drt_host_load_scene(config->input_scene, spectra_dir, &csvs, width, height, config->min_wl, config->max_wl, config->wl_interval);
+    if (!hs)
+    {
+        fprintf(stderr, "render_image: %s\n", drt_host_last_error());
+        return -1;
+    }
+    const drt_scene *scene = drt_host_scene_data(hs);
+    const u32 S = scene->num_wavelengths;
+    const u64 num_pixels = (u64)width * height;
+    f64 *dst_pixels = (f64 *)calloc(num_pixels * (S + 1), sizeof(f64));
+    f64 *dst_avgs = (f64 *)calloc(num_pixels * S, sizeof(f64));
+    f64 *dst_vars = (f64 *)calloc(num_pixels * S, sizeof(f64));
+    u8 *bgra = (u8 *)malloc(num_pixels * 4 + 4);
+    if (!dst_pixels || !dst_avgs || !dst_vars || !bgra)
+    {
+        fprintf(stderr, "render_image: out of memory for %llu pixels\n", (unsigned long long)num_pixels);
+        return -1;
+    }
+    drt_params p;
+    memset(&p, 0, sizeof(p));
+    p.width = width;
+    p.height = height;
+    p.tile_w = width;
+    p.tile_h = height;
+    p.row_stride = 1;
+    p.spp = config->num_pixel_samples;
+    p.max_depth = config->max_cast_depth;
+    p.pixel_scheme = (u32)config->pixel_scheme;
+    p.seed = opt->seed;
+    p.mode = DRT_MODE_SPECTRAL;
+    p.device = opt->device;
+    p.batch_spp = opt->batch_spp;
+    drt_host_checkpoint_projection(0, 0.0);
+    int32_t one_device = p.device;
+    const int32_t *devices = &one_device;
+    u32 n_devices = 1;
+    if (opt->all_devices) { devices = NULL; n_devices = 0; }
+    else if (opt->n_devices) { devices = opt->devices; n_devices = opt->n_devices; }
+    drt_stats stats;
+    memset(&stats, 0, sizeof(stats));
+    int rc = 0, wrc = 0;
+    drt_group *ctx = drt_group_create(scene, drt_host_camera_data(hs), &p, devices, n_devices);
+    if (!ctx) rc = -1;
+    if (!rc && !opt->quiet && drt_group_size(ctx) > 1) printf("Rendering on %u devices\n", drt_group_size(ctx));
+    for (u32 k = 0; !rc && !wrc && k < frames; k += 1)
+    {
+        const f64 t0 = now_ms();
+        config_arguments fc = *config;
+        frame_path(fc.output_spd, config->output_spd, k);
+        frame_path(fc.average_spd, config->average_spd, k);
+        frame_path(fc.variance_spd, config->variance_spd, k);
+        frame_path(fc.output_bmp, config->output_bmp, k);
+        frame_path(fc.average_bmp, config->average_bmp, k);
+        frame_path(fc.variance_bmp, config->variance_bmp, k);
+        drt_camera cam;
+        if (drt_host_turntable_camera(hs, width, height, k, frames, &cam) != 0) { rc = -1; break; }
+        if ((rc = drt_group_reset_film(ctx))) break;
+        if ((rc = drt_group_set_camera(ctx, &cam))) break;
+        if (opt->adaptive)
+        {
+            drt_adaptive a;
+            memset(&a, 0, sizeof(a));
+            a.min_spp = opt->adaptive_min_spp;
+            a.max_spp = p.spp;
+            a.step = opt->adaptive_step;
+            a.rel_error = opt->adaptive_error;
+            a.floor = opt->adaptive_floor;
+            if ((rc = drt_group_render_adaptive(ctx, &a))) break;
+        }
+        else if ((rc = drt_group_render(ctx, 0, p.spp))) break;
+        if ((rc = drt_group_read_film(ctx, dst_pixels, dst_avgs, dst_vars))) break;
+        if ((rc = drt_group_get_stats(ctx, &stats))) break;
+        wrc = drt_host_write_outputs(&fc, width, height, S, scene->min_wavelength, scene->wavelength_interval, dst_pixels, dst_avgs, dst_vars, 0, p.spp, p.seed);
+        if (wrc) { fprintf(stderr, "render_image: %s\n", drt_host_checkpoint_error()); break; }
+        const char *bmp_path[3] = { fc.output_bmp, fc.average_bmp, fc.variance_bmp };
+        for (int b = 0; !rc && !wrc && b < 3 && fc.output_bmp[0]; b += 1)
+        {
+            if (!bmp_path[b][0]) continue;
+            if ((rc = drt_group_read_bgra(ctx, b, bgra))) break;
+            if (drt_host_write_bmp_bgra(bmp_path[b], width, height, bgra) != 0)
+            {
+                fprintf(stderr, "render_image: could not write one of the .bmp outputs\n");
+                wrc = -1;
+            }
+        }
+        if (!rc && !wrc && !opt->quiet)
+            printf("Frame %u / %u: %fms (device %fms: trace %fms, shade+film %fms)\n", k + 1, frames, now_ms() - t0, stats.total_ms, stats.trace_ms, stats.shade_ms);
+    }
+    if (rc) fprintf(stderr, "render_image: the HIP launcher failed (%d): %s\n", rc, drt_last_error());
+    if (ctx) drt_group_destroy(ctx);
+    if (stats_out) *stats_out = stats;
+    free(bgra);
+    free(dst_vars);
+    free(dst_avgs);
+    free(dst_pixels);
+    drt_host_free_scene(hs);
+    return rc ? rc : (wrc ? -2 : 0);
+}
+
 int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_stats *stats_out)
 {
+    if (opt && opt->turntable) return render_turntable(config, opt, stats_out);
     u32 width = config->output_width, height = config->output_height;
     spd_tables_csvs csvs;
     csvs.white = config->white_spd;  csvs.cmf_x = config->cmf_x;      csvs.cmf_y = config->cmf_y;
@@ -683,6 +817,22 @@ static int projection_options(drt_host_options *opt)
     return 0;
 }
 
+/* DRT_TURNTABLE=n (a whole number, 1 or more): parsed and checked here, before any device call, after the options it cannot be combined with. */
+static int turntable_options(drt_host_options *opt)
+{
+    opt->turntable = 0;
+    if (!getenv("DRT_TURNTABLE")) return 0;
+    if (env_u32("DRT_TURNTABLE", &opt->turntable)) return -1;
+    if (opt->turntable < 1 || opt->turntable > 9999) { fprintf(stderr, "render_image: DRT_TURNTABLE=%u: from 1 to 9999 frames\n", opt->turntable); return -1; }
+    static const char *const names[] = { "DRT_CHECKPOINT_SPP", "DRT_RESUME", "DRT_ADAPTIVE_CHECKPOINT_ROUNDS", "DRT_ADAPTIVE_RESUME", "DRT_PROJECTION",
+                                         "DRT_DENOISE_K", "DRT_PICK" };
+    for (int k = 0; k < 7; k += 1)
+        if (getenv(names[k])) { fprintf(stderr, "render_image: DRT_TURNTABLE cannot be combined with %s\n", names[k]); return -1; }
+    if (opt->features) { fprintf(stderr, "render_image: DRT_TURNTABLE cannot be combined with DRT_FEATURES\n"); return -1; }
+    if (opt->mattes) { fprintf(stderr, "render_image: DRT_TURNTABLE cannot be combined with DRT_MATTES\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -713,5 +863,6 @@ void render_image(config_arguments *config)
     if (mattes_options(&opt) != 0) exit(-1);
     if (pick_options(config, &opt) != 0) exit(-1);
     if (projection_options(&opt) != 0) exit(-1);
+    if (turntable_options(&opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

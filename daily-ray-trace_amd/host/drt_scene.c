@@ -577,6 +577,7 @@ struct drt_host_scene
 {
     drt_scene     scene;
     drt_camera    camera;
+    camera_input  camera_in; /* what `camera` was made from (drt_host_turntable_camera makes its frames from it) */
     drt_surface  *surfaces;
     drt_material *materials;
     f64          *spds;
@@ -828,6 +829,7 @@ static drt_host_scene *build_scene(scene_input *in, const char *spectra_dir, con
 
     const camera_input *c = &in->camera;
     drt_host_init_camera(&h->camera, c->position, c->target, c->roll, c->fov, c->fdepth, c->flength, c->aperture, width_px, height_px);
+    h->camera_in = *c;
 
     h->scene.num_surfaces = in->num_surfaces;
     h->scene.surfaces = h->surfaces;
@@ -901,5 +903,37 @@ void drt_host_free_scene(drt_host_scene *h)
 }
 const drt_scene *drt_host_scene_data(const drt_host_scene *h) { return &h->scene; }
 const drt_camera *drt_host_camera_data(const drt_host_scene *h) { return &h->camera; }
+
+/* Frame k of an n-frame turntable: the scene's own camera with its position turned by 360 k / n degrees about the axis through its
+ * target along init_camera's reference up (0, 1, 0), made by drt_host_init_camera itself. Frame 0 (and every multiple of n) leaves the
+ * position untouched, so it is the scene's camera bit for bit; quarter turns take their sine and cosine as the whole numbers they are. */
+int drt_host_turntable_camera(const drt_host_scene *h, u32 width_px, u32 height_px, u32 k, u32 n, drt_camera *out)
+{
+    if (!h || !out || n == 0 || width_px == 0 || height_px == 0) return -1;
+    const camera_input *c = &h->camera_in;
+    f64 pos[3] = { c->position[0], c->position[1], c->position[2] };
+    k %= n;
+    if (k)
+    {
+        f64 cs, sn;
+        if ((4 * (u64)k) % n == 0)
+        {
+            static const f64 quarter[4][2] = { { 1.0, 0.0 }, { 0.0, 1.0 }, { -1.0, 0.0 }, { 0.0, -1.0 } };
+            cs = quarter[(4 * (u64)k) / n][0];
+            sn = quarter[(4 * (u64)k) / n][1];
+        }
+        else
+        {
+            const f64 angle = (2.0 * PI * (f64)k) / (f64)n;
+            cs = cos(angle);
+            sn = sin(angle);
+        }
+        const f64 dx = c->position[0] - c->target[0], dz = c->position[2] - c->target[2];
+        pos[0] = c->target[0] + (cs * dx + sn * dz);
+        pos[2] = c->target[2] + (cs * dz - sn * dx);
+    }
+    drt_host_init_camera(out, pos, c->target, c->roll, c->fov, c->fdepth, c->flength, c->aperture, width_px, height_px);
+    return 0;
+}
 const char *drt_host_material_name(const drt_host_scene *h, u32 i) { return i < h->scene.num_materials ? h->material_names[i] : ""; }
 const char *drt_host_surface_name(const drt_host_scene *h, u32 i) { return i < h->scene.num_surfaces ? h->surface_names[i] : ""; }

@@ -207,6 +207,72 @@ def _ray_table(origins, dirs, weights, width, height, device):
     return t, arrs
 
 
+SURFACES_DEVICE, SURFACES_REBUILD = 1, 2  # DRT_SURFACES_*
+SURFACE_ROW = 14  # a drt_surface as doubles: word 0 holds type and material, then position, radius, normal, u, v
+
+
+class UpdateReport(C.Structure):
+    """drt_update_report (include/drt_hip.h). 24 bytes."""
+    _fields_ = [("updates", C.c_uint32), ("refits_since_build", C.c_uint32), ("extent", C.c_double), ("kernel_ms", C.c_double)]
+
+
+assert C.sizeof(Surface) == 8 * SURFACE_ROW == 112 and C.sizeof(UpdateReport) == 24
+
+
+def surface_rows(bundle_or_surfaces):
+    """[n][14] float64: the bytes of the scene's drt_surface records viewed as doubles (word 0 holds type and material, so it is
+    no number to compute with). Takes a SceneBundle or a ctypes Surface array; a copy."""
+    if hasattr(bundle_or_surfaces, "scene"):
+        sc = bundle_or_surfaces.scene
+        n, src = int(sc.num_surfaces), sc.surfaces
+    else:
+        n, src = len(bundle_or_surfaces), bundle_or_surfaces
+    rows = np.empty((n, SURFACE_ROW), dtype=np.float64)
+    if n:
+        C.memmove(rows.ctypes.data, src, n * C.sizeof(Surface))
+    return rows
+
+
+def surfaces_from_rows(rows):
+    """the inverse of surface_rows: a ctypes Surface array with the rows' bytes"""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2 or rows.shape[1] != SURFACE_ROW:
+        raise ValueError("rows: an [n][%d] float64 array" % SURFACE_ROW)
+    sa = (Surface * max(1, rows.shape[0]))()
+    if rows.shape[0]:
+        C.memmove(sa, rows.ctypes.data, rows.shape[0] * C.sizeof(Surface))
+    return sa
+
+
+def _update_args(surfaces, device):
+    """(pointer, count, flags, what must stay referenced) of update_surfaces' three input forms"""
+    if _is_tensor(surfaces):
+        torch = sys.modules["torch"]
+        t = surfaces
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != SURFACE_ROW:
+            raise ValueError("surfaces: a contiguous [n][%d] float64 tensor" % SURFACE_ROW)
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError("surfaces: a tensor on the context's device (cuda:%d)" % device)
+        return t.data_ptr(), int(t.shape[0]), SURFACES_DEVICE, t
+    if isinstance(surfaces, np.ndarray):
+        rows = np.ascontiguousarray(surfaces, dtype=np.float64)
+        if rows.ndim != 2 or rows.shape[1] != SURFACE_ROW:
+            raise ValueError("surfaces: an [n][%d] float64 array" % SURFACE_ROW)
+        return rows.ctypes.data, int(rows.shape[0]), 0, rows
+    return C.cast(surfaces, C.c_void_p).value, len(surfaces), 0, surfaces
+
+
+def turntable_camera(bundle, width, height, k, n):
+    """drt_host_turntable_camera (host/drt_host.h): the camera of frame k of an n-frame turntable about the target of a LOADED scene's
+    camera (load_scene / load_scene_text); k = 0 is the scene's camera bit for bit."""
+    if bundle._handle is None:
+        raise ValueError("turntable_camera: a scene loaded through the host library (it keeps the camera's position and target)")
+    cam = Camera()
+    if host_lib().drt_host_turntable_camera(bundle._handle, width, height, k, n, C.byref(cam)) != 0:
+        raise ValueError("turntable_camera: n of at least 1 and an image of at least one pixel")
+    return cam
+
+
 def _camera_of(bundle_or_camera):
     return bundle_or_camera.camera if hasattr(bundle_or_camera, "camera") else bundle_or_camera
 
@@ -319,6 +385,7 @@ def host_lib():
         f64p = C.POINTER(C.c_double)
         L.drt_host_rays_equirect.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, f64p, f64p]
         L.drt_host_rays_ortho.argtypes = [C.POINTER(Camera), C.c_uint32, C.c_uint32, C.c_double, f64p, f64p]
+        L.drt_host_turntable_camera.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Camera)]
         _host = L
     return _host
 
@@ -547,6 +614,13 @@ def hip_lib():
             L.drt_bind_rays.argtypes = [C.c_void_p, C.POINTER(RayTable)]
             L.drt_group_bind_rays.argtypes = [C.c_void_p, C.POINTER(RayTable)]
         L.drt_batch_spp.argtypes = [C.c_void_p]
+        if hasattr(L, "drt_update_surfaces"):
+            L.drt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+            L.drt_update_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+            L.drt_get_update_report.argtypes = [C.c_void_p, C.POINTER(UpdateReport)]
+            L.drt_group_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
+            L.drt_group_update_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+            L.drt_group_reset_film.argtypes = [C.c_void_p]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
         L.drt_selftest_arith.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -575,7 +649,9 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_render_features", "drt_read_features", "drt_read_feature_bgra", "drt_group_render_features",
                "drt_render_mattes", "drt_read_mattes", "drt_read_matte", "drt_read_matte_bgra", "drt_group_render_mattes",
                "drt_cast_rays", "drt_test_visibility", "drt_cast_pixels", "drt_group_cast_rays", "drt_group_test_visibility",
-               "drt_group_cast_pixels", "drt_bind_rays", "drt_group_bind_rays"]
+               "drt_group_cast_pixels", "drt_bind_rays", "drt_group_bind_rays",
+               "drt_set_camera", "drt_update_surfaces", "drt_get_update_report", "drt_group_set_camera", "drt_group_update_surfaces",
+               "drt_group_reset_film"]
 
 
 def _check(rc, what):
@@ -839,6 +915,30 @@ class Renderer:
         _check(self.L.drt_bind_rays(self.ctx, C.byref(t)), "drt_bind_rays")
         self._ray_arrays = keep if t.flags & RAYS_DEVICE else None
 
+    def set_camera(self, camera_or_bundle):
+        """drt_set_camera: from now on the context renders through this camera (a Camera, or a SceneBundle's). The film must hold no
+        samples. Bit for bit a fresh context's results with that camera."""
+        cam = _camera_of(camera_or_bundle)
+        _check(self.L.drt_set_camera(self.ctx, C.byref(cam)), "drt_set_camera")
+
+    def update_surfaces(self, surfaces, first=0, rebuild=False):
+        """drt_update_surfaces: surfaces [first, first + n) replaced; types, materials and the surface count stay. A ctypes Surface array
+        or a numpy [n][14] float64 array of raw rows (surface_rows): host mode, checked before anything changes. A float64 torch tensor
+        [n][14] on the context's device: device mode, enqueued on the context's stream without waiting. rebuild: build the hierarchy anew
+        (host mode only). The film must hold no samples. Bit for bit a fresh context's results on the updated scene."""
+        ptr, n, flags, keep = _update_args(surfaces, int(self.params.device))
+        if rebuild:
+            flags |= SURFACES_REBUILD
+        _check(self.L.drt_update_surfaces(self.ctx, ptr, first, n, flags), "drt_update_surfaces")
+        if flags & SURFACES_DEVICE:
+            self._update_rows = keep  # until the stream has read it: the next update or close() at the latest
+
+    def update_report(self):
+        """drt_get_update_report: {"updates", "refits_since_build", "extent", "kernel_ms"}"""
+        r = UpdateReport()
+        _check(self.L.drt_get_update_report(self.ctx, C.byref(r)), "drt_get_update_report")
+        return {n: getattr(r, n) for n, _ in r._fields_}
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -973,6 +1073,21 @@ class Group:
             raise ValueError("Group.bind_rays: numpy arrays (a group takes host pointers only)")
         t, _ = _ray_table(origins, dirs, weights, int(self.params.width), int(self.params.height), 0)
         _check(self.L.drt_group_bind_rays(self.g, C.byref(t)), "drt_group_bind_rays")
+
+    def reset_film(self):
+        _check(self.L.drt_group_reset_film(self.g), "drt_group_reset_film")
+
+    def set_camera(self, camera_or_bundle):
+        """drt_group_set_camera: every context is checked before any is changed"""
+        cam = _camera_of(camera_or_bundle)
+        _check(self.L.drt_group_set_camera(self.g, C.byref(cam)), "drt_group_set_camera")
+
+    def update_surfaces(self, surfaces, first=0, rebuild=False):
+        """drt_group_update_surfaces: as Renderer.update_surfaces in host mode (a ctypes Surface array or numpy rows)"""
+        if _is_tensor(surfaces):
+            raise ValueError("Group.update_surfaces: a Surface array or numpy rows (a group takes host pointers only)")
+        ptr, n, flags, _keep = _update_args(surfaces, 0)
+        _check(self.L.drt_group_update_surfaces(self.g, ptr, first, n, flags | (SURFACES_REBUILD if rebuild else 0)), "drt_group_update_surfaces")
 
     def close(self):
         if self.g:

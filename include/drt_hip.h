@@ -554,6 +554,63 @@ int drt_bind_rays(drt_context *ctx, const drt_ray_table *t);   /* t == NULL: bac
  * is changed: a call that fails on one device leaves the whole group as it was. */
 int drt_group_bind_rays(drt_group *g, const drt_ray_table *t);
 
+/*
+ * Scene updates: move the camera and the surfaces of a live context, where the only way used to be drt_destroy + drt_create (the
+ * pool freed and allocated again, the pool measurement rendered again, the hierarchy built again). DESIGN.md section 5g.
+ *
+ * The rule: after a successful call the context gives, for every later call -- drt_render, the adaptive calls, features, mattes, ray
+ * queries, ray films, drt_read_* -- bit for bit the results of a fresh context that drt_create would make from the scene with surfaces
+ * [first, first + count) replaced, or from the new camera, with the same drt_params, materials and spectral tables: films, hit logs, the
+ * counting fields of drt_stats, RNG draw counts and query answers. Three things may differ from that fresh context, because none of them
+ * can change a result bit: the shape of the hierarchy (it is refitted, not rebuilt, unless DRT_SURFACES_REBUILD asks), the size of the
+ * record pool, and the shade kernel's dark-skip choice. The pool is NOT measured again: a launch that runs out of it is rendered again by
+ * the existing mechanism, and drt_stats.redone_launches shows it.
+ *
+ * An update fixes the surface count and every surface's type and material (so the light list, the record width, the LDS layout and the
+ * kernel instantiations stay); position, radius, normal, u and v may change on any surface, lights and point lights included.
+ * History does not matter: the context keeps the caller's raw surfaces (a host copy from drt_create, a device copy made at the first
+ * update), an update writes its range into that copy, and every table is derived again from all of it: update A then update B equals
+ * update B alone. Both calls need a film without samples (a fresh context, or drt_reset_film), as drt_bind_rays does.
+ *
+ * Host mode (flags without DRT_SURFACES_DEVICE): everything is checked before anything changes, and the call is refused with a message
+ * and nothing changed for: a null pointer with count > 0, first + count beyond the surface count, unknown flag bits; a film with samples;
+ * a surface whose type or material differs from the one it replaces (the message names the first); and, in a DRT_PATH_BVH context,
+ * coordinates that take the extent to 2^27 or beyond or (DRT_SURFACES_REBUILD) a tree deeper than the traversal stack -- drt_create's
+ * two refusals. The caller's array is free when the call returns. count == 0 is a successful no-op (whatever the film holds). In a
+ * context without the hierarchy DRT_SURFACES_REBUILD has nothing to build and changes nothing.
+ *
+ * Device mode: `surfaces` is count records of sizeof(drt_surface) (112 bytes) on the context's device; their type and material words are
+ * not read. The work is enqueued on the context's stream and the call returns without waiting. The one condition the host cannot check
+ * is the 2^27 extent: the kernel records a violation in a status word, and every later synchronising call (drt_synchronize, drt_read_*,
+ * drt_get_stats) fails, naming it, until a later update or drt_set_camera brings the extent back. Renders enqueued in between are not
+ * held to the rule but stay within their buffers (the box test only prunes). DRT_SURFACES_REBUILD with DRT_SURFACES_DEVICE is refused.
+ *
+ * drt_set_camera replaces the camera; in a DRT_PATH_BVH context the camera's reach is part of the extent, so the same derivation is
+ * enqueued. It works while a ray table is bound (the film then does not depend on it).
+ *
+ * After either call results that describe the old scene are stale: drt_read_features / drt_read_mattes of a pass taken before it are
+ * refused. Everything is rewritten in place on the context's stream, so what was enqueued before stays ordered before the update.
+ */
+#define DRT_SURFACES_DEVICE  1u /* `surfaces` is device memory on the context's device */
+#define DRT_SURFACES_REBUILD 2u /* host mode only: build the hierarchy anew instead of refitting it */
+int drt_set_camera(drt_context *ctx, const drt_camera *camera);
+int drt_update_surfaces(drt_context *ctx, const drt_surface *surfaces, uint32_t first, uint32_t count, uint32_t flags);
+/* Every context is checked, and every device's staging copy is made, before any context is changed. Host pointers only. Same bits for
+ * any device list. */
+/* drt_reset_film on every device: what a group needs between two frames, since both calls want a film without samples. */
+int drt_group_reset_film(drt_group *g);
+int drt_group_set_camera(drt_group *g, const drt_camera *camera);
+int drt_group_update_surfaces(drt_group *g, const drt_surface *surfaces, uint32_t first, uint32_t count, uint32_t flags);
+typedef struct drt_update_report
+{
+    uint32_t updates;            /* successful drt_update_surfaces (count > 0) and drt_set_camera calls */
+    uint32_t refits_since_build; /* of those, the ones that refitted the hierarchy since it was last built (0 without DRT_PATH_BVH) */
+    double   extent;             /* the extent the hierarchy's paddings are made for: max(camera reach, surfaces); 0 without DRT_PATH_BVH */
+    double   kernel_ms;          /* HIP-event time of the last update's kernels (0: it launched none) */
+} drt_update_report;             /* 24 bytes */
+/* Waits for the last update's kernels. */
+int drt_get_update_report(drt_context *ctx, drt_update_report *out);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */
