@@ -11,6 +11,7 @@
 #include "drt_matte_kernels.h"
 #include "drt_ray_kernels.h"
 #include "drt_update_kernels.h"
+#include "drt_build_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -182,6 +183,18 @@ struct drt_context
     bool      upd_check = false, upd_violation = false; /* device mode: the status word is to be read at the next synchronisation; what it said */
     uint32_t  updates = 0, refits = 0;
     double    upd_ms = 0.0;
+    /* device hierarchy builds (drt_rebuild_hierarchy; drt_build_kernels.h): the temporaries, made at the first one, and the host's
+     * copy of the tree on its way back */
+    bool      boxes_valid = false;         /* d_boxes and the extent word hold the current surfaces' (an update has run the derive kernel) */
+    bool      hb_ready = false, hb_timed = false;
+    bool      hb_mirror_pending = false;   /* h_nodes, h_order and level_first are the tree before the last device build: hb_ev[2] says when hb_mirror holds the new ones */
+    uint32_t *d_hb_tree_surf = nullptr, *d_hb_pos[2] = {nullptr, nullptr}, *d_hb_table = nullptr, *d_hb_order = nullptr;
+    uint64_t *d_hb_keys[2] = {nullptr, nullptr};
+    uint4    *d_hb_items[2] = {nullptr, nullptr};
+    unsigned char *d_hb_status = nullptr, *hb_mirror = nullptr; /* BUILD_STATUS_BYTES; pinned: nodes, leaf order, level counts */
+    hipEvent_t hb_ev[3] = {nullptr, nullptr, nullptr}; /* the last build's kernels: start, end; its copy into hb_mirror */
+    uint32_t  hb_builds = 0, hb_built_by = 0, hb_depth = 0;
+    double    hb_ms = 0.0;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -703,6 +716,7 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
         if ((rc = upload(ctx, leaf, &d.bvh_leaf))) return rc;
         ctx->h_nodes = bb.nodes;
         ctx->h_order = bb.order;
+        ctx->hb_depth = (uint32_t)bb.max_depth;
         ctx->extent = bb.extent;
     }
     if (!ctx->scene_in_lds) ctx->trace_lds = 0;
@@ -1211,6 +1225,19 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_leaf_parent);
     (void)hipFree(ctx->d_levels);
     (void)hipFree(ctx->d_upd_status);
+    (void)hipFree(ctx->d_hb_tree_surf);
+    (void)hipFree(ctx->d_hb_table);
+    (void)hipFree(ctx->d_hb_order);
+    (void)hipFree(ctx->d_hb_status);
+    for (int k = 0; k < 2; k += 1)
+    {
+        (void)hipFree(ctx->d_hb_pos[k]);
+        (void)hipFree(ctx->d_hb_keys[k]);
+        (void)hipFree(ctx->d_hb_items[k]);
+    }
+    (void)hipHostFree(ctx->hb_mirror);
+    for (hipEvent_t e : ctx->hb_ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->upd_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->mt_ev)
@@ -3817,32 +3844,51 @@ static int update_prepare(drt_context *ctx)
 }
 
 /* the three kernels, on the context's stream: every table derived again from ALL raw surfaces and the camera's reach */
+static int hierarchy_adopt(drt_context *ctx);
+
+/* the derive kernel over all raw surfaces: every column, the boxes and the extent word */
+static int update_enqueue_derive(drt_context *ctx)
+{
+    const uint32_t n = ctx->dsc.n_surf;
+    HIP_TRY(hipMemsetAsync(ctx->d_upd_status, 0, UPD_STATUS_WORDS * sizeof(unsigned long long), ctx->stream));
+    UpdateTables t;
+    t.raw = (const double *)ctx->d_raw;
+    t.surf = const_cast<double *>(ctx->dsc.surf);
+    t.lights = const_cast<double *>(ctx->dsc.lights);
+    t.light_slot = ctx->d_light_slot;
+    t.boxes = ctx->use_bvh ? ctx->d_boxes : nullptr;
+    t.status = ctx->d_upd_status;
+    hipLaunchKernelGGL(drt_surface_derive_kernel, dim3((n + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, ctx->stream, ctx->dsc, t);
+    HIP_TRY(hipGetLastError());
+    ctx->boxes_valid = ctx->use_bvh;
+    return 0;
+}
+
+static LeafTables update_leaf_tables(drt_context *ctx)
+{
+    LeafTables lt;
+    lt.raw = (const double *)ctx->d_raw;
+    lt.boxes = ctx->d_boxes;
+    lt.leaf_parent = ctx->d_leaf_parent;
+    lt.leaf = const_cast<BvhLeafPrim *>(ctx->dsc.bvh_leaf);
+    lt.nodes = const_cast<BvhNode *>(ctx->dsc.bvh_nodes);
+    lt.status = ctx->d_upd_status;
+    return lt;
+}
+
 static int update_enqueue(drt_context *ctx)
 {
+    int rc = hierarchy_adopt(ctx); /* a refit goes level by level, and after a device build only the device knows the levels yet */
+    if (rc) return rc;
     HIP_TRY(hipEventRecord(ctx->upd_ev[0], ctx->stream));
     const uint32_t n = ctx->dsc.n_surf;
     if (n > 0)
     {
-        HIP_TRY(hipMemsetAsync(ctx->d_upd_status, 0, UPD_STATUS_WORDS * sizeof(unsigned long long), ctx->stream));
-        UpdateTables t;
-        t.raw = (const double *)ctx->d_raw;
-        t.surf = const_cast<double *>(ctx->dsc.surf);
-        t.lights = const_cast<double *>(ctx->dsc.lights);
-        t.light_slot = ctx->d_light_slot;
-        t.boxes = ctx->use_bvh ? ctx->d_boxes : nullptr;
-        t.status = ctx->d_upd_status;
-        hipLaunchKernelGGL(drt_surface_derive_kernel, dim3((n + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, ctx->stream, ctx->dsc, t);
-        HIP_TRY(hipGetLastError());
+        if ((rc = update_enqueue_derive(ctx))) return rc;
         const uint32_t n_leaf = (uint32_t)ctx->h_order.size();
         if (ctx->use_bvh && n_leaf > 0)
         {
-            LeafTables lt;
-            lt.raw = t.raw;
-            lt.boxes = ctx->d_boxes;
-            lt.leaf_parent = ctx->d_leaf_parent;
-            lt.leaf = const_cast<BvhLeafPrim *>(ctx->dsc.bvh_leaf);
-            lt.nodes = const_cast<BvhNode *>(ctx->dsc.bvh_nodes);
-            lt.status = ctx->d_upd_status;
+            const LeafTables lt = update_leaf_tables(ctx);
             hipLaunchKernelGGL(drt_bvh_leaf_kernel, dim3((n_leaf + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, ctx->stream, lt, n_leaf, ctx->cam_reach);
             HIP_TRY(hipGetLastError());
             for (size_t l = 0; l + 1 < ctx->level_first.size(); l += 1) /* deepest level first; a kernel boundary between two levels */
@@ -3956,6 +4002,9 @@ static int update_commit(drt_context *ctx, uint32_t first, uint32_t count, Pendi
     {
         /* nodes and leaf order into the same allocations; the kernels below fill in every box and every leaf's numbers */
         HIP_TRY(hipStreamSynchronize(ctx->stream));
+        ctx->hb_mirror_pending = false; /* (a device-built tree's links on their way back: this tree replaces them) */
+        ctx->hb_built_by = 0;
+        ctx->hb_depth = (uint32_t)pu->bb.max_depth;
         std::vector<BvhLeafPrim> leaf(std::max<size_t>(pu->bb.order.size(), 1));
         memset(leaf.data(), 0, leaf.size() * sizeof(BvhLeafPrim));
         for (size_t k = 0; k < pu->bb.order.size(); k += 1)
@@ -4105,6 +4154,234 @@ extern "C" int drt_group_update_surfaces(drt_group *g, const drt_surface *surfac
         if (c && (rc = update_stage(c, surfaces, count))) return rc;
     for (size_t k = 0; k < g->ctx.size(); k += 1)
         if (g->ctx[k] && (rc = update_commit(g->ctx[k], first, count, &pending[k]))) return rc;
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Device hierarchy builds: the tree of a live context anew, on its stream (include/drt_hip.h) */
+
+/* hb_mirror: the nodes, the surface of every leaf slot, the level counts */
+static size_t hierarchy_mirror_order(const drt_context *ctx) { return ctx->h_nodes.size() * sizeof(BvhNode); }
+static size_t hierarchy_mirror_counts(const drt_context *ctx) { return hierarchy_mirror_order(ctx) + ctx->h_order.size() * sizeof(uint32_t); }
+
+/* the deepest level an inner node can be on: the rule's budget keeps depth + 2 + ceil(log2 range) <= BVH_STACK, and a chain of
+ * inner nodes that deep takes as many surfaces */
+static uint32_t hierarchy_max_level(uint32_t m) { return std::min<uint32_t>(BUILD_LEVELS - 2, m - 2u); }
+
+/* the temporaries of a build, made at the first one (with everything an update needs: the raw surfaces, the boxes, the maps) */
+static int hierarchy_prepare(drt_context *ctx)
+{
+    int rc = update_prepare(ctx);
+    if (rc || ctx->hb_ready) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t m = ctx->h_order.size(), m1 = std::max<size_t>(m, 1);
+    if (!ctx->d_hb_tree_surf)
+    {
+        std::vector<uint32_t> tree_surf; /* spheres and planes in surface order: types do not change */
+        for (size_t i = 0; i < ctx->h_surfaces.size(); i += 1)
+            if (ctx->h_surfaces[i].type == DRT_GEO_SPHERE || ctx->h_surfaces[i].type == DRT_GEO_PLANE) tree_surf.push_back((uint32_t)i);
+        if (tree_surf.size() != m) return fail(-2, "drt_rebuild_hierarchy: %zu surfaces for a tree of %zu leaf slots", tree_surf.size(), m);
+        HIP_TRY(hipMalloc((void **)&ctx->d_hb_tree_surf, m1 * sizeof(uint32_t)));
+        if (m) HIP_TRY(hipMemcpy(ctx->d_hb_tree_surf, tree_surf.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    const size_t n_tiles = (m1 + SORT_TILE - 1) / SORT_TILE;
+    for (int k = 0; k < 2; k += 1)
+    {
+        if (!ctx->d_hb_keys[k]) HIP_TRY(hipMalloc((void **)&ctx->d_hb_keys[k], m1 * sizeof(uint64_t)));
+        if (!ctx->d_hb_pos[k]) HIP_TRY(hipMalloc((void **)&ctx->d_hb_pos[k], m1 * sizeof(uint32_t)));
+        if (!ctx->d_hb_items[k]) HIP_TRY(hipMalloc((void **)&ctx->d_hb_items[k], (m1 / 2 + 1) * sizeof(uint4))); /* an item covers two surfaces at least */
+    }
+    if (!ctx->d_hb_table) HIP_TRY(hipMalloc((void **)&ctx->d_hb_table, (size_t)SORT_DIGITS * n_tiles * sizeof(uint32_t)));
+    if (!ctx->d_hb_order) HIP_TRY(hipMalloc((void **)&ctx->d_hb_order, m1 * sizeof(uint32_t)));
+    if (!ctx->d_hb_status) HIP_TRY(hipMalloc((void **)&ctx->d_hb_status, BUILD_STATUS_BYTES));
+    if (!ctx->hb_mirror) HIP_TRY(hipHostMalloc((void **)&ctx->hb_mirror, hierarchy_mirror_counts(ctx) + (BUILD_LEVELS + 1) * sizeof(uint32_t), hipHostMallocDefault));
+    for (hipEvent_t &e : ctx->hb_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    ctx->hb_ready = true;
+    return 0;
+}
+
+/* the host's copy of a device-built tree, when something needs it: waits for the copy the build enqueued, never for more */
+static int hierarchy_adopt(drt_context *ctx)
+{
+    if (!ctx->hb_mirror_pending) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipEventSynchronize(ctx->hb_ev[2]));
+    memcpy(ctx->h_nodes.data(), ctx->hb_mirror, hierarchy_mirror_order(ctx));
+    memcpy(ctx->h_order.data(), ctx->hb_mirror + hierarchy_mirror_order(ctx), ctx->h_order.size() * sizeof(uint32_t));
+    uint32_t count[BUILD_LEVELS + 1];
+    memcpy(count, ctx->hb_mirror + hierarchy_mirror_counts(ctx), sizeof(count));
+    /* the level table is the deepest level first (drt_build_kernels.h), as tree_maps lays it out */
+    ctx->level_first.assign(1, 0u);
+    ctx->hb_depth = 1;
+    for (uint32_t l = BUILD_LEVELS; l >= 1; l -= 1)
+    {
+        if (count[l] == 0u) continue;
+        ctx->hb_depth = std::max(ctx->hb_depth, l + 1u);
+        ctx->level_first.push_back(ctx->level_first.back() + count[l]);
+    }
+    ctx->hb_mirror_pending = false;
+    return 0;
+}
+
+static int hierarchy_check(const drt_context *ctx, uint32_t flags, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: ctx is null", name);
+    if (flags != 0u) return fail(-1, "%s: unknown flags 0x%x", name, flags);
+    return 0;
+}
+
+static int hierarchy_enqueue(drt_context *ctx)
+{
+    if (!ctx->use_bvh) return 0; /* nothing to build: as DRT_SURFACES_REBUILD there */
+    int rc = hierarchy_prepare(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t m = (uint32_t)ctx->h_order.size();
+    if (m >= 2u) /* (the trees over no surface and over one are the two special roots the context has) */
+    {
+        HIP_TRY(hipEventRecord(ctx->hb_ev[0], st));
+        if (!ctx->boxes_valid && (rc = update_enqueue_derive(ctx))) return rc; /* no update yet: the boxes and the extent word are not made */
+        const uint32_t grid = (m + BUILD_BLOCK - 1) / BUILD_BLOCK, n_tiles = (m + SORT_TILE - 1) / SORT_TILE;
+        BuildTables bt;
+        bt.boxes = ctx->d_boxes;
+        bt.tree_surf = ctx->d_hb_tree_surf;
+        bt.bounds = (unsigned long long *)ctx->d_hb_status;
+        bt.level_count = (uint32_t *)(ctx->d_hb_status + BUILD_BOUND_WORDS * 8);
+        bt.m = m;
+        hipLaunchKernelGGL(drt_build_init_kernel, dim3(1), dim3(64), 0, st, bt, ctx->d_hb_items[0]);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(drt_build_bounds_kernel, dim3(grid), dim3(BUILD_BLOCK), 0, st, bt);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(drt_build_keys_kernel, dim3(grid), dim3(BUILD_BLOCK), 0, st, bt, ctx->d_hb_keys[0], ctx->d_hb_pos[0]);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t pass = 0; pass < SORT_PASSES; pass += 1) /* the sorted keys end where they began: SORT_PASSES is even */
+        {
+            const int from = (int)(pass & 1u), to = 1 - from;
+            hipLaunchKernelGGL(drt_build_count_kernel, dim3(n_tiles), dim3(BUILD_BLOCK), 0, st, ctx->d_hb_keys[from], m, pass * 8u, ctx->d_hb_table, n_tiles);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(drt_build_scan_kernel, dim3(1), dim3(SORT_DIGITS), 0, st, ctx->d_hb_table, n_tiles);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(drt_build_scatter_kernel, dim3(n_tiles), dim3(BUILD_BLOCK), 0, st, ctx->d_hb_keys[from], ctx->d_hb_pos[from], ctx->d_hb_keys[to],
+                               ctx->d_hb_pos[to], m, pass * 8u, ctx->d_hb_table, n_tiles);
+            HIP_TRY(hipGetLastError());
+        }
+        TopologyTables tt;
+        tt.keys = ctx->d_hb_keys[0];
+        tt.pos = ctx->d_hb_pos[0];
+        tt.tree_surf = ctx->d_hb_tree_surf;
+        tt.surf_type = ctx->dsc.surf_type;
+        tt.nodes = const_cast<BvhNode *>(ctx->dsc.bvh_nodes);
+        tt.leaf = const_cast<BvhLeafPrim *>(ctx->dsc.bvh_leaf);
+        tt.leaf_parent = ctx->d_leaf_parent;
+        tt.order = ctx->d_hb_order;
+        tt.levels = ctx->d_levels;
+        tt.level_count = bt.level_count;
+        tt.m = m;
+        const uint32_t deepest = hierarchy_max_level(m);
+        /* a level's size is the device's to know: the grid is sized by its bound, min(2^level, m / 2) items, and strides over what is there */
+        auto level_grid = [m](uint32_t level) {
+            const uint32_t bound = std::min<uint32_t>(level < 31u ? 1u << level : 0x80000000u, m / 2u);
+            return (std::max(bound, 1u) + BUILD_BLOCK - 1) / BUILD_BLOCK;
+        };
+        for (uint32_t level = 0; level <= deepest; level += 1) /* top down; a kernel boundary between two levels */
+        {
+            hipLaunchKernelGGL(drt_build_topology_kernel, dim3(level_grid(level)), dim3(BUILD_BLOCK), 0, st, tt, ctx->d_hb_items[level & 1u], ctx->d_hb_items[1u - (level & 1u)], level);
+            HIP_TRY(hipGetLastError());
+        }
+        const LeafTables lt = update_leaf_tables(ctx);
+        hipLaunchKernelGGL(drt_bvh_leaf_kernel, dim3((m + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, st, lt, m, ctx->cam_reach);
+        HIP_TRY(hipGetLastError());
+        for (uint32_t level = deepest; level >= 1u; level -= 1) /* deepest first */
+        {
+            hipLaunchKernelGGL(drt_build_refit_kernel, dim3(level_grid(level)), dim3(BUILD_BLOCK), 0, st, tt.nodes, ctx->d_levels, bt.level_count, m, level);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    ctx->hb_timed = false;
+    ctx->hb_ms = 0.0; /* (no kernels: no time) */
+    if (m >= 2u)
+    {
+        HIP_TRY(hipEventRecord(ctx->hb_ev[1], st));
+        ctx->hb_timed = true;
+        /* the host's copy, on its way behind the build: whoever needs it waits for hb_ev[2] (hierarchy_adopt) */
+        HIP_TRY(hipMemcpyAsync(ctx->hb_mirror, ctx->dsc.bvh_nodes, hierarchy_mirror_order(ctx), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctx->hb_mirror + hierarchy_mirror_order(ctx), ctx->d_hb_order, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctx->hb_mirror + hierarchy_mirror_counts(ctx), ctx->d_hb_status + BUILD_BOUND_WORDS * 8, (BUILD_LEVELS + 1) * sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(ctx->hb_ev[2], st));
+        ctx->hb_mirror_pending = true;
+    }
+    ctx->hb_builds += 1;
+    ctx->hb_built_by = 1;
+    ctx->refits = 0;
+    return 0;
+}
+
+extern "C" int drt_rebuild_hierarchy(drt_context *ctx, uint32_t flags)
+{
+    g_last_error.clear();
+    int rc = hierarchy_check(ctx, flags, "drt_rebuild_hierarchy");
+    if (rc) return rc;
+    return hierarchy_enqueue(ctx);
+}
+
+extern "C" int drt_group_rebuild_hierarchy(drt_group *g, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_rebuild_hierarchy: the group is null");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = hierarchy_check(c, flags, "drt_group_rebuild_hierarchy"))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && c->use_bvh && (rc = hierarchy_prepare(c))) return rc; /* what can fail, before any context changes */
+    for (drt_context *c : g->ctx)
+        if (c && (rc = hierarchy_enqueue(c))) return rc;
+    return 0;
+}
+
+extern "C" int drt_get_hierarchy_report(drt_context *ctx, drt_hierarchy_report *out)
+{
+    g_last_error.clear();
+    if (!ctx || !out) return fail(-1, "drt_get_hierarchy_report: null argument");
+    memset(out, 0, sizeof(*out));
+    if (!ctx->use_bvh) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->hb_timed)
+    {
+        float ms = 0.0f;
+        HIP_TRY(hipEventSynchronize(ctx->hb_ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->hb_ev[0], ctx->hb_ev[1]));
+        ctx->hb_ms = (double)ms;
+        ctx->hb_timed = false;
+    }
+    int rc = hierarchy_adopt(ctx);
+    if (rc) return rc;
+    out->nodes = (uint32_t)ctx->h_nodes.size();
+    out->leaf_surfaces = (uint32_t)ctx->h_order.size();
+    out->depth = ctx->hb_depth;
+    out->device_builds = ctx->hb_builds;
+    out->built_by = ctx->hb_built_by;
+    out->kernel_ms = ctx->hb_ms;
+    return 0;
+}
+
+extern "C" int drt_read_hierarchy(drt_context *ctx, void *nodes, uint32_t n_nodes, uint32_t *leaf_surface, uint32_t n_leaf)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "drt_read_hierarchy: ctx is null");
+    if (!ctx->use_bvh) return fail(-1, "drt_read_hierarchy: the context has no hierarchy (its scene is scanned out of LDS)");
+    if (n_nodes != ctx->h_nodes.size() || n_leaf != ctx->h_order.size())
+        return fail(-1, "drt_read_hierarchy: room for %u nodes and %u leaf slots, the tree has %zu and %zu", n_nodes, n_leaf, ctx->h_nodes.size(), ctx->h_order.size());
+    if (!nodes || (n_leaf > 0 && !leaf_surface)) return fail(-1, "drt_read_hierarchy: null argument");
+    int rc = hierarchy_adopt(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    /* the boxes are the device's business after an update or a device build: the nodes come from there */
+    HIP_TRY(hipMemcpy(nodes, ctx->dsc.bvh_nodes, (size_t)n_nodes * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    if (n_leaf) memcpy(leaf_surface, ctx->h_order.data(), (size_t)n_leaf * sizeof(uint32_t));
     return 0;
 }
 

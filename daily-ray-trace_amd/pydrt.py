@@ -219,6 +219,17 @@ class UpdateReport(C.Structure):
 assert C.sizeof(Surface) == 8 * SURFACE_ROW == 112 and C.sizeof(UpdateReport) == 24
 
 
+class HierarchyReport(C.Structure):
+    """drt_hierarchy_report (include/drt_hip.h). 32 bytes."""
+    _fields_ = [("nodes", C.c_uint32), ("leaf_surfaces", C.c_uint32), ("depth", C.c_uint32), ("device_builds", C.c_uint32),
+                ("built_by", C.c_uint32), ("pad", C.c_uint32), ("kernel_ms", C.c_double)]
+
+
+# a BvhNode (csrc/drt_kernels.h): the two children's f32 boxes, the traversal's references to them, and their kinds. 64 bytes.
+BVH_NODE = np.dtype([("lo", "<f4", (2, 3)), ("hi", "<f4", (2, 3)), ("child", "<i4", (2,)), ("count", "<i4", (2,))])
+assert C.sizeof(HierarchyReport) == 32 and BVH_NODE.itemsize == 64
+
+
 def surface_rows(bundle_or_surfaces):
     """[n][14] float64: the bytes of the scene's drt_surface records viewed as doubles (word 0 holds type and material, so it is
     no number to compute with). Takes a SceneBundle or a ctypes Surface array; a copy."""
@@ -621,6 +632,11 @@ def hip_lib():
             L.drt_group_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
             L.drt_group_update_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
             L.drt_group_reset_film.argtypes = [C.c_void_p]
+        if hasattr(L, "drt_rebuild_hierarchy"):
+            L.drt_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
+            L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
+            L.drt_get_hierarchy_report.argtypes = [C.c_void_p, C.POINTER(HierarchyReport)]
+            L.drt_read_hierarchy.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
         L.drt_selftest_arith.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -651,7 +667,8 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_cast_rays", "drt_test_visibility", "drt_cast_pixels", "drt_group_cast_rays", "drt_group_test_visibility",
                "drt_group_cast_pixels", "drt_bind_rays", "drt_group_bind_rays",
                "drt_set_camera", "drt_update_surfaces", "drt_get_update_report", "drt_group_set_camera", "drt_group_update_surfaces",
-               "drt_group_reset_film"]
+               "drt_group_reset_film",
+               "drt_rebuild_hierarchy", "drt_group_rebuild_hierarchy", "drt_get_hierarchy_report", "drt_read_hierarchy"]
 
 
 def _check(rc, what):
@@ -939,6 +956,26 @@ class Renderer:
         _check(self.L.drt_get_update_report(self.ctx, C.byref(r)), "drt_get_update_report")
         return {n: getattr(r, n) for n, _ in r._fields_}
 
+    def rebuild_hierarchy(self):
+        """drt_rebuild_hierarchy: the hierarchy built anew on the device from the context's current surfaces, enqueued on the context's
+        stream without waiting. No result changes by a bit; needs no empty film; nothing happens in a context without the hierarchy."""
+        _check(self.L.drt_rebuild_hierarchy(self.ctx, 0), "drt_rebuild_hierarchy")
+
+    def hierarchy_report(self):
+        """drt_get_hierarchy_report: {"nodes", "leaf_surfaces", "depth", "device_builds", "built_by", "kernel_ms"}"""
+        r = HierarchyReport()
+        _check(self.L.drt_get_hierarchy_report(self.ctx, C.byref(r)), "drt_get_hierarchy_report")
+        return {n: getattr(r, n) for n, _ in r._fields_ if n != "pad"}
+
+    def read_hierarchy(self):
+        """drt_read_hierarchy: (nodes, leaf_surface) -- the tree in use as a BVH_NODE structured array, and the surface index in every
+        leaf slot (uint32)"""
+        rep = self.hierarchy_report()
+        nodes = np.zeros(rep["nodes"], dtype=BVH_NODE)
+        leaf = np.zeros(rep["leaf_surfaces"], dtype=np.uint32)
+        _check(self.L.drt_read_hierarchy(self.ctx, nodes.ctypes.data, len(nodes), _ptr(leaf, C.c_uint32), len(leaf)), "drt_read_hierarchy")
+        return nodes, leaf
+
     def read_sample_counts(self):
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
@@ -1088,6 +1125,10 @@ class Group:
             raise ValueError("Group.update_surfaces: a Surface array or numpy rows (a group takes host pointers only)")
         ptr, n, flags, _keep = _update_args(surfaces, 0)
         _check(self.L.drt_group_update_surfaces(self.g, ptr, first, n, flags | (SURFACES_REBUILD if rebuild else 0)), "drt_group_update_surfaces")
+
+    def rebuild_hierarchy(self):
+        """drt_group_rebuild_hierarchy: as Renderer.rebuild_hierarchy, every context from its own device copy of the surfaces"""
+        _check(self.L.drt_group_rebuild_hierarchy(self.g, 0), "drt_group_rebuild_hierarchy")
 
     def close(self):
         if self.g:

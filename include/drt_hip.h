@@ -671,6 +671,43 @@ int drt_selftest_unit(int device, int func, const double *in, uint32_t in_stride
  * list that holds a Fresnel function. Synchronises. */
 int drt_selftest_material(drt_context *ctx, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
 
+/*
+ * Device hierarchy builds: the tree of a live DRT_PATH_BVH context built anew on the device, from the context's own device copy of its
+ * surfaces -- what a caller whose surfaces arrive in device memory (DRT_SURFACES_DEVICE) can do about a tree that refits have left the
+ * wrong shape for (drt_update_report.refits_since_build), where DRT_SURFACES_REBUILD needs host surfaces and stops the stream.
+ * DESIGN.md section 5h.
+ *
+ * drt_rebuild_hierarchy enqueues the work on the context's stream and returns without waiting for it: no stream synchronisation, no
+ * blocking copy, and no allocation after the first call (drt_destroy frees the temporaries). What was enqueued before stays ordered
+ * before it. The tree is a Morton-ordered one over the surfaces' current boxes, one surface per leaf, written into the allocations the
+ * context has; its shape is a deterministic function of the boxes (csrc/drt_build_rule.h, restated in tests/hierarchy_rule.py) and it
+ * is never deeper than the traversal stack, by construction.
+ *
+ * No result changes: the hierarchy only prunes, so films, hit logs, the counting statistics and RNG draw counts are bit for bit what
+ * they were. The call needs no empty film and may come between two drt_render calls of one film. It is not an update:
+ * drt_update_report.updates does not move, refits_since_build goes to 0, features and mattes that have been read stay readable, and a
+ * pending 2^27 extent violation of a device-mode update stays pending. In a context without the hierarchy the call returns 0 and
+ * changes nothing. `flags` must be 0. Refits (drt_update_surfaces, drt_set_camera), DRT_SURFACES_REBUILD and further device builds
+ * work afterwards in any order; the first of them, or drt_read_hierarchy, waits for the host's copy of the tree's links to arrive.
+ */
+int drt_rebuild_hierarchy(drt_context *ctx, uint32_t flags);
+/* Every context from its own device copy. Same bits for any device list. */
+int drt_group_rebuild_hierarchy(drt_group *g, uint32_t flags);
+typedef struct drt_hierarchy_report
+{
+    uint32_t nodes, leaf_surfaces; /* BvhNode records and leaf slots (0, 0 without DRT_PATH_BVH) */
+    uint32_t depth;                /* levels, as drt_bvh_stats counts them */
+    uint32_t device_builds;        /* successful drt_rebuild_hierarchy calls that built a tree */
+    uint32_t built_by;             /* who made the tree in use: 0 the host (drt_create, DRT_SURFACES_REBUILD), 1 the device */
+    uint32_t pad;
+    double   kernel_ms;            /* HIP-event time of the last device build's kernels (0: there was none) */
+} drt_hierarchy_report;            /* 32 bytes */
+/* Waits for the last device build. */
+int drt_get_hierarchy_report(drt_context *ctx, drt_hierarchy_report *out);
+/* The tree in use: `nodes` takes n_nodes records of 64 bytes (csrc/drt_kernels.h, BvhNode: float lo[2][3], hi[2][3]; int32 child[2],
+ * count[2]), leaf_surface the surface index of every leaf slot. n_nodes and n_leaf must be the report's counts. Synchronises. */
+int drt_read_hierarchy(drt_context *ctx, void *nodes, uint32_t n_nodes, uint32_t *leaf_surface, uint32_t n_leaf);
+
 #ifdef __cplusplus
 }
 #endif

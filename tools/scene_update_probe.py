@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
-"""What a scene update costs (drt_update_surfaces, drt_set_camera), beside the only thing there was before it:
+"""What a scene update costs (drt_update_surfaces, drt_set_camera, drt_rebuild_hierarchy), beside the only thing there was before it:
 drt_destroy + drt_create. One process, one MI355X.
 
     python3 tools/scene_update_probe.py cost  [--scene headline | spheres:N] [--size 1024] [--spp 256] [--depth 8] [--reps 5]
     python3 tools/scene_update_probe.py refit [--spheres 10000] [--size 1024] [--spp 4] [--depth 8] [--frac 0.01]
+    python3 tools/scene_update_probe.py build [--spheres 10000] [--size 4096] [--spp 64] [--reps 5]
+    python3 tools/scene_update_probe.py drift [--spheres 10000] [--size 1024] [--spp 4] [--frames 8] [--frac 0.05] [--every 0]
 
 cost:  on a resident context (DRT_BATCH_RESIDENT) the medians over --reps of: destroy + create (wall), the host build of the tree by
        itself (drt_bvh_stats, which runs the builder and nothing else; 0 for a scene that fits the LDS), a whole-scene host-mode
        update (wall until the stream is idle, and the kernels' HIP-event time), the same in device mode, the same with
        DRT_SURFACES_REBUILD, and a drt_set_camera.
 refit: the trace-stage time of the frame after a refit of spheres displaced by --frac of the scene's size (40), against the same
-       scene in a fresh context and against the refit context after DRT_SURFACES_REBUILD.
+       scene in a fresh context, against the refit context after DRT_SURFACES_REBUILD, and against it after a device build
+       (drt_rebuild_hierarchy).
+build: what a device build costs beside DRT_SURFACES_REBUILD of the same scene on the same context: medians over --reps of the
+       kernels' HIP-event time and of the wall time of the call plus drt_synchronize, and the device-mode update a build follows.
+drift: what a device-mode caller sees: --frames device-mode updates, each displacing every sphere by --frac of the scene's size from
+       where it began, the trace stage of every frame, with a device build after every --every updates (0: never).
 Each prints its lines and one JSON line."""
 import argparse
 import ctypes as C
@@ -135,8 +142,95 @@ def refit(a):
     r.update_surfaces(moved, rebuild=True)
     out["rebuilt"] = frame(r)
     r.close()
-    for k in ("fresh", "refit", "rebuilt"):
+    r = pydrt.Renderer(bundle, params)
+    r.update_surfaces(moved)
+    r.rebuild_hierarchy()
+    out["device_built"] = frame(r)
+    out["device_built"]["depth"] = r.hierarchy_report()["depth"]
+    r.close()
+    out["device_over_host_trace"] = out["device_built"]["trace_ms"] / out["rebuilt"]["trace_ms"] if out["rebuilt"]["trace_ms"] > 0.0 else 0.0
+    for k in ("fresh", "refit", "rebuilt", "device_built"):
         print("%-8s trace %.3f ms, shade + film %.3f ms, %d launches redone" % (k, out[k]["trace_ms"], out[k]["shade_ms"], out[k]["redone_launches"]))
+    print(json.dumps(out))
+
+
+def build(a):
+    bundle = pydrt.synthetic_sphere_scene(a.spheres, a.size, a.size)
+    params = pydrt.make_params(a.size, a.size, spp=a.spp, max_depth=a.depth, seed=1, batch_spp=pydrt.BATCH_RESIDENT)
+    rows = pydrt.surface_rows(bundle)
+    moved = rows.copy()
+    moved[:, 1:4] += 0.01
+    import torch
+    dev = [torch.from_numpy(moved).to("cuda:0"), torch.from_numpy(rows).to("cuda:0")]
+    torch.cuda.synchronize()
+    r = pydrt.Renderer(bundle, params)
+    r.render(0, 1)  # a context that has rendered, as a live one has
+    r.reset_film()
+    out = {"spheres": a.spheres, "size": a.size, "spp": a.spp, "reps": a.reps}
+
+    def device_build(k):
+        r.rebuild_hierarchy()
+        r.synchronize()
+
+    def device_update(k):
+        r.update_surfaces(dev[k % 2])
+        r.synchronize()
+
+    def host_rebuild(k):
+        r.update_surfaces(moved if k % 2 == 0 else rows, rebuild=True)
+        r.synchronize()
+
+    def call_only(k):
+        r.rebuild_hierarchy()
+
+    for name, leg, kernel in (("device_update", device_update, lambda: r.update_report()["kernel_ms"]),
+                              ("device_build", device_build, lambda: r.hierarchy_report()["kernel_ms"]),
+                              ("host_rebuild", host_rebuild, lambda: r.update_report()["kernel_ms"])):
+        leg(0)
+        leg(1)  # the first call makes the temporaries: not what a frame pays
+        walls, kernels = [], []
+        for k in range(a.reps):
+            walls.append(wall_ms(lambda: leg(k))[0])
+            kernels.append(kernel())
+        out[name + "_wall_ms"], out[name + "_kernel_ms"] = median(walls), median(kernels)
+    calls = []
+    for k in range(a.reps):  # the call by itself: it enqueues and returns
+        calls.append(wall_ms(lambda: call_only(k))[0])
+        r.synchronize()
+    out["device_build_call_ms"] = median(calls)
+    rep = r.hierarchy_report()
+    out["nodes"], out["depth"] = rep["nodes"], rep["depth"]
+    out["device_below_host"] = out["device_build_wall_ms"] < out["host_rebuild_wall_ms"]
+    r.close()
+    for k, v in out.items():
+        print("%-28s %s" % (k, ("%.3f" % v) if isinstance(v, float) else v))
+    print(json.dumps(out))
+
+
+def drift(a):
+    import torch
+    bundle = pydrt.synthetic_sphere_scene(a.spheres, a.size, a.size)
+    params = pydrt.make_params(a.size, a.size, spp=a.spp, max_depth=a.depth, seed=1, batch_spp=pydrt.BATCH_RESIDENT)
+    rows = pydrt.surface_rows(bundle)
+    rng = np.random.default_rng(1)
+    step = rng.uniform(-1.0, 1.0, (a.spheres, 3)) * (a.frac * 40.0)
+    r = pydrt.Renderer(bundle, params)
+    r.render(0, a.spp)
+    r.synchronize()
+    out = {"spheres": a.spheres, "size": a.size, "spp": a.spp, "frac": a.frac, "every": a.every, "frames": []}
+    for k in range(1, a.frames + 1):
+        moved = rows.copy()
+        moved[:a.spheres, 1:4] += step * k
+        r.reset_film()
+        r.update_surfaces(torch.from_numpy(moved).to("cuda:0"))
+        built = a.every > 0 and r.update_report()["refits_since_build"] >= a.every
+        if built:
+            r.rebuild_hierarchy()
+        r.render(0, a.spp)
+        st = r.stats()
+        out["frames"].append({"frame": k, "built": built, "trace_ms": st.trace_ms})
+        print("frame %2d  %s  trace %.3f ms" % (k, "build" if built else "refit", st.trace_ms))
+    r.close()
     print(json.dumps(out))
 
 
@@ -155,8 +249,22 @@ def main():
     f.add_argument("--spp", type=int, default=4)
     f.add_argument("--depth", type=int, default=8)
     f.add_argument("--frac", type=float, default=0.01)
+    b = sub.add_parser("build")
+    b.add_argument("--spheres", type=int, default=10000)
+    b.add_argument("--size", type=int, default=4096)
+    b.add_argument("--spp", type=int, default=64)
+    b.add_argument("--depth", type=int, default=8)
+    b.add_argument("--reps", type=int, default=5)
+    d = sub.add_parser("drift")
+    d.add_argument("--spheres", type=int, default=10000)
+    d.add_argument("--size", type=int, default=1024)
+    d.add_argument("--spp", type=int, default=4)
+    d.add_argument("--depth", type=int, default=8)
+    d.add_argument("--frames", type=int, default=8)
+    d.add_argument("--frac", type=float, default=0.05)
+    d.add_argument("--every", type=int, default=0)
     a = ap.parse_args()
-    cost(a) if a.what == "cost" else refit(a)
+    {"cost": cost, "refit": refit, "build": build, "drift": drift}[a.what](a)
 
 
 if __name__ == "__main__":
