@@ -4231,6 +4231,55 @@ static int hierarchy_check(const drt_context *ctx, uint32_t flags, const char *n
     return 0;
 }
 
+/* a level's size is the device's to know: the grid is sized by its bound, min(2^level, m / 2) items, and strides over what is there */
+static uint32_t hierarchy_level_grid(uint32_t m, uint32_t level)
+{
+    const uint32_t bound = std::min<uint32_t>(level < 31u ? 1u << level : 0x80000000u, m / 2u);
+    return (std::max(bound, 1u) + BUILD_BLOCK - 1) / BUILD_BLOCK;
+}
+
+/* The three stages of a build that need no scene, each on buffers it is given: hierarchy_enqueue runs them on the context's, the
+ * selftests (drt_selftest_build_sort, drt_selftest_build_topology) on scratch of their own. Nothing else launches these kernels. */
+
+/* the status words and the root item: before the bounds pass and before the topology */
+static int hierarchy_enqueue_init(hipStream_t st, const BuildTables &bt, uint4 *items0)
+{
+    hipLaunchKernelGGL(drt_build_init_kernel, dim3(1), dim3(64), 0, st, bt, items0);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* the sort of m (key, payload) pairs in keys[0], pos[0], in place: keys[1], pos[1] ([m] each) and table ([SORT_DIGITS][tiles]) are its
+ * temporaries, and the result ends where it began because SORT_PASSES is even */
+static int hierarchy_enqueue_sort(hipStream_t st, uint64_t *const keys[2], uint32_t *const pos[2], uint32_t *table, uint32_t m)
+{
+    const uint32_t n_tiles = (m + SORT_TILE - 1) / SORT_TILE;
+    for (uint32_t pass = 0; pass < SORT_PASSES; pass += 1)
+    {
+        const int from = (int)(pass & 1u), to = 1 - from;
+        hipLaunchKernelGGL(drt_build_count_kernel, dim3(n_tiles), dim3(BUILD_BLOCK), 0, st, keys[from], m, pass * 8u, table, n_tiles);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(drt_build_scan_kernel, dim3(1), dim3(SORT_DIGITS), 0, st, table, n_tiles);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(drt_build_scatter_kernel, dim3(n_tiles), dim3(BUILD_BLOCK), 0, st, keys[from], pos[from], keys[to], pos[to], m, pass * 8u, table, n_tiles);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+/* the links of the tree over tt.m >= 2 sorted keys, level by level: tt.level_count and items[0] as hierarchy_enqueue_init left them,
+ * items[0] and items[1] ([m / 2 + 1] each) the lists of two neighbouring levels in turn */
+static int hierarchy_enqueue_topology(hipStream_t st, const TopologyTables &tt, uint4 *const items[2])
+{
+    const uint32_t deepest = hierarchy_max_level(tt.m);
+    for (uint32_t level = 0; level <= deepest; level += 1) /* top down; a kernel boundary between two levels */
+    {
+        hipLaunchKernelGGL(drt_build_topology_kernel, dim3(hierarchy_level_grid(tt.m, level)), dim3(BUILD_BLOCK), 0, st, tt, items[level & 1u], items[1u - (level & 1u)], level);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 static int hierarchy_enqueue(drt_context *ctx)
 {
     if (!ctx->use_bvh) return 0; /* nothing to build: as DRT_SURFACES_REBUILD there */
@@ -4243,30 +4292,19 @@ static int hierarchy_enqueue(drt_context *ctx)
     {
         HIP_TRY(hipEventRecord(ctx->hb_ev[0], st));
         if (!ctx->boxes_valid && (rc = update_enqueue_derive(ctx))) return rc; /* no update yet: the boxes and the extent word are not made */
-        const uint32_t grid = (m + BUILD_BLOCK - 1) / BUILD_BLOCK, n_tiles = (m + SORT_TILE - 1) / SORT_TILE;
+        const uint32_t grid = (m + BUILD_BLOCK - 1) / BUILD_BLOCK;
         BuildTables bt;
         bt.boxes = ctx->d_boxes;
         bt.tree_surf = ctx->d_hb_tree_surf;
         bt.bounds = (unsigned long long *)ctx->d_hb_status;
         bt.level_count = (uint32_t *)(ctx->d_hb_status + BUILD_BOUND_WORDS * 8);
         bt.m = m;
-        hipLaunchKernelGGL(drt_build_init_kernel, dim3(1), dim3(64), 0, st, bt, ctx->d_hb_items[0]);
-        HIP_TRY(hipGetLastError());
+        if ((rc = hierarchy_enqueue_init(st, bt, ctx->d_hb_items[0]))) return rc;
         hipLaunchKernelGGL(drt_build_bounds_kernel, dim3(grid), dim3(BUILD_BLOCK), 0, st, bt);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(drt_build_keys_kernel, dim3(grid), dim3(BUILD_BLOCK), 0, st, bt, ctx->d_hb_keys[0], ctx->d_hb_pos[0]);
         HIP_TRY(hipGetLastError());
-        for (uint32_t pass = 0; pass < SORT_PASSES; pass += 1) /* the sorted keys end where they began: SORT_PASSES is even */
-        {
-            const int from = (int)(pass & 1u), to = 1 - from;
-            hipLaunchKernelGGL(drt_build_count_kernel, dim3(n_tiles), dim3(BUILD_BLOCK), 0, st, ctx->d_hb_keys[from], m, pass * 8u, ctx->d_hb_table, n_tiles);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(drt_build_scan_kernel, dim3(1), dim3(SORT_DIGITS), 0, st, ctx->d_hb_table, n_tiles);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(drt_build_scatter_kernel, dim3(n_tiles), dim3(BUILD_BLOCK), 0, st, ctx->d_hb_keys[from], ctx->d_hb_pos[from], ctx->d_hb_keys[to],
-                               ctx->d_hb_pos[to], m, pass * 8u, ctx->d_hb_table, n_tiles);
-            HIP_TRY(hipGetLastError());
-        }
+        if ((rc = hierarchy_enqueue_sort(st, ctx->d_hb_keys, ctx->d_hb_pos, ctx->d_hb_table, m))) return rc;
         TopologyTables tt;
         tt.keys = ctx->d_hb_keys[0];
         tt.pos = ctx->d_hb_pos[0];
@@ -4279,23 +4317,13 @@ static int hierarchy_enqueue(drt_context *ctx)
         tt.levels = ctx->d_levels;
         tt.level_count = bt.level_count;
         tt.m = m;
-        const uint32_t deepest = hierarchy_max_level(m);
-        /* a level's size is the device's to know: the grid is sized by its bound, min(2^level, m / 2) items, and strides over what is there */
-        auto level_grid = [m](uint32_t level) {
-            const uint32_t bound = std::min<uint32_t>(level < 31u ? 1u << level : 0x80000000u, m / 2u);
-            return (std::max(bound, 1u) + BUILD_BLOCK - 1) / BUILD_BLOCK;
-        };
-        for (uint32_t level = 0; level <= deepest; level += 1) /* top down; a kernel boundary between two levels */
-        {
-            hipLaunchKernelGGL(drt_build_topology_kernel, dim3(level_grid(level)), dim3(BUILD_BLOCK), 0, st, tt, ctx->d_hb_items[level & 1u], ctx->d_hb_items[1u - (level & 1u)], level);
-            HIP_TRY(hipGetLastError());
-        }
+        if ((rc = hierarchy_enqueue_topology(st, tt, ctx->d_hb_items))) return rc;
         const LeafTables lt = update_leaf_tables(ctx);
         hipLaunchKernelGGL(drt_bvh_leaf_kernel, dim3((m + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, st, lt, m, ctx->cam_reach);
         HIP_TRY(hipGetLastError());
-        for (uint32_t level = deepest; level >= 1u; level -= 1) /* deepest first */
+        for (uint32_t level = hierarchy_max_level(m); level >= 1u; level -= 1) /* deepest first */
         {
-            hipLaunchKernelGGL(drt_build_refit_kernel, dim3(level_grid(level)), dim3(BUILD_BLOCK), 0, st, tt.nodes, ctx->d_levels, bt.level_count, m, level);
+            hipLaunchKernelGGL(drt_build_refit_kernel, dim3(hierarchy_level_grid(m, level)), dim3(BUILD_BLOCK), 0, st, tt.nodes, ctx->d_levels, bt.level_count, m, level);
             HIP_TRY(hipGetLastError());
         }
     }
@@ -4466,6 +4494,140 @@ extern "C" int drt_selftest_arith(int device, int op, const double *a, const dou
     (void)hipFree(da);
     (void)hipFree(db);
     (void)hipFree(dout);
+    return 0;
+}
+
+/* device scratch of a selftest, freed however the call ends */
+struct SelftestScratch
+{
+    std::vector<void *> held;
+    ~SelftestScratch()
+    {
+        for (void *p : held) (void)hipFree(p);
+    }
+    template <typename T> hipError_t get(T **p, size_t n)
+    {
+        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) held.push_back(*p);
+        return e;
+    }
+};
+
+#define BUILD_SELFTEST_MAX (1u << 24) /* elements: far above any test, far below where an index would wrap */
+#define BUILD_SELFTEST_GUARD 64u      /* elements in front of and behind every array the sort writes */
+
+extern "C" int drt_selftest_build_sort(int device, const uint64_t *keys, uint32_t m, uint64_t *keys_out, uint32_t *pos_out)
+{
+    g_last_error.clear();
+    if (!keys || !keys_out || !pos_out) return fail(-1, "drt_selftest_build_sort: null argument");
+    if (m == 0u || m > BUILD_SELFTEST_MAX) return fail(-1, "drt_selftest_build_sort: %u keys, not in 1..%u", m, BUILD_SELFTEST_MAX);
+    for (uint32_t k = 0; k < m; k += 1)
+        if (keys[k] > BUILD_KEY_UNBOUNDED) return fail(-1, "drt_selftest_build_sort: key %u has bit 63 set", k);
+    HIP_TRY(hipSetDevice(device));
+    /* both halves of the double buffer between guard words: a scatter outside [0, m) is reported, not left to chance */
+    const size_t G = BUILD_SELFTEST_GUARD, room = (size_t)m + 2 * G;
+    const uint64_t key_guard = 0xA5A5A5A5A5A5A5A5ull;
+    const uint32_t pos_guard = 0xA5A5A5A5u;
+    std::vector<uint64_t> hk(room, key_guard);
+    std::vector<uint32_t> hp(room, pos_guard);
+    SelftestScratch scratch;
+    uint64_t *dk[2] = {nullptr, nullptr}, *d_keys[2];
+    uint32_t *dp[2] = {nullptr, nullptr}, *d_pos[2], *d_table = nullptr;
+    for (int k = 0; k < 2; k += 1)
+    {
+        HIP_TRY(scratch.get(&dk[k], room));
+        HIP_TRY(scratch.get(&dp[k], room));
+        HIP_TRY(hipMemcpy(dk[k], hk.data(), room * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dp[k], hp.data(), room * sizeof(uint32_t), hipMemcpyHostToDevice));
+        d_keys[k] = dk[k] + G;
+        d_pos[k] = dp[k] + G;
+    }
+    HIP_TRY(scratch.get(&d_table, (size_t)SORT_DIGITS * ((m + SORT_TILE - 1) / SORT_TILE)));
+    for (uint32_t k = 0; k < m; k += 1) hp[G + k] = k; /* the payload drt_build_keys_kernel writes: the position */
+    HIP_TRY(hipMemcpy(d_keys[0], keys, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pos[0], hp.data() + G, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
+    int rc = hierarchy_enqueue_sort(0, d_keys, d_pos, d_table, m);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k < 2; k += 1)
+    {
+        HIP_TRY(hipMemcpy(hk.data(), dk[k], room * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(hp.data(), dp[k], room * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (size_t g = 0; g < G; g += 1)
+            if (hk[g] != key_guard || hk[G + m + g] != key_guard || hp[g] != pos_guard || hp[G + m + g] != pos_guard)
+                return fail(-3, "drt_selftest_build_sort: buffer %d was written outside its %u elements", k, m);
+    }
+    HIP_TRY(hipMemcpy(keys_out, d_keys[0], (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos_out, d_pos[0], (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_selftest_build_topology(int device, const uint64_t *sorted_keys, uint32_t m, int32_t *child, int32_t *count, uint32_t *level_count,
+                                           uint32_t *levels_out)
+{
+    g_last_error.clear();
+    if (!sorted_keys || !child || !count || !level_count || (m > 2u && !levels_out)) return fail(-1, "drt_selftest_build_topology: null argument");
+    if (m < 2u || m > BUILD_SELFTEST_MAX) return fail(-1, "drt_selftest_build_topology: %u keys, not in 2..%u (a build launches nothing below 2)", m, BUILD_SELFTEST_MAX);
+    for (uint32_t k = 0; k < m; k += 1)
+        if (sorted_keys[k] > BUILD_KEY_UNBOUNDED || (k > 0u && sorted_keys[k - 1] > sorted_keys[k]))
+            return fail(-1, "drt_selftest_build_topology: key %u is out of order or has bit 63 set", k);
+    HIP_TRY(hipSetDevice(device));
+    SelftestScratch scratch;
+    uint64_t *d_keys = nullptr;
+    uint32_t *d_same = nullptr, *d_type = nullptr, *d_leaf_parent = nullptr, *d_order = nullptr;
+    BvhNode *d_nodes = nullptr;
+    BvhLeafPrim *d_leaf = nullptr;
+    uint2 *d_levels = nullptr;
+    uint4 *d_items[2] = {nullptr, nullptr};
+    unsigned char *d_status = nullptr;
+    HIP_TRY(scratch.get(&d_keys, m));
+    HIP_TRY(scratch.get(&d_same, m));
+    HIP_TRY(scratch.get(&d_type, m));
+    HIP_TRY(scratch.get(&d_leaf_parent, m));
+    HIP_TRY(scratch.get(&d_order, m));
+    HIP_TRY(scratch.get(&d_nodes, (size_t)m - 1));
+    HIP_TRY(scratch.get(&d_leaf, m));
+    HIP_TRY(scratch.get(&d_levels, (size_t)m - 2));
+    for (int k = 0; k < 2; k += 1) HIP_TRY(scratch.get(&d_items[k], (size_t)m / 2 + 1)); /* as hierarchy_prepare sizes them */
+    HIP_TRY(scratch.get(&d_status, BUILD_STATUS_BYTES));
+    std::vector<uint32_t> same(m), type(m, (uint32_t)DRT_GEO_SPHERE);
+    for (uint32_t k = 0; k < m; k += 1) same[k] = k; /* tree_surf and pos are identities: slot j holds surface j */
+    HIP_TRY(hipMemcpy(d_keys, sorted_keys, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_same, same.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_type, type.data(), (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_nodes, 0xFF, ((size_t)m - 1) * sizeof(BvhNode)));
+    HIP_TRY(hipMemset(d_levels, 0xFF, std::max<size_t>((size_t)m - 2, 1) * sizeof(uint2)));
+    BuildTables bt;
+    bt.boxes = nullptr; /* no bounds pass, no keys pass: nothing reads it */
+    bt.tree_surf = d_same;
+    bt.bounds = (unsigned long long *)d_status;
+    bt.level_count = (uint32_t *)(d_status + BUILD_BOUND_WORDS * 8);
+    bt.m = m;
+    TopologyTables tt;
+    tt.keys = d_keys;
+    tt.pos = d_same;
+    tt.tree_surf = d_same;
+    tt.surf_type = d_type;
+    tt.nodes = d_nodes;
+    tt.leaf = d_leaf;
+    tt.leaf_parent = d_leaf_parent;
+    tt.order = d_order;
+    tt.levels = d_levels;
+    tt.level_count = bt.level_count;
+    tt.m = m;
+    int rc = hierarchy_enqueue_init(0, bt, d_items[0]);
+    if (rc || (rc = hierarchy_enqueue_topology(0, tt, d_items))) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<BvhNode> nodes((size_t)m - 1);
+    HIP_TRY(hipMemcpy(nodes.data(), d_nodes, nodes.size() * sizeof(BvhNode), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < nodes.size(); i += 1)
+        for (int c = 0; c < 2; c += 1)
+        {
+            child[2 * i + c] = nodes[i].child[c];
+            count[2 * i + c] = nodes[i].count[c];
+        }
+    HIP_TRY(hipMemcpy(level_count, bt.level_count, (BUILD_LEVELS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (m > 2u) HIP_TRY(hipMemcpy(levels_out, d_levels, ((size_t)m - 2) * sizeof(uint2), hipMemcpyDeviceToHost));
     return 0;
 }
 

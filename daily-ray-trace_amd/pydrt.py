@@ -649,6 +649,10 @@ def hip_lib():
                                         C.c_uint64]
         L.drt_selftest_material.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
                                             C.c_uint64]
+        if hasattr(L, "drt_selftest_build_sort"):  # (as drt_selftest_path_ids above)
+            u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+            L.drt_selftest_build_sort.argtypes = [C.c_int, u64p, C.c_uint32, u64p, u32p]
+            L.drt_selftest_build_topology.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), u32p, u32p]
         _hip = L
     return _hip
 
@@ -657,6 +661,7 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_render", "drt_synchronize", "drt_reset_film", "drt_film_device_ptrs", "drt_read_film", "drt_write_film",
                "drt_read_xyz", "drt_read_bgra", "drt_read_hit_indices", "drt_get_stats", "drt_batch_spp", "drt_render_tile", "drt_selftest_arith",
                "drt_selftest_unit", "drt_selftest_material", "drt_selftest_path_ids", "drt_bvh_stats",
+               "drt_selftest_build_sort", "drt_selftest_build_topology",
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
@@ -1227,6 +1232,40 @@ def selftest_unit(func, records, device=0):
     out = np.zeros((n, m), dtype=np.float64)
     _check(hip_lib().drt_selftest_unit(device, func, _ptr(rec, C.c_double), k, _ptr(out, C.c_double), m, n), "drt_selftest_unit")
     return out
+
+
+BUILD_LEVEL_COUNTS = 33  # BUILD_LEVELS + 1 (csrc/drt_build_kernels.h)
+
+
+def selftest_build_sort(keys, keys_out=None, pos_out=None, device=0):
+    """The radix sort of a device hierarchy build over `keys` (uint64, below 2^63), through the build's own enqueue code. Returns
+    (keys_out, pos_out): the key and the position that end in every slot. The two may be given, as contiguous views of the caller's
+    (a test puts guard words around them)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    m = keys.size
+    keys_out = np.zeros(m, dtype=np.uint64) if keys_out is None else keys_out
+    pos_out = np.zeros(m, dtype=np.uint32) if pos_out is None else pos_out
+    for a, t in ((keys_out, np.uint64), (pos_out, np.uint32)):
+        if a.dtype != t or a.shape != (m,) or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+            raise ValueError("selftest_build_sort: an output array is not a contiguous %s[%d]" % (np.dtype(t).name, m))
+    _check(hip_lib().drt_selftest_build_sort(device, _ptr(keys, C.c_uint64), m, _ptr(keys_out, C.c_uint64), _ptr(pos_out, C.c_uint32)),
+           "drt_selftest_build_sort")
+    return keys_out, pos_out
+
+
+def selftest_build_topology(sorted_keys, device=0):
+    """The topology passes of a device hierarchy build over ascending keys, through the build's own enqueue code. Returns (child
+    [m - 1][2] int32, count [m - 1][2] int32, the 33 level counts uint32, the level table [m - 2][2] uint32: (inner node, parent * 2 +
+    child slot), the deepest level first)."""
+    keys = np.ascontiguousarray(sorted_keys, dtype=np.uint64)
+    m = keys.size
+    child, count = np.zeros((max(m - 1, 1), 2), dtype=np.int32), np.zeros((max(m - 1, 1), 2), dtype=np.int32)
+    level_count = np.zeros(BUILD_LEVEL_COUNTS, dtype=np.uint32)
+    levels = np.zeros((max(m - 2, 0), 2), dtype=np.uint32)
+    _check(hip_lib().drt_selftest_build_topology(device, _ptr(keys, C.c_uint64), m, _ptr(child, C.c_int32), _ptr(count, C.c_int32),
+                                                 _ptr(level_count, C.c_uint32), _ptr(levels, C.c_uint32) if m > 2 else None),
+           "drt_selftest_build_topology")
+    return child, count, level_count, levels
 
 
 # ------------------------------------------------------------------------------------------------

@@ -671,6 +671,23 @@ int drt_selftest_unit(int device, int func, const double *in, uint32_t in_stride
  * list that holds a Fresnel function. Synchronises. */
 int drt_selftest_material(drt_context *ctx, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
 
+/* Build-pass self-tests: two stages of a device hierarchy build (drt_rebuild_hierarchy below; csrc/drt_build_kernels.h) on arrays the
+ * caller supplies, without a scene. Both go through the very enqueue helpers drt_rebuild_hierarchy goes through (the launch loops,
+ * grids and buffer roles are the product's; only the buffers are scratch) on the null stream, and synchronise.
+ *
+ * drt_selftest_build_sort: the eight count / scan / scatter passes over m keys (1 <= m <= 2^24, every key below 2^63; the payload is
+ * the position 0 .. m - 1, as the keys kernel writes it). keys_out[j] and pos_out[j] are the key and the position that end in slot j:
+ * a stable sort, so pos_out is numpy's argsort(kind="stable"). Both halves of the sort's double buffer lie between guard words on the
+ * device; the call fails (-3) if one of them changed. */
+int drt_selftest_build_sort(int device, const uint64_t *keys, uint32_t m, uint64_t *keys_out, uint32_t *pos_out);
+/* drt_selftest_build_topology: the status kernel and the level-by-level topology launches over m ascending keys (2 <= m <= 2^24; a
+ * build launches nothing below 2), with nodes, leaves, leaf parents and leaf order of its own; tree_surf and pos are identities and
+ * every surface is a sphere. child and count take the [m - 1][2] links of the nodes (csrc/drt_build_rule.h: step 6-7 of DESIGN.md
+ * 5h), level_count the 33 level counts (inner nodes per depth, the root's 1 first), levels_out the level table: [m - 2] pairs
+ * (inner node, parent * 2 + child slot), the deepest level first, in any order within a level. Keys out of order are refused. */
+int drt_selftest_build_topology(int device, const uint64_t *sorted_keys, uint32_t m, int32_t *child, int32_t *count, uint32_t *level_count,
+                                uint32_t *levels_out);
+
 /*
  * Device hierarchy builds: the tree of a live DRT_PATH_BVH context built anew on the device, from the context's own device copy of its
  * surfaces -- what a caller whose surfaces arrive in device memory (DRT_SURFACES_DEVICE) can do about a tree that refits have left the

@@ -184,3 +184,16 @@ def check_tree(child, count, m):
     assert (seen == 1).all()
     assert visited == list(range(n)), "not in pre-order"
     return levels, ranges
+
+
+def level_entries(child, count):
+    """the inner nodes below the root by depth, from the links of a tree check_tree has passed: entries[d] is the sorted list of
+    (node, parent * 2 + child slot) of the inner nodes at depth d (entries[0] is empty: the root has no parent). What
+    drt_build_topology_kernel's level table and level counts must hold."""
+    entries, level = [[]], [0]
+    while level:
+        below = [(int(child[i, c]), 2 * i + c) for i in level for c in range(2) if count[i, c] == 0]
+        if below:
+            entries.append(sorted(below))
+        level = [node for node, _ in below]
+    return entries

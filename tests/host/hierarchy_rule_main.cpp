@@ -2,7 +2,8 @@
  * The hierarchy rule's own text (csrc/drt_build_rule.h) on the host: tests/test_hierarchy_cpu.py builds this with the address and
  * undefined-behaviour sanitizers and compares what it prints with tests/hierarchy_rule.py. The kernels compile the same header.
  *
- * stdin:  m, then m lines "bounded cx cy cz": whether the box of tree position k is bounded, and its centre (hexadecimal doubles)
+ * stdin:  m, then m lines "bounded cx cy cz": whether the box of tree position k is bounded, and its centre (hexadecimal doubles);
+ *         or the word "keys", m, then m keys in decimal: the keys themselves, for key sets no scene gives (tests/build_pass_cases.py)
  * stdout: "levels L", then "key k" per position, "slot position" per leaf slot in order, "node child0 child1 count0 count1" per node
  */
 #include "drt_build_rule.h"
@@ -10,18 +11,24 @@
 #include <algorithm>
 #include <cinttypes>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 int main()
 {
     uint32_t m = 0;
-    if (scanf("%" SCNu32, &m) != 1) return 2;
+    char word[32];
+    if (scanf("%31s", word) != 1) return 2;
+    const bool raw = strcmp(word, "keys") == 0;
+    if ((raw ? scanf("%" SCNu32, &m) : sscanf(word, "%" SCNu32, &m)) != 1) return 2;
     std::vector<uint64_t> key(m);
     std::vector<double> c(3 * (size_t)m);
     std::vector<uint32_t> bounded(m);
     double clo[3] = {0.0, 0.0, 0.0}, chi[3] = {0.0, 0.0, 0.0};
     bool any = false;
-    for (uint32_t k = 0; k < m; k += 1)
+    for (uint32_t k = 0; raw && k < m; k += 1)
+        if (scanf("%" SCNu64, &key[k]) != 1 || key[k] > BUILD_KEY_UNBOUNDED) return 2;
+    for (uint32_t k = 0; !raw && k < m; k += 1)
     {
         if (scanf("%" SCNu32 " %la %la %la", &bounded[k], &c[3 * k], &c[3 * k + 1], &c[3 * k + 2]) != 4) return 2;
         if (!bounded[k]) continue;
@@ -33,7 +40,7 @@ int main()
         }
         any = true;
     }
-    for (uint32_t k = 0; k < m; k += 1)
+    for (uint32_t k = 0; !raw && k < m; k += 1)
         key[k] = bounded[k] ? build_key(build_quantise(c[3 * k], clo[0], chi[0]), build_quantise(c[3 * k + 1], clo[1], chi[1]), build_quantise(c[3 * k + 2], clo[2], chi[2]))
                             : BUILD_KEY_UNBOUNDED;
     std::vector<uint32_t> order(m);

@@ -252,14 +252,16 @@ def _subnormal(q):
 def subnormal_quotients(name):
     """Quotients of the set that are subnormal and not zero: the plane intersector's l of every (ray, plane) and (pair, plane), and
     every component of the normals and normalised directions involved."""
-    bundle, _ = load(name)
-    sc = bundle.scene
     s = ray_sets(name)
+    return subnormal_quotients_of(load(name)[0], *s["rays"], *s["pairs"], expected(name)["hits"]["normal"])
+
+
+def subnormal_quotients_of(bundle, ro, rd, p0, p1, normals):
+    """the same count for any rays and pairs on a scene (`normals`: the oracle's hit normals of the rays)"""
+    sc = bundle.scene
     planes = [sc.surfaces[i] for i in range(int(sc.num_surfaces)) if int(sc.surfaces[i].type) == pydrt.GEO_PLANE]
     pp = np.array([list(p.position) for p in planes]).reshape(-1, 3)
     pn = np.array([list(p.normal) for p in planes]).reshape(-1, 3)
-    ro, rd = s["rays"]
-    p0, p1 = s["pairs"]
     count = 0
     with np.errstate(all="ignore"):
         diff = p1 - p0
@@ -272,5 +274,5 @@ def subnormal_quotients(name):
                 t = pp[k][None, :] - o
                 num = t[:, 0] * pn[k, 0] + t[:, 1] * pn[k, 1] + t[:, 2] * pn[k, 2]
                 count += _subnormal(np.where(dn != 0.0, num / dn, 0.0))
-    count += _subnormal(expected(name)["hits"]["normal"])
+    count += _subnormal(normals)
     return count

@@ -169,8 +169,8 @@ def load(name):
 
 def seeded_rays(name, n=4096, seed=7, centre=None):
     """(origins, dirs, p0, p1) of n rays and n pairs, seeded: origins and points in a box around `centre` (default: where the
-    "after" surfaces have their anchor points), unit directions"""
-    c = load(name)
+    "after" surfaces have their anchor points), unit directions. `name` may be a case itself (tests/hierarchy_cases.py has its own)."""
+    c = load(name) if isinstance(name, str) else name
     rows = pydrt.surface_rows(c["after"])
     pos = rows[:, ROW_POS]
     lo, hi = pos.min(axis=0), pos.max(axis=0)

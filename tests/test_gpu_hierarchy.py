@@ -2,7 +2,8 @@
 bindings). Two rules. The tree the device builds is the one tests/hierarchy_rule.py states, byte for byte: child,
 count and the leaf order, from boxes computed in numpy. And no result moves: films (cases.same_bits on all three buffers), hit logs
 (array_equal) and the counting statistics (==) are those of the context before the build, of a fresh context, and of the oracle.
-tests/test_hierarchy_cpu.py holds the premises (the rule's trees are valid and at most 32 levels deep)."""
+tests/test_hierarchy_cpu.py holds the premises (the rule's trees are valid and at most 32 levels deep). The scenes run from 1 to 20001
+tree surfaces (tests/hierarchy_cases.py); tests/test_gpu_build_passes.py holds the sort and the topology passes alone, on keys made for them."""
 import contextlib
 import os
 
@@ -18,7 +19,12 @@ import scene_update_cases as U
 
 pytestmark = pytest.mark.gpu
 
-CASES = ["spheres_1500", "spheres_96", "lights_all_bvh", "one_sphere", "two_surfaces", "parallel_edges", "coincident_300", "deep_64"]
+CASES = ["spheres_1500", "spheres_96", "lights_all_bvh", "one_sphere", "two_surfaces", "parallel_edges", "coincident_300", "deep_64",
+         # past one tile of the sort, one block of a level, one wave of the bounds pass (tests/hierarchy_cases.py)
+         "three_spheres", "four_spheres", "five_spheres", "spheres_1024", "spheres_2049", "spheres_4097", "lattice_5000", "planes_first",
+         "planes_last_only_bounded", "spheres_20000"]
+RAY_CASES = ("spheres_1500", "spheres_20000")  # 4096 seeded rays and pairs after the build (spheres_20000's film is one sample per pixel: the
+# oracle's scan of 20001 surfaces per vertex keeps that to a fraction of a second, and the queries to about a second)
 HIT_FLOATS = ("position", "normal", "out", "on_dot", "distance")
 HIT_INTS = ("index", "surface_material", "incident_material", "transmit_material")
 _fresh, _oracle, _rule = {}, {}, {}
@@ -92,6 +98,13 @@ def assert_is_the_rules_tree(r, want, what):
     assert np.array_equal(nodes["count"], want["count"]), what + ": count"
     assert np.array_equal(leaf, want["leaf_surface"]), what + ": leaf order"
     assert rep["depth"] == want["depth"] <= R.BVH_STACK, what
+    assert_boxes_hold(nodes, want["order"], want, what)
+    return nodes, leaf
+
+
+def assert_boxes_hold(nodes, order, boxes, what):
+    """every child's box around what hangs below it: the nodes of an inner child, boxes["lo"], boxes["hi"] of the tree position
+    order[slot] of a leaf"""
     with np.errstate(invalid="ignore"):
         for i in range(len(nodes)):
             for c in range(2):
@@ -100,9 +113,8 @@ def assert_is_the_rules_tree(r, want, what):
                     k = nodes["child"][i, c]
                     assert (lo <= nodes["lo"][k].min(axis=0)).all() and (hi >= nodes["hi"][k].max(axis=0)).all(), "%s: node %d child %d" % (what, i, c)
                 elif nodes["count"][i, c] == 1:
-                    k = want["order"][(-2 - nodes["child"][i, c]) // 8]
-                    assert (lo <= want["lo"][k]).all() and (hi >= want["hi"][k]).all(), "%s: node %d leaf %d" % (what, i, c)
-    return nodes, leaf
+                    k = order[(-2 - nodes["child"][i, c]) // 8]
+                    assert (lo <= boxes["lo"][k]).all() and (hi >= boxes["hi"][k]).all(), "%s: node %d leaf %d" % (what, i, c)
 
 
 def assert_hits(got, want, what):
@@ -144,8 +156,8 @@ def test_no_result_moves(name):
         assert_same(built, oracle(name), name + ": after the build against the oracle")
         if name in ("coincident_300", "deep_64"):  # (the two scenes of this file's own: camera rays do meet them)
             assert np.any(built[1][:, 0] >= 0) and np.any(built[1][:, 0] < 0)
-        if name == "spheres_1500":
-            ro, rd, p0, p1 = U.seeded_rays(name, n=4096)
+        if name in RAY_CASES:
+            ro, rd, p0, p1 = HC.seeded_rays(name)
             hits, vis = r.cast_rays(ro, rd), r.test_visibility(p0, p1)
             want = Q.oracle_hits(c["after"], ro, rd)
             want["distance"] = Q.oracle_distances(c["after"], ro, rd, want["index"])
@@ -218,6 +230,56 @@ def test_two_builds_in_a_row_give_the_same_bytes():
         a = r.read_hierarchy()
         r.rebuild_hierarchy()
         r.rebuild_hierarchy()  # (and one whose copy for the host nobody waited for)
+        b = r.read_hierarchy()
+        assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+        assert r.hierarchy_report()["device_builds"] == 3
+
+
+# ------------------------------------------------------------------------------------------------ 4 to 7 past one tile
+@pytest.mark.parametrize("name", HC.MULTI_TILE)
+def test_a_device_mode_update_then_a_build_past_one_tile(name):
+    torch = pytest.importorskip("torch")
+    c = HC.load(name)
+    with context(name, "before") as r:
+        r.update_surfaces(torch.from_numpy(pydrt.surface_rows(c["after"])).to("cuda:0"))
+        assert r.update_report()["refits_since_build"] == 1
+        r.rebuild_hierarchy()
+        assert r.update_report()["refits_since_build"] == 0
+        assert_same(rendered(r, c["params"]), fresh(name), name + ": device-mode update, then a build")
+        assert_is_the_rules_tree(r, rule(name), name)
+
+
+@pytest.mark.parametrize("rebuild", [False, True])
+@pytest.mark.parametrize("name", HC.MULTI_TILE)
+def test_a_build_then_a_host_mode_update_past_one_tile(name, rebuild):
+    """the refit goes through the maps the device made and the level_first hierarchy_adopt makes of the device's level counts: five
+    tiles of the sort, levels of more than one block"""
+    c = HC.load(name)
+    with context(name, "before") as r:
+        r.rebuild_hierarchy()
+        assert_is_the_rules_tree(r, rule(name, "before"), name + ": before")
+        r.update_surfaces(pydrt.surface_rows(c["after"]), rebuild=rebuild)
+        rep, hrep = r.update_report(), r.hierarchy_report()
+        assert rep["updates"] == 1 and rep["refits_since_build"] == (0 if rebuild else 1)
+        assert (hrep["built_by"], hrep["device_builds"]) == ((0, 1) if rebuild else (1, 1))
+        assert_same(rendered(r, c["params"]), fresh(name), name + ": a build, then an update")
+        nodes, leaf = r.read_hierarchy()
+        if not rebuild:  # the links are the build's, every box is around what the update put below it
+            assert np.array_equal(nodes["child"], rule(name, "before")["child"]) and np.array_equal(leaf, rule(name, "before")["leaf_surface"])
+            assert_boxes_hold(nodes, rule(name, "before")["order"], rule(name), name + ": refitted")
+        r.reset_film()
+        r.rebuild_hierarchy()
+        assert_is_the_rules_tree(r, rule(name), name + ": built again")
+        assert_same(rendered(r, c["params"]), fresh(name), name + ": and a build again")
+
+
+@pytest.mark.parametrize("name", HC.MULTI_TILE)
+def test_two_builds_in_a_row_give_the_same_bytes_past_one_tile(name):
+    with context(name) as r:
+        r.rebuild_hierarchy()
+        a = r.read_hierarchy()
+        r.rebuild_hierarchy()
+        r.rebuild_hierarchy()
         b = r.read_hierarchy()
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
         assert r.hierarchy_report()["device_builds"] == 3

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import cases
+import hierarchy_cases as HC
 import pydrt
 import ray_query_cases as Q
 
@@ -124,6 +125,21 @@ def test_the_generated_sets_are_worth_running(name):
         again = mo[on] + rd[on] * hits["distance"][on][:, None]
     assert cases.same_bits(again, hits["position"][on]), cases.first_difference(again, hits["position"][on])
     assert not hits["distance"][~on].any() and not hits["position"][~on].any()
+
+
+@pytest.mark.parametrize("name", ["spheres_1500", "spheres_20000"])
+def test_the_seeded_rays_of_the_hierarchy_tests_are_worth_running(name):
+    """tests/test_gpu_hierarchy.py compares every one of these 4096 rays and pairs bit for bit after a device build: the same premise,
+    no subnormal quotient, and both answers of both queries occur, some hundreds of times each (the sparse 1500 spheres are hit by one
+    ray in thirteen)."""
+    bundle = HC.load(name)["after"]
+    ro, rd, p0, p1 = HC.seeded_rays(name)
+    assert len(ro) == len(p0) == 4096
+    hits, vis = Q.oracle_hits(bundle, ro, rd), Q.oracle_visible(bundle, p0, p1)
+    assert Q.subnormal_quotients_of(bundle, ro, rd, p0, p1, hits["normal"]) == 0
+    hit_share, vis_share = float((hits["index"] >= 0).mean()), float(vis.mean())
+    print("%s: %.1f %% of the rays hit, %.1f %% of the pairs are visible" % (name, 100 * hit_share, 100 * vis_share))
+    assert 0.05 <= hit_share <= 0.95 and 0.05 <= vis_share <= 0.95
 
 
 def test_the_restated_camera_rays_hit_what_the_paths_own_hit_log_says():
