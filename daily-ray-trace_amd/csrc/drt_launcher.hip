@@ -12,6 +12,7 @@
 #include "drt_ray_kernels.h"
 #include "drt_update_kernels.h"
 #include "drt_build_kernels.h"
+#include "drt_material_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -195,6 +196,20 @@ struct drt_context
     hipEvent_t hb_ev[3] = {nullptr, nullptr, nullptr}; /* the last build's kernels: start, end; its copy into hb_mirror */
     uint32_t  hb_builds = 0, hb_built_by = 0, hb_depth = 0;
     double    hb_ms = 0.0;
+    /* material updates (drt_update_spectra, drt_update_materials; drt_material_kernels.h): how every row of d.spds is made (recorded by
+     * build_device_scene), the caller's raw rows on the device, and the pinned buffers host mode goes through. Everything on the device
+     * is made at the first update. */
+    std::vector<SpdRowDesc> spd_desc;      /* [d.n_spd] */
+    bool      mu_ready = false;
+    bool      spd_stale = false;           /* a device-mode update has gone into d_spd_raw only: ft_spds and host_mats' refract_i0 / refract_i1 are read back before the host uses them */
+    bool      variants_stale = false;      /* d_mat_variants was made from host_mats as they were before an update */
+    SpdRowDesc *d_spd_desc = nullptr;
+    double   *d_spd_raw = nullptr, *d_spd_in = nullptr, *h_spd_stage = nullptr; /* [ft_n_spd][S] each: raw rows; host mode's rows on the device; pinned */
+    int32_t  *d_mat_refract = nullptr;     /* [n_mat] */
+    DevMaterial *h_mat_stage = nullptr;    /* pinned, [n_mat] */
+    hipEvent_t mu_ev[2] = {nullptr, nullptr}; /* the copies out of h_spd_stage and h_mat_stage are done */
+    bool      spd_stage_busy = false, mat_stage_busy = false;
+    uint32_t  spectra_updates = 0, material_updates = 0;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -553,6 +568,9 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
     }
 
     std::vector<double> spds(scene->spds, scene->spds + (size_t)scene->num_spds * S);
+    std::vector<SpdRowDesc> &desc = ctx->spd_desc; /* how every row is made: what drt_update_spectra derives the table from again */
+    desc.clear();
+    for (uint32_t r = 0; r < scene->num_spds; r += 1) desc.push_back(SpdRowDesc{SPD_ROW_SCENE, (int32_t)r, -1, -1});
     std::map<int32_t, uint32_t> diffuse_pi_row;
     /* the zero row is appended last; derived rows go between: reserve its index now */
     uint32_t n_diffuse = 0;
@@ -607,6 +625,7 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
                 const double inv_pi = 1.0 / DRT_PI;
                 uint32_t r = (uint32_t)(spds.size() / S);
                 for (uint32_t k = 0; k < S; k += 1) spds.push_back(scene->spds[(size_t)m.diffuse_spd * S + k] * inv_pi);
+                desc.push_back(SpdRowDesc{SPD_ROW_DIFFUSE_PI, m.diffuse_spd, -1, -1});
                 it = diffuse_pi_row.emplace(m.diffuse_spd, r).first;
             }
             dm.diffuse_spd = (int32_t)it->second;
@@ -640,6 +659,8 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
                 /* rel_sq = (ir / tr) (ir / tr), src/bdsf.c:52-56: entering (ir the base material's, tr this one's), then leaving */
                 for (uint32_t k = 0; k < S; k += 1) { const double rel = at(bm.refract_spd, k) / at(m.refract_spd, k); spds.push_back(rel * rel); }
                 for (uint32_t k = 0; k < S; k += 1) { const double rel = at(m.refract_spd, k) / at(bm.refract_spd, k); spds.push_back(rel * rel); }
+                desc.push_back(SpdRowDesc{SPD_ROW_REL_SQ, bm.refract_spd, m.refract_spd, -1});
+                desc.push_back(SpdRowDesc{SPD_ROW_REL_SQ, m.refract_spd, bm.refract_spd, -1});
                 dm.pair_out = (uint16_t)r0;
                 dm.pair_in = (uint16_t)(r0 + 1u);
             }
@@ -655,12 +676,15 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
                     cB[k] = 4.0 * rr_sq * re_sq;
                 }
                 spds.insert(spds.end(), cB.begin(), cB.end());
+                desc.push_back(SpdRowDesc{SPD_ROW_CONDUCTOR_A, m.refract_spd, m.extinct_spd, bm.refract_spd});
+                desc.push_back(SpdRowDesc{SPD_ROW_CONDUCTOR_B, m.refract_spd, m.extinct_spd, bm.refract_spd});
                 dm.pair_out = (uint16_t)(r0 | PAIR_CONDUCTOR);
             }
         }
         if (!m.is_black_body && dm.dir_func >= DRT_NUM_DIRFS) return fail(-2, "material %u: unknown dir_func id %u", i, dm.dir_func);
     }
     spds.resize((size_t)(zero_row + 1) * S, 0.0); /* + the all-zero row */
+    desc.resize((size_t)zero_row + 1, SpdRowDesc{SPD_ROW_ZERO, -1, -1, -1});
     d.n_spd = zero_row + 1;
 
     int rc;
@@ -1236,6 +1260,14 @@ extern "C" void drt_destroy(drt_context *ctx)
         (void)hipFree(ctx->d_hb_items[k]);
     }
     (void)hipHostFree(ctx->hb_mirror);
+    (void)hipFree(ctx->d_spd_desc);
+    (void)hipFree(ctx->d_spd_raw);
+    (void)hipFree(ctx->d_spd_in);
+    (void)hipFree(ctx->d_mat_refract);
+    (void)hipHostFree(ctx->h_spd_stage);
+    (void)hipHostFree(ctx->h_mat_stage);
+    for (hipEvent_t e : ctx->mu_ev)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->hb_ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : ctx->upd_ev)
@@ -2893,6 +2925,7 @@ static size_t feature_lds_bytes(uint32_t n_surf)
 
 /* [num_materials][3], the rule's "material colour": sums sequential over ascending wavelength, no contraction (the host is built
  * with -ffp-contract=off, like the kernels) */
+static int spectra_read_back(drt_context *ctx);
 static int feature_colour_table(const drt_context *ctx, std::vector<double> *table)
 {
     const uint32_t S = ctx->ft_S;
@@ -2989,8 +3022,9 @@ static int features_enqueue(drt_context *ctx, const drt_features *f)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     std::vector<double> table;
-    int rc = feature_colour_table(ctx, &table);
+    int rc = spectra_read_back(ctx); /* the table is made from the host's mirror of the spectra */
     if (rc) return rc;
+    if ((rc = feature_colour_table(ctx, &table))) return rc;
     if (!table.empty()) HIP_TRY(hipMemcpy(ctx->d_ft_colour, table.data(), table.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(ctx->d_ft_info, 0, FEATURE_INFO_WORDS * sizeof(unsigned long long), ctx->stream));
     const drt_params &p = ctx->params;
@@ -4158,6 +4192,270 @@ extern "C" int drt_group_update_surfaces(drt_group *g, const drt_surface *surfac
 }
 
 /* ---------------------------------------------------------------------------------------------- */
+/* Material updates: new spectra and parameters for a live context (include/drt_hip.h) */
+
+/* everything a material update needs on the device, made at the first one. Changes nothing a render reads. */
+static int material_prepare(drt_context *ctx)
+{
+    if (ctx->mu_ready) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t n_mat = ctx->ft_mats.size();
+    const size_t row_bytes = std::max<size_t>((size_t)ctx->ft_n_spd * ctx->ft_S, 1) * sizeof(double);
+    if (!ctx->d_spd_raw)
+    {
+        /* the raw copy starts as the mirror, so the mirror must be the device's: this is the first update, and it is */
+        HIP_TRY(hipMalloc((void **)&ctx->d_spd_raw, row_bytes));
+        if (!ctx->ft_spds.empty()) HIP_TRY(hipMemcpy(ctx->d_spd_raw, ctx->ft_spds.data(), ctx->ft_spds.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (!ctx->d_spd_in) HIP_TRY(hipMalloc((void **)&ctx->d_spd_in, row_bytes));
+    if (!ctx->h_spd_stage) HIP_TRY(hipHostMalloc((void **)&ctx->h_spd_stage, row_bytes, hipHostMallocDefault));
+    if (!ctx->h_mat_stage) HIP_TRY(hipHostMalloc((void **)&ctx->h_mat_stage, std::max<size_t>(n_mat, 1) * sizeof(DevMaterial), hipHostMallocDefault));
+    if (!ctx->d_spd_desc)
+    {
+        HIP_TRY(hipMalloc((void **)&ctx->d_spd_desc, std::max<size_t>(ctx->spd_desc.size(), 1) * sizeof(SpdRowDesc)));
+        if (!ctx->spd_desc.empty())
+            HIP_TRY(hipMemcpy(ctx->d_spd_desc, ctx->spd_desc.data(), ctx->spd_desc.size() * sizeof(SpdRowDesc), hipMemcpyHostToDevice));
+    }
+    if (!ctx->d_mat_refract)
+    {
+        /* a given refract spectrum is a scene row, and scene rows keep their numbers in the device table */
+        std::vector<int32_t> refract(std::max<size_t>(n_mat, 1), -1);
+        for (size_t m = 0; m < n_mat; m += 1) refract[m] = ctx->ft_mats[m].refract_spd >= 0 ? ctx->ft_mats[m].refract_spd : -1;
+        HIP_TRY(hipMalloc((void **)&ctx->d_mat_refract, refract.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(ctx->d_mat_refract, refract.data(), refract.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    for (hipEvent_t &e : ctx->mu_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    ctx->mu_ready = true;
+    return 0;
+}
+
+/* host_mats' two samples around trans_wl from the mirror, as build_device_scene takes them */
+static void material_refract_samples(drt_context *ctx)
+{
+    const uint32_t S = ctx->ft_S;
+    for (size_t m = 0; m < ctx->ft_mats.size(); m += 1)
+    {
+        const int32_t r = ctx->ft_mats[m].refract_spd;
+        if (r < 0) continue;
+        ctx->host_mats[m].refract_i0 = ctx->ft_spds[(size_t)r * S + ctx->dsc.trans_i0];
+        ctx->host_mats[m].refract_i1 = ctx->ft_spds[(size_t)r * S + ctx->dsc.trans_i0 + 1];
+    }
+    ctx->variants_stale = true;
+}
+
+/* the host mirrors again after device-mode updates (update_read_back's twin): ft_spds from the raw copy, and from it host_mats' refract samples */
+static int spectra_read_back(drt_context *ctx)
+{
+    if (!ctx->spd_stale) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!ctx->ft_spds.empty()) HIP_TRY(hipMemcpy(ctx->ft_spds.data(), ctx->d_spd_raw, ctx->ft_spds.size() * sizeof(double), hipMemcpyDeviceToHost));
+    material_refract_samples(ctx);
+    ctx->spd_stale = false;
+    return 0;
+}
+
+/* everything drt_update_spectra can be refused for; changes nothing */
+static int spectra_check(drt_context *ctx, const double *rows, uint32_t first_row, uint32_t count, uint32_t flags, const char *name, bool group)
+{
+    if (flags & ~DRT_SPECTRA_DEVICE) return fail(-1, "%s: unknown flags 0x%x", name, flags);
+    if (group && (flags & DRT_SPECTRA_DEVICE)) return fail(-1, "%s: host pointers only (DRT_SPECTRA_DEVICE is per context: drt_update_spectra)", name);
+    if ((uint64_t)first_row + count > ctx->ft_n_spd)
+        return fail(-1, "%s: rows [%u, %llu) of %u", name, first_row, (unsigned long long)first_row + count, ctx->ft_n_spd);
+    if (count > 0 && !rows) return fail(-1, "%s: rows is null", name);
+    if (count == 0) return 0; /* a no-op, whatever the film holds */
+    const uint32_t cmf[4] = {ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z};
+    static const char *const cmf_name[4] = {"cmf_rw", "cmf_x", "cmf_y", "cmf_z"};
+    for (int k = 0; k < 4; k += 1)
+        if (cmf[k] >= first_row && cmf[k] - first_row < count)
+            return fail(-2, "%s: row %u is the scene's %s (the observer's rows are no material: an update keeps them)", name, cmf[k], cmf_name[k]);
+    return update_film_check(ctx, name);
+}
+
+/* the caller's rows into the pinned buffer: can fail, and changes nothing a render reads */
+static int spectra_stage(drt_context *ctx, const double *rows, uint32_t count)
+{
+    int rc = material_prepare(ctx);
+    if (rc) return rc;
+    if ((rc = spectra_read_back(ctx))) return rc;
+    if (ctx->spd_stage_busy) HIP_TRY(hipEventSynchronize(ctx->mu_ev[0])); /* the last update's copy out of it */
+    ctx->spd_stage_busy = false;
+    memcpy(ctx->h_spd_stage, rows, (size_t)count * ctx->ft_S * sizeof(double));
+    return 0;
+}
+
+/* the two kernels, on the context's stream: every derived row, the refract samples and the tail columns again from ALL raw rows */
+static int spectra_enqueue(drt_context *ctx, const double *d_rows, uint32_t first_row, uint32_t count)
+{
+    const DevScene &d = ctx->dsc;
+    SpectraTables t;
+    t.src = d_rows;
+    t.raw = ctx->d_spd_raw;
+    t.table = const_cast<double *>(d.spds);
+    t.desc = ctx->d_spd_desc;
+    t.first_row = first_row; t.count = count; t.n_spd = d.n_spd; t.S = d.S;
+    const uint64_t lanes = (uint64_t)d.n_spd * d.S;
+    hipLaunchKernelGGL(drt_spectra_derive_kernel, dim3((uint32_t)((lanes + MATERIAL_BLOCK - 1) / MATERIAL_BLOCK)), dim3(MATERIAL_BLOCK), 0, ctx->stream, t);
+    HIP_TRY(hipGetLastError());
+    SpectraFinish f;
+    f.table = d.spds;
+    f.mats = const_cast<DevMaterial *>(d.mats);
+    f.mat_refract = ctx->d_mat_refract;
+    f.tail = ctx->trace_tail ? const_cast<double *>(ctx->d_spd_tail) : nullptr;
+    f.n_mat = d.n_mat; f.n_spd = d.n_spd; f.S = d.S; f.trans_i0 = d.trans_i0;
+    f.tail_first = ctx->tail_first; f.tail_count = ctx->tail_count;
+    const uint64_t lanes2 = (uint64_t)d.n_mat + (f.tail ? (uint64_t)d.n_spd * ctx->tail_count : 0);
+    hipLaunchKernelGGL(drt_spectra_finish_kernel, dim3((uint32_t)((lanes2 + MATERIAL_BLOCK - 1) / MATERIAL_BLOCK)), dim3(MATERIAL_BLOCK), 0, ctx->stream, f);
+    HIP_TRY(hipGetLastError());
+    ctx->spectra_updates += 1;
+    ctx->ft_valid = ctx->mt_valid = false; /* what describes the old scene is stale */
+    return 0;
+}
+
+static int spectra_commit(drt_context *ctx, uint32_t first_row, uint32_t count)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t words = (size_t)count * ctx->ft_S;
+    std::copy(ctx->h_spd_stage, ctx->h_spd_stage + words, ctx->ft_spds.begin() + (size_t)first_row * ctx->ft_S);
+    material_refract_samples(ctx);
+    HIP_TRY(hipMemcpyAsync(ctx->d_spd_in, ctx->h_spd_stage, words * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->mu_ev[0], ctx->stream));
+    ctx->spd_stage_busy = true;
+    return spectra_enqueue(ctx, ctx->d_spd_in, first_row, count);
+}
+
+extern "C" int drt_update_spectra(drt_context *ctx, const double *rows, uint32_t first_row, uint32_t count, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "drt_update_spectra: ctx is null");
+    int rc = spectra_check(ctx, rows, first_row, count, flags, "drt_update_spectra", false);
+    if (rc || count == 0) return rc;
+    if (flags & DRT_SPECTRA_DEVICE)
+    {
+        if ((rc = material_prepare(ctx))) return rc;
+        HIP_TRY(hipSetDevice(ctx->device));
+        ctx->spd_stale = true;
+        ctx->variants_stale = true;
+        return spectra_enqueue(ctx, rows, first_row, count);
+    }
+    if ((rc = spectra_stage(ctx, rows, count))) return rc;
+    return spectra_commit(ctx, first_row, count);
+}
+
+extern "C" int drt_group_update_spectra(drt_group *g, const double *rows, uint32_t first_row, uint32_t count, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_update_spectra: the group is null");
+    int rc = 0;
+    /* every context is checked, and every device's staging copy is made, before any context changes */
+    for (drt_context *c : g->ctx)
+        if (c && (rc = spectra_check(c, rows, first_row, count, flags, "drt_group_update_spectra", true))) return rc;
+    if (count == 0) return 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = spectra_stage(c, rows, count))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = spectra_commit(c, first_row, count))) return rc;
+    return 0;
+}
+
+/* everything drt_update_materials can be refused for; changes nothing */
+static int materials_check(drt_context *ctx, const drt_material *materials, uint32_t first, uint32_t count, uint32_t flags, const char *name)
+{
+    const size_t n = ctx->ft_mats.size();
+    if (flags != 0) return fail(-1, "%s: unknown flags 0x%x", name, flags);
+    if ((uint64_t)first + count > n) return fail(-1, "%s: materials [%u, %llu) of %zu", name, first, (unsigned long long)first + count, n);
+    if (count > 0 && !materials) return fail(-1, "%s: materials is null", name);
+    if (count == 0) return 0; /* a no-op, whatever the film holds */
+    int rc = update_film_check(ctx, name);
+    if (rc) return rc;
+    for (uint32_t i = 0; i < count; i += 1)
+    {
+        const drt_material &is = materials[i], &was = ctx->ft_mats[first + i];
+        const uint32_t m = first + i;
+#define DRT_MATERIAL_KEEPS(field, fmt)                                                                                                     \
+    if (is.field != was.field)                                                                                                             \
+        return fail(-2, "%s: material %u: " #field " " fmt ", was " fmt " (an update changes shininess and roughness only)", name, m, is.field, was.field)
+        DRT_MATERIAL_KEEPS(is_black_body, "%u");
+        DRT_MATERIAL_KEEPS(is_emissive, "%u");
+        DRT_MATERIAL_KEEPS(emission_spd, "%d");
+        DRT_MATERIAL_KEEPS(diffuse_spd, "%d");
+        DRT_MATERIAL_KEEPS(glossy_spd, "%d");
+        DRT_MATERIAL_KEEPS(mirror_spd, "%d");
+        DRT_MATERIAL_KEEPS(refract_spd, "%d");
+        DRT_MATERIAL_KEEPS(extinct_spd, "%d");
+        DRT_MATERIAL_KEEPS(num_bdsfs, "%u");
+        for (uint32_t j = 0; j < std::min<uint32_t>(was.num_bdsfs, DRT_MAX_BDSFS); j += 1)
+            if (is.bdsfs[j] != was.bdsfs[j])
+                return fail(-2, "%s: material %u: bdsfs[%u] %u, was %u (an update changes shininess and roughness only)", name, m, j, is.bdsfs[j], was.bdsfs[j]);
+        DRT_MATERIAL_KEEPS(dir_func, "%u");
+#undef DRT_MATERIAL_KEEPS
+    }
+    return 0;
+}
+
+/* the records as the device will hold them, into the pinned buffer: can fail, and changes nothing a render reads */
+static int materials_stage(drt_context *ctx, const drt_material *materials, uint32_t first, uint32_t count)
+{
+    int rc = material_prepare(ctx);
+    if (rc) return rc;
+    if ((rc = spectra_read_back(ctx))) return rc; /* the records carry refract_i0 / refract_i1 */
+    if (ctx->mat_stage_busy) HIP_TRY(hipEventSynchronize(ctx->mu_ev[1]));
+    ctx->mat_stage_busy = false;
+    for (uint32_t i = 0; i < count; i += 1)
+    {
+        DevMaterial dm = ctx->host_mats[first + i];
+        dm.shininess = materials[i].shininess;
+        dm.roughness = materials[i].roughness;
+        ctx->h_mat_stage[i] = dm;
+    }
+    return 0;
+}
+
+static int materials_commit(drt_context *ctx, uint32_t first, uint32_t count)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    for (uint32_t i = 0; i < count; i += 1)
+    {
+        ctx->host_mats[first + i] = ctx->h_mat_stage[i];
+        ctx->ft_mats[first + i].shininess = ctx->h_mat_stage[i].shininess;
+        ctx->ft_mats[first + i].roughness = ctx->h_mat_stage[i].roughness;
+    }
+    ctx->variants_stale = true;
+    HIP_TRY(hipMemcpyAsync(const_cast<DevMaterial *>(ctx->dsc.mats) + first, ctx->h_mat_stage, (size_t)count * sizeof(DevMaterial), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->mu_ev[1], ctx->stream));
+    ctx->mat_stage_busy = true;
+    ctx->material_updates += 1;
+    ctx->ft_valid = ctx->mt_valid = false;
+    return 0;
+}
+
+extern "C" int drt_update_materials(drt_context *ctx, const drt_material *materials, uint32_t first, uint32_t count, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!ctx) return fail(-1, "drt_update_materials: ctx is null");
+    int rc = materials_check(ctx, materials, first, count, flags, "drt_update_materials");
+    if (rc || count == 0) return rc;
+    if ((rc = materials_stage(ctx, materials, first, count))) return rc;
+    return materials_commit(ctx, first, count);
+}
+
+extern "C" int drt_group_update_materials(drt_group *g, const drt_material *materials, uint32_t first, uint32_t count, uint32_t flags)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_update_materials: the group is null");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = materials_check(c, materials, first, count, flags, "drt_group_update_materials"))) return rc;
+    if (count == 0) return 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = materials_stage(c, materials, first, count))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = materials_commit(c, first, count))) return rc;
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
 /* Device hierarchy builds: the tree of a live context anew, on its stream (include/drt_hip.h) */
 
 /* hb_mirror: the nodes, the surface of every leaf slot, the level counts */
@@ -4670,7 +4968,9 @@ static int bdsf_fresnel_kind(uint32_t b)
  * function is of the kind the rows were tabulated for (never read a dielectric's rel_sq row as a conductor's cA, cB), else PAIR_NONE. */
 static int material_variants(drt_context *ctx)
 {
-    if (ctx->d_mat_variants) return 0;
+    int rc = spectra_read_back(ctx);
+    if (rc) return rc;
+    if (ctx->d_mat_variants && !ctx->variants_stale) return 0;
     const uint32_t n_mat = ctx->dsc.n_mat;
     std::vector<DevMaterial> v((size_t)DRT_MAT_VARIANTS * n_mat);
     for (uint32_t k = 0; k < (uint32_t)DRT_MAT_VARIANTS; k += 1)
@@ -4691,11 +4991,15 @@ static int material_variants(drt_context *ctx)
             else dm.dir_func = k - (uint32_t)DRT_NUM_BDSFS;
             v[(size_t)k * n_mat + m] = dm;
         }
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, v.size() * sizeof(DevMaterial)));
-    ctx->allocations.push_back(p);
+    void *p = ctx->d_mat_variants; /* after a material update: the same allocation, made again */
+    if (!p)
+    {
+        HIP_TRY(hipMalloc(&p, v.size() * sizeof(DevMaterial)));
+        ctx->allocations.push_back(p);
+    }
     HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
     ctx->d_mat_variants = (DevMaterial *)p;
+    ctx->variants_stale = false;
     return 0;
 }
 

@@ -83,6 +83,7 @@ typedef struct
  * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK,
  * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE. */
 #define DRT_HOST_MAX_PICKS 64
+#define DRT_HOST_MAX_LEVELS 64
 typedef struct
 {
     int32_t  device;
@@ -130,6 +131,12 @@ typedef struct
      * .%04u before the extension. Not combined with checkpoints, resuming, DRT_PROJECTION or the post-passes (denoiser, features, mattes,
      * picks). 0: off, and everything as without it */
     uint32_t turntable;
+    /* DRT_LIGHT_LEVELS="k0,k1,...": one frame per level from ONE group: per frame one drt_group_reset_film, one drt_group_update_spectra
+     * that gives every row an emissive material names as its emission the scene's own row times k (one multiplication per sample, on
+     * the host), and the render the configuration asks for; frame j writes the three standard outputs with .%04u before the extension.
+     * Not combined with DRT_TURNTABLE or with what the turntable is not combined with. 0 levels: off, and everything as without it */
+    uint32_t n_levels;
+    double   levels[DRT_HOST_MAX_LEVELS];
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u

@@ -89,10 +89,42 @@ static int frame_path(char dst[64], const char *src, u32 frame)
     return snprintf(dst, 64, "%.*s.%04u%s", stem, src, frame, dot ? dot : "") < 64 ? 0 : -1;
 }
 
-/* DRT_TURNTABLE=n: n frames from one group, the second and every later one at the price of a drt_set_camera instead of a drt_group_create */
+/* Frame k of DRT_LIGHT_LEVELS: `rows` gets the scene's rows [*first_row, *first_row + *count) -- from the first to the last row an emissive
+ * material names as its emission -- with every such row times `level` (one multiplication per sample) and the rows between as they are.
+ * No emissive material: *count = 0. */
+static void light_level_rows(const drt_scene *scene, f64 level, f64 *rows, u32 *first_row, u32 *count)
+{
+    const u32 S = scene->num_wavelengths;
+    u32 lo = 0xFFFFFFFFu, hi = 0;
+    for (u32 m = 0; m < scene->num_materials; m += 1)
+        if (scene->materials[m].is_emissive && scene->materials[m].emission_spd >= 0)
+        {
+            const u32 r = (u32)scene->materials[m].emission_spd;
+            if (r < lo) lo = r;
+            if (r > hi) hi = r;
+        }
+    *first_row = 0;
+    *count = 0;
+    if (lo == 0xFFFFFFFFu) return;
+    *first_row = lo;
+    *count = hi - lo + 1;
+    memcpy(rows, scene->spds + (size_t)lo * S, (size_t)*count * S * sizeof(f64));
+    for (u32 r = lo; r <= hi; r += 1)
+    {
+        int names_it = 0;
+        for (u32 m = 0; m < scene->num_materials && !names_it; m += 1)
+            names_it = scene->materials[m].is_emissive && scene->materials[m].emission_spd == (int32_t)r;
+        if (!names_it) continue;
+        for (u32 i = 0; i < S; i += 1) rows[(size_t)(r - lo) * S + i] = scene->spds[(size_t)r * S + i] * level;
+    }
+}
+
+/* DRT_TURNTABLE=n: n frames from one group, the second and every later one at the price of a drt_set_camera instead of a drt_group_create.
+ * DRT_LIGHT_LEVELS: one frame per level from one group through the scene's own camera, at the price of a drt_group_update_spectra */
 static int render_turntable(config_arguments *config, const drt_host_options *opt, drt_stats *stats_out)
 {
-    const u32 width = config->output_width, height = config->output_height, frames = opt->turntable;
+    const u32 width = config->output_width, height = config->output_height, frames = opt->turntable ? opt->turntable : opt->n_levels;
+    const char *const mode_name = opt->turntable ? "DRT_TURNTABLE" : "DRT_LIGHT_LEVELS";
     spd_tables_csvs csvs;
     csvs.white = config->white_spd;  csvs.cmf_x = config->cmf_x;      csvs.cmf_y = config->cmf_y;
     csvs.cmf_z = config->cmf_z;      csvs.rgb_red = config->red_spd;  csvs.rgb_green = config->green_spd;
@@ -109,7 +141,7 @@ static int render_turntable(config_arguments *config, const drt_host_options *op
             frame_path(fc.variance_spd, config->variance_spd, k) || frame_path(fc.output_bmp, config->output_bmp, k) ||
             frame_path(fc.average_bmp, config->average_bmp, k) || frame_path(fc.variance_bmp, config->variance_bmp, k))
         {
-            fprintf(stderr, "render_image: DRT_TURNTABLE: an output name with .%04u before its extension is longer than 63 characters\n", k);
+            fprintf(stderr, "render_image: %s: an output name with .%04u before its extension is longer than 63 characters\n", mode_name, k);
             return -1;
         }
     }
@@ -126,7 +158,8 @@ static int render_turntable(config_arguments *config, const drt_host_options *op
     f64 *dst_avgs = (f64 *)calloc(num_pixels * S, sizeof(f64));
     f64 *dst_vars = (f64 *)calloc(num_pixels * S, sizeof(f64));
     u8 *bgra = (u8 *)malloc(num_pixels * 4 + 4);
-    if (!dst_pixels || !dst_avgs || !dst_vars || !bgra)
+    f64 *level_rows = opt->n_levels ? (f64 *)malloc((size_t)scene->num_spds * S * sizeof(f64) + 8) : NULL;
+    if (!dst_pixels || !dst_avgs || !dst_vars || !bgra || (opt->n_levels && !level_rows))
     {
         fprintf(stderr, "render_image: out of memory for %llu pixels\n", (unsigned long long)num_pixels);
         return -1;
@@ -167,10 +200,20 @@ static int render_turntable(config_arguments *config, const drt_host_options *op
         frame_path(fc.output_bmp, config->output_bmp, k);
         frame_path(fc.average_bmp, config->average_bmp, k);
         frame_path(fc.variance_bmp, config->variance_bmp, k);
-        drt_camera cam;
-        if (drt_host_turntable_camera(hs, width, height, k, frames, &cam) != 0) { rc = -1; break; }
-        if ((rc = drt_group_reset_film(ctx))) break;
-        if ((rc = drt_group_set_camera(ctx, &cam))) break;
+        if (opt->turntable)
+        {
+            drt_camera cam;
+            if (drt_host_turntable_camera(hs, width, height, k, frames, &cam) != 0) { rc = -1; break; }
+            if ((rc = drt_group_reset_film(ctx))) break;
+            if ((rc = drt_group_set_camera(ctx, &cam))) break;
+        }
+        else
+        {
+            u32 first_row = 0, count = 0;
+            light_level_rows(scene, opt->levels[k], level_rows, &first_row, &count);
+            if ((rc = drt_group_reset_film(ctx))) break;
+            if ((rc = drt_group_update_spectra(ctx, level_rows, first_row, count, 0))) break;
+        }
         if (opt->adaptive)
         {
             drt_adaptive a;
@@ -204,6 +247,7 @@ static int render_turntable(config_arguments *config, const drt_host_options *op
     if (rc) fprintf(stderr, "render_image: the HIP launcher failed (%d): %s\n", rc, drt_last_error());
     if (ctx) drt_group_destroy(ctx);
     if (stats_out) *stats_out = stats;
+    free(level_rows);
     free(bgra);
     free(dst_vars);
     free(dst_avgs);
@@ -214,7 +258,7 @@ static int render_turntable(config_arguments *config, const drt_host_options *op
 
 int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_stats *stats_out)
 {
-    if (opt && opt->turntable) return render_turntable(config, opt, stats_out);
+    if (opt && (opt->turntable || opt->n_levels)) return render_turntable(config, opt, stats_out);
     u32 width = config->output_width, height = config->output_height;
     spd_tables_csvs csvs;
     csvs.white = config->white_spd;  csvs.cmf_x = config->cmf_x;      csvs.cmf_y = config->cmf_y;
@@ -833,6 +877,33 @@ static int turntable_options(drt_host_options *opt)
     return 0;
 }
 
+/* DRT_LIGHT_LEVELS="k0,k1,..." (finite numbers, DRT_HOST_MAX_LEVELS at most): parsed and checked here, before any device call, after the
+ * options it cannot be combined with. */
+static int light_levels_options(drt_host_options *opt)
+{
+    opt->n_levels = 0;
+    const char *e = getenv("DRT_LIGHT_LEVELS");
+    if (!e) return 0;
+    static const char *const names[] = { "DRT_TURNTABLE", "DRT_CHECKPOINT_SPP", "DRT_RESUME", "DRT_ADAPTIVE_CHECKPOINT_ROUNDS", "DRT_ADAPTIVE_RESUME",
+                                         "DRT_PROJECTION", "DRT_DENOISE_K", "DRT_PICK" };
+    for (int k = 0; k < 8; k += 1)
+        if (getenv(names[k])) { fprintf(stderr, "render_image: DRT_LIGHT_LEVELS cannot be combined with %s\n", names[k]); return -1; }
+    if (opt->features) { fprintf(stderr, "render_image: DRT_LIGHT_LEVELS cannot be combined with DRT_FEATURES\n"); return -1; }
+    if (opt->mattes) { fprintf(stderr, "render_image: DRT_LIGHT_LEVELS cannot be combined with DRT_MATTES\n"); return -1; }
+    for (const char *c = e;;)
+    {
+        char *end;
+        const double level = strtod(c, &end);
+        if (end == c || !isfinite(level) || (*end && *end != ','))
+        { fprintf(stderr, "render_image: DRT_LIGHT_LEVELS=\"%s\": finite numbers separated by commas\n", e); return -1; }
+        if (opt->n_levels == DRT_HOST_MAX_LEVELS) { fprintf(stderr, "render_image: DRT_LIGHT_LEVELS: %d levels at most\n", DRT_HOST_MAX_LEVELS); return -1; }
+        opt->levels[opt->n_levels++] = level;
+        if (!*end) break;
+        c = end + 1;
+    }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -864,5 +935,6 @@ void render_image(config_arguments *config)
     if (pick_options(config, &opt) != 0) exit(-1);
     if (projection_options(&opt) != 0) exit(-1);
     if (turntable_options(&opt) != 0) exit(-1);
+    if (light_levels_options(&opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

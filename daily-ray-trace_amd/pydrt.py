@@ -208,6 +208,7 @@ def _ray_table(origins, dirs, weights, width, height, device):
 
 
 SURFACES_DEVICE, SURFACES_REBUILD = 1, 2  # DRT_SURFACES_*
+SPECTRA_DEVICE = 1  # DRT_SPECTRA_DEVICE
 SURFACE_ROW = 14  # a drt_surface as doubles: word 0 holds type and material, then position, radius, normal, u, v
 
 
@@ -271,6 +272,29 @@ def _update_args(surfaces, device):
             raise ValueError("surfaces: an [n][%d] float64 array" % SURFACE_ROW)
         return rows.ctypes.data, int(rows.shape[0]), 0, rows
     return C.cast(surfaces, C.c_void_p).value, len(surfaces), 0, surfaces
+
+
+def _spectra_args(rows, S, device):
+    """(pointer, count, flags, what must stay referenced) of update_spectra's two input forms"""
+    if _is_tensor(rows):
+        torch = sys.modules["torch"]
+        t = rows
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != S:
+            raise ValueError("rows: a contiguous [n][%d] float64 tensor" % S)
+        if t.device.type != "cuda" or t.device.index != device:
+            raise ValueError("rows: a tensor on the context's device (cuda:%d)" % device)
+        return t.data_ptr(), int(t.shape[0]), SPECTRA_DEVICE, t
+    a = np.ascontiguousarray(rows, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != S:
+        raise ValueError("rows: an [n][%d] float64 array" % S)
+    return a.ctypes.data, int(a.shape[0]), 0, a
+
+
+def _materials_args(materials):
+    """(pointer, count, what must stay referenced): a ctypes Material array, or a sequence of Material"""
+    if not isinstance(materials, C.Array):
+        materials = (Material * max(1, len(materials)))(*materials) if len(materials) else (Material * 0)()
+    return C.cast(materials, C.c_void_p).value, len(materials), materials
 
 
 def turntable_camera(bundle, width, height, k, n):
@@ -417,6 +441,14 @@ class SceneBundle:
     def spds(self):
         n = int(self.scene.num_spds) * self.S
         return np.ctypeslib.as_array(self.scene.spds, shape=(n,)).reshape(int(self.scene.num_spds), self.S).copy()
+
+    def materials(self):
+        """a copy of the scene's Material array"""
+        n = int(self.scene.num_materials)
+        out = (Material * n)()
+        if n:
+            C.memmove(out, self.scene.materials, n * C.sizeof(Material))
+        return out
 
     def material_names(self):
         if self._handle is None:
@@ -632,6 +664,11 @@ def hip_lib():
             L.drt_group_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
             L.drt_group_update_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
             L.drt_group_reset_film.argtypes = [C.c_void_p]
+        if hasattr(L, "drt_update_spectra"):
+            L.drt_update_spectra.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+            L.drt_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+            L.drt_group_update_spectra.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+            L.drt_group_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
         if hasattr(L, "drt_rebuild_hierarchy"):
             L.drt_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
@@ -673,7 +710,8 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_group_cast_pixels", "drt_bind_rays", "drt_group_bind_rays",
                "drt_set_camera", "drt_update_surfaces", "drt_get_update_report", "drt_group_set_camera", "drt_group_update_surfaces",
                "drt_group_reset_film",
-               "drt_rebuild_hierarchy", "drt_group_rebuild_hierarchy", "drt_get_hierarchy_report", "drt_read_hierarchy"]
+               "drt_rebuild_hierarchy", "drt_group_rebuild_hierarchy", "drt_get_hierarchy_report", "drt_read_hierarchy",
+               "drt_update_spectra", "drt_update_materials", "drt_group_update_spectra", "drt_group_update_materials"]
 
 
 def _check(rc, what):
@@ -955,6 +993,22 @@ class Renderer:
         if flags & SURFACES_DEVICE:
             self._update_rows = keep  # until the stream has read it: the next update or close() at the latest
 
+    def update_spectra(self, rows, first=0):
+        """drt_update_spectra: rows [first, first + n) of the scene's SPD table (SceneBundle.spds numbering) replaced. A numpy [n][S]
+        float64 array: host mode, checked before anything changes. A float64 torch tensor [n][S] on the context's device: device mode,
+        enqueued on the context's stream without waiting. The colour-matching rows are refused; the film must hold no samples. Bit for
+        bit a fresh context's results on the scene with those rows."""
+        ptr, n, flags, keep = _spectra_args(rows, self.S, int(self.params.device))
+        _check(self.L.drt_update_spectra(self.ctx, ptr, first, n, flags), "drt_update_spectra")
+        if flags & SPECTRA_DEVICE:
+            self._spectra_rows = keep  # until the stream has read it: the next update or close() at the latest
+
+    def update_materials(self, materials, first=0):
+        """drt_update_materials: materials [first, first + n) given the shininess and roughness of these Material records (a ctypes
+        array or a sequence); every other field must equal what the context holds. The film must hold no samples."""
+        ptr, n, _keep = _materials_args(materials)
+        _check(self.L.drt_update_materials(self.ctx, ptr, first, n, 0), "drt_update_materials")
+
     def update_report(self):
         """drt_get_update_report: {"updates", "refits_since_build", "extent", "kernel_ms"}"""
         r = UpdateReport()
@@ -1130,6 +1184,18 @@ class Group:
             raise ValueError("Group.update_surfaces: a Surface array or numpy rows (a group takes host pointers only)")
         ptr, n, flags, _keep = _update_args(surfaces, 0)
         _check(self.L.drt_group_update_surfaces(self.g, ptr, first, n, flags | (SURFACES_REBUILD if rebuild else 0)), "drt_group_update_surfaces")
+
+    def update_spectra(self, rows, first=0):
+        """drt_group_update_spectra: as Renderer.update_spectra in host mode (numpy rows)"""
+        if _is_tensor(rows):
+            raise ValueError("Group.update_spectra: numpy rows (a group takes host pointers only)")
+        ptr, n, flags, _keep = _spectra_args(rows, self.S, 0)
+        _check(self.L.drt_group_update_spectra(self.g, ptr, first, n, flags), "drt_group_update_spectra")
+
+    def update_materials(self, materials, first=0):
+        """drt_group_update_materials: as Renderer.update_materials"""
+        ptr, n, _keep = _materials_args(materials)
+        _check(self.L.drt_group_update_materials(self.g, ptr, first, n, 0), "drt_group_update_materials")
 
     def rebuild_hierarchy(self):
         """drt_group_rebuild_hierarchy: as Renderer.rebuild_hierarchy, every context from its own device copy of the surfaces"""

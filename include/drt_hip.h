@@ -611,6 +611,50 @@ typedef struct drt_update_report
 /* Waits for the last update's kernels. */
 int drt_get_update_report(drt_context *ctx, drt_update_report *out);
 
+/*
+ * Material updates: new spectra and parameters for a live context -- a wall's colour, a light's spectrum or level, the glass's index,
+ * the gold's n and k, a lobe's shininess or roughness -- where the only way used to be drt_destroy + drt_create. DESIGN.md section 5i.
+ *
+ * The rule is 5g's: after a successful call the context gives, for every later call -- drt_render, the adaptive calls, the denoiser,
+ * features, mattes, ray queries, ray films, drt_read_* -- bit for bit the results of a fresh context that drt_create would make from the
+ * scene with those SPD rows or material parameters replaced, with the same drt_params, surfaces and camera: films, hit logs, the counting
+ * fields of drt_stats, RNG draw counts and query answers. The same three things may differ from that fresh context, because none can
+ * change a result bit: the shape of the hierarchy, the size of the record pool, and the shade kernel's dark-skip choice. The pool is NOT
+ * measured again, though a material edit can lengthen paths (an index of refraction, a roughness): a launch that runs out of it is
+ * rendered again by the existing mechanism, and drt_stats.redone_launches shows it.
+ *
+ * History does not matter: the context keeps the caller's raw rows (a host copy from drt_create, a device copy made at the first
+ * update), an update writes its range into that copy, and every derived table -- the diffuse / PI rows, the Fresnel pair rows, the
+ * materials' two refract samples around 630 nm, the trace kernel's tail columns -- is made again from all of it: update A then update B
+ * equals update B alone. Both calls need a film without samples (a fresh context, or drt_reset_film), as drt_update_surfaces does, and
+ * both work under a bound ray table and in DRT_MODE_XYZ.
+ *
+ * drt_update_spectra gives rows [first_row, first_row + count) of the scene's SPD table (drt_scene.spds numbering) the values in
+ * `rows`, [count][num_wavelengths] doubles. Any double is a legal value: the rule is whatever a fresh context makes of it, a NaN
+ * included. The rows named by drt_scene.cmf_rw / cmf_x / cmf_y / cmf_z are the observer, not a material, and a range that holds one is
+ * refused. Host mode (flags 0): the caller's array is free when the call returns. Device mode (DRT_SPECTRA_DEVICE): `rows` is memory on
+ * the context's device; the work is enqueued on the context's stream and the call returns without waiting (the rows must stay until
+ * the stream has passed it). There is nothing in it the host cannot check, so there is no status word.
+ *
+ * drt_update_materials takes whole drt_material records for materials [first, first + count) and accepts a difference in shininess and
+ * roughness only: is_black_body, is_emissive, num_bdsfs, every bdsfs[j] below num_bdsfs, dir_func and all six SPD indices must equal
+ * what the context holds (so the light list, the record width, the SPD table's layout and the kernel instantiations stay as drt_create
+ * chose them; a material gets another colour by drt_update_spectra on its row). Host memory only; `flags` must be 0.
+ *
+ * Both calls check everything before anything changes and are refused, with a message and the context exactly as it was, for: a null
+ * pointer with count > 0, a range beyond the table, unknown flag bits, a film with samples, a colour-matching row, a material field
+ * other than the two (the message names the first material and field that differs). count == 0 is a successful no-op (whatever the
+ * film holds). After either call results that describe the old scene are stale: drt_read_features / drt_read_mattes of a pass taken
+ * before it are refused. Everything is rewritten in place on the context's stream, so what was enqueued before stays ordered before it.
+ */
+#define DRT_SPECTRA_DEVICE 1u /* `rows` is device memory on the context's device */
+int drt_update_spectra(drt_context *ctx, const double *rows /* [count][S] */, uint32_t first_row, uint32_t count, uint32_t flags);
+int drt_update_materials(drt_context *ctx, const drt_material *materials, uint32_t first, uint32_t count, uint32_t flags /* 0 */);
+/* Every context is checked, and every device's staging copy is made, before any context is changed. Host pointers only. Same bits for
+ * any device list. */
+int drt_group_update_spectra(drt_group *g, const double *rows, uint32_t first_row, uint32_t count, uint32_t flags /* 0: host memory */);
+int drt_group_update_materials(drt_group *g, const drt_material *materials, uint32_t first, uint32_t count, uint32_t flags /* 0 */);
+
 /* Shape of the bounding-volume hierarchy drt_create() builds for scenes too large for LDS: node count, surfaces in
  * leaves, levels, and the traversal stack's capacity in entries (one per level at most; drt_create() refuses a deeper tree).
  * Host only: runs without a GPU. */

@@ -2,7 +2,7 @@
 """Per-kernel register / spill / scratch / occupancy figures of libdrt_hip.so's kernels, from the compiler's own output: the device
 assembly of csrc/drt_launcher.hip (the Makefile's flags plus -S -gline-tables-only) and the kernel metadata at its end. Extra
 arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring | group] [--loops] [-D...]
-A filter that names a group (GROUPS below: `features`, `mattes`, `rays`, `rayfilm`, `update`, `build`) stands for the group's kernels.
+A filter that names a group (GROUPS below: `features`, `mattes`, `rays`, `rayfilm`, `update`, `build`, `material`) stands for the group's kernels.
 
 Columns: VGPRs, SGPRs, `sspill` / `vspill` = the metadata's .sgpr_spill_count / .vgpr_spill_count, scratch bytes per lane, static
 LDS, occupancy (waves per SIMD, from the VGPR count), `valu` = vector ALU instructions in the kernel's text, `lanemv` = how many of
@@ -34,7 +34,9 @@ GROUPS = {"features": ("drt_feature_kernel", "drt_feature_bvh_kernel", "drt_feat
           "update": ("drt_surface_derive_kernel", "drt_bvh_leaf_kernel", "drt_bvh_refit_kernel"),
           # device hierarchy builds (drt_rebuild_hierarchy)
           "build": ("drt_build_init_kernel", "drt_build_bounds_kernel", "drt_build_keys_kernel", "drt_build_count_kernel", "drt_build_scan_kernel",
-                    "drt_build_scatter_kernel", "drt_build_topology_kernel", "drt_build_refit_kernel")}
+                    "drt_build_scatter_kernel", "drt_build_topology_kernel", "drt_build_refit_kernel"),
+          # material updates (drt_update_spectra, drt_update_materials)
+          "material": ("drt_spectra_derive_kernel", "drt_spectra_finish_kernel")}
 
 # vector ALU mnemonics: v_* except the few that are not issued to the VALU
 _NOT_VALU = ("v_nop", "v_interp")
