@@ -19,6 +19,7 @@
 #pragma once
 
 #include "drt_device.h"
+#include <type_traits>
 #include "../../include/drt_hip.h"
 
 /* ---------------------------------------------------------------------------------------------- */
@@ -1679,12 +1680,32 @@ struct ShadeParams
                                              kernel has put every path's tail wavelengths into tail_stage, the tail pass only updates the film */
     double  *tail_stage;                  /* [n_pix * batch][tail_count]: per-sample results of the tail pass (see the kernel) */
     uint32_t cmf_rw, cmf_x, cmf_y, cmf_z; /* XYZ film mode: SPD rows of the white table and the colour-matching functions */
-    uint32_t tail_period_mains, pad1;  /* split queue with a tail: main-pass items between two tail items (<= main items per group) */
+    uint32_t tail_period_mains, no_fixed_lists; /* split queue with a tail: main-pass items between two tail items (<= main items per group);
+                                                   no_fixed_lists: DRT_NO_FIXED_LISTS, every non-plastic vertex of the main pass takes the general list */
     uint32_t items_per_group, n_items; /* work items: per group of `chunk` pixels, ceil(chunk/sub_pixels) main-pass items and, with a tail,
                                           one tail-pass item; items_per_group == 1: one item does the group's main pass and then its tail */
     const uint32_t *pixel_list;        /* the LIST instantiations: launch pixel q's film rows are tile pixel pixel_list[q]'s, and its */
     const uint32_t *sample_base;       /* first sample of this launch is sample_base[pixel_list[q]] + first_sample ([tile pixels]) */
 };
+
+/* The shade kernel's argument list, in its order: the kernarg segment has this very layout (as TraceConst above). What the queue
+ * reads once per work item, and the switches a vertex tests, are read from there where they are used -- a scalar load -- instead of
+ * being held in scalar registers (or parked in vector lanes) across the whole sample loop. */
+struct ShadeConst
+{
+    DevScene    sc;
+    ShadeParams sp;
+    const uint64_t     *records, *headers;
+    double             *film_pixels, *film_avgs, *film_vars;
+    unsigned long long *work_counter;
+};
+static_assert(sizeof(DevScene) % 8 == 0 && sizeof(ShadeParams) % 8 == 0, "ShadeConst mirrors the kernarg segment only while every argument ends on an 8-byte boundary");
+__device__ __forceinline__ const ShadeConst &shade_const()
+{
+    uint32_t off = 0;
+    asm volatile("" : "+s"(off));
+    return *(const ShadeConst *)((const char *)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
 
 __device__ __forceinline__ double word_as_double(uint64_t w) { return __longlong_as_double((long long)w); }
 
@@ -1722,11 +1743,22 @@ __device__ __forceinline__ double spd_at(SpdPtr spds, uint32_t S, uint32_t idx, 
  * checks): the Fresnel cases, their divisions and square roots and the registers they live in are not compiled in, and the shade kernel
  * that is left fits five waves per SIMD instead of four (config 3, all plastic: shade 1772 -> 1691 ms). Same bits: the cases left
  * are the same code (tests/test_gpu_parity.py flips DRT_NO_SIMPLE_SHADE). */
-template <bool SIMPLE = false>
-__device__ __forceinline__ double bdsf_at_wavelength(uint64_t list, uint32_t num_bdsfs, double diffuse_pi, double glossy, double mirror,
+/* FIXED_N != 0: the fixed-list form -- the list is FIXED_LIST and its length FIXED_N, both known to the compiler (the arguments
+ * `list` and `num_bdsfs` are not read): the loop below unrolls and the switch folds away, what is left is the listed functions' own
+ * code in the list's order with the same carry-over of bdsf_result (Q1) and the same sum, `R + (R + 0)` included. One body for both
+ * forms, so they cannot drift apart. The shade kernel's main pass takes this form for {mirror}, {dielectric reflectance, dielectric
+ * transmittance} and {smooth conductor} vertices; DRT_NO_FIXED_LISTS=1 (read when the context is created) sends them through the
+ * general form instead: same film, bit for bit (tests/test_gpu_fixed_lists.py flips it). */
+#define DRT_LIST_MIRROR ((uint64_t)DRT_BDSF_mirror_bdsf)
+#define DRT_LIST_GLASS ((uint64_t)DRT_BDSF_fs_dielectric_reflectance_bdsf | ((uint64_t)DRT_BDSF_fs_dielectric_transmittance_bdsf << 4))
+#define DRT_LIST_CONDUCTOR ((uint64_t)DRT_BDSF_fs_conductor_bdsf)
+template <bool SIMPLE = false, uint32_t FIXED_N = 0, uint64_t FIXED_LIST = 0>
+__device__ __forceinline__ double bdsf_at_wavelength(uint64_t list_arg, uint32_t num_bdsfs_arg, double diffuse_pi, double glossy, double mirror,
                                                      double ir, double tr, double te, double on_dot, double a_in, double spec,
                                                      double mn_dot, double ct_coef, uint32_t flags, bool paired)
 {
+    const uint64_t list = FIXED_N != 0u ? FIXED_LIST : list_arg;
+    const uint32_t num_bdsfs = FIXED_N != 0u ? FIXED_N : num_bdsfs_arg;
     double bdsf_result = 0.0;
     double reflectance = 0.0;
 /* The Fresnel terms are pure f64 arithmetic, so the optimiser would hoist them out of this loop and
@@ -1798,7 +1830,9 @@ __device__ __forceinline__ double bdsf_at_wavelength(uint64_t list, uint32_t num
  * inlined), the vignette (:615) and render_image's film update (:732-743) on accumulators kept in
  * registers. The film is read and written once per batch. Waves are persistent (SPD tables staged
  * into LDS once) and draw work items (pixel groups, or pieces of them: see the queue below) from a global counter,
- * because pixel cost varies.
+ * because pixel cost varies. Three kinds of vertex have straight-line code of their own in the main pass: the leading run of
+ * two-lobe plastic vertices, and -- unless DRT_NO_FIXED_LISTS is set (ShadeParams::no_fixed_lists) -- mirror, glass and
+ * smooth-conductor vertices (fixed_vertex); every other list goes through the general loop.
  */
 #ifndef SHADE_PREFETCH_REGS
 #define SHADE_PREFETCH_REGS 2 /* 64-word registers per path: 128 record words are prefetched, deeper paths fall back */
@@ -1832,7 +1866,6 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
     const uint32_t vw = sp.vertex_words;
     const uint32_t R = sp.tail_count;
     const uint32_t g = lane / R, j = lane - g * R;
-    const uint64_t pix_l = chunk_base + g;
     const bool act = g < (uint32_t)(chunk_end - chunk_base) && g < 64u / R;
     const uint32_t lam = sp.tail_first + j; /* < S by construction */
     const double *table = SPDS_IN_LDS ? (const double *)lds : sc.spds;
@@ -2068,14 +2101,23 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
         }
         __builtin_amdgcn_wave_barrier(); /* every lane is through the window before its headers are overwritten */
     }
-    const uint64_t pix_f = LIST ? (act ? (uint64_t)sp.pixel_list[pix_l] : 0u) : pix_l; /* its film row */
+    /* Phase B's own copies of g, j, the pixel and lam, re-read from g's and j's registers here: left alone, their 64-bit forms (the
+     * film rows' indices) are made at the kernel's entry and held in vector register pairs through every main-pass item, where
+     * there is none to spare */
+    uint32_t j_b = j;
+    asm volatile("" : "+v"(j_b));
+    const uint32_t lam_b = sp.tail_first + j_b;
+    uint32_t g_b = g;
+    asm volatile("" : "+v"(g_b));
+    const uint64_t pix_b = chunk_base + g_b;
+    const uint64_t pix_f = LIST ? (act ? (uint64_t)sp.pixel_list[pix_b] : 0u) : pix_b; /* its film row */
     double *px = film_pixels + pix_f * (uint64_t)(XYZ ? XYZ_FILM_WORDS : S + 1);
     double *pa = XYZ ? nullptr : film_avgs + pix_f * (uint64_t)S;
     double *pv = XYZ ? nullptr : film_vars + pix_f * (uint64_t)S;
-    const double *stage = sp.tail_stage + (pix_l * (uint64_t)sp.batch) * R + j;
+    const double *stage = sp.tail_stage + (pix_b * (uint64_t)sp.batch) * R + j_b;
     /* Phase B -- the film update (src/daily_ray_trace.c:732-743), the pixels' samples in order, all pixels in step */
     const uint32_t first = LIST ? sp.first_sample + (act ? sp.sample_base[pix_f] : 0u) : sp.first_sample; /* per lane group */
-    double f_sum = (act && !XYZ) ? px[lam] : 0.0, f_avg = (act && !XYZ) ? pa[lam] : 0.0, f_var = (act && !XYZ) ? pv[lam] : 0.0;
+    double f_sum = (act && !XYZ) ? px[lam_b] : 0.0, f_avg = (act && !XYZ) ? pa[lam_b] : 0.0, f_var = (act && !XYZ) ? pv[lam_b] : 0.0;
 #pragma unroll 4
     for (uint32_t k = 0; k < sp.n_samples; k += 1)
     {
@@ -2096,19 +2138,19 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
     if (XYZ)
     {
         /* the pixel's tail wavelengths, summed over its R lanes by the group's first lane */
-        const double rw = spd_at(table, S, sp.cmf_rw, lam);
-        const double x = act ? (spd_at(table, S, sp.cmf_x, lam) * f_sum * rw) : 0.0;
-        const double y = act ? (spd_at(table, S, sp.cmf_y, lam) * f_sum * rw) : 0.0;
-        const double z = act ? (spd_at(table, S, sp.cmf_z, lam) * f_sum * rw) : 0.0;
+        const double rw = spd_at(table, S, sp.cmf_rw, lam_b);
+        const double x = act ? (spd_at(table, S, sp.cmf_x, lam_b) * f_sum * rw) : 0.0;
+        const double y = act ? (spd_at(table, S, sp.cmf_y, lam_b) * f_sum * rw) : 0.0;
+        const double z = act ? (spd_at(table, S, sp.cmf_z, lam_b) * f_sum * rw) : 0.0;
         double X = 0.0, Y = 0.0, Z = 0.0;
         for (uint32_t t = 0; t < R; t += 1)
         {
-            const int src = (int)((lane - j + t) & 63u);
+            const int src = (int)((lane - j_b + t) & 63u);
             X += __shfl(x, src);
             Y += __shfl(y, src);
             Z += __shfl(z, src);
         }
-        if (act && j == 0)
+        if (act && j_b == 0)
         {
             px[4] += X;
             px[5] += Y;
@@ -2117,9 +2159,9 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
     }
     else if (act)
     {
-        px[lam] = f_sum;
-        pa[lam] = f_avg;
-        pv[lam] = f_var;
+        px[lam_b] = f_sum;
+        pa[lam_b] = f_avg;
+        pv[lam_b] = f_var;
     }
 }
 
@@ -2160,16 +2202,17 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
     for (;;)
     {
         /* draw the next work item (wave-uniform): part of a pixel group's main pass, its tail pass, or both */
+        const ShadeParams &qc = shade_const().sp; /* the queue's parameters, read here only */
         uint32_t item = 0;
         if (lane == 0) item = (uint32_t)atomicAdd(work_counter, 1ull);
         item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
-        if (item >= sp.n_items) break;
+        if (item >= qc.n_items) break;
         /* split queue: a group's tail pass is the longest item, so the tail items are dealt out early -- one at the head of
          * every period of 1 + tail_period_mains items, between main-pass pieces so that latency-bound tail waves and
          * arithmetic-bound main waves share the SIMDs -- and the launch ends on main-pass pieces only */
-        const bool split = sp.items_per_group > 1;
-        const bool inline_tail = sp.tail_count != 0;
-        const uint32_t mains_per_group = sp.items_per_group - (inline_tail ? 1u : 0u);
+        const bool split = qc.items_per_group > 1;
+        const bool inline_tail = qc.tail_count != 0;
+        const uint32_t mains_per_group = qc.items_per_group - (inline_tail ? 1u : 0u);
         bool tail_item = inline_tail;
         uint32_t group = item, sub = 0;
         if (split)
@@ -2177,8 +2220,8 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
             uint32_t m = item; /* index among the main-pass pieces */
             if (inline_tail)
             {
-                const uint32_t n_groups = sp.n_items / sp.items_per_group;
-                const uint32_t q = sp.tail_period_mains, mixed = n_groups * (q + 1u);
+                const uint32_t n_groups = qc.n_items / qc.items_per_group;
+                const uint32_t q = qc.tail_period_mains, mixed = n_groups * (q + 1u);
                 if (item < mixed)
                 {
                     const uint32_t period = item / (q + 1u), r = item - period * (q + 1u);
@@ -2198,17 +2241,17 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                 sub = m - group * mains_per_group;
             }
         }
-        const uint64_t chunk_base = (uint64_t)group * sp.chunk;
-        const uint64_t chunk_end = (chunk_base + sp.chunk < sp.n_pix) ? chunk_base + sp.chunk : sp.n_pix;
+        const uint64_t chunk_base = (uint64_t)group * qc.chunk;
+        const uint64_t chunk_end = (chunk_base + qc.chunk < qc.n_pix) ? chunk_base + qc.chunk : qc.n_pix;
         uint64_t main_base = chunk_base, main_end = chunk_end;
         if (split)
         {
-            main_base = chunk_base + (uint64_t)sub * sp.sub_pixels;
-            main_end = (main_base + sp.sub_pixels < chunk_end) ? main_base + sp.sub_pixels : chunk_end;
+            main_base = chunk_base + (uint64_t)sub * qc.sub_pixels;
+            main_end = (main_base + qc.sub_pixels < chunk_end) ? main_base + qc.sub_pixels : chunk_end;
             if (tail_item || main_base > chunk_end) main_base = main_end = chunk_end; /* nothing for the main pass */
         }
 
-      if (sp.mode == 2u) main_base = main_end;
+      if (qc.mode == 2u) main_base = main_end;
       for (uint64_t pix = main_base; pix < main_end; pix += 1)
       {
 
@@ -2517,11 +2560,102 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                 }
                 const uint64_t list = readlane64(src, lane0 + 0);
                 const uint64_t w1 = readlane64(src, lane0 + 1);
+                const uint32_t num_bdsfs = (uint32_t)(w1 & 0xFFu);
+                const uint32_t sflags = (uint32_t)(w1 >> 8) & 0xFFu;
+                /* The specular lists, straight-line: bdsf_at_wavelength's fixed-list form, so no loop and no switch per evaluation, and
+                 * only what the list reads leaves the record -- the flags (w1), for the Fresnel lists the media word and on_dot, dir_pdf,
+                 * and of a light its flag word and `c` -- and only its SPD rows are read (one for a mirror, three otherwise). Words
+                 * that are only ever multiplicands (on_dot, dir_pdf, c) come as broadcast LDS reads from the sample's slot while the
+                 * vertex is among the prefetched ones, as in the plastic path. Same operations in the same order as the general list
+                 * below; the light block keeps `((sum + 0) * em) * c` whatever the flags say (em or c may be infinite or NaN).
+                 * ONE body for the three lists, which differ in one scalar comparison per evaluation: three bodies of their own cost
+                 * the kernel ten scalar spills and a vector register pair in scratch (tests/test_kernel_spill_budget.py). */
+                auto fixed_vertex = [&](uint32_t kind) { /* wave-uniform: 0 {mirror}, 1 {dielectric reflectance, transmittance}, 2 {smooth conductor} */
+                    const bool fresnel = !SIMPLE && kind != 0u;
+                    const bool in_lds = v < n_fast;
+                    const uint64_t *vwords = rec_words + v * vw;
+                    uint32_t i_r0 = (uint32_t)(w1 >> 48) & 0xFFFFu, i_r1 = 0, i_r2 = 0; /* the mirror's one row, or the three Fresnel rows */
+                    bool paired = false;
+                    double on_dot = 0.0;
+                    double r0[NSETS], r1[NSETS], r2[NSETS];
+#pragma unroll
+                    for (int k = 0; k < NSETS; k += 1) r1[k] = r2[k] = 0.0;
+                    if (fresnel)
+                    {
+                        fresnel_rows(readlane64(src, lane0 + 2), i_r0, i_r1, i_r2, paired);
+                        on_dot = in_lds ? word_as_double(vwords[3]) : word_as_double(readlane64(src, lane0 + 3));
+#pragma unroll
+                        for (int k = 0; k < NSETS; k += 1)
+                        {
+                            r1[k] = spd_at(table, S, i_r1, lam_c[k]);
+                            r2[k] = spd_at(table, S, i_r2, lam_c[k]);
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < NSETS; k += 1) r0[k] = spd_at(table, S, i_r0, lam_c[k]);
+                    /* the list's sum for one wavelength set: the fixed-list forms, chosen by one scalar comparison */
+                    auto eval = [&](int k, uint32_t flags) -> double {
+                        if (SIMPLE || kind == 0u)
+                            return bdsf_at_wavelength<SIMPLE, 1u, DRT_LIST_MIRROR>(0ull, 0u, 0.0, 0.0, r0[k], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, flags, false);
+                        if (kind == 1u)
+                            return bdsf_at_wavelength<SIMPLE, 2u, DRT_LIST_GLASS>(0ull, 0u, 0.0, 0.0, 0.0, r0[k], r1[k], r2[k], on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
+                        return bdsf_at_wavelength<SIMPLE, 1u, DRT_LIST_CONDUCTOR>(0ull, 0u, 0.0, 0.0, 0.0, r0[k], r1[k], r2[k], on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
+                    };
+                    for (uint32_t l = 0; l < sp.n_lights; l += 1) /* direct_light_contribution, :272-332 */
+                    {
+                        if (l == 0 && v < 8u && !((vis0_mask >> v) & 1u)) continue; /* known from the header: not visible */
+                        const uint32_t off = REC_VERTEX_WORDS + l * REC_LIGHT_WORDS;
+                        uint64_t lw0;
+                        double c;
+                        if (off + REC_LIGHT_WORDS <= 64 || v < n_fast)
+                        {
+                            lw0 = readlane64(src, lane0 + off);
+                            c = in_lds ? word_as_double(vwords[off + 1u]) : word_as_double(readlane64(src, lane0 + off + 1u));
+                        }
+                        else
+                        {
+                            /* light block beyond the register: uniform loads straight from the record */
+                            const uint64_t *lp = path_vertex(records, sp.block_words, vw, readlane64(h2, s), readlane64(h3, s), v) + off;
+                            lw0 = readlane64(lp[0], 0);
+                            c = word_as_double(lp[1]);
+                        }
+                        const uint32_t lflags = (uint32_t)(lw0 >> 16) & 0xFFu;
+                        if (!(lflags & FLAG_VISIBLE)) continue;
+                        const uint32_t i_em = (uint32_t)(lw0 & 0xFFFFu);
+#pragma unroll
+                        for (int k = 0; k < NSETS; k += 1)
+                        {
+                            double reflectance = eval(k, lflags);
+                            contribution[k] = contribution[k] + reflectance;                      /* :323 */
+                            contribution[k] = contribution[k] * spd_at(table, S, i_em, lam_c[k]); /* :324 */
+                            contribution[k] = contribution[k] * c;                                /* :326-327 */
+                        }
+                    }
+#pragma unroll
+                    for (int k = 0; k < NSETS; k += 1)
+                    {
+                        dst[k] = dst[k] + throughput[k] * contribution[k]; /* :461-462 */
+                        double reflectance = eval(k, sflags);
+                        const double dir_pdf = in_lds ? word_as_double(vwords[4]) : word_as_double(readlane64(src, lane0 + 4));
+                        reflectance = reflectance * dir_pdf;         /* :468 */
+                        throughput[k] = throughput[k] * reflectance; /* :469 */
+                    }
+                };
+                if (!shade_const().sp.no_fixed_lists)
+                {
+                    uint32_t kind = 3u;
+                    if (num_bdsfs == 1u && list == DRT_LIST_MIRROR) kind = 0u;
+                    if (!SIMPLE && num_bdsfs == 2u && list == DRT_LIST_GLASS) kind = 1u;
+                    if (!SIMPLE && num_bdsfs == 1u && list == DRT_LIST_CONDUCTOR) kind = 2u;
+                    if (kind != 3u)
+                    {
+                        fixed_vertex(kind);
+                        continue;
+                    }
+                }
                 const uint64_t w2 = readlane64(src, lane0 + 2);
                 const double on_dot = word_as_double(readlane64(src, lane0 + 3));
                 const double dir_pdf = word_as_double(readlane64(src, lane0 + 4));
-                const uint32_t num_bdsfs = (uint32_t)(w1 & 0xFFu);
-                const uint32_t sflags = (uint32_t)(w1 >> 8) & 0xFFu;
                 const uint32_t i_diffuse = (uint32_t)(w1 >> 16) & 0xFFFFu, i_glossy = (uint32_t)(w1 >> 32) & 0xFFFFu;
                 const uint32_t i_mirror = (uint32_t)(w1 >> 48) & 0xFFFFu;
                 uint32_t i_ir, i_tr, i_te; /* or the pair's rows in their place */
@@ -2546,6 +2680,7 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                 }
                 for (uint32_t l = 0; l < sp.n_lights; l += 1) /* direct_light_contribution, :272-332 */
                 {
+                    if (l == 0 && v < 8u && !((vis0_mask >> v) & 1u)) continue; /* known from the header: not visible, nothing to lift */
                     const uint32_t off = REC_VERTEX_WORDS + l * REC_LIGHT_WORDS;
                     uint64_t lw[REC_LIGHT_WORDS];
                     if (off + REC_LIGHT_WORDS <= 64 || v < n_fast)

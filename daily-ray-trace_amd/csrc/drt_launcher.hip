@@ -99,6 +99,7 @@ struct drt_context
                                          and mirror vertices only, and those without a vertex */
     bool      tail_all_staged = false; /* ... and in this scene that is every path: the shade kernel's tail pass has nothing to replay */
     bool      dark_skip = true;        /* the shade kernel's instantiation that passes over samples worth 0 in pixels nothing has reached yet */
+    bool      no_fixed_lists = false;  /* DRT_NO_FIXED_LISTS, read when the context is created: the shade kernel's fixed-list bodies are not taken */
     bool      simple_bdsfs = false;    /* no material lists anything but bp_diffuse_bdsf, bp_glossy_bdsf, mirror_bdsf: the shade kernel without the Fresnel code */
     const double *d_spd_tail = nullptr; /* [n_spd][tail_count]: the SPD table's tail columns */
 
@@ -756,6 +757,7 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
         const size_t extra = (size_t)d.n_spd * tc * 8 + (size_t)(TRACE_BLOCK / 64) * 2 * tc * 64 * 8;
         /* every list of every material (used by a surface or not: a ray can only meet a surface's, but the check is cheap) */
         ctx->simple_bdsfs = !getenv("DRT_NO_SIMPLE_SHADE");
+        ctx->no_fixed_lists = getenv("DRT_NO_FIXED_LISTS") != nullptr; /* A/B: the main pass's mirror / glass / smooth-conductor vertices through the general list */
         for (uint32_t i = 0; i < scene->num_materials; i += 1)
             for (uint32_t j = 0; j < mats[i].num_bdsfs; j += 1)
             {
@@ -1480,6 +1482,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     sp.tail_count = ctx->tail_count;
     sp.tail_stage = ctx->d_tail_stage;
     sp.light0_em_spd = ctx->light0_em_spd;
+    sp.no_fixed_lists = ctx->no_fixed_lists ? 1u : 0u;
     sp.tail_staged = (ctx->tail_all_staged && ctx->d_tail_stage) ? 1u : 0u;
     sp.pixel_list = list;
     sp.sample_base = list ? ctx->d_counts : nullptr;
