@@ -147,8 +147,11 @@ struct DevRayTable
 /* samples again with launches sized for the worst case (drt_launcher.hip, redo_batches).           */
 /*                                                                                                  */
 /*  path header (4 words, own array, indexed by slot = pixel * batch + sample_in_batch):           */
-/*     w0 = n_shaded (bits 0-15) | term (16-23: 0 none/escape, 1 emissive hit) | light 0 visible from vertex v < 8 (24-31) |
- *          emission SPD (32-47) | vertex v < 16 has the two-lobe plastic list (48-63)                                      */
+/*     w0 = n_shaded (bits 0-15) | term (16-23: bits 0-1: 0 none/escape, 1 emissive hit; bits 2-5: resume vertex k, see below;
+ *          bit 6: tail staged; bit 7: not done) | light 0 visible from vertex v < 8 (24-31) |
+ *          emission SPD (32-47) | vertex v < 16 has the two-lobe plastic list (48-63)
+ *          resume vertex k (1-15, 0: none): the trace kernel carried the path's tail wavelengths over vertices 0 .. k-1 and left
+ *          (throughput, dst) after vertex k-1 in tail_resume / tail_stage: the shade kernel's tail pass replays from vertex k   */
 /*     w1 = vignette (double)                                                                      */
 /*     w2 = block of vertices 0-3 (bits 0-31) | block of vertices 4-7 (32-63)                       */
 /*     w3 = block of vertices 8-11 (bits 0-31) | TABLE block (32-63): a pool block used as an array */
@@ -174,7 +177,9 @@ struct DevRayTable
 #define REC_HEADER_BLOCKS 3 /* blocks named in the header itself; further ones through the table block */
 #define HDR_TERM_NOT_DONE 0x80u /* header `term` byte of a path that found the pool exhausted */
 #define HDR_TERM_TAIL_STAGED 0x40u /* header `term` byte, or'ed in: the trace kernel has put the path's tail wavelengths into tail_stage */
-#define HDR_TERM_MASK 0x3Fu
+#define HDR_TERM_MASK 0x03u /* how the path ended: 0 or 1 */
+#define HDR_TERM_RESUME_SHIFT 2u /* header `term` byte, bits 2-5: the vertex the tail pass resumes the path from (0: from the start) */
+#define HDR_TERM_RESUME_MASK 0xFu
 #define REC_VERTEX_WORDS 10
 #define REC_LIGHT_WORDS 6
 #define FLAG_EQR 1u
@@ -196,6 +201,8 @@ struct TraceParams
     /* the tail wavelengths (S mod 64 of them) of plastic-only paths, done here: see "Tail wavelengths in the trace kernel" */
     double       *tail_stage;            /* [n_pix * batch][tail_count] per-sample values the shade kernel's film phase reads; NULL: off */
     const double *spd_tail;              /* [n_spd][tail_count]: the SPD table's tail columns */
+    double       *tail_resume;           /* [n_pix * batch][tail_count], indexed as tail_stage: the carried throughput of a path that stopped being
+                                            carried at a vertex k >= 1 (its dst goes to tail_stage, k into the header); NULL: such paths are replayed whole */
     uint32_t      tail_count, n_spd;
     /* adaptive rounds (the LIST instantiations only): launch pixel q is tile pixel pixel_list[q]; n_pix counts the list's entries.
      * Headers, records, the hit log and tail_stage stay indexed by q. Tile pixel t's samples start at sample_base[t] (the count it holds
@@ -1244,7 +1251,8 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
     uint64_t rs = 1, hit_row = 0; /* hit_row: the path's row in the hit log, ordered (sample, pixel) */
     uint32_t depth = 0, shaded = 0;
     uint32_t vis0_mask = 0;    /* bit v: light 0 is visible from shaded vertex v (< 8); header bits 24-31 */
-    uint32_t plastic_mask = 0; /* bit v: shaded vertex v (< 16) has the two-lobe plastic list; header bits 48-63, read by the shade kernel's tail pass */
+    uint32_t plastic_mask = 0; /* bit v: shaded vertex v (< 16) has the two-lobe plastic list; header bits 48-63, read by the shade kernel's tail pass.
+                                  Bits 16-19 (they do not reach the header's field): the vertex k, 1-15, at which the path stopped being carried */
     V3 ro = v3(0, 0, 0), rd = v3(0, 0, 0);
     uint64_t *hdr = nullptr;
     uint32_t blk = 0, tbl = 0;              /* the pool block of the current four vertices; the path's table block (deep paths) */
@@ -1554,7 +1562,13 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                             tail_state[(2u * j + 1u) * 64u] = dst;
                         }
                     }
-                    else tail_ok = false; /* any other material: the shade kernel's tail pass replays this path */
+                    else
+                    {
+                        /* any other material: the shade kernel's tail pass replays this path -- from this vertex on, if what was carried
+                         * so far is kept when the path ends (tail_state is not written again until then) */
+                        tail_ok = false;
+                        if (shaded <= HDR_TERM_RESUME_MASK) plastic_mask |= shaded << 16;
+                    }
                 }
                 vrec[0] = mat.bdsf_packed;
                 vrec[1] = (uint64_t)mat.num_bdsfs | ((uint64_t)(e.flags | mat.vertex_flags) << 8) | ((uint64_t)((uint32_t)mat.diffuse_spd & 0xFFFFu) << 16) |
@@ -1588,6 +1602,26 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                         st[j] = dst * vignette;
                     }
                     staged = HDR_TERM_TAIL_STAGED;
+                }
+                else if (TAIL && (plastic_mask >> 16) != 0u)
+                {
+                    /* carried as far as vertex k - 1: throughput and dst after it are kept for the tail pass, which starts at vertex k */
+                    double *rt = LC.tp.tail_resume;
+                    if (rt != nullptr)
+                    {
+                        const uint64_t at = (uint64_t)(hdr - headers) / REC_HEADER_WORDS * TR;
+                        double *st = LC.tp.tail_stage + at;
+                        rt += at;
+                        const uint32_t tr = pinned_scalar(TR);
+#pragma unroll
+                        for (uint32_t j = 0; j < DRT_TRACE_TAIL_MAX; j += 1)
+                        {
+                            if (j >= tr) break;
+                            rt[j] = tail_state[(2u * j) * 64u];
+                            st[j] = tail_state[(2u * j + 1u) * 64u];
+                        }
+                        staged = (plastic_mask >> 16) << HDR_TERM_RESUME_SHIFT;
+                    }
                 }
                 hdr[0] = (uint64_t)shaded | ((uint64_t)(term | staged) << 16) | ((uint64_t)(term_spd & 0xFFFFu) << 32) | ((uint64_t)plastic_mask << 48) | ((uint64_t)vis0_mask << 24);
                 alive = false;
@@ -1679,6 +1713,8 @@ struct ShadeParams
     uint32_t light0_em_spd, tail_staged;  /* emission SPD row of light 0 (what every light block of light 0 says); tail_staged: the trace
                                              kernel has put every path's tail wavelengths into tail_stage, the tail pass only updates the film */
     double  *tail_stage;                  /* [n_pix * batch][tail_count]: per-sample results of the tail pass (see the kernel) */
+    const double *tail_resume;            /* [n_pix * batch][tail_count]: throughput of the paths the trace kernel carried part of the way (header: resume
+                                             vertex k), their dst being in tail_stage; NULL: no header names a resume vertex */
     uint32_t cmf_rw, cmf_x, cmf_y, cmf_z; /* XYZ film mode: SPD rows of the white table and the colour-matching functions */
     uint32_t tail_period_mains, no_fixed_lists; /* split queue with a tail: main-pass items between two tail items (<= main items per group);
                                                    no_fixed_lists: DRT_NO_FIXED_LISTS, every non-plastic vertex of the main pass takes the general list */
@@ -1973,10 +2009,23 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     vignette = word_as_double(w[1]);
                     ph2 = w[2];
                     n_shaded = (uint32_t)(ph0 & 0xFFFFu);
-                    v = 0;
-                    vcur = records + (uint64_t)(uint32_t)ph2 * sp.block_words; /* vertex 0 opens the header's first block */
+                    /* the vertex to start from: 0, or the one at which the trace kernel stopped carrying this path's tail wavelengths. What
+                     * it had by then is the same operations in the same order as the steps below, so the replay takes it over: throughput
+                     * from tail_resume, dst from the path's own staging slot (overwritten with the sample's value when the path closes).
+                     * Neither load waits for anything but the header, so they travel with the first record's loads */
+                    const uint32_t k = ((uint32_t)(ph0 >> 16) >> HDR_TERM_RESUME_SHIFT) & HDR_TERM_RESUME_MASK;
+                    v = k;
                     throughput = 1.0;
                     dst = 0.0;
+                    if (k != 0u)
+                    {
+                        /* one address for both loads (tail_resume is indexed as tail_stage: the distance between them is a scalar) */
+                        const double *at = sp.tail_stage + (slot * R + j);
+                        dst = at[0];
+                        throughput = at[shade_const().sp.tail_resume - sp.tail_stage];
+                        vcur = path_vertex(records, sp.block_words, vw, ph2, deep_blocks(k), k);
+                    }
+                    else vcur = records + (uint64_t)(uint32_t)ph2 * sp.block_words; /* vertex 0 opens the header's first block */
                     busy = true;
                 }
                 next_task += (uint32_t)__popcll(want);
@@ -2069,6 +2118,30 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     fresnel_rows(w2, f0, f1, f2, paired);
                     const double ir = SIMPLE ? 0.0 : spd_at(table, S, f0, lam), tr = SIMPLE ? 0.0 : spd_at(table, S, f1, lam), te = SIMPLE ? 0.0 : spd_at(table, S, f2, lam);
                     double contribution = 0.0;
+                    /* glass lanes (a quarter and more of what is replayed) take the fixed-list form the main pass uses: of the record
+                     * only the words that list reads, no diffuse / glossy / mirror row. One branch on the lane's list inside this step,
+                     * not a third vote class: no iteration serves fewer lanes than before */
+                    const bool glass = !SIMPLE && num_bdsfs == 2u && list == DRT_LIST_GLASS;
+                    if (glass)
+                    {
+                        for (uint32_t l = 0; l < sp.n_lights; l += 1)
+                        {
+                            const uint64_t *lrec = vrec + REC_VERTEX_WORDS + l * REC_LIGHT_WORDS;
+                            const uint64_t lw0 = lrec[0];
+                            const uint32_t lflags = (uint32_t)(lw0 >> 16) & 0xFFu;
+                            if (!(lflags & FLAG_VISIBLE)) continue;
+                            double reflectance = bdsf_at_wavelength<SIMPLE, 2, DRT_LIST_GLASS>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, on_dot, 0.0, 0.0, 0.0, 0.0, lflags, paired);
+                            contribution = contribution + reflectance;
+                            contribution = contribution * spd_at(table, S, (uint32_t)(lw0 & 0xFFFFu), lam);
+                            contribution = contribution * word_as_double(lrec[1]);
+                        }
+                        dst = dst + throughput * contribution;
+                        double reflectance = bdsf_at_wavelength<SIMPLE, 2, DRT_LIST_GLASS>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, on_dot, 0.0, 0.0, 0.0, 0.0, sflags, paired);
+                        reflectance = reflectance * dir_pdf;
+                        throughput = throughput * reflectance;
+                    }
+                    else
+                    {
                     for (uint32_t l = 0; l < sp.n_lights; l += 1)
                     {
                         const uint64_t *lrec = vrec + REC_VERTEX_WORDS + l * REC_LIGHT_WORDS;
@@ -2087,6 +2160,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                                                             word_as_double(vrec[7]), word_as_double(vrec[8]), sflags, paired);
                     reflectance = reflectance * dir_pdf;
                     throughput = throughput * reflectance;
+                    }
                     v += 1;
                     if (v < n_shaded) vcur = (v & (REC_BLOCK_VERTICES - 1u)) != 0u ? vcur + vw : path_vertex(records, sp.block_words, vw, ph2, deep_blocks(v), v); /* the next record: the one behind, or a new block */
                 }

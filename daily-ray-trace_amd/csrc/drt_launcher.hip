@@ -76,6 +76,8 @@ struct drt_context
     uint64_t *d_records = nullptr, *d_headers = nullptr;
     uint32_t  light0_em_spd = 0;      /* emission SPD row of the first light (0 when there is none) */
     double   *d_tail_stage = nullptr; /* [n_pix * batch][tail_count]: per-sample results of the shade kernel's tail pass */
+    double   *d_tail_resume = nullptr; /* [n_pix * batch][tail_count]: the throughput the trace kernel carried for a path it handed over at a vertex
+                                          k >= 1 (TraceParams::tail_resume); only where trace_tail && !tail_all_staged && tail_resume */
     uint32_t  batch_spp = 1;
     uint32_t  vertex_words = 0, vertex_shift = 0, block_words = 0; /* a vertex record, its log2, a pool block (four vertices), in 8-byte words */
     uint64_t  pool_blocks = 0;          /* blocks in d_records */
@@ -98,6 +100,7 @@ struct drt_context
     bool      trace_tail = false;     /* the trace kernel carries the tail wavelengths of the paths it can (drt_trace_kernel<true, true>): those of plastic
                                          and mirror vertices only, and those without a vertex */
     bool      tail_all_staged = false; /* ... and in this scene that is every path: the shade kernel's tail pass has nothing to replay */
+    bool      tail_resume = false;     /* ... and where it is not, the tail pass resumes a path from the vertex the trace kernel carried it to (DRT_TAIL_RESUME=0: off) */
     bool      dark_skip = true;        /* the shade kernel's instantiation that passes over samples worth 0 in pixels nothing has reached yet */
     bool      no_fixed_lists = false;  /* DRT_NO_FIXED_LISTS, read when the context is created: the shade kernel's fixed-list bodies are not taken */
     bool      simple_bdsfs = false;    /* no material lists anything but bp_diffuse_bdsf, bp_glossy_bdsf, mirror_bdsf: the shade kernel without the Fresnel code */
@@ -778,6 +781,10 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
         ctx->trace_tail = ctx->scene_in_lds && sets == 1 && tc > 0 && tc <= 8 && n_lights == 1 && ctx->trace_lds + extra <= 48 * 1024 && !(e && *e == '0') &&
                           (all_simple || !(e && *e == '2'));
         ctx->tail_all_staged = ctx->trace_tail && all_simple;
+        /* DRT_TAIL_RESUME=0: paths the trace kernel stops carrying are replayed from vertex 0 (the parity tests' A/B); it travels as a null
+         * tail_resume pointer in both kernels' parameters */
+        const char *er = getenv("DRT_TAIL_RESUME");
+        ctx->tail_resume = ctx->trace_tail && !ctx->tail_all_staged && !(er && *er == '0');
         if (ctx->trace_tail)
         {
             std::vector<double> cols((size_t)d.n_spd * tc);
@@ -1064,7 +1071,8 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
      */
     const size_t block_bytes = (size_t)ctx->block_words * 8;
     const uint64_t npx = std::max<uint64_t>(ctx->n_pix, 1);
-    const size_t per_path_fixed = REC_HEADER_WORDS * 8 + (size_t)ctx->tail_count * 8 + (ctx->bvh_pipeline ? sizeof(PrimaryHit) + sizeof(uint64_t) : 0);
+    const size_t per_path_fixed = REC_HEADER_WORDS * 8 + (size_t)ctx->tail_count * 8 * (ctx->tail_resume ? 2 : 1) + /* tail_stage, and tail_resume beside it */
+                                  (ctx->bvh_pipeline ? sizeof(PrimaryHit) + sizeof(uint64_t) : 0);
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     ctx->est_blocks_per_path = (double)ctx->worst_blocks_per_path;
@@ -1163,6 +1171,7 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         HIP_TRY(hipMalloc((void **)&ctx->d_queue, (size_t)npx * batch * sizeof(uint64_t)));
     }
     if (ctx->tail_count) HIP_TRY(hipMalloc((void **)&ctx->d_tail_stage, (size_t)npx * batch * ctx->tail_count * 8));
+    if (ctx->tail_count && ctx->tail_resume) HIP_TRY(hipMalloc((void **)&ctx->d_tail_resume, (size_t)npx * batch * ctx->tail_count * 8));
     if (const char *e = getenv("DRT_DARK_SKIP")) ctx->dark_skip = atoi(e) != 0; /* A/B switch of the parity tests: same film either way */
     if (getenv("DRT_VERBOSE"))
         fprintf(stderr, "drt: %d CUs, trace %d blocks/CU (lds %zu), shade %d blocks/CU (lds %zu), batch %u, %.3f blocks/path measured (worst %u), pool %.2f GB\n",
@@ -1205,6 +1214,7 @@ extern "C" void drt_destroy(drt_context *ctx)
     (void)hipFree(ctx->d_primary);
     (void)hipFree(ctx->d_queue);
     (void)hipFree(ctx->d_tail_stage);
+    (void)hipFree(ctx->d_tail_resume);
     (void)hipFree(ctx->d_hits);
     (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_xyz);
@@ -1394,6 +1404,7 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
     tp.batch = stride ? stride : ctx->batch_spp; /* sample slots per pixel in the header array (a launch over fewer rows may take more samples) */
     tp.pool_blocks = (uint32_t)ctx->pool_blocks;
     tp.tail_stage = ctx->trace_tail ? ctx->d_tail_stage : nullptr;
+    tp.tail_resume = tp.tail_stage ? ctx->d_tail_resume : nullptr;
     tp.spd_tail = ctx->d_spd_tail;
     tp.tail_count = ctx->tail_count;
     tp.n_spd = ctx->dsc.n_spd;
@@ -1481,6 +1492,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     sp.tail_first = ctx->tail_first;
     sp.tail_count = ctx->tail_count;
     sp.tail_stage = ctx->d_tail_stage;
+    sp.tail_resume = ctx->d_tail_resume;
     sp.light0_em_spd = ctx->light0_em_spd;
     sp.no_fixed_lists = ctx->no_fixed_lists ? 1u : 0u;
     sp.tail_staged = (ctx->tail_all_staged && ctx->d_tail_stage) ? 1u : 0u;
