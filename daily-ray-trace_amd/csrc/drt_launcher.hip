@@ -2469,27 +2469,43 @@ extern "C" int drt_group_reset_film(drt_group *g)
     return 0;
 }
 
-/* rows k, k+n, ... of a whole-tile host buffer <-> device k's contiguous rows: one strided copy */
-static int group_copy(drt_group *g, double *host, int which, bool to_device)
+/* Of n devices, device k holds rows k, k + n, ... of the tile, contiguously in the buffer `buf` of its context: rows of row_bytes
+ * bytes of a whole-tile host buffer <-> every device's own, one strided copy per device. A null host buffer is left out. */
+template <typename T>
+static int group_move_rows(drt_group *g, void *host, size_t row_bytes, T *drt_context::*buf, bool to_device)
 {
     if (!host) return 0;
     const size_t n = g->ctx.size();
-    const size_t C = which == 0 ? (g->xyz_mode ? (size_t)XYZ_FILM_WORDS : (size_t)g->S + 1) : (size_t)g->S;
-    if (g->xyz_mode && which != 0) return fail(-4, "the XYZ film has no mean / variance buffers");
-    const size_t row_bytes = (size_t)g->tile_w * C * 8;
     for (size_t k = 0; k < n; k += 1)
     {
         drt_context *c = g->ctx[k];
         if (!c) continue;
         HIP_TRY(hipSetDevice(c->device));
-        void *dev = which == 0 ? (void *)c->d_pixels : which == 1 ? (void *)c->d_avgs : (void *)c->d_vars;
         char *h = (char *)host + k * row_bytes;
         if (to_device)
-            HIP_TRY(hipMemcpy2D(dev, row_bytes, h, n * row_bytes, row_bytes, g->rows[k], hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy2D(c->*buf, row_bytes, h, n * row_bytes, row_bytes, g->rows[k], hipMemcpyHostToDevice));
         else
-            HIP_TRY(hipMemcpy2D(h, n * row_bytes, dev, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy2D(h, n * row_bytes, c->*buf, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
     }
     return 0;
+}
+template <typename T>
+static int group_gather_rows(drt_group *g, void *host, size_t row_bytes, T *drt_context::*buf) { return group_move_rows(g, host, row_bytes, buf, false); }
+template <typename T>
+static int group_scatter_rows(drt_group *g, const void *host, size_t row_bytes, T *drt_context::*buf)
+{
+    return group_move_rows(g, const_cast<void *>(host), row_bytes, buf, true);
+}
+
+/* which: 0 the film's sums, 1 the running means, 2 the variances */
+static int group_copy(drt_group *g, double *host, int which, bool to_device)
+{
+    if (!host) return 0;
+    const size_t C = which == 0 ? (g->xyz_mode ? (size_t)XYZ_FILM_WORDS : (size_t)g->S + 1) : (size_t)g->S;
+    if (g->xyz_mode && which != 0) return fail(-4, "the XYZ film has no mean / variance buffers");
+    double *drt_context::*buf = which == 0 ? &drt_context::d_pixels : which == 1 ? &drt_context::d_avgs : &drt_context::d_vars;
+    const size_t row_bytes = (size_t)g->tile_w * C * 8;
+    return to_device ? group_scatter_rows(g, host, row_bytes, buf) : group_gather_rows(g, host, row_bytes, buf);
 }
 
 extern "C" int drt_group_read_film(drt_group *g, double *pixels, double *avgs, double *vars)
@@ -2521,17 +2537,10 @@ extern "C" int drt_group_write_film(drt_group *g, const double *pixels, const do
 extern "C" int drt_group_read_bgra(drt_group *g, int which, uint8_t *bgra)
 {
     if (!g || !bgra) return fail(-1, "null argument");
-    const size_t n = g->ctx.size();
-    const size_t row_bytes = (size_t)g->tile_w * 4;
-    for (size_t k = 0; k < n; k += 1)
-    {
-        drt_context *c = g->ctx[k];
-        if (!c) continue;
-        int rc = film_to_bgra(c, which);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpy2D(bgra + k * row_bytes, n * row_bytes, c->d_bgra, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
-    }
-    return 0;
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = film_to_bgra(c, which))) return rc;
+    return group_gather_rows(g, bgra, (size_t)g->tile_w * 4, &drt_context::d_bgra);
 }
 
 extern "C" int drt_group_get_stats(drt_group *g, drt_stats *out)
@@ -2669,18 +2678,14 @@ extern "C" int drt_group_render_adaptive_continue(drt_group *g, drt_adaptive *a,
 extern "C" int drt_group_read_sample_counts(drt_group *g, uint32_t *counts)
 {
     if (!g || !counts) return fail(-1, "null argument");
-    const size_t n = g->ctx.size();
-    const size_t row_bytes = (size_t)g->tile_w * sizeof(uint32_t);
-    for (size_t k = 0; k < n; k += 1)
+    for (drt_context *c : g->ctx)
     {
-        drt_context *c = g->ctx[k];
         if (!c) continue;
         if (!c->adaptive_done || !c->d_counts) return fail(-4, "no adaptive render: the counts come from drt_group_render_adaptive");
         int rc = drt_synchronize(c);
         if (rc) return rc;
-        HIP_TRY(hipMemcpy2D((char *)counts + k * row_bytes, n * row_bytes, c->d_counts, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
     }
-    return 0;
+    return group_gather_rows(g, counts, (size_t)g->tile_w * sizeof(uint32_t), &drt_context::d_counts);
 }
 
 /* ---------------------------------------------------------------------------------------------- */
@@ -2933,10 +2938,14 @@ extern "C" int drt_group_denoise(drt_group *g, drt_denoise *d, double *mean, dou
 /* ---------------------------------------------------------------------------------------------- */
 /* First-hit feature buffers (kernels in drt_feature_kernels.h)              */
 
+/* the size rule of stage_surfaces' carve-up (drt_first_hit.h): the scans' rows, the SoA table, the type and material words */
 static size_t feature_lds_bytes(uint32_t n_surf)
 {
     return (size_t)(SR_STRIDE + SF_COUNT) * n_surf * 8 + (((size_t)2 * n_surf * 4 + 7) & ~(size_t)7);
 }
+
+/* one lane per tile pixel, FEATURE_BLOCK to a workgroup */
+static dim3 pixel_grid(const drt_context *ctx) { return dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)); }
 
 /* [num_materials][3], the rule's "material colour": sums sequential over ascending wavelength, no contraction (the host is built
  * with -ffp-contract=off, like the kernels) */
@@ -2975,11 +2984,12 @@ static int feature_colour_table(const drt_context *ctx, std::vector<double> *tab
     return 0;
 }
 
-static int features_check(const drt_features *f)
+/* The pixel passes (features, mattes) share what follows; `who` is the pass's name in its messages, "features" or "mattes". */
+static int first_hit_check(const char *who, uint32_t flags, uint32_t first_sample, uint32_t n_samples)
 {
-    if (f->flags != 0) return fail(-1, "features: flags = %u: 0 (reserved)", f->flags);
-    if (f->n_samples && (uint64_t)f->first_sample + f->n_samples > 0xFFFFFFFFull)
-        return fail(-1, "features: first_sample %u + %u samples: sample numbers are 32 bits", f->first_sample, f->n_samples);
+    if (flags != 0) return fail(-1, "%s: flags = %u: 0 (reserved)", who, flags);
+    if (n_samples && (uint64_t)first_sample + n_samples > 0xFFFFFFFFull)
+        return fail(-1, "%s: first_sample %u + %u samples: sample numbers are 32 bits", who, first_sample, n_samples);
     return 0;
 }
 
@@ -2992,7 +3002,7 @@ static int film_counts(drt_context *ctx, const char *who, uint32_t first_sample)
     if (!ctx->d_ft_report) HIP_TRY(hipMalloc((void **)&ctx->d_ft_report, 2 * sizeof(uint32_t)));
     uint32_t report[2] = {0xFFFFFFFFu, 0u};
     HIP_TRY(hipMemcpyAsync(ctx->d_ft_report, report, sizeof(report), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(drt_feature_counts_kernel, dim3((uint32_t)((n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+    hipLaunchKernelGGL(drt_feature_counts_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        ctx->d_pixels, ctx->dsc.S, (uint32_t)n_pix, ctx->d_ft_counts, ctx->d_ft_report);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(report, ctx->d_ft_report, sizeof(report), hipMemcpyDeviceToHost, ctx->stream));
@@ -3009,18 +3019,51 @@ static int film_counts(drt_context *ctx, const char *who, uint32_t first_sample)
     return 0;
 }
 
-/* The film complete, the buffers there, and with n_samples = 0 every pixel's count from its filter sum. Refuses before anything is
- * rendered; the film, the adaptive counts and the render state stay as they are. */
-static int features_prepare(drt_context *ctx, const drt_features *f)
+/* The film complete and the pass's earlier results (*valid) given up. Refuses before anything is rendered; the film, the adaptive
+ * counts, the render state and the other pass's buffers stay as they are. The caller allocates its buffers next and then, with
+ * n_samples = 0, takes every pixel's count from its filter sum (film_counts). */
+static int first_hit_prepare(drt_context *ctx, const char *who, uint32_t n_samples, bool *valid)
 {
-    if (ctx->rays_bound) return fail(-7, "features: they are made from the camera's rays, and a ray table is bound (drt_bind_rays with NULL unbinds it)");
-    if (f->n_samples == 0 && ctx->xyz_mode)
-        return fail(-4, "features: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)");
-    if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "features: a tile of %llu pixels", (unsigned long long)ctx->n_pix);
+    if (ctx->rays_bound) return fail(-7, "%s: they are made from the camera's rays, and a ray table is bound (drt_bind_rays with NULL unbinds it)", who);
+    if (n_samples == 0 && ctx->xyz_mode)
+        return fail(-4, "%s: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)", who);
+    if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "%s: a tile of %llu pixels", who, (unsigned long long)ctx->n_pix);
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = drt_synchronize(ctx);
     if (rc) return rc;
-    ctx->ft_valid = false;
+    *valid = false;
+    return 0;
+}
+
+/* what the pixel passes' kernels read of a pass: the tile, the samples, the counts */
+static FeatureParams first_hit_params(const drt_context *ctx, uint32_t n_samples, uint32_t first_sample)
+{
+    const drt_params &p = ctx->params;
+    FeatureParams fp{};
+    fp.width = p.width; fp.height = p.height; fp.x0 = p.x0; fp.y0 = p.y0;
+    fp.tile_w = p.tile_w; fp.tile_h = p.tile_h; fp.row_stride = p.row_stride;
+    fp.n_samples = n_samples;
+    fp.first_sample = first_sample;
+    fp.pixel_scheme = p.pixel_scheme;
+    fp.seed = p.seed;
+    fp.n_pix = ctx->n_pix;
+    fp.counts = n_samples ? nullptr : ctx->d_ft_counts;
+    return fp;
+}
+
+/* results of a pass (`what`: "feature", "matte") that took its counts from the film are refused once the film has changed */
+static int first_hit_current(bool valid, bool from_film, uint64_t gen, uint64_t film_gen, const char *what)
+{
+    if (!valid) return fail(-4, "no %s buffers: drt_render_%ss first", what, what);
+    if (from_film && gen != film_gen)
+        return fail(-4, "the film has changed since drt_render_%ss took its counts from it (n_samples = 0): render the %ss again", what, what);
+    return 0;
+}
+
+static int features_prepare(drt_context *ctx, const drt_features *f)
+{
+    int rc = first_hit_prepare(ctx, "features", f->n_samples, &ctx->ft_valid);
+    if (rc) return rc;
     const size_t n_pix = (size_t)ctx->n_pix;
     if (!ctx->d_ft_mean) HIP_TRY(hipMalloc((void **)&ctx->d_ft_mean, n_pix * DRT_FEATURE_CHANNELS * 8));
     if (!ctx->d_ft_m2) HIP_TRY(hipMalloc((void **)&ctx->d_ft_m2, n_pix * DRT_FEATURE_CHANNELS * 8));
@@ -3029,8 +3072,7 @@ static int features_prepare(drt_context *ctx, const drt_features *f)
     if (!ctx->d_ft_colour) HIP_TRY(hipMalloc((void **)&ctx->d_ft_colour, std::max<size_t>(ctx->ft_mats.size(), 1) * 3 * 8));
     for (hipEvent_t &e : ctx->ft_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    if (f->n_samples == 0 && (rc = film_counts(ctx, "features", f->first_sample))) return rc;
-    return 0;
+    return f->n_samples == 0 ? film_counts(ctx, "features", f->first_sample) : 0;
 }
 
 static int features_enqueue(drt_context *ctx, const drt_features *f)
@@ -3042,27 +3084,17 @@ static int features_enqueue(drt_context *ctx, const drt_features *f)
     if ((rc = feature_colour_table(ctx, &table))) return rc;
     if (!table.empty()) HIP_TRY(hipMemcpy(ctx->d_ft_colour, table.data(), table.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(ctx->d_ft_info, 0, FEATURE_INFO_WORDS * sizeof(unsigned long long), ctx->stream));
-    const drt_params &p = ctx->params;
-    FeatureParams fp{};
-    fp.width = p.width; fp.height = p.height; fp.x0 = p.x0; fp.y0 = p.y0;
-    fp.tile_w = p.tile_w; fp.tile_h = p.tile_h; fp.row_stride = p.row_stride;
-    fp.n_samples = f->n_samples;
-    fp.first_sample = f->first_sample;
-    fp.pixel_scheme = p.pixel_scheme;
-    fp.seed = p.seed;
-    fp.n_pix = ctx->n_pix;
-    fp.counts = f->n_samples ? nullptr : ctx->d_ft_counts;
+    FeatureParams fp = first_hit_params(ctx, f->n_samples, f->first_sample);
     fp.colour = ctx->d_ft_colour;
     fp.mean = ctx->d_ft_mean;
     fp.m2 = ctx->d_ft_m2;
     fp.ids = ctx->d_ft_ids;
     fp.info = ctx->d_ft_info;
-    const uint32_t grid = (uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK);
     HIP_TRY(hipEventRecord(ctx->ft_ev[0], ctx->stream));
     if (ctx->scene_in_lds)
-        hipLaunchKernelGGL(drt_feature_kernel, dim3(grid), dim3(FEATURE_BLOCK), feature_lds_bytes(ctx->dsc.n_surf), ctx->stream, ctx->dsc, ctx->dcam, fp);
+        hipLaunchKernelGGL(drt_feature_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), feature_lds_bytes(ctx->dsc.n_surf), ctx->stream, ctx->dsc, ctx->dcam, fp);
     else
-        hipLaunchKernelGGL(drt_feature_bvh_kernel, dim3(grid), dim3(FEATURE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, fp);
+        hipLaunchKernelGGL(drt_feature_bvh_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, fp);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->ft_ev[1], ctx->stream));
     return 0;
@@ -3090,7 +3122,7 @@ static int features_finish(drt_context *ctx, drt_features *f)
 extern "C" int drt_render_features(drt_context *ctx, drt_features *f)
 {
     if (!ctx || !f) return fail(-1, "null argument");
-    int rc = features_check(f);
+    int rc = first_hit_check("features", f->flags, f->first_sample, f->n_samples);
     if (rc) return rc;
     if ((rc = features_prepare(ctx, f))) return rc;
     if ((rc = features_enqueue(ctx, f))) return rc;
@@ -3100,13 +3132,7 @@ extern "C" int drt_render_features(drt_context *ctx, drt_features *f)
     return features_finish(ctx, f);
 }
 
-static int features_current(drt_context *ctx)
-{
-    if (!ctx->ft_valid) return fail(-4, "no feature buffers: drt_render_features first");
-    if (ctx->ft_from_film && ctx->ft_gen != ctx->film_gen)
-        return fail(-4, "the film has changed since drt_render_features took its counts from it (n_samples = 0): render the features again");
-    return 0;
-}
+static int features_current(drt_context *ctx) { return first_hit_current(ctx->ft_valid, ctx->ft_from_film, ctx->ft_gen, ctx->film_gen, "feature"); }
 
 extern "C" int drt_read_features(drt_context *ctx, double *mean, double *m2, int32_t *ids)
 {
@@ -3130,7 +3156,7 @@ extern "C" int drt_read_feature_bgra(drt_context *ctx, int which, double lo, dou
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
-    hipLaunchKernelGGL(drt_feature_bgra_kernel, dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+    hipLaunchKernelGGL(drt_feature_bgra_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        (const double *)ctx->d_ft_mean, ctx->n_pix, which, lo, hi, ctx->d_bgra);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -3143,7 +3169,7 @@ extern "C" int drt_group_render_features(drt_group *g, drt_features *f, double *
 {
     g_last_error.clear();
     if (!g || !f) return fail(-1, "null argument");
-    int rc = features_check(f);
+    int rc = first_hit_check("features", f->flags, f->first_sample, f->n_samples);
     if (rc) return rc;
     for (drt_context *c : g->ctx)
         if (c && (rc = features_prepare(c, f))) return rc;
@@ -3154,18 +3180,10 @@ extern "C" int drt_group_render_features(drt_group *g, drt_features *f, double *
     f->kernel_ms = 0.0;
     for (drt_context *c : g->ctx)
         if (c && (rc = features_finish(c, f))) return rc;
-    const size_t n = g->ctx.size();
-    for (size_t k = 0; k < n; k += 1)
-    {
-        drt_context *c = g->ctx[k];
-        if (!c) continue;
-        HIP_TRY(hipSetDevice(c->device));
-        const size_t row8 = (size_t)g->tile_w * DRT_FEATURE_CHANNELS * 8, row4 = (size_t)g->tile_w * sizeof(int32_t);
-        if (mean) HIP_TRY(hipMemcpy2D((char *)mean + k * row8, n * row8, c->d_ft_mean, row8, row8, g->rows[k], hipMemcpyDeviceToHost));
-        if (m2) HIP_TRY(hipMemcpy2D((char *)m2 + k * row8, n * row8, c->d_ft_m2, row8, row8, g->rows[k], hipMemcpyDeviceToHost));
-        if (ids) HIP_TRY(hipMemcpy2D((char *)ids + k * row4, n * row4, c->d_ft_ids, row4, row4, g->rows[k], hipMemcpyDeviceToHost));
-    }
-    return 0;
+    const size_t row8 = (size_t)g->tile_w * DRT_FEATURE_CHANNELS * 8;
+    if ((rc = group_gather_rows(g, mean, row8, &drt_context::d_ft_mean))) return rc;
+    if ((rc = group_gather_rows(g, m2, row8, &drt_context::d_ft_m2))) return rc;
+    return group_gather_rows(g, ids, (size_t)g->tile_w * sizeof(int32_t), &drt_context::d_ft_ids);
 }
 
 /* ---------------------------------------------------------------------------------------------- */
@@ -3174,26 +3192,10 @@ extern "C" int drt_group_render_features(drt_group *g, drt_features *f, double *
 #define MATTE_MAX_IDS 4096u
 #define MATTE_WORDS (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS) /* ids and counts per pixel */
 
-static int mattes_check(const drt_mattes *m)
-{
-    if (m->flags != 0) return fail(-1, "mattes: flags = %u: 0 (reserved)", m->flags);
-    if (m->n_samples && (uint64_t)m->first_sample + m->n_samples > 0xFFFFFFFFull)
-        return fail(-1, "mattes: first_sample %u + %u samples: sample numbers are 32 bits", m->first_sample, m->n_samples);
-    return 0;
-}
-
-/* As features_prepare: refuses before anything is rendered; the film, the adaptive counts, the render state and the feature buffers
- * stay as they are. */
 static int mattes_prepare(drt_context *ctx, const drt_mattes *m)
 {
-    if (ctx->rays_bound) return fail(-7, "mattes: they are made from the camera's rays, and a ray table is bound (drt_bind_rays with NULL unbinds it)");
-    if (m->n_samples == 0 && ctx->xyz_mode)
-        return fail(-4, "mattes: n_samples = 0 takes every pixel's count from the spectral film's filter column: DRT_MODE_XYZ keeps none (give n_samples)");
-    if (ctx->n_pix >= 0xFFFFFFFFull) return fail(-1, "mattes: a tile of %llu pixels", (unsigned long long)ctx->n_pix);
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = drt_synchronize(ctx);
+    int rc = first_hit_prepare(ctx, "mattes", m->n_samples, &ctx->mt_valid);
     if (rc) return rc;
-    ctx->mt_valid = false;
     const size_t n_pix = (size_t)ctx->n_pix;
     if (!ctx->d_mt_ids) HIP_TRY(hipMalloc((void **)&ctx->d_mt_ids, n_pix * MATTE_WORDS * sizeof(int32_t)));
     if (!ctx->d_mt_counts) HIP_TRY(hipMalloc((void **)&ctx->d_mt_counts, n_pix * MATTE_WORDS * sizeof(uint32_t)));
@@ -3201,35 +3203,24 @@ static int mattes_prepare(drt_context *ctx, const drt_mattes *m)
     if (!ctx->d_mt_info) HIP_TRY(hipMalloc((void **)&ctx->d_mt_info, MATTE_INFO_WORDS * sizeof(unsigned long long)));
     for (hipEvent_t &e : ctx->mt_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    if (m->n_samples == 0 && (rc = film_counts(ctx, "mattes", m->first_sample))) return rc;
-    return 0;
+    return m->n_samples == 0 ? film_counts(ctx, "mattes", m->first_sample) : 0;
 }
 
 static int mattes_enqueue(drt_context *ctx, const drt_mattes *m)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemsetAsync(ctx->d_mt_info, 0, MATTE_INFO_WORDS * sizeof(unsigned long long), ctx->stream));
-    const drt_params &p = ctx->params;
     MatteParams mp{};
-    FeatureParams &fp = mp.fp;
-    fp.width = p.width; fp.height = p.height; fp.x0 = p.x0; fp.y0 = p.y0;
-    fp.tile_w = p.tile_w; fp.tile_h = p.tile_h; fp.row_stride = p.row_stride;
-    fp.n_samples = m->n_samples;
-    fp.first_sample = m->first_sample;
-    fp.pixel_scheme = p.pixel_scheme;
-    fp.seed = p.seed;
-    fp.n_pix = ctx->n_pix;
-    fp.counts = m->n_samples ? nullptr : ctx->d_ft_counts;
+    mp.fp = first_hit_params(ctx, m->n_samples, m->first_sample);
     mp.ids = ctx->d_mt_ids;
     mp.counts = ctx->d_mt_counts;
     mp.tail = ctx->d_mt_tail;
     mp.info = ctx->d_mt_info;
-    const uint32_t grid = (uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK);
     HIP_TRY(hipEventRecord(ctx->mt_ev[0], ctx->stream));
     if (ctx->scene_in_lds)
-        hipLaunchKernelGGL(drt_matte_kernel, dim3(grid), dim3(FEATURE_BLOCK), feature_lds_bytes(ctx->dsc.n_surf), ctx->stream, ctx->dsc, ctx->dcam, mp);
+        hipLaunchKernelGGL(drt_matte_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), feature_lds_bytes(ctx->dsc.n_surf), ctx->stream, ctx->dsc, ctx->dcam, mp);
     else
-        hipLaunchKernelGGL(drt_matte_bvh_kernel, dim3(grid), dim3(FEATURE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, mp);
+        hipLaunchKernelGGL(drt_matte_bvh_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream, ctx->dsc, ctx->dcam, mp);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ctx->mt_ev[1], ctx->stream));
     return 0;
@@ -3267,7 +3258,7 @@ static void mattes_clear_out(drt_mattes *m)
 extern "C" int drt_render_mattes(drt_context *ctx, drt_mattes *m)
 {
     if (!ctx || !m) return fail(-1, "null argument");
-    int rc = mattes_check(m);
+    int rc = first_hit_check("mattes", m->flags, m->first_sample, m->n_samples);
     if (rc) return rc;
     if ((rc = mattes_prepare(ctx, m))) return rc;
     if ((rc = mattes_enqueue(ctx, m))) return rc;
@@ -3275,13 +3266,7 @@ extern "C" int drt_render_mattes(drt_context *ctx, drt_mattes *m)
     return mattes_finish(ctx, m);
 }
 
-static int mattes_current(drt_context *ctx)
-{
-    if (!ctx->mt_valid) return fail(-4, "no matte buffers: drt_render_mattes first");
-    if (ctx->mt_from_film && ctx->mt_gen != ctx->film_gen)
-        return fail(-4, "the film has changed since drt_render_mattes took its counts from it (n_samples = 0): render the mattes again");
-    return 0;
-}
+static int mattes_current(drt_context *ctx) { return first_hit_current(ctx->mt_valid, ctx->mt_from_film, ctx->mt_gen, ctx->film_gen, "matte"); }
 
 extern "C" int drt_read_mattes(drt_context *ctx, int32_t *ids, uint32_t *counts, uint32_t *tail)
 {
@@ -3321,7 +3306,7 @@ extern "C" int drt_read_matte(drt_context *ctx, int layer, const int32_t *id_lis
     if (!ctx->d_mt_list) HIP_TRY(hipMalloc((void **)&ctx->d_mt_list, MATTE_MAX_IDS * sizeof(int32_t)));
     if (!ctx->d_mt_cover) HIP_TRY(hipMalloc((void **)&ctx->d_mt_cover, (size_t)ctx->n_pix * sizeof(double)));
     HIP_TRY(hipMemcpy(ctx->d_mt_list, id_list, n_ids * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(drt_matte_select_kernel, dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+    hipLaunchKernelGGL(drt_matte_select_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        (const int32_t *)ctx->d_mt_ids, (const uint32_t *)ctx->d_mt_counts, (const uint32_t *)ctx->d_mt_tail, ctx->n_pix, layer,
                        (const int32_t *)ctx->d_mt_list, n_ids, ctx->d_mt_cover);
     HIP_TRY(hipGetLastError());
@@ -3338,7 +3323,7 @@ extern "C" int drt_read_matte_bgra(drt_context *ctx, int layer, uint8_t *bgra)
     if ((rc = mattes_current(ctx))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
-    hipLaunchKernelGGL(drt_matte_bgra_kernel, dim3((uint32_t)((ctx->n_pix + FEATURE_BLOCK - 1) / FEATURE_BLOCK)), dim3(FEATURE_BLOCK), 0, ctx->stream,
+    hipLaunchKernelGGL(drt_matte_bgra_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        (const int32_t *)ctx->d_mt_ids, (const uint32_t *)ctx->d_mt_counts, (const uint32_t *)ctx->d_mt_tail, ctx->n_pix, layer, ctx->d_bgra);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -3351,7 +3336,7 @@ extern "C" int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids
 {
     g_last_error.clear();
     if (!g || !m) return fail(-1, "null argument");
-    int rc = mattes_check(m);
+    int rc = first_hit_check("mattes", m->flags, m->first_sample, m->n_samples);
     if (rc) return rc;
     for (drt_context *c : g->ctx)
         if (c && (rc = mattes_prepare(c, m))) return rc;
@@ -3360,18 +3345,10 @@ extern "C" int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids
     mattes_clear_out(m);
     for (drt_context *c : g->ctx)
         if (c && (rc = mattes_finish(c, m))) return rc;
-    const size_t n = g->ctx.size();
-    for (size_t k = 0; k < n; k += 1)
-    {
-        drt_context *c = g->ctx[k];
-        if (!c) continue;
-        HIP_TRY(hipSetDevice(c->device));
-        const size_t row = (size_t)g->tile_w * MATTE_WORDS * 4, row_tail = (size_t)g->tile_w * 4 * 4;
-        if (ids) HIP_TRY(hipMemcpy2D((char *)ids + k * row, n * row, c->d_mt_ids, row, row, g->rows[k], hipMemcpyDeviceToHost));
-        if (counts) HIP_TRY(hipMemcpy2D((char *)counts + k * row, n * row, c->d_mt_counts, row, row, g->rows[k], hipMemcpyDeviceToHost));
-        if (tail) HIP_TRY(hipMemcpy2D((char *)tail + k * row_tail, n * row_tail, c->d_mt_tail, row_tail, row_tail, g->rows[k], hipMemcpyDeviceToHost));
-    }
-    return 0;
+    const size_t row = (size_t)g->tile_w * MATTE_WORDS * 4;
+    if ((rc = group_gather_rows(g, ids, row, &drt_context::d_mt_ids))) return rc;
+    if ((rc = group_gather_rows(g, counts, row, &drt_context::d_mt_counts))) return rc;
+    return group_gather_rows(g, tail, (size_t)g->tile_w * 4 * 4, &drt_context::d_mt_tail);
 }
 
 /* ---------------------------------------------------------------------------------------------- */

@@ -4,9 +4,8 @@
  * hit nothing. DESIGN.md, section 5d, states the rule; tests/matte_rule.py restates it. Integer counting only: the kernels equal the
  * rule with ==.
  *
- * The two render kernels are drt_feature_kernel's and drt_feature_bvh_kernel's loops (drt_feature_kernels.h): one lane per tile pixel,
- * its samples in ascending order, the camera ray feature_ray's, the closest hit find_ray_intersection<true>'s over rows staged in LDS
- * or one whole-wave bvh_walk and hit_point_from_scan. What a lane carries differs: twelve (id, count) slots in registers, updated
+ * The two render kernels are the pixel passes of drt_first_hit.h, as drt_feature_kernel and drt_feature_bvh_kernel are: one lane per
+ * tile pixel, its samples in ascending order. What a lane carries differs (MatteAcc): twelve (id, count) slots in registers, updated
  * by an unrolled compare / select chain (no runtime index, so nothing goes to scratch), ranked once at the end by a fixed network.
  *
  *   drt_matte_kernel         scenes in LDS
@@ -36,27 +35,6 @@ struct MatteLayer
     uint32_t n[DRT_MATTE_SLOTS];
     uint32_t other;
 };
-struct MatteAcc
-{
-    MatteLayer l[DRT_MATTE_LAYERS];
-    uint32_t misses;
-};
-
-__device__ __forceinline__ void matte_clear(MatteAcc &a)
-{
-#pragma unroll
-    for (int y = 0; y < DRT_MATTE_LAYERS; y += 1)
-    {
-#pragma unroll
-        for (int k = 0; k < DRT_MATTE_SLOTS; k += 1)
-        {
-            a.l[y].id[k] = DRT_MATTE_ID_MISS;
-            a.l[y].n[k] = 0u;
-        }
-        a.l[y].other = 0u;
-    }
-    a.misses = 0u;
-}
 
 /* A hit's id goes to the slot that holds it, else to the lowest empty one, else to `other`. Going up the slots, the first that holds
  * the id or is empty is the one: an empty slot has only empty slots above it, so the id is in none of those. Selects only, and `hit`
@@ -74,15 +52,6 @@ __device__ __forceinline__ void matte_layer_add(MatteLayer &l, bool hit, int32_t
         placed = placed || take;
     }
     l.other += placed ? 0u : 1u;
-}
-
-/* one sample: its closest-hit index and that surface's material, or a miss */
-__device__ __forceinline__ void matte_update(MatteAcc &a, const HitPoint &ip)
-{
-    const bool hit = ip.index >= 0;
-    matte_layer_add(a.l[DRT_MATTE_SURFACE], hit, ip.index);
-    matte_layer_add(a.l[DRT_MATTE_MATERIAL], hit, (int32_t)ip.surface_mat);
-    a.misses += hit ? 0u : 1u;
 }
 
 /* slots i < j in rank order: count descending, then id ascending (an empty slot, count 0, after every used one) */
@@ -108,141 +77,96 @@ __device__ __forceinline__ void matte_rank(MatteLayer &l)
     matte_exchange(l, 1, 2); matte_exchange(l, 3, 4);
 }
 
-/* ranks the lane's slots and stores them, and the launch's four sums: one atomic per word and wave */
-__device__ __forceinline__ void matte_store(const MatteParams &mp, uint64_t p, bool valid, MatteAcc &a, uint32_t count)
+/* a lane's two layers and its misses */
+struct MatteAcc
 {
-    matte_rank(a.l[0]);
-    matte_rank(a.l[1]);
-    if (valid)
+    const MatteParams &mp;
+    MatteLayer l[DRT_MATTE_LAYERS];
+    uint32_t misses;
+
+    __device__ __forceinline__ explicit MatteAcc(const MatteParams &mp_) : mp(mp_) {}
+
+    __device__ __forceinline__ void clear()
     {
-        int32_t *ids = mp.ids + (size_t)p * (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS);
-        uint32_t *counts = mp.counts + (size_t)p * (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS);
 #pragma unroll
         for (int y = 0; y < DRT_MATTE_LAYERS; y += 1)
         {
 #pragma unroll
             for (int k = 0; k < DRT_MATTE_SLOTS; k += 1)
             {
-                ids[y * DRT_MATTE_SLOTS + k] = a.l[y].id[k];
-                counts[y * DRT_MATTE_SLOTS + k] = a.l[y].n[k];
+                l[y].id[k] = DRT_MATTE_ID_MISS;
+                l[y].n[k] = 0u;
             }
+            l[y].other = 0u;
         }
-        uint32_t *tail = mp.tail + (size_t)p * 4u;
-        tail[0] = count;
-        tail[1] = a.misses;
-        tail[2] = a.l[0].other;
-        tail[3] = a.l[1].other;
+        misses = 0u;
     }
-    const unsigned long long empty = __ballot(valid && a.misses == count);
-    const unsigned long long over0 = __ballot(valid && a.l[0].other > 0u);
-    const unsigned long long over1 = __ballot(valid && a.l[1].other > 0u);
-    uint64_t rays = valid ? count : 0u;
-    for (int off = 32; off > 0; off >>= 1) rays += __shfl_down(rays, off);
-    if ((threadIdx.x & 63u) == 0)
-    {
-        if (empty) atomicAdd(mp.info, (unsigned long long)__popcll(empty));
-        if (over0) atomicAdd(mp.info + 1, (unsigned long long)__popcll(over0));
-        if (over1) atomicAdd(mp.info + 2, (unsigned long long)__popcll(over1));
-        if (rays) atomicAdd(mp.info + 3, (unsigned long long)rays);
-    }
-}
 
-/* LDS carve-up: drt_feature_kernel's (feature_lds_bytes in the launcher) */
+    /* one sample: its closest-hit index and that surface's material, or a miss */
+    __device__ __forceinline__ void add(const HitPoint &ip, uint32_t)
+    {
+        const bool hit = ip.index >= 0;
+        matte_layer_add(l[DRT_MATTE_SURFACE], hit, ip.index);
+        matte_layer_add(l[DRT_MATTE_MATERIAL], hit, (int32_t)ip.surface_mat);
+        misses += hit ? 0u : 1u;
+    }
+
+    /* ranks the lane's slots and stores them, and the launch's four sums: one atomic per word and wave */
+    __device__ __forceinline__ void store(uint64_t p, bool valid, uint32_t count)
+    {
+        matte_rank(l[0]);
+        matte_rank(l[1]);
+        if (valid)
+        {
+            int32_t *ids = mp.ids + (size_t)p * (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS);
+            uint32_t *counts = mp.counts + (size_t)p * (DRT_MATTE_LAYERS * DRT_MATTE_SLOTS);
+#pragma unroll
+            for (int y = 0; y < DRT_MATTE_LAYERS; y += 1)
+            {
+#pragma unroll
+                for (int k = 0; k < DRT_MATTE_SLOTS; k += 1)
+                {
+                    ids[y * DRT_MATTE_SLOTS + k] = l[y].id[k];
+                    counts[y * DRT_MATTE_SLOTS + k] = l[y].n[k];
+                }
+            }
+            uint32_t *tail = mp.tail + (size_t)p * 4u;
+            tail[0] = count;
+            tail[1] = misses;
+            tail[2] = l[0].other;
+            tail[3] = l[1].other;
+        }
+        const unsigned long long empty = __ballot(valid && misses == count);
+        const unsigned long long over0 = __ballot(valid && l[0].other > 0u);
+        const unsigned long long over1 = __ballot(valid && l[1].other > 0u);
+        uint64_t rays = valid ? count : 0u;
+        for (int off = 32; off > 0; off >>= 1) rays += __shfl_down(rays, off);
+        if ((threadIdx.x & 63u) == 0)
+        {
+            if (empty) atomicAdd(mp.info, (unsigned long long)__popcll(empty));
+            if (over0) atomicAdd(mp.info + 1, (unsigned long long)__popcll(over0));
+            if (over1) atomicAdd(mp.info + 2, (unsigned long long)__popcll(over1));
+            if (rays) atomicAdd(mp.info + 3, (unsigned long long)rays);
+        }
+    }
+};
+
+/* the dynamic LDS is first_hit_pixels_lds's (feature_lds_bytes in the launcher) */
 __global__ __launch_bounds__(FEATURE_BLOCK) void drt_matte_kernel(DevScene sc, DevCamera cam, MatteParams mp)
 {
     extern __shared__ double mt_lds[];
-    const FeatureParams &fp = mp.fp;
-    SceneView sv;
-    sv.n_surf = sc.n_surf;
-    sv.n_lights = sc.n_lights;
-    {
-        double *l_rows = mt_lds;
-        double *l_surf = l_rows + (size_t)SR_STRIDE * sc.n_surf;
-        uint32_t *l_u32 = (uint32_t *)(l_surf + (size_t)SF_COUNT * sc.n_surf);
-        for (uint32_t k = threadIdx.x; k < SR_STRIDE * sc.n_surf; k += FEATURE_BLOCK)
-        {
-            const uint32_t i = k / SR_STRIDE, f = k % SR_STRIDE;
-            l_rows[k] = f < SF_COUNT ? sc.surf[f * sc.n_surf + i] : f == SR_TYPE ? __longlong_as_double((long long)sc.surf_type[i]) : 0.0;
-        }
-        for (uint32_t k = threadIdx.x; k < SF_COUNT * sc.n_surf; k += FEATURE_BLOCK) l_surf[k] = sc.surf[k];
-        for (uint32_t k = threadIdx.x; k < sc.n_surf; k += FEATURE_BLOCK)
-        {
-            l_u32[k] = sc.surf_type[k];
-            l_u32[sc.n_surf + k] = sc.surf_mat[k];
-        }
-        __syncthreads();
-        sv.rows = l_rows;
-        sv.surf = l_surf;
-        sv.surf_type = l_u32;
-        sv.surf_mat = l_u32 + sc.n_surf;
-        sv.lights = sc.lights;
-        sv.light_type = sc.light_type;
-        sv.light_mat = sc.light_mat;
-        sv.mats = sc.mats;
-        sv.bvh_nodes = nullptr; /* a scene that fits LDS is scanned whole */
-        sv.bvh_leaf = nullptr;
-    }
-    const uint64_t p = (uint64_t)blockIdx.x * FEATURE_BLOCK + threadIdx.x;
-    const bool valid = p < fp.n_pix;
-    const uint32_t count = valid ? (fp.counts ? fp.counts[p] : fp.n_samples) : 0u;
-    uint32_t i, j;
-    tile_pixel_ij(valid ? p : 0, fp.tile_w, i, j);
-    const uint32_t x = fp.x0 + i, y = fp.y0 + j * fp.row_stride;
-    MatteAcc a;
-    matte_clear(a);
-    for (uint32_t k = 0; k < count; k += 1)
-    {
-        V3 ro, rd;
-        feature_ray(fp, cam, x, y, fp.first_sample + k, ro, rd);
-        HitPoint ip;
-        ip.position = ip.normal = v3(0, 0, 0);
-        find_ray_intersection<true>(sv, sc, ip, ro, rd);
-        matte_update(a, ip);
-    }
-    matte_store(mp, p, valid, a, count);
+    MatteAcc a(mp);
+    a.clear();
+    const PixelLane px = first_hit_pixels_lds<FEATURE_BLOCK>(sc, cam, mp.fp, mt_lds, [&](const HitPoint &ip, uint32_t k) { a.add(ip, k); });
+    a.store(px.p, px.valid, px.count);
 }
 
 __global__ __launch_bounds__(FEATURE_BLOCK) void drt_matte_bvh_kernel(DevScene sc, DevCamera cam, MatteParams mp)
 {
-    __shared__ int s_stack[FEATURE_BLOCK / 64][BVH_LDS_STACK * 64];
-    __shared__ int s_leaf_queue[FEATURE_BLOCK / 64][BVH_QUEUE_WORDS];
-    const FeatureParams &fp = mp.fp;
-    SceneView sv;
-    sv.n_surf = sc.n_surf; sv.n_lights = sc.n_lights;
-    sv.surf = sc.surf; sv.lights = sc.lights; sv.surf_type = sc.surf_type; sv.surf_mat = sc.surf_mat;
-    sv.light_type = sc.light_type; sv.light_mat = sc.light_mat; sv.mats = sc.mats;
-    sv.bvh_nodes = sc.bvh_nodes; sv.bvh_leaf = sc.bvh_leaf;
-    const uint32_t lane = threadIdx.x & 63u;
-    int *stack = s_stack[threadIdx.x >> 6];
-    int *leaf_queue = s_leaf_queue[threadIdx.x >> 6];
-    const uint64_t p = (uint64_t)blockIdx.x * FEATURE_BLOCK + threadIdx.x;
-    const bool valid = p < fp.n_pix;
-    const uint32_t count = valid ? (fp.counts ? fp.counts[p] : fp.n_samples) : 0u;
-    uint32_t i, j;
-    tile_pixel_ij(valid ? p : 0, fp.tile_w, i, j);
-    const uint32_t x = fp.x0 + i, y = fp.y0 + j * fp.row_stride;
-    MatteAcc a;
-    matte_clear(a);
-    /* the whole wave goes round until its last lane is done */
-    for (uint32_t k = 0; __any(k < count); k += 1)
-    {
-        const bool mine = k < count;
-        V3 ro = v3(0, 0, 0), rd = v3(0, 0, 1);
-        if (mine) feature_ray(fp, cam, x, y, fp.first_sample + k, ro, rd);
-        const V3 jo = v_sum(ro, v_mul(rd, DRT_VIS_FUDGE)); /* src/daily_ray_trace.c:339 */
-        double limit = DRT_INF;
-        int index = -1;
-        bool occluded = false;
-        bvh_walk(sv, stack, leaf_queue, lane, mine ? JOB_CLOSEST : JOB_NONE, jo, rd, limit, index, occluded);
-        if (mine)
-        {
-            HitPoint ip;
-            ip.position = ip.normal = v3(0, 0, 0);
-            hit_point_from_scan(sv, sc, ip, jo, rd, limit, index);
-            matte_update(a, ip);
-        }
-    }
-    matte_store(mp, p, valid, a, count);
+    MatteAcc a(mp);
+    a.clear();
+    FIRST_HIT_PIXELS_BVH(FEATURE_BLOCK, sc, cam, mp.fp, px, a)
+    a.store(px.p, px.valid, px.count);
 }
 
 /* coverage[p] = (the counts of the layer's slots whose id is in id_list, summed in integers, plus misses if the list holds

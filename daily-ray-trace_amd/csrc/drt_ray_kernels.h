@@ -7,17 +7,18 @@
  * One ray per lane, RAY_BLOCK lanes per workgroup, a workgroup loops over ray blocks (grid-stride): the LDS kernels pay their
  * staging once per workgroup. Both scans hold whole-wave operations (wave-uniform surface loops, __any in the shadow scan), so every
  * lane of a wave runs them: a lane past n takes the last ray of the list -- a ray of its own block, since a block that starts past
- * n is not entered -- and stores nothing. In the hierarchy kernels such a lane walks with JOB_NONE.
+ * n is not entered -- and stores nothing. In the hierarchy kernels such a lane walks with JOB_NONE. The scene views, the wave's
+ * traversal storage and the first-hit step are drt_first_hit.h's, which states the whole-wave contract.
  *
- *   drt_ray_closest_kernel<PIXELS>      scenes in LDS: find_ray_intersection<true>
+ *   drt_ray_closest_kernel<PIXELS>      scenes in LDS: first_hit_lds
  *   drt_ray_visible_kernel              scenes in LDS: points_mutually_visible<true>
- *   drt_ray_closest_bvh_kernel<PIXELS>  scenes behind the hierarchy: bvh_walk JOB_CLOSEST, hit_point_from_scan
+ *   drt_ray_closest_bvh_kernel<PIXELS>  scenes behind the hierarchy: first_hit_bvh
  *   drt_ray_visible_bvh_kernel          scenes behind the hierarchy: bvh_walk JOB_SHADOW
  * PIXELS: the lane builds the path's own camera ray of (x, y, sample) with feature_ray in place of loading a ray (drt_cast_pixels).
  */
 #pragma once
 
-#include "drt_feature_kernels.h"
+#include "drt_first_hit.h"
 
 #define RAY_BLOCK 256
 
@@ -117,53 +118,12 @@ __device__ __forceinline__ void ray_store_visible(uint8_t *visible, uint64_t i, 
     else if (valid) visible[i] = vis ? 1 : 0;
 }
 
-/* drt_feature_kernel's staging: the scans' surface rows, the SoA surface table, then the types and materials (feature_lds_bytes in the
- * launcher). Lights and materials are not read. Ends with the workgroup's barrier. */
-__device__ __forceinline__ void ray_stage_scene(const DevScene &sc, double *lds, SceneView &sv)
-{
-    double *l_rows = lds;
-    double *l_surf = l_rows + (size_t)SR_STRIDE * sc.n_surf;
-    uint32_t *l_u32 = (uint32_t *)(l_surf + (size_t)SF_COUNT * sc.n_surf);
-    for (uint32_t k = threadIdx.x; k < SR_STRIDE * sc.n_surf; k += RAY_BLOCK)
-    {
-        const uint32_t i = k / SR_STRIDE, f = k % SR_STRIDE;
-        l_rows[k] = f < SF_COUNT ? sc.surf[f * sc.n_surf + i] : f == SR_TYPE ? __longlong_as_double((long long)sc.surf_type[i]) : 0.0;
-    }
-    for (uint32_t k = threadIdx.x; k < SF_COUNT * sc.n_surf; k += RAY_BLOCK) l_surf[k] = sc.surf[k];
-    for (uint32_t k = threadIdx.x; k < sc.n_surf; k += RAY_BLOCK)
-    {
-        l_u32[k] = sc.surf_type[k];
-        l_u32[sc.n_surf + k] = sc.surf_mat[k];
-    }
-    __syncthreads();
-    sv.n_surf = sc.n_surf;
-    sv.n_lights = sc.n_lights;
-    sv.rows = l_rows;
-    sv.surf = l_surf;
-    sv.surf_type = l_u32;
-    sv.surf_mat = l_u32 + sc.n_surf;
-    sv.lights = sc.lights;
-    sv.light_type = sc.light_type;
-    sv.light_mat = sc.light_mat;
-    sv.mats = sc.mats;
-    sv.bvh_nodes = nullptr; /* a scene that fits LDS is scanned whole */
-    sv.bvh_leaf = nullptr;
-}
-
-__device__ __forceinline__ void ray_global_scene(const DevScene &sc, SceneView &sv)
-{
-    sv.n_surf = sc.n_surf; sv.n_lights = sc.n_lights;
-    sv.surf = sc.surf; sv.lights = sc.lights; sv.surf_type = sc.surf_type; sv.surf_mat = sc.surf_mat;
-    sv.light_type = sc.light_type; sv.light_mat = sc.light_mat; sv.mats = sc.mats;
-    sv.bvh_nodes = sc.bvh_nodes; sv.bvh_leaf = sc.bvh_leaf;
-}
-
 template <bool PIXELS>
 __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_closest_kernel(DevScene sc, DevCamera cam, RayParams rp)
 {
     extern __shared__ double ray_lds[];
     SceneView sv;
-    ray_stage_scene(sc, ray_lds, sv);
+    stage_surfaces<RAY_BLOCK>(sc, ray_lds, sv);
     for (uint64_t base = (uint64_t)blockIdx.x * RAY_BLOCK; base < rp.n; base += (uint64_t)gridDim.x * RAY_BLOCK)
     {
         const uint64_t i = base + threadIdx.x;
@@ -171,11 +131,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_closest_kernel(DevScene sc,
         const uint64_t j = valid ? i : rp.n - 1;
         V3 ro, rd;
         ray_fetch<PIXELS>(rp, cam, j, valid, ro, rd);
-        HitPoint ip;
-        ip.position = ip.normal = ip.out = v3(0, 0, 0);
-        ip.on_dot = 0.0;
-        ip.incident_mat = ip.transmit_mat = 0u;
-        find_ray_intersection<true>(sv, sc, ip, ro, rd);
+        const HitPoint ip = first_hit_lds(sv, sc, ro, rd);
         /* min_dist: the hit surface's intersector again, on the operands the scan gave it (src/daily_ray_trace.c:339-364) */
         double distance = 0.0;
         if (ip.index >= 0) distance = surface_distance(sv, (uint32_t)ip.index, sv.surf_type[ip.index], v_sum(ro, v_mul(rd, DRT_VIS_FUDGE)), rd);
@@ -187,7 +143,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_visible_kernel(DevScene sc,
 {
     extern __shared__ double ray_lds[];
     SceneView sv;
-    ray_stage_scene(sc, ray_lds, sv);
+    stage_surfaces<RAY_BLOCK>(sc, ray_lds, sv);
     for (uint64_t base = (uint64_t)blockIdx.x * RAY_BLOCK; base < rp.n; base += (uint64_t)gridDim.x * RAY_BLOCK)
     {
         const uint64_t i = base + threadIdx.x;
@@ -201,45 +157,25 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_visible_kernel(DevScene sc,
 template <bool PIXELS>
 __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_closest_bvh_kernel(DevScene sc, DevCamera cam, RayParams rp)
 {
-    __shared__ int s_stack[RAY_BLOCK / 64][BVH_LDS_STACK * 64];
-    __shared__ int s_leaf_queue[RAY_BLOCK / 64][BVH_QUEUE_WORDS];
-    SceneView sv;
-    ray_global_scene(sc, sv);
+    const SceneView sv = scene_view_global(sc);
+    const WaveStore store = wave_store<RAY_BLOCK>();
     const uint32_t lane = threadIdx.x & 63u;
-    int *stack = s_stack[threadIdx.x >> 6];
-    int *leaf_queue = s_leaf_queue[threadIdx.x >> 6];
     for (uint64_t base = (uint64_t)blockIdx.x * RAY_BLOCK; base < rp.n; base += (uint64_t)gridDim.x * RAY_BLOCK)
     {
         const uint64_t i = base + threadIdx.x;
         const bool valid = i < rp.n;
         V3 ro = v3(0, 0, 0), rd = v3(0, 0, 1);
         if (valid) ray_fetch<PIXELS>(rp, cam, i, true, ro, rd);
-        const V3 jo = v_sum(ro, v_mul(rd, DRT_VIS_FUDGE)); /* src/daily_ray_trace.c:339 */
-        double limit = DRT_INF;
-        int index = -1;
-        bool occluded = false;
-        bvh_walk(sv, stack, leaf_queue, lane, valid ? JOB_CLOSEST : JOB_NONE, jo, rd, limit, index, occluded);
-        if (valid)
-        {
-            HitPoint ip;
-            ip.position = ip.normal = ip.out = v3(0, 0, 0);
-            ip.on_dot = 0.0;
-            ip.incident_mat = ip.transmit_mat = 0u;
-            hit_point_from_scan(sv, sc, ip, jo, rd, limit, index);
-            ray_store_hit(rp.hits, i, ip, limit);
-        }
+        first_hit_bvh(sv, sc, store, lane, valid, ro, rd, [&](const HitPoint &ip, double min_dist) { ray_store_hit(rp.hits, i, ip, min_dist); });
     }
 }
 
+/* the shadow job: the one walk outside first_hit_bvh, under the same contract (drt_first_hit.h) */
 __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_visible_bvh_kernel(DevScene sc, RayParams rp)
 {
-    __shared__ int s_stack[RAY_BLOCK / 64][BVH_LDS_STACK * 64];
-    __shared__ int s_leaf_queue[RAY_BLOCK / 64][BVH_QUEUE_WORDS];
-    SceneView sv;
-    ray_global_scene(sc, sv);
+    const SceneView sv = scene_view_global(sc);
+    const WaveStore store = wave_store<RAY_BLOCK>();
     const uint32_t lane = threadIdx.x & 63u;
-    int *stack = s_stack[threadIdx.x >> 6];
-    int *leaf_queue = s_leaf_queue[threadIdx.x >> 6];
     for (uint64_t base = (uint64_t)blockIdx.x * RAY_BLOCK; base < rp.n; base += (uint64_t)gridDim.x * RAY_BLOCK)
     {
         const uint64_t i = base + threadIdx.x;
@@ -256,7 +192,7 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_visible_bvh_kernel(DevScene
         }
         int index = -1;
         bool occluded = false;
-        bvh_walk(sv, stack, leaf_queue, lane, valid ? JOB_SHADOW : JOB_NONE, jo, jd, limit, index, occluded);
+        bvh_walk(sv, store.stack, store.leaf_queue, lane, valid ? JOB_SHADOW : JOB_NONE, jo, jd, limit, index, occluded);
         ray_store_visible(rp.visible, i, valid, !occluded);
     }
 }

@@ -139,6 +139,53 @@ def test_an_adaptive_film_gives_every_pixel_its_own_count():
         r.close()
 
 
+def hierarchy_renderer(bundle, params):
+    """a context behind the hierarchy whatever the scene's size (DRT_FORCE_BVH is read when the context is created)"""
+    saved = os.environ.get("DRT_FORCE_BVH")
+    os.environ["DRT_FORCE_BVH"] = "1"
+    try:
+        r = pydrt.Renderer(bundle, params)
+    finally:
+        os.environ.pop("DRT_FORCE_BVH", None)
+        if saved is not None:
+            os.environ["DRT_FORCE_BVH"] = saved
+    assert r.stats().path_flags & pydrt.PATH_BVH
+    return r
+
+
+def test_behind_the_hierarchy_lanes_of_one_wave_hold_different_counts():
+    """drt_matte_bvh_kernel's whole-wave loop with lanes that are done while others go on: an adaptive film's counts. Forcing the
+    hierarchy changes no hit, so the rule is the LDS form's."""
+    bundle, p = cases.load_case("plane_light_48")
+    params = pydrt.make_params(int(p.width), int(p.height), spp=32, max_depth=int(p.max_depth), seed=int(p.seed))
+    r = hierarchy_renderer(bundle, params)
+    try:
+        r.render_adaptive(4, 24, 4, 0.08)
+        counts = r.read_sample_counts().reshape(-1)
+        assert any(len(np.unique(counts[k:k + 64])) >= 2 for k in range(0, counts.size, 64))  # mixed counts in one wave
+        rep = r.render_mattes(0)
+        got = r.read_mattes()
+    finally:
+        r.close()
+    assert np.array_equal(got[2][:, 0], counts)
+    assert_mattes(got, rep, rule(bundle, params, counts=counts), "adaptive, behind the hierarchy")
+
+
+def test_behind_the_hierarchy_a_tile_that_leaves_lanes_without_a_pixel():
+    """35 pixels: one wave with 29 lanes that never have a ray, and three waves with none at all"""
+    bundle, _ = cases.load_case("plane_light_48")
+    params = pydrt.make_params(48, 48, spp=4, max_depth=8, seed=1, x0=20, y0=9, tile_w=7, tile_h=5)
+    want = rule(bundle, params, n_samples=4)
+    r = hierarchy_renderer(bundle, params)
+    try:
+        rep = r.render_mattes(4)
+        got = r.read_mattes()
+    finally:
+        r.close()
+    assert_mattes(got, rep, want, "7 x 5 tile behind the hierarchy")
+    assert (want[0] >= 0).any()
+
+
 def test_a_render_goes_on_as_if_the_mattes_had_not_run():
     bundle, p = cases.load_case("lens")
     params = pydrt.make_params(int(p.width), int(p.height), spp=6, max_depth=int(p.max_depth), seed=int(p.seed))
