@@ -24,6 +24,24 @@
 /* a box value the builder takes for bounded (BvhBuilder::build, drt_launcher.hip); false for a NaN */
 DRT_RULE_FN bool build_bounded(double x) { return (x < 0.0 ? -x : x) < 1e299; }
 
+/* A leaf sphere's reach for the f32 filter (drt_kernels.h, sphere_certainly_missed): |radius| + 64 u E = 2^-18 E, E the extent the
+ * hierarchy holds for, to f32 and then up by two f32 steps. The one statement of the pad: build_device_scene, drt_bvh_leaf_kernel and
+ * drt_selftest_unit's function 14 call it. */
+DRT_RULE_FN float build_f32_up(float x) /* nextafterf(x, +inf), without an include: +inf and NaN stay, +-0 give the least subnormal */
+{
+    if (!(x <= 3.402823466e+38f)) return x;
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    u = x == 0.0f ? 1u : x > 0.0f ? u + 1u : u - 1u;
+    __builtin_memcpy(&x, &u, 4);
+    return x;
+}
+DRT_RULE_FN float bvh_sphere_reach32(double radius, double extent)
+{
+    const float reach = (float)((radius < 0.0 ? -radius : radius) + extent * 3.814697265625e-06 /* 2^-18 */);
+    return build_f32_up(build_f32_up(reach));
+}
+
 /* the centre of a bounded surface's box along one axis, on the 2^21 grid between the smallest and the largest centre: - / * only */
 DRT_RULE_FN uint32_t build_quantise(double c, double clo, double chi)
 {

@@ -19,6 +19,7 @@
 #pragma once
 
 #include "drt_device.h"
+#include "drt_build_rule.h"
 #include <type_traits>
 #include "../../include/drt_hip.h"
 
@@ -442,9 +443,17 @@ __device__ __forceinline__ Ray32 bvh_ray32(V3 o, V3 d)
 /* A sphere the ray certainly does not hit within `lim`: its centre is farther from the ray's line than radius + bound, or it
  * lies wholly behind the origin, or wholly beyond the limit. All in f32; with u = 2^-24 and E the largest coordinate, the
  * rounding of centre, origin, direction and the three fused dot products moves the foot point by < 40 u E and the distance
- * along the ray by < 17 u E; reach32 = radius + 64 u E (rounded up) pays for both, so whenever this says "missed" the f64
- * intersector (line_sphere) would have returned no hit, or one beyond `lim`, and skipping it changes no result. Anything
- * not finite compares false: not skipped. */
+ * along the ray by < 17 u E; reach32 = radius + 64 u E (rounded up; bvh_sphere_reach32, drt_build_rule.h) pays for both, so whenever
+ * this says "missed" the f64 intersector (line_sphere) would have returned no hit, or one beyond `lim`, and skipping it changes no
+ * result. A NaN compares false by itself; an infinity does not (an infinite direction component makes t = -inf and the sphere
+ * "behind the origin", where line_sphere returns -inf, a hit under the rule), but whatever is not finite in centre, origin or
+ * direction leaves p2 infinite or NaN, and the last comparison keeps such a ray from being skipped.
+ * Held to the rule on its own by drt_selftest_unit's function 14 (tests/test_gpu_sphere_filter.py, against the oracle's line_sphere;
+ * DESIGN.md 5e). Measured there on an MI355X: no hit below the limit is rejected; every unit-direction ray that clears the sphere by
+ * m = 2 pads is rejected (m = 1 is not met: the error bound is just below one pad); and |d| = 1 is assumed -- with d times
+ * 1 + k 2^-53 no hit is rejected up to k_ok = 16384 (| d.d - 1 | <= 2^-38) and some are from k = 65536, while the path's own
+ * directions stay within 280.5 x 2^-52 of unit length (524 reflections; v_normalise 2.5, 524 refractions 1). Callers' directions
+ * farther than 2^-42 from unit length never get here from a ray query (drt_ray_kernels.h, RAY_UNIT_TOLERANCE). */
 __device__ __forceinline__ bool sphere_certainly_missed(const BvhLeafPrim &lp, const Ray32 &r, float lim)
 {
     const float cx = lp.c32[0] - r.ox, cy = lp.c32[1] - r.oy, cz = lp.c32[2] - r.oz;
@@ -452,7 +461,7 @@ __device__ __forceinline__ bool sphere_certainly_missed(const BvhLeafPrim &lp, c
     const float px = __builtin_fmaf(-t, r.dx, cx), py = __builtin_fmaf(-t, r.dy, cy), pz = __builtin_fmaf(-t, r.dz, cz);
     const float p2 = __builtin_fmaf(pz, pz, __builtin_fmaf(py, py, px * px));
     const float R = lp.reach32;
-    return p2 > R * R || t + R < 0.0f || t - R > lim;
+    return (p2 > R * R || t + R < 0.0f || t - R > lim) && p2 < INFINITY;
 }
 /* a distance limit for f32 comparisons, rounded UP (inf stays inf, 0 stays 0) */
 __device__ __forceinline__ float bvh_limit32(double limit) { return (float)limit * 1.00000024f; }
@@ -3065,6 +3074,7 @@ enum
     DRT_UNIT_SEED_AND_DRAW,     /* in: path key (u64 bits)                 out: state (bits), first rng() src/rng.c:1-12, SURVEY 8a-R */
     DRT_UNIT_BVH_BOX,           /* in: o[3] d[3] lo[3] hi[3] (box in f32 values) out: the f32 slab test's entry bound, or < 0 = box rejected (bvh_box_entry) */
     DRT_UNIT_LINE_PLANE_LIMITED, /* in: LINE_PLANE's 18, limit, want (0 = false) out: line_plane_limited: t where want && t < limit, else +inf */
+    DRT_UNIT_BVH_SPHERE,        /* in: o[3] d[3] c[3] r E limit (o as bvh_walk receives it) out: 1 = sphere_certainly_missed, else 0; line_sphere(o, d, c, r) */
     DRT_UNIT_COUNT
 };
 
@@ -3139,6 +3149,16 @@ __global__ void drt_unit_kernel(int func, const double *__restrict__ in, uint32_
             V3 u = V(12), v = V(15);
             double ul = v_length(u), vl = v_length(v);
             o[0] = line_plane_limited(V(0), V(3), V(6), V(9), v_div(u, ul), v_div(v, vl), ul, vl, a[18], a[19] != 0.0);
+            break;
+        }
+        case DRT_UNIT_BVH_SPHERE:
+        {
+            /* the leaf as build_device_scene and drt_bvh_leaf_kernel fill it, the ray and the limit as bvh_walk makes them */
+            BvhLeafPrim lp;
+            for (int k = 0; k < 3; k += 1) lp.c32[k] = (float)a[6 + k];
+            lp.reach32 = bvh_sphere_reach32(a[9], a[10]);
+            o[0] = sphere_certainly_missed(lp, bvh_ray32(V(0), V(3)), bvh_limit32(a[11])) ? 1.0 : 0.0;
+            o[1] = line_sphere(V(0), V(3), V(6), a[9]);
             break;
         }
         default: break;

@@ -735,9 +735,7 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
             if (stype[i] == DRT_GEO_SPHERE)
             {
                 for (int f = 0; f < 3; f += 1) leaf[k].c32[f] = (float)leaf[k].f[f];
-                /* radius + 64 u E (drt_kernels.h, sphere_certainly_missed), rounded up twice over */
-                float reach = (float)(std::fabs(leaf[k].f[3]) + std::ldexp(bb.extent, -18));
-                leaf[k].reach32 = std::nextafterf(std::nextafterf(reach, INFINITY), INFINITY);
+                leaf[k].reach32 = bvh_sphere_reach32(leaf[k].f[3], bb.extent);
             }
         }
         if ((rc = upload(ctx, bb.nodes, &d.bvh_nodes))) return rc;
@@ -3631,6 +3629,30 @@ static int bind_rays_check(const drt_context *ctx, const drt_ray_table *t, const
     }
     if (ctx->film_used || ctx->adaptive_done)
         return fail(-7, "%s: the film holds samples, and the first ray cannot change under them: drt_reset_film first", name);
+    /* Behind the hierarchy a first direction keeps its length through mirror and glass vertices into drt_bounce_kernel's walk, which
+     * is derived for |d| = 1 (drt_ray_kernels.h, RAY_UNIT_TOLERANCE) and which the camera path shares: there is no scan to fall back
+     * on, so a table the host can read is looked at here, the tile's rows of every layer. Zero, NaN and infinite directions pass. */
+    if (t && !(t->flags & DRT_RAYS_DEVICE) && ctx->use_bvh)
+    {
+        const drt_params &p = ctx->params;
+        for (uint64_t l = 0; l < t->n_layers; l += 1)
+            for (uint32_t j = 0; j < p.tile_h; j += 1)
+            {
+                const uint32_t y = p.y0 + j * p.row_stride;
+                const double *row = t->dirs + ((l * p.height + y) * p.width + p.x0) * 3u;
+                for (uint32_t i = 0; i < p.tile_w; i += 1)
+                {
+                    const double *d = row + 3u * i;
+                    const bool finite = std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2]);
+                    const bool zero = d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0;
+                    const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+                    if (finite && !zero && !(std::fabs(dd - 1.0) <= RAY_UNIT_TOLERANCE))
+                        return fail(-1, "%s: layer %llu, pixel (%u, %u): the direction (%.17g, %.17g, %.17g) is not of unit length (d.d = %.17g, "
+                                        "| d.d - 1 | > 2^-42) and the scene is behind the hierarchy, whose walk holds for |d| = 1: normalise the table's directions",
+                                    name, (unsigned long long)l, p.x0 + i, y, d[0], d[1], d[2], dd);
+                }
+            }
+    }
     return 0;
 }
 
@@ -4927,8 +4949,8 @@ extern "C" int drt_selftest_unit(int device, int func, const double *in, uint32_
     if (func < 0 || func >= DRT_UNIT_COUNT) return fail(-1, "unknown unit function %d", func);
     if (!in || !out || in_stride == 0 || out_stride == 0) return fail(-1, "null argument");
     /* what each function reads and writes per record: a caller with narrower records would make the kernel read past its buffers */
-    static const uint32_t need_in[DRT_UNIT_COUNT] = {10, 18, 6, 8, 6, 1, 1, 7, 10, 3, 4, 1, 12, 20};
-    static const uint32_t need_out[DRT_UNIT_COUNT] = {1, 1, 3, 3, 9, 4, 4, 1, 1, 1, 1, 2, 1, 1};
+    static const uint32_t need_in[DRT_UNIT_COUNT] = {10, 18, 6, 8, 6, 1, 1, 7, 10, 3, 4, 1, 12, 20, 12};
+    static const uint32_t need_out[DRT_UNIT_COUNT] = {1, 1, 3, 3, 9, 4, 4, 1, 1, 1, 1, 2, 1, 1, 2};
     if (in_stride < need_in[func] || out_stride < need_out[func])
         return fail(-1, "unit function %d needs %u doubles in and %u out per record", func, need_in[func], need_out[func]);
     if (n == 0) return 0;

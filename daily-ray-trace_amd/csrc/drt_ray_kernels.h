@@ -12,7 +12,8 @@
  *
  *   drt_ray_closest_kernel<PIXELS>      scenes in LDS: first_hit_lds
  *   drt_ray_visible_kernel              scenes in LDS: points_mutually_visible<true>
- *   drt_ray_closest_bvh_kernel<PIXELS>  scenes behind the hierarchy: first_hit_bvh
+ *   drt_ray_closest_bvh_kernel<PIXELS>  scenes behind the hierarchy: first_hit_bvh; a caller's direction that is not of unit length
+ *                                       (RAY_UNIT_TOLERANCE): the LDS kernel's loop over the tables in HBM
  *   drt_ray_visible_bvh_kernel          scenes behind the hierarchy: bvh_walk JOB_SHADOW
  * PIXELS: the lane builds the path's own camera ray of (x, y, sample) with feature_ray in place of loading a ray (drt_cast_pixels).
  */
@@ -154,6 +155,20 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_visible_kernel(DevScene sc,
     }
 }
 
+/* How far d.d may be from 1 for a caller's ray to take the hierarchy walk: 2^-42. The walk's f32 tests and its distance pruning are
+ * derived for |d| = 1, and the rule (line_sphere_intersection sets a = 1 whatever |d| is) is not the geometric answer otherwise. On
+ * the device the sphere filter rejects no hit for | d.d - 1 | up to 2^-38 (k_ok = 16384 of tests/test_gpu_sphere_filter.py's length
+ * family; first false rejections at 2^-36); the constant is a sixteenth of that, and 1024 ulp of 1, so whatever was normalised in f64
+ * (2.5 ulp) or reflected a few hundred times (280.5 ulp after 524 mirrors) walks. A finite direction beyond it is answered by the
+ * reference's own loop over all surfaces: exact, and as slow as a scene of that size without a hierarchy. NaN and infinite directions
+ * walk, and miss. */
+#define RAY_UNIT_TOLERANCE 0x1p-42
+__device__ __forceinline__ bool ray_off_unit(V3 d)
+{
+    const bool finite = __builtin_fabs(d.x) < DRT_INF && __builtin_fabs(d.y) < DRT_INF && __builtin_fabs(d.z) < DRT_INF;
+    return finite && !(__builtin_fabs(v_dot(d, d) - 1.0) <= RAY_UNIT_TOLERANCE);
+}
+
 template <bool PIXELS>
 __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_closest_bvh_kernel(DevScene sc, DevCamera cam, RayParams rp)
 {
@@ -166,7 +181,17 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_closest_bvh_kernel(DevScene
         const bool valid = i < rp.n;
         V3 ro = v3(0, 0, 0), rd = v3(0, 0, 1);
         if (valid) ray_fetch<PIXELS>(rp, cam, i, true, ro, rd);
-        first_hit_bvh(sv, sc, store, lane, valid, ro, rd, [&](const HitPoint &ip, double min_dist) { ray_store_hit(rp.hits, i, ip, min_dist); });
+        const bool scan = !PIXELS && valid && ray_off_unit(rd); /* (a camera ray is normalised) */
+        first_hit_bvh(sv, sc, store, lane, valid && !scan, ro, rd, [&](const HitPoint &ip, double min_dist) { ray_store_hit(rp.hits, i, ip, min_dist); });
+        if (scan)
+        {
+            /* as drt_ray_closest_kernel, on the tables where they lie; the loop holds no whole-wave operation, so it may run divergent */
+            HitPoint ip = no_hit_point();
+            find_ray_intersection<false>(sv, sc, ip, ro, rd);
+            double distance = 0.0;
+            if (ip.index >= 0) distance = surface_distance(sv, (uint32_t)ip.index, sv.surf_type[ip.index], v_sum(ro, v_mul(rd, DRT_VIS_FUDGE)), rd);
+            ray_store_hit(rp.hits, i, ip, distance);
+        }
     }
 }
 

@@ -208,9 +208,7 @@ __global__ void __launch_bounds__(UPDATE_BLOCK) drt_bvh_leaf_kernel(LeafTables t
     if (lp->type == DRT_GEO_SPHERE)
     {
         for (int f = 0; f < 3; f += 1) lp->c32[f] = (float)r[RAW_POS + f];
-        /* radius + 64 u E (drt_kernels.h, sphere_certainly_missed), rounded up twice over */
-        const float reach = (float)(__builtin_fabs(r[RAW_RADIUS]) + extent * 0x1p-18);
-        lp->reach32 = nextafterf(nextafterf(reach, INFINITY), INFINITY);
+        lp->reach32 = bvh_sphere_reach32(r[RAW_RADIUS], extent);
     }
     /* the leaf's box, padded by 2^-19 extent for the f32 test (BvhBuilder::set_child) */
     const double pad32 = extent * 0x1p-19;

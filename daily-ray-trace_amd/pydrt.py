@@ -1259,10 +1259,11 @@ def selftest_path_ids(bases, steps, n_samples, tile_w, device=0):
 
 
 (UNIT_LINE_SPHERE, UNIT_LINE_PLANE, UNIT_REFLECT, UNIT_TRANSMIT, UNIT_ROTATION_BETWEEN, UNIT_SAMPLE_SPHERE, UNIT_SAMPLE_DISC,
- UNIT_GGX, UNIT_GGX_ATT, UNIT_FS_DIELECTRIC, UNIT_FS_CONDUCTOR, UNIT_SEED_AND_DRAW, UNIT_BVH_BOX, UNIT_LINE_PLANE_LIMITED) = range(14)
+ UNIT_GGX, UNIT_GGX_ATT, UNIT_FS_DIELECTRIC, UNIT_FS_CONDUCTOR, UNIT_SEED_AND_DRAW, UNIT_BVH_BOX, UNIT_LINE_PLANE_LIMITED,
+ UNIT_BVH_SPHERE) = range(15)
 _UNIT_OUT = {UNIT_LINE_SPHERE: 1, UNIT_LINE_PLANE: 1, UNIT_REFLECT: 3, UNIT_TRANSMIT: 3, UNIT_ROTATION_BETWEEN: 9,
              UNIT_SAMPLE_SPHERE: 4, UNIT_SAMPLE_DISC: 4, UNIT_GGX: 1, UNIT_GGX_ATT: 1, UNIT_FS_DIELECTRIC: 1, UNIT_FS_CONDUCTOR: 1,
-             UNIT_SEED_AND_DRAW: 2, UNIT_BVH_BOX: 1, UNIT_LINE_PLANE_LIMITED: 1}
+             UNIT_SEED_AND_DRAW: 2, UNIT_BVH_BOX: 1, UNIT_LINE_PLANE_LIMITED: 1, UNIT_BVH_SPHERE: 2}
 
 
 MAT_EVALUATE, MAT_SAMPLE = 0, 1

@@ -487,6 +487,12 @@ int drt_group_render_mattes(drt_group *g, drt_mattes *m, int32_t *ids, uint32_t 
  * caller's own stream order completes it. There the host cannot read xy: a pixel outside the image gets a NaN ray, which misses.
  * In a context whose scene is behind the hierarchy (DRT_PATH_BVH) the box tests' error budget covers origins within the extent the
  * hierarchy was built for (the scene and the camera); origins far outside it are not held to the rule.
+ * Directions in a DRT_PATH_BVH context: the hierarchy walk is derived for |d| = 1, and the rule is not the geometric answer otherwise
+ * (line_sphere_intersection sets a = 1 whatever |d| is). drt_cast_rays keeps the rule bit for bit all the same: a ray whose finite
+ * direction has | d.d - 1 | > 2^-42 is answered by the reference's own loop over ALL surfaces, so it costs a scan of the whole scene
+ * instead of a walk (anything normalised in f64 is far inside the tolerance). NaN and infinite directions walk, and miss; for an
+ * infinite component the rule can answer a hit at -inf, so behind the hierarchy infinite directions are not held to the rule.
+ * drt_test_visibility normalises its own directions; drt_cast_pixels casts the camera's.
  */
 typedef struct drt_ray_hit /* scene_point, src/daily_ray_trace.h:113-125, plus the distance */
 {
@@ -542,7 +548,12 @@ int drt_group_cast_pixels(drt_group *g, const uint32_t *xy, const uint32_t *samp
  * writes, the XYZ mode, the hit log, the denoiser, drt_cast_rays and drt_test_visibility work as before; drt_render_features,
  * drt_render_mattes, drt_cast_pixels and their group forms are refused, since they ask for the camera's rays. drt_stats.path_flags
  * carries DRT_PATH_RAYS while a table is bound. As for the ray queries, in a DRT_PATH_BVH context the box tests' error budget covers origins
- * within the extent the hierarchy was built for (the scene and the context's camera).
+ * within the extent the hierarchy was built for (the scene and the context's camera). Directions there: a first direction keeps its
+ * length through mirror and glass vertices into the hierarchy walk, which is derived for |d| = 1, and the path has no scan to fall
+ * back on. So in a DRT_PATH_BVH context host mode refuses a table whose tile rows hold a finite, nonzero direction with
+ * | d.d - 1 | > 2^-42 (the message names the first such layer and pixel; nothing is changed, no film bit included); zero, NaN and
+ * infinite directions are taken. Device mode cannot look at the table: there such rays are not held to the rule. Contexts scanned
+ * out of LDS take any direction and give the rule's answer.
  */
 typedef struct drt_ray_table
 {
@@ -691,7 +702,10 @@ int drt_selftest_path_ids(int device, const uint64_t *bases, uint32_t n_draws, c
  *  12 the hierarchy's f32 box test (prunes the scan of src/daily_ray_trace.c:340-364; no reference counterpart)
  *                                                          in o[3] d[3] lo[3] hi[3]            out lower bound of the entry distance, < 0: rejected
  *  13 line_plane_limited, the plane test of the LDS row scans (csrc/drt_device.h; the reference's function cut short where the scan's
- *     one comparison `t < limit` cannot come out true)    in func 1's 18, limit, want (0 = false)  out t where want and t < limit, else +inf */
+ *     one comparison `t < limit` cannot come out true)    in func 1's 18, limit, want (0 = false)  out t where want and t < limit, else +inf
+ *  14 the hierarchy's f32 sphere filter, sphere_certainly_missed (csrc/drt_kernels.h; spares the f64 intersector, no reference
+ *     counterpart), on the leaf, the f32 ray and the f32 limit the walk makes from the record; E is the extent the leaf's pad is for
+ *                                                          in o[3] d[3] c[3] r E limit         out 1 = "certainly missed" else 0, func 0's t */
 int drt_selftest_unit(int device, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
 
 /* Material-layer self-test: runs n records (`in_stride` doubles in, `out_stride` doubles out per record) against the device scene of

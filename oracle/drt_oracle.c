@@ -957,12 +957,34 @@ static int cast_ray(const drt_scene *sc, double *dst, v3 ray_origin, v3 ray_dire
     return scans;
 }
 
+/* A ray film's table (include/drt_hip.h, drt_bind_rays): while one is set, sample_scene takes the first ray of image pixel (x, y),
+ * absolute sample s from entry ((s % n_layers) * height + y) * width + x as it stands -- no draw, no normalisation -- and the weight
+ * (1.0 without weights) stands where dot(ray_direction, forward) stood. Read-only while a render runs. */
+static const double *g_rt_origins = NULL, *g_rt_dirs = NULL, *g_rt_weights = NULL;
+static uint32_t g_rt_layers = 0;
+void drt_oracle_set_ray_table(const double *origins, const double *dirs, const double *weights, uint32_t n_layers)
+{
+    g_rt_origins = origins; g_rt_dirs = dirs; g_rt_weights = weights;
+    g_rt_layers = (origins && dirs) ? n_layers : 0;
+}
+
 /* sample_pixel_point :550-569 and sample_scene :571-618 */
 static int sample_scene(const drt_scene *sc, const drt_camera *cam, double *contribution, double *filter,
-                        uint32_t x, uint32_t y, uint32_t max_depth, uint32_t scheme, int32_t *hit_seq)
+                        uint32_t x, uint32_t y, uint32_t max_depth, uint32_t scheme, int32_t *hit_seq,
+                        uint32_t width, uint32_t height, uint32_t sample)
 {
     uint32_t S = sc->num_wavelengths;
     memset(contribution, 0, S * sizeof(double));
+    if (g_rt_layers)
+    {
+        uint64_t r = ((uint64_t)(sample % g_rt_layers) * height + y) * width + x;
+        if (hit_seq) for (uint32_t d = 0; d < max_depth; d += 1) hit_seq[d] = -2;
+        int scans = cast_ray(sc, contribution, from3(g_rt_origins + 3 * r), from3(g_rt_dirs + 3 * r), max_depth, hit_seq);
+        double m = (g_rt_weights ? g_rt_weights[r] : 1.0) * 1.0;
+        for (uint32_t k = 0; k < S; k += 1) contribution[k] = contribution[k] * m;
+        *filter = 1.0;
+        return scans;
+    }
     double px = 0.0, py = 0.0;
     if (scheme == DRT_FILM_SAMPLE_CENTER) { px = 0.5; py = 0.5; }
     else if (scheme == DRT_FILM_SAMPLE_RANDOM) { px = rng(); py = rng(); }
@@ -1005,7 +1027,7 @@ int drt_oracle_sample_scene(const drt_scene *sc, const drt_camera *cam, const dr
                             uint32_t x, uint32_t y, uint32_t sample, double *contribution, double *filter, int32_t *hit_seq)
 {
     drt_oracle_seed_path(drt_oracle_path_key(p->seed, p->width, p->height, x, y, sample));
-    return sample_scene(sc, cam, contribution, filter, x, y, p->max_depth, p->pixel_scheme, hit_seq);
+    return sample_scene(sc, cam, contribution, filter, x, y, p->max_depth, p->pixel_scheme, hit_seq, p->width, p->height, sample);
 }
 
 /* The pixel loop of render_image, :710-745, over one tile. */
@@ -1049,7 +1071,7 @@ static void *render_rows(void *arg)
                     ? job->hits + (((uint64_t)s * p->tile_h + j) * p->tile_w + i) * p->max_depth : NULL;
                 double filter = 0.0;
                 drt_oracle_seed_path(drt_oracle_path_key(p->seed, p->width, p->height, x, y, sample));
-                sample_scene(job->sc, job->cam, contribution, &filter, x, y, p->max_depth, p->pixel_scheme, hit_seq);
+                sample_scene(job->sc, job->cam, contribution, &filter, x, y, p->max_depth, p->pixel_scheme, hit_seq, p->width, p->height, sample);
                 paths += 1;
                 for (uint32_t k = 0; k < S; k += 1) dst_pixel[k] = dst_pixel[k] + contribution[k]; /* :732 */
                 dst_pixel[S] += filter;                                                            /* :733 */
@@ -1180,6 +1202,14 @@ void drt_oracle_film_to_xyz(const drt_scene *sc, const double *pixels, uint64_t 
 double drt_oracle_line_sphere(const double o[3], const double d[3], const double c[3], double r)
 {
     return line_sphere(from3(o), from3(d), from3(c), r);
+}
+void drt_oracle_line_sphere_records(const double *rec, uint32_t stride, uint64_t n, double *out)
+{
+    for (uint64_t i = 0; i < n; i += 1)
+    {
+        const double *a = rec + i * stride;
+        out[i] = drt_oracle_line_sphere(a, a + 3, a + 6, a[9]);
+    }
 }
 double drt_oracle_line_plane(const double o[3], const double d[3], const double p[3], const double n[3], const double u[3], const double v[3])
 {

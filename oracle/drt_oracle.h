@@ -82,6 +82,11 @@ int drt_oracle_sample_scene(const drt_scene *scene, const drt_camera *camera, co
                             uint32_t x, uint32_t y, uint32_t sample,
                             double *contribution, double *filter, int32_t *hit_seq);
 
+/* A ray film (drt_bind_rays): origins / dirs [n_layers][height][width][3], weights [n_layers][height][width] or NULL, over the whole
+ * image of the params given to the calls above, which then start every path from the table instead of the camera. NULL origins:
+ * back to the camera. The arrays stay the caller's and must outlive the renders. */
+void drt_oracle_set_ray_table(const double *origins, const double *dirs, const double *weights, uint32_t n_layers);
+
 /* spectrum_to_xyz (src/spectrum.c:49-70). */
 void drt_oracle_spectrum_to_xyz(const drt_scene *scene, const double *spd, double xyz[3]);
 /* Per-pixel XYZ of sum/filter for a [n_pixels][S+1] film (src/daily_ray_trace.c:15-23 + spectrum_to_xyz). */
@@ -90,6 +95,8 @@ void drt_oracle_film_to_xyz(const drt_scene *scene, const double *pixels, uint64
 /* ---- unit-level entry points (pinned one by one against oracle/_ref) ----------------------- */
 
 double drt_oracle_line_sphere(const double o[3], const double d[3], const double c[3], double r);
+/* drt_oracle_line_sphere of n records `o[3] d[3] c[3] r ...`, `stride` doubles apart: out[i], one call for a whole table */
+void   drt_oracle_line_sphere_records(const double *rec, uint32_t stride, uint64_t n, double *out);
 double drt_oracle_line_plane(const double o[3], const double d[3], const double p[3], const double n[3],
                              const double u[3], const double v[3]);
 void   drt_oracle_reflect(const double v[3], const double n[3], double out[3]);

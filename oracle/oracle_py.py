@@ -2,6 +2,7 @@
 was built, oracle/_ref/libdrt_ref.so (the real reference path). Imported by tests/, bench.py's
 cpu_baseline leg and __graft_entry__.smoke() only -- never by the product.
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -65,6 +66,10 @@ def oracle_lib():
         L.drt_oracle_film_to_xyz.argtypes = [S, f64p, C.c_uint64, f64p]
         L.drt_oracle_line_sphere.restype = C.c_double
         L.drt_oracle_line_sphere.argtypes = [f64p, f64p, f64p, C.c_double]
+        L.drt_oracle_set_ray_table.restype = None
+        L.drt_oracle_set_ray_table.argtypes = [f64p, f64p, f64p, C.c_uint32]
+        L.drt_oracle_line_sphere_records.restype = None
+        L.drt_oracle_line_sphere_records.argtypes = [f64p, C.c_uint32, C.c_uint64, f64p]
         L.drt_oracle_line_plane.restype = C.c_double
         L.drt_oracle_line_plane.argtypes = [f64p] * 6
         L.drt_oracle_reflect.argtypes = [f64p, f64p, f64p]
@@ -96,6 +101,21 @@ def oracle_lib():
         L.drt_oracle_direct_light.argtypes = [S, C.POINTER(Point), f64p]
         _oracle = L
     return _oracle
+
+
+@contextlib.contextmanager
+def ray_table(origins, dirs, weights=None):
+    """while inside, the oracle's renders start every path from this table ([L][h][w][3] or [h][w][3] over the whole image, weights
+    [L][h][w] or None) instead of the camera: drt_bind_rays' rule"""
+    o, d = (np.ascontiguousarray(a, dtype=np.float64) for a in (origins, dirs))
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    layers = o.shape[0] if o.ndim == 4 else 1
+    assert o.shape == d.shape and (w is None or w.shape == o.shape[:-1])
+    oracle_lib().drt_oracle_set_ray_table(_ptr(o), _ptr(d), _ptr(w), layers)
+    try:
+        yield
+    finally:
+        oracle_lib().drt_oracle_set_ray_table(None, None, None, 0)
 
 
 def set_math_mode(mode):

@@ -7,6 +7,10 @@ cast_ray and gives every sample of a pixel the same ray, so a ray table filled w
 feature_rule.camera_rays -- and weighted with that camera's vignette must reproduce the camera's film bit for bit. Tables stitched
 from several cameras, by rows or by layers, are general rays with the same ground truth: each part is some camera's film.
 
+One case has no camera behind it: scaled_rows(), the table with directions that are not of unit length. Its ground truth is the
+oracle rendering from the table itself (drt_oracle_set_ray_table), which tests/test_ray_film_cpu.py first holds to the camera's film
+on the unscaled table.
+
 Every camera here is forced to aperture_radius = 0 and every params block to FILM_SAMPLE_CENTER. A weight is
 rd[0]*f[0] + rd[1]*f[1] + rd[2]*f[2] in that order (v_dot's); the path header stores that value * 1.0."""
 import numpy as np
@@ -84,6 +88,23 @@ def camera_table(name):
             a.setflags(write=False)
         _tables[name] = t
     return _tables[name]
+
+
+SCALED_ROWS = "lights"  # scanned out of LDS: the reference's own loop, which takes a direction of any length
+
+
+def scaled_rows(name=SCALED_ROWS):
+    """the camera-parity case's own table with the directions of the even rows multiplied by 2 and those of the odd rows by 0.5.
+    Such rays are no camera's: the ground truth is the oracle rendering from the same table (oracle_py.ray_table). Under the rule a
+    sphere's answer depends on |d| (line_sphere_intersection sets a = 1), so this is another film than the camera's."""
+    key = "scaled:" + name
+    if key not in _tables:
+        o, d, w = camera_table(name)
+        f = np.where(np.arange(d.shape[0]) % 2 == 0, 2.0, 0.5)[:, None, None]
+        t = (o, np.ascontiguousarray(d * f), w)
+        t[1].setflags(write=False)
+        _tables[key] = t
+    return _tables[key]
 
 
 def stitch(scene):

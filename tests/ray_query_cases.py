@@ -8,6 +8,14 @@ Per scene, the rays are
       unit directions;
   (c) rays with one and with two exact-zero direction components, from points inside the scene's bounds;
   (d) one each of: a NaN direction, a zero direction, an infinite origin, a ray that starts exactly on a surface;
+  (e) `scaled`, directions that are not of unit length: every second ray of (b) (all of them, five times over, take the closed scene
+      deg_camera_inside_the_glass_ball below the 10 % of misses the CPU test asserts) and rays that graze the scene's spheres, each with d
+      multiplied by 0.5, 2, 1 + 2^-20, 1e-3 and 1e3, and the unnormalised directions `light point - hit position`. The rule
+      (line_sphere_intersection sets a = 1 whatever |d| is) does not give such a ray the answer of its normalised ray: a grazing ray
+      passes its sphere outside by a quarter of what the factor 1 + 2^-20 adds to the discriminant, or inside by as much, so a longer
+      d hits a sphere the unit ray misses and a shorter one misses a sphere it hits. "Normalise first" is not a passing
+      implementation; tests/test_ray_query_cpu.py asserts that per factor, in every scene that has a sphere (a plane's answer does
+      not depend on |d|);
 and the visibility pairs are (hit position, a point on each light), (hit position, the hit position of another pixel), p0 == p1,
 pairs whose segment ends exactly on a surface (the camera ray's origin and its own hit position), neighbours a step apart and
 segments that leave the scene's bounds. The last two and the `away` probe rays (from a shell around the scene, pointing outward) keep
@@ -43,6 +51,8 @@ SCENE_NAMES = sorted({n for n, _ in ALL_SCENES})
 # cornell_plane_light.scn and cornell_gold_mirror.scn let no ray from inside escape, but the `away` probe rays start outside them,
 # so every scene meets the bound.
 CLOSED_ROOMS = frozenset()
+
+SCALE_FACTORS = (0.5, 2.0, 1.0 + 2.0 ** -20, 1e-3, 1e3)
 
 _loaded, _sets, _expected = {}, {}, {}
 
@@ -162,8 +172,32 @@ def _light_points(bundle, rng):
     return np.array(pts).reshape(-1, 3)
 
 
+def spheres_of(bundle):
+    sc = bundle.scene
+    return [sc.surfaces[i] for i in range(int(sc.num_surfaces)) if int(sc.surfaces[i].type) == pydrt.GEO_SPHERE]
+
+
+def _grazing(bundle, rng, per_sphere=8, most=8):
+    """unit rays along tangents of up to `most` spheres, from 0.5 to 2 radii before the tangent point, moved outward (even rays) or
+    inward (odd rays) by 2^-22 t^2 / r: a quarter of the 2^-19 t^2 that |d| = 1 + 2^-20 adds to the rule's discriminant / 4"""
+    sph = [s for s in spheres_of(bundle) if 1e-6 < abs(float(s.radius)) < 1e3]
+    sph = sph[:: max(1, len(sph) // most)][:most]
+    o, d = [], []
+    for s in sph:
+        c, r = np.array(list(s.position)), abs(float(s.radius))
+        nrm = _unit(rng, per_sphere)
+        u = np.cross(nrm, _unit(rng, per_sphere))
+        u /= np.sqrt((u * u).sum(axis=1))[:, None]
+        t = rng.uniform(0.5, 2.0, per_sphere) * r
+        off = np.where(np.arange(per_sphere) % 2 == 0, 1.0, -1.0) * 2.0 ** -22 * t * t / r
+        o.append(c + (r + off)[:, None] * nrm - t[:, None] * u)
+        d.append(u)
+    return (np.concatenate(o), np.concatenate(d)) if o else (np.zeros((0, 3)), np.zeros((0, 3)))
+
+
 def ray_sets(name):
-    """{"rays": (origins, dirs), "parts": {set name: slice}, "pairs": (p0, p1), "pair_parts": {...}, "camera": (xy, samples)}"""
+    """{"rays": (origins, dirs), "parts": {set name: slice}, "pairs": (p0, p1), "pair_parts": {...}, "camera": (xy, samples),
+    "scaled": (base origins, base unit dirs, factor of every ray of the part `scaled`; 0 = an unnormalised light direction)}"""
     if name in _sets:
         return _sets[name]
     bundle, params = load(name)
@@ -203,6 +237,22 @@ def ray_sets(name):
     on_normal = cam_hits["normal"][hit[0]] if len(hit) else np.array([0.0, 1.0, 0.0])
     add("special", [centre, centre, [np.inf, 0.0, 0.0], on_surface],
         [[np.nan, 0.0, 1.0], [0.0, 0.0, 0.0], [-1.0, 0.0, 0.0], on_normal])
+    # (e): after every other part, whose places in the list the other tests rely on
+    rng_e = np.random.default_rng(0xE5CA + sum(map(ord, name)))  # its own stream: the draws of the other parts stay what they were
+    lights = _light_points(bundle, rng_e)
+    so, sd = _grazing(bundle, rng_e)
+    if len(take):
+        so = np.concatenate([so, O_[1][::2], O_[2][::2]])
+        sd = np.concatenate([sd, D_[1][::2], D_[2][::2]])
+    lo_, ld_ = np.zeros((0, 3)), np.zeros((0, 3))
+    if len(take) and len(lights):
+        lo_ = np.concatenate([cam_hits["position"][take][k::2] for k in range(min(2, len(lights)))])
+        ld_ = np.concatenate([lights[k] - cam_hits["position"][take][k::2] for k in range(min(2, len(lights)))])
+    with np.errstate(all="ignore"):
+        ln_ = np.sqrt((ld_ * ld_).sum(axis=1))[:, None]
+        scaled = (np.concatenate([so] * len(SCALE_FACTORS) + [lo_]), np.concatenate([sd] * len(SCALE_FACTORS) + [ld_ / ln_]),
+                  np.concatenate([np.repeat(np.array(SCALE_FACTORS), len(so)), np.zeros(len(lo_))]))
+    add("scaled", scaled[0], np.concatenate([sd * f for f in SCALE_FACTORS] + [ld_]))
     origins, dirs = np.ascontiguousarray(np.concatenate(O_)), np.ascontiguousarray(np.concatenate(D_))
 
     pair_parts, P0, P1 = {}, [], []
@@ -228,7 +278,7 @@ def ray_sets(name):
     add_pairs("a_step_apart", base, base + _unit(rng, m) * 0.05)
     add_pairs("out_of_bounds", base, centre + _unit(rng, m) * (3.0 * np.sqrt(((hi - lo) ** 2).sum())))
     _sets[name] = {"rays": (origins, dirs), "parts": parts, "pairs": (np.ascontiguousarray(np.concatenate(P0)), np.ascontiguousarray(np.concatenate(P1))),
-                   "pair_parts": pair_parts, "camera": (xy, smp)}
+                   "pair_parts": pair_parts, "camera": (xy, smp), "scaled": scaled}
     return _sets[name]
 
 

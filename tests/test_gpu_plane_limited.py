@@ -161,7 +161,10 @@ def test_unit_tables_agree():
     for i, name in enumerate(names):
         assert getattr(pydrt, name[len("DRT_"):]) == i, name
         assert pydrt._UNIT_OUT[i] == need_out[i], name
-    assert names[-1] == "DRT_UNIT_LINE_PLANE_LIMITED" and names[-2] == "DRT_UNIT_BVH_BOX"
-    assert need_in[-1] == need_in[names.index("DRT_UNIT_LINE_PLANE")] + 2 and need_out[-1] == 1
+    assert names[13] == "DRT_UNIT_LINE_PLANE_LIMITED" and names[12] == "DRT_UNIT_BVH_BOX"
+    assert need_in[13] == need_in[names.index("DRT_UNIT_LINE_PLANE")] + 2 and need_out[13] == 1
     header = open(os.path.join(repo, "include", "drt_hip.h")).read()
-    assert re.search(r"^ \*\s+%d line_plane_limited" % (len(names) - 1), header, re.M)
+    assert re.search(r"^ \*\s+13 line_plane_limited", header, re.M)
+    # the functions added since keep the table in step (tests/test_gpu_sphere_filter.py runs function 14)
+    assert names[14:] == ["DRT_UNIT_BVH_SPHERE"] and need_in[14] == 12 and need_out[14] == 2
+    assert re.search(r"^ \*\s+14 the hierarchy's f32 sphere filter", header, re.M)

@@ -66,6 +66,24 @@ def test_a_table_of_the_cameras_rays_gives_the_cameras_film(name):
     assert st.rng_draws == ost.rng_draws and np.any(opx[:, :-1] != 0.0)
 
 
+# ------------------------------------------------------------------------------------------------ 1b
+def test_rows_with_directions_that_are_not_of_unit_length_against_the_oracle():
+    """A context scanned out of LDS takes the table's directions as given: with those of alternate rows multiplied by 2 and by 0.5 the
+    film, the hit log and the counts are the oracle's, rendering from the same table, bit for bit (and not the camera's film)."""
+    import oracle_py as O
+    name = R.SCALED_ROWS
+    bundle, p = R.load(name)
+    table = R.scaled_rows()
+    film, log, st = render(bundle, p, table, hits=True)
+    assert st.path_flags & pydrt.PATH_RAYS and not st.path_flags & pydrt.PATH_BVH
+    with O.ray_table(*table):
+        opx, oav, ova, olog, ost = cases.oracle_render_device_pow(bundle, p, want_hits=True)
+    assert_same_film(film, (opx, oav, ova), name + " scaled rows against the oracle")
+    assert np.array_equal(log, olog)
+    assert cases.stat_counts(st) == cases.stat_counts(ost)
+    assert not cases.same_bits(film[0], parity_ray_film(name)[0][0])
+
+
 # ------------------------------------------------------------------------------------------------ 2
 @pytest.mark.parametrize("scene", R.STITCH_SCENES)
 def test_rows_stitched_from_three_cameras_give_each_cameras_tile(scene):
@@ -357,6 +375,52 @@ def test_binding_state_and_refusals():
             r.bind_rays(o, d, w)
     finally:
         r.close()
+    # behind the hierarchy, host mode: a table with a finite, nonzero direction that is not of unit length is refused, the first such
+    # layer and pixel named, nothing changed -- no film bit included; zero, NaN and infinite directions are taken
+    name = "spheres_1500"
+    bundle, p = R.load(name)
+    o, d, w = R.camera_table(name)
+    H, W = d.shape[:2]
+    two = (np.stack([o, o]), np.stack([d, d]), np.stack([w, w]))
+    fresh, _, st = render(bundle, p)
+    assert st.path_flags & pydrt.PATH_BVH
+    r = pydrt.Renderer(bundle, p)
+    g = pydrt.Group(bundle, R.params_like(p, flags=0), devices=[0, 0])
+    try:
+        for layer, y, x, factor in ((0, 2, 3, 2.0), (1, H - 1, W - 1, 0.5), (1, 5, 0, 1.0 + 2.0 ** -40), (0, 0, 1, 1e-3)):
+            bad = two[1].copy()
+            bad[layer, y, x] *= factor
+            bad[1, H - 1, W - 1] *= 3.0  # a later one, or the same: the FIRST is named
+            for who in (r, g):
+                with pytest.raises(RuntimeError, match=r"layer %d, pixel \(%d, %d\).*unit length" % (layer, x, y)):
+                    who.bind_rays(two[0], bad, two[2])
+                assert not who.stats().path_flags & pydrt.PATH_RAYS
+        r.render()
+        assert_same_film(r.read_film(), fresh, "the camera's film after the refused bindings")
+        r.reset_film()
+        odd = two[1].copy()
+        odd[0, 0, 0] = 0.0
+        odd[0, 1, 1] = np.nan
+        odd[1, 2, 2, 0] = np.inf
+        odd[1, 3, 3] *= 1.0 + 2.0 ** -44  # inside the tolerance
+        r.bind_rays(two[0], odd, two[2])
+        assert r.stats().path_flags & pydrt.PATH_RAYS
+        g.bind_rays(two[0], odd, two[2])
+        assert g.stats().path_flags & pydrt.PATH_RAYS
+    finally:
+        r.close()
+        g.close()
+    # out of LDS any direction is taken (test_rows_with_directions_that_are_not_of_unit_length_against_the_oracle renders it)
+    bundle, p = R.load(R.SCALED_ROWS)
+    r = pydrt.Renderer(bundle, p)
+    try:
+        r.bind_rays(*R.scaled_rows())
+        assert r.stats().path_flags & pydrt.PATH_RAYS and not r.stats().path_flags & pydrt.PATH_BVH
+    finally:
+        r.close()
+    name = "lights"
+    bundle, p = R.load(name)
+    o, d, w = R.camera_table(name)
     # shapes pydrt refuses before the C call
     r = pydrt.Renderer(bundle, p)
     try:

@@ -299,3 +299,37 @@ def test_a_checkpoint_belongs_to_its_projection():
         assert ("scene %x\n" % hsh) in manifests[0]
     finally:
         H.drt_host_checkpoint_projection(CAMERA, 0.0)
+
+
+def test_the_oracles_ray_table_is_the_cameras_film_and_the_scaled_rows_are_not():
+    """The oracle's own ray film (drt_oracle_set_ray_table): from the camera's table it is the camera's film, bit for bit, hit log and
+    counts included; through two layers it is sample s through camera s % 2, as tests/test_gpu_ray_film.py builds it sample by sample;
+    and the table of R.scaled_rows() gives another hit log -- on even rows (d times 2) and on odd rows (d times 0.5) -- so the GPU
+    test that binds it checks more than the camera cases do."""
+    name = R.SCALED_ROWS
+    bundle, p = R.load(name)
+    o, d, w = R.camera_table(name)
+    cam = O.oracle_render_tile(bundle, p, want_hits=True, math_mode=O.MATH_DEVICE)
+    with O.ray_table(o, d, w):
+        tab = O.oracle_render_tile(bundle, p, want_hits=True, math_mode=O.MATH_DEVICE)
+    for a, b in zip(cam[:3], tab[:3]):
+        assert cases.same_bits(a, b), cases.first_difference(a, b)
+    assert np.array_equal(cam[3], tab[3]) and cases.stat_counts(cam[4]) == cases.stat_counts(tab[4])
+    after = O.oracle_render_tile(bundle, p, want_hits=True, math_mode=O.MATH_DEVICE)  # the table is gone after the block
+    assert cases.same_bits(after[0], cam[0])
+    ly = R.layers()
+    want = R.render_by_samples(lambda b, q, film: O.oracle_render_tile(b, q, math_mode=O.MATH_DEVICE, film=film), ly["cameras"], ly["params"])
+    with O.ray_table(*ly["table"]):
+        got = O.oracle_render_tile(ly["bundle"], ly["params"], math_mode=O.MATH_DEVICE)
+    for a, b in zip(got[:3], want):
+        assert cases.same_bits(a, b), cases.first_difference(a, b)
+    so, sd, sw = R.scaled_rows()
+    W, H = int(p.width), int(p.height)
+    assert np.array_equal(sd[0::2], d[0::2] * 2.0) and np.array_equal(sd[1::2], d[1::2] * 0.5) and so is o and sw is w
+    with O.ray_table(so, sd, sw):
+        sc = O.oracle_render_tile(bundle, p, want_hits=True, math_mode=O.MATH_DEVICE)
+    first = lambda log: log[:, 0].reshape(int(p.spp), H, W)[0]
+    differ = first(sc[3]) != first(cam[3])
+    print("%s: first hits that differ from the camera's: %d on even rows, %d on odd rows" % (name, differ[0::2].sum(), differ[1::2].sum()))
+    assert differ[0::2].any() and differ[1::2].any()
+    assert not cases.same_bits(sc[0], cam[0])

@@ -151,3 +151,33 @@ def test_the_restated_camera_rays_hit_what_the_paths_own_hit_log_says():
         first = log[:, 0].reshape(spp, P)
         cam = Q.expected(name)["hits"]["index"][Q.ray_sets(name)["parts"]["camera"]].reshape(2, P)
         assert np.array_equal(cam, first[:2])
+
+
+# exempt from the assertion below, by name: a scene that loses its spheres fails instead of going unchecked. None today.
+SCENES_WITHOUT_A_SPHERE = frozenset()
+
+
+@pytest.mark.parametrize("name", Q.SCENE_NAMES)
+def test_scaled_directions_are_not_answered_by_normalising_first(name):
+    """Part (e): per factor, rays whose closest hit under the rule is another surface (or none) than their normalised ray's. Only a
+    sphere can tell: line_plane's hit does not depend on |d|, so a scene without a sphere would be exempt, by name
+    (SCENES_WITHOUT_A_SPHERE) -- none is: every scene of the set has one."""
+    s, e = Q.ray_sets(name), Q.expected(name)
+    part = s["parts"]["scaled"]
+    bo, bd, factor = s["scaled"]
+    ro, rd = s["rays"]
+    assert len(bo) == part.stop - part.start and np.array_equal(ro[part], bo)
+    off = np.abs((bd * bd).sum(axis=1) - 1.0)
+    assert off.max() <= 16 * 2.0 ** -52, off.max() / 2.0 ** -52  # (a mirror direction is a reflected unit vector)
+    for f in Q.SCALE_FACTORS:
+        assert np.array_equal(rd[part][factor == f], bd[factor == f] * f)
+    bundle = Q.load(name)[0]
+    assert bool(Q.spheres_of(bundle)) == (name not in SCENES_WITHOUT_A_SPHERE)
+    if name in SCENES_WITHOUT_A_SPHERE:
+        return
+    base = Q.oracle_hits(bundle, bo, bd)["index"]
+    got = e["hits"]["index"][part]
+    counts = {f: int((base != got)[factor == f].sum()) for f in Q.SCALE_FACTORS}
+    print("%s: %d scaled rays; closest hit differs from the normalised ray's, per factor: %s; light directions: %d of %d" % (
+        name, len(bo), counts, int((base != got)[factor == 0.0].sum()), int((factor == 0.0).sum())))
+    assert all(n >= 1 for n in counts.values()), counts
