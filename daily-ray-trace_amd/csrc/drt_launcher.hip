@@ -13,6 +13,7 @@
 #include "drt_update_kernels.h"
 #include "drt_build_kernels.h"
 #include "drt_material_kernels.h"
+#include "drt_owned.h"
 
 #include <algorithm>
 #include <cmath>
@@ -56,27 +57,54 @@ static int fail(int code, const char *fmt, ...)
         if (e_ != hipSuccess) return fail(-100 - (int)e_, "%s: %s", #expr, hipGetErrorString(e_));         \
     } while (0)
 
+/* the two memory policies of Owned (drt_owned.h), each with its count of live allocations */
+struct DeviceMem
+{
+    static std::atomic<uint64_t> &live() { static std::atomic<uint64_t> n{0}; return n; }
+    static hipError_t alloc(void **p, size_t bytes)
+    {
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) live() += 1;
+        return e;
+    }
+    static void free(void *p) { (void)hipFree(p); live() -= 1; }
+};
+struct PinnedMem
+{
+    static std::atomic<uint64_t> &live() { static std::atomic<uint64_t> n{0}; return n; }
+    static hipError_t alloc(void **p, size_t bytes)
+    {
+        const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+        if (e == hipSuccess) live() += 1;
+        return e;
+    }
+    static void free(void *p) { (void)hipHostFree(p); live() -= 1; }
+};
+template <typename T> using DevBuf = Owned<T, DeviceMem>;
+template <typename T> using PinnedBuf = Owned<T, PinnedMem>;
+
 struct drt_context
 {
     int         device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
+    Stream      own_stream; /* declared before every buffer and event: destroyed after all of them */
     drt_params  params{};
     DevScene    dsc{};
     DevCamera   dcam{};
     uint32_t    cmf_rw = 0, cmf_x = 0, cmf_y = 0, cmf_z = 0;
     double      interval = 0.0;
 
-    std::vector<void *> allocations; /* scene tables */
+    std::vector<DevBuf<unsigned char>> allocations; /* scene tables */
     std::vector<DevMaterial> host_mats;        /* what d.mats holds (drt_selftest_material derives its override tables from it) */
-    DevMaterial *d_mat_variants = nullptr;     /* those tables, made on the first drt_selftest_material call */
+    DevMaterial *d_mat_variants = nullptr;     /* (held by `allocations`) those tables, made on the first drt_selftest_material call */
     double *d_pixels = nullptr, *d_avgs = nullptr, *d_vars = nullptr; /* XYZ film mode: d_pixels is [n_pix][XYZ_FILM_WORDS], the others stay null */
+    DevBuf<double> own_pixels, own_avgs, own_vars; /* own_film: what the three point at; after drt_bind_film they point at the caller's memory, never freed here */
     bool    xyz_mode = false;
     bool    own_film = false;
-    uint64_t *d_records = nullptr, *d_headers = nullptr;
+    DevBuf<uint64_t> d_records, d_headers;
     uint32_t  light0_em_spd = 0;      /* emission SPD row of the first light (0 when there is none) */
-    double   *d_tail_stage = nullptr; /* [n_pix * batch][tail_count]: per-sample results of the shade kernel's tail pass */
-    double   *d_tail_resume = nullptr; /* [n_pix * batch][tail_count]: the throughput the trace kernel carried for a path it handed over at a vertex
+    DevBuf<double> d_tail_stage; /* [n_pix * batch][tail_count]: per-sample results of the shade kernel's tail pass */
+    DevBuf<double> d_tail_resume; /* [n_pix * batch][tail_count]: the throughput the trace kernel carried for a path it handed over at a vertex
                                           k >= 1 (TraceParams::tail_resume); only where trace_tail && !tail_all_staged && tail_resume */
     uint32_t  batch_spp = 1;
     uint32_t  vertex_words = 0, vertex_shift = 0, block_words = 0; /* a vertex record, its log2, a pool block (four vertices), in 8-byte words */
@@ -87,16 +115,16 @@ struct drt_context
     std::vector<Batch> inflight;         /* kernel pairs enqueued since the last synchronisation (redone if the pool ran out) */
     uint64_t  next_seq = 1;
     uint64_t  redone_batches = 0, pool_peak = 0;
-    int32_t  *d_hits = nullptr;
+    DevBuf<int32_t> d_hits;
     uint64_t  hits_capacity = 0; /* in paths */
     uint32_t  hits_samples = 0;
-    unsigned long long *d_counters = nullptr; /* DRT_COUNTER_WORDS words: layout at DRT_PAIR_COUNTERS above */
-    PrimaryHit *d_primary = nullptr;          /* BVH pipeline: closest hit of every path's camera ray (drt_bvh_kernels.h) */
-    uint64_t   *d_queue = nullptr;            /* BVH pipeline: ids of the paths that go on after their first hit */
+    DevBuf<unsigned long long> d_counters; /* DRT_COUNTER_WORDS words: layout at DRT_PAIR_COUNTERS above */
+    DevBuf<PrimaryHit> d_primary;         /* BVH pipeline: closest hit of every path's camera ray (drt_bvh_kernels.h) */
+    DevBuf<uint64_t> d_queue;         /* BVH pipeline: ids of the paths that go on after their first hit */
     bool        bvh_pipeline = false;
     int         primary_grid_cap = 0, bounce_grid_cap = 0;
-    double   *d_xyz = nullptr;
-    uint8_t  *d_bgra = nullptr;
+    DevBuf<double> d_xyz;
+    DevBuf<uint8_t> d_bgra;
     bool      trace_tail = false;     /* the trace kernel carries the tail wavelengths of the paths it can (drt_trace_kernel<true, true>): those of plastic
                                          and mirror vertices only, and those without a vertex */
     bool      tail_all_staged = false; /* ... and in this scene that is every path: the shade kernel's tail pass has nothing to replay */
@@ -104,7 +132,7 @@ struct drt_context
     bool      dark_skip = true;        /* the shade kernel's instantiation that passes over samples worth 0 in pixels nothing has reached yet */
     bool      no_fixed_lists = false;  /* DRT_NO_FIXED_LISTS, read when the context is created: the shade kernel's fixed-list bodies are not taken */
     bool      simple_bdsfs = false;    /* no material lists anything but bp_diffuse_bdsf, bp_glossy_bdsf, mirror_bdsf: the shade kernel without the Fresnel code */
-    const double *d_spd_tail = nullptr; /* [n_spd][tail_count]: the SPD table's tail columns */
+    const double *d_spd_tail = nullptr; /* (held by `allocations`) [n_spd][tail_count]: the SPD table's tail columns */
 
     bool   scene_in_lds = true, spds_in_lds = true, use_bvh = false;
     size_t trace_lds = 0, shade_lds = 0;
@@ -113,7 +141,7 @@ struct drt_context
     uint32_t shade_sets = 1, tail_first = 0, tail_count = 0;
     uint64_t n_pix = 0;
 
-    std::vector<hipEvent_t> ev; /* triples: trace start, trace end / shade start, shade end */
+    std::vector<Event> ev; /* triples: trace start, trace end / shade start, shade end */
     std::vector<double> ev_paths; /* per triple: the paths of that kernel pair */
     size_t ev_used = 0;
     double trace_ms = 0.0, shade_ms = 0.0;
@@ -122,51 +150,51 @@ struct drt_context
 
     /* adaptive sampling (drt_render_adaptive): the film has had samples from drt_render / drt_write_film, or an adaptive render */
     bool film_used = false, adaptive_done = false;
-    uint32_t *d_counts = nullptr;          /* [n_pix] samples per pixel */
-    uint32_t *d_alist[2] = {nullptr, nullptr}; /* the round's active pixels and the next round's (ping-pong) */
-    unsigned long long *d_keep = nullptr;  /* [ceil(n_pix / 64)] keep bits */
-    uint32_t *d_bkeep = nullptr;           /* [blocks of drt_converge_kernel + 1]: per block, then the active count */
-    uint32_t *d_ainfo = nullptr;           /* [1 + ADOPT_WORDS]: pixels at max_spp so far, then the report of the adoption kernels */
-    uint32_t *h_active = nullptr;          /* pinned host words the active count, then d_ainfo, are copied to: the copies stay asynchronous,
+    DevBuf<uint32_t> d_counts;        /* [n_pix] samples per pixel */
+    DevBuf<uint32_t> d_alist[2]; /* the round's active pixels and the next round's (ping-pong) */
+    DevBuf<unsigned long long> d_keep; /* [ceil(n_pix / 64)] keep bits */
+    DevBuf<uint32_t> d_bkeep;         /* [blocks of drt_converge_kernel + 1]: per block, then the active count */
+    DevBuf<uint32_t> d_ainfo;         /* [1 + ADOPT_WORDS]: pixels at max_spp so far, then the report of the adoption kernels */
+    PinnedBuf<uint32_t> h_active;         /* pinned host words the active count, then d_ainfo, are copied to: the copies stay asynchronous,
                                               so the devices of a group are all given their round before any is waited for */
     /* n: the count all active pixels hold (same); !same: they hold different counts, each max_spp - count a multiple of step */
     /* the denoiser (drt_denoise_film): its result and work buffers, kept from call to call, and the film they were made from */
     uint64_t film_gen = 0;                 /* counts what changes the film: kernel pairs, drt_write_film, drt_reset_film, drt_bind_film */
     uint64_t dn_gen = 0;                   /* film_gen at the last drt_denoise_film */
     bool     dn_valid = false;
-    double  *d_dn_mean = nullptr, *d_dn_var = nullptr, *d_dn_guide = nullptr, *d_dn_weights = nullptr, *d_dn_wsum = nullptr;
-    uint32_t *d_dn_unusable = nullptr;
+    DevBuf<double> d_dn_mean, d_dn_var, d_dn_guide, d_dn_weights, d_dn_wsum;
+    DevBuf<uint32_t> d_dn_unusable;
     uint32_t dn_window_cap = 0;            /* window entries per pixel d_dn_weights holds */
     /* first-hit features (drt_render_features): what the colour table is made from, the result, and the film it took its counts from */
     std::vector<drt_material> ft_mats;     /* the scene's materials and SPD rows as the caller gave them */
     std::vector<double> ft_spds;
     uint32_t ft_n_spd = 0, ft_S = 0;
-    double  *d_ft_mean = nullptr, *d_ft_m2 = nullptr, *d_ft_colour = nullptr;
-    int32_t *d_ft_ids = nullptr;
-    uint32_t *d_ft_counts = nullptr, *d_ft_report = nullptr;
-    unsigned long long *d_ft_info = nullptr;
-    hipEvent_t ft_ev[2] = {nullptr, nullptr};
+    DevBuf<double> d_ft_mean, d_ft_m2, d_ft_colour;
+    DevBuf<int32_t> d_ft_ids;
+    DevBuf<uint32_t> d_ft_counts, d_ft_report;
+    DevBuf<unsigned long long> d_ft_info;
+    Event    ft_ev[2];
     bool     ft_valid = false, ft_from_film = false;
     uint64_t ft_gen = 0;                   /* film_gen at the last drt_render_features */
     /* ID mattes (drt_render_mattes): the result and the film it took its counts from; d_ft_counts and d_ft_report are shared */
-    int32_t *d_mt_ids = nullptr, *d_mt_list = nullptr;
-    uint32_t *d_mt_counts = nullptr, *d_mt_tail = nullptr;
-    double  *d_mt_cover = nullptr;
-    unsigned long long *d_mt_info = nullptr;
-    hipEvent_t mt_ev[2] = {nullptr, nullptr};
+    DevBuf<int32_t> d_mt_ids, d_mt_list;
+    DevBuf<uint32_t> d_mt_counts, d_mt_tail;
+    DevBuf<double> d_mt_cover;
+    DevBuf<unsigned long long> d_mt_info;
+    Event    mt_ev[2];
     bool     mt_valid = false, mt_from_film = false;
     uint64_t mt_gen = 0;                   /* film_gen at the last drt_render_mattes */
     /* ray queries (drt_cast_rays, drt_test_visibility, drt_cast_pixels): the staging buffers of host mode, made when first needed */
     uint64_t ray_chunk = RAY_STAGING_RAYS; /* rays per host-mode launch (DRT_RAY_CHUNK: a test knob, read here at creation) */
     int      ray_grid_cap = 1;
-    double  *d_ray_a = nullptr, *d_ray_b = nullptr;
-    drt_ray_hit *d_ray_hits = nullptr;
-    uint8_t *d_ray_visible = nullptr;
-    uint32_t *d_ray_xy = nullptr, *d_ray_samples = nullptr;
+    DevBuf<double> d_ray_a, d_ray_b;
+    DevBuf<drt_ray_hit> d_ray_hits;
+    DevBuf<uint8_t> d_ray_visible;
+    DevBuf<uint32_t> d_ray_xy, d_ray_samples;
     /* ray films (drt_bind_rays): the table the ray-mode kernels read, and the device copies of the tile's rows that host mode made */
     bool        rays_bound = false;
     DevRayTable rt{};
-    double     *d_rt_origins = nullptr, *d_rt_dirs = nullptr, *d_rt_weights = nullptr;
+    DevBuf<double> d_rt_origins, d_rt_dirs, d_rt_weights;
     /* scene updates (drt_update_surfaces, drt_set_camera; drt_update_kernels.h): the caller's raw surfaces on both sides, the host's
      * tree, and what the three kernels read. Everything on the device is made at the first update. */
     std::vector<drt_surface> h_surfaces;   /* as drt_create got them, with every host-mode update written in */
@@ -176,14 +204,14 @@ struct drt_context
     double    cam_reach = 0.0, extent = 0.0; /* the camera's share of the extent; the extent in use (hierarchy contexts) */
     bool      extent_known = true;
     bool      upd_ready = false;
-    drt_surface *d_raw = nullptr, *h_stage = nullptr; /* the device copy; the pinned buffer host mode goes through */
-    int32_t  *d_light_slot = nullptr;
-    double   *d_boxes = nullptr;
-    uint32_t *d_leaf_parent = nullptr;
-    uint2    *d_levels = nullptr;
+    DevBuf<drt_surface> d_raw; PinnedBuf<drt_surface> h_stage; /* the device copy; the pinned buffer host mode goes through */
+    DevBuf<int32_t> d_light_slot;
+    DevBuf<double> d_boxes;
+    DevBuf<uint32_t> d_leaf_parent;
+    DevBuf<uint2> d_levels;
     std::vector<uint32_t> level_first;     /* level l, deepest first, is d_levels[level_first[l] .. level_first[l + 1]) */
-    unsigned long long *d_upd_status = nullptr;
-    hipEvent_t upd_ev[3] = {nullptr, nullptr, nullptr}; /* the last update's kernels: start, end; the pinned buffer is free again */
+    DevBuf<unsigned long long> d_upd_status;
+    Event     upd_ev[3]; /* the last update's kernels: start, end; the pinned buffer is free again */
     bool      upd_timed = false, stage_busy = false;
     bool      upd_check = false, upd_violation = false; /* device mode: the status word is to be read at the next synchronisation; what it said */
     uint32_t  updates = 0, refits = 0;
@@ -193,11 +221,11 @@ struct drt_context
     bool      boxes_valid = false;         /* d_boxes and the extent word hold the current surfaces' (an update has run the derive kernel) */
     bool      hb_ready = false, hb_timed = false;
     bool      hb_mirror_pending = false;   /* h_nodes, h_order and level_first are the tree before the last device build: hb_ev[2] says when hb_mirror holds the new ones */
-    uint32_t *d_hb_tree_surf = nullptr, *d_hb_pos[2] = {nullptr, nullptr}, *d_hb_table = nullptr, *d_hb_order = nullptr;
-    uint64_t *d_hb_keys[2] = {nullptr, nullptr};
-    uint4    *d_hb_items[2] = {nullptr, nullptr};
-    unsigned char *d_hb_status = nullptr, *hb_mirror = nullptr; /* BUILD_STATUS_BYTES; pinned: nodes, leaf order, level counts */
-    hipEvent_t hb_ev[3] = {nullptr, nullptr, nullptr}; /* the last build's kernels: start, end; its copy into hb_mirror */
+    DevBuf<uint32_t> d_hb_tree_surf, d_hb_pos[2], d_hb_table, d_hb_order;
+    DevBuf<uint64_t> d_hb_keys[2];
+    DevBuf<uint4> d_hb_items[2];
+    DevBuf<unsigned char> d_hb_status; PinnedBuf<unsigned char> hb_mirror; /* BUILD_STATUS_BYTES; pinned: nodes, leaf order, level counts */
+    Event     hb_ev[3]; /* the last build's kernels: start, end; its copy into hb_mirror */
     uint32_t  hb_builds = 0, hb_built_by = 0, hb_depth = 0;
     double    hb_ms = 0.0;
     /* material updates (drt_update_spectra, drt_update_materials; drt_material_kernels.h): how every row of d.spds is made (recorded by
@@ -207,11 +235,11 @@ struct drt_context
     bool      mu_ready = false;
     bool      spd_stale = false;           /* a device-mode update has gone into d_spd_raw only: ft_spds and host_mats' refract_i0 / refract_i1 are read back before the host uses them */
     bool      variants_stale = false;      /* d_mat_variants was made from host_mats as they were before an update */
-    SpdRowDesc *d_spd_desc = nullptr;
-    double   *d_spd_raw = nullptr, *d_spd_in = nullptr, *h_spd_stage = nullptr; /* [ft_n_spd][S] each: raw rows; host mode's rows on the device; pinned */
-    int32_t  *d_mat_refract = nullptr;     /* [n_mat] */
-    DevMaterial *h_mat_stage = nullptr;    /* pinned, [n_mat] */
-    hipEvent_t mu_ev[2] = {nullptr, nullptr}; /* the copies out of h_spd_stage and h_mat_stage are done */
+    DevBuf<SpdRowDesc> d_spd_desc;
+    DevBuf<double> d_spd_raw, d_spd_in; PinnedBuf<double> h_spd_stage; /* [ft_n_spd][S] each: raw rows; host mode's rows on the device; pinned */
+    DevBuf<int32_t> d_mat_refract;    /* [n_mat] */
+    PinnedBuf<DevMaterial> h_mat_stage;    /* pinned, [n_mat] */
+    Event     mu_ev[2]; /* the copies out of h_spd_stage and h_mat_stage are done */
     bool      spd_stage_busy = false, mat_stage_busy = false;
     uint32_t  spectra_updates = 0, material_updates = 0;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
@@ -229,10 +257,10 @@ static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat
 template <typename T>
 static int upload(drt_context *ctx, const std::vector<T> &host, const T **dev)
 {
-    void *p = nullptr;
-    size_t bytes = std::max<size_t>(host.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc(&p, bytes));
-    ctx->allocations.push_back(p);
+    DevBuf<unsigned char> buf;
+    HIP_TRY(buf.need(std::max<size_t>(host.size(), 1) * sizeof(T)));
+    unsigned char *p = buf;
+    ctx->allocations.push_back(std::move(buf));
     if (!host.empty()) HIP_TRY(hipMemcpy(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     *dev = (const T *)p;
     return 0;
@@ -950,7 +978,7 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     if (ctx->params.row_stride == 0) ctx->params.row_stride = 1;
     ctx->device = params->device;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
+    HIP_TRY(ctx->own_stream.create(hipStreamNonBlocking));
     ctx->stream = ctx->own_stream;
     const double reach = camera_reach(camera);
     int rc = build_device_scene(ctx, scene, reach);
@@ -988,17 +1016,20 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     /* scenes behind the hierarchy: camera rays walk it a wave at a time, the rest of each path runs from a queue (drt_bvh_kernels.h) */
     ctx->bvh_pipeline = !ctx->scene_in_lds;
 
-    HIP_TRY(hipMalloc((void **)&ctx->d_pixels, pixels_bytes(ctx)));
+    HIP_TRY(ctx->own_pixels.need(pixels_bytes(ctx) / 8));
     if (!ctx->xyz_mode)
     {
-        HIP_TRY(hipMalloc((void **)&ctx->d_avgs, (size_t)ctx->n_pix * S * 8));
-        HIP_TRY(hipMalloc((void **)&ctx->d_vars, (size_t)ctx->n_pix * S * 8));
+        HIP_TRY(ctx->own_avgs.need((size_t)ctx->n_pix * S));
+        HIP_TRY(ctx->own_vars.need((size_t)ctx->n_pix * S));
     }
+    ctx->d_pixels = ctx->own_pixels;
+    ctx->d_avgs = ctx->own_avgs;
+    ctx->d_vars = ctx->own_vars;
     ctx->own_film = true;
     HIP_TRY(hipMemsetAsync(ctx->d_pixels, 0, pixels_bytes(ctx), ctx->stream));
     if (ctx->d_avgs) HIP_TRY(hipMemsetAsync(ctx->d_avgs, 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
     if (ctx->d_vars) HIP_TRY(hipMemsetAsync(ctx->d_vars, 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
-    HIP_TRY(hipMalloc((void **)&ctx->d_counters, DRT_COUNTER_WORDS * sizeof(unsigned long long)));
+    HIP_TRY(ctx->d_counters.need(DRT_COUNTER_WORDS));
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
 
     /* persistent trace grid: as many workgroups as the chip keeps resident */
@@ -1085,12 +1116,12 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         ctx->n_pix = n_sample;
         ctx->pool_blocks = blocks_worst_case(ctx, n_sample);
         ctx->n_pix = npx;
-        HIP_TRY(hipMalloc((void **)&ctx->d_records, ctx->pool_blocks * block_bytes));
-        HIP_TRY(hipMalloc((void **)&ctx->d_headers, n_sample * REC_HEADER_WORDS * 8));
+        HIP_TRY(ctx->d_records.need(ctx->pool_blocks * ctx->block_words));
+        HIP_TRY(ctx->d_headers.need(n_sample * REC_HEADER_WORDS));
         if (ctx->bvh_pipeline)
         {
-            HIP_TRY(hipMalloc((void **)&ctx->d_primary, n_sample * sizeof(PrimaryHit)));
-            HIP_TRY(hipMalloc((void **)&ctx->d_queue, n_sample * sizeof(uint64_t)));
+            HIP_TRY(ctx->d_primary.need(n_sample));
+            HIP_TRY(ctx->d_queue.need(n_sample));
         }
         const drt_params keep = ctx->params;
         const uint64_t keep_pix = ctx->n_pix;
@@ -1113,10 +1144,10 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
             HIP_TRY(hipMemcpy(cnt, ctx->d_counters + DRT_PAIR_COUNTERS, sizeof(cnt), hipMemcpyDeviceToHost));
             if (cnt[0] > 0) ctx->dark_skip = (double)cnt[2] / (double)cnt[0] < 3.0;
         }
-        (void)hipFree(ctx->d_records); ctx->d_records = nullptr;
-        (void)hipFree(ctx->d_headers); ctx->d_headers = nullptr;
-        (void)hipFree(ctx->d_primary); ctx->d_primary = nullptr;
-        (void)hipFree(ctx->d_queue); ctx->d_queue = nullptr;
+        ctx->d_records.reset();
+        ctx->d_headers.reset();
+        ctx->d_primary.reset();
+        ctx->d_queue.reset();
         HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream)); /* the sample does not count */
         ctx->ev_used = 0;
         ctx->ev_paths.clear();
@@ -1161,15 +1192,15 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     if (const char *e = getenv("DRT_POOL_BLOCKS")) /* test knob: a pool this small (never below one worst-case sample per pixel) */
         ctx->pool_blocks = std::max<uint64_t>(blocks_worst_case(ctx, npx), std::min<uint64_t>(ctx->pool_blocks, strtoull(e, nullptr, 0)));
     if (ctx->pool_blocks >= 0xFFFFFFF0ull) return fail(-3, "record pool of %llu blocks: block numbers are 32 bits", (unsigned long long)ctx->pool_blocks);
-    HIP_TRY(hipMalloc((void **)&ctx->d_records, ctx->pool_blocks * block_bytes));
-    HIP_TRY(hipMalloc((void **)&ctx->d_headers, (size_t)npx * batch * REC_HEADER_WORDS * 8));
+    HIP_TRY(ctx->d_records.need(ctx->pool_blocks * ctx->block_words));
+    HIP_TRY(ctx->d_headers.need((size_t)npx * batch * REC_HEADER_WORDS));
     if (ctx->bvh_pipeline)
     {
-        HIP_TRY(hipMalloc((void **)&ctx->d_primary, (size_t)npx * batch * sizeof(PrimaryHit)));
-        HIP_TRY(hipMalloc((void **)&ctx->d_queue, (size_t)npx * batch * sizeof(uint64_t)));
+        HIP_TRY(ctx->d_primary.need((size_t)npx * batch));
+        HIP_TRY(ctx->d_queue.need((size_t)npx * batch));
     }
-    if (ctx->tail_count) HIP_TRY(hipMalloc((void **)&ctx->d_tail_stage, (size_t)npx * batch * ctx->tail_count * 8));
-    if (ctx->tail_count && ctx->tail_resume) HIP_TRY(hipMalloc((void **)&ctx->d_tail_resume, (size_t)npx * batch * ctx->tail_count * 8));
+    if (ctx->tail_count) HIP_TRY(ctx->d_tail_stage.need((size_t)npx * batch * ctx->tail_count));
+    if (ctx->tail_count && ctx->tail_resume) HIP_TRY(ctx->d_tail_resume.need((size_t)npx * batch * ctx->tail_count));
     if (const char *e = getenv("DRT_DARK_SKIP")) ctx->dark_skip = atoi(e) != 0; /* A/B switch of the parity tests: same film either way */
     if (getenv("DRT_VERBOSE"))
         fprintf(stderr, "drt: %d CUs, trace %d blocks/CU (lds %zu), shade %d blocks/CU (lds %zu), batch %u, %.3f blocks/path measured (worst %u), pool %.2f GB\n",
@@ -1200,93 +1231,6 @@ extern "C" void drt_destroy(drt_context *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (void *p : ctx->allocations) (void)hipFree(p);
-    if (ctx->own_film)
-    {
-        (void)hipFree(ctx->d_pixels);
-        (void)hipFree(ctx->d_avgs);
-        (void)hipFree(ctx->d_vars);
-    }
-    (void)hipFree(ctx->d_records);
-    (void)hipFree(ctx->d_headers);
-    (void)hipFree(ctx->d_primary);
-    (void)hipFree(ctx->d_queue);
-    (void)hipFree(ctx->d_tail_stage);
-    (void)hipFree(ctx->d_tail_resume);
-    (void)hipFree(ctx->d_hits);
-    (void)hipFree(ctx->d_counters);
-    (void)hipFree(ctx->d_xyz);
-    (void)hipFree(ctx->d_bgra);
-    (void)hipFree(ctx->d_counts);
-    (void)hipFree(ctx->d_alist[0]);
-    (void)hipFree(ctx->d_alist[1]);
-    (void)hipFree(ctx->d_keep);
-    (void)hipFree(ctx->d_bkeep);
-    (void)hipFree(ctx->d_dn_mean);
-    (void)hipFree(ctx->d_dn_var);
-    (void)hipFree(ctx->d_dn_guide);
-    (void)hipFree(ctx->d_dn_weights);
-    (void)hipFree(ctx->d_dn_wsum);
-    (void)hipFree(ctx->d_dn_unusable);
-    (void)hipFree(ctx->d_ft_mean);
-    (void)hipFree(ctx->d_ft_m2);
-    (void)hipFree(ctx->d_ft_colour);
-    (void)hipFree(ctx->d_ft_ids);
-    (void)hipFree(ctx->d_ft_counts);
-    (void)hipFree(ctx->d_ft_report);
-    (void)hipFree(ctx->d_ft_info);
-    for (hipEvent_t e : ctx->ft_ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipFree(ctx->d_mt_ids);
-    (void)hipFree(ctx->d_mt_list);
-    (void)hipFree(ctx->d_mt_counts);
-    (void)hipFree(ctx->d_mt_tail);
-    (void)hipFree(ctx->d_mt_cover);
-    (void)hipFree(ctx->d_mt_info);
-    (void)hipFree(ctx->d_ray_a);
-    (void)hipFree(ctx->d_ray_b);
-    (void)hipFree(ctx->d_ray_hits);
-    (void)hipFree(ctx->d_ray_visible);
-    (void)hipFree(ctx->d_ray_xy);
-    (void)hipFree(ctx->d_ray_samples);
-    (void)hipFree(ctx->d_rt_origins);
-    (void)hipFree(ctx->d_rt_dirs);
-    (void)hipFree(ctx->d_rt_weights);
-    (void)hipFree(ctx->d_raw);
-    (void)hipHostFree(ctx->h_stage);
-    (void)hipFree(ctx->d_light_slot);
-    (void)hipFree(ctx->d_boxes);
-    (void)hipFree(ctx->d_leaf_parent);
-    (void)hipFree(ctx->d_levels);
-    (void)hipFree(ctx->d_upd_status);
-    (void)hipFree(ctx->d_hb_tree_surf);
-    (void)hipFree(ctx->d_hb_table);
-    (void)hipFree(ctx->d_hb_order);
-    (void)hipFree(ctx->d_hb_status);
-    for (int k = 0; k < 2; k += 1)
-    {
-        (void)hipFree(ctx->d_hb_pos[k]);
-        (void)hipFree(ctx->d_hb_keys[k]);
-        (void)hipFree(ctx->d_hb_items[k]);
-    }
-    (void)hipHostFree(ctx->hb_mirror);
-    (void)hipFree(ctx->d_spd_desc);
-    (void)hipFree(ctx->d_spd_raw);
-    (void)hipFree(ctx->d_spd_in);
-    (void)hipFree(ctx->d_mat_refract);
-    (void)hipHostFree(ctx->h_spd_stage);
-    (void)hipHostFree(ctx->h_mat_stage);
-    for (hipEvent_t e : ctx->mu_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->hb_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->upd_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ctx->mt_ev)
-        if (e) (void)hipEventDestroy(e);
-    (void)hipHostFree(ctx->h_active);
-    for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
 
@@ -1295,13 +1239,10 @@ extern "C" int drt_bind_film(drt_context *ctx, void *d_pixels, void *d_avgs, voi
     if (!ctx || !d_pixels || (!ctx->xyz_mode && (!d_avgs || !d_vars))) return fail(-1, "null argument");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->own_film)
-    {
-        (void)hipFree(ctx->d_pixels);
-        (void)hipFree(ctx->d_avgs);
-        (void)hipFree(ctx->d_vars);
-        ctx->own_film = false;
-    }
+    ctx->own_pixels.reset();
+    ctx->own_avgs.reset();
+    ctx->own_vars.reset();
+    ctx->own_film = false;
     ctx->film_gen += 1;
     ctx->d_pixels = (double *)d_pixels;
     ctx->d_avgs = (double *)d_avgs;
@@ -1322,12 +1263,8 @@ extern "C" int drt_synchronize(drt_context *ctx);
 
 static int next_events(drt_context *ctx, hipEvent_t out[3])
 {
-    while (ctx->ev.size() < ctx->ev_used + 3)
-    {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        ctx->ev.push_back(e);
-    }
+    if (ctx->ev.size() < ctx->ev_used + 3) ctx->ev.resize(ctx->ev_used + 3);
+    for (int k = 0; k < 3; k += 1) HIP_TRY(ctx->ev[ctx->ev_used + k].need());
     for (int k = 0; k < 3; k += 1) out[k] = ctx->ev[ctx->ev_used + k];
     ctx->ev_used += 3;
     return 0;
@@ -1606,7 +1543,7 @@ static int redo_batches(drt_context *ctx, uint64_t last_good_seq)
  * film -- read and written once per pair, 3328 bytes a pixel -- is touched that much less often. Samples per pair: five eighths of
  * what the pool's size would allow, because it is sized from the tile's AVERAGE path and the rows of an image that hold its objects
  * run above that (a block that runs out anyway is rendered again: redo_batches). done[k], if asked for, is recorded behind block k. */
-static int enqueue_blocks(drt_context *ctx, uint32_t first_sample, uint32_t num_samples, uint32_t n_blocks, std::vector<hipEvent_t> *done)
+static int enqueue_blocks(drt_context *ctx, uint32_t first_sample, uint32_t num_samples, uint32_t n_blocks, std::vector<Event> *done)
 {
     const uint32_t H = ctx->params.tile_h, W = ctx->params.tile_w;
     const uint32_t per = (H + n_blocks - 1) / n_blocks;
@@ -1625,10 +1562,9 @@ static int enqueue_blocks(drt_context *ctx, uint32_t first_sample, uint32_t num_
         }
         if (done)
         {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            done->push_back(e);
-            HIP_TRY(hipEventRecord(e, ctx->stream));
+            done->emplace_back();
+            HIP_TRY(done->back().need(hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(done->back(), ctx->stream));
         }
     }
     return 0;
@@ -1655,9 +1591,7 @@ static int render_impl(drt_context *ctx, uint32_t first_sample, uint32_t num_sam
         if (need > ctx->hits_capacity)
         {
             HIP_TRY(hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->d_hits);
-            ctx->d_hits = nullptr;
-            HIP_TRY(hipMalloc((void **)&ctx->d_hits, std::max<uint64_t>(need, 1) * p.max_depth * sizeof(int32_t)));
+            HIP_TRY(ctx->d_hits.remake(std::max<uint64_t>(need, 1) * p.max_depth));
             ctx->hits_capacity = need;
         }
         ctx->hits_samples = num_samples;
@@ -1798,7 +1732,7 @@ extern "C" int drt_read_xyz(drt_context *ctx, double *xyz)
      * a conversion enqueued before it would read the incomplete film */
     int rc = drt_synchronize(ctx);
     if (rc) return rc;
-    if (!ctx->d_xyz) HIP_TRY(hipMalloc((void **)&ctx->d_xyz, (size_t)ctx->n_pix * 3 * 8));
+    HIP_TRY(ctx->d_xyz.need((size_t)ctx->n_pix * 3));
     uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
     if (ctx->xyz_mode)
         hipLaunchKernelGGL(drt_xyz_finish_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_y, ctx->interval,
@@ -1820,7 +1754,7 @@ static int film_to_bgra(drt_context *ctx, int which)
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = drt_synchronize(ctx); /* the complete film first (see drt_read_xyz) */
     if (rc) return rc;
-    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
     const double *film = which == 0 ? ctx->d_pixels : which == 1 ? ctx->d_avgs : ctx->d_vars;
     uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
     hipLaunchKernelGGL(drt_film_bgra_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y,
@@ -1941,42 +1875,32 @@ static int enqueue_converge(drt_context *ctx)
     return 0;
 }
 
-static void adaptive_free(drt_context *ctx)
-{
-    (void)hipFree(ctx->d_counts);
-    (void)hipFree(ctx->d_alist[0]);
-    (void)hipFree(ctx->d_alist[1]);
-    (void)hipFree(ctx->d_keep);
-    (void)hipFree(ctx->d_bkeep);
-    (void)hipFree(ctx->d_ainfo);
-    (void)hipHostFree(ctx->h_active);
-    ctx->d_counts = ctx->d_alist[0] = ctx->d_alist[1] = ctx->d_bkeep = ctx->d_ainfo = ctx->h_active = nullptr;
-    ctx->d_keep = nullptr;
-}
-
 static int adaptive_alloc(drt_context *ctx)
 {
-    adaptive_free(ctx);
     const uint64_t n_pix = ctx->n_pix;
-    HIP_TRY(hipMalloc((void **)&ctx->d_counts, n_pix * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_alist[0], n_pix * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_alist[1], n_pix * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_keep, (n_pix + 63) / 64 * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_bkeep, ((n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK + 1) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_ainfo, (1 + ADOPT_WORDS) * sizeof(uint32_t)));
-    HIP_TRY(hipHostMalloc((void **)&ctx->h_active, (2 + ADOPT_WORDS) * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(ctx->d_counts.need(n_pix));
+    HIP_TRY(ctx->d_alist[0].need(n_pix));
+    HIP_TRY(ctx->d_alist[1].need(n_pix));
+    HIP_TRY(ctx->d_keep.need((n_pix + 63) / 64));
+    HIP_TRY(ctx->d_bkeep.need((n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK + 1));
+    HIP_TRY(ctx->d_ainfo.need(1 + ADOPT_WORDS));
+    HIP_TRY(ctx->h_active.need(2 + ADOPT_WORDS));
     return 0;
 }
 
 /* the buffers of an adaptive render; the count of pixels at max_spp starts from zero */
 static int adaptive_buffers(drt_context *ctx)
 {
-    if (!ctx->d_counts || !ctx->d_alist[0] || !ctx->d_alist[1] || !ctx->d_keep || !ctx->d_bkeep || !ctx->d_ainfo || !ctx->h_active)
+    if (!ctx->h_active) /* the last of the set, which is whole or absent */
     {
         /* all or none: a call that failed half way leaves no buffer behind that a later call would take for the whole set */
         const int rc = adaptive_alloc(ctx);
-        if (rc) adaptive_free(ctx);
-        if (rc) return rc;
+        if (rc)
+        {
+            for (DevBuf<uint32_t> *b : {&ctx->d_counts, &ctx->d_alist[0], &ctx->d_alist[1], &ctx->d_bkeep, &ctx->d_ainfo}) b->reset();
+            ctx->d_keep.reset();
+            return rc;
+        }
     }
     HIP_TRY(hipMemsetAsync(ctx->d_ainfo, 0, sizeof(uint32_t), ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->d_ainfo + 1 + ADOPT_BAD, 0xFF, sizeof(uint32_t), ctx->stream));
@@ -2292,7 +2216,7 @@ extern "C" int drt_render_tile(const drt_scene *scene, const drt_camera *camera,
         const uint32_t per = (ctx->params.tile_h + n_blocks - 1) / n_blocks; /* rows per block */
         const bool blocks_ok = params->spp != 0 && n_blocks > 1 && !(params->flags & DRT_FLAG_RECORD_HITS) && ctx->params.tile_h >= 16 * n_blocks &&
                                (uint64_t)ctx->params.tile_w * ctx->params.tile_h >= (1u << 18);
-        std::vector<hipEvent_t> block_done;
+        std::vector<Event> block_done;
         if (!blocks_ok)
         {
             if ((rc = drt_render(ctx, params->first_sample, params->spp))) break;
@@ -2333,7 +2257,7 @@ extern "C" int drt_render_tile(const drt_scene *scene, const drt_camera *camera,
                     if (host[f] && dev[f] && hipMemcpy(host[f] + r0 * W * words[f], dev[f] + r0 * W * words[f], rows * W * words[f] * 8, hipMemcpyDeviceToHost) != hipSuccess) fetched = false;
             }
         }
-        for (hipEvent_t e : block_done) (void)hipEventDestroy(e);
+        block_done.clear();
         if ((rc = drt_synchronize(ctx))) break; /* timings, and what a pool that ran out left undone */
         if (!fetched && (rc = drt_read_film(ctx, dst_pixels, dst_avgs, dst_vars))) break;
         if (stats && (rc = drt_get_stats(ctx, stats))) break;
@@ -2468,9 +2392,10 @@ extern "C" int drt_group_reset_film(drt_group *g)
 }
 
 /* Of n devices, device k holds rows k, k + n, ... of the tile, contiguously in the buffer `buf` of its context: rows of row_bytes
- * bytes of a whole-tile host buffer <-> every device's own, one strided copy per device. A null host buffer is left out. */
-template <typename T>
-static int group_move_rows(drt_group *g, void *host, size_t row_bytes, T *drt_context::*buf, bool to_device)
+ * bytes of a whole-tile host buffer <-> every device's own, one strided copy per device. A null host buffer is left out.
+ * B: a DevBuf<T>, or the double * of a film member. */
+template <typename B>
+static int group_move_rows(drt_group *g, void *host, size_t row_bytes, B drt_context::*buf, bool to_device)
 {
     if (!host) return 0;
     const size_t n = g->ctx.size();
@@ -2480,17 +2405,18 @@ static int group_move_rows(drt_group *g, void *host, size_t row_bytes, T *drt_co
         if (!c) continue;
         HIP_TRY(hipSetDevice(c->device));
         char *h = (char *)host + k * row_bytes;
+        void *dev = c->*buf;
         if (to_device)
-            HIP_TRY(hipMemcpy2D(c->*buf, row_bytes, h, n * row_bytes, row_bytes, g->rows[k], hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy2D(dev, row_bytes, h, n * row_bytes, row_bytes, g->rows[k], hipMemcpyHostToDevice));
         else
-            HIP_TRY(hipMemcpy2D(h, n * row_bytes, c->*buf, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy2D(h, n * row_bytes, dev, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
     }
     return 0;
 }
-template <typename T>
-static int group_gather_rows(drt_group *g, void *host, size_t row_bytes, T *drt_context::*buf) { return group_move_rows(g, host, row_bytes, buf, false); }
-template <typename T>
-static int group_scatter_rows(drt_group *g, const void *host, size_t row_bytes, T *drt_context::*buf)
+template <typename B>
+static int group_gather_rows(drt_group *g, void *host, size_t row_bytes, B drt_context::*buf) { return group_move_rows(g, host, row_bytes, buf, false); }
+template <typename B>
+static int group_scatter_rows(drt_group *g, const void *host, size_t row_bytes, B drt_context::*buf)
 {
     return group_move_rows(g, const_cast<void *>(host), row_bytes, buf, true);
 }
@@ -2721,27 +2647,21 @@ static int denoise_enqueue(hipStream_t stream, const DenoiseParams &dp, const dr
     const uint64_t n_pix = (uint64_t)dp.tile_w * dp.tile_h;
     const size_t halo = denoise_halo_bytes(d);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(drt_denoise_weight_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)halo));
-    hipEvent_t ev[2];
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    hipError_t e = hipMemsetAsync(dp.unusable, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], stream);
-    if (e == hipSuccess)
-    {
-        hipLaunchKernelGGL(drt_denoise_guide_kernel, dim3((uint32_t)((n_pix + DENOISE_BLOCK - 1) / DENOISE_BLOCK)), dim3(DENOISE_BLOCK), 0, stream, dp);
-        hipLaunchKernelGGL(drt_denoise_weight_kernel, dim3((dp.tile_w + DENOISE_TILE - 1) / DENOISE_TILE, (dp.tile_h + DENOISE_TILE - 1) / DENOISE_TILE),
-                           dim3(DENOISE_TILE, DENOISE_TILE), halo, stream, dp);
-        hipLaunchKernelGGL(drt_denoise_apply_kernel, dim3((dp.tile_w + DENOISE_APPLY_SIDE - 1) / DENOISE_APPLY_SIDE, (dp.tile_h + DENOISE_APPLY_SIDE - 1) / DENOISE_APPLY_SIDE),
-                           dim3(DENOISE_BLOCK), 0, stream, dp);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    Event ev[2];
+    HIP_TRY(ev[0].need());
+    HIP_TRY(ev[1].need());
+    HIP_TRY(hipMemsetAsync(dp.unusable, 0, sizeof(uint32_t), stream));
+    HIP_TRY(hipEventRecord(ev[0], stream));
+    hipLaunchKernelGGL(drt_denoise_guide_kernel, dim3((uint32_t)((n_pix + DENOISE_BLOCK - 1) / DENOISE_BLOCK)), dim3(DENOISE_BLOCK), 0, stream, dp);
+    hipLaunchKernelGGL(drt_denoise_weight_kernel, dim3((dp.tile_w + DENOISE_TILE - 1) / DENOISE_TILE, (dp.tile_h + DENOISE_TILE - 1) / DENOISE_TILE),
+                       dim3(DENOISE_TILE, DENOISE_TILE), halo, stream, dp);
+    hipLaunchKernelGGL(drt_denoise_apply_kernel, dim3((dp.tile_w + DENOISE_APPLY_SIDE - 1) / DENOISE_APPLY_SIDE, (dp.tile_h + DENOISE_APPLY_SIDE - 1) / DENOISE_APPLY_SIDE),
+                       dim3(DENOISE_BLOCK), 0, stream, dp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[1], stream));
+    HIP_TRY(hipStreamSynchronize(stream));
     float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    (void)hipEventDestroy(ev[0]);
-    (void)hipEventDestroy(ev[1]);
-    if (e != hipSuccess) return fail(-100 - (int)e, "denoise kernels: %s", hipGetErrorString(e));
+    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
     if (kernel_ms) *kernel_ms = (double)ms;
     return 0;
 }
@@ -2773,17 +2693,15 @@ extern "C" int drt_denoise_film(drt_context *ctx, drt_denoise *d)
     const size_t n_pix = ctx->n_pix;
     DenoiseParams dp;
     denoise_fill(&dp, d, S, ctx->params.tile_w, ctx->params.tile_h, ctx->interval);
-    if (!ctx->d_dn_mean) HIP_TRY(hipMalloc((void **)&ctx->d_dn_mean, n_pix * S * 8));
-    if (!ctx->d_dn_var) HIP_TRY(hipMalloc((void **)&ctx->d_dn_var, n_pix * S * 8));
-    if (!ctx->d_dn_guide) HIP_TRY(hipMalloc((void **)&ctx->d_dn_guide, n_pix * DENOISE_GUIDE_WORDS * 8));
-    if (!ctx->d_dn_wsum) HIP_TRY(hipMalloc((void **)&ctx->d_dn_wsum, n_pix * 8));
-    if (!ctx->d_dn_unusable) HIP_TRY(hipMalloc((void **)&ctx->d_dn_unusable, sizeof(uint32_t)));
+    HIP_TRY(ctx->d_dn_mean.need(n_pix * S));
+    HIP_TRY(ctx->d_dn_var.need(n_pix * S));
+    HIP_TRY(ctx->d_dn_guide.need(n_pix * DENOISE_GUIDE_WORDS));
+    HIP_TRY(ctx->d_dn_wsum.need(n_pix));
+    HIP_TRY(ctx->d_dn_unusable.need(1));
     if (ctx->dn_window_cap < dp.n_window)
     {
-        (void)hipFree(ctx->d_dn_weights);
-        ctx->d_dn_weights = nullptr;
         ctx->dn_window_cap = 0;
-        HIP_TRY(hipMalloc((void **)&ctx->d_dn_weights, n_pix * dp.n_window * 8));
+        HIP_TRY(ctx->d_dn_weights.remake(n_pix * dp.n_window));
         ctx->dn_window_cap = dp.n_window;
     }
     dp.rw = ctx->dsc.spds + (size_t)ctx->cmf_rw * S;
@@ -2831,7 +2749,7 @@ extern "C" int drt_read_denoised_bgra(drt_context *ctx, uint8_t *bgra)
     int rc = denoise_current(ctx);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
     /* the conversion drt_read_bgra(ctx, 1, ...) applies to the running mean, on the denoised mean */
     hipLaunchKernelGGL(drt_film_bgra_kernel, dim3((uint32_t)((ctx->n_pix + 255) / 256)), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x,
                        ctx->cmf_y, ctx->cmf_z, ctx->interval, ctx->n_pix, (const double *)ctx->d_dn_mean, 1, ctx->d_bgra);
@@ -2848,41 +2766,36 @@ static int denoise_host_film(const double *const d_rows[4], uint32_t S, uint32_t
     const size_t n_pix = (size_t)tile_w * tile_h;
     DenoiseParams dp;
     denoise_fill(&dp, d, S, tile_w, tile_h, interval);
-    const size_t sizes[9] = {n_pix * (S + 1) * 8, n_pix * S * 8, n_pix * S * 8, n_pix * S * 8, n_pix * S * 8, n_pix * DENOISE_GUIDE_WORDS * 8,
-                             n_pix * dp.n_window * 8, n_pix * 8, sizeof(uint32_t)};
-    void *buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int rc = 0;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 9 && e == hipSuccess; k += 1) e = hipMalloc(&buf[k], sizes[k]);
-    const void *src[3] = {pixels, avgs, vars};
-    for (int k = 0; k < 3 && e == hipSuccess; k += 1) e = hipMemcpy(buf[k], src[k], sizes[k], hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(-100 - (int)e, "denoise: film buffers on the device: %s", hipGetErrorString(e));
-    if (!rc)
-    {
-        dp.rw = d_rows[0];
-        dp.cx = d_rows[1];
-        dp.cy = d_rows[2];
-        dp.cz = d_rows[3];
-        dp.pixels = (const double *)buf[0];
-        dp.avgs = (const double *)buf[1];
-        dp.vars = (const double *)buf[2];
-        dp.mean = (double *)buf[3];
-        dp.var = (double *)buf[4];
-        dp.guide = (double *)buf[5];
-        dp.weights = (double *)buf[6];
-        dp.wsum = (double *)buf[7];
-        dp.unusable = (uint32_t *)buf[8];
-        rc = denoise_enqueue(nullptr, dp, d, &d->kernel_ms);
-    }
-    if (!rc)
-    {
-        if (mean) e = hipMemcpy(mean, buf[3], sizes[3], hipMemcpyDeviceToHost);
-        if (var && e == hipSuccess) e = hipMemcpy(var, buf[4], sizes[4], hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(&d->unusable, buf[8], sizeof(uint32_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = fail(-100 - (int)e, "denoise: reading the result: %s", hipGetErrorString(e));
-    }
-    for (int k = 0; k < 9; k += 1) (void)hipFree(buf[k]);
-    return rc;
+    DevBuf<double> film[3], out[2], guide, weights, wsum; /* pixels, avgs, vars; mean, var */
+    DevBuf<uint32_t> unusable;
+    const size_t words[3] = {n_pix * (S + 1), n_pix * S, n_pix * S};
+    for (int k = 0; k < 3; k += 1) HIP_TRY(film[k].need(words[k]));
+    for (int k = 0; k < 2; k += 1) HIP_TRY(out[k].need(n_pix * S));
+    HIP_TRY(guide.need(n_pix * DENOISE_GUIDE_WORDS));
+    HIP_TRY(weights.need(n_pix * dp.n_window));
+    HIP_TRY(wsum.need(n_pix));
+    HIP_TRY(unusable.need(1));
+    const double *src[3] = {pixels, avgs, vars};
+    for (int k = 0; k < 3; k += 1) HIP_TRY(hipMemcpy(film[k], src[k], words[k] * 8, hipMemcpyHostToDevice));
+    dp.rw = d_rows[0];
+    dp.cx = d_rows[1];
+    dp.cy = d_rows[2];
+    dp.cz = d_rows[3];
+    dp.pixels = film[0];
+    dp.avgs = film[1];
+    dp.vars = film[2];
+    dp.mean = out[0];
+    dp.var = out[1];
+    dp.guide = guide;
+    dp.weights = weights;
+    dp.wsum = wsum;
+    dp.unusable = unusable;
+    const int rc = denoise_enqueue(nullptr, dp, d, &d->kernel_ms);
+    if (rc) return rc;
+    if (mean) HIP_TRY(hipMemcpy(mean, out[0], n_pix * S * 8, hipMemcpyDeviceToHost));
+    if (var) HIP_TRY(hipMemcpy(var, out[1], n_pix * S * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&d->unusable, unusable, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int drt_denoise_buffers(const drt_scene *scene, const drt_params *params, drt_denoise *d, const double *pixels, const double *avgs,
@@ -2899,16 +2812,12 @@ extern "C" int drt_denoise_buffers(const drt_scene *scene, const drt_params *par
     for (int k = 0; k < 4; k += 1)
         if (rows[k] >= scene->num_spds || !scene->spds) return fail(-1, "denoise: colour-matching row %u of %u SPDs", rows[k], scene->num_spds);
     HIP_TRY(hipSetDevice(params->device));
-    double *d_cmf = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_cmf, (size_t)4 * S * 8));
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 4 && e == hipSuccess; k += 1)
-        e = hipMemcpy(d_cmf + (size_t)k * S, scene->spds + (size_t)rows[k] * S, (size_t)S * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = fail(-100 - (int)e, "denoise: colour-matching rows on the device: %s", hipGetErrorString(e));
+    DevBuf<double> d_cmf;
+    HIP_TRY(d_cmf.need((size_t)4 * S));
+    for (int k = 0; k < 4; k += 1)
+        HIP_TRY(hipMemcpy(d_cmf + (size_t)k * S, scene->spds + (size_t)rows[k] * S, (size_t)S * 8, hipMemcpyHostToDevice));
     const double *d_rows[4] = {d_cmf, d_cmf + S, d_cmf + 2 * (size_t)S, d_cmf + 3 * (size_t)S};
-    if (!rc) rc = denoise_host_film(d_rows, S, params->tile_w, params->tile_h, scene->wavelength_interval, d, pixels, avgs, vars, mean, var);
-    (void)hipFree(d_cmf);
-    return rc;
+    return denoise_host_film(d_rows, S, params->tile_w, params->tile_h, scene->wavelength_interval, d, pixels, avgs, vars, mean, var);
 }
 
 /* Row-cyclic devices hold no neighbours of their own rows: the group gathers the film (drt_group_read_film) and its first device
@@ -2996,8 +2905,8 @@ static int first_hit_check(const char *who, uint32_t flags, uint32_t first_sampl
 static int film_counts(drt_context *ctx, const char *who, uint32_t first_sample)
 {
     const size_t n_pix = (size_t)ctx->n_pix;
-    if (!ctx->d_ft_counts) HIP_TRY(hipMalloc((void **)&ctx->d_ft_counts, n_pix * sizeof(uint32_t)));
-    if (!ctx->d_ft_report) HIP_TRY(hipMalloc((void **)&ctx->d_ft_report, 2 * sizeof(uint32_t)));
+    HIP_TRY(ctx->d_ft_counts.need(n_pix));
+    HIP_TRY(ctx->d_ft_report.need(2));
     uint32_t report[2] = {0xFFFFFFFFu, 0u};
     HIP_TRY(hipMemcpyAsync(ctx->d_ft_report, report, sizeof(report), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(drt_feature_counts_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
@@ -3063,13 +2972,12 @@ static int features_prepare(drt_context *ctx, const drt_features *f)
     int rc = first_hit_prepare(ctx, "features", f->n_samples, &ctx->ft_valid);
     if (rc) return rc;
     const size_t n_pix = (size_t)ctx->n_pix;
-    if (!ctx->d_ft_mean) HIP_TRY(hipMalloc((void **)&ctx->d_ft_mean, n_pix * DRT_FEATURE_CHANNELS * 8));
-    if (!ctx->d_ft_m2) HIP_TRY(hipMalloc((void **)&ctx->d_ft_m2, n_pix * DRT_FEATURE_CHANNELS * 8));
-    if (!ctx->d_ft_ids) HIP_TRY(hipMalloc((void **)&ctx->d_ft_ids, n_pix * sizeof(int32_t)));
-    if (!ctx->d_ft_info) HIP_TRY(hipMalloc((void **)&ctx->d_ft_info, FEATURE_INFO_WORDS * sizeof(unsigned long long)));
-    if (!ctx->d_ft_colour) HIP_TRY(hipMalloc((void **)&ctx->d_ft_colour, std::max<size_t>(ctx->ft_mats.size(), 1) * 3 * 8));
-    for (hipEvent_t &e : ctx->ft_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ctx->d_ft_mean.need(n_pix * DRT_FEATURE_CHANNELS));
+    HIP_TRY(ctx->d_ft_m2.need(n_pix * DRT_FEATURE_CHANNELS));
+    HIP_TRY(ctx->d_ft_ids.need(n_pix));
+    HIP_TRY(ctx->d_ft_info.need(FEATURE_INFO_WORDS));
+    HIP_TRY(ctx->d_ft_colour.need(std::max<size_t>(ctx->ft_mats.size(), 1) * 3));
+    for (Event &e : ctx->ft_ev) HIP_TRY(e.need());
     return f->n_samples == 0 ? film_counts(ctx, "features", f->first_sample) : 0;
 }
 
@@ -3153,7 +3061,7 @@ extern "C" int drt_read_feature_bgra(drt_context *ctx, int which, double lo, dou
     int rc = features_current(ctx);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
     hipLaunchKernelGGL(drt_feature_bgra_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        (const double *)ctx->d_ft_mean, ctx->n_pix, which, lo, hi, ctx->d_bgra);
     HIP_TRY(hipGetLastError());
@@ -3195,12 +3103,11 @@ static int mattes_prepare(drt_context *ctx, const drt_mattes *m)
     int rc = first_hit_prepare(ctx, "mattes", m->n_samples, &ctx->mt_valid);
     if (rc) return rc;
     const size_t n_pix = (size_t)ctx->n_pix;
-    if (!ctx->d_mt_ids) HIP_TRY(hipMalloc((void **)&ctx->d_mt_ids, n_pix * MATTE_WORDS * sizeof(int32_t)));
-    if (!ctx->d_mt_counts) HIP_TRY(hipMalloc((void **)&ctx->d_mt_counts, n_pix * MATTE_WORDS * sizeof(uint32_t)));
-    if (!ctx->d_mt_tail) HIP_TRY(hipMalloc((void **)&ctx->d_mt_tail, n_pix * 4 * sizeof(uint32_t)));
-    if (!ctx->d_mt_info) HIP_TRY(hipMalloc((void **)&ctx->d_mt_info, MATTE_INFO_WORDS * sizeof(unsigned long long)));
-    for (hipEvent_t &e : ctx->mt_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ctx->d_mt_ids.need(n_pix * MATTE_WORDS));
+    HIP_TRY(ctx->d_mt_counts.need(n_pix * MATTE_WORDS));
+    HIP_TRY(ctx->d_mt_tail.need(n_pix * 4));
+    HIP_TRY(ctx->d_mt_info.need(MATTE_INFO_WORDS));
+    for (Event &e : ctx->mt_ev) HIP_TRY(e.need());
     return m->n_samples == 0 ? film_counts(ctx, "mattes", m->first_sample) : 0;
 }
 
@@ -3301,8 +3208,8 @@ extern "C" int drt_read_matte(drt_context *ctx, int layer, const int32_t *id_lis
             return fail(-1, "mattes: id_list[%u] = %d: the scene has %u %s", k, id_list[k], limit, layer == DRT_MATTE_SURFACE ? "surfaces" : "materials");
     if ((rc = mattes_current(ctx))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_mt_list) HIP_TRY(hipMalloc((void **)&ctx->d_mt_list, MATTE_MAX_IDS * sizeof(int32_t)));
-    if (!ctx->d_mt_cover) HIP_TRY(hipMalloc((void **)&ctx->d_mt_cover, (size_t)ctx->n_pix * sizeof(double)));
+    HIP_TRY(ctx->d_mt_list.need(MATTE_MAX_IDS));
+    HIP_TRY(ctx->d_mt_cover.need((size_t)ctx->n_pix));
     HIP_TRY(hipMemcpy(ctx->d_mt_list, id_list, n_ids * sizeof(int32_t), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(drt_matte_select_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        (const int32_t *)ctx->d_mt_ids, (const uint32_t *)ctx->d_mt_counts, (const uint32_t *)ctx->d_mt_tail, ctx->n_pix, layer,
@@ -3320,7 +3227,7 @@ extern "C" int drt_read_matte_bgra(drt_context *ctx, int layer, uint8_t *bgra)
     if (rc) return rc;
     if ((rc = mattes_current(ctx))) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_bgra) HIP_TRY(hipMalloc((void **)&ctx->d_bgra, (size_t)ctx->n_pix * 4));
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
     hipLaunchKernelGGL(drt_matte_bgra_kernel, pixel_grid(ctx), dim3(FEATURE_BLOCK), 0, ctx->stream,
                        (const int32_t *)ctx->d_mt_ids, (const uint32_t *)ctx->d_mt_counts, (const uint32_t *)ctx->d_mt_tail, ctx->n_pix, layer, ctx->d_bgra);
     HIP_TRY(hipGetLastError());
@@ -3445,13 +3352,6 @@ static int rays_launch(drt_context *ctx, int kind, const RayArgs &d, uint64_t n)
     return 0;
 }
 
-template <typename T>
-static int ray_staging(T **p, size_t count)
-{
-    if (!*p) HIP_TRY(hipMalloc((void **)p, count * sizeof(T)));
-    return 0;
-}
-
 /* Host mode: the list in chunks of ctx->ray_chunk rays through the staging buffers, all on the context's stream and in its order, so
  * a buffer is reused only after the kernel and the copies of the chunk before. Enqueues only; rays_host_finish waits. */
 static int rays_host_enqueue(drt_context *ctx, int kind, const RayArgs &h, uint64_t n)
@@ -3462,34 +3362,36 @@ static int rays_host_enqueue(drt_context *ctx, int kind, const RayArgs &h, uint6
     RayArgs d;
     if (kind != RAYS_PIXELS)
     {
-        if ((rc = ray_staging(&ctx->d_ray_a, cap * 3)) || (rc = ray_staging(&ctx->d_ray_b, cap * 3))) return rc;
+        HIP_TRY(ctx->d_ray_a.need(cap * 3));
+        HIP_TRY(ctx->d_ray_b.need(cap * 3));
         d.a = ctx->d_ray_a;
         d.b = ctx->d_ray_b;
     }
     else
     {
-        if ((rc = ray_staging(&ctx->d_ray_xy, cap * 2)) || (rc = ray_staging(&ctx->d_ray_samples, cap))) return rc;
+        HIP_TRY(ctx->d_ray_xy.need(cap * 2));
+        HIP_TRY(ctx->d_ray_samples.need(cap));
         d.xy = ctx->d_ray_xy;
         d.samples = ctx->d_ray_samples;
         if (h.out_a)
         {
-            if ((rc = ray_staging(&ctx->d_ray_a, cap * 3))) return rc;
+            HIP_TRY(ctx->d_ray_a.need(cap * 3));
             d.out_a = ctx->d_ray_a;
         }
         if (h.out_b)
         {
-            if ((rc = ray_staging(&ctx->d_ray_b, cap * 3))) return rc;
+            HIP_TRY(ctx->d_ray_b.need(cap * 3));
             d.out_b = ctx->d_ray_b;
         }
     }
     if (kind == RAYS_VISIBLE)
     {
-        if ((rc = ray_staging(&ctx->d_ray_visible, cap))) return rc;
+        HIP_TRY(ctx->d_ray_visible.need(cap));
         d.visible = ctx->d_ray_visible;
     }
     else
     {
-        if ((rc = ray_staging(&ctx->d_ray_hits, cap))) return rc;
+        HIP_TRY(ctx->d_ray_hits.need(cap));
         d.hits = ctx->d_ray_hits;
     }
     hipStream_t st = ctx->stream;
@@ -3661,19 +3563,9 @@ static int bind_rays_check(const drt_context *ctx, const drt_ray_table *t, const
 struct PendingRays
 {
     DevRayTable rt{};
-    double     *d_new[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> d_new[3]; /* origins, dirs, weights: dropped with the binding unless it is put in force */
     bool        bound = false;
 };
-
-static void bind_rays_drop(drt_context *ctx, PendingRays &pr)
-{
-    (void)hipSetDevice(ctx->device);
-    for (double *&d : pr.d_new)
-    {
-        (void)hipFree(d);
-        d = nullptr;
-    }
-}
 
 static int bind_rays_prepare(drt_context *ctx, const drt_ray_table *t, PendingRays &pr, const char *name)
 {
@@ -3699,24 +3591,19 @@ static int bind_rays_prepare(drt_context *ctx, const drt_ray_table *t, PendingRa
         const size_t per = a < 2 ? 3 : 1;
         const size_t count = (size_t)entries * per;
         double *rows = (double *)malloc(std::max<size_t>(count, 1) * sizeof(double));
-        if (!rows)
-        {
-            bind_rays_drop(ctx, pr);
-            return fail(-3, "%s: out of host memory for %llu table entries", name, (unsigned long long)entries);
-        }
+        if (!rows) return fail(-3, "%s: out of host memory for %llu table entries", name, (unsigned long long)entries);
         for (uint64_t l = 0; l < t->n_layers; l += 1)
             for (uint32_t j = 0; j < p.tile_h; j += 1)
             {
                 const uint64_t from = ((l * p.height + (uint64_t)p.y0 + (uint64_t)j * p.row_stride) * p.width + p.x0) * per;
                 memcpy(rows + (l * n_tile + (uint64_t)j * p.tile_w) * per, src[a] + from, (size_t)p.tile_w * per * sizeof(double));
             }
-        hipError_t e = hipMalloc((void **)&pr.d_new[a], std::max<size_t>(count, 1) * sizeof(double));
+        hipError_t e = pr.d_new[a].need(count);
         if (e == hipSuccess && count) e = hipMemcpy(pr.d_new[a], rows, count * sizeof(double), hipMemcpyHostToDevice);
         free(rows);
         if (e != hipSuccess)
         {
             (void)hipGetLastError();
-            bind_rays_drop(ctx, pr);
             return fail(-100 - (int)e, "%s: %s", name, hipGetErrorString(e));
         }
     }
@@ -3731,11 +3618,9 @@ static int bind_rays_prepare(drt_context *ctx, const drt_ray_table *t, PendingRa
 static void bind_rays_commit(drt_context *ctx, PendingRays &pr)
 {
     (void)hipSetDevice(ctx->device);
-    (void)hipFree(ctx->d_rt_origins);
-    (void)hipFree(ctx->d_rt_dirs);
-    (void)hipFree(ctx->d_rt_weights);
-    ctx->d_rt_origins = pr.d_new[0]; ctx->d_rt_dirs = pr.d_new[1]; ctx->d_rt_weights = pr.d_new[2];
-    pr.d_new[0] = pr.d_new[1] = pr.d_new[2] = nullptr;
+    ctx->d_rt_origins = std::move(pr.d_new[0]);
+    ctx->d_rt_dirs = std::move(pr.d_new[1]);
+    ctx->d_rt_weights = std::move(pr.d_new[2]);
     ctx->rt = pr.rt;
     ctx->rays_bound = pr.bound;
 }
@@ -3764,14 +3649,7 @@ extern "C" int drt_group_bind_rays(drt_group *g, const drt_ray_table *t)
     const size_t n = g->ctx.size();
     for (size_t k = 0; k < n && !rc; k += 1)
         if (g->ctx[k]) rc = bind_rays_prepare(g->ctx[k], t, pending[k], "drt_group_bind_rays");
-    if (rc)
-    {
-        const std::string keep = g_last_error;
-        for (size_t k = 0; k < n; k += 1)
-            if (g->ctx[k]) bind_rays_drop(g->ctx[k], pending[k]);
-        g_last_error = keep;
-        return rc;
-    }
+    if (rc) return rc; /* the copies made so far go with `pending` */
     for (size_t k = 0; k < n; k += 1)
         if (g->ctx[k]) bind_rays_commit(g->ctx[k], pending[k]);
     return 0;
@@ -3848,8 +3726,8 @@ static int update_upload_maps(drt_context *ctx)
     TreeMaps m;
     tree_maps(ctx->h_nodes, ctx->h_order.size(), &m);
     const size_t n_leaf = std::max<size_t>(ctx->h_order.size(), 1);
-    if (!ctx->d_leaf_parent) HIP_TRY(hipMalloc((void **)&ctx->d_leaf_parent, n_leaf * sizeof(uint32_t)));
-    if (!ctx->d_levels) HIP_TRY(hipMalloc((void **)&ctx->d_levels, std::max<size_t>(ctx->h_nodes.size(), 1) * sizeof(uint2)));
+    HIP_TRY(ctx->d_leaf_parent.need(n_leaf));
+    HIP_TRY(ctx->d_levels.need(std::max<size_t>(ctx->h_nodes.size(), 1)));
     HIP_TRY(hipMemcpy(ctx->d_leaf_parent, m.leaf_parent.data(), n_leaf * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!m.entries.empty()) HIP_TRY(hipMemcpy(ctx->d_levels, m.entries.data(), m.entries.size() * sizeof(uint2), hipMemcpyHostToDevice));
     ctx->level_first = m.level_first;
@@ -3861,13 +3739,13 @@ static int update_prepare(drt_context *ctx)
 {
     if (ctx->upd_ready) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    const size_t n = ctx->h_surfaces.size(), bytes = std::max<size_t>(n, 1) * sizeof(drt_surface);
+    const size_t n = ctx->h_surfaces.size();
     if (!ctx->d_raw)
     {
-        HIP_TRY(hipMalloc((void **)&ctx->d_raw, bytes));
+        HIP_TRY(ctx->d_raw.need(n));
         if (n) HIP_TRY(hipMemcpy(ctx->d_raw, ctx->h_surfaces.data(), n * sizeof(drt_surface), hipMemcpyHostToDevice));
     }
-    if (!ctx->h_stage) HIP_TRY(hipHostMalloc((void **)&ctx->h_stage, bytes, hipHostMallocDefault));
+    HIP_TRY(ctx->h_stage.need(n));
     if (!ctx->d_light_slot)
     {
         /* the light list is the emissive surfaces in surface order (build_device_scene); types and materials do not change */
@@ -3875,15 +3753,14 @@ static int update_prepare(drt_context *ctx)
         int32_t l = 0;
         for (size_t i = 0; i < n; i += 1)
             if (ctx->ft_mats[ctx->h_surfaces[i].material].is_emissive) slot[i] = l++;
-        HIP_TRY(hipMalloc((void **)&ctx->d_light_slot, slot.size() * sizeof(int32_t)));
+        HIP_TRY(ctx->d_light_slot.need(slot.size()));
         HIP_TRY(hipMemcpy(ctx->d_light_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    if (!ctx->d_upd_status) HIP_TRY(hipMalloc((void **)&ctx->d_upd_status, UPD_STATUS_WORDS * sizeof(unsigned long long)));
-    for (hipEvent_t &e : ctx->upd_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ctx->d_upd_status.need(UPD_STATUS_WORDS));
+    for (Event &e : ctx->upd_ev) HIP_TRY(e.need());
     if (ctx->use_bvh)
     {
-        if (!ctx->d_boxes) HIP_TRY(hipMalloc((void **)&ctx->d_boxes, std::max<size_t>(n, 1) * 6 * sizeof(double)));
+        HIP_TRY(ctx->d_boxes.need(std::max<size_t>(n, 1) * 6));
         int rc = update_upload_maps(ctx);
         if (rc) return rc;
     }
@@ -3900,7 +3777,7 @@ static int update_enqueue_derive(drt_context *ctx)
     const uint32_t n = ctx->dsc.n_surf;
     HIP_TRY(hipMemsetAsync(ctx->d_upd_status, 0, UPD_STATUS_WORDS * sizeof(unsigned long long), ctx->stream));
     UpdateTables t;
-    t.raw = (const double *)ctx->d_raw;
+    t.raw = (const double *)ctx->d_raw.get();
     t.surf = const_cast<double *>(ctx->dsc.surf);
     t.lights = const_cast<double *>(ctx->dsc.lights);
     t.light_slot = ctx->d_light_slot;
@@ -3915,7 +3792,7 @@ static int update_enqueue_derive(drt_context *ctx)
 static LeafTables update_leaf_tables(drt_context *ctx)
 {
     LeafTables lt;
-    lt.raw = (const double *)ctx->d_raw;
+    lt.raw = (const double *)ctx->d_raw.get();
     lt.boxes = ctx->d_boxes;
     lt.leaf_parent = ctx->d_leaf_parent;
     lt.leaf = const_cast<BvhLeafPrim *>(ctx->dsc.bvh_leaf);
@@ -4042,7 +3919,7 @@ static int update_stage(drt_context *ctx, const drt_surface *surfaces, uint32_t 
 static int update_commit(drt_context *ctx, uint32_t first, uint32_t count, PendingUpdate *pu)
 {
     HIP_TRY(hipSetDevice(ctx->device));
-    std::copy(ctx->h_stage, ctx->h_stage + count, ctx->h_surfaces.begin() + first);
+    std::copy(ctx->h_stage.get(), ctx->h_stage + count, ctx->h_surfaces.begin() + first);
     HIP_TRY(hipMemcpyAsync(ctx->d_raw + first, ctx->h_stage, (size_t)count * sizeof(drt_surface), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->upd_ev[2], ctx->stream));
     ctx->stage_busy = true;
@@ -4214,19 +4091,19 @@ static int material_prepare(drt_context *ctx)
     if (ctx->mu_ready) return 0;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t n_mat = ctx->ft_mats.size();
-    const size_t row_bytes = std::max<size_t>((size_t)ctx->ft_n_spd * ctx->ft_S, 1) * sizeof(double);
+    const size_t row_words = (size_t)ctx->ft_n_spd * ctx->ft_S;
     if (!ctx->d_spd_raw)
     {
         /* the raw copy starts as the mirror, so the mirror must be the device's: this is the first update, and it is */
-        HIP_TRY(hipMalloc((void **)&ctx->d_spd_raw, row_bytes));
+        HIP_TRY(ctx->d_spd_raw.need(row_words));
         if (!ctx->ft_spds.empty()) HIP_TRY(hipMemcpy(ctx->d_spd_raw, ctx->ft_spds.data(), ctx->ft_spds.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (!ctx->d_spd_in) HIP_TRY(hipMalloc((void **)&ctx->d_spd_in, row_bytes));
-    if (!ctx->h_spd_stage) HIP_TRY(hipHostMalloc((void **)&ctx->h_spd_stage, row_bytes, hipHostMallocDefault));
-    if (!ctx->h_mat_stage) HIP_TRY(hipHostMalloc((void **)&ctx->h_mat_stage, std::max<size_t>(n_mat, 1) * sizeof(DevMaterial), hipHostMallocDefault));
+    HIP_TRY(ctx->d_spd_in.need(row_words));
+    HIP_TRY(ctx->h_spd_stage.need(row_words));
+    HIP_TRY(ctx->h_mat_stage.need(n_mat));
     if (!ctx->d_spd_desc)
     {
-        HIP_TRY(hipMalloc((void **)&ctx->d_spd_desc, std::max<size_t>(ctx->spd_desc.size(), 1) * sizeof(SpdRowDesc)));
+        HIP_TRY(ctx->d_spd_desc.need(ctx->spd_desc.size()));
         if (!ctx->spd_desc.empty())
             HIP_TRY(hipMemcpy(ctx->d_spd_desc, ctx->spd_desc.data(), ctx->spd_desc.size() * sizeof(SpdRowDesc), hipMemcpyHostToDevice));
     }
@@ -4235,11 +4112,10 @@ static int material_prepare(drt_context *ctx)
         /* a given refract spectrum is a scene row, and scene rows keep their numbers in the device table */
         std::vector<int32_t> refract(std::max<size_t>(n_mat, 1), -1);
         for (size_t m = 0; m < n_mat; m += 1) refract[m] = ctx->ft_mats[m].refract_spd >= 0 ? ctx->ft_mats[m].refract_spd : -1;
-        HIP_TRY(hipMalloc((void **)&ctx->d_mat_refract, refract.size() * sizeof(int32_t)));
+        HIP_TRY(ctx->d_mat_refract.need(refract.size()));
         HIP_TRY(hipMemcpy(ctx->d_mat_refract, refract.data(), refract.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    for (hipEvent_t &e : ctx->mu_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    for (Event &e : ctx->mu_ev) HIP_TRY(e.need());
     ctx->mu_ready = true;
     return 0;
 }
@@ -4331,7 +4207,7 @@ static int spectra_commit(drt_context *ctx, uint32_t first_row, uint32_t count)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t words = (size_t)count * ctx->ft_S;
-    std::copy(ctx->h_spd_stage, ctx->h_spd_stage + words, ctx->ft_spds.begin() + (size_t)first_row * ctx->ft_S);
+    std::copy(ctx->h_spd_stage.get(), ctx->h_spd_stage + words, ctx->ft_spds.begin() + (size_t)first_row * ctx->ft_S);
     material_refract_samples(ctx);
     HIP_TRY(hipMemcpyAsync(ctx->d_spd_in, ctx->h_spd_stage, words * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->mu_ev[0], ctx->stream));
@@ -4493,22 +4369,21 @@ static int hierarchy_prepare(drt_context *ctx)
         for (size_t i = 0; i < ctx->h_surfaces.size(); i += 1)
             if (ctx->h_surfaces[i].type == DRT_GEO_SPHERE || ctx->h_surfaces[i].type == DRT_GEO_PLANE) tree_surf.push_back((uint32_t)i);
         if (tree_surf.size() != m) return fail(-2, "drt_rebuild_hierarchy: %zu surfaces for a tree of %zu leaf slots", tree_surf.size(), m);
-        HIP_TRY(hipMalloc((void **)&ctx->d_hb_tree_surf, m1 * sizeof(uint32_t)));
+        HIP_TRY(ctx->d_hb_tree_surf.need(m1));
         if (m) HIP_TRY(hipMemcpy(ctx->d_hb_tree_surf, tree_surf.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     const size_t n_tiles = (m1 + SORT_TILE - 1) / SORT_TILE;
     for (int k = 0; k < 2; k += 1)
     {
-        if (!ctx->d_hb_keys[k]) HIP_TRY(hipMalloc((void **)&ctx->d_hb_keys[k], m1 * sizeof(uint64_t)));
-        if (!ctx->d_hb_pos[k]) HIP_TRY(hipMalloc((void **)&ctx->d_hb_pos[k], m1 * sizeof(uint32_t)));
-        if (!ctx->d_hb_items[k]) HIP_TRY(hipMalloc((void **)&ctx->d_hb_items[k], (m1 / 2 + 1) * sizeof(uint4))); /* an item covers two surfaces at least */
+        HIP_TRY(ctx->d_hb_keys[k].need(m1));
+        HIP_TRY(ctx->d_hb_pos[k].need(m1));
+        HIP_TRY(ctx->d_hb_items[k].need(m1 / 2 + 1)); /* an item covers two surfaces at least */
     }
-    if (!ctx->d_hb_table) HIP_TRY(hipMalloc((void **)&ctx->d_hb_table, (size_t)SORT_DIGITS * n_tiles * sizeof(uint32_t)));
-    if (!ctx->d_hb_order) HIP_TRY(hipMalloc((void **)&ctx->d_hb_order, m1 * sizeof(uint32_t)));
-    if (!ctx->d_hb_status) HIP_TRY(hipMalloc((void **)&ctx->d_hb_status, BUILD_STATUS_BYTES));
-    if (!ctx->hb_mirror) HIP_TRY(hipHostMalloc((void **)&ctx->hb_mirror, hierarchy_mirror_counts(ctx) + (BUILD_LEVELS + 1) * sizeof(uint32_t), hipHostMallocDefault));
-    for (hipEvent_t &e : ctx->hb_ev)
-        if (!e) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(ctx->d_hb_table.need((size_t)SORT_DIGITS * n_tiles));
+    HIP_TRY(ctx->d_hb_order.need(m1));
+    HIP_TRY(ctx->d_hb_status.need(BUILD_STATUS_BYTES));
+    HIP_TRY(ctx->hb_mirror.need(hierarchy_mirror_counts(ctx) + (BUILD_LEVELS + 1) * sizeof(uint32_t)));
+    for (Event &e : ctx->hb_ev) HIP_TRY(e.need());
     ctx->hb_ready = true;
     return 0;
 }
@@ -4608,7 +4483,7 @@ static int hierarchy_enqueue(drt_context *ctx)
         BuildTables bt;
         bt.boxes = ctx->d_boxes;
         bt.tree_surf = ctx->d_hb_tree_surf;
-        bt.bounds = (unsigned long long *)ctx->d_hb_status;
+        bt.bounds = (unsigned long long *)ctx->d_hb_status.get();
         bt.level_count = (uint32_t *)(ctx->d_hb_status + BUILD_BOUND_WORDS * 8);
         bt.m = m;
         if ((rc = hierarchy_enqueue_init(st, bt, ctx->d_hb_items[0]))) return rc;
@@ -4616,7 +4491,10 @@ static int hierarchy_enqueue(drt_context *ctx)
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(drt_build_keys_kernel, dim3(grid), dim3(BUILD_BLOCK), 0, st, bt, ctx->d_hb_keys[0], ctx->d_hb_pos[0]);
         HIP_TRY(hipGetLastError());
-        if ((rc = hierarchy_enqueue_sort(st, ctx->d_hb_keys, ctx->d_hb_pos, ctx->d_hb_table, m))) return rc;
+        uint64_t *const keys[2] = {ctx->d_hb_keys[0], ctx->d_hb_keys[1]};
+        uint32_t *const pos[2] = {ctx->d_hb_pos[0], ctx->d_hb_pos[1]};
+        uint4 *const items[2] = {ctx->d_hb_items[0], ctx->d_hb_items[1]};
+        if ((rc = hierarchy_enqueue_sort(st, keys, pos, ctx->d_hb_table, m))) return rc;
         TopologyTables tt;
         tt.keys = ctx->d_hb_keys[0];
         tt.pos = ctx->d_hb_pos[0];
@@ -4629,7 +4507,7 @@ static int hierarchy_enqueue(drt_context *ctx)
         tt.levels = ctx->d_levels;
         tt.level_count = bt.level_count;
         tt.m = m;
-        if ((rc = hierarchy_enqueue_topology(st, tt, ctx->d_hb_items))) return rc;
+        if ((rc = hierarchy_enqueue_topology(st, tt, items))) return rc;
         const LeafTables lt = update_leaf_tables(ctx);
         hipLaunchKernelGGL(drt_bvh_leaf_kernel, dim3((m + UPDATE_BLOCK - 1) / UPDATE_BLOCK), dim3(UPDATE_BLOCK), 0, st, lt, m, ctx->cam_reach);
         HIP_TRY(hipGetLastError());
@@ -4760,21 +4638,18 @@ extern "C" int drt_selftest_path_ids(int device, const uint64_t *bases, uint32_t
     }
     if (total > (1u << 20) || total * n_draws > (1u << 24)) return fail(-1, "drt_selftest_path_ids: too many ids");
     HIP_TRY(hipSetDevice(device));
-    uint64_t *d_bases = nullptr, *d_out = nullptr;
-    uint32_t *d_steps = nullptr;
+    DevBuf<uint64_t> d_bases, d_out;
+    DevBuf<uint32_t> d_steps;
     const size_t out_bytes = (size_t)total * n_draws * 4 * 8;
-    HIP_TRY(hipMalloc((void **)&d_bases, (size_t)n_draws * 8));
-    HIP_TRY(hipMalloc((void **)&d_steps, (size_t)n_steps * 4));
-    HIP_TRY(hipMalloc((void **)&d_out, out_bytes));
+    HIP_TRY(d_bases.need(n_draws));
+    HIP_TRY(d_steps.need(n_steps));
+    HIP_TRY(d_out.need(out_bytes / 8));
     HIP_TRY(hipMemcpy(d_bases, bases, (size_t)n_draws * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_steps, steps, (size_t)n_steps * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(drt_path_id_kernel, dim3(n_draws), dim3(64), 0, 0, d_bases, d_steps, n_steps, (uint32_t)total, n_samples, tile_w, d_out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
-    (void)hipFree(d_bases);
-    (void)hipFree(d_steps);
-    (void)hipFree(d_out);
     return 0;
 }
 
@@ -4782,16 +4657,16 @@ extern "C" int drt_selftest_arith(int device, int op, const double *a, const dou
 {
     g_last_error.clear();
     HIP_TRY(hipSetDevice(device));
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
+    DevBuf<double> da, db, dout;
     size_t out_n = (op == 2) ? 2 * n : n;
-    HIP_TRY(hipMalloc((void **)&da, std::max<uint64_t>(n, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&db, std::max<uint64_t>(n, 1) * 8));
-    HIP_TRY(hipMalloc((void **)&dout, std::max<size_t>(out_n, 1) * 8));
+    HIP_TRY(da.need(n));
+    HIP_TRY(db.need(n));
+    HIP_TRY(dout.need(out_n));
     HIP_TRY(hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    HIP_TRY(e0.need());
+    HIP_TRY(e1.need());
     HIP_TRY(hipEventRecord(e0, 0));
     hipLaunchKernelGGL(drt_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, da, db, dout, n);
     HIP_TRY(hipGetLastError());
@@ -4800,30 +4675,9 @@ extern "C" int drt_selftest_arith(int device, int op, const double *a, const dou
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
     if (getenv("DRT_VERBOSE")) fprintf(stderr, "drt_selftest_arith op %d n %llu: %.3f ms\n", op, (unsigned long long)n, ms);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     HIP_TRY(hipMemcpy(out, dout, out_n * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(da);
-    (void)hipFree(db);
-    (void)hipFree(dout);
     return 0;
 }
-
-/* device scratch of a selftest, freed however the call ends */
-struct SelftestScratch
-{
-    std::vector<void *> held;
-    ~SelftestScratch()
-    {
-        for (void *p : held) (void)hipFree(p);
-    }
-    template <typename T> hipError_t get(T **p, size_t n)
-    {
-        const hipError_t e = hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) held.push_back(*p);
-        return e;
-    }
-};
 
 #define BUILD_SELFTEST_MAX (1u << 24) /* elements: far above any test, far below where an index would wrap */
 #define BUILD_SELFTEST_GUARD 64u      /* elements in front of and behind every array the sort writes */
@@ -4842,19 +4696,20 @@ extern "C" int drt_selftest_build_sort(int device, const uint64_t *keys, uint32_
     const uint32_t pos_guard = 0xA5A5A5A5u;
     std::vector<uint64_t> hk(room, key_guard);
     std::vector<uint32_t> hp(room, pos_guard);
-    SelftestScratch scratch;
-    uint64_t *dk[2] = {nullptr, nullptr}, *d_keys[2];
-    uint32_t *dp[2] = {nullptr, nullptr}, *d_pos[2], *d_table = nullptr;
+    DevBuf<uint64_t> dk[2];
+    DevBuf<uint32_t> dp[2], d_table;
+    uint64_t *d_keys[2];
+    uint32_t *d_pos[2];
     for (int k = 0; k < 2; k += 1)
     {
-        HIP_TRY(scratch.get(&dk[k], room));
-        HIP_TRY(scratch.get(&dp[k], room));
+        HIP_TRY(dk[k].need(room));
+        HIP_TRY(dp[k].need(room));
         HIP_TRY(hipMemcpy(dk[k], hk.data(), room * sizeof(uint64_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dp[k], hp.data(), room * sizeof(uint32_t), hipMemcpyHostToDevice));
         d_keys[k] = dk[k] + G;
         d_pos[k] = dp[k] + G;
     }
-    HIP_TRY(scratch.get(&d_table, (size_t)SORT_DIGITS * ((m + SORT_TILE - 1) / SORT_TILE)));
+    HIP_TRY(d_table.need((size_t)SORT_DIGITS * ((m + SORT_TILE - 1) / SORT_TILE)));
     for (uint32_t k = 0; k < m; k += 1) hp[G + k] = k; /* the payload drt_build_keys_kernel writes: the position */
     HIP_TRY(hipMemcpy(d_keys[0], keys, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_pos[0], hp.data() + G, (size_t)m * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -4874,6 +4729,17 @@ extern "C" int drt_selftest_build_sort(int device, const uint64_t *keys, uint32_
     return 0;
 }
 
+extern "C" int drt_selftest_live_resources(uint64_t out[4])
+{
+    g_last_error.clear();
+    if (!out) return fail(-1, "drt_selftest_live_resources: null argument");
+    out[0] = DeviceMem::live();
+    out[1] = PinnedMem::live();
+    out[2] = Event::live();
+    out[3] = Stream::live();
+    return 0;
+}
+
 extern "C" int drt_selftest_build_topology(int device, const uint64_t *sorted_keys, uint32_t m, int32_t *child, int32_t *count, uint32_t *level_count,
                                            uint32_t *levels_out)
 {
@@ -4884,24 +4750,23 @@ extern "C" int drt_selftest_build_topology(int device, const uint64_t *sorted_ke
         if (sorted_keys[k] > BUILD_KEY_UNBOUNDED || (k > 0u && sorted_keys[k - 1] > sorted_keys[k]))
             return fail(-1, "drt_selftest_build_topology: key %u is out of order or has bit 63 set", k);
     HIP_TRY(hipSetDevice(device));
-    SelftestScratch scratch;
-    uint64_t *d_keys = nullptr;
-    uint32_t *d_same = nullptr, *d_type = nullptr, *d_leaf_parent = nullptr, *d_order = nullptr;
-    BvhNode *d_nodes = nullptr;
-    BvhLeafPrim *d_leaf = nullptr;
-    uint2 *d_levels = nullptr;
-    uint4 *d_items[2] = {nullptr, nullptr};
-    unsigned char *d_status = nullptr;
-    HIP_TRY(scratch.get(&d_keys, m));
-    HIP_TRY(scratch.get(&d_same, m));
-    HIP_TRY(scratch.get(&d_type, m));
-    HIP_TRY(scratch.get(&d_leaf_parent, m));
-    HIP_TRY(scratch.get(&d_order, m));
-    HIP_TRY(scratch.get(&d_nodes, (size_t)m - 1));
-    HIP_TRY(scratch.get(&d_leaf, m));
-    HIP_TRY(scratch.get(&d_levels, (size_t)m - 2));
-    for (int k = 0; k < 2; k += 1) HIP_TRY(scratch.get(&d_items[k], (size_t)m / 2 + 1)); /* as hierarchy_prepare sizes them */
-    HIP_TRY(scratch.get(&d_status, BUILD_STATUS_BYTES));
+    DevBuf<uint64_t> d_keys;
+    DevBuf<uint32_t> d_same, d_type, d_leaf_parent, d_order;
+    DevBuf<BvhNode> d_nodes;
+    DevBuf<BvhLeafPrim> d_leaf;
+    DevBuf<uint2> d_levels;
+    DevBuf<uint4> d_items[2];
+    DevBuf<unsigned char> d_status;
+    HIP_TRY(d_keys.need(m));
+    HIP_TRY(d_same.need(m));
+    HIP_TRY(d_type.need(m));
+    HIP_TRY(d_leaf_parent.need(m));
+    HIP_TRY(d_order.need(m));
+    HIP_TRY(d_nodes.need((size_t)m - 1));
+    HIP_TRY(d_leaf.need(m));
+    HIP_TRY(d_levels.need((size_t)m - 2));
+    for (int k = 0; k < 2; k += 1) HIP_TRY(d_items[k].need((size_t)m / 2 + 1)); /* as hierarchy_prepare sizes them */
+    HIP_TRY(d_status.need(BUILD_STATUS_BYTES));
     std::vector<uint32_t> same(m), type(m, (uint32_t)DRT_GEO_SPHERE);
     for (uint32_t k = 0; k < m; k += 1) same[k] = k; /* tree_surf and pos are identities: slot j holds surface j */
     HIP_TRY(hipMemcpy(d_keys, sorted_keys, (size_t)m * sizeof(uint64_t), hipMemcpyHostToDevice));
@@ -4912,7 +4777,7 @@ extern "C" int drt_selftest_build_topology(int device, const uint64_t *sorted_ke
     BuildTables bt;
     bt.boxes = nullptr; /* no bounds pass, no keys pass: nothing reads it */
     bt.tree_surf = d_same;
-    bt.bounds = (unsigned long long *)d_status;
+    bt.bounds = (unsigned long long *)d_status.get();
     bt.level_count = (uint32_t *)(d_status + BUILD_BOUND_WORDS * 8);
     bt.m = m;
     TopologyTables tt;
@@ -4928,7 +4793,8 @@ extern "C" int drt_selftest_build_topology(int device, const uint64_t *sorted_ke
     tt.level_count = bt.level_count;
     tt.m = m;
     int rc = hierarchy_enqueue_init(0, bt, d_items[0]);
-    if (rc || (rc = hierarchy_enqueue_topology(0, tt, d_items))) return rc;
+    uint4 *const items[2] = {d_items[0], d_items[1]};
+    if (rc || (rc = hierarchy_enqueue_topology(0, tt, items))) return rc;
     HIP_TRY(hipDeviceSynchronize());
     std::vector<BvhNode> nodes((size_t)m - 1);
     HIP_TRY(hipMemcpy(nodes.data(), d_nodes, nodes.size() * sizeof(BvhNode), hipMemcpyDeviceToHost));
@@ -4955,17 +4821,15 @@ extern "C" int drt_selftest_unit(int device, int func, const double *in, uint32_
         return fail(-1, "unit function %d needs %u doubles in and %u out per record", func, need_in[func], need_out[func]);
     if (n == 0) return 0;
     HIP_TRY(hipSetDevice(device));
-    double *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&din, n * in_stride * 8));
-    HIP_TRY(hipMalloc((void **)&dout, n * out_stride * 8));
+    DevBuf<double> din, dout;
+    HIP_TRY(din.need(n * in_stride));
+    HIP_TRY(dout.need(n * out_stride));
     HIP_TRY(hipMemcpy(din, in, n * in_stride * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dout, 0, n * out_stride * 8));
     hipLaunchKernelGGL(drt_unit_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, func, din, in_stride, dout, out_stride, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, n * out_stride * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
     return 0;
 }
 
@@ -5005,14 +4869,14 @@ static int material_variants(drt_context *ctx)
             else dm.dir_func = k - (uint32_t)DRT_NUM_BDSFS;
             v[(size_t)k * n_mat + m] = dm;
         }
-    void *p = ctx->d_mat_variants; /* after a material update: the same allocation, made again */
-    if (!p)
+    if (!ctx->d_mat_variants) /* after a material update: the same allocation, made again */
     {
-        HIP_TRY(hipMalloc(&p, v.size() * sizeof(DevMaterial)));
-        ctx->allocations.push_back(p);
+        DevBuf<unsigned char> buf;
+        HIP_TRY(buf.need(v.size() * sizeof(DevMaterial)));
+        ctx->d_mat_variants = (DevMaterial *)(unsigned char *)buf;
+        ctx->allocations.push_back(std::move(buf));
     }
-    HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
-    ctx->d_mat_variants = (DevMaterial *)p;
+    HIP_TRY(hipMemcpy(ctx->d_mat_variants, v.data(), v.size() * sizeof(DevMaterial), hipMemcpyHostToDevice));
     ctx->variants_stale = false;
     return 0;
 }
@@ -5058,9 +4922,9 @@ extern "C" int drt_selftest_material(drt_context *ctx, int func, const double *i
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = material_variants(ctx);
     if (rc) return rc;
-    double *din = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&din, n * in_stride * 8));
-    HIP_TRY(hipMalloc((void **)&dout, n * out_stride * 8));
+    DevBuf<double> din, dout;
+    HIP_TRY(din.need(n * in_stride));
+    HIP_TRY(dout.need(n * out_stride));
     HIP_TRY(hipMemcpy(din, in, n * in_stride * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(dout, 0, n * out_stride * 8));
     hipLaunchKernelGGL(drt_material_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, ctx->dsc, ctx->d_mat_variants, func, din, in_stride,
@@ -5068,7 +4932,5 @@ extern "C" int drt_selftest_material(drt_context *ctx, int func, const double *i
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout, n * out_stride * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(din);
-    (void)hipFree(dout);
     return 0;
 }

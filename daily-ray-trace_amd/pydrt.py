@@ -690,6 +690,8 @@ def hip_lib():
             u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
             L.drt_selftest_build_sort.argtypes = [C.c_int, u64p, C.c_uint32, u64p, u32p]
             L.drt_selftest_build_topology.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), u32p, u32p]
+        if hasattr(L, "drt_selftest_live_resources"):  # (as drt_selftest_path_ids above)
+            L.drt_selftest_live_resources.argtypes = [C.POINTER(C.c_uint64)]
         _hip = L
     return _hip
 
@@ -698,7 +700,7 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_render", "drt_synchronize", "drt_reset_film", "drt_film_device_ptrs", "drt_read_film", "drt_write_film",
                "drt_read_xyz", "drt_read_bgra", "drt_read_hit_indices", "drt_get_stats", "drt_batch_spp", "drt_render_tile", "drt_selftest_arith",
                "drt_selftest_unit", "drt_selftest_material", "drt_selftest_path_ids", "drt_bvh_stats",
-               "drt_selftest_build_sort", "drt_selftest_build_topology",
+               "drt_selftest_build_sort", "drt_selftest_build_topology", "drt_selftest_live_resources",
                "drt_group_create", "drt_group_destroy", "drt_group_size", "drt_group_render", "drt_group_synchronize",
                "drt_group_read_film", "drt_group_write_film", "drt_group_read_bgra", "drt_group_get_stats", "drt_render_tile_multi",
                "drt_render_adaptive", "drt_read_sample_counts", "drt_group_render_adaptive", "drt_group_read_sample_counts",
@@ -1333,6 +1335,13 @@ def selftest_build_topology(sorted_keys, device=0):
                                                  _ptr(level_count, C.c_uint32), _ptr(levels, C.c_uint32) if m > 2 else None),
            "drt_selftest_build_topology")
     return child, count, level_count, levels
+
+
+def selftest_live_resources():
+    """What the process holds through the library right now: (device allocations, pinned allocations, events, streams)."""
+    out = (C.c_uint64 * 4)()
+    _check(hip_lib().drt_selftest_live_resources(out), "drt_selftest_live_resources")
+    return tuple(int(v) for v in out)
 
 
 # ------------------------------------------------------------------------------------------------

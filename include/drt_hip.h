@@ -745,6 +745,11 @@ int drt_selftest_build_sort(int device, const uint64_t *keys, uint32_t m, uint64
  * (inner node, parent * 2 + child slot), the deepest level first, in any order within a level. Keys out of order are refused. */
 int drt_selftest_build_topology(int device, const uint64_t *sorted_keys, uint32_t m, int32_t *child, int32_t *count, uint32_t *level_count,
                                 uint32_t *levels_out);
+/* drt_selftest_live_resources: what this process holds through the library right now, over all contexts, groups and calls in flight:
+ * out[0] device allocations, out[1] pinned host allocations, out[2] HIP events, out[3] HIP streams. Each goes up when one is made and
+ * down when it is released, so a count that does not return to where it was after drt_destroy is a leak. Memory the caller bound with
+ * drt_bind_film is the caller's and is not counted. Touches no device. */
+int drt_selftest_live_resources(uint64_t out[4]);
 
 /*
  * Device hierarchy builds: the tree of a live DRT_PATH_BVH context built anew on the device, from the context's own device copy of its

@@ -33,15 +33,18 @@ def test_the_pointer_is_a_field_of_both_parameter_structs():
 
 
 def test_the_resume_array_is_allocated_and_freed_with_the_staging_array():
-    alloc_stage = LAUNCHER.index("hipMalloc((void **)&ctx->d_tail_stage")
-    alloc_resume = LAUNCHER.index("hipMalloc((void **)&ctx->d_tail_resume")
-    assert LAUNCHER.count("hipMalloc((void **)&ctx->d_tail_resume") == 1
+    alloc_stage = LAUNCHER.index("ctx->d_tail_stage.need(")
+    alloc_resume = LAUNCHER.index("ctx->d_tail_resume.need(")
+    assert LAUNCHER.count("ctx->d_tail_resume.need(") == 1 and "ctx->d_tail_resume.remake(" not in LAUNCHER
     assert 0 < alloc_resume - alloc_stage < 300, "allocated on the line after d_tail_stage"
     line = LAUNCHER[alloc_resume - 120:LAUNCHER.index("\n", alloc_resume)]
-    assert "ctx->tail_resume" in line and "npx * batch * ctx->tail_count * 8" in line
-    free_stage = LAUNCHER.index("hipFree(ctx->d_tail_stage)")
-    free_resume = LAUNCHER.index("hipFree(ctx->d_tail_resume)")
-    assert 0 < free_resume - free_stage < 100, "freed on the line after d_tail_stage"
+    assert "ctx->tail_resume" in line and "npx * batch * ctx->tail_count)" in line  # in doubles, as d_tail_stage
+    # both are owning members of the context (csrc/drt_owned.h), declared one after the other: freed with it, by nothing else
+    context = LAUNCHER[LAUNCHER.index("struct drt_context\n"):LAUNCHER.index("static size_t trace_lds_bytes")]
+    own_stage = context.index("DevBuf<double> d_tail_stage;")
+    own_resume = context.index("DevBuf<double> d_tail_resume;")
+    assert 0 < own_resume - own_stage < 200, "declared on the line after d_tail_stage"
+    assert "hipFree(ctx->" not in LAUNCHER and "d_tail_resume.reset(" not in LAUNCHER and "d_tail_resume.release(" not in LAUNCHER
     # only contexts whose trace kernel carries tails and leaves paths to the tail pass get one, and the memory-fit check counts it
     assert re.search(r"ctx->tail_resume\s*=\s*ctx->trace_tail\s*&&\s*!ctx->tail_all_staged\s*&&", LAUNCHER)
     fixed = LAUNCHER[LAUNCHER.index("const size_t per_path_fixed"):]
