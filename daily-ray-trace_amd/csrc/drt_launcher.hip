@@ -13,6 +13,7 @@
 #include "drt_update_kernels.h"
 #include "drt_build_kernels.h"
 #include "drt_material_kernels.h"
+#include "drt_depth_kernels.h"
 #include "drt_owned.h"
 
 #include <algorithm>
@@ -242,6 +243,10 @@ struct drt_context
     Event     mu_ev[2]; /* the copies out of h_spd_stage and h_mat_stage are done */
     bool      spd_stage_busy = false, mat_stage_busy = false;
     uint32_t  spectra_updates = 0, material_updates = 0;
+    /* depth cuts (drt_bind_depth_cuts; drt_depth_kernels.h): the bound depths, ascending, and one film per cut, laid out as the main film */
+    uint32_t  n_cuts = 0, cut_depth[DRT_MAX_DEPTH_CUTS] = {};
+    struct CutFilms { DevBuf<double> pixels[DRT_MAX_DEPTH_CUTS], avgs[DRT_MAX_DEPTH_CUTS], vars[DRT_MAX_DEPTH_CUTS]; } cuts;
+    int       depth_grid_cap = 1;
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -880,6 +885,56 @@ static int launch_shade(drt_context *ctx, uint32_t grid, const ShadeParams &sp, 
     }
 }
 
+/* The cut pass of one kernel pair (depth cuts bound): drt_depth_cut_kernel over the pair's pixels and samples, behind its shade kernel.
+ * pix0: the launch's first pixel in the tile, where its rows of the cut films start. Its queue is word +3 of the pair's work words. */
+template <int NCUTS>
+static const void *depth_kernel(bool lds) { return lds ? (const void *)drt_depth_cut_kernel<NCUTS, true> : (const void *)drt_depth_cut_kernel<NCUTS, false>; }
+static const void *depth_kernel(uint32_t n_cuts, bool lds)
+{
+    switch (n_cuts)
+    {
+        case 1: return depth_kernel<1>(lds);
+        case 2: return depth_kernel<2>(lds);
+        case 3: return depth_kernel<3>(lds);
+        case 4: return depth_kernel<4>(lds);
+        case 5: return depth_kernel<5>(lds);
+        case 6: return depth_kernel<6>(lds);
+        case 7: return depth_kernel<7>(lds);
+        default: return depth_kernel<8>(lds);
+    }
+}
+static size_t depth_lds_bytes(const drt_context *ctx) { return ctx->spds_in_lds ? (size_t)ctx->dsc.n_spd * ctx->dsc.S * 8 : 0; }
+
+static int launch_depth_cuts(drt_context *ctx, const ShadeParams &sp, uint64_t pix0)
+{
+    const size_t S = ctx->dsc.S;
+    DepthCutParams dp{};
+    dp.n_pix = sp.n_pix;
+    dp.n_samples = sp.n_samples;
+    dp.first_sample = sp.first_sample;
+    dp.vertex_words = sp.vertex_words;
+    dp.block_words = sp.block_words;
+    dp.n_lights = sp.n_lights;
+    dp.batch = sp.batch;
+    dp.overflow = sp.overflow;
+    dp.n_sets = (uint32_t)((S + 63) / 64);
+    if (sp.n_pix * dp.n_sets >= 0xFFFFFFFFull) return fail(-1, "tile too large for the depth-cut work queue");
+    dp.n_items = (uint32_t)(sp.n_pix * dp.n_sets);
+    for (uint32_t c = 0; c < ctx->n_cuts; c += 1)
+    {
+        dp.depth[c] = ctx->cut_depth[c];
+        dp.pixels[c] = ctx->cuts.pixels[c] + pix0 * (S + 1);
+        dp.avgs[c] = ctx->cuts.avgs[c] + pix0 * S;
+        dp.vars[c] = ctx->cuts.vars[c] + pix0 * S;
+    }
+    const uint64_t *records = ctx->d_records, *headers = ctx->d_headers;
+    unsigned long long *queue = ctx->d_counters + DRT_NUM_COUNTERS + 3;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)dp.n_items + DEPTH_WAVES - 1) / DEPTH_WAVES, (uint64_t)ctx->depth_grid_cap);
+    void *args[] = {&ctx->dsc, &dp, &records, &headers, &queue};
+    HIP_TRY(hipLaunchKernel(depth_kernel(ctx->n_cuts, ctx->spds_in_lds), dim3(grid), dim3(DEPTH_BLOCK), args, depth_lds_bytes(ctx), ctx->stream));
+    return 0;
+}
+
 template <int NSETS, bool XYZ>
 static int shade_occupancy_mode(drt_context *ctx, int *per_cu)
 {
@@ -1497,6 +1552,7 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     rc = launch_shade(ctx, sgrid, sp, film);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
+    if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, pix0))) return rc;
     const uint64_t seq = ctx->next_seq++;
     hipLaunchKernelGGL(drt_mark_pair_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_counters, (unsigned long long)seq);
     HIP_TRY(hipGetLastError());
@@ -1676,6 +1732,12 @@ extern "C" int drt_reset_film(drt_context *ctx)
     HIP_TRY(hipMemsetAsync(ctx->d_pixels, 0, pixels_bytes(ctx), ctx->stream));
     if (ctx->d_avgs) HIP_TRY(hipMemsetAsync(ctx->d_avgs, 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
     if (ctx->d_vars) HIP_TRY(hipMemsetAsync(ctx->d_vars, 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+    for (uint32_t c = 0; c < ctx->n_cuts; c += 1)
+    {
+        HIP_TRY(hipMemsetAsync(ctx->cuts.pixels[c], 0, (size_t)ctx->n_pix * (S + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->cuts.avgs[c], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->cuts.vars[c], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+    }
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->film_used = ctx->adaptive_done = false;
@@ -1826,6 +1888,7 @@ extern "C" uint32_t drt_batch_spp(drt_context *ctx) { return ctx ? ctx->batch_sp
 static int adaptive_check(drt_context *ctx, const drt_adaptive *a, bool held = false) /* held: drt_render_adaptive_continue, on the film as it is */
 {
     if (!ctx || !a) return fail(-1, "null argument");
+    if (ctx->n_cuts) return fail(-4, "adaptive sampling with depth cuts bound is not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
     if (ctx->xyz_mode) return fail(-4, "adaptive sampling needs the spectral film (DRT_MODE_XYZ keeps no variance)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "adaptive sampling does not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (!held && ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
@@ -2610,6 +2673,186 @@ extern "C" int drt_group_read_sample_counts(drt_group *g, uint32_t *counts)
         if (rc) return rc;
     }
     return group_gather_rows(g, counts, (size_t)g->tile_w * sizeof(uint32_t), &drt_context::d_counts);
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Depth-cut films (the kernel in drt_depth_kernels.h)                        */
+
+/* what a bind is refused for, before any device call; n == 0 (the unbind) passes on any context */
+static int depth_cuts_check(const drt_context *ctx, const uint32_t *depths, uint32_t n, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (n == 0) return 0;
+    if (!depths) return fail(-1, "%s: null depths", name);
+    if (n > DRT_MAX_DEPTH_CUTS) return fail(-1, "%s: %u cuts, at most %u", name, n, (unsigned)DRT_MAX_DEPTH_CUTS);
+    for (uint32_t c = 0; c < n; c += 1)
+    {
+        if (depths[c] == 0 || depths[c] > ctx->params.max_depth)
+            return fail(-1, "%s: cut %u has depth %u, not in 1..max_depth = %u", name, c, depths[c], ctx->params.max_depth);
+        if (c > 0 && depths[c] <= depths[c - 1]) return fail(-1, "%s: the depths are not strictly ascending (cut %u: %u after %u)", name, c, depths[c], depths[c - 1]);
+    }
+    if (ctx->xyz_mode) return fail(-4, "%s: the cut films are spectral films: DRT_MODE_XYZ keeps none", name);
+    if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render: drt_reset_film first", name);
+    if (ctx->film_used) return fail(-7, "%s: the film already holds samples the cut films would lack: drt_reset_film first", name);
+    return 0;
+}
+
+/* n zero-filled cut films for ctx, into `out`; the context is not touched */
+static int depth_cuts_alloc(drt_context *ctx, uint32_t n, drt_context::CutFilms *out)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t S = ctx->dsc.S, n_pix = ctx->n_pix;
+    for (uint32_t c = 0; c < n; c += 1)
+    {
+        hipError_t e = out->pixels[c].need(n_pix * (S + 1));
+        if (e == hipSuccess) e = out->avgs[c].need(n_pix * S);
+        if (e == hipSuccess) e = out->vars[c].need(n_pix * S);
+        if (e != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(-3, "drt_bind_depth_cuts: no memory for cut film %u of %u (%zu bytes each): %s", c, n, n_pix * (3 * S + 1) * 8, hipGetErrorString(e));
+        }
+        HIP_TRY(hipMemsetAsync(out->pixels[c], 0, n_pix * (S + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(out->avgs[c], 0, n_pix * S * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(out->vars[c], 0, n_pix * S * 8, ctx->stream));
+    }
+    if (n)
+    {
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, depth_kernel(n, ctx->spds_in_lds), DEPTH_BLOCK, depth_lds_bytes(ctx)));
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
+        ctx->depth_grid_cap = std::max(1, prop.multiProcessorCount * std::max(1, per_cu)); /* (read only while cuts are bound, and set anew by every bind) */
+    }
+    return 0;
+}
+
+/* the stream idle, then the new films in place of the old (n == 0: none) */
+static int depth_cuts_commit(drt_context *ctx, const uint32_t *depths, uint32_t n, drt_context::CutFilms *films)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->cuts = std::move(*films);
+    ctx->n_cuts = n;
+    for (uint32_t c = 0; c < DRT_MAX_DEPTH_CUTS; c += 1) ctx->cut_depth[c] = c < n ? depths[c] : 0;
+    return 0;
+}
+
+extern "C" int drt_bind_depth_cuts(drt_context *ctx, const uint32_t *depths, uint32_t n)
+{
+    g_last_error.clear();
+    int rc = depth_cuts_check(ctx, depths, n, "drt_bind_depth_cuts");
+    if (rc) return rc;
+    drt_context::CutFilms films;
+    if ((rc = depth_cuts_alloc(ctx, n, &films))) return rc;
+    return depth_cuts_commit(ctx, depths, n, &films);
+}
+
+static int depth_cut_index(const drt_context *ctx, uint32_t cut, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (ctx->n_cuts == 0) return fail(-4, "%s: no depth cuts are bound (drt_bind_depth_cuts)", name);
+    if (cut >= ctx->n_cuts) return fail(-1, "%s: cut %u of %u", name, cut, ctx->n_cuts);
+    return 0;
+}
+
+extern "C" int drt_depth_film_device_ptrs(drt_context *ctx, uint32_t cut, void **d_pixels, void **d_avgs, void **d_vars)
+{
+    int rc = depth_cut_index(ctx, cut, "drt_depth_film_device_ptrs");
+    if (rc) return rc;
+    if (d_pixels) *d_pixels = ctx->cuts.pixels[cut].get();
+    if (d_avgs) *d_avgs = ctx->cuts.avgs[cut].get();
+    if (d_vars) *d_vars = ctx->cuts.vars[cut].get();
+    return 0;
+}
+
+extern "C" int drt_read_depth_film(drt_context *ctx, uint32_t cut, double *pixels, double *avgs, double *vars)
+{
+    int rc = depth_cut_index(ctx, cut, "drt_read_depth_film");
+    if (rc) return rc;
+    if ((rc = drt_synchronize(ctx))) return rc;
+    const size_t S = ctx->dsc.S;
+    if (pixels) HIP_TRY(hipMemcpy(pixels, ctx->cuts.pixels[cut], (size_t)ctx->n_pix * (S + 1) * 8, hipMemcpyDeviceToHost));
+    if (avgs) HIP_TRY(hipMemcpy(avgs, ctx->cuts.avgs[cut], (size_t)ctx->n_pix * S * 8, hipMemcpyDeviceToHost));
+    if (vars) HIP_TRY(hipMemcpy(vars, ctx->cuts.vars[cut], (size_t)ctx->n_pix * S * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_depth_xyz(drt_context *ctx, uint32_t cut, double *xyz)
+{
+    int rc = depth_cut_index(ctx, cut, "drt_read_depth_xyz");
+    if (rc) return rc;
+    if (!xyz) return fail(-1, "drt_read_depth_xyz: null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = drt_synchronize(ctx))) return rc; /* the complete films first (see drt_read_xyz) */
+    HIP_TRY(ctx->d_xyz.need((size_t)ctx->n_pix * 3));
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_film_xyz_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z,
+                       ctx->interval, ctx->n_pix, ctx->cuts.pixels[cut].get(), ctx->d_xyz);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(xyz, ctx->d_xyz, (size_t)ctx->n_pix * 3 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_depth_bgra(drt_context *ctx, uint32_t cut, int which, uint8_t *bgra)
+{
+    int rc = depth_cut_index(ctx, cut, "drt_read_depth_bgra");
+    if (rc) return rc;
+    if (!bgra) return fail(-1, "drt_read_depth_bgra: null argument");
+    if (which < 0 || which > 2) return fail(-1, "which = %d: 0 sum, 1 mean, 2 variance", which);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = drt_synchronize(ctx))) return rc;
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
+    const double *film = which == 0 ? ctx->cuts.pixels[cut].get() : which == 1 ? ctx->cuts.avgs[cut].get() : ctx->cuts.vars[cut].get();
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_film_bgra_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z,
+                       ctx->interval, ctx->n_pix, film, which, ctx->d_bgra);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_group_bind_depth_cuts(drt_group *g, const uint32_t *depths, uint32_t n)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_bind_depth_cuts: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = depth_cuts_check(c, depths, n, "drt_group_bind_depth_cuts"))) return rc;
+    std::vector<drt_context::CutFilms> films(g->ctx.size());
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = depth_cuts_alloc(g->ctx[k], n, &films[k]))) return rc; /* (what was allocated so far is released with `films`) */
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = depth_cuts_commit(g->ctx[k], depths, n, &films[k]))) return rc;
+    return 0;
+}
+
+extern "C" int drt_group_read_depth_film(drt_group *g, uint32_t cut, double *pixels, double *avgs, double *vars)
+{
+    if (!g) return fail(-1, "drt_group_read_depth_film: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = depth_cut_index(c, cut, "drt_group_read_depth_film"))) return rc;
+    if ((rc = drt_group_synchronize(g))) return rc;
+    /* as group_move_rows: device k holds rows k, k + n, ... of the tile */
+    const size_t n = g->ctx.size();
+    double *host[3] = {pixels, avgs, vars};
+    for (int f = 0; f < 3; f += 1)
+    {
+        if (!host[f]) continue;
+        const size_t row_bytes = (size_t)g->tile_w * (f == 0 ? (size_t)g->S + 1 : (size_t)g->S) * 8;
+        for (size_t k = 0; k < n; k += 1)
+        {
+            drt_context *c = g->ctx[k];
+            if (!c) continue;
+            HIP_TRY(hipSetDevice(c->device));
+            const double *dev = f == 0 ? c->cuts.pixels[cut].get() : f == 1 ? c->cuts.avgs[cut].get() : c->cuts.vars[cut].get();
+            HIP_TRY(hipMemcpy2D((char *)host[f] + k * row_bytes, n * row_bytes, dev, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
 }
 
 /* ---------------------------------------------------------------------------------------------- */

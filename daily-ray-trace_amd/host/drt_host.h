@@ -81,7 +81,7 @@ typedef struct
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
  * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK,
- * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE. */
+ * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS. */
 #define DRT_HOST_MAX_PICKS 64
 #define DRT_HOST_MAX_LEVELS 64
 typedef struct
@@ -137,6 +137,13 @@ typedef struct
      * Not combined with DRT_TURNTABLE or with what the turntable is not combined with. 0 levels: off, and everything as without it */
     uint32_t n_levels;
     double   levels[DRT_HOST_MAX_LEVELS];
+    /* DRT_DEPTH_CUTS="d0,d1,...": beside the render, its film at every shorter max_cast_depth listed (drt_group_bind_depth_cuts: ascending
+     * whole numbers from 1 to max_cast_depth, DRT_MAX_DEPTH_CUTS at most): per cut d the three standard .spd outputs again as
+     * <output_spd>.depth<d>.spd, <average_spd>.depth<d>.spd, <variance_spd>.depth<d>.spd and the picture <output_spd>.depth<d>.bmp; every
+     * other output stays byte for byte what it is without it. Not combined with adaptive sampling, checkpoints or resuming, DRT_TURNTABLE
+     * or DRT_LIGHT_LEVELS. 0 cuts: off */
+    uint32_t n_depth_cuts;
+    uint32_t depth_cuts[DRT_MAX_DEPTH_CUTS];
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u

@@ -89,6 +89,12 @@ static int frame_path(char dst[64], const char *src, u32 frame)
     return snprintf(dst, 64, "%.*s.%04u%s", stem, src, frame, dot ? dot : "") < 64 ? 0 : -1;
 }
 
+/* DRT_DEPTH_CUTS: "<src>.depth<d><ext>" into a config field; -1 when it does not fit */
+static int depth_path(char dst[64], const char *src, u32 depth, const char *ext)
+{
+    return snprintf(dst, 64, "%s.depth%u%s", src, depth, ext) < 64 ? 0 : -1;
+}
+
 /* Frame k of DRT_LIGHT_LEVELS: `rows` gets the scene's rows [*first_row, *first_row + *count) -- from the first to the last row an emissive
  * material names as its emission -- with every such row times `level` (one multiplication per sample) and the rows between as they are.
  * No emissive material: *count = 0. */
@@ -367,6 +373,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         free(ray_d);
         free(ray_o);
     }
+    /* DRT_DEPTH_CUTS: the cut films, bound while the film is still without samples */
+    if (!rc && opt && opt->n_depth_cuts) rc = drt_group_bind_depth_cuts(ctx, opt->depth_cuts, opt->n_depth_cuts);
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc && opt && opt->adaptive && (opt->adaptive_checkpoint_rounds || opt->adaptive_resume))
     {
@@ -457,6 +465,39 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     }
     if (!rc) rc = drt_group_read_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc) rc = drt_group_get_stats(ctx, &stats);
+    /* DRT_DEPTH_CUTS: every cut film through the standard writer (the variance normalised as the standard output's is) under the
+     * outputs' names with .depth<d> behind them, and the picture of its sum film by the .spd -> .bmp post-process */
+    int cut_bad = 0;
+    if (!rc && opt && opt->n_depth_cuts)
+    {
+        f64 *cut_pixels = (f64 *)malloc(num_pixels * (S + 1) * sizeof(f64));
+        f64 *cut_avgs = (f64 *)malloc(num_pixels * S * sizeof(f64)), *cut_vars = (f64 *)malloc(num_pixels * S * sizeof(f64));
+        f64 *cmf = (f64 *)malloc((size_t)4 * S * sizeof(f64));
+        if (!cut_pixels || !cut_avgs || !cut_vars || !cmf) rc = -3;
+        if (!rc)
+        {
+            const u32 rows[4] = { scene->cmf_rw, scene->cmf_x, scene->cmf_y, scene->cmf_z };
+            for (int r = 0; r < 4; r += 1) memcpy(cmf + (size_t)r * S, scene->spds + (size_t)rows[r] * S, (size_t)S * sizeof(f64));
+        }
+        for (u32 k = 0; !rc && !cut_bad && k < opt->n_depth_cuts; k += 1)
+        {
+            const u32 d = opt->depth_cuts[k];
+            config_arguments cc = *config;
+            char bmp[64];
+            if ((rc = drt_group_read_depth_film(ctx, k, cut_pixels, cut_avgs, cut_vars))) break;
+            if (depth_path(cc.output_spd, config->output_spd, d, ".spd") || depth_path(cc.average_spd, config->average_spd, d, ".spd") ||
+                depth_path(cc.variance_spd, config->variance_spd, d, ".spd") || depth_path(bmp, config->output_spd, d, ".bmp") ||
+                drt_host_write_outputs(&cc, width, height, S, scene->min_wavelength, scene->wavelength_interval, cut_pixels, cut_avgs, cut_vars, 0, done, seed) ||
+                drt_host_spd_file_to_bmp(cc.output_spd, bmp, cmf))
+                cut_bad = -1;
+            else if (!opt->quiet) printf("Depth cut %u: %s\n", d, cc.output_spd);
+        }
+        if (cut_bad) fprintf(stderr, "render_image: could not write the outputs of a depth cut\n");
+        free(cmf);
+        free(cut_vars);
+        free(cut_avgs);
+        free(cut_pixels);
+    }
     /* the denoised film, while the devices still hold the scene's tables (the film itself is not changed) */
     f64 *dn_mean = NULL, *dn_var = NULL;
     if (!rc && opt && opt->denoise)
@@ -640,7 +681,7 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     free(dst_avgs);
     free(dst_pixels);
     drt_host_free_scene(hs);
-    return (w0 || w1 || w2 || w3 || w4) ? -2 : 0;
+    return (w0 || w1 || w2 || w3 || w4 || cut_bad) ? -2 : 0;
 }
 
 /* a whole-string number from the environment: 0 and *out set, -1 (and a message naming the variable) when it does not parse */
@@ -904,6 +945,43 @@ static int light_levels_options(drt_host_options *opt)
     return 0;
 }
 
+/* DRT_DEPTH_CUTS="d0,d1,..." (whole numbers from 1 to max_cast_depth, strictly ascending, DRT_MAX_DEPTH_CUTS at most): parsed and
+ * checked here, before any device call, after the options it cannot be combined with. */
+static int depth_cuts_options(const config_arguments *config, drt_host_options *opt)
+{
+    opt->n_depth_cuts = 0;
+    const char *e = getenv("DRT_DEPTH_CUTS");
+    if (!e) return 0;
+    if (getenv("DRT_ADAPTIVE_ERROR")) { fprintf(stderr, "render_image: DRT_DEPTH_CUTS cannot be combined with DRT_ADAPTIVE_ERROR: an adaptive render keeps no cut films\n"); return -1; }
+    if (getenv("DRT_CHECKPOINT_SPP")) { fprintf(stderr, "render_image: DRT_DEPTH_CUTS cannot be combined with DRT_CHECKPOINT_SPP: a checkpoint holds no cut films\n"); return -1; }
+    if (getenv("DRT_RESUME")) { fprintf(stderr, "render_image: DRT_DEPTH_CUTS cannot be combined with DRT_RESUME: a checkpoint holds no cut films\n"); return -1; }
+    if (getenv("DRT_TURNTABLE")) { fprintf(stderr, "render_image: DRT_DEPTH_CUTS cannot be combined with DRT_TURNTABLE\n"); return -1; }
+    if (getenv("DRT_LIGHT_LEVELS")) { fprintf(stderr, "render_image: DRT_DEPTH_CUTS cannot be combined with DRT_LIGHT_LEVELS\n"); return -1; }
+    for (const char *c = e;;)
+    {
+        if (*c < '0' || *c > '9')
+        { fprintf(stderr, "render_image: DRT_DEPTH_CUTS=\"%s\": whole numbers separated by commas\n", e); return -1; }
+        char *end;
+        const unsigned long long d = strtoull(c, &end, 10);
+        if (*end && *end != ',')
+        { fprintf(stderr, "render_image: DRT_DEPTH_CUTS=\"%s\": whole numbers separated by commas\n", e); return -1; }
+        if (opt->n_depth_cuts == DRT_MAX_DEPTH_CUTS) { fprintf(stderr, "render_image: DRT_DEPTH_CUTS: %d depths at most\n", DRT_MAX_DEPTH_CUTS); return -1; }
+        if (d < 1 || d > config->max_cast_depth)
+        { fprintf(stderr, "render_image: DRT_DEPTH_CUTS: depth %llu is not in 1..max_cast_depth (%u)\n", d, config->max_cast_depth); return -1; }
+        if (opt->n_depth_cuts && (u32)d <= opt->depth_cuts[opt->n_depth_cuts - 1])
+        { fprintf(stderr, "render_image: DRT_DEPTH_CUTS=\"%s\": the depths are not strictly ascending\n", e); return -1; }
+        opt->depth_cuts[opt->n_depth_cuts++] = (u32)d;
+        if (!*end) break;
+        c = end + 1;
+    }
+    char path[64];
+    const u32 deepest = opt->depth_cuts[opt->n_depth_cuts - 1];
+    if (depth_path(path, config->output_spd, deepest, ".spd") || depth_path(path, config->average_spd, deepest, ".spd") ||
+        depth_path(path, config->variance_spd, deepest, ".spd") || depth_path(path, config->output_spd, deepest, ".bmp"))
+    { fprintf(stderr, "render_image: DRT_DEPTH_CUTS: an output name with .depth%u.spd behind it is longer than 63 characters\n", deepest); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -936,5 +1014,6 @@ void render_image(config_arguments *config)
     if (projection_options(&opt) != 0) exit(-1);
     if (turntable_options(&opt) != 0) exit(-1);
     if (light_levels_options(&opt) != 0) exit(-1);
+    if (depth_cuts_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

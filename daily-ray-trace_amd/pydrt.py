@@ -669,6 +669,15 @@ def hip_lib():
             L.drt_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
             L.drt_group_update_spectra.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
             L.drt_group_update_materials.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        if hasattr(L, "drt_bind_depth_cuts"):  # (as drt_selftest_path_ids below)
+            u32p, vpp = C.POINTER(C.c_uint32), C.POINTER(C.c_void_p)
+            L.drt_bind_depth_cuts.argtypes = [C.c_void_p, u32p, C.c_uint32]
+            L.drt_read_depth_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
+            L.drt_depth_film_device_ptrs.argtypes = [C.c_void_p, C.c_uint32, vpp, vpp, vpp]
+            L.drt_read_depth_xyz.argtypes = [C.c_void_p, C.c_uint32, f64p]
+            L.drt_read_depth_bgra.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
+            L.drt_group_bind_depth_cuts.argtypes = [C.c_void_p, u32p, C.c_uint32]
+            L.drt_group_read_depth_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
         if hasattr(L, "drt_rebuild_hierarchy"):
             L.drt_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
@@ -713,7 +722,31 @@ HIP_SYMBOLS = ["drt_last_error", "drt_device_count", "drt_create", "drt_destroy"
                "drt_set_camera", "drt_update_surfaces", "drt_get_update_report", "drt_group_set_camera", "drt_group_update_surfaces",
                "drt_group_reset_film",
                "drt_rebuild_hierarchy", "drt_group_rebuild_hierarchy", "drt_get_hierarchy_report", "drt_read_hierarchy",
-               "drt_update_spectra", "drt_update_materials", "drt_group_update_spectra", "drt_group_update_materials"]
+               "drt_update_spectra", "drt_update_materials", "drt_group_update_spectra", "drt_group_update_materials",
+               "drt_bind_depth_cuts", "drt_read_depth_film", "drt_depth_film_device_ptrs", "drt_read_depth_xyz", "drt_read_depth_bgra",
+               "drt_group_bind_depth_cuts", "drt_group_read_depth_film"]
+
+MAX_DEPTH_CUTS = 8  # DRT_MAX_DEPTH_CUTS
+
+
+def _depth_array(depths):
+    """the (uint32 array or None, count) of drt_bind_depth_cuts: None or an empty sequence unbinds"""
+    depths = [] if depths is None else [int(d) for d in depths]
+    if any(d < 0 or d > 0xFFFFFFFF for d in depths):
+        raise ValueError("bind_depth_cuts: depths are unsigned 32-bit numbers")
+    return ((C.c_uint32 * len(depths))(*depths) if depths else None), len(depths)
+
+
+def depth_layers(means):
+    """Cumulative cut means [n_cuts][...] (cut k = everything up to depth d_k, ascending) as per-bounce layers: layer 0 is cut 0, layer
+    k is cut k minus cut k - 1, what the loop iterations d_(k-1) .. d_k - 1 add. Pure numpy; the layers sum back to the last cut up to
+    rounding."""
+    m = np.asarray(means, dtype=np.float64)
+    if m.ndim < 1 or m.shape[0] < 1:
+        raise ValueError("depth_layers: at least one cut")
+    out = m.copy()
+    out[1:] = m[1:] - m[:-1]
+    return out
 
 
 def _check(rc, what):
@@ -797,6 +830,36 @@ class Renderer:
         """BMP pixel bytes [n][4] = B, G, R, 255 of the sum (0), mean (1) or normalised variance (2) film."""
         out = np.empty((self.n_pixels, 4), dtype=np.uint8)
         _check(self.L.drt_read_bgra(self.ctx, int(which), _ptr(out, C.c_uint8)), "drt_read_bgra")
+        return out
+
+    def bind_depth_cuts(self, depths):
+        """drt_bind_depth_cuts: one cut film per depth (ascending, each in 1..max_depth, at most MAX_DEPTH_CUTS) beside the main film,
+        on a film without samples. None or an empty sequence unbinds."""
+        arr, n = _depth_array(depths)
+        _check(self.L.drt_bind_depth_cuts(self.ctx, arr, n), "drt_bind_depth_cuts")
+
+    def read_depth_film(self, cut):
+        """(pixels, means, variances) of cut film `cut`, laid out as read_film's"""
+        px = np.empty((self.n_pixels, self.S + 1), dtype=np.float64)
+        av = np.empty((self.n_pixels, self.S), dtype=np.float64)
+        va = np.empty((self.n_pixels, self.S), dtype=np.float64)
+        _check(self.L.drt_read_depth_film(self.ctx, int(cut), _ptr(px, C.c_double), _ptr(av, C.c_double), _ptr(va, C.c_double)), "drt_read_depth_film")
+        return px, av, va
+
+    def depth_film_device_ptrs(self, cut):
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self.L.drt_depth_film_device_ptrs(self.ctx, int(cut), C.byref(a), C.byref(b), C.byref(c)), "drt_depth_film_device_ptrs")
+        return a.value, b.value, c.value
+
+    def read_depth_xyz(self, cut):
+        xyz = np.empty((self.n_pixels, 3), dtype=np.float64)
+        _check(self.L.drt_read_depth_xyz(self.ctx, int(cut), _ptr(xyz, C.c_double)), "drt_read_depth_xyz")
+        return xyz
+
+    def read_depth_bgra(self, cut, which=0):
+        """read_bgra of cut film `cut`"""
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_depth_bgra(self.ctx, int(cut), int(which), _ptr(out, C.c_uint8)), "drt_read_depth_bgra")
         return out
 
     def read_hit_indices(self, num_samples):
@@ -1171,6 +1234,19 @@ class Group:
             raise ValueError("Group.bind_rays: numpy arrays (a group takes host pointers only)")
         t, _ = _ray_table(origins, dirs, weights, int(self.params.width), int(self.params.height), 0)
         _check(self.L.drt_group_bind_rays(self.g, C.byref(t)), "drt_group_bind_rays")
+
+    def bind_depth_cuts(self, depths):
+        """drt_group_bind_depth_cuts: as Renderer.bind_depth_cuts, every context checked before any is changed"""
+        arr, n = _depth_array(depths)
+        _check(self.L.drt_group_bind_depth_cuts(self.g, arr, n), "drt_group_bind_depth_cuts")
+
+    def read_depth_film(self, cut):
+        """drt_group_read_depth_film: cut film `cut` of the whole tile, in image order"""
+        px = np.empty((self.n_pixels, self.S + 1)); av = np.empty((self.n_pixels, self.S)); va = np.empty((self.n_pixels, self.S))
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.drt_group_read_depth_film(self.g, int(cut), px.ctypes.data_as(f64p), av.ctypes.data_as(f64p), va.ctypes.data_as(f64p)),
+               "drt_group_read_depth_film")
+        return px, av, va
 
     def reset_film(self):
         _check(self.L.drt_group_reset_film(self.g), "drt_group_reset_film")

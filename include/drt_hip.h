@@ -188,7 +188,7 @@ typedef struct drt_stats
     uint64_t shadow_scans;      /* points_mutually_visible calls             */
     uint64_t rng_draws;
     double   trace_ms;          /* path-geometry kernel, HIP-event time      */
-    double   shade_ms;          /* spectral shade + film kernel              */
+    double   shade_ms;          /* spectral shade + film kernel; while depth cuts are bound (drt_bind_depth_cuts), the cut pass too */
     double   total_ms;
     /* the pool of vertex records (four vertices per block): its size, the most a launch has used, and how many launches had to be
      * rendered again in worst-case-sized pieces because the pool ran out (0 unless the tile's paths grew after the context measured them) */
@@ -564,6 +564,38 @@ int drt_bind_rays(drt_context *ctx, const drt_ray_table *t);   /* t == NULL: bac
 /* Host pointers only: every device copies its own rows. All contexts are checked, and every device's copy is made, before any context
  * is changed: a call that fails on one device leaves the whole group as it was. */
 int drt_group_bind_rays(drt_group *g, const drt_ray_table *t);
+
+/*
+ * Depth-cut films: beside the film of a render at max_depth D, the film the same render would leave at a shorter max_depth, for up
+ * to DRT_MAX_DEPTH_CUTS depths at once and without tracing anything again. DESIGN.md section 5j.
+ *
+ * The rule: cut k of a context bound to depths d_0 < d_1 < ... holds, bit for bit, the film of a context created with
+ * max_depth = d_k and otherwise the same parameters, after the same drt_render calls. The path generator is keyed by (seed, pixel,
+ * sample) only, so that render walks the first d_k loop iterations of cast_ray (src/daily_ray_trace.c:440-472) of this one: its value
+ * is `dst` after them, times the same vignette (:615), through the same film update (:732-743) with the sample's own number.
+ *
+ * A cut film has the main film's three buffers and layout: [tile_h*tile_w][S+1] sum + filter, [..][S] mean, [..][S] variance, owned
+ * by the context, zero-filled at the bind and by drt_reset_film, released at the unbind and by drt_destroy. From the bind on every
+ * sample drt_render adds to the film is added to every cut film too; a launch whose record pool ran out leaves them untouched and
+ * is rendered again with the rest.
+ */
+#define DRT_MAX_DEPTH_CUTS 8
+/* Bind the context to n cut depths (n == 0: unbind, the cut films are released). Refused, with the reason in drt_last_error() and the
+ * context as it was: n > DRT_MAX_DEPTH_CUTS, a depth of 0 or above params.max_depth, depths not strictly ascending, DRT_MODE_XYZ, a
+ * film that holds samples or an adaptive render (drt_reset_film first), an allocation failure. While cuts are bound
+ * drt_render_adaptive and drt_render_adaptive_continue are refused. */
+int drt_bind_depth_cuts(drt_context *ctx, const uint32_t *depths, uint32_t n);
+/* Copy cut film `cut` (0 .. n-1) to host buffers (any may be NULL). Synchronises. */
+int drt_read_depth_film(drt_context *ctx, uint32_t cut, double *pixels, double *avgs, double *vars);
+/* Device pointers of cut film `cut`'s buffers; valid until the next bind, unbind or drt_destroy. */
+int drt_depth_film_device_ptrs(drt_context *ctx, uint32_t cut, void **d_pixels, void **d_avgs, void **d_vars);
+/* drt_read_xyz and drt_read_bgra of cut film `cut`: the same kernels over its buffers. Synchronise before they convert. */
+int drt_read_depth_xyz(drt_context *ctx, uint32_t cut, double *xyz);
+int drt_read_depth_bgra(drt_context *ctx, uint32_t cut, int which, uint8_t *bgra);
+/* Every context is checked before any is changed; a device whose allocation fails leaves the whole group unbound. */
+int drt_group_bind_depth_cuts(drt_group *g, const uint32_t *depths, uint32_t n);
+/* Cut film `cut` of the whole tile, in image order, as drt_group_read_film. */
+int drt_group_read_depth_film(drt_group *g, uint32_t cut, double *pixels, double *avgs, double *vars);
 
 /*
  * Scene updates: move the camera and the surfaces of a live context, where the only way used to be drt_destroy + drt_create (the
