@@ -1797,6 +1797,8 @@ __device__ __forceinline__ double spd_at(SpdPtr spds, uint32_t S, uint32_t idx, 
 #define DRT_LIST_MIRROR ((uint64_t)DRT_BDSF_mirror_bdsf)
 #define DRT_LIST_GLASS ((uint64_t)DRT_BDSF_fs_dielectric_reflectance_bdsf | ((uint64_t)DRT_BDSF_fs_dielectric_transmittance_bdsf << 4))
 #define DRT_LIST_CONDUCTOR ((uint64_t)DRT_BDSF_fs_conductor_bdsf)
+#define DRT_LIST_GGX ((uint64_t)DRT_BDSF_ct_conductor_bdsf) /* the rough conductor: the fourth fixed list (fixed_vertex kind 3) */
+#define DRT_LIST_PLASTIC ((uint64_t)DRT_BDSF_bp_diffuse_bdsf | ((uint64_t)DRT_BDSF_bp_glossy_bdsf << 4)) /* FLAG_PLASTIC's list */
 template <bool SIMPLE = false, uint32_t FIXED_N = 0, uint64_t FIXED_LIST = 0>
 __device__ __forceinline__ double bdsf_at_wavelength(uint64_t list_arg, uint32_t num_bdsfs_arg, double diffuse_pi, double glossy, double mirror,
                                                      double ir, double tr, double te, double on_dot, double a_in, double spec,
@@ -1877,7 +1879,9 @@ __device__ __forceinline__ double bdsf_at_wavelength(uint64_t list_arg, uint32_t
  * into LDS once) and draw work items (pixel groups, or pieces of them: see the queue below) from a global counter,
  * because pixel cost varies. Three kinds of vertex have straight-line code of their own in the main pass: the leading run of
  * two-lobe plastic vertices, and -- unless DRT_NO_FIXED_LISTS is set (ShadeParams::no_fixed_lists) -- mirror, glass and
- * smooth-conductor vertices (fixed_vertex); every other list goes through the general loop.
+ * smooth-conductor vertices (fixed_vertex); every other list goes through the general loop. Where every list of the scene has such
+ * code -- the rough conductor's fixed form is fixed_vertex's fourth kind -- the launcher takes drt_shade_kernel_closed, the same
+ * body without the general loop (shade_pixels, CLOSED).
  */
 #ifndef SHADE_PREFETCH_REGS
 #define SHADE_PREFETCH_REGS 2 /* 64-word registers per path: 128 record words are prefetched, deeper paths fall back */
@@ -1905,7 +1909,7 @@ template <bool SPDS_IN_LDS, bool XYZ, bool SIMPLE, bool LIST = false>
 __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const ShadeParams &sp, const double *lds, uint64_t *wave_lds, const uint64_t *__restrict__ records,
                                                  const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                                  double *__restrict__ film_avgs, double *__restrict__ film_vars, uint64_t chunk_base,
-                                                 uint64_t chunk_end, uint32_t lane)
+                                                 uint64_t chunk_end, uint32_t lane, const bool closed)
 {
     const uint32_t S = sc.S;
     const uint32_t vw = sp.vertex_words;
@@ -2116,7 +2120,6 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     const uint64_t *vrec = vcur;
                     const uint64_t list = vrec[0], w1 = vrec[1], w2 = vrec[2];
                     const double on_dot = word_as_double(vrec[3]), dir_pdf = word_as_double(vrec[4]);
-                    const double s_a_in = word_as_double(vrec[5]), s_spec = word_as_double(vrec[6]);
                     const uint32_t num_bdsfs = (uint32_t)(w1 & 0xFFu);
                     const uint32_t sflags = (uint32_t)(w1 >> 8) & 0xFFu;
                     const uint32_t i_diffuse = (uint32_t)(w1 >> 16) & 0xFFFFu, i_glossy = (uint32_t)(w1 >> 32) & 0xFFFFu;
@@ -2126,50 +2129,59 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     bool paired;
                     fresnel_rows(w2, f0, f1, f2, paired);
                     const double ir = SIMPLE ? 0.0 : spd_at(table, S, f0, lam), tr = SIMPLE ? 0.0 : spd_at(table, S, f1, lam), te = SIMPLE ? 0.0 : spd_at(table, S, f2, lam);
-                    double contribution = 0.0;
-                    /* glass lanes (a quarter and more of what is replayed) take the fixed-list form the main pass uses: of the record
-                     * only the words that list reads, no diffuse / glossy / mirror row. One branch on the lane's list inside this step,
-                     * not a third vote class: no iteration serves fewer lanes than before */
-                    const bool glass = !SIMPLE && num_bdsfs == 2u && list == DRT_LIST_GLASS;
-                    if (glass)
-                    {
+                    /* One lane's vertex in a fixed-list form or in the general one: `eval(flags, words)` is the list's sum, words[0..3] being
+                     * a_in, spec, mn_dot, ct_coef of the light block or of the sampled direction (the two lie in the same order). Glass lanes
+                     * (a quarter and more of what is replayed) take the fixed-list form the main pass uses: of the record only the words that
+                     * list reads, no diffuse / glossy / mirror row. A branch on the lane's list inside this step, not a third vote class: no
+                     * iteration serves fewer lanes than before. `closed` (a constant of the instantiation: every list of the scene has a
+                     * fixed form): every lane takes its list's fixed form this way, and the general form is never reached and not compiled.
+                     * In the general instantiations rough-conductor lanes stay with the general form: a branch of their own measured
+                     * 0.6 ms slower there. */
+                    auto lane_vertex = [&](auto eval) {
+                        double contribution = 0.0;
                         for (uint32_t l = 0; l < sp.n_lights; l += 1)
                         {
                             const uint64_t *lrec = vrec + REC_VERTEX_WORDS + l * REC_LIGHT_WORDS;
                             const uint64_t lw0 = lrec[0];
                             const uint32_t lflags = (uint32_t)(lw0 >> 16) & 0xFFu;
                             if (!(lflags & FLAG_VISIBLE)) continue;
-                            double reflectance = bdsf_at_wavelength<SIMPLE, 2, DRT_LIST_GLASS>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, on_dot, 0.0, 0.0, 0.0, 0.0, lflags, paired);
+                            double reflectance = eval(lflags, lrec + 2);
                             contribution = contribution + reflectance;
                             contribution = contribution * spd_at(table, S, (uint32_t)(lw0 & 0xFFFFu), lam);
                             contribution = contribution * word_as_double(lrec[1]);
                         }
                         dst = dst + throughput * contribution;
-                        double reflectance = bdsf_at_wavelength<SIMPLE, 2, DRT_LIST_GLASS>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, on_dot, 0.0, 0.0, 0.0, 0.0, sflags, paired);
+                        double reflectance = eval(sflags, vrec + 5);
                         reflectance = reflectance * dir_pdf;
                         throughput = throughput * reflectance;
-                    }
+                    };
+                    const bool glass = !SIMPLE && num_bdsfs == 2u && list == DRT_LIST_GLASS;
+                    const bool ggx = closed && list == DRT_LIST_GGX;
+                    if (glass)
+                        lane_vertex([&](uint32_t flags, const uint64_t *) {
+                            return bdsf_at_wavelength<SIMPLE, 2, DRT_LIST_GLASS>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
+                        });
+                    else if (ggx)
+                        lane_vertex([&](uint32_t flags, const uint64_t *a) {
+                            return bdsf_at_wavelength<SIMPLE, 1, DRT_LIST_GGX>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, 0.0, 0.0, 0.0, word_as_double(a[2]), word_as_double(a[3]), flags, paired);
+                        });
+                    else if (closed && list == DRT_LIST_MIRROR)
+                        lane_vertex([&](uint32_t flags, const uint64_t *) {
+                            return bdsf_at_wavelength<SIMPLE, 1, DRT_LIST_MIRROR>(0, 0, 0.0, 0.0, mirror, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, flags, false);
+                        });
+                    else if (closed && list == DRT_LIST_CONDUCTOR)
+                        lane_vertex([&](uint32_t flags, const uint64_t *) {
+                            return bdsf_at_wavelength<SIMPLE, 1, DRT_LIST_CONDUCTOR>(0, 0, 0.0, 0.0, 0.0, ir, tr, te, on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
+                        });
+                    else if (closed) /* a plastic vertex beyond the header's 16 flags */
+                        lane_vertex([&](uint32_t flags, const uint64_t *a) {
+                            return bdsf_at_wavelength<SIMPLE, 2, DRT_LIST_PLASTIC>(0, 0, diffuse_pi, glossy, 0.0, 0.0, 0.0, 0.0, 0.0, word_as_double(a[0]), word_as_double(a[1]), 0.0, 0.0, flags, false);
+                        });
                     else
-                    {
-                    for (uint32_t l = 0; l < sp.n_lights; l += 1)
-                    {
-                        const uint64_t *lrec = vrec + REC_VERTEX_WORDS + l * REC_LIGHT_WORDS;
-                        const uint64_t lw0 = lrec[0];
-                        const uint32_t lflags = (uint32_t)(lw0 >> 16) & 0xFFu;
-                        if (!(lflags & FLAG_VISIBLE)) continue;
-                        double reflectance = bdsf_at_wavelength<SIMPLE>(list, num_bdsfs, diffuse_pi, glossy, mirror, ir, tr, te, on_dot,
-                                                                word_as_double(lrec[2]), word_as_double(lrec[3]), word_as_double(lrec[4]),
-                                                                word_as_double(lrec[5]), lflags, paired);
-                        contribution = contribution + reflectance;
-                        contribution = contribution * spd_at(table, S, (uint32_t)(lw0 & 0xFFFFu), lam);
-                        contribution = contribution * word_as_double(lrec[1]);
-                    }
-                    dst = dst + throughput * contribution;
-                    double reflectance = bdsf_at_wavelength<SIMPLE>(list, num_bdsfs, diffuse_pi, glossy, mirror, ir, tr, te, on_dot, s_a_in, s_spec,
-                                                            word_as_double(vrec[7]), word_as_double(vrec[8]), sflags, paired);
-                    reflectance = reflectance * dir_pdf;
-                    throughput = throughput * reflectance;
-                    }
+                        lane_vertex([&](uint32_t flags, const uint64_t *a) {
+                            return bdsf_at_wavelength<SIMPLE>(list, num_bdsfs, diffuse_pi, glossy, mirror, ir, tr, te, on_dot, word_as_double(a[0]), word_as_double(a[1]),
+                                                              word_as_double(a[2]), word_as_double(a[3]), flags, paired);
+                        });
                     v += 1;
                     if (v < n_shaded) vcur = (v & (REC_BLOCK_VERTICES - 1u)) != 0u ? vcur + vw : path_vertex(records, sp.block_words, vw, ph2, deep_blocks(v), v); /* the next record: the one behind, or a new block */
                 }
@@ -2249,12 +2261,17 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
 }
 
 
-template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE = false, bool LIST = false>
-__global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAVES_SIMPLE : SHADE_WAVES_PER_SIMD_FOR(NSETS)) void drt_shade_kernel(DevScene sc, ShadeParams sp, const uint64_t *__restrict__ records,
-                                                                 const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
-                                                                 double *__restrict__ film_avgs, double *__restrict__ film_vars,
-                                                                 unsigned long long *__restrict__ work_counter)
+/* The kernel's body, shared by its two entry points below. CLOSED: every BDSF list of the scene is the two-lobe plastic or one of
+ * fixed_vertex's four (the launcher checks, closed_lists()): the general list does not exist, neither in the main pass nor in the tail
+ * pass's general step -- its loop, its switch and the registers they hold are not compiled. Same operations in the same order: what
+ * is left is the very code the general instantiation runs for these lists (tests/test_gpu_closed_lists.py flips DRT_NO_CLOSED_SHADE). */
+template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE, bool LIST, bool CLOSED>
+__device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadeParams &sp, const uint64_t *__restrict__ records,
+                                             const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
+                                             double *__restrict__ film_avgs, double *__restrict__ film_vars,
+                                             unsigned long long *__restrict__ work_counter)
 {
+    static_assert(!CLOSED || (NSETS == 1 && SPDS_IN_LDS && !XYZ && !SIMPLE && !LIST), "the closed form exists for one wavelength set, tables in LDS, spectral film, dense launches");
     extern __shared__ double lds[];
     const uint32_t S = sc.S;
     if (*sp.overflow) return; /* the records of this launch are incomplete: leave the film as it is (see the record layout) */
@@ -2653,20 +2670,26 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                  * below; the light block keeps `((sum + 0) * em) * c` whatever the flags say (em or c may be infinite or NaN).
                  * ONE body for the three lists, which differ in one scalar comparison per evaluation: three bodies of their own cost
                  * the kernel ten scalar spills and a vector register pair in scratch (tests/test_kernel_spill_budget.py). */
-                auto fixed_vertex = [&](uint32_t kind) { /* wave-uniform: 0 {mirror}, 1 {dielectric reflectance, transmittance}, 2 {smooth conductor} */
+                /* The rough conductor {ct_conductor_bdsf} is the fourth kind: it reads the three Fresnel rows, and in place of on_dot the
+                 * half vector's mn_dot and ct_coef -- of the sampled direction, and of every visible light -- again as broadcast LDS
+                 * reads while the vertex is among the prefetched ones. */
+                auto fixed_vertex = [&](uint32_t kind) { /* wave-uniform: 0 {mirror}, 1 {dielectric reflectance, transmittance}, 2 {smooth conductor}, 3 {rough conductor} */
                     const bool fresnel = !SIMPLE && kind != 0u;
+                    constexpr bool GGX_BODY = CLOSED; /* the general instantiations keep the general loop for the rough conductor */
+                    const bool rough = GGX_BODY && kind == 3u;
                     const bool in_lds = v < n_fast;
                     const uint64_t *vwords = rec_words + v * vw;
                     uint32_t i_r0 = (uint32_t)(w1 >> 48) & 0xFFFFu, i_r1 = 0, i_r2 = 0; /* the mirror's one row, or the three Fresnel rows */
                     bool paired = false;
-                    double on_dot = 0.0;
+                    double on_dot = 0.0; /* the cosine the Fresnel term is taken at: on_dot, or the rough conductor's mn_dot */
+                    double ct = 0.0;     /* the rough conductor's ct_coef */
                     double r0[NSETS], r1[NSETS], r2[NSETS];
 #pragma unroll
                     for (int k = 0; k < NSETS; k += 1) r1[k] = r2[k] = 0.0;
                     if (fresnel)
                     {
                         fresnel_rows(readlane64(src, lane0 + 2), i_r0, i_r1, i_r2, paired);
-                        on_dot = in_lds ? word_as_double(vwords[3]) : word_as_double(readlane64(src, lane0 + 3));
+                        if (!rough) on_dot = in_lds ? word_as_double(vwords[3]) : word_as_double(readlane64(src, lane0 + 3));
 #pragma unroll
                         for (int k = 0; k < NSETS; k += 1)
                         {
@@ -2677,12 +2700,14 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
 #pragma unroll
                     for (int k = 0; k < NSETS; k += 1) r0[k] = spd_at(table, S, i_r0, lam_c[k]);
                     /* the list's sum for one wavelength set: the fixed-list forms, chosen by one scalar comparison */
-                    auto eval = [&](int k, uint32_t flags) -> double {
+                    auto eval = [&](int k, uint32_t flags) -> double { /* (the rough conductor: on_dot and ct hold the evaluation's mn_dot and ct_coef) */
                         if (SIMPLE || kind == 0u)
                             return bdsf_at_wavelength<SIMPLE, 1u, DRT_LIST_MIRROR>(0ull, 0u, 0.0, 0.0, r0[k], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, flags, false);
                         if (kind == 1u)
                             return bdsf_at_wavelength<SIMPLE, 2u, DRT_LIST_GLASS>(0ull, 0u, 0.0, 0.0, 0.0, r0[k], r1[k], r2[k], on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
-                        return bdsf_at_wavelength<SIMPLE, 1u, DRT_LIST_CONDUCTOR>(0ull, 0u, 0.0, 0.0, 0.0, r0[k], r1[k], r2[k], on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
+                        if (kind == 2u || !GGX_BODY)
+                            return bdsf_at_wavelength<SIMPLE, 1u, DRT_LIST_CONDUCTOR>(0ull, 0u, 0.0, 0.0, 0.0, r0[k], r1[k], r2[k], on_dot, 0.0, 0.0, 0.0, 0.0, flags, paired);
+                        return bdsf_at_wavelength<SIMPLE, 1u, DRT_LIST_GGX>(0ull, 0u, 0.0, 0.0, 0.0, r0[k], r1[k], r2[k], 0.0, 0.0, 0.0, on_dot, ct, flags, paired);
                     };
                     for (uint32_t l = 0; l < sp.n_lights; l += 1) /* direct_light_contribution, :272-332 */
                     {
@@ -2694,6 +2719,11 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                         {
                             lw0 = readlane64(src, lane0 + off);
                             c = in_lds ? word_as_double(vwords[off + 1u]) : word_as_double(readlane64(src, lane0 + off + 1u));
+                            if (rough)
+                            {
+                                on_dot = in_lds ? word_as_double(vwords[off + 4u]) : word_as_double(readlane64(src, lane0 + off + 4u));
+                                ct = in_lds ? word_as_double(vwords[off + 5u]) : word_as_double(readlane64(src, lane0 + off + 5u));
+                            }
                         }
                         else
                         {
@@ -2701,6 +2731,11 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                             const uint64_t *lp = path_vertex(records, sp.block_words, vw, readlane64(h2, s), readlane64(h3, s), v) + off;
                             lw0 = readlane64(lp[0], 0);
                             c = word_as_double(lp[1]);
+                            if (rough)
+                            {
+                                on_dot = word_as_double(lp[4]);
+                                ct = word_as_double(lp[5]);
+                            }
                         }
                         const uint32_t lflags = (uint32_t)(lw0 >> 16) & 0xFFu;
                         if (!(lflags & FLAG_VISIBLE)) continue;
@@ -2714,6 +2749,11 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                             contribution[k] = contribution[k] * c;                                /* :326-327 */
                         }
                     }
+                    if (rough) /* the sampled direction's mn_dot and ct_coef */
+                    {
+                        on_dot = in_lds ? word_as_double(vwords[7]) : word_as_double(readlane64(src, lane0 + 7));
+                        ct = in_lds ? word_as_double(vwords[8]) : word_as_double(readlane64(src, lane0 + 8));
+                    }
 #pragma unroll
                     for (int k = 0; k < NSETS; k += 1)
                     {
@@ -2724,13 +2764,22 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
                         throughput[k] = throughput[k] * reflectance; /* :469 */
                     }
                 };
+                if (CLOSED)
+                {
+                    /* every list of the scene is covered: a plastic vertex beyond the header's 16 flags, or one of the four fixed kinds */
+                    if (sflags & FLAG_PLASTIC)
+                        plastic_vertex(w1, word_as_double(readlane64(src, lane0 + 4)), word_as_double(readlane64(src, lane0 + 5)), word_as_double(readlane64(src, lane0 + 6)));
+                    else
+                        fixed_vertex(list == DRT_LIST_MIRROR ? 0u : list == DRT_LIST_GLASS ? 1u : list == DRT_LIST_CONDUCTOR ? 2u : 3u);
+                    continue;
+                }
                 if (!shade_const().sp.no_fixed_lists)
                 {
-                    uint32_t kind = 3u;
+                    uint32_t kind = 4u;
                     if (num_bdsfs == 1u && list == DRT_LIST_MIRROR) kind = 0u;
                     if (!SIMPLE && num_bdsfs == 2u && list == DRT_LIST_GLASS) kind = 1u;
                     if (!SIMPLE && num_bdsfs == 1u && list == DRT_LIST_CONDUCTOR) kind = 2u;
-                    if (kind != 3u)
+                    if (kind != 4u)
                     {
                         fixed_vertex(kind);
                         continue;
@@ -2878,8 +2927,34 @@ __global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAV
         }
       }
 
-        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, lane);
+        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, lane, CLOSED);
     }
+}
+
+template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE = false, bool LIST = false>
+__global__ __launch_bounds__(SHADE_BLOCK, (SIMPLE && NSETS == 1) ? DRT_SHADE_WAVES_SIMPLE : SHADE_WAVES_PER_SIMD_FOR(NSETS)) void drt_shade_kernel(DevScene sc, ShadeParams sp, const uint64_t *__restrict__ records,
+                                                                 const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
+                                                                 double *__restrict__ film_avgs, double *__restrict__ film_vars,
+                                                                 unsigned long long *__restrict__ work_counter)
+{
+    shade_pixels<NSETS, SPDS_IN_LDS, XYZ, DARK, SIMPLE, LIST, false>(sc, sp, records, headers, film_pixels, film_avgs, film_vars, work_counter);
+}
+
+/* The closed instantiation (shade_pixels, CLOSED): one wavelength set per lane, SPD tables in LDS, spectral film, dense launches. An
+ * entry point of its own, with the argument list -- so the kernarg layout ShadeConst mirrors -- of drt_shade_kernel, and a bound on
+ * its waves of its own. Four: 108 registers (109 without DARK), nothing spilled. Five (96 registers, six to eight of them in scratch, 28-36 bytes, read
+ * back inside the pixel and sample loops) measured SLOWER than the general instantiation, shade 70.4 -> 71.4 ms on the headline where
+ * four gives 68.6; six spills 27-53 vector registers (DESIGN.md sections 4 and 7). */
+#ifndef DRT_SHADE_WAVES_CLOSED
+#define DRT_SHADE_WAVES_CLOSED 4
+#endif
+template <bool DARK>
+__global__ __launch_bounds__(SHADE_BLOCK, DRT_SHADE_WAVES_CLOSED) void drt_shade_kernel_closed(DevScene sc, ShadeParams sp, const uint64_t *__restrict__ records,
+                                                                 const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
+                                                                 double *__restrict__ film_avgs, double *__restrict__ film_vars,
+                                                                 unsigned long long *__restrict__ work_counter)
+{
+    shade_pixels<1, true, false, DARK, false, false, true>(sc, sp, records, headers, film_pixels, film_avgs, film_vars, work_counter);
 }
 
 /* spectrum_to_xyz over the film (src/daily_ray_trace.c:15-23, src/spectrum.c:49-70): one thread per

@@ -133,6 +133,10 @@ struct drt_context
     bool      dark_skip = true;        /* the shade kernel's instantiation that passes over samples worth 0 in pixels nothing has reached yet */
     bool      no_fixed_lists = false;  /* DRT_NO_FIXED_LISTS, read when the context is created: the shade kernel's fixed-list bodies are not taken */
     bool      simple_bdsfs = false;    /* no material lists anything but bp_diffuse_bdsf, bp_glossy_bdsf, mirror_bdsf: the shade kernel without the Fresnel code */
+    bool      no_closed_shade = false; /* DRT_NO_CLOSED_SHADE, read when the context is created: the closed shade instantiation is not taken */
+    bool      closed_lists = false;    /* every material lists nothing, or exactly one of the lists with straight-line code (closed_lists()): the
+                                          shade kernel without the general list. Decided with simple_bdsfs; a material update keeps every list
+                                          (materials_check), so no later call can change it */
     const double *d_spd_tail = nullptr; /* (held by `allocations`) [n_spd][tail_count]: the SPD table's tail columns */
 
     bool   scene_in_lds = true, spds_in_lds = true, use_bvh = false;
@@ -523,6 +527,28 @@ static uint32_t bdsf_needs(uint32_t b)
     return 0u;
 }
 
+/* Can the closed shade instantiation (csrc/drt_kernels.h, shade_pixels<CLOSED>) replay this scene? Every material -- used by a surface
+ * or not -- must list nothing or exactly one of the five lists that have straight-line code: the two-lobe plastic, {mirror},
+ * {dielectric reflectance, dielectric transmittance}, {smooth conductor}, {rough conductor}. A permutation, a sublist or a superset of
+ * one of them is another list: the general instantiation's. And a material that lists NOTHING must never be shaded: the trace kernel
+ * records a vertex for every hit on a surface whose material is no black body, the general list sums such a vertex to zero, and the
+ * closed code has no form for the empty list (it would take it for the rough conductor or the plastic). So no surface's material may
+ * be one that is no black body and lists nothing (smat: the material of every surface). Surfaces keep their materials and
+ * materials their lists and their is_black_body for a context's life (update_surfaces, materials_check), so this is decided once. */
+static bool closed_lists(const DevMaterial *mats, uint32_t n, const uint32_t *smat, uint32_t n_surf)
+{
+    for (uint32_t i = 0; i < n_surf; i += 1)
+        if (!mats[smat[i]].is_black_body && mats[smat[i]].num_bdsfs == 0u) return false;
+    for (uint32_t i = 0; i < n; i += 1)
+    {
+        const DevMaterial &m = mats[i];
+        const bool one = m.num_bdsfs == 1u && (m.bdsf_packed == DRT_LIST_MIRROR || m.bdsf_packed == DRT_LIST_CONDUCTOR || m.bdsf_packed == DRT_LIST_GGX);
+        const bool two = m.num_bdsfs == 2u && (m.bdsf_packed == DRT_LIST_PLASTIC || m.bdsf_packed == DRT_LIST_GLASS);
+        if (m.num_bdsfs != 0u && !one && !two) return false;
+    }
+    return true;
+}
+
 static int build_device_scene(drt_context *ctx, const drt_scene *scene, double reach)
 {
     const uint32_t S = scene->num_wavelengths;
@@ -798,6 +824,8 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
                 const uint32_t b = mats[i].bdsfs[j];
                 if (b != DRT_BDSF_bp_diffuse_bdsf && b != DRT_BDSF_bp_glossy_bdsf && b != DRT_BDSF_mirror_bdsf) ctx->simple_bdsfs = false;
             }
+        ctx->no_closed_shade = getenv("DRT_NO_CLOSED_SHADE") != nullptr; /* A/B: the general instantiation where the closed one would run */
+        ctx->closed_lists = closed_lists(mats.data(), scene->num_materials, smat.data(), n_surf);
         bool all_simple = true;
         for (uint32_t i = 0; i < n_surf; i += 1)
         {
@@ -830,9 +858,32 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
 
 static bool shade_simple(const drt_context *ctx) { return ctx->simple_bdsfs && ctx->spds_in_lds && ctx->shade_sets == 1; }
 
+/* The closed instantiation is taken for a context's dense launches (an adaptive round's pixel list keeps the general one) when
+ *   - every material's list is covered and no surface's material is a non-black body that lists nothing (closed_lists()), and the
+ *     scene is not SIMPLE's (which is leaner still),
+ *   - neither DRT_NO_CLOSED_SHADE nor DRT_NO_FIXED_LISTS was set when the context was created,
+ *   - the S wavelengths are one set per lane (with or without a packed tail) and the SPD table is in LDS,
+ *   - the film is spectral (the XYZ film keeps the general instantiation).
+ * Nothing else is asked: lights beyond the first, vertices beyond the prefetched records and records wider than a register go through
+ * plastic_vertex's and fixed_vertex's own block-by-block paths, which the closed code keeps. */
+static bool shade_closed(const drt_context *ctx)
+{
+    return ctx->closed_lists && !ctx->no_closed_shade && !ctx->no_fixed_lists && !shade_simple(ctx) && ctx->spds_in_lds && ctx->shade_sets == 1 && !ctx->xyz_mode;
+}
+
 template <int NSETS, bool XYZ, bool LIST>
 static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams &sp, double *const film[3])
 {
+    if (NSETS == 1 && !XYZ && !LIST && shade_closed(ctx))
+    {
+#define DRT_LAUNCH_CLOSED(DARK)                                                                                                                    \
+    hipLaunchKernelGGL((drt_shade_kernel_closed<DARK>), dim3(grid), dim3(SHADE_BLOCK), ctx->shade_lds, ctx->stream, ctx->dsc, sp, ctx->d_records, \
+                       ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
+        if (ctx->dark_skip) DRT_LAUNCH_CLOSED(true);
+        else DRT_LAUNCH_CLOSED(false);
+#undef DRT_LAUNCH_CLOSED
+        return 0;
+    }
 #define DRT_LAUNCH_SHADE(LDS, DARK, SIMPLE)                                                                                                       \
     hipLaunchKernelGGL((drt_shade_kernel<NSETS, LDS, XYZ, DARK, SIMPLE, LIST>), dim3(grid), dim3(SHADE_BLOCK), ctx->shade_lds, ctx->stream, ctx->dsc, sp, \
                        ctx->d_records, ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
@@ -939,7 +990,11 @@ template <int NSETS, bool XYZ>
 static int shade_occupancy_mode(drt_context *ctx, int *per_cu)
 {
     /* (the DARK instantiations have the same registers and LDS) */
-    if (NSETS == 1 && shade_simple(ctx))
+    /* (a closed context's adaptive rounds launch the general LIST instantiation on the same grid cap: both are bound at four waves;
+     * were the bounds to differ, blocks beyond what is resident would only queue behind the persistent ones and find the work gone) */
+    if (NSETS == 1 && !XYZ && shade_closed(ctx))
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, drt_shade_kernel_closed<true>, SHADE_BLOCK, ctx->shade_lds));
+    else if (NSETS == 1 && shade_simple(ctx))
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, drt_shade_kernel<NSETS, true, XYZ, true, (NSETS == 1)>, SHADE_BLOCK, ctx->shade_lds));
     else if (ctx->spds_in_lds)
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, drt_shade_kernel<NSETS, true, XYZ, true>, SHADE_BLOCK, ctx->shade_lds));
@@ -1876,6 +1931,13 @@ extern "C" int drt_get_stats(drt_context *ctx, drt_stats *out)
 }
 
 extern "C" uint32_t drt_batch_spp(drt_context *ctx) { return ctx ? ctx->batch_spp : 0; }
+
+extern "C" int drt_shade_instantiation(const drt_context *ctx)
+{
+    if (!ctx) return -1;
+    if (shade_closed(ctx)) return DRT_SHADE_CLOSED;
+    return shade_simple(ctx) ? DRT_SHADE_SIMPLE : DRT_SHADE_GENERAL;
+}
 
 /*
  * Adaptive sampling ("Adaptive sampling"). Round 0 renders samples [0, min_spp) of every tile pixel through the dense

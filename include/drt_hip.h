@@ -253,6 +253,17 @@ int drt_get_stats(drt_context *ctx, drt_stats *out);
 /* Samples per pixel one trace+shade kernel pair processes (the launch granularity); 0 on error. */
 uint32_t drt_batch_spp(drt_context *ctx);
 
+/* Which instantiation of the shade kernel the context's dense launches run (read-only; -1: ctx is null). GENERAL has the general BDSF
+ * list; SIMPLE is for scenes that list nothing but bp_diffuse_bdsf, bp_glossy_bdsf and mirror_bdsf; CLOSED is for scenes whose every
+ * material lists nothing or exactly one of the lists that have straight-line code (two-lobe plastic, mirror, glass pair, smooth
+ * conductor, rough conductor) and no surface has a material that is no black body and lists nothing, on a spectral film with one wavelength set per lane and the SPD table in LDS. Decided when the context
+ * is created (DRT_NO_SIMPLE_SHADE, DRT_NO_CLOSED_SHADE and DRT_NO_FIXED_LISTS are read there); material updates keep every list, so it
+ * holds for the context's life. All three compute the same film, bit for bit. */
+#define DRT_SHADE_GENERAL 0
+#define DRT_SHADE_SIMPLE 1
+#define DRT_SHADE_CLOSED 2
+int drt_shade_instantiation(const drt_context *ctx);
+
 /*
  * One-shot form matching the reference's loop: host buffers, caller-owned,
  * accumulated INTO (so the caller zero-fills them, as alloc() does in the reference).
