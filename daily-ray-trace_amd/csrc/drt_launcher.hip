@@ -6,6 +6,7 @@
 #include "drt_kernels.h"
 #include "drt_bvh_kernels.h"
 #include "drt_adaptive_kernels.h"
+#include "drt_sample_map_kernels.h"
 #include "drt_denoise_kernels.h"
 #include "drt_feature_kernels.h"
 #include "drt_matte_kernels.h"
@@ -251,6 +252,11 @@ struct drt_context
     uint32_t  n_cuts = 0, cut_depth[DRT_MAX_DEPTH_CUTS] = {};
     struct CutFilms { DevBuf<double> pixels[DRT_MAX_DEPTH_CUTS], avgs[DRT_MAX_DEPTH_CUTS], vars[DRT_MAX_DEPTH_CUTS]; } cuts;
     int       depth_grid_cap = 1;
+    /* sample maps (drt_render_sample_map; drt_sample_map_kernels.h): the call's remainders, host targets on their way to the adopt
+     * kernel, the report and its pinned copy -- a set of its own, whole or absent like the adaptive one it is used with */
+    DevBuf<uint32_t> d_sm_rem, d_sm_targets, d_sm_report;
+    PinnedBuf<uint32_t> h_sm_report;
+    uint32_t  sm_bits = 0;                 /* the rounds of the call in progress that are still to be enqueued: bits of this device's B */
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
 };
 
@@ -2058,6 +2064,19 @@ static int adaptive_begin(drt_context *ctx, const drt_adaptive *a)
     return enqueue_converge(ctx);
 }
 
+/* the kernel pairs of a round that renders k samples of each of n_in listed pixels: m samples and P pixels per pair. A pair takes up
+ * to five eighths of the paths the record pool is sized for and at most 4096 samples of a pixel; pairs of equal size */
+struct RoundPairs { uint32_t m; uint64_t P; };
+static RoundPairs round_pairs(const drt_context *ctx, uint32_t k, uint64_t n_in)
+{
+    const uint64_t budget = std::max<uint64_t>(1, ctx->n_pix * (uint64_t)ctx->batch_spp * 5 / 8);
+    const uint32_t m_fit = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, budget), 4096);
+    const uint32_t n_sp = (k + m_fit - 1) / m_fit, m = (k + n_sp - 1) / n_sp;   /* samples per pair */
+    const uint64_t p_fit = std::max<uint64_t>(1, budget / m);
+    const uint64_t n_pp = (n_in + p_fit - 1) / p_fit, P = (n_in + n_pp - 1) / n_pp; /* pixels per pair */
+    return {m, P};
+}
+
 /* a later round: the next k samples of the ad.active pixels of list d_alist[cur] -- each from the count it holds, d_counts -- in kernel
  * pairs over ranges of the list. k: min(step, max_spp - n) while all active pixels hold n samples, step otherwise (the contract). A pair
  * takes up to five eighths of the paths the record pool is sized for (the pixels still active are the ones with the long paths: a
@@ -2069,11 +2088,9 @@ static int adaptive_enqueue_round(drt_context *ctx)
     ad.n_in = ad.active;
     ad.k = ad.same ? std::min(ad.a.step, ad.a.max_spp - ad.n) : ad.a.step;
     if (ad.same) ad.n += ad.k;
-    const uint64_t budget = std::max<uint64_t>(1, ctx->n_pix * (uint64_t)ctx->batch_spp * 5 / 8);
-    const uint32_t m_fit = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(ad.k, budget), 4096);
-    const uint32_t n_sp = (ad.k + m_fit - 1) / m_fit, m = (ad.k + n_sp - 1) / n_sp;   /* samples per pair */
-    const uint64_t p_fit = std::max<uint64_t>(1, budget / m);
-    const uint64_t n_pp = (ad.n_in + p_fit - 1) / p_fit, P = (ad.n_in + n_pp - 1) / n_pp; /* pixels per pair */
+    const RoundPairs rp = round_pairs(ctx, ad.k, ad.n_in);
+    const uint32_t m = rp.m;
+    const uint64_t P = rp.P;
     const uint32_t *list = ctx->d_alist[ad.cur];
     for (uint64_t off = 0; off < ad.n_in; off += P)
     {
@@ -2735,6 +2752,331 @@ extern "C" int drt_group_read_sample_counts(drt_group *g, uint32_t *counts)
         if (rc) return rc;
     }
     return group_gather_rows(g, counts, (size_t)g->tile_w * sizeof(uint32_t), &drt_context::d_counts);
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Sample maps (the kernels in drt_sample_map_kernels.h)                      */
+
+/*
+ * drt_render_sample_map in steps, so that a group takes each of them on all its devices before the next: map_check, map_adopt (the
+ * film complete, counts and remainders of every tile pixel, the report on its way to the host), map_report (the report's words
+ * combined; its two refusals), map_accept (the context becomes an adaptive render's and the first round's list is enqueued),
+ * then per round map_enqueue_round and map_finish_round. Until map_accept nothing is rendered and no film bit changes.
+ * A round is its kernel pairs over ranges of the list and, behind them, the NEXT round's select + scan + scatter (after the last round:
+ * a select that keeps nothing, which leaves the counts current and the list empty): one host wait per round, and one before the first
+ * for its list's length. The select does nothing when a pair ran out of records; the finish renders those pairs again and reruns it.
+ */
+struct MapReport { uint32_t bits = 0, max_count = 0, rendered = 0, above = 0; uint64_t paths = 0; };
+
+static int map_check(const drt_context *ctx, const drt_sample_map *m, bool group)
+{
+    if (!ctx || !m || !m->targets) return fail(-1, "null argument");
+    if (m->flags & ~(DRT_MAP_DEVICE | DRT_MAP_ADD)) return fail(-1, "flags %u: DRT_MAP_DEVICE and DRT_MAP_ADD are defined", m->flags);
+    if (group && (m->flags & DRT_MAP_DEVICE)) return fail(-1, "a group takes the map from host memory (DRT_MAP_DEVICE is per context)");
+    if (ctx->n_cuts) return fail(-4, "sample maps with depth cuts bound are not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
+    if (ctx->xyz_mode) return fail(-4, "sample maps need the spectral film (the DRT_MODE_XYZ film keeps no filter sum per pixel)");
+    if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "sample maps do not record hit indices (DRT_FLAG_RECORD_HITS)");
+    if (ctx->n_pix > 0xFFFFFFFFull) return fail(-1, "sample maps list pixels in 32 bits: the tile has %llu", (unsigned long long)ctx->n_pix);
+    return 0;
+}
+
+/* what a call made is given up when the call is refused: a refusal leaves the process's live resources as they were */
+struct MapMade { bool adaptive = false, map = false; };
+
+static void map_drop(drt_context *ctx, const MapMade &made)
+{
+    if (made.adaptive)
+    {
+        for (DevBuf<uint32_t> *b : {&ctx->d_counts, &ctx->d_alist[0], &ctx->d_alist[1], &ctx->d_bkeep, &ctx->d_ainfo}) b->reset();
+        ctx->d_keep.reset();
+        ctx->h_active.reset();
+    }
+    if (made.map)
+    {
+        for (DevBuf<uint32_t> *b : {&ctx->d_sm_rem, &ctx->d_sm_targets, &ctx->d_sm_report}) b->reset();
+        ctx->h_sm_report.reset();
+    }
+}
+
+static int map_alloc(drt_context *ctx)
+{
+    HIP_TRY(ctx->d_sm_rem.need(ctx->n_pix));
+    HIP_TRY(ctx->d_sm_targets.need(ctx->n_pix));
+    HIP_TRY(ctx->d_sm_report.need(MAP_WORDS));
+    HIP_TRY(ctx->h_sm_report.need(MAP_WORDS));
+    return 0;
+}
+
+/* targets: device memory on the context's device (the caller's, or d_sm_targets filled by the caller of this function) */
+static int map_adopt(drt_context *ctx, const uint32_t *host_targets, const uint32_t *dev_targets, uint32_t flags, MapMade *made)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    (void)hipGetLastError();
+    int rc = drt_synchronize(ctx); /* the film complete: samples of an earlier call that ran out of records are rendered again here */
+    if (rc) return rc;
+    made->adaptive = !ctx->h_active;
+    made->map = !ctx->h_sm_report; /* the last of the set, which is whole or absent */
+    if ((rc = adaptive_buffers(ctx))) { made->adaptive = false; return rc; } /* (all or none already) */
+    if (made->map && (rc = map_alloc(ctx)))
+    {
+        map_drop(ctx, *made);
+        return rc;
+    }
+    HIP_TRY(hipMemsetAsync(ctx->d_sm_report, 0xFF, 2 * sizeof(uint32_t), ctx->stream)); /* MAP_BAD, MAP_OVER */
+    HIP_TRY(hipMemsetAsync(ctx->d_sm_report + 2, 0, (MAP_WORDS - 2) * sizeof(uint32_t), ctx->stream));
+    if (host_targets)
+    {
+        /* (the caller's memory stays as it is until map_report has waited for the stream) */
+        HIP_TRY(hipMemcpyAsync(ctx->d_sm_targets, host_targets, ctx->n_pix * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        dev_targets = ctx->d_sm_targets;
+    }
+    const uint32_t n_blocks = (uint32_t)((ctx->n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK);
+    hipLaunchKernelGGL(drt_map_adopt_kernel, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, (const double *)ctx->d_pixels, ctx->dsc.S,
+                       (uint32_t)ctx->n_pix, dev_targets, (flags & DRT_MAP_ADD) ? 1u : 0u, ctx->d_counts.get(), ctx->d_sm_rem.get(),
+                       ctx->d_sm_report.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_sm_report, ctx->d_sm_report, MAP_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static int map_report(drt_context *ctx, MapReport *r)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint32_t *w = ctx->h_sm_report;
+    const uint32_t W = ctx->params.tile_w;
+    if (w[MAP_BAD] != 0xFFFFFFFFu)
+    {
+        const uint32_t bad = w[MAP_BAD];
+        double f = 0.0;
+        HIP_TRY(hipMemcpy(&f, ctx->d_pixels + (size_t)bad * (ctx->dsc.S + 1) + ctx->dsc.S, sizeof(f), hipMemcpyDeviceToHost));
+        return fail(-7, "tile pixel %u (column %u, row %u of the tile) holds the filter sum %g: a sample count is a whole number from 0 to 2^32 - 1",
+                    bad, bad % W, bad / W, f);
+    }
+    if (w[MAP_OVER] != 0xFFFFFFFFu)
+    {
+        const uint32_t at = w[MAP_OVER];
+        uint32_t n = 0;
+        HIP_TRY(hipMemcpy(&n, ctx->d_counts + at, sizeof(n), hipMemcpyDeviceToHost));
+        return fail(-1, "tile pixel %u (column %u, row %u of the tile) holds %u samples and DRT_MAP_ADD asks for more than the %u that take it to 2^32 - 1",
+                    at, at % W, at / W, n, 0xFFFFFFFFu - n);
+    }
+    r->bits |= w[MAP_BITS];
+    r->max_count = std::max(r->max_count, w[MAP_MAX]);
+    r->rendered += w[MAP_RENDERED];
+    r->above += w[MAP_ABOVE];
+    r->paths += (uint64_t)w[MAP_PATHS] | ((uint64_t)w[MAP_PATHS + 1] << 32);
+    return 0;
+}
+
+/* select + scan + scatter for round b over every tile pixel, the list to d_alist[cur ^ 1], its length on its way to h_active */
+static int map_enqueue_select(drt_context *ctx, uint32_t b)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    const uint32_t n_pix = (uint32_t)ctx->n_pix;
+    const uint32_t n_blocks = (uint32_t)((ctx->n_pix + CONVERGE_BLOCK - 1) / CONVERGE_BLOCK);
+    ConvergeParams cp{};
+    cp.list_in = nullptr;
+    cp.n_in = n_pix;
+    cp.counts = ctx->d_counts;
+    cp.keep_mask = ctx->d_keep;
+    cp.block_keep = ctx->d_bkeep;
+    cp.active = ctx->d_bkeep + n_blocks;
+    cp.list_out = ctx->d_alist[ad.cur ^ 1];
+    cp.overflow = (const uint32_t *)(ctx->d_counters + DRT_NUM_COUNTERS + 5);
+    cp.pixels = ctx->d_pixels;
+    hipLaunchKernelGGL(drt_map_select_kernel, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, (const double *)ctx->d_pixels, ctx->dsc.S, n_pix,
+                       (const uint32_t *)ctx->d_sm_rem, b, cp.counts, cp.keep_mask, cp.block_keep, cp.overflow);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(drt_converge_scan, dim3(1), dim3(CONVERGE_SCAN_BLOCK), 0, ctx->stream, cp, n_blocks);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(drt_converge_scatter, dim3(n_blocks), dim3(CONVERGE_BLOCK), 0, ctx->stream, cp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(ctx->h_active, cp.active, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return 0;
+}
+
+static uint32_t lowest_bit(uint32_t bits) { return bits ? (uint32_t)__builtin_ctz(bits) : 32u; }
+
+/* the context becomes an adaptive render's, its counts the adopted ones; a device with rounds to run gets its first list enqueued */
+static int map_accept(drt_context *ctx)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    const int cur = ctx->adaptive_done ? ad.cur : 1;
+    ctx->adaptive_done = true;
+    ad = drt_context::Adaptive{};
+    ad.cur = cur;
+    ad.first = false;
+    ctx->sm_bits = ctx->h_sm_report[MAP_BITS];
+    if (!ctx->sm_bits) return 0; /* nothing to render: the list stays empty (ad.active == 0) */
+    HIP_TRY(hipSetDevice(ctx->device));
+    return map_enqueue_select(ctx, lowest_bit(ctx->sm_bits));
+}
+
+/* the list's length (the wait before the first round) */
+static int map_first_list(drt_context *ctx)
+{
+    if (!ctx->sm_bits) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->ad.active = *ctx->h_active;
+    ctx->ad.cur ^= 1;
+    return 0;
+}
+
+/* the round of the lowest bit left: 2^b samples of the listed pixels, each from the count it holds, then the next round's list */
+static int map_enqueue_round(drt_context *ctx)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t b = lowest_bit(ctx->sm_bits);
+    ctx->sm_bits &= ctx->sm_bits - 1u;
+    ad.n_in = ad.active;
+    ad.k = 1u << b;
+    const RoundPairs rp = round_pairs(ctx, ad.k, ad.n_in);
+    const uint32_t *list = ctx->d_alist[ad.cur];
+    for (uint64_t off = 0; off < ad.n_in; off += rp.P)
+    {
+        const uint64_t len = std::min<uint64_t>(rp.P, ad.n_in - off);
+        for (uint32_t at = 0; at < ad.k; at += rp.m)
+        {
+            int rc = 0;
+            /* the pending timing events stay bounded (a round of 2^31 samples is half a million pairs): the counts and the list are
+             * the round's until its select runs, so pairs redone here start where they started */
+            if (ctx->ev_used >= 3 * 256 && (rc = drt_synchronize(ctx))) return rc;
+            const uint32_t ns = std::min(rp.m, ad.k - at);
+            if ((rc = enqueue_pair(ctx, at, ns, 0, 0, 0, ns, list + off, len))) return rc;
+        }
+    }
+    return map_enqueue_select(ctx, lowest_bit(ctx->sm_bits));
+}
+
+/* the round's one wait; pairs whose record pool ran out are rendered again (drt_synchronize) and the select they held back rerun */
+static int map_finish_round(drt_context *ctx)
+{
+    drt_context::Adaptive &ad = ctx->ad;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint64_t redone = ctx->redone_batches;
+    int rc = drt_synchronize(ctx);
+    if (rc) return rc;
+    if (ctx->redone_batches != redone)
+    {
+        if ((rc = map_enqueue_select(ctx, lowest_bit(ctx->sm_bits)))) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    ad.active = *ctx->h_active;
+    ad.cur ^= 1;
+    return 0;
+}
+
+static void map_fill(drt_sample_map *m, const MapReport &r)
+{
+    m->rounds = (uint32_t)__builtin_popcount(r.bits);
+    m->pixels_rendered = r.rendered;
+    m->pixels_above = r.above;
+    m->max_count = r.max_count;
+    m->paths = r.paths;
+}
+
+extern "C" int drt_render_sample_map(drt_context *ctx, drt_sample_map *m)
+{
+    g_last_error.clear();
+    int rc = map_check(ctx, m, false);
+    if (rc) return rc;
+    const bool device = (m->flags & DRT_MAP_DEVICE) != 0;
+    if (device)
+    {
+        HIP_TRY(hipSetDevice(ctx->device));
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, m->targets) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device)
+        {
+            (void)hipGetLastError();
+            return fail(-1, "DRT_MAP_DEVICE: targets is not device memory on the context's device %d", ctx->device);
+        }
+    }
+    const drt_context::Adaptive before = ctx->ad;
+    MapMade made;
+    MapReport r;
+    if ((rc = map_adopt(ctx, device ? nullptr : m->targets, device ? m->targets : nullptr, m->flags, &made)) || (rc = map_report(ctx, &r)))
+    {
+        const std::string keep = g_last_error;
+        (void)hipStreamSynchronize(ctx->stream);
+        map_drop(ctx, made);
+        ctx->ad = before;
+        g_last_error = keep;
+        return rc;
+    }
+    if ((rc = map_accept(ctx)) || (rc = map_first_list(ctx))) return rc;
+    while (ctx->sm_bits)
+    {
+        if ((rc = map_enqueue_round(ctx))) return rc;
+        if ((rc = map_finish_round(ctx))) return rc;
+    }
+    map_fill(m, r);
+    return 0;
+}
+
+/* every device its own rows of the map and its own rounds, side by side; all the checks, the adoption included, before any renders */
+extern "C" int drt_group_render_sample_map(drt_group *g, drt_sample_map *m)
+{
+    g_last_error.clear();
+    if (!g || !m) return fail(-1, "null argument");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = map_check(c, m, true))) return rc;
+    const size_t n = g->ctx.size();
+    std::vector<drt_context::Adaptive> before;
+    for (drt_context *c : g->ctx) before.push_back(c ? c->ad : drt_context::Adaptive{});
+    std::vector<MapMade> made(n);
+    auto refuse = [&](int code)
+    {
+        const std::string keep = g_last_error;
+        for (size_t k = 0; k < n; k += 1)
+            if (drt_context *c = g->ctx[k])
+            {
+                (void)hipSetDevice(c->device);
+                (void)hipStreamSynchronize(c->stream);
+                map_drop(c, made[k]);
+                c->ad = before[k];
+            }
+        g_last_error = keep;
+        return code;
+    };
+    /* device k of n holds rows k, k + n, ... of the tile: its targets contiguously, in a vector that lives until the reports are in */
+    std::vector<std::vector<uint32_t>> rows(n);
+    for (size_t k = 0; k < n; k += 1)
+    {
+        drt_context *c = g->ctx[k];
+        if (!c) continue;
+        rows[k].resize((size_t)g->rows[k] * g->tile_w);
+        for (uint32_t r = 0; r < g->rows[k]; r += 1)
+            memcpy(rows[k].data() + (size_t)r * g->tile_w, m->targets + ((size_t)r * n + k) * g->tile_w, (size_t)g->tile_w * sizeof(uint32_t));
+        if ((rc = map_adopt(c, rows[k].data(), nullptr, m->flags, &made[k]))) return refuse(rc);
+    }
+    MapReport r;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = map_report(c, &r))) return refuse(rc);
+    for (drt_context *c : g->ctx)
+        if (c && (rc = map_accept(c))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = map_first_list(c))) return rc;
+    std::vector<char> running(n, 0);
+    for (;;)
+    {
+        bool any = false;
+        for (size_t k = 0; k < n; k += 1)
+        {
+            running[k] = g->ctx[k] && g->ctx[k]->sm_bits;
+            if (running[k] && (rc = map_enqueue_round(g->ctx[k]))) return rc;
+            any = any || running[k];
+        }
+        if (!any) break;
+        for (size_t k = 0; k < n; k += 1)
+            if (running[k] && (rc = map_finish_round(g->ctx[k]))) return rc;
+    }
+    map_fill(m, r);
+    return 0;
 }
 
 /* ---------------------------------------------------------------------------------------------- */

@@ -84,6 +84,7 @@ typedef struct
  * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS. */
 #define DRT_HOST_MAX_PICKS 64
 #define DRT_HOST_MAX_LEVELS 64
+#define DRT_HOST_MAX_REGIONS 64
 typedef struct
 {
     int32_t  device;
@@ -144,6 +145,12 @@ typedef struct
      * or DRT_LIGHT_LEVELS. 0 cuts: off */
     uint32_t n_depth_cuts;
     uint32_t depth_cuts[DRT_MAX_DEPTH_CUTS];
+    /* DRT_REGIONS="x,y,w,h:spp;...": a sample map (drt_group_render_sample_map) of num_pixel_samples everywhere and, inside a region
+     * (clipped to the image), the largest spp of the regions that cover the pixel. The three standard outputs through the standard
+     * writer, and <output_spd>.counts.bmp: every pixel's count over the largest, as a grey picture. Not combined with adaptive sampling,
+     * checkpoints or resuming, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS or DRT_PROJECTION. 0 regions: off */
+    uint32_t n_regions;
+    uint32_t regions[DRT_HOST_MAX_REGIONS][5]; /* x, y, w, h, spp */
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u

@@ -449,6 +449,35 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
                    (unsigned long long)a.paths, (unsigned long long)p.spp * num_pixels, 100.0 * (f64)a.paths / ((f64)p.spp * (f64)num_pixels),
                    a.pixels_at_max, (unsigned long long)num_pixels, p.spp);
     }
+    /* DRT_REGIONS: one sample map over the whole image, num_pixel_samples and inside the regions the largest spp that covers the pixel */
+    u32 map_max = 0;
+    if (!rc && opt && opt->n_regions)
+    {
+        u32 *targets = (u32 *)malloc(num_pixels * sizeof(u32));
+        if (!targets) rc = -3;
+        if (!rc)
+        {
+            for (u64 px = 0; px < num_pixels; px += 1) targets[px] = p.spp;
+            for (u32 k = 0; k < opt->n_regions; k += 1)
+            {
+                const u32 *r = opt->regions[k];
+                const u64 x1 = (u64)r[0] + r[2] < width ? (u64)r[0] + r[2] : width, y1 = (u64)r[1] + r[3] < height ? (u64)r[1] + r[3] : height;
+                for (u64 y = r[1]; y < y1; y += 1)
+                    for (u64 x = r[0]; x < x1; x += 1)
+                        if (targets[y * width + x] < r[4]) targets[y * width + x] = r[4];
+            }
+            drt_sample_map map;
+            memset(&map, 0, sizeof(map));
+            map.targets = targets;
+            rc = drt_group_render_sample_map(ctx, &map);
+            map_max = map.max_count;
+            if (!rc) done = map.max_count;
+            if (!rc && !opt->quiet)
+                printf("Sample map: %u regions, %u rounds, %llu paths traced, %u samples at most\n", opt->n_regions, map.rounds,
+                       (unsigned long long)map.paths, map.max_count);
+        }
+        free(targets);
+    }
     u32 step = (opt && opt->checkpoint_spp) ? opt->checkpoint_spp : p.spp;
     while (!rc && done < p.spp)
     {
@@ -660,8 +689,27 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         w4 = publish_mattes(config->output_spd, hs, width, height, mt_ids, mt_counts, mt_tail);
         if (w4) fprintf(stderr, "render_image: could not write the matte outputs\n");
     }
+    int w5 = 0;
+    if (!(w0 || w1 || w2 || w3 || w4) && opt && opt->n_regions)
+    {
+        /* DRT_REGIONS: every pixel's count (its filter sum) over the largest, grey */
+        char path[80], tmp[84];
+        u8 *fb = (u8 *)malloc(num_pixels * 4 + 4);
+        snprintf(path, sizeof(path), "%s.counts.bmp", config->output_spd);
+        snprintf(tmp, sizeof(tmp), "%s.tmp", path);
+        if (!fb) w5 = -1;
+        for (u64 px = 0; !w5 && px < num_pixels; px += 1)
+        {
+            const u8 v = (u8)(255.0 * dst_pixels[px * (S + 1) + S] / (f64)map_max + 0.5);
+            fb[px * 4 + 0] = fb[px * 4 + 1] = fb[px * 4 + 2] = v;
+            fb[px * 4 + 3] = 255;
+        }
+        if (!w5 && (drt_host_write_bmp_bgra(tmp, width, height, fb) != 0 || rename(tmp, path) != 0)) w5 = -1;
+        free(fb);
+        if (w5) fprintf(stderr, "render_image: could not write the picture of the sample counts\n");
+    }
     /* post-process like the reference's main(): each film -> linear RGB -> BMP (src/win32_main.c:150-152) */
-    if (!(w0 || w1 || w2 || w3 || w4))
+    if (!(w0 || w1 || w2 || w3 || w4 || w5))
     {
         int bad = 0;
         for (int k = 0; k < 3; k += 1)
@@ -681,7 +729,7 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     free(dst_avgs);
     free(dst_pixels);
     drt_host_free_scene(hs);
-    return (w0 || w1 || w2 || w3 || w4 || cut_bad) ? -2 : 0;
+    return (w0 || w1 || w2 || w3 || w4 || w5 || cut_bad) ? -2 : 0;
 }
 
 /* a whole-string number from the environment: 0 and *out set, -1 (and a message naming the variable) when it does not parse */
@@ -982,6 +1030,59 @@ static int depth_cuts_options(const config_arguments *config, drt_host_options *
     return 0;
 }
 
+/* DRT_REGIONS="x,y,w,h:spp;x,y,w,h:spp;..." (whole numbers; DRT_HOST_MAX_REGIONS regions at most; a region has a size, begins inside
+ * the image and asks for num_pixel_samples or more): parsed and checked here, before any device call. */
+static int regions_options(const config_arguments *config, drt_host_options *opt)
+{
+    opt->n_regions = 0;
+    const char *e = getenv("DRT_REGIONS");
+    if (!e) return 0;
+    static const char *const others[] = { "DRT_ADAPTIVE_ERROR", "DRT_CHECKPOINT_SPP", "DRT_RESUME", "DRT_TURNTABLE", "DRT_LIGHT_LEVELS", "DRT_DEPTH_CUTS", "DRT_PROJECTION" };
+    for (size_t k = 0; k < sizeof(others) / sizeof(others[0]); k += 1)
+        if (getenv(others[k])) { fprintf(stderr, "render_image: DRT_REGIONS cannot be combined with %s\n", others[k]); return -1; }
+    static const char seps[4] = { ',', ',', ',', ':' };
+    for (const char *c = e;;)
+    {
+        unsigned long long v[5];
+        const char *end = c;
+        int ok = 1;
+        for (int k = 0; ok && k < 5; k += 1)
+        {
+            char *stop = NULL;
+            ok = *end >= '0' && *end <= '9';
+            if (!ok) break;
+            v[k] = strtoull(end, &stop, 10);
+            end = stop;
+            ok = v[k] <= 0xFFFFFFFFull && (k == 4 || *end == seps[k]);
+            if (ok && k < 4) end += 1;
+        }
+        if (!ok || (*end && *end != ';'))
+        { fprintf(stderr, "render_image: DRT_REGIONS=\"%s\": regions x,y,w,h:spp of whole numbers, separated by semicolons\n", e); return -1; }
+        if (opt->n_regions == DRT_HOST_MAX_REGIONS) { fprintf(stderr, "render_image: DRT_REGIONS: %d regions at most\n", DRT_HOST_MAX_REGIONS); return -1; }
+        if (v[2] == 0 || v[3] == 0)
+        { fprintf(stderr, "render_image: DRT_REGIONS: region %u (%llu,%llu,%llu,%llu) has no size\n", opt->n_regions, v[0], v[1], v[2], v[3]); return -1; }
+        if (v[0] >= config->output_width || v[1] >= config->output_height)
+        {
+            fprintf(stderr, "render_image: DRT_REGIONS: region %u (%llu,%llu,%llu,%llu) lies outside the %u x %u image\n", opt->n_regions, v[0], v[1], v[2], v[3],
+                    config->output_width, config->output_height);
+            return -1;
+        }
+        if (v[4] == 0 || v[4] < config->num_pixel_samples)
+        {
+            fprintf(stderr, "render_image: DRT_REGIONS: region %u asks for %llu samples: num_pixel_samples (%u) or more\n", opt->n_regions, v[4],
+                    config->num_pixel_samples);
+            return -1;
+        }
+        for (int k = 0; k < 5; k += 1) opt->regions[opt->n_regions][k] = (u32)v[k];
+        opt->n_regions += 1;
+        if (!*end) break;
+        c = end + 1;
+    }
+    if (strlen(config->output_spd) + strlen(".counts.bmp") > 63)
+    { fprintf(stderr, "render_image: DRT_REGIONS: the output name with .counts.bmp behind it is longer than 63 characters\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -1015,5 +1116,6 @@ void render_image(config_arguments *config)
     if (turntable_options(&opt) != 0) exit(-1);
     if (light_levels_options(&opt) != 0) exit(-1);
     if (depth_cuts_options(config, &opt) != 0) exit(-1);
+    if (regions_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

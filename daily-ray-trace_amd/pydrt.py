@@ -95,6 +95,65 @@ def make_adaptive(min_spp, max_spp, step, rel_error, floor=0.0):
     return a
 
 
+MAP_DEVICE, MAP_ADD = 1, 2  # DRT_MAP_DEVICE, DRT_MAP_ADD
+
+
+class SampleMap(C.Structure):
+    """drt_sample_map (include/drt_hip.h): the targets and flags of a sample-map render and, after it, its report."""
+    _fields_ = [("targets", C.c_void_p), ("flags", C.c_uint32), ("rounds", C.c_uint32), ("pixels_rendered", C.c_uint32),
+                ("pixels_above", C.c_uint32), ("max_count", C.c_uint32), ("paths", C.c_uint64)]
+
+
+def _map_report(m):
+    return {"rounds": m.rounds, "paths": m.paths, "pixels_rendered": m.pixels_rendered, "pixels_above": m.pixels_above,
+            "max_count": m.max_count}
+
+
+def _map_u32(targets, tile_w, tile_h, name):
+    """a host map as a contiguous uint32 array [tile_h * tile_w]: any integer dtype, every value in [0, 2^32), (tile_h, tile_w) or flat"""
+    a = np.asarray(targets)
+    if a.dtype.kind not in "iu":
+        raise ValueError("%s: the targets are integers, not %s" % (name, a.dtype))
+    if a.shape != (tile_h, tile_w) and a.shape != (tile_h * tile_w,):
+        raise ValueError("%s: targets of shape (%d, %d) or (%d,), not %s" % (name, tile_h, tile_w, tile_h * tile_w, a.shape))
+    if a.size and a.dtype != np.uint32:
+        lo, hi = int(a.min()), int(a.max())
+        if lo < 0:
+            raise ValueError("%s: a target is negative (%d)" % (name, lo))
+        if hi > 0xFFFFFFFF:
+            raise ValueError("%s: a target is above 2^32 - 1 (%d)" % (name, hi))
+    return np.ascontiguousarray(a.reshape(-1), dtype=np.uint32)
+
+
+def region_map(tile_w, tile_h, base, regions):
+    """A sample map [tile_h][tile_w] (uint32): `base` everywhere, and inside every region (x, y, w, h, spp) -- clipped to the tile -- the
+    largest spp of the regions that cover the pixel, where that is above base."""
+    tile_w, tile_h, base = int(tile_w), int(tile_h), int(base)
+    if tile_w < 1 or tile_h < 1 or not 0 <= base <= 0xFFFFFFFF:
+        raise ValueError("region_map: a tile of at least one pixel and a base in [0, 2^32)")
+    m = np.full((tile_h, tile_w), base, dtype=np.uint32)
+    for x, y, w, h, spp in regions:
+        x, y, w, h, spp = int(x), int(y), int(w), int(h), int(spp)
+        if w < 0 or h < 0 or not 0 <= spp <= 0xFFFFFFFF:
+            raise ValueError("region_map: a region's size is not negative and its spp is in [0, 2^32)")
+        x0, y0, x1, y1 = max(x, 0), max(y, 0), min(x + w, tile_w), min(y + h, tile_h)
+        if x1 > x0 and y1 > y0:
+            m[y0:y1, x0:x1] = np.maximum(m[y0:y1, x0:x1], np.uint32(spp))
+    return m
+
+
+def coverage_map(coverage, base, extra):
+    """A sample map of the shape of `coverage` (a read_matte buffer, values in [0, 1]): base + ceil(extra * coverage), uint32."""
+    c = np.asarray(coverage, dtype=np.float64)
+    base, extra = int(base), int(extra)
+    if base < 0 or extra < 0 or not np.all((c >= 0.0) & (c <= 1.0)):
+        raise ValueError("coverage_map: base and extra are not negative and the coverage lies in [0, 1]")
+    m = np.ceil(np.float64(extra) * c) + np.float64(base)
+    if m.size and m.max() > 0xFFFFFFFF:
+        raise ValueError("coverage_map: a target is above 2^32 - 1")
+    return m.astype(np.uint32)
+
+
 class Denoise(C.Structure):
     """drt_denoise (include/drt_hip.h): the inputs of the variance-guided denoiser and, after it, unusable / kernel_ms."""
     _fields_ = [("radius", C.c_uint32), ("patch", C.c_uint32), ("flags", C.c_uint32), ("unusable", C.c_uint32),
@@ -626,6 +685,9 @@ def hip_lib():
         L.drt_group_read_sample_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.drt_render_adaptive_continue.argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.POINTER(C.c_uint32)]
         L.drt_group_render_adaptive_continue.argtypes = [C.c_void_p, C.POINTER(Adaptive), C.c_uint32, C.POINTER(C.c_uint32)]
+        if hasattr(L, "drt_render_sample_map"):  # (as drt_selftest_path_ids below)
+            L.drt_render_sample_map.argtypes = [C.c_void_p, C.POINTER(SampleMap)]
+            L.drt_group_render_sample_map.argtypes = [C.c_void_p, C.POINTER(SampleMap)]
         if hasattr(L, "drt_denoise_film"):  # (as drt_selftest_path_ids below)
             L.drt_denoise_film.argtypes = [C.c_void_p, C.POINTER(Denoise)]
             L.drt_read_denoised.argtypes = [C.c_void_p, f64p, f64p]
@@ -730,7 +792,8 @@ HIP_SYMBOLS = ["drt_shade_instantiation",
                "drt_rebuild_hierarchy", "drt_group_rebuild_hierarchy", "drt_get_hierarchy_report", "drt_read_hierarchy",
                "drt_update_spectra", "drt_update_materials", "drt_group_update_spectra", "drt_group_update_materials",
                "drt_bind_depth_cuts", "drt_read_depth_film", "drt_depth_film_device_ptrs", "drt_read_depth_xyz", "drt_read_depth_bgra",
-               "drt_group_bind_depth_cuts", "drt_group_read_depth_film"]
+               "drt_group_bind_depth_cuts", "drt_group_read_depth_film",
+               "drt_render_sample_map", "drt_group_render_sample_map"]
 
 MAX_DEPTH_CUTS = 8  # DRT_MAX_DEPTH_CUTS
 
@@ -1115,6 +1178,36 @@ class Renderer:
         _check(self.L.drt_read_sample_counts(self.ctx, _ptr(out, C.c_uint32)), "drt_read_sample_counts")
         return out
 
+    def render_sample_map(self, targets, add=False):
+        """Every tile pixel rendered to the count `targets` gives it (drt_render_sample_map; add: that many more samples). targets: a
+        numpy integer array (tile_h, tile_w) or flat; a torch int32 / uint32 tensor on the context's device, which the library reads
+        where it is; or a torch CPU tensor. Returns {"rounds", "paths", "pixels_rendered", "pixels_above", "max_count"}."""
+        m = SampleMap()
+        m.flags = MAP_ADD if add else 0
+        tw, th = int(self.params.tile_w), int(self.params.tile_h)
+        if _is_tensor(targets) and targets.device.type != "cpu":
+            torch = sys.modules["torch"]
+            t = targets
+            if t.dtype not in (torch.int32, torch.uint32):
+                raise ValueError("render_sample_map: a device tensor of int32 or uint32 (int32 values are read as unsigned)")
+            if tuple(t.shape) not in ((th, tw), (th * tw,)) or not t.is_contiguous():
+                raise ValueError("render_sample_map: a contiguous tensor of shape (%d, %d) or (%d,)" % (th, tw, th * tw))
+            if t.device.type != "cuda" or t.device.index != int(self.params.device):
+                raise ValueError("render_sample_map: a tensor on the context's device (cuda:%d)" % int(self.params.device))
+            torch.cuda.current_stream(t.device).synchronize()  # what filled the tensor is done before the context's stream reads it
+            m.targets = t.data_ptr()
+            m.flags |= MAP_DEVICE
+            keep = t
+        else:
+            if _is_tensor(targets):
+                torch = sys.modules["torch"]
+                targets = targets.view(torch.int32).numpy().view(np.uint32) if targets.dtype == torch.uint32 else targets.numpy()
+            keep = _map_u32(targets, tw, th, "render_sample_map")
+            m.targets = keep.ctypes.data
+        _check(self.L.drt_render_sample_map(self.ctx, C.byref(m)), "drt_render_sample_map")
+        del keep
+        return _map_report(m)
+
     def read_active_list(self):
         """the tile pixels still active after the last adaptive round (DRT_ADAPTIVE_ROUNDS stops a render early), ascending"""
         out = np.empty(self.n_pixels, dtype=np.uint32)
@@ -1179,6 +1272,18 @@ class Group:
         out = np.empty((int(self.params.tile_h), int(self.params.tile_w)), dtype=np.uint32)
         _check(self.L.drt_group_read_sample_counts(self.g, _ptr(out, C.c_uint32)), "drt_group_read_sample_counts")
         return out
+
+    def render_sample_map(self, targets, add=False):
+        """drt_group_render_sample_map: as Renderer.render_sample_map, from a host array over the whole tile in image order."""
+        if _is_tensor(targets):
+            raise ValueError("Group.render_sample_map: a host array (device maps are per context)")
+        m = SampleMap()
+        m.flags = MAP_ADD if add else 0
+        keep = _map_u32(targets, int(self.params.tile_w), int(self.params.tile_h), "Group.render_sample_map")
+        m.targets = keep.ctypes.data
+        _check(self.L.drt_group_render_sample_map(self.g, C.byref(m)), "drt_group_render_sample_map")
+        del keep
+        return _map_report(m)
 
     def denoise(self, radius=5, patch=1, k=1.0, alpha=1.0):
         """drt_group_denoise: the group's film gathered and filtered on its first device. Returns (mean', var', {"unusable", "kernel_ms"})."""

@@ -358,6 +358,43 @@ int drt_render_adaptive_continue(drt_context *ctx, drt_adaptive *a, uint32_t max
 int drt_group_render_adaptive_continue(drt_group *g, drt_adaptive *a, uint32_t max_rounds, uint32_t *still_active);
 
 /*
+ * Sample maps: render every tile pixel to a sample count the caller gives. targets[p] belongs to tile pixel p (tile order). Pixel p's
+ * count n_p is its filter sum, a whole number in [0, 2^32): 0 and 1 are counts here, and a fresh film holds 0 everywhere.
+ *     absolute mode (flags 0):  R_p = targets[p] > n_p ? targets[p] - n_p : 0     (a pixel above its target is left alone)
+ *     DRT_MAP_ADD:              R_p = targets[p]                                  (n_p + targets[p] must not pass 2^32 - 1)
+ * The call renders samples [n_p, n_p + R_p) of every pixel in binary rounds: with B the OR of all R_p, one round per set bit b of B
+ * in ascending order, which renders the next 2^b samples of every pixel whose R_p has bit b, each from the count it holds then, the
+ * round's pixels listed in ascending tile order. A remainder of 5 is 1 sample in round 0 and 4 in round 2; there are at most 32 rounds.
+ * Afterwards pixel p holds, bit for bit in all three buffers, the film of a uniform render of samples [0, n_p + R_p).
+ * Out: rounds = popcount(B); paths = sum of R_p; pixels_rendered = pixels with R_p > 0; pixels_above = pixels with n_p > targets[p]
+ * (absolute mode; 0 with DRT_MAP_ADD); max_count = the largest count after the call.
+ * DRT_MAP_DEVICE: targets is device memory on the context's device, read by a kernel on the context's stream and never copied to the
+ * host; without it targets is host memory. Synchronous.
+ * Afterwards the context is in the state an adaptive render leaves, with an empty active list: drt_read_sample_counts,
+ * drt_read_active_list (0 entries), drt_read_film, drt_read_bgra, drt_read_xyz, drt_denoise_film, drt_render_features and
+ * drt_render_mattes with n_samples = 0 (under their own count rules), drt_render_adaptive_continue (under its own rules) and another
+ * drt_render_sample_map work; drt_render and drt_write_film are refused until drt_reset_film. A map that asks for nothing succeeds
+ * with 0 rounds and leaves the same state.
+ * Refused (nonzero, drt_last_error, nothing rendered, no film bit changed): a null pointer, undefined flag bits, bound depth cuts,
+ * DRT_MODE_XYZ, DRT_FLAG_RECORD_HITS, a tile of more than 2^32 - 1 pixels, a filter sum that is not a whole number in [0, 2^32) and a
+ * DRT_MAP_ADD overflow (either message names the first such tile pixel), and a failed allocation.
+ * The group form takes host memory only (DRT_MAP_DEVICE is refused): the whole tile in image order, every device its own rows. All
+ * checks, the adoption included, run on all devices before any device renders; rounds = popcount of the OR over all devices, the sums
+ * and the maximum are taken over all devices; film, counts and report are the same for any device list.
+ */
+#define DRT_MAP_DEVICE 1u
+#define DRT_MAP_ADD    2u
+typedef struct drt_sample_map
+{
+    const uint32_t *targets;            /* [tile_h*tile_w] */
+    uint32_t flags;
+    uint32_t rounds, pixels_rendered, pixels_above, max_count;  /* out */
+    uint64_t paths;                                             /* out */
+} drt_sample_map;                       /* 40 bytes */
+int drt_render_sample_map(drt_context *ctx, drt_sample_map *map);
+int drt_group_render_sample_map(drt_group *g, drt_sample_map *map);
+
+/*
  * Variance-guided denoising of the spectral film. The film holds, per pixel and wavelength, a running mean and a sum of squared
  * deviations, and in its filter column the sample count c: what is left after a render is noise of known size. The filter is a
  * non-local mean over a (2 radius + 1)^2 window whose weights compare (2 patch + 1)^2 patches of the pixels' XYZ against the
