@@ -297,7 +297,7 @@ __device__ __forceinline__ void bvh_node_step(const SceneView &sv, int *stack, u
     int ref[2];
     float t[2];
     bool hit[2];
-    bvh_children(n, r32, lim, ref, t, hit);
+    bvh_children<true>(n, r32, lim, ref, t, hit); /* (a direction that is not of unit length enters every child there is) */
     if (hit[0] && hit[1])
     {
         const int near = t[1] < t[0] ? 1 : 0;
@@ -313,7 +313,9 @@ __device__ __forceinline__ void bvh_node_step(const SceneView &sv, int *stack, u
 __device__ __forceinline__ void bvh_walk(const SceneView &sv, int *stack, int *leaf_queue, uint32_t lane, int job, V3 o, V3 d, double &limit, int &index,
                                          bool &occluded)
 {
-    const Ray32 r32 = bvh_ray32(o, d);
+    /* a direction that is not of unit length (a hemisphere sample next to the sampler's pole: drt_kernels.h, RAY_UNIT_TOLERANCE) is
+     * not pruned: the walk's tests hold for |d| = 1, the rule's answer for such a ray is the loop's over all surfaces */
+    const Ray32 r32 = bvh_ray32_unpruned(o, d);
     float lim = bvh_limit32(limit);
     int sp = 0;
     int cur = job == JOB_NONE ? BVH_DONE : 0;

@@ -421,24 +421,60 @@ struct Ray32
     float ix, iy, iz, nx, ny, nz; /* 1/d and -o/d */
     float ox, oy, oz, dx, dy, dz; /* o and d */
 };
-__device__ __forceinline__ float bvh_inv32(double d)
+__device__ __forceinline__ float bvh_inv32(float d)
 {
-    const float i = __builtin_amdgcn_rcpf((float)d); /* v_rcp_f32: 1 ulp, inside the budget above */
+    const float i = __builtin_amdgcn_rcpf(d); /* v_rcp_f32: 1 ulp, inside the budget above */
     return __builtin_fabsf(i) > BVH_INV_CAP ? __builtin_copysignf(BVH_INV_CAP, i) : i;
 }
-__device__ __forceinline__ Ray32 bvh_ray32(V3 o, V3 d)
+/* the ray of origin o and the direction (dx, dy, dz), already in f32 */
+__device__ __forceinline__ Ray32 bvh_ray32f(V3 o, float dx, float dy, float dz)
 {
     Ray32 r;
-    r.ix = bvh_inv32(d.x);
-    r.iy = bvh_inv32(d.y);
-    r.iz = bvh_inv32(d.z);
+    r.ix = bvh_inv32(dx);
+    r.iy = bvh_inv32(dy);
+    r.iz = bvh_inv32(dz);
     r.nx = -((float)o.x * r.ix);
     r.ny = -((float)o.y * r.iy);
     r.nz = -((float)o.z * r.iz);
     r.ox = (float)o.x; r.oy = (float)o.y; r.oz = (float)o.z;
-    r.dx = (float)d.x; r.dy = (float)d.y; r.dz = (float)d.z;
+    r.dx = dx; r.dy = dy; r.dz = dz;
     return r;
 }
+__device__ __forceinline__ Ray32 bvh_ray32(V3 o, V3 d) { return bvh_ray32f(o, (float)d.x, (float)d.y, (float)d.z); }
+
+/* How far d.d may be from 1 for a ray to be PRUNED by the hierarchy: 2^-42. The walk's f32 tests and its distance pruning are derived
+ * for |d| = 1, and the rule (line_sphere_intersection sets a = 1 whatever |d| is) is not the geometric answer otherwise. On the device
+ * the sphere filter rejects no hit for | d.d - 1 | up to 2^-38 (k_ok = 16384 of tests/test_gpu_sphere_filter.py's length family; first
+ * false rejections at 2^-36); the constant is a sixteenth of that, and 1024 ulp of 1, so whatever was normalised in f64 (2.5 ulp) or
+ * reflected a few hundred times (280.5 ulp after 524 mirrors) is pruned as ever. NaN and infinite directions walk, and miss.
+ * A path's own direction CAN be farther off: the hemisphere samplers turn their sample by find_rotation_between_vectors((0, 0, 1),
+ * normal) (src/bdsf.c:191-213, src/geometry.c:263-295), whose 1 / (1 + c) loses the matrix's orthogonality when the normal is within
+ * some 1e-8 of (0, 0, -1) without being it -- the normal at the point where an axis-parallel ray touches a sphere from below, for
+ * one -- and then hand back a direction of length 2 and more, which the reference follows as it stands. */
+#define RAY_UNIT_TOLERANCE 0x1p-42
+#define BVH_WALK_UNIT_TOLERANCE 0x1p-38 /* bvh_ray32_unpruned, below */
+__device__ __forceinline__ bool ray_off_unit(V3 d)
+{
+    const bool finite = __builtin_fabs(d.x) < DRT_INF && __builtin_fabs(d.y) < DRT_INF && __builtin_fabs(d.z) < DRT_INF;
+    return finite && !(__builtin_fabs(v_dot(d, d) - 1.0) <= RAY_UNIT_TOLERANCE);
+}
+/* bvh_ray32 for bvh_walk: a ray_off_unit direction gets the ray of a walk that prunes NOTHING, marked by an infinite dx. bvh_node_step
+ * enters every child of such a ray whatever the box test says (no arithmetic on the boxes: the box of a surface without bounds, and of
+ * every node above it, is infinite, and 0 x inf is a NaN), and the infinite dx leaves sphere_certainly_missed's p2 infinite or NaN,
+ * which rules no leaf out. Such a walk hands every surface in the tree to the f64 intersector -- with the ray's own origin and
+ * direction -- and keeps the minimum with the lowest index on ties: the reference's own loop over all surfaces, at that loop's cost. */
+__device__ __forceinline__ Ray32 bvh_ray32_unpruned(V3 o, V3 d)
+{
+    /* one comparison (the kernels that walk are short of registers, lane masks included): false for a NaN direction, which walks
+     * pruned and misses as ever; true for an infinite one. The bound is the filter's own measured one, 2^-38 (k_ok; its first false
+     * rejections come at 2^-36), not the sixteenth of it that callers' rays are held to: an unpruned walk costs a visit of every
+     * leaf while the lane's wave waits, and the samplers' rotation leaves | d.d - 1 | above 2^-42 for one direction in some 300
+     * (normals within a degree or two of (0, 0, -1)) -- 681 -> 1276 ms per step of BASELINE config 5 with 2^-42, 947 ms with 2^-38
+     * (the remedy is a scan by the whole wave, not yet built). */
+    const bool off = __builtin_fabs(v_dot(d, d) - 1.0) > BVH_WALK_UNIT_TOLERANCE;
+    return bvh_ray32f(o, off ? INFINITY : (float)d.x, (float)d.y, (float)d.z);
+}
+__device__ __forceinline__ bool bvh_ray32_is_unpruned(const Ray32 &r) { return r.dx == INFINITY; }
 
 /* A sphere the ray certainly does not hit within `lim`: its centre is farther from the ray's line than radius + bound, or it
  * lies wholly behind the origin, or wholly beyond the limit. All in f32; with u = 2^-24 and E the largest coordinate, the
@@ -451,9 +487,10 @@ __device__ __forceinline__ Ray32 bvh_ray32(V3 o, V3 d)
  * Held to the rule on its own by drt_selftest_unit's function 14 (tests/test_gpu_sphere_filter.py, against the oracle's line_sphere;
  * DESIGN.md 5e). Measured there on an MI355X: no hit below the limit is rejected; every unit-direction ray that clears the sphere by
  * m = 2 pads is rejected (m = 1 is not met: the error bound is just below one pad); and |d| = 1 is assumed -- with d times
- * 1 + k 2^-53 no hit is rejected up to k_ok = 16384 (| d.d - 1 | <= 2^-38) and some are from k = 65536, while the path's own
- * directions stay within 280.5 x 2^-52 of unit length (524 reflections; v_normalise 2.5, 524 refractions 1). Callers' directions
- * farther than 2^-42 from unit length never get here from a ray query (drt_ray_kernels.h, RAY_UNIT_TOLERANCE). */
+ * 1 + k 2^-53 no hit is rejected up to k_ok = 16384 (| d.d - 1 | <= 2^-38) and some are from k = 65536, while normalised,
+ * reflected and refracted directions stay within 280.5 x 2^-52 of unit length (524 reflections; v_normalise 2.5, 524 refractions 1).
+ * Directions farther from unit length never get here: a caller's beyond 2^-42 is answered by a scan of the tables
+ * (drt_ray_kernels.h), and a hemisphere sampler's next to its pole beyond 2^-38 gets bvh_ray32_unpruned from bvh_walk (above). */
 __device__ __forceinline__ bool sphere_certainly_missed(const BvhLeafPrim &lp, const Ray32 &r, float lim)
 {
     const float cx = lp.c32[0] - r.ox, cy = lp.c32[1] - r.oy, cz = lp.c32[2] - r.oz;
@@ -488,7 +525,9 @@ __device__ __forceinline__ int bvh_leaf_ref(int first, int count) { return -2 - 
 __device__ __forceinline__ bool bvh_is_leaf(int ref) { return ref < BVH_DONE; }
 
 /* the two children of inner node `node` against the ray: which may be entered within `limit` (an f32 upper bound of the
- * distance limit), and a lower bound of where */
+ * distance limit), and a lower bound of where. UNPRUNED: the caller's ray may be bvh_ray32_unpruned's, which enters every child at 0
+ * (a select on the entry distance, not on the lane masks: the walking kernels have no scalar registers to spare) */
+template <bool UNPRUNED = false>
 __device__ __forceinline__ void bvh_children(const BvhNode &n, const Ray32 &r, float limit, int ref[2], float t[2], bool hit[2])
 {
 #pragma unroll
@@ -496,6 +535,7 @@ __device__ __forceinline__ void bvh_children(const BvhNode &n, const Ray32 &r, f
     {
         ref[c] = n.child[c];
         t[c] = bvh_box_entry(n, c, r);
+        if (UNPRUNED) t[c] = bvh_ray32_is_unpruned(r) ? 0.0f : t[c];
         hit[c] = ref[c] != BVH_DONE && t[c] >= 0.0f && t[c] <= limit;
     }
 }

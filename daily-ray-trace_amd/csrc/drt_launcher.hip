@@ -4179,7 +4179,7 @@ static int bind_rays_check(const drt_context *ctx, const drt_ray_table *t, const
     if (ctx->film_used || ctx->adaptive_done)
         return fail(-7, "%s: the film holds samples, and the first ray cannot change under them: drt_reset_film first", name);
     /* Behind the hierarchy a first direction keeps its length through mirror and glass vertices into drt_bounce_kernel's walk, which
-     * is derived for |d| = 1 (drt_ray_kernels.h, RAY_UNIT_TOLERANCE) and which the camera path shares: there is no scan to fall back
+     * is derived for |d| = 1 (drt_kernels.h, RAY_UNIT_TOLERANCE) and which the camera path shares: there is no scan to fall back
      * on, so a table the host can read is looked at here, the tile's rows of every layer. Zero, NaN and infinite directions pass. */
     if (t && !(t->flags & DRT_RAYS_DEVICE) && ctx->use_bvh)
     {

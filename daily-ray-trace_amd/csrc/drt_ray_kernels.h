@@ -155,20 +155,9 @@ __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_visible_kernel(DevScene sc,
     }
 }
 
-/* How far d.d may be from 1 for a caller's ray to take the hierarchy walk: 2^-42. The walk's f32 tests and its distance pruning are
- * derived for |d| = 1, and the rule (line_sphere_intersection sets a = 1 whatever |d| is) is not the geometric answer otherwise. On
- * the device the sphere filter rejects no hit for | d.d - 1 | up to 2^-38 (k_ok = 16384 of tests/test_gpu_sphere_filter.py's length
- * family; first false rejections at 2^-36); the constant is a sixteenth of that, and 1024 ulp of 1, so whatever was normalised in f64
- * (2.5 ulp) or reflected a few hundred times (280.5 ulp after 524 mirrors) walks. A finite direction beyond it is answered by the
- * reference's own loop over all surfaces: exact, and as slow as a scene of that size without a hierarchy. NaN and infinite directions
- * walk, and miss. */
-#define RAY_UNIT_TOLERANCE 0x1p-42
-__device__ __forceinline__ bool ray_off_unit(V3 d)
-{
-    const bool finite = __builtin_fabs(d.x) < DRT_INF && __builtin_fabs(d.y) < DRT_INF && __builtin_fabs(d.z) < DRT_INF;
-    return finite && !(__builtin_fabs(v_dot(d, d) - 1.0) <= RAY_UNIT_TOLERANCE);
-}
-
+/* A caller's ray whose direction is finite and farther than RAY_UNIT_TOLERANCE (2^-42, drt_kernels.h: ray_off_unit) from unit length
+ * does not take the hierarchy walk: it is answered by the reference's own loop over all surfaces, exact, and as slow as a scene of
+ * that size without a hierarchy. NaN and infinite directions walk, and miss. */
 template <bool PIXELS>
 __global__ __launch_bounds__(RAY_BLOCK) void drt_ray_closest_bvh_kernel(DevScene sc, DevCamera cam, RayParams rp)
 {

@@ -3,9 +3,9 @@
 Run in a container where /root/reference exists:  make -C oracle ref && python oracle/make_golden.py [render case ...]
 `python oracle/make_golden.py --records` instead rewrites tests/golden/reference_records.json and reference_arrays.npz: the
 reference's answers to the checks of tests/test_oracle_vs_reference.py and tests/test_reference_parser.py, recorded by running
-those tests against oracle/_ref (tests/reference_records.py).
+those tests against oracle/_ref (tests/reference_records.py). `python oracle/make_golden.py --edge-rays` writes only edge_rays.npz.
 The fixtures are data only (inputs + the reference's outputs); they let the oracle be checked on
-machines where the reference cannot be built (the GPU box). Every array is float64/int32/uint64,
+machines where the reference cannot be built (the GPU box). Every array is float64/int32/int64/uint64/uint8,
 loaded with numpy.load(allow_pickle=False).
 """
 import ctypes as C
@@ -245,9 +245,76 @@ def gen_renders(R, only=None):
         print("render", name, "ok", "paths", px.shape[0] * int(params.spp))
 
 
+EDGE_DIRECT_POINTS, EDGE_DIRECT_DARK = 96, 64  # direct-light points per scene, and how many of them may be all-zero answers
+
+
+def edge_direct_choice(special_nan, special_zero, total=EDGE_DIRECT_POINTS, dark=EDGE_DIRECT_DARK):
+    """Which candidate points (hit points on materials that are no black bodies, in ray order) get a direct-light record: every point
+    whose answer holds a NaN, then the points whose answer is zero in every wavelength -- all of them, or every k-th where they alone
+    would take more than `dark` places --, then every k-th of the rest, `total` at the most."""
+    nan = np.flatnonzero(special_nan)[:total]
+    zero = np.flatnonzero(special_zero & ~special_nan)
+    room = max(0, min(dark, total - len(nan)))
+    if len(zero) > room:
+        zero = zero[(np.arange(room) * len(zero)) // max(room, 1)]
+    rest = np.flatnonzero(~special_nan & ~special_zero)
+    room = total - len(nan) - len(zero)
+    if len(rest) > room:
+        rest = rest[(np.arange(room) * len(rest)) // max(room, 1)]
+    return np.sort(np.concatenate([nan, zero, rest])).astype(np.int64)
+
+
+def gen_edge_rays(R):
+    """The reference's answers on the edge-ray tables' `through` and `from_lattice` rays (tests/edge_ray_cases.py) of FIXTURE_SCENES:
+    find_ray_intersection's record of every ray, points_mutually_visible of three kinds of pair, and direct_light_contribution from a
+    given RNG state, with the state afterwards, at no more than 96 hit points per scene."""
+    import edge_ray_cases as E
+    data = {}
+    for name in E.FIXTURE_SCENES:
+        bundle, _ = E.load(name)
+        S = bundle.S
+        R.ref_set_scene(C.byref(bundle.scene))
+        ro, rd = (np.array(a) for a in E.lattice_rays(name))
+        n = len(ro)
+        index = np.full(n, -1, dtype=np.int32); ids = np.zeros((n, 3), dtype=np.int32)
+        pos = np.zeros((n, 3)); nrm = np.zeros((n, 3)); out = np.zeros((n, 3)); on_dot = np.zeros(n)
+        points = {}
+        for k in range(n):
+            pt = O.Point()
+            index[k] = R.ref_find_ray_intersection(p(ro[k]), p(rd[k]), C.byref(pt))
+            ids[k] = (pt.surface_material, pt.incident_material, pt.transmit_material)
+            if index[k] >= 0:
+                pos[k], nrm[k], out[k], on_dot[k] = pt.position[:], pt.normal[:], pt.out[:], pt.on_dot
+                assert pt.trans_wl == 630.0
+                points[k] = pt
+        p0, p1 = E.visibility_pairs(bundle, ro, rd, index, pos)
+        vis = np.array([R.ref_points_mutually_visible(p(p0[k]), p(p1[k])) for k in range(len(p0))], dtype=np.uint8)
+        # direct light: every candidate first, to see which answers are NaN or dark; then the chosen ones are stored
+        cand = np.array([k for k in sorted(points) if not int(bundle.scene.materials[int(ids[k, 0])].is_black_body)], dtype=np.int64)
+        states = np.random.default_rng([0xD1EC, sum(map(ord, name))]).integers(1, 2 ** 62, len(cand)).astype(np.uint64)
+        direct = np.zeros((len(cand), S)); after = np.zeros(len(cand), dtype=np.uint64)
+        for j, k in enumerate(cand):
+            R.ref_set_rng_state(int(states[j]))
+            R.ref_direct_light(C.byref(points[int(k)]), p(direct[j]))
+            after[j] = R.ref_get_rng_state()
+        take = edge_direct_choice(np.isnan(direct).any(axis=1), (direct == 0.0).all(axis=1))
+        data.update({name + ".o": ro, name + ".d": rd, name + ".index": index, name + ".position": pos, name + ".normal": nrm,
+                     name + ".out": out, name + ".on_dot": on_dot, name + ".materials": ids, name + ".visible": vis,
+                     name + ".direct_ray": cand[take], name + ".direct_state": states[take], name + ".direct": direct[take],
+                     name + ".direct_state_after": after[take]})
+        print("edge rays", name, "rays", n, "hits", int((index >= 0).sum()), "pairs", len(p0), "direct points", len(take), "of", len(cand),
+              "NaN", int(np.isnan(direct[take]).any(axis=1).sum()), "dark", int((direct[take] == 0.0).all(axis=1).sum()))
+    path = os.path.join(OUT, "edge_rays.npz")
+    np.savez_compressed(path, **data)
+    print("edge_rays.npz %.1f KB" % (os.path.getsize(path) / 1024))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     R = O.ref_lib()
+    if sys.argv[1:] == ["--edge-rays"]:  # only tests/golden/edge_rays.npz
+        gen_edge_rays(R)
+        return
     if sys.argv[1:] == ["--records"]:
         import subprocess
         tests = [os.path.join(REPO, "tests", t) for t in ("test_oracle_vs_reference.py", "test_reference_parser.py")]
@@ -263,6 +330,7 @@ def main():
     gen_spectral(R, bundle)
     gen_bdsf(R, bundle)
     gen_renders(R)
+    gen_edge_rays(R)
     total = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden fixtures written to", OUT, "total %.1f KB" % (total / 1024))
 

@@ -18,7 +18,10 @@ and the six direction samplers (src/bdsf.c:188-292) -- one record at a time on t
 
 Records of one launch mix materials, overrides and samplers, so the lanes of a wave diverge as they do in the kernels.
 Not covered here: the trace / shade kernels' hand-inlined plastic and mirror fast paths (they are not bdsf_at_wavelength; the films
-of tests/test_gpu_parity.py cover them) and direct_light_contribution (it needs the shadow ray's geometry)."""
+of tests/test_gpu_parity.py cover them) and direct_light_contribution (it needs the shadow ray's geometry: tests/test_gpu_edge_rays.py
+holds the next-event code of every kernel that carries it to the oracle on rays built from the scenes' own coordinates, its depth-1
+films being direct light and emission alone, and tests/test_edge_rays_cpu.py holds the oracle's direct_light_contribution at such hit
+points to the compiled reference's, tests/golden/edge_rays.npz)."""
 import ctypes as C
 import math
 import os
