@@ -255,6 +255,14 @@ __device__ __forceinline__ double line_plane_limited(V3 o, V3 d, V3 pp, V3 pn, V
     return DRT_INF;
 }
 
+/* The media either side of a hit (scene_point's incident and transmit material, src/daily_ray_trace.c:380-394) from ONE bit: the ray
+ * comes out of the base material into the surface's, or -- swapped: it meets the back of a surface that is not a plane -- out of the
+ * surface's into the base material. */
+__device__ __forceinline__ uint32_t media_index(bool swapped, bool incident, uint32_t surface_mat, uint32_t base_mat)
+{
+    return (swapped == incident) ? surface_mat : base_mat;
+}
+
 /* ---- pow(x, y) as bp_glossy_bdsf uses it (src/bdsf.c:116): x in [0, 1], y the material's shininess ------------------------ */
 /* For an integer shininess (what scenes carry: 100, 32, ...) by repeated squaring in double-double arithmetic: the value carried is
  * hi + lo with |lo| <= ulp(hi) / 2, every product is exact to 2^-104, so after the <= 20 products of an exponent below 1024 the
@@ -267,7 +275,12 @@ __device__ __forceinline__ double drt_pow_shininess(double x, double y)
     if (!(y >= 0.0 && y < 1024.0 && (double)n == y) || !(x >= 0.0 && x <= 1.0)) return pow(x, y);
     double rh = 1.0, rl = 0.0; /* the result so far */
     double bh = x, bl = 0.0;   /* x^(2^k) */
-    for (uint32_t k = n; __any(k != 0u); k >>= 1)
+    /* The loop's exponent is converted again from a copy of y the compiler cannot see through: taken from `n`, the value was live
+     * across the pow() branch above, and the trace kernel spilled it there and reloaded it here -- behind its light-record stores,
+     * which the one vector-memory counter then made it wait for. The same integer either way. */
+    double yk = y;
+    asm volatile("" : "+v"(yk));
+    for (uint32_t k = (uint32_t)yk; __any(k != 0u); k >>= 1)
     {
         if (k & 1u)
         {

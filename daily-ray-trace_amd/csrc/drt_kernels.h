@@ -220,6 +220,7 @@ struct TraceParams
 struct WavePool
 {
     uint32_t base, left; /* wave-uniform: first block of the current chunk not handed out yet, blocks left in it */
+    uint32_t handed;     /* wave-uniform: blocks handed to lanes so far (statistics: the trace kernel's form of `taken`) */
     uint32_t taken;      /* per lane: blocks this lane's paths have opened (statistics; spares held at the end are not in it) */
 };
 
@@ -247,6 +248,7 @@ __device__ __forceinline__ uint32_t pool_alloc(const TraceParams &tp, WavePool &
     const uint32_t id = wp.base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
     wp.base += n;
     wp.left -= n;
+    wp.handed += n;
     return need ? id : ~0u;
 }
 
@@ -569,9 +571,32 @@ struct HitPoint /* scene_point, src/daily_ray_trace.h:113-125 */
     int      index;
 };
 
+/* The trace kernel's scene point. The media either side of the hit are the surface's material and the scene's base material, one way
+ * round or the other (find_ray_intersection below: swapped where the ray leaves a surface that is not a plane), so the kernel holds
+ * that one bit from the scan to the end of the vertex and forms the two indices where they are used (media_index, drt_device.h);
+ * as two registers they were spilled behind the vertex record's first store and reloaded three times a vertex. */
+struct TraceHit
+{
+    V3       position, normal, out;
+    double   on_dot;
+    uint32_t surface_mat;
+    bool     swapped;
+    int      index;
+};
+__device__ __forceinline__ void hit_set_media(const DevScene &sc, HitPoint &ip, uint32_t smat, bool swapped)
+{
+    ip.incident_mat = media_index(swapped, true, smat, sc.base_mat);
+    ip.transmit_mat = media_index(swapped, false, smat, sc.base_mat);
+}
+__device__ __forceinline__ void hit_set_media(const DevScene &, TraceHit &ip, uint32_t, bool swapped) { ip.swapped = swapped; }
+__device__ __forceinline__ uint32_t incident_mat_of(const DevScene &, const HitPoint &ip) { return ip.incident_mat; }
+__device__ __forceinline__ uint32_t transmit_mat_of(const DevScene &, const HitPoint &ip) { return ip.transmit_mat; }
+__device__ __forceinline__ uint32_t incident_mat_of(const DevScene &sc, const TraceHit &ip) { return media_index(ip.swapped, true, ip.surface_mat, sc.base_mat); }
+__device__ __forceinline__ uint32_t transmit_mat_of(const DevScene &sc, const TraceHit &ip) { return media_index(ip.swapped, false, ip.surface_mat, sc.base_mat); }
+
 /* find_ray_intersection, src/daily_ray_trace.c:334-403 */
-template <bool ROWS = false>
-__device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const DevScene &sc, HitPoint &ip, V3 ro, V3 rd DRT_SCAN_STATS_PARAM)
+template <bool ROWS = false, class HP = HitPoint>
+__device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const DevScene &sc, HP &ip, V3 ro, V3 rd DRT_SCAN_STATS_PARAM)
 {
     double min_dist = DRT_INF;
     int index = -1;
@@ -600,15 +625,10 @@ __device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const
         else ip.normal = sf3(sv, SF_NX, index);
         ip.out = v_reverse(rd);
         ip.on_dot = v_dot(ip.normal, ip.out);
-        ip.transmit_mat = smat;
-        ip.incident_mat = sc.base_mat;
+        hit_set_media(sc, ip, smat, false);
         if (ip.on_dot < 0.0)
         {
-            if (type != DRT_GEO_PLANE)
-            {
-                ip.transmit_mat = sc.base_mat;
-                ip.incident_mat = smat;
-            }
+            if (type != DRT_GEO_PLANE) hit_set_media(sc, ip, smat, true);
             ip.normal = v_reverse(ip.normal);
             ip.on_dot = v_dot(ip.normal, ip.out);
         }
@@ -624,15 +644,17 @@ __device__ __forceinline__ double refract_at_trans_wl(const DevScene &sc, const 
 }
 
 /* vertex record word 2: the SPD rows of the media either side of the hit, and the rows tabulated for that pair (if any) */
-__device__ __forceinline__ uint64_t record_media_word(const DevScene &sc, const SceneView &sv, const HitPoint &ip)
+template <class HP>
+__device__ __forceinline__ uint64_t record_media_word(const DevScene &sc, const SceneView &sv, const HP &ip)
 {
     const DevMaterial &sm = sv.mats[ip.surface_mat];
+    const uint32_t incident_mat = incident_mat_of(sc, ip), transmit_mat = transmit_mat_of(sc, ip);
     uint32_t pair = PAIR_NONE;
-    if (ip.incident_mat == sc.base_mat && ip.transmit_mat == ip.surface_mat) pair = sm.pair_out;
-    else if (ip.incident_mat == ip.surface_mat && ip.transmit_mat == sc.base_mat) pair = sm.pair_in;
-    return (uint64_t)((uint32_t)sv.mats[ip.incident_mat].refract_spd & 0xFFFFu) |
-           ((uint64_t)((uint32_t)sv.mats[ip.transmit_mat].refract_spd & 0xFFFFu) << 16) |
-           ((uint64_t)((uint32_t)sv.mats[ip.transmit_mat].extinct_spd & 0xFFFFu) << 32) | ((uint64_t)pair << 48);
+    if (incident_mat == sc.base_mat && transmit_mat == ip.surface_mat) pair = sm.pair_out;
+    else if (incident_mat == ip.surface_mat && transmit_mat == sc.base_mat) pair = sm.pair_in;
+    return (uint64_t)((uint32_t)sv.mats[incident_mat].refract_spd & 0xFFFFu) |
+           ((uint64_t)((uint32_t)sv.mats[transmit_mat].refract_spd & 0xFFFFu) << 16) |
+           ((uint64_t)((uint32_t)sv.mats[transmit_mat].extinct_spd & 0xFFFFu) << 32) | ((uint64_t)pair << 48);
 }
 /* which three table rows a vertex's per-wavelength Fresnel inputs come from: (ir, tr, te) as the reference has them, or --
  * pair rows tabulated -- (ir, tr, rel_sq) for a dielectric and (cA, cB, -) for a conductor: same registers, same three loads */
@@ -668,7 +690,8 @@ __device__ __forceinline__ bool dirs_need_trans(const DevMaterial &m)
     return (m.needs & NEED_EQT) || m.dir_func == DRT_DIRF_sample_transmit_direction || m.dir_func == DRT_DIRF_sample_reflect_or_transmit_direction;
 }
 
-__device__ __forceinline__ VertexDirs vertex_dirs(const DevScene &sc, const SceneView &sv, const HitPoint &ip)
+template <class HP>
+__device__ __forceinline__ VertexDirs vertex_dirs(const DevScene &sc, const SceneView &sv, const HP &ip)
 {
     const DevMaterial &mat = sv.mats[ip.surface_mat];
     VertexDirs vd;
@@ -678,8 +701,8 @@ __device__ __forceinline__ VertexDirs vertex_dirs(const DevScene &sc, const Scen
     if (dirs_need_refl(mat)) vd.refl = v_reflect(w, ip.normal);
     if (dirs_need_trans(mat))
     {
-        double ir = refract_at_trans_wl(sc, sv.mats[ip.incident_mat]);
-        double tr = refract_at_trans_wl(sc, sv.mats[ip.transmit_mat]);
+        double ir = refract_at_trans_wl(sc, sv.mats[incident_mat_of(sc, ip)]);
+        double tr = refract_at_trans_wl(sc, sv.mats[transmit_mat_of(sc, ip)]);
         vd.trans = v_transmit(w, ip.normal, ir, tr);
     }
     return vd;
@@ -688,7 +711,8 @@ __device__ __forceinline__ VertexDirs vertex_dirs(const DevScene &sc, const Scen
 /* The per-direction scalars of every BDSF in the material's list (src/bdsf.c:105-186):
  * what remains of bdsf(p, in) once the per-wavelength work is taken out. bp_glossy_bdsf's bisector and ct_conductor_bdsf's
  * micro-normal are one expression, normalise(out + in), computed once for the lanes of either. */
-__device__ __forceinline__ EvalCoef eval_coefficients(const SceneView &sv, const HitPoint &ip, const VertexDirs &vd, V3 in)
+template <class HP>
+__device__ __forceinline__ EvalCoef eval_coefficients(const SceneView &sv, const HP &ip, const VertexDirs &vd, V3 in)
 {
     const DevMaterial &mat = sv.mats[ip.surface_mat];
     EvalCoef e;
@@ -724,7 +748,8 @@ __device__ __forceinline__ EvalCoef eval_coefficients(const SceneView &sv, const
  * operands by select, so every lane still performs its own sampler's operations, in its order, on its operands. The disc's and the
  * GGX sampler's rejection loops are one loop in which a lane repeats its own body until it accepts; the disc's z and the rotation of
  * a rejected point are computed and dropped (the rotation matrix depends on the normal alone and is built once, before the loop). */
-__device__ __forceinline__ void sample_direction(const DevScene &sc, const SceneView &sv, const HitPoint &ip, const VertexDirs &vd, uint64_t &rs,
+template <class HP>
+__device__ __forceinline__ void sample_direction(const DevScene &sc, const SceneView &sv, const HP &ip, const VertexDirs &vd, uint64_t &rs,
                                                  uint32_t &draws, V3 &dir, double &recip_pdf)
 {
     const DevMaterial &mat = sv.mats[ip.surface_mat];
@@ -748,8 +773,8 @@ __device__ __forceinline__ void sample_direction(const DevScene &sc, const Scene
     double num = 0.0, den = 1.0; /* recip_pdf = num / den for the disc, GGX and reflect-or-transmit samplers */
     if (coin)
     {
-        const DevMaterial &im = sv.mats[ip.incident_mat];
-        const DevMaterial &tm = sv.mats[ip.transmit_mat];
+        const DevMaterial &im = sv.mats[incident_mat_of(sc, ip)];
+        const DevMaterial &tm = sv.mats[transmit_mat_of(sc, ip)];
         /* value_at_wl(reflectance spectrum, 630) needs the Fresnel term at the two bracketing samples */
         double inc_sin_sq = 1.0 - ip.on_dot * ip.on_dot;
         double r0 = dielectric_reflectance(im.refract_i0, tm.refract_i0, ip.on_dot, inc_sin_sq);
@@ -1139,6 +1164,20 @@ __device__ __forceinline__ const TraceConst &trace_const(const double *lds)
     return *(const TraceConst *)((const char *)lds + off);
 #endif
 }
+/* Per-lane words the trace kernel keeps in LDS instead of vector registers: a wave has TRACE_LANE_ROWS rows of 64 x 8 bytes, a lane
+ * its 8 bytes of each (index from the lane's pointer, in 4-byte words). The kernel stands at the register count where it spills, and
+ * a spilled register's reload waits on the one vector-memory counter, that is for every record store issued before it; LDS has a
+ * counter of its own. The block of the current four vertices is read once per vertex; the three statistics are only ever added
+ * to (scans and shaded vertices when a path ends, draws where they are made) and summed over the wave at the kernel's end. */
+#define TRACE_LANE_ROWS 2u
+#define TRACE_LW_BLK 0u
+#define TRACE_LW_DRAWS 1u
+#define TRACE_LW_SCANS 128u
+#define TRACE_LW_SHADED 129u
+__device__ __forceinline__ void lane_word_add(uint32_t *w, uint32_t v)
+{
+    (void)__hip_atomic_fetch_add(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* one LDS add, nothing returned */
+}
 #define DRT_TRACE_TAIL_MAX 8u /* tail wavelengths the trace kernel carries at most (the launcher's rule: S mod 64 <= 8) */
 #ifndef DRT_TRACE_WAVES_PER_SIMD
 #define DRT_TRACE_WAVES_PER_SIMD 3 /* register budget: launch_bounds' 2nd argument is waves per SIMD */
@@ -1190,6 +1229,8 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
 #endif
     SceneView sv;
     double *l_spd_tail = nullptr, *tail_state = nullptr;
+    double *lane_area = nullptr;
+    uint32_t *lane_words = nullptr;
     uint32_t TR, max_depth, vertex_words, block_words;
     bool tail_on, record_hits;
     {
@@ -1257,7 +1298,9 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
      * the reference grid) cost it a pass of their own in which a lane must decode records by itself. HERE a lane is a path and
      * already holds every number a vertex contributes, so the same arithmetic for those few wavelengths is a handful of f64
      * operations per vertex at full lane use. It is done for paths that consist of two-lobe plastic and mirror vertices only (and
-     * for paths without a vertex): running throughput and radiance per tail wavelength live in LDS (a wave's block: [2 R][64 lanes]),
+     * for paths without a vertex): running throughput and radiance per tail wavelength live in LDS (a wave's block: [1 + 2 R][64 lanes]
+     * behind its lane rows; the first row is the path's vignette -- in ray mode its weight -- kept from the path's start to its
+     * end, so that the loop loads nothing back from the header it stores: a load there would wait for every record store in front of it),
      * the table's tail columns too, and when the path ends its values go to tail_stage, flagged in the header
      * (HDR_TERM_TAIL_STAGED). A path that meets any other material stays unflagged and is replayed by the shade kernel's tail pass,
      * which takes such paths as tasks and skips the flagged ones; in a scene where EVERY path is carried here the launcher says so
@@ -1267,11 +1310,25 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
      */
     TR = tp.tail_count;
     tail_on = TAIL && SCENE_IN_LDS && tp.tail_stage != nullptr; /* TAIL: an instantiation of its own, so that scenes that cannot use it run the kernel without any of this */
+    /* behind the LDS copy of the materials, the last of the scene's tables */
+    lane_area = SCENE_IN_LDS ? (double *)(sv.mats + sc.n_mat) : lds_raw + TRACE_CONST_BYTES / 8;
     if (tail_on)
     {
-        l_spd_tail = (double *)(sv.mats + sc.n_mat); /* behind the LDS copy of the materials, the last of the scene's tables */
+        l_spd_tail = lane_area;
         for (uint32_t k = threadIdx.x; k < tp.n_spd * TR; k += TRACE_BLOCK) l_spd_tail[k] = tp.spd_tail[k];
-        tail_state = l_spd_tail + (size_t)tp.n_spd * TR + (size_t)(threadIdx.x >> 6) * (2u * TR * 64u) + (threadIdx.x & 63u);
+        lane_area += (size_t)tp.n_spd * TR;
+    }
+    /* a wave's lane rows, [TRACE_LANE_ROWS][64 lanes] of 8 bytes (see TRACE_LW_*), and behind them its tail rows: one address
+     * register per lane, every row an immediate offset from it */
+    lane_area += (size_t)(threadIdx.x >> 6) * ((TRACE_LANE_ROWS + (tail_on ? 1u + 2u * TR : 0u)) * 64u) + (threadIdx.x & 63u);
+    lane_words = (uint32_t *)lane_area;
+    lane_words[TRACE_LW_BLK] = 0u;
+    lane_words[TRACE_LW_DRAWS] = 0u;
+    lane_words[TRACE_LW_SCANS] = 0u;
+    lane_words[TRACE_LW_SHADED] = 0u;
+    if (tail_on)
+    {
+        tail_state = lane_area + (TRACE_LANE_ROWS + 1u) * 64u;
         __syncthreads();
     }
     /* what every iteration reads, in scalar registers */
@@ -1289,7 +1346,12 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
     uint64_t chunk_next = 0, chunk_end = 0; /* wave-uniform */
     PathPos chunk_pos = {0, 0};             /* wave-uniform: pixel and sample of path id chunk_next */
 
-    uint32_t n_scans = 0, n_shaded = 0, n_shadow = 0, n_draws = 0, n_paths = 0;
+    /* Statistics, none of them in a vector register across the loop: paths are counted per WAVE where they are handed out (a
+     * population count added to a scalar, the control flow there is wave-uniform); a path's scans and shaded vertices are its
+     * `depth` and `shaded` when it ends, added to the lane's words in LDS, its draws are added there where they are made
+     * (TRACE_LW_*); shadow scans are shaded vertices x lights; record blocks are what pool_alloc handed out less the spares the
+     * lanes still hold at the end. The totals are the same numbers. */
+    uint32_t w_paths = 0; /* wave-uniform */
 #ifdef DRT_BRANCH_STATS
     uint64_t bs[DRT_BS_WORDS] = {};
 #endif
@@ -1304,9 +1366,9 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                                   Bits 16-19 (they do not reach the header's field): the vertex k, 1-15, at which the path stopped being carried */
     V3 ro = v3(0, 0, 0), rd = v3(0, 0, 0);
     uint64_t *hdr = nullptr;
-    uint32_t blk = 0, tbl = 0;              /* the pool block of the current four vertices; the path's table block (deep paths) */
+    uint32_t tbl = 0;                       /* the path's table block (deep paths); the block of the current four vertices is TRACE_LW_BLK */
     uint32_t spare = ~0u, spare_tbl = ~0u; /* a block (and, for deep paths, a table block) held ready: see path_spare_block */
-    WavePool wp = {0u, 0u, 0u};
+    WavePool wp = {0u, 0u, 0u, 0u};
 
     for (;;)
     {
@@ -1362,6 +1424,7 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
             }
             /* start the newly assigned paths: lanes that were idle in idle_mask and are alive now */
             bool started = alive && ((idle_mask >> lane) & 1ull);
+            w_paths += (uint32_t)__popcll(__ballot(started));
             if (started)
             {
                 const TraceConst &c = LC;
@@ -1380,7 +1443,12 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                 rs = drt_splitmix64(key);
                 double weight = 1.0;
                 if (RAYS) weight = table_ray(LC_RT, c.tp.width, t, x, y, sample, ro, rd); /* no draw before cast_ray */
-                else camera_ray(c.cam, c.tp.pixel_scheme, x, y, rs, n_draws, ro, rd);
+                else
+                {
+                    uint32_t drawn = 0;
+                    camera_ray(c.cam, c.tp.pixel_scheme, x, y, rs, drawn, ro, rd);
+                    lane_word_add(lane_words + TRACE_LW_DRAWS, drawn);
+                }
                 depth = 0;
                 shaded = 0;
                 plastic_mask = 0;
@@ -1400,8 +1468,9 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                 uint64_t slot = q * (uint64_t)c.tp.batch + s_local;
                 hdr = headers + slot * REC_HEADER_WORDS;
                 /* vignette: dot(ray_direction, forward) of the PRIMARY ray, src/daily_ray_trace.c:614 */
-                hdr[1] = (uint64_t)__double_as_longlong((RAYS ? weight : v_dot(rd, c.cam.forward)) * 1.0);
-                n_paths += 1;
+                const double vignette = (RAYS ? weight : v_dot(rd, c.cam.forward)) * 1.0;
+                hdr[1] = (uint64_t)__double_as_longlong(vignette); /* for the shade kernel: never loaded back here */
+                if (tail_on) lane_area[TRACE_LANE_ROWS * 64u] = vignette;
                 if (record_hits)
                 {
                     int32_t *h = c.hits + ((uint64_t)c.tp.hits_sample_offset * c.tp.n_pix + hit_row) * max_depth;
@@ -1416,13 +1485,14 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
         {
             hdr[0] = (uint64_t)HDR_TERM_NOT_DONE << 16;
             alive = false;
+            lane_word_add(lane_words + TRACE_LW_SCANS, depth); /* cut short: what it did so far counts */
+            lane_word_add(lane_words + TRACE_LW_SHADED, shaded);
         }
         if (alive)
         {
             /* ---- one iteration of cast_ray's loop, src/daily_ray_trace.c:446-474 ---- */
-            HitPoint ip;
+            TraceHit ip;
             find_ray_intersection<SCENE_IN_LDS>(sv, LC.sc, ip, ro, rd DRT_SCAN_STATS_ARG(bs + 16));
-            n_scans += 1;
             if (record_hits)
             {
                 const TraceConst &c = LC;
@@ -1440,14 +1510,15 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
             }
             else
             {
+                uint32_t blk = lane_words[TRACE_LW_BLK]; /* the pool block of the current four vertices */
                 path_open_vertex(LC.tp, wp, records, shaded, hdr, blk, tbl, spare, spare_tbl);
+                lane_words[TRACE_LW_BLK] = blk;
                 uint64_t *vrec = records + (uint64_t)blk * block_words + (uint64_t)(shaded & (REC_BLOCK_VERTICES - 1u)) * vertex_words;
                 /* the vertex's mirror and refracted directions, shared by the lights' evaluations, the sampler and the continuation's
                  * evaluation. Computed before the light loop, so they are live across the shadow scans (after the first scan instead:
                  * more scratch) */
                 const VertexDirs vd = vertex_dirs(LC.sc, sv, ip);
                 /* direct_light_contribution, :272-332 -- light samples are drawn before the shadow test */
-                n_shaded += 1;
                 bool t_vis = false; /* light 0 as the tail arithmetic below wants it (the kernel carries tails only in one-light scenes) */
                 double t_c = 0.0, t_a_in = 0.0, t_spec = 0.0;
                 uint32_t t_em = 0, t_flags = 0;
@@ -1465,8 +1536,10 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                     }
                     else if (ltype == DRT_GEO_SPHERE)
                     {
-                        double u = drt_rng(rs, n_draws);
-                        double v = drt_rng(rs, n_draws);
+                        uint32_t drawn = 0;
+                        double u = drt_rng(rs, drawn);
+                        double v = drt_rng(rs, drawn);
+                        lane_word_add(lane_words + TRACE_LW_DRAWS, drawn);
                         double r = __builtin_sqrt(1.0 - u * u);
                         double t = (2.0 * DRT_PI) * v;
                         double st, ct;
@@ -1476,13 +1549,14 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                     }
                     else if (ltype == DRT_GEO_PLANE)
                     {
-                        double u = drt_rng(rs, n_draws);
-                        double v = drt_rng(rs, n_draws);
+                        uint32_t drawn = 0;
+                        double u = drt_rng(rs, drawn);
+                        double v = drt_rng(rs, drawn);
+                        lane_word_add(lane_words + TRACE_LW_DRAWS, drawn);
                         V3 lu = v3(sv.lights[LF_UX * sv.n_lights + l], sv.lights[LF_UY * sv.n_lights + l], sv.lights[LF_UZ * sv.n_lights + l]);
                         V3 lv = v3(sv.lights[LF_VX * sv.n_lights + l], sv.lights[LF_VY * sv.n_lights + l], sv.lights[LF_VZ * sv.n_lights + l]);
                         light_position = v_sum(v_sum(lpos, v_mul(lu, u)), v_mul(lv, v));
                     }
-                    n_shadow += 1;
                     bool visible = points_mutually_visible<SCENE_IN_LDS>(sv, ip.position, light_position DRT_SCAN_STATS_ARG(bs + 18));
                     uint64_t *lrec = vrec + REC_VERTEX_WORDS + (uint64_t)l * REC_LIGHT_WORDS;
                     uint32_t lflags = 0;
@@ -1504,10 +1578,9 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                 /* sampled continuation, :464-472 */
                 V3 in;
                 double dir_pdf;
-#ifdef DRT_BRANCH_STATS
-                const uint32_t draws_before = n_draws;
-#endif
-                sample_direction(LC.sc, sv, ip, vd, rs, n_draws, in, dir_pdf);
+                uint32_t drawn = 0;
+                sample_direction(LC.sc, sv, ip, vd, rs, drawn, in, dir_pdf);
+                lane_word_add(lane_words + TRACE_LW_DRAWS, drawn);
                 EvalCoef e = eval_coefficients(sv, ip, vd, in);
 #ifdef DRT_BRANCH_STATS
                 {
@@ -1521,7 +1594,7 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                     const unsigned long long m_coin = __ballot(df == DRT_DIRF_sample_reflect_or_transmit_direction);
                     const unsigned long long m_spec = __ballot(df == DRT_DIRF_sample_specular_direction);
                     const unsigned long long m_loop = __ballot(in_loop);
-                    const unsigned long long m_again = __ballot(in_loop && n_draws - draws_before > 2u);
+                    const unsigned long long m_again = __ballot(in_loop && drawn > 2u);
                     const unsigned long long m_half = __ballot((mat.needs & (NEED_GLOSSY | NEED_CT)) != 0u);
                     const unsigned long long m_eqt = __ballot((mat.needs & NEED_EQT) != 0u);
                     if (lane == (uint32_t)(__ffsll((long long)m_all) - 1))
@@ -1638,7 +1711,7 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                 if (tail_ok)
                 {
                     /* the sample's value at the tail wavelengths: emission of what the path ended on, vignette (:452-457, :615) */
-                    const double vignette = __longlong_as_double((long long)hdr[1]);
+                    const double vignette = lane_area[TRACE_LANE_ROWS * 64u]; /* the row written when the path started */
                     double *st = LC.tp.tail_stage + (uint64_t)(hdr - headers) / REC_HEADER_WORDS * TR;
                     const double *row_t = l_spd_tail + (term_spd & 0xFFFFu) * TR;
                     const uint32_t tr = pinned_scalar(TR);
@@ -1674,19 +1747,26 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
                 }
                 hdr[0] = (uint64_t)shaded | ((uint64_t)(term | staged) << 16) | ((uint64_t)(term_spd & 0xFFFFu) << 32) | ((uint64_t)plastic_mask << 48) | ((uint64_t)vis0_mask << 24);
                 alive = false;
+                lane_word_add(lane_words + TRACE_LW_SCANS, depth);
+                lane_word_add(lane_words + TRACE_LW_SHADED, shaded);
             }
         }
     }
 
-    /* statistics: wave reduction, one atomic per wave and counter */
-    uint64_t vals[6] = {n_paths, n_scans, n_shaded, n_shadow, n_draws, wp.taken};
+    /* statistics: the per-lane counts reduced over the wave, then one atomic per wave and counter */
+    uint64_t scans = lane_words[TRACE_LW_SCANS], n_shaded = lane_words[TRACE_LW_SHADED], draws = lane_words[TRACE_LW_DRAWS];
+    uint64_t held = (uint64_t)(spare != ~0u) + (uint64_t)(spare_tbl != ~0u);
+    for (int off = 32; off > 0; off >>= 1)
+    {
+        scans += __shfl_down(scans, off);
+        n_shaded += __shfl_down(n_shaded, off);
+        draws += __shfl_down(draws, off);
+        held += __shfl_down(held, off);
+    }
+    uint64_t vals[6] = {w_paths, scans, n_shaded, n_shaded * sv.n_lights, draws, (uint64_t)wp.handed - held};
     unsigned long long *counters = LC.counters;
     for (int k = 0; k < 6; k += 1)
-    {
-        uint64_t v = vals[k];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-        if (lane == 0 && v) atomicAdd(&counters[k], (unsigned long long)v);
-    }
+        if (lane == 0 && vals[k]) atomicAdd(&counters[k], (unsigned long long)vals[k]);
 #ifdef DRT_BRANCH_STATS
     for (int k = 0; k < DRT_BS_WORDS; k += 1)
     {

@@ -266,6 +266,7 @@ static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat
     b += (size_t)(SR_STRIDE + SF_COUNT) * n_surf * 8 + (size_t)LF_COUNT * n_lights * 8;
     b += ((size_t)(2 * n_surf + 2 * n_lights) * 4 + 7) & ~(size_t)7;
     b += (size_t)n_mat * sizeof(DevMaterial);
+    b += (size_t)(TRACE_BLOCK / 64) * TRACE_LANE_ROWS * 64 * 8; /* the waves' lane rows (TRACE_LW_*) */
     return b;
 }
 
@@ -813,14 +814,17 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
     if (!ctx->scene_in_lds) ctx->trace_lds = 0;
     ctx->spds_in_lds = (size_t)d.n_spd * S * 8 <= 64 * 1024;
     /* The tail wavelengths in the trace kernel (csrc/drt_kernels.h, drt_trace_kernel<true, true>): scenes scanned out of LDS with one
-     * light and a tail of at most 8 wavelengths, when the table's tail columns and the waves' running values ([2 R][64 lanes] each)
+     * light and a tail of at most 8 wavelengths, when the table's tail columns and the waves' running values ([2 R + 1][64 lanes] each)
      * fit beside the scene. Paths of two-lobe plastic and mirror vertices (and those without a vertex) are carried there; where
      * every surface is a light, a black body, plastic or a mirror that is EVERY path, and the shade kernel's tail pass has nothing
-     * to replay (tail_all_staged). With glass or gold in the scene the paths that touch them stay with the tail pass, as tasks. */
+     * to replay (tail_all_staged). With glass or gold in the scene the paths that touch them stay with the tail pass, as tasks.
+     * The rule's 48 KB is of the scene, the table's tail columns and the running values; the lanes' rows (TRACE_LW_*) and the vignette
+     * row, 6 KB, are not counted in it, so that a scene takes the kernel it took before they existed. Up to 47 KB of the rule's
+     * quantity three workgroups still share a CU's 160 KB. */
     {
         uint32_t sets = 0, tf = 0, tc = 0;
         shade_sets(S, &sets, &tf, &tc);
-        const size_t extra = (size_t)d.n_spd * tc * 8 + (size_t)(TRACE_BLOCK / 64) * 2 * tc * 64 * 8;
+        const size_t extra = (size_t)d.n_spd * tc * 8 + (size_t)(TRACE_BLOCK / 64) * (2 * tc + 1) * 64 * 8; /* + 1: the vignette row */
         /* every list of every material (used by a surface or not: a ray can only meet a surface's, but the check is cheap) */
         ctx->simple_bdsfs = !getenv("DRT_NO_SIMPLE_SHADE");
         ctx->no_fixed_lists = getenv("DRT_NO_FIXED_LISTS") != nullptr; /* A/B: the main pass's mirror / glass / smooth-conductor vertices through the general list */
@@ -843,7 +847,9 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
          * carried (round 2's rule); default: whenever the kernel can run -- paths that meet glass or gold stay with the tail pass, which
          * takes them as tasks while the others, three quarters and more, cost it nothing */
         const char *e = getenv("DRT_TRACE_TAIL");
-        ctx->trace_tail = ctx->scene_in_lds && sets == 1 && tc > 0 && tc <= 8 && n_lights == 1 && ctx->trace_lds + extra <= 48 * 1024 && !(e && *e == '0') &&
+        /* the rule's 48 KB stays what it was of: the lanes' rows and the vignette row (6 KB) come on top */
+        const size_t lane_rows = (size_t)(TRACE_BLOCK / 64) * (TRACE_LANE_ROWS + 1) * 64 * 8;
+        ctx->trace_tail = ctx->scene_in_lds && sets == 1 && tc > 0 && tc <= 8 && n_lights == 1 && ctx->trace_lds + extra - lane_rows <= 48 * 1024 && !(e && *e == '0') &&
                           (all_simple || !(e && *e == '2'));
         ctx->tail_all_staged = ctx->trace_tail && all_simple;
         /* DRT_TAIL_RESUME=0: paths the trace kernel stops carrying are replayed from vertex 0 (the parity tests' A/B); it travels as a null

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / scratch / occupancy figures of libdrt_hip.so's kernels, from the compiler's own output: the device
 assembly of csrc/drt_launcher.hip (the Makefile's flags plus -S -gline-tables-only) and the kernel metadata at its end. Extra
-arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring | group] [--loops] [-D...]
+arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring | group] [--loops] [--waits] [--asm=FILE] [-D...]
 A filter that names a group (GROUPS below: `features`, `mattes`, `rays`, `rayfilm`, `update`, `build`, `material`) stands for the group's kernels.
 
 Columns: VGPRs, SGPRs, `sspill` / `vspill` = the metadata's .sgpr_spill_count / .vgpr_spill_count, scratch bytes per lane, static
@@ -10,7 +10,14 @@ them are SPILL LANE MOVES. On gfx9 a spilled scalar register is parked in a lane
 stores it, v_readlane_b32 with a constant lane brings it back, and both issue in the vector pipe. Counted are every v_writelane_b32,
 and every v_readlane_b32 with a constant lane whose source is a register some v_writelane_b32 of the kernel writes (a kernel's own
 v_readlane with a variable lane, or on a register it never writes lanes of, is its algorithm and not a spill).
---loops adds, per kernel, both counts by loop depth as the assembly's loop annotations nest the basic blocks."""
+--loops adds, per kernel, both counts by loop depth as the assembly's loop annotations nest the basic blocks.
+
+--waits adds, per kernel and per OUTERMOST loop (named by its header's label; `main` marks the one with the most instructions, a
+persistent kernel's path loop), what the loop waits for on the vector-memory counter: its vector-memory loads by kind (global_load,
+scratch_load, ...; atomics that return a value are listed apart), and every s_waitcnt with a vmcnt field, with the kind of the
+vector-memory instruction that stands before it in the text and the source line the wait belongs to. gfx9 has ONE vmcnt, counted in
+order for loads and stores alike, so a wait for a loaded value also waits for every store issued before the load: a reload behind a
+burst of record stores costs the stores' round trip. --asm=FILE reads a saved listing instead of compiling."""
 import os
 import re
 import subprocess
@@ -126,6 +133,54 @@ def _body_stats(body):
             "by_depth": {d: (valu[d], moves.get(d, 0)) for d in sorted(valu)}}
 
 
+_VMEM = re.compile(r"^(global|scratch|buffer|flat)_(load|store|atomic)")
+
+
+def _wait_stats(body):
+    """{outermost loop's header label: figures} for one kernel's text, and the label of the loop with the most instructions."""
+    outer, src, last = None, "", None
+    loops = {}
+    for line in body:
+        t = line.strip()
+        m = re.match(r"^\.?L?(BB\d+_\d+):", t)
+        if m or re.match(r"^; %bb\.\d+", t):
+            outer = None  # a basic block: which loop it is in follows on the label's line and the comment lines after it
+            label = m.group(1) if m else None
+        if t.startswith(";") or t.startswith(".LBB"):
+            if outer is None:  # the first annotation names the outermost loop: a parent of depth 1, else the block's own loop
+                m = re.search(r"Parent Loop (BB\d+_\d+) Depth=1\b", t) or re.search(r"in Loop: Header=(BB\d+_\d+) Depth=1\b", t)
+                if m:
+                    outer = m.group(1)
+                elif re.search(r"This (?:Inner )?Loop Header: Depth=1\b", t):
+                    outer = label
+            continue
+        if t.startswith(".loc"):
+            m = re.search(r";\s*(\S+?):(\d+):\d+", t)
+            if m:
+                src = "%s:%s" % (os.path.basename(m.group(1)), m.group(2))
+            continue
+        if not t or t.startswith("."):
+            continue
+        op = t.split()[0]
+        m = _VMEM.match(op)
+        kind = m.group(0) if m else None
+        if kind and kind.endswith("atomic"):
+            kind += "_ret" if re.search(r"\bsc0\b|\bglc\b", t) else ""
+        if outer is not None:
+            lp = loops.setdefault(outer, {"insts": 0, "loads": {}, "vmcnt_waits": 0, "waits": []})
+            lp["insts"] += 1
+            if kind and (kind.endswith("_load") or kind.endswith("_ret")):
+                lp["loads"][kind] = lp["loads"].get(kind, 0) + 1
+            m = re.match(r"^s_waitcnt\b.*\bvmcnt\((\d+)\)", t)
+            if m:
+                lp["vmcnt_waits"] += 1
+                lp["waits"].append((int(m.group(1)), last or "-", src))
+        if kind:
+            last = kind
+    main = max(loops, key=lambda k: loops[k]["insts"]) if loops else None
+    return loops, main
+
+
 def kernel_stats(extra=(), asm=None):
     """{demangled kernel name: figures}; see the module's docstring for what they are."""
     asm = asm if asm is not None else device_asm(extra)
@@ -146,6 +201,7 @@ def kernel_stats(extra=(), asm=None):
             b += 1
         body = lines[a + 1:b]
         st = _body_stats(body)
+        st["loops"], st["main_loop"] = _wait_stats(body)
         occ = None
         for l in lines[b:b + 400]:
             m = re.search(r";\s*Occupancy:\s*(\d+)", l)
@@ -160,11 +216,12 @@ def kernel_stats(extra=(), asm=None):
 
 
 def main(argv):
-    loops = "--loops" in argv
-    argv = [a for a in argv if a != "--loops"]
+    loops, waits = "--loops" in argv, "--waits" in argv
+    saved = [a[len("--asm="):] for a in argv if a.startswith("--asm=")]
+    argv = [a for a in argv if a not in ("--loops", "--waits") and not a.startswith("--asm=")]
     args = [a for a in argv if a.startswith("-")]
     flt = [s for a in argv if not a.startswith("-") for s in GROUPS.get(a, (a,))]
-    rows = kernel_stats(args)
+    rows = kernel_stats(args, asm=open(saved[0], encoding="utf-8", errors="replace").read() if saved else None)
     print("%-60s %5s %5s %6s %6s %7s %6s %4s %6s %6s" % ("kernel", "VGPRs", "SGPRs", "sspill", "vspill", "scratch", "LDS", "occ", "valu", "lanemv"))
     for name, r in rows.items():
         if flt and not any(f in name for f in flt):
@@ -175,6 +232,15 @@ def main(argv):
             print("    lane moves: %d v_writelane, %d v_readlane, parked in %s" % (r["lane_writes"], r["lane_reads"], " ".join(r["parked_in"]) or "-"))
             for d, (v, m) in r["by_depth"].items():
                 print("    loop depth %d: %5d vector instructions, %4d spill lane moves" % (d, v, m))
+        if waits:
+            for hdr, lp in r["loops"].items():
+                if not lp["loads"] and not lp["vmcnt_waits"]:
+                    continue
+                print("    loop %s%s: %d instructions; loads: %s; %d vmcnt waits" % (
+                    hdr, " (main)" if hdr == r["main_loop"] else "", lp["insts"],
+                    ", ".join("%d %s" % (n, k) for k, n in sorted(lp["loads"].items())) or "none", lp["vmcnt_waits"]))
+                for n, before, src in lp["waits"]:
+                    print("        vmcnt(%d) behind %-18s %s" % (n, before, src))
 
 
 if __name__ == "__main__":
