@@ -15,6 +15,8 @@
 #include "drt_build_kernels.h"
 #include "drt_material_kernels.h"
 #include "drt_depth_kernels.h"
+#include "drt_window_kernels.h"
+#include "drt_window_rule.h"
 #include "drt_owned.h"
 
 #include <algorithm>
@@ -131,7 +133,9 @@ struct drt_context
                                          and mirror vertices only, and those without a vertex */
     bool      tail_all_staged = false; /* ... and in this scene that is every path: the shade kernel's tail pass has nothing to replay */
     bool      tail_resume = false;     /* ... and where it is not, the tail pass resumes a path from the vertex the trace kernel carried it to (DRT_TAIL_RESUME=0: off) */
-    bool      dark_skip = true;        /* the shade kernel's instantiation that passes over samples worth 0 in pixels nothing has reached yet */
+    bool      dark_skip = true;        /* the shade kernel's instantiation that passes over samples worth 0 in pixels nothing has reached yet: for
+                                          pairs over the whole tile or a pixel list, from the TILE's vertices per path */
+    bool      dark_skip_win = true;    /* ... and for windowed pairs, from the live window's own (shade_dark()) */
     bool      no_fixed_lists = false;  /* DRT_NO_FIXED_LISTS, read when the context is created: the shade kernel's fixed-list bodies are not taken */
     bool      simple_bdsfs = false;    /* no material lists anything but bp_diffuse_bdsf, bp_glossy_bdsf, mirror_bdsf: the shade kernel without the Fresnel code */
     bool      no_closed_shade = false; /* DRT_NO_CLOSED_SHADE, read when the context is created: the closed shade instantiation is not taken */
@@ -258,6 +262,16 @@ struct drt_context
     PinnedBuf<uint32_t> h_sm_report;
     uint32_t  sm_bits = 0;                 /* the rounds of the call in progress that are still to be enqueued: bits of this device's B */
     struct Adaptive { drt_adaptive a; uint32_t n = 0, n_in = 0, k = 0, active = 0; int cur = 0; bool first = true, same = true; uint64_t redone = 0; } ad;
+    /* the live window (drt_window_rule.h, drt_window_kernels.h): dense pairs trace and shade its pixels only, on a compact staging film */
+    drt_camera h_camera{};                 /* the camera as the caller gave it (drt_create, drt_set_camera) */
+    bool      win_allowed = true;          /* not DRT_NO_LIVE_WINDOW, read when the context is created */
+    bool      win_dirty = true;            /* camera, surfaces or hierarchy have changed since `win` was worked out */
+    LiveWindow win{};                      /* in image pixels; whole: the rule does not apply */
+    uint32_t  wx0 = 0, wx1 = 0, wy0 = 0, wy1 = 0; /* ... and in tile columns and tile rows */
+    bool      win_part = false;            /* the window is a proper part of the tile (possibly empty): what a dense pair can use */
+    bool      win_open = false;            /* between window_open and window_close: the pairs in between are windowed ones */
+    DevBuf<double> d_win_film[3];          /* the staging film [win rows][win columns], laid out as the film */
+    uint64_t  win_film_pix = 0;            /* pixels it holds */
 };
 
 static size_t trace_lds_bytes(uint32_t n_surf, uint32_t n_lights, uint32_t n_mat)
@@ -870,6 +884,14 @@ static int build_device_scene(drt_context *ctx, const drt_scene *scene, double r
 
 static bool shade_simple(const drt_context *ctx) { return ctx->simple_bdsfs && ctx->spds_in_lds && ctx->shade_sets == 1; }
 
+/* DARK or not, per launch: a windowed pair (the live window is open and the launch has no pixel list) goes by the window's vertices
+ * per path, every other launch by the whole tile's -- so a whole-tile or list launch of a context that has a window runs what it ran
+ * before there was one. Same film either way. */
+static bool shade_dark(const drt_context *ctx, const ShadeParams &sp)
+{
+    return (ctx->win_open && !sp.pixel_list) ? ctx->dark_skip_win : ctx->dark_skip;
+}
+
 /* The closed instantiation is taken for a context's dense launches (an adaptive round's pixel list keeps the general one) when
  *   - every material's list is covered and no surface's material is a non-black body that lists nothing (closed_lists()), and the
  *     scene is not SIMPLE's (which is leaner still),
@@ -891,7 +913,7 @@ static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams 
 #define DRT_LAUNCH_CLOSED(DARK)                                                                                                                    \
     hipLaunchKernelGGL((drt_shade_kernel_closed<DARK>), dim3(grid), dim3(SHADE_BLOCK), ctx->shade_lds, ctx->stream, ctx->dsc, sp, ctx->d_records, \
                        ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
-        if (ctx->dark_skip) DRT_LAUNCH_CLOSED(true);
+        if (shade_dark(ctx, sp)) DRT_LAUNCH_CLOSED(true);
         else DRT_LAUNCH_CLOSED(false);
 #undef DRT_LAUNCH_CLOSED
         return 0;
@@ -902,12 +924,12 @@ static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams 
     /* SIMPLE: scenes without a Fresnel function, one wavelength set per lane, tables in LDS (shade_simple()) */
     if (NSETS == 1 && shade_simple(ctx))
     {
-        if (ctx->dark_skip) DRT_LAUNCH_SHADE(true, true, (NSETS == 1));
+        if (shade_dark(ctx, sp)) DRT_LAUNCH_SHADE(true, true, (NSETS == 1));
         else DRT_LAUNCH_SHADE(true, false, (NSETS == 1));
     }
-    else if (ctx->spds_in_lds && ctx->dark_skip) DRT_LAUNCH_SHADE(true, true, false);
+    else if (ctx->spds_in_lds && shade_dark(ctx, sp)) DRT_LAUNCH_SHADE(true, true, false);
     else if (ctx->spds_in_lds) DRT_LAUNCH_SHADE(true, false, false);
-    else if (ctx->dark_skip) DRT_LAUNCH_SHADE(false, true, false);
+    else if (shade_dark(ctx, sp)) DRT_LAUNCH_SHADE(false, true, false);
     else DRT_LAUNCH_SHADE(false, false, false);
 #undef DRT_LAUNCH_SHADE
     return 0;
@@ -1052,7 +1074,7 @@ static size_t pixels_bytes(const drt_context *ctx)
 }
 
 static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0,
-                         const uint32_t *list = nullptr, uint64_t list_len = 0);
+                         const uint32_t *list = nullptr, uint64_t list_len = 0, uint32_t col0 = 0, uint32_t cols = 0);
 
 /* waves of the trace-stage kernel that takes record blocks, for a launch of n_paths */
 static uint64_t trace_waves(const drt_context *ctx, uint64_t n_paths)
@@ -1086,6 +1108,61 @@ static void set_device_camera(drt_context *ctx, const drt_camera *camera)
     c.aperture_position = hv(camera->aperture_position); c.film_bottom_left = hv(camera->film_bottom_left);
     c.aperture_radius = camera->aperture_radius; c.focal_depth = camera->focal_depth;
     c.pixel_width = camera->pixel_width; c.pixel_height = camera->pixel_height;
+    ctx->h_camera = *camera;
+    ctx->win_dirty = true;
+}
+
+/* The live window of the context as it stands: from the host's surfaces and camera. After a device-mode surface update the host does
+ * not know the bounds: the whole tile, until a host-mode update (or a read-back) makes h_surfaces current again. */
+static LiveWindow live_window_of(const drt_surface *surfaces, size_t n_surf, const drt_material &escape, const drt_camera &camera, const drt_params &params)
+{
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    bool any = false;
+    for (size_t i = 0; i < n_surf; i += 1)
+    {
+        if (surfaces[i].type != DRT_GEO_SPHERE && surfaces[i].type != DRT_GEO_PLANE) continue; /* points are never intersected */
+        double l[3], h[3];
+        prim_bounds(surfaces[i], l, h);
+        for (int k = 0; k < 3; k += 1)
+        {
+            if (!(l[k] <= h[k])) return live_window_whole(params); /* a NaN coordinate */
+            lo[k] = std::min(lo[k], l[k]);
+            hi[k] = std::max(hi[k], h[k]);
+        }
+        any = true;
+    }
+    const bool escape_dark = escape.is_black_body != 0u && escape.is_emissive == 0u;
+    if (!any) return live_window_whole(params); /* nothing to bound: the rule does not apply */
+    return live_window_rule(lo, hi, camera, params, escape_dark);
+}
+
+static void window_refresh(drt_context *ctx)
+{
+    if (!ctx->win_dirty) return;
+    const drt_params &p = ctx->params;
+    ctx->win = live_window_whole(p);
+    if (ctx->win_allowed && !ctx->h_stale && ctx->dsc.escape_mat < ctx->ft_mats.size())
+        ctx->win = live_window_of(ctx->h_surfaces.data(), ctx->h_surfaces.size(), ctx->ft_mats[ctx->dsc.escape_mat], ctx->h_camera, p);
+    const LiveWindow &w = ctx->win;
+    if (w.x_lo >= w.x_hi || w.y_lo >= w.y_hi) ctx->wx0 = ctx->wx1 = ctx->wy0 = ctx->wy1 = 0;
+    else
+    {
+        ctx->wx0 = w.x_lo - p.x0;
+        ctx->wx1 = w.x_hi - p.x0;
+        /* tile row j is image row y0 + j row_stride */
+        ctx->wy0 = (w.y_lo - p.y0 + p.row_stride - 1) / p.row_stride;
+        ctx->wy1 = std::min<uint32_t>(p.tile_h, (w.y_hi - p.y0 + p.row_stride - 1) / p.row_stride);
+        if (ctx->wy0 >= ctx->wy1) ctx->wx0 = ctx->wx1 = ctx->wy0 = ctx->wy1 = 0;
+    }
+    ctx->win_part = !w.whole && !(ctx->wx0 == 0 && ctx->wx1 == p.tile_w && ctx->wy0 == 0 && ctx->wy1 == p.tile_h);
+    ctx->win_dirty = false;
+}
+
+/* whether dense pairs of this context go out windowed now */
+static bool window_in_use(drt_context *ctx)
+{
+    window_refresh(ctx);
+    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0;
 }
 
 static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camera *camera, const drt_params *params)
@@ -1111,6 +1188,15 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     ctx->ft_n_spd = scene->num_spds;
     ctx->ft_S = scene->num_wavelengths;
     ctx->ft_spds.assign(scene->spds, scene->spds + (size_t)scene->num_spds * scene->num_wavelengths);
+    if (const char *e = getenv("DRT_NO_LIVE_WINDOW")) ctx->win_allowed = atoi(e) == 0; /* A/B switch of the parity tests: same film either way */
+    if (ctx->xyz_mode)
+    {
+        /* the XYZ film adds observer row x spectral sum x row per pair: +0 for a pair worth +0 only where the observer's rows are finite */
+        const uint32_t rows[4] = {scene->cmf_rw, scene->cmf_x, scene->cmf_y, scene->cmf_z};
+        for (int k = 0; k < 4; k += 1)
+            for (uint32_t i = 0; i < scene->num_wavelengths; i += 1)
+                if (!std::isfinite(scene->spds[(size_t)rows[k] * scene->num_wavelengths + i])) ctx->win_allowed = false;
+    }
 
     set_device_camera(ctx, camera);
 
@@ -1229,10 +1315,22 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     ctx->est_blocks_per_path = (double)ctx->worst_blocks_per_path;
     if (npx * (uint64_t)ctx->worst_blocks_per_path * block_bytes > (256ull << 20) && !getenv("DRT_POOL_WORST_CASE"))
     {
-        /* the sample: tile rows 0, k, 2k, ... with k such that it holds about 128 k paths */
-        const uint32_t k = (uint32_t)std::max<uint64_t>(1, npx / (128u << 10));
+        /* the sample: tile rows 0, k, 2k, ... with k such that it holds about 128 k paths. Where dense pairs will go out windowed, the
+         * rows and columns of the live window: its paths are the ones that take blocks (a path outside takes none), 2.5 times the
+         * tile's average on the Cornell frame, in launches of 0.4 times the paths -- so b below stays blocks per TILE path, and the pool
+         * serves windowed and whole-tile launches of the same samples alike */
+        const bool win = window_in_use(ctx);
+        const uint64_t live_px = win ? (uint64_t)(ctx->wx1 - ctx->wx0) * (ctx->wy1 - ctx->wy0) : npx;
+        const uint32_t k = (uint32_t)std::max<uint64_t>(1, live_px / (128u << 10));
         drt_params pp = ctx->params;
-        pp.tile_h = (ctx->params.tile_h + k - 1) / k;
+        if (win && live_px > 0)
+        {
+            pp.x0 += ctx->wx0;
+            pp.tile_w = ctx->wx1 - ctx->wx0;
+            pp.y0 += ctx->wy0 * ctx->params.row_stride;
+            pp.tile_h = ctx->wy1 - ctx->wy0;
+        }
+        pp.tile_h = (pp.tile_h + k - 1) / k;
         pp.row_stride = ctx->params.row_stride * k;
         const uint64_t n_sample = (uint64_t)pp.tile_w * pp.tile_h;
         ctx->n_pix = n_sample;
@@ -1258,13 +1356,21 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         unsigned long long used = 0; /* blocks handed to paths (the cursor also counts the waves' part-used chunks) */
         HIP_TRY(hipMemcpyAsync(&used, ctx->d_counters + DRT_PAIR_COUNTERS + 5, sizeof(used), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        ctx->est_blocks_per_path = (double)used / (double)n_sample;
+        ctx->est_blocks_per_path = (double)used / (double)n_sample * ((double)live_px / (double)npx);
         {
             /* vertices per path on the sample: a scene whose paths average three vertices and more is a closed one -- hardly a pixel
              * stays dark there, and the shade kernel without the test for it is the faster one (config 3: 1767 against 1806-1837 ms) */
             unsigned long long cnt[3] = {0, 0, 0}; /* paths, scans, shaded vertices of the sample */
             HIP_TRY(hipMemcpy(cnt, ctx->d_counters + DRT_PAIR_COUNTERS, sizeof(cnt), hipMemcpyDeviceToHost));
-            if (cnt[0] > 0) ctx->dark_skip = (double)cnt[2] / (double)cnt[0] < 3.0;
+            /* the sample is the live window's where dense pairs go out windowed: its own figure decides for those pairs (hardly a pixel
+             * of the window stays dark), and the figure of the whole tile -- the paths outside the window have no vertex -- for every
+             * pair that is not windowed, as it did before there was a window */
+            if (cnt[0] > 0)
+            {
+                const double per_path = (double)cnt[2] / (double)cnt[0];
+                ctx->dark_skip_win = per_path < 3.0;
+                ctx->dark_skip = per_path * ((double)live_px / (double)npx) < 3.0;
+            }
         }
         ctx->d_records.reset();
         ctx->d_headers.reset();
@@ -1312,7 +1418,15 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     ctx->batch_spp = batch;
     ctx->pool_blocks = blocks_for(npx * batch);
     if (const char *e = getenv("DRT_POOL_BLOCKS")) /* test knob: a pool this small (never below one worst-case sample per pixel) */
-        ctx->pool_blocks = std::max<uint64_t>(blocks_worst_case(ctx, npx), std::min<uint64_t>(ctx->pool_blocks, strtoull(e, nullptr, 0)));
+    {
+        /* ... per pixel of what a dense pair launches: with the live window in use that is the window (a row of the tile at least), so
+         * that the knob makes windowed pairs run out as it makes whole-tile ones; the first pair that is not windowed grows the pool
+         * to the whole tile's floor (pool_floor) */
+        const bool win = window_in_use(ctx); /* (works the window out where the pool sample above has not) */
+        const uint64_t live = (uint64_t)(ctx->wx1 - ctx->wx0) * (ctx->wy1 - ctx->wy0);
+        const uint64_t floor_px = win ? std::min<uint64_t>(npx, std::max<uint64_t>(live, params->tile_w)) : npx;
+        ctx->pool_blocks = std::max<uint64_t>(blocks_worst_case(ctx, floor_px), std::min<uint64_t>(ctx->pool_blocks, strtoull(e, nullptr, 0)));
+    }
     if (ctx->pool_blocks >= 0xFFFFFFF0ull) return fail(-3, "record pool of %llu blocks: block numbers are 32 bits", (unsigned long long)ctx->pool_blocks);
     HIP_TRY(ctx->d_records.need(ctx->pool_blocks * ctx->block_words));
     HIP_TRY(ctx->d_headers.need((size_t)npx * batch * REC_HEADER_WORDS));
@@ -1323,7 +1437,7 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     }
     if (ctx->tail_count) HIP_TRY(ctx->d_tail_stage.need((size_t)npx * batch * ctx->tail_count));
     if (ctx->tail_count && ctx->tail_resume) HIP_TRY(ctx->d_tail_resume.need((size_t)npx * batch * ctx->tail_count));
-    if (const char *e = getenv("DRT_DARK_SKIP")) ctx->dark_skip = atoi(e) != 0; /* A/B switch of the parity tests: same film either way */
+    if (const char *e = getenv("DRT_DARK_SKIP")) ctx->dark_skip = ctx->dark_skip_win = atoi(e) != 0; /* A/B switch of the parity tests: same film either way */
     if (getenv("DRT_VERBOSE"))
         fprintf(stderr, "drt: %d CUs, trace %d blocks/CU (lds %zu), shade %d blocks/CU (lds %zu), batch %u, %.3f blocks/path measured (worst %u), pool %.2f GB\n",
                 prop.multiProcessorCount, per_cu, ctx->trace_lds, s_per_cu, ctx->shade_lds, ctx->batch_spp, ctx->est_blocks_per_path,
@@ -1432,10 +1546,102 @@ __global__ void drt_mark_pair_kernel(unsigned long long *totals, unsigned long l
     }
 }
 
+static WindowParams window_params(const drt_context *ctx)
+{
+    WindowParams wp{};
+    wp.tile_w = ctx->params.tile_w;
+    wp.wx0 = ctx->wx0; wp.wx1 = ctx->wx1; wp.wy0 = ctx->wy0; wp.wy1 = ctx->wy1;
+    wp.S = ctx->dsc.S;
+    wp.xyz = ctx->xyz_mode ? 1u : 0u;
+    wp.tail = ctx->tail_count ? 1u : 0u;
+    wp.draws = ctx->params.pixel_scheme == DRT_FILM_SAMPLE_RANDOM ? 2u : 0u;
+    return wp;
+}
+
+/* While the window is open: the window's part of tile rows [row0, row0 + rows) (rows == 0: of the whole tile) into the staging film
+ * (to_stage), or back. Dense pairs of those rows go in between. */
+static int window_copy(drt_context *ctx, bool to_stage, uint32_t row0 = 0, uint32_t rows = 0)
+{
+    if (!ctx->win_open) return 0;
+    WindowParams wp = window_params(ctx);
+    if (rows == 0) { row0 = 0; rows = ctx->params.tile_h; }
+    const uint32_t lo = std::max(row0, wp.wy0), hi = std::min(row0 + rows, wp.wy1);
+    if (hi <= lo || wp.wx1 <= wp.wx0) return 0;
+    const uint64_t stage0 = (uint64_t)(lo - wp.wy0) * (wp.wx1 - wp.wx0); /* the rows' first pixel in the staging film */
+    wp.wy0 = lo; wp.wy1 = hi;
+    const uint64_t pix = (uint64_t)(wp.wx1 - wp.wx0) * (hi - lo);
+    double *const film[3] = {ctx->d_pixels, ctx->d_avgs, ctx->d_vars};
+    const uint32_t words[3] = {ctx->xyz_mode ? (uint32_t)XYZ_FILM_WORDS : wp.S + 1u, wp.S, wp.S};
+    for (int f = 0; f < (ctx->xyz_mode ? 1 : 3); f += 1)
+    {
+        const uint64_t n = pix * words[f];
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((n + WINDOW_BLOCK - 1) / WINDOW_BLOCK, 1u << 16);
+        hipLaunchKernelGGL(drt_window_copy_kernel, dim3(grid), dim3(WINDOW_BLOCK), 0, ctx->stream, film[f], ctx->d_win_film[f] + stage0 * words[f], wp, words[f],
+                           to_stage ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+/* Before the dense pairs of a render call: if they can use the live window, the pairs up to window_close are windowed ones, on the
+ * staging film (window_copy moves the rows). It grows when the window has (after a camera move); that waits for the stream. */
+static int window_open(drt_context *ctx)
+{
+    ctx->win_open = false;
+    if (!window_in_use(ctx)) return 0;
+    const uint64_t pix = (uint64_t)(ctx->wx1 - ctx->wx0) * (ctx->wy1 - ctx->wy0);
+    if (pix > ctx->win_film_pix)
+    {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        const size_t S = ctx->dsc.S;
+        ctx->win_film_pix = 0;
+        HIP_TRY(ctx->d_win_film[0].remake(pix * (ctx->xyz_mode ? (size_t)XYZ_FILM_WORDS : S + 1)));
+        if (!ctx->xyz_mode)
+        {
+            HIP_TRY(ctx->d_win_film[1].remake(pix * S));
+            HIP_TRY(ctx->d_win_film[2].remake(pix * S));
+        }
+        ctx->win_film_pix = pix;
+    }
+    ctx->win_open = true;
+    return 0;
+}
+
+static void window_close(drt_context *ctx) { ctx->win_open = false; }
+
+/* A pair over the whole tile, or over a pixel list, counts on a pool that holds one worst-case sample of every tile pixel (what
+ * redo_batches launches). Only the DRT_POOL_BLOCKS test knob makes a pool smaller than that, sized for the window's pixels: the
+ * first pair that is not windowed makes it the tile's. Waits for the stream: nothing in flight reads the records then. */
+static int pool_floor(drt_context *ctx)
+{
+    const uint64_t floor_blocks = blocks_worst_case(ctx, ctx->n_pix);
+    if (ctx->pool_blocks >= floor_blocks) return 0;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx->d_records.remake(floor_blocks * ctx->block_words));
+    ctx->pool_blocks = floor_blocks;
+    return 0;
+}
+
+/* behind a windowed pair's shade kernel: the pair's pixels outside the window (drt_window_fill_kernel) */
+static int enqueue_window_fill(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t row0, uint32_t rows)
+{
+    WindowParams wp = window_params(ctx);
+    wp.row0 = row0; wp.rows = rows;
+    wp.first_sample = first_sample; wp.n_samples = n;
+    const uint64_t threads = (uint64_t)rows * wp.tile_w * (wp.xyz ? 7u : wp.S + 1u);
+    const uint64_t grid = (threads + WINDOW_BLOCK - 1) / WINDOW_BLOCK;
+    if (grid == 0) return 0;
+    if (grid >= 0x7FFFFFFFull) return fail(-1, "tile too large for the live window's fill pass");
+    hipLaunchKernelGGL(drt_window_fill_kernel, dim3((uint32_t)grid), dim3(WINDOW_BLOCK), 0, ctx->stream, ctx->d_pixels, ctx->d_avgs, ctx->d_vars, wp,
+                       (const uint32_t *)(ctx->d_counters + DRT_NUM_COUNTERS + 5), ctx->d_counters + DRT_PAIR_COUNTERS);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 /* The trace stage of one kernel pair over samples [first_sample, first_sample + n) of every tile pixel: work queues and the
  * pool cursor reset, then drt_trace_kernel (scene in LDS) or drt_primary_kernel + drt_bounce_kernel (scene behind the hierarchy). */
 static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0, uint32_t rows, uint32_t stride,
-                         const uint32_t *list, uint64_t list_len)
+                         const uint32_t *list, uint64_t list_len, uint32_t col0, uint32_t cols)
 {
     const drt_params &p = ctx->params;
     TraceParams tp{};
@@ -1443,15 +1649,17 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
      * staging buffers are indexed from the launch's first pixel */
     const bool whole = rows == 0;
     if (whole) { row0 = 0; rows = p.tile_h; }
-    tp.width = p.width; tp.height = p.height; tp.x0 = p.x0; tp.y0 = p.y0 + row0 * p.row_stride;
-    tp.tile_w = p.tile_w; tp.tile_h = rows; tp.row_stride = p.row_stride;
+    /* columns [col0, col0 + cols) of those rows (cols == 0: all of them): a windowed pair's tile is the live window's part of the rows */
+    if (cols == 0) { col0 = 0; cols = p.tile_w; }
+    tp.width = p.width; tp.height = p.height; tp.x0 = p.x0 + col0; tp.y0 = p.y0 + row0 * p.row_stride;
+    tp.tile_w = cols; tp.tile_h = rows; tp.row_stride = p.row_stride;
     tp.first_sample = first_sample;
     tp.n_samples = n;
     tp.max_depth = p.max_depth;
     tp.pixel_scheme = p.pixel_scheme;
     tp.record_hits = (p.flags & DRT_FLAG_RECORD_HITS) ? 1u : 0u;
     tp.seed = p.seed;
-    tp.n_pix = list ? list_len : whole ? ctx->n_pix : (uint64_t)rows * p.tile_w; /* a list: its pixels, anywhere in the whole tile */
+    tp.n_pix = list ? list_len : (whole && cols == p.tile_w) ? ctx->n_pix : (uint64_t)rows * cols; /* a list: its pixels, anywhere in the whole tile */
     tp.pixel_list = list;
     tp.sample_base = list ? ctx->d_counts : nullptr;
     tp.n_paths = tp.n_pix * n;
@@ -1530,8 +1738,23 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     if (rc) return rc;
     ctx->film_gen += 1;
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
-    if ((rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, row0, rows, stride, list, list_len))) return rc;
-    const uint64_t n_pix = list ? list_len : rows ? (uint64_t)rows * ctx->params.tile_w : ctx->n_pix; /* pixels of this launch */
+    /* A windowed pair (between window_open and window_close): the kernels' tile is the live window's part of the pair's rows, their
+     * film the staging film; the pair's other pixels are drt_window_fill_kernel's, below. Nothing live in these rows: no kernels. */
+    const bool windowed = ctx->win_open && !list;
+    const uint32_t t_row0 = rows ? row0 : 0u, t_rows = rows ? rows : ctx->params.tile_h; /* the pair's tile rows */
+    uint32_t l_row0 = t_row0, l_rows = t_rows, l_cols = ctx->params.tile_w;
+    if (windowed)
+    {
+        const uint32_t lo = std::max(t_row0, ctx->wy0), hi = std::min(t_row0 + t_rows, ctx->wy1);
+        l_row0 = lo;
+        l_rows = hi > lo ? hi - lo : 0u;
+        l_cols = ctx->wx1 - ctx->wx0;
+    }
+    const bool nothing = windowed && (l_rows == 0u || l_cols == 0u);
+    if (!windowed && (rc = pool_floor(ctx))) return rc;
+    if (windowed) { if (!nothing && (rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, l_row0, l_rows, stride, nullptr, 0, ctx->wx0, l_cols))) return rc; }
+    else if ((rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, row0, rows, stride, list, list_len))) return rc;
+    const uint64_t n_pix = list ? list_len : windowed ? (uint64_t)l_rows * l_cols : rows ? (uint64_t)rows * ctx->params.tile_w : ctx->n_pix; /* pixels of this launch */
     const uint64_t pix0 = (rows && !list) ? (uint64_t)row0 * ctx->params.tile_w : 0;                  /* its first pixel in the tile */
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
 
@@ -1614,18 +1837,25 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     }
     uint32_t sgrid = (uint32_t)std::min<uint64_t>(((uint64_t)sp.n_items + SHADE_WAVES - 1) / SHADE_WAVES, (uint64_t)ctx->shade_grid_cap);
     const size_t S_ = ctx->dsc.S;
-    double *const film[3] = {ctx->d_pixels + pix0 * (ctx->xyz_mode ? (size_t)XYZ_FILM_WORDS : S_ + 1),
-                             ctx->d_avgs ? ctx->d_avgs + pix0 * S_ : nullptr, ctx->d_vars ? ctx->d_vars + pix0 * S_ : nullptr};
-    rc = launch_shade(ctx, sgrid, sp, film);
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
+    const size_t film_words = ctx->xyz_mode ? (size_t)XYZ_FILM_WORDS : S_ + 1;
+    const uint64_t stage0 = windowed ? (uint64_t)(l_row0 - std::min(l_row0, ctx->wy0)) * l_cols : 0; /* the launch's first pixel in the staging film */
+    double *const film[3] = {windowed ? ctx->d_win_film[0] + stage0 * film_words : ctx->d_pixels + pix0 * film_words,
+                             windowed ? (ctx->xyz_mode ? nullptr : ctx->d_win_film[1] + stage0 * S_) : ctx->d_avgs ? ctx->d_avgs + pix0 * S_ : nullptr,
+                             windowed ? (ctx->xyz_mode ? nullptr : ctx->d_win_film[2] + stage0 * S_) : ctx->d_vars ? ctx->d_vars + pix0 * S_ : nullptr};
+    if (!nothing)
+    {
+        rc = launch_shade(ctx, sgrid, sp, film);
+        if (rc) return rc;
+        HIP_TRY(hipGetLastError());
+    }
     if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, pix0))) return rc;
+    if (windowed && (rc = enqueue_window_fill(ctx, first_sample, n, t_row0, t_rows))) return rc;
     const uint64_t seq = ctx->next_seq++;
     hipLaunchKernelGGL(drt_mark_pair_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_counters, (unsigned long long)seq);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[2], ctx->stream));
     ctx->ev_paths.resize(ctx->ev_used / 3, 0.0);
-    ctx->ev_paths[ctx->ev_used / 3 - 1] = (double)n_pix * (double)n;
+    ctx->ev_paths[ctx->ev_used / 3 - 1] = (double)(windowed ? (uint64_t)t_rows * ctx->params.tile_w : n_pix) * (double)n; /* (a windowed pair renders all its rows' pixels) */
     ctx->inflight.push_back({first_sample, n, seq, row0, rows, hits_sample_offset, stride, list, list_len});
     return 0;
 }
@@ -1642,17 +1872,35 @@ static int redo_batches(drt_context *ctx, uint64_t last_good_seq)
     /* samples per launch that fit the pool whatever the paths do (one always does: the pool is never smaller, create_impl) */
     uint32_t safe = 1;
     while (safe < ctx->batch_spp && blocks_worst_case(ctx, ctx->n_pix * (uint64_t)(safe + 1)) <= ctx->pool_blocks) safe += 1;
+    /* Dense pairs are replayed as windowed pairs where the context can use the live window (the pair that ran out and everything
+     * behind it, fills included, did nothing; the staging film went back as the last complete pair left it). A render call that
+     * synchronises does so before it has staged anything, so the film is whole here, whether the window is open already or not. */
+    bool lists = false; /* (pixel-list pairs write the film itself: no staging film around them) */
+    for (const auto &b : todo) lists = lists || b.list != nullptr;
+    const bool was_open = ctx->win_open;
+    int rc = 0;
+    if (lists) window_close(ctx);
+    else if (!was_open) rc = window_open(ctx);
+    if (!rc) rc = window_copy(ctx, true);
+    if (rc) { ctx->win_open = was_open; return rc; }
     for (const auto &b : todo)
     {
         ctx->redone_batches += 1;
         for (uint32_t done = 0; done < b.n_samples; done += safe)
         {
             /* (the hit log is indexed by sample offset within the caller's drt_render call: the batch remembers its own) */
-            int rc = enqueue_pair(ctx, b.first_sample + done, std::min(safe, b.n_samples - done), b.hits_sample_offset + done, b.row0, b.rows, 0,
-                                  b.list, b.list_len);
-            if (rc) return rc;
+            rc = enqueue_pair(ctx, b.first_sample + done, std::min(safe, b.n_samples - done), b.hits_sample_offset + done, b.row0, b.rows, 0,
+                              b.list, b.list_len);
+            if (rc) break;
         }
+        if (rc) break;
     }
+    {
+        const int rc_back = window_copy(ctx, false);
+        if (!rc) rc = rc_back;
+        ctx->win_open = was_open;
+    }
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     unsigned long long st[4] = {0, 0, 0, 0};
     HIP_TRY(hipMemcpy(st, work + 4, sizeof(st), hipMemcpyDeviceToHost));
@@ -1677,12 +1925,14 @@ static int enqueue_blocks(drt_context *ctx, uint32_t first_sample, uint32_t num_
     for (uint32_t r0 = 0; r0 < H; r0 += per)
     {
         const uint32_t rows = std::min(per, H - r0);
-        for (uint32_t at = 0; at < num_samples; at += n_blk)
+        int rc = window_copy(ctx, true, r0, rows); /* (an open live window: the block's part of it, there and back around the block's pairs) */
+        for (uint32_t at = 0; at < num_samples && !rc; at += n_blk)
         {
             const uint32_t n = std::min(n_blk, num_samples - at);
-            int rc = enqueue_pair(ctx, first_sample + at, n, 0, r0, rows, n);
-            if (rc) return rc;
+            rc = enqueue_pair(ctx, first_sample + at, n, 0, r0, rows, n);
         }
+        const int rc_back = window_copy(ctx, false, r0, rows);
+        if (rc || rc_back) return rc ? rc : rc_back;
         if (done)
         {
             done->emplace_back();
@@ -1703,7 +1953,21 @@ extern "C" int drt_render(drt_context *ctx, uint32_t first_sample, uint32_t num_
     return render_impl(ctx, first_sample, num_samples);
 }
 
+static int render_pairs(drt_context *ctx, uint32_t first_sample, uint32_t num_samples);
+
+/* the call's dense pairs, between the live window's two film copies where the context can use it */
 static int render_impl(drt_context *ctx, uint32_t first_sample, uint32_t num_samples)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    (void)hipGetLastError(); /* (as render_pairs: a stale error of an earlier, unrelated call) */
+    int rc = window_open(ctx);
+    if (rc) return rc;
+    rc = render_pairs(ctx, first_sample, num_samples);
+    window_close(ctx);
+    return rc;
+}
+
+static int render_pairs(drt_context *ctx, uint32_t first_sample, uint32_t num_samples)
 {
     HIP_TRY(hipSetDevice(ctx->device));
     (void)hipGetLastError(); /* drop a stale error of an earlier, unrelated call: launches below are checked against a clean slate */
@@ -1738,12 +2002,11 @@ static int render_impl(drt_context *ctx, uint32_t first_sample, uint32_t num_sam
     /* (pairs of equal size here too: 100 samples where 64 fit are 50 + 50) */
     const uint32_t n_pairs = (num_samples + ctx->batch_spp - 1) / ctx->batch_spp;
     const uint32_t each = n_pairs ? (num_samples + n_pairs - 1) / n_pairs : 1u;
-    for (uint32_t done = 0; done < num_samples; done += each)
-    {
-        int rc = enqueue_pair(ctx, first_sample + done, std::min(each, num_samples - done), done);
-        if (rc) return rc;
-    }
-    return 0;
+    int rc = window_copy(ctx, true);
+    for (uint32_t done = 0; done < num_samples && !rc; done += each)
+        rc = enqueue_pair(ctx, first_sample + done, std::min(each, num_samples - done), done);
+    const int rc_back = window_copy(ctx, false);
+    return rc ? rc : rc_back;
 }
 
 static int synchronize_impl(drt_context *ctx);
@@ -1943,6 +2206,31 @@ extern "C" int drt_get_stats(drt_context *ctx, drt_stats *out)
 }
 
 extern "C" uint32_t drt_batch_spp(drt_context *ctx) { return ctx ? ctx->batch_spp : 0; }
+
+static void window_out(const LiveWindow &w, uint32_t out[4]) { out[0] = w.x_lo; out[1] = w.x_hi; out[2] = w.y_lo; out[3] = w.y_hi; }
+
+/* host only, like drt_bvh_stats: no device is touched */
+extern "C" int drt_live_window_of(const drt_scene *scene, const drt_camera *camera, const drt_params *params, uint32_t out[4])
+{
+    g_last_error.clear();
+    if (!scene || !camera || !params || !out) return fail(-1, "drt_live_window_of: null argument");
+    if (scene->escape_material >= scene->num_materials) return fail(-2, "base/escape material index out of range");
+    if ((uint64_t)params->x0 + params->tile_w > params->width ||
+        (params->tile_h && (uint64_t)params->y0 + (uint64_t)(params->tile_h - 1) * (params->row_stride ? params->row_stride : 1) >= params->height))
+        return fail(-1, "tile does not fit the %ux%u image", params->width, params->height);
+    drt_params p = *params;
+    if (p.row_stride == 0) p.row_stride = 1;
+    window_out(live_window_of(scene->surfaces, scene->num_surfaces, scene->materials[scene->escape_material], *camera, p), out);
+    return 0;
+}
+
+extern "C" int drt_live_window(drt_context *ctx, uint32_t out[4])
+{
+    if (!ctx || !out) return fail(-1, "drt_live_window: null argument");
+    window_refresh(ctx);
+    window_out(ctx->win, out);
+    return 0;
+}
 
 extern "C" int drt_shade_instantiation(const drt_context *ctx)
 {
@@ -2369,7 +2657,13 @@ extern "C" int drt_render_tile(const drt_scene *scene, const drt_camera *camera,
         {
             if ((rc = drt_render(ctx, params->first_sample, params->spp))) break;
         }
-        else if ((rc = enqueue_blocks(ctx, params->first_sample, params->spp, n_blocks, &block_done))) break;
+        else
+        {
+            if ((rc = window_open(ctx))) break;
+            rc = enqueue_blocks(ctx, params->first_sample, params->spp, n_blocks, &block_done);
+            window_close(ctx);
+            if (rc) break;
+        }
         if (params->flags & DRT_FLAG_FILM_ZERO)
         {
             /* Buffers that come zero-filled (the reference's alloc()) have usually never been touched: the download would then
@@ -4510,6 +4804,7 @@ static int update_read_back(drt_context *ctx)
     if (!ctx->h_surfaces.empty())
         HIP_TRY(hipMemcpy(ctx->h_surfaces.data(), ctx->d_raw, ctx->h_surfaces.size() * sizeof(drt_surface), hipMemcpyDeviceToHost));
     ctx->h_stale = false;
+    ctx->win_dirty = true; /* the host knows the bounds again */
     return 0;
 }
 
@@ -4573,6 +4868,7 @@ static int update_commit(drt_context *ctx, uint32_t first, uint32_t count, Pendi
 {
     HIP_TRY(hipSetDevice(ctx->device));
     std::copy(ctx->h_stage.get(), ctx->h_stage + count, ctx->h_surfaces.begin() + first);
+    ctx->win_dirty = true;
     HIP_TRY(hipMemcpyAsync(ctx->d_raw + first, ctx->h_stage, (size_t)count * sizeof(drt_surface), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->upd_ev[2], ctx->stream));
     ctx->stage_busy = true;
@@ -4621,6 +4917,7 @@ extern "C" int drt_update_surfaces(drt_context *ctx, const drt_surface *surfaces
         HIP_TRY(hipMemcpy2DAsync((char *)(ctx->d_raw + first) + 8, sizeof(drt_surface), (const char *)surfaces + 8, sizeof(drt_surface), sizeof(drt_surface) - 8, count,
                                  hipMemcpyDeviceToDevice, ctx->stream));
         ctx->h_stale = true;
+        ctx->win_dirty = true; /* the host cannot know the bounds: the live window is the whole tile until it does */
         if ((rc = update_enqueue(ctx))) return rc;
         ctx->extent_known = !ctx->use_bvh;
         ctx->upd_check = ctx->use_bvh;
@@ -5185,6 +5482,7 @@ static int hierarchy_enqueue(drt_context *ctx)
         ctx->hb_mirror_pending = true;
     }
     ctx->hb_builds += 1;
+    ctx->win_dirty = true; /* (the live window is worked out again: from the host's surfaces, where those are current) */
     ctx->hb_built_by = 1;
     ctx->refits = 0;
     return 0;

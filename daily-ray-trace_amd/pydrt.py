@@ -748,6 +748,9 @@ def hip_lib():
             L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_get_hierarchy_report.argtypes = [C.c_void_p, C.POINTER(HierarchyReport)]
             L.drt_read_hierarchy.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32]
+        if hasattr(L, "drt_live_window_of"):  # (as drt_selftest_path_ids below)
+            L.drt_live_window_of.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_uint32)]
+            L.drt_live_window.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.drt_render_tile.argtypes = [C.POINTER(Scene), C.POINTER(Camera), C.POINTER(Params), C.POINTER(C.c_double),
                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Stats)]
         L.drt_selftest_arith.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -793,7 +796,8 @@ HIP_SYMBOLS = ["drt_shade_instantiation",
                "drt_update_spectra", "drt_update_materials", "drt_group_update_spectra", "drt_group_update_materials",
                "drt_bind_depth_cuts", "drt_read_depth_film", "drt_depth_film_device_ptrs", "drt_read_depth_xyz", "drt_read_depth_bgra",
                "drt_group_bind_depth_cuts", "drt_group_read_depth_film",
-               "drt_render_sample_map", "drt_group_render_sample_map"]
+               "drt_render_sample_map", "drt_group_render_sample_map",
+               "drt_live_window_of", "drt_live_window"]
 
 MAX_DEPTH_CUTS = 8  # DRT_MAX_DEPTH_CUTS
 
@@ -823,6 +827,15 @@ def _check(rc, what):
         raise RuntimeError("%s failed (%d): %s" % (what, rc, hip_lib().drt_last_error().decode()))
 
 
+def live_window_of(bundle, params, camera=None):
+    """(x_lo, x_hi, y_lo, y_hi) in image pixels: drt_live_window_of, the rectangle outside which no camera ray reaches the scene.
+    Host only (no GPU). camera: another one than the bundle's."""
+    out = (C.c_uint32 * 4)()
+    cam = bundle.camera if camera is None else camera
+    _check(hip_lib().drt_live_window_of(C.byref(bundle.scene), C.byref(cam), C.byref(params), out), "drt_live_window_of")
+    return tuple(int(v) for v in out)
+
+
 class Renderer:
     """Session form of the C-ABI: scene resident on the device, film accumulated on the device."""
 
@@ -846,6 +859,12 @@ class Renderer:
             self.close()
         except Exception:
             pass
+
+    def live_window(self):
+        """(x_lo, x_hi, y_lo, y_hi) in image pixels: the context's live window as it stands (drt_live_window)"""
+        out = (C.c_uint32 * 4)()
+        _check(self.L.drt_live_window(self.ctx, out), "drt_live_window")
+        return tuple(int(v) for v in out)
 
     def bind_film(self, d_pixels, d_avgs, d_vars):
         _check(self.L.drt_bind_film(self.ctx, d_pixels, d_avgs, d_vars), "drt_bind_film")

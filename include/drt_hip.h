@@ -868,6 +868,24 @@ int drt_get_hierarchy_report(drt_context *ctx, drt_hierarchy_report *out);
  * count[2]), leaf_surface the surface index of every leaf slot. n_nodes and n_leaf must be the report's counts. Synchronises. */
 int drt_read_hierarchy(drt_context *ctx, void *nodes, uint32_t n_nodes, uint32_t *leaf_surface, uint32_t n_leaf);
 
+/*
+ * The live window: the rectangle of image pixels [x_lo, x_hi) x [y_lo, y_hi), clipped to the tile, outside which no camera ray can
+ * reach the scene, whatever the pixel draws (csrc/drt_window_rule.h; DESIGN.md section 3 has the proof). out = {x_lo, x_hi, y_lo,
+ * y_hi}; x_lo == x_hi: empty, the scene is wholly off the tile. It is the whole tile -- {x0, x0 + tile_w, y0, the tile's last image
+ * row + 1} -- where the rule does not apply: a lens camera (aperture_radius > 0), an escape material that emits or is no black body,
+ * a scene corner not in front of the pinhole, a coordinate that is not finite.
+ * Dense renders (drt_render, drt_render_tile, the group forms) trace and shade the window's pixels only; every other tile pixel gets,
+ * per kernel pair, what its samples -- all worth +0 -- leave on the film, and its paths are counted in drt_stats as the reference
+ * counts them (a path, one closest-hit scan, the pixel's draws). Films, statistics and draw counts are bit for bit what they are
+ * without it; DRT_NO_LIVE_WINDOW=1, read by drt_create, turns it off. Not used with DRT_FLAG_RECORD_HITS, pixel lists (adaptive
+ * rounds, sample maps), a bound ray table or bound depth cuts.
+ */
+/* Host only, like drt_bvh_stats: the rule on the scene and camera as given. */
+int drt_live_window_of(const drt_scene *scene, const drt_camera *camera, const drt_params *params, uint32_t out[4]);
+/* The live context's: follows drt_set_camera, host-mode drt_update_surfaces and hierarchy rebuilds; after a device-mode surface update
+ * the host does not know the scene's bounds, and the window is the whole tile until a host-mode update. */
+int drt_live_window(drt_context *ctx, uint32_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif
