@@ -20,6 +20,7 @@
 
 #include "drt_device.h"
 #include "drt_build_rule.h"
+#include "drt_stash_rule.h"
 #include <type_traits>
 #include "../../include/drt_hip.h"
 
@@ -1178,6 +1179,17 @@ __device__ __forceinline__ void lane_word_add(uint32_t *w, uint32_t v)
 {
     (void)__hip_atomic_fetch_add(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); /* one LDS add, nothing returned */
 }
+/* The ray stash (the STASH form of trace_paths, drt_stash_rule.h): a wave's rows [TRACE_STASH_ROWS][64 entries] of 8 bytes behind all
+ * waves' lane and tail rows, and behind each wave's rows the (pixel, sample) pair of the id its next fill starts at (16 bytes) */
+#define TRACE_ST_OX 0u
+#define TRACE_ST_DX 3u
+#define TRACE_ST_RS 6u    /* the generator's state after the camera's draws */
+#define TRACE_ST_VIG 7u   /* the vignette */
+#define TRACE_ST_Q 8u     /* the launch pixel */
+#define TRACE_ST_SD 9u    /* low half: the sample within the launch; high half: the draws the camera ray took */
+#define TRACE_STASH_ROWS 10u
+#define TRACE_STASH_WAVE_WORDS (TRACE_STASH_ROWS * 64u + 2u)
+#define TRACE_STASH_BYTES ((size_t)(TRACE_BLOCK / 64) * TRACE_STASH_WAVE_WORDS * 8u)
 #define DRT_TRACE_TAIL_MAX 8u /* tail wavelengths the trace kernel carries at most (the launcher's rule: S mod 64 <= 8) */
 #ifndef DRT_TRACE_WAVES_PER_SIMD
 #define DRT_TRACE_WAVES_PER_SIMD 3 /* register budget: launch_bounds' 2nd argument is waves per SIMD */
@@ -1189,15 +1201,16 @@ __device__ __forceinline__ void lane_word_add(uint32_t *w, uint32_t v)
 #ifdef DRT_BRANCH_STATS
 /* Measurement build only (-DDRT_BRANCH_STATS, never in the product): per wave-iteration that shades, which samplers and evaluator
  * branches its lanes take. The last wave of a launch to finish prints the launch's totals and clears them. */
-#define DRT_BS_WORDS 20 /* [16], [17]: plane steps of the closest-hit scans and how many the whole wave skipped; [18], [19]: of the shadow scans */
+#define DRT_BS_WORDS 23 /* [16], [17]: plane steps of the closest-hit scans and how many the whole wave skipped; [18], [19]: of the shadow scans;
+                           [20], [21]: wave-iterations that enter the path-start block and the lanes they start; [22]: all wave-iterations */
 __device__ unsigned long long drt_branch_stats[DRT_BS_WORDS];
 __device__ unsigned int drt_branch_waves_done;
 #endif
 
 /* The kernel's body, shared by the camera entry points (drt_trace_kernel, RAYS = false: k_rt is not read) and the ray-mode ones
  * (drt_trace_rays_kernel): they differ in the path's first ray and in the factor the header carries, nothing else. */
-template <bool SCENE_IN_LDS, bool TAIL, bool LIST, bool RAYS>
-__device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
+template <bool SCENE_IN_LDS, bool TAIL, bool LIST, bool RAYS, bool STASH>
+__device__ __forceinline__ void trace_paths_form(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
                                             uint64_t *records, uint64_t *headers,
                                             int32_t *k_hits, unsigned long long *k_counters,
                                             unsigned long long *k_work_counter, const DevRayTable &k_rt)
@@ -1230,6 +1243,7 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
     SceneView sv;
     double *l_spd_tail = nullptr, *tail_state = nullptr;
     double *lane_area = nullptr;
+    double *stash = nullptr; /* STASH: the wave's rows, entry 0 */
     uint32_t *lane_words = nullptr;
     uint32_t TR, max_depth, vertex_words, block_words;
     bool tail_on, record_hits;
@@ -1320,6 +1334,7 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
     }
     /* a wave's lane rows, [TRACE_LANE_ROWS][64 lanes] of 8 bytes (see TRACE_LW_*), and behind them its tail rows: one address
      * register per lane, every row an immediate offset from it */
+    if (STASH) stash = lane_area + (size_t)(TRACE_BLOCK / 64) * ((TRACE_LANE_ROWS + (tail_on ? 1u + 2u * TR : 0u)) * 64u) + (size_t)(threadIdx.x >> 6) * TRACE_STASH_WAVE_WORDS;
     lane_area += (size_t)(threadIdx.x >> 6) * ((TRACE_LANE_ROWS + (tail_on ? 1u + 2u * TR : 0u)) * 64u) + (threadIdx.x & 63u);
     lane_words = (uint32_t *)lane_area;
     lane_words[TRACE_LW_BLK] = 0u;
@@ -1344,7 +1359,8 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
     /* per-wave work queue: a wave draws chunks of consecutive path ids from the global counter and
      * deals them to its idle lanes by ballot + prefix count */
     uint64_t chunk_next = 0, chunk_end = 0; /* wave-uniform */
-    PathPos chunk_pos = {0, 0};             /* wave-uniform: pixel and sample of path id chunk_next */
+    PathPos chunk_pos = {0, 0};             /* wave-uniform: pixel and sample of path id chunk_next (the direct form; the stash form keeps it in LDS) */
+    StashState st = {0u, 0u};               /* wave-uniform (STASH) */
 
     /* Statistics, none of them in a vector register across the loop: paths are counted per WAVE where they are handed out (a
      * population count added to a scalar, the control flow there is wave-uniform); a path's scans and shaded vertices are its
@@ -1374,6 +1390,170 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
     {
         /* ---- refill idle lanes ---- */
         unsigned long long idle_mask = __ballot(!alive);
+        if constexpr (STASH)
+        {
+        /* The stash form (camera starts only: ray mode's table_ray is three loads and no arithmetic, so drt_trace_rays_kernel stays on
+         * the direct start below). What a path starts with is a function of its id, so the wave makes the starts of its next 64 ids
+         * with every lane busy and an idle lane only picks its entry up. Same ids to the same lanes in the same order as the direct
+         * form (drt_stash_rule.h), the same operations on the same values. The stash is written and read by different lanes of ONE
+         * wave: wavefront fences and wave barriers order the two, and nothing here waits for another wave. */
+        if (idle_mask != 0ull && !exhausted)
+        {
+            const uint32_t want = (uint32_t)__popcll(idle_mask);
+            const uint32_t rank = (uint32_t)__popcll(idle_mask & ((1ull << lane) - 1ull)); /* prefix count among idle lanes */
+            bool started = false;
+            /* pick-up: the entry's rows, then what depends on them. The lane is idle, so its path state is free to take them. Draws
+             * are counted HERE, where the path starts, not at the fill: an entry made but never started (there is none today: a
+             * wave starts every id it stashes, also after the pool ran out) would otherwise be counted */
+            auto pick = [&](uint32_t entry) __attribute__((always_inline)) {
+                const TraceConst &c = LC;
+                const double *e = stash + entry;
+                ro = v3(e[(TRACE_ST_OX + 0u) * 64u], e[(TRACE_ST_OX + 1u) * 64u], e[(TRACE_ST_OX + 2u) * 64u]);
+                rd = v3(e[(TRACE_ST_DX + 0u) * 64u], e[(TRACE_ST_DX + 1u) * 64u], e[(TRACE_ST_DX + 2u) * 64u]);
+                rs = (uint64_t)__double_as_longlong(e[TRACE_ST_RS * 64u]);
+                const double vignette = e[TRACE_ST_VIG * 64u];
+                const uint64_t q = (uint64_t)__double_as_longlong(e[TRACE_ST_Q * 64u]);
+                const uint64_t sd = (uint64_t)__double_as_longlong(e[TRACE_ST_SD * 64u]);
+                const uint64_t s_local = sd & 0xFFFFFFFFull;
+                lane_word_add(lane_words + TRACE_LW_DRAWS, (uint32_t)(sd >> 32));
+                if (record_hits) hit_row = s_local * c.tp.n_pix + q;
+                const uint64_t slot = q * (uint64_t)c.tp.batch + s_local;
+                hdr = headers + slot * REC_HEADER_WORDS;
+                hdr[1] = (uint64_t)__double_as_longlong(vignette); /* for the shade kernel: never loaded back here */
+                if (tail_on) lane_area[TRACE_LANE_ROWS * 64u] = vignette;
+                started = true;
+            };
+            const int32_t e1 = stash_first_entry(st, want, rank);
+            if (!alive && e1 >= 0) pick((uint32_t)e1);
+            const uint32_t take1 = stash_after_first(st, want);
+            if (take1 < want)
+            {
+                /* the stash is empty: draw a new chunk if this one is used up, then make the next 64 starts */
+                uint64_t *pos_slot = (uint64_t *)(stash + TRACE_STASH_ROWS * 64u); /* (pixel, sample) of id chunk_next, stepped by every fill */
+                if (chunk_next == chunk_end)
+                {
+                    const TraceConst &c = LC;
+                    const uint64_t CHUNK = c.tp.chunk, n_paths_all = c.tp.n_paths;
+                    unsigned long long base = 0;
+                    if (lane == 0) base = atomicAdd(c.work_counter, (unsigned long long)CHUNK);
+                    /* lane 0's value to the scalar side (every lane is active here): no lane index held in a vector register across the loop */
+                    base = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)base) |
+                           ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(base >> 32)) << 32);
+                    if (base >= n_paths_all)
+                    {
+                        exhausted = true;
+                        chunk_next = chunk_end = 0;
+                    }
+                    else
+                    {
+                        chunk_next = base;
+                        chunk_end = (base + CHUNK < n_paths_all) ? base + CHUNK : n_paths_all;
+                        const PathPos p0 = path_pos_of_id(base, c.tp.n_samples); /* the one 64-bit division: per draw, not per path */
+                        if (lane == 0)
+                        {
+                            pos_slot[0] = p0.q;
+                            pos_slot[1] = (uint64_t)p0.s;
+                        }
+                        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                        __builtin_amdgcn_wave_barrier();
+                    }
+                }
+                if (!exhausted)
+                {
+                    const uint32_t n = stash_fill_size(chunk_next, chunk_end);
+                    /* every lane, running paths included: the entry is made in temporaries, ro, rd and rs are not touched */
+                    PathPos from;
+                    from.q = pos_slot[0];
+                    from.s = (uint32_t)pos_slot[1];
+                    const uint32_t n_samples = LC.tp.n_samples;
+                    if (lane < n)
+                    {
+                        const TraceConst &c = LC;
+                        const PathPos me = path_pos_step(from, lane, n_samples); /* id chunk_next + lane */
+                        const uint64_t q = me.q;
+                        const uint64_t s_local = me.s;
+                        const uint64_t t = LIST ? (uint64_t)c.tp.pixel_list[q] : q; /* the tile pixel */
+                        uint32_t i, j;
+                        tile_pixel_ij(t, c.tp.tile_w, i, j);
+                        const uint32_t x = c.tp.x0 + i;
+                        const uint32_t y = c.tp.y0 + j * c.tp.row_stride;
+                        uint32_t sample = c.tp.first_sample + (uint32_t)s_local;
+                        if (LIST) sample += c.tp.sample_base[t];
+                        const uint64_t key = c.tp.seed + (((uint64_t)sample * (uint64_t)c.tp.height + (uint64_t)y) * (uint64_t)c.tp.width + (uint64_t)x);
+                        uint64_t f_rs = drt_splitmix64(key);
+                        uint32_t drawn = 0;
+                        V3 f_ro, f_rd;
+                        camera_ray(c.cam, c.tp.pixel_scheme, x, y, f_rs, drawn, f_ro, f_rd);
+                        /* vignette: dot(ray_direction, forward) of the PRIMARY ray, src/daily_ray_trace.c:614 */
+                        const double vignette = v_dot(f_rd, c.cam.forward) * 1.0;
+                        double *w = stash + lane;
+                        w[(TRACE_ST_OX + 0u) * 64u] = f_ro.x;
+                        w[(TRACE_ST_OX + 1u) * 64u] = f_ro.y;
+                        w[(TRACE_ST_OX + 2u) * 64u] = f_ro.z;
+                        w[(TRACE_ST_DX + 0u) * 64u] = f_rd.x;
+                        w[(TRACE_ST_DX + 1u) * 64u] = f_rd.y;
+                        w[(TRACE_ST_DX + 2u) * 64u] = f_rd.z;
+                        w[TRACE_ST_RS * 64u] = __longlong_as_double((long long)f_rs);
+                        w[TRACE_ST_VIG * 64u] = vignette;
+                        w[TRACE_ST_Q * 64u] = __longlong_as_double((long long)q);
+                        w[TRACE_ST_SD * 64u] = __longlong_as_double((long long)(s_local | ((uint64_t)drawn << 32)));
+                    }
+                    if (lane == 0)
+                    {
+                        const PathPos next = path_pos_step(from, n, n_samples);
+                        pos_slot[0] = next.q;
+                        pos_slot[1] = (uint64_t)next.s;
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    const int32_t e2 = stash_second_entry(n, want, take1, rank);
+                    if (!alive && !started && e2 >= 0) pick((uint32_t)e2);
+                    stash_after_fill(st, chunk_next, n, want, take1);
+                    /* the entries just read are overwritten by the next fill only, an iteration later at the earliest, and LDS
+                     * runs a wave's operations in order */
+                }
+            }
+            w_paths += (uint32_t)__popcll(__ballot(started));
+#ifdef DRT_BRANCH_STATS
+            {
+                const unsigned long long m_started = __ballot(started);
+                if (m_started != 0ull && lane == 0u)
+                {
+                    bs[20] += 1;
+                    bs[21] += __popcll(m_started);
+                }
+            }
+#endif
+            if (started)
+            {
+                /* the per-path resets */
+                alive = true;
+                depth = 0;
+                shaded = 0;
+                plastic_mask = 0;
+                vis0_mask = 0;
+                tail_ok = tail_on;
+                if (tail_on)
+                {
+                    const uint32_t tr = pinned_scalar(TR);
+#pragma unroll
+                    for (uint32_t j = 0; j < DRT_TRACE_TAIL_MAX; j += 1)
+                    {
+                        if (j >= tr) break;
+                        tail_state[(2u * j) * 64u] = 1.0;      /* throughput, const_spectrum(throughput, 1.0), :440 */
+                        tail_state[(2u * j + 1u) * 64u] = 0.0; /* dst */
+                    }
+                }
+                if (record_hits)
+                {
+                    const TraceConst &c = LC;
+                    int32_t *h = c.hits + ((uint64_t)c.tp.hits_sample_offset * c.tp.n_pix + hit_row) * max_depth;
+                    for (uint32_t d = 0; d < max_depth; d += 1) h[d] = -2;
+                }
+            }
+        }
+        }
+        else
         if (idle_mask != 0ull && !exhausted)
         {
             uint32_t want = (uint32_t)__popcll(idle_mask);
@@ -1425,6 +1605,16 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
             /* start the newly assigned paths: lanes that were idle in idle_mask and are alive now */
             bool started = alive && ((idle_mask >> lane) & 1ull);
             w_paths += (uint32_t)__popcll(__ballot(started));
+#ifdef DRT_BRANCH_STATS
+            {
+                const unsigned long long m_started = __ballot(started);
+                if (m_started != 0ull && lane == 0u)
+                {
+                    bs[20] += 1;
+                    bs[21] += __popcll(m_started);
+                }
+            }
+#endif
             if (started)
             {
                 const TraceConst &c = LC;
@@ -1479,6 +1669,9 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
             }
         }
         if (!__any(alive)) break;
+#ifdef DRT_BRANCH_STATS
+        if (lane == 0u) bs[22] += 1;
+#endif
 
         /* a spare record block for the lanes whose path may open one at this iteration's vertex (the whole wave takes part) */
         if (!path_spare_block(LC.tp, wp, alive, shaded, spare, spare_tbl, lane))
@@ -1780,8 +1973,10 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
         unsigned long long t[DRT_BS_WORDS];
         for (int k = 0; k < DRT_BS_WORDS; k += 1) t[k] = atomicExch(&drt_branch_stats[k], 0ull);
         printf("DRT_BRANCH_STATS iters %llu lanes %llu | disc %llu %llu | ggx %llu %llu | coin %llu %llu | spec %llu %llu | all4 %llu | "
-               "loop %llu again %llu | half %llu eqt %llu | uniform %llu | closest plane steps %llu skipped %llu | shadow plane steps %llu skipped %llu\n",
-               t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15], t[16], t[17], t[18], t[19]);
+               "loop %llu again %llu | half %llu eqt %llu | uniform %llu | closest plane steps %llu skipped %llu | shadow plane steps %llu skipped %llu | "
+               "starts entered %llu lanes %llu of %llu wave-iterations\n",
+               t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10], t[11], t[12], t[13], t[14], t[15], t[16], t[17], t[18], t[19],
+               t[20], t[21], t[22]);
         drt_branch_waves_done = 0u;
     }
 #endif
@@ -1789,8 +1984,30 @@ __device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, Trac
 #undef LC_RT
 }
 
+/* the direct form: a lane that falls idle computes its path's start itself (drt_trace_direct_kernel, and ray mode) */
+template <bool SCENE_IN_LDS, bool TAIL, bool LIST, bool RAYS>
+__device__ __forceinline__ void trace_paths(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
+                                            uint64_t *records, uint64_t *headers,
+                                            int32_t *k_hits, unsigned long long *k_counters,
+                                            unsigned long long *k_work_counter, const DevRayTable &k_rt)
+{
+    trace_paths_form<SCENE_IN_LDS, TAIL, LIST, RAYS, false>(k_sc, k_cam, k_tp, records, headers, k_hits, k_counters, k_work_counter, k_rt);
+}
+
 template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
 __global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_kernel(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
+                                                                 uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
+                                                                 int32_t *__restrict__ k_hits, unsigned long long *__restrict__ k_counters,
+                                                                 unsigned long long *__restrict__ k_work_counter)
+{
+    const DevRayTable no_table = {nullptr, nullptr, nullptr, 0u, 0u, 0u, 0u};
+    trace_paths_form<SCENE_IN_LDS, TAIL, LIST, false, SCENE_IN_LDS>(k_sc, k_cam, k_tp, records, headers, k_hits, k_counters, k_work_counter, no_table); /* the stash form */
+}
+
+/* The direct form: a lane that falls idle computes its path's start itself. For the scenes whose block has no room for the stash
+ * (the launcher's occupancy rule) and for DRT_NO_RAY_STASH=1, the A/B switch. */
+template <bool SCENE_IN_LDS, bool TAIL = false, bool LIST = false>
+__global__ __launch_bounds__(TRACE_BLOCK, DRT_TRACE_WAVES_PER_SIMD) void drt_trace_direct_kernel(DevScene k_sc, DevCamera k_cam, TraceParams k_tp,
                                                                  uint64_t *__restrict__ records, uint64_t *__restrict__ headers,
                                                                  int32_t *__restrict__ k_hits, unsigned long long *__restrict__ k_counters,
                                                                  unsigned long long *__restrict__ k_work_counter)

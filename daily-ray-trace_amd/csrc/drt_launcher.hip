@@ -146,6 +146,7 @@ struct drt_context
 
     bool   scene_in_lds = true, spds_in_lds = true, use_bvh = false;
     size_t trace_lds = 0, shade_lds = 0;
+    bool trace_stash = false; /* camera launches run the stash form, drt_trace_kernel, with TRACE_STASH_BYTES of LDS behind trace_lds; else drt_trace_direct_kernel */
     int    trace_grid_cap = 0, shade_grid_cap = 0;
     uint32_t trace_chunk_override = 0, shade_subs_override = ~0u, tail_period_override = 0; /* DRT_TRACE_CHUNK, DRT_SHADE_SUBS tuning knobs */
     uint32_t shade_sets = 1, tail_first = 0, tail_count = 0;
@@ -1245,9 +1246,20 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
     int per_cu = 0;
     if (ctx->scene_in_lds && ctx->trace_tail) /* the instantiation that will be launched: its registers and LDS decide the grid */
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, drt_trace_kernel<true, true>, TRACE_BLOCK, ctx->trace_lds));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, drt_trace_direct_kernel<true, true>, TRACE_BLOCK, ctx->trace_lds));
     else if (ctx->scene_in_lds)
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, drt_trace_kernel<true, false>, TRACE_BLOCK, ctx->trace_lds));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, drt_trace_direct_kernel<true, false>, TRACE_BLOCK, ctx->trace_lds));
+    /* The ray stash (drt_trace_kernel, 5 KB of LDS a wave): taken only where the block with it still is a plain 64 KB block and the
+     * CU keeps as many of them as it keeps of the direct form; DRT_NO_RAY_STASH=1 is the A/B switch. scene_in_lds and the tail rule
+     * do not count it. */
+    ctx->trace_stash = false;
+    if (ctx->scene_in_lds && !(getenv("DRT_NO_RAY_STASH") && atoi(getenv("DRT_NO_RAY_STASH")) != 0) && ctx->trace_lds + TRACE_STASH_BYTES <= 64 * 1024)
+    {
+        int with = 0;
+        if (ctx->trace_tail) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&with, drt_trace_kernel<true, true>, TRACE_BLOCK, ctx->trace_lds + TRACE_STASH_BYTES));
+        else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&with, drt_trace_kernel<true, false>, TRACE_BLOCK, ctx->trace_lds + TRACE_STASH_BYTES));
+        ctx->trace_stash = with >= 1 && with >= per_cu;
+    }
     if (per_cu < 1) per_cu = 1;
     if (const char *e = getenv("DRT_TRACE_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(e)); /* tuning knob */
     ctx->trace_grid_cap = prop.multiProcessorCount * per_cu;
@@ -1716,7 +1728,8 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
 #define DRT_TRACE_ARGS ctx->dsc, ctx->dcam, tp, ctx->d_records, ctx->d_headers, ctx->d_hits, ctx->d_counters + DRT_PAIR_COUNTERS, work
 #define DRT_LAUNCH_TRACE(TAIL, LIST)                                                                                                                       \
         if (rays) hipLaunchKernelGGL((drt_trace_rays_kernel<true, TAIL, LIST>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, DRT_TRACE_ARGS, rt); \
-        else hipLaunchKernelGGL((drt_trace_kernel<true, TAIL, LIST>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, DRT_TRACE_ARGS)
+        else if (ctx->trace_stash) hipLaunchKernelGGL((drt_trace_kernel<true, TAIL, LIST>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds + TRACE_STASH_BYTES, ctx->stream, DRT_TRACE_ARGS); \
+        else hipLaunchKernelGGL((drt_trace_direct_kernel<true, TAIL, LIST>), dim3(grid), dim3(TRACE_BLOCK), ctx->trace_lds, ctx->stream, DRT_TRACE_ARGS)
         const bool tail = ctx->trace_tail && tp.tail_stage;
         if (list && tail) { DRT_LAUNCH_TRACE(true, true); }
         else if (list) { DRT_LAUNCH_TRACE(false, true); }
@@ -2198,7 +2211,7 @@ extern "C" int drt_get_stats(drt_context *ctx, drt_stats *out)
     out->redone_launches = (uint32_t)ctx->redone_batches;
     out->launches = (uint32_t)std::min<uint64_t>(ctx->timed_pairs, 0xFFFFFFFFull);
     out->path_flags = (ctx->bvh_pipeline ? DRT_PATH_BVH : 0u) | ((ctx->trace_tail && ctx->d_tail_stage) ? DRT_PATH_TRACE_TAIL : 0u) |
-                      (ctx->rays_bound ? DRT_PATH_RAYS : 0u);
+                      (ctx->rays_bound ? DRT_PATH_RAYS : 0u) | ((ctx->trace_stash && !ctx->bvh_pipeline) ? DRT_PATH_RAY_STASH : 0u); /* the context's camera launches; DRT_PATH_RAYS says when those do not run */
     out->min_sample_ms = ctx->min_sample_ms;
     out->max_sample_ms = ctx->max_sample_ms;
     out->avg_sample_ms = ctx->avg_sample_ms;

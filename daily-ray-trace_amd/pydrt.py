@@ -21,7 +21,7 @@ MODE_SPECTRAL, MODE_XYZ = 0, 1
 FLAG_RECORD_HITS = 1
 BATCH_RESIDENT = 0xFFFFFFFF  # make_params(batch_spp=...): launches sized for a context kept across frames
 FLAG_FILM_ZERO = 2
-PATH_BVH, PATH_TRACE_TAIL, PATH_RAYS = 1, 2, 4  # Stats.path_flags
+PATH_BVH, PATH_TRACE_TAIL, PATH_RAYS, PATH_RAY_STASH = 1, 2, 4, 8  # Stats.path_flags
 
 # names and order of include/bdsf_list.h
 BDSF_NAMES = ["bp_diffuse_bdsf", "bp_glossy_bdsf", "mirror_bdsf", "fs_conductor_bdsf",

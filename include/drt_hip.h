@@ -208,7 +208,11 @@ enum
 {
     DRT_PATH_BVH        = 1u, /* the scene is behind the bounding-volume hierarchy: drt_primary_kernel + drt_bounce_kernel trace it */
     DRT_PATH_TRACE_TAIL = 2u, /* the trace kernel carries every path's tail wavelengths (all-plastic scenes); the shade kernel's tail pass only updates the film */
-    DRT_PATH_RAYS       = 4u  /* a ray table is bound (drt_bind_rays): the ray-mode entry points of those kernels run; set while bound, and only then */
+    DRT_PATH_RAYS       = 4u, /* a ray table is bound (drt_bind_rays): the ray-mode entry points of those kernels run; set while bound, and only then */
+    DRT_PATH_RAY_STASH  = 8u  /* the context's camera launches start their paths from the trace kernel's ray stash (drt_trace_kernel); unset: from the direct
+                                 start (drt_trace_direct_kernel: DRT_NO_RAY_STASH=1, or an LDS block without room for the stash) or in the hierarchy's
+                                 kernels. A property of the context like the two above: while DRT_PATH_RAYS is set the ray-mode kernels run instead,
+                                 and those start directly */
 };
 
 typedef struct drt_context drt_context;
