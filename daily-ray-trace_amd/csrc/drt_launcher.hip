@@ -17,6 +17,7 @@
 #include "drt_depth_kernels.h"
 #include "drt_window_kernels.h"
 #include "drt_window_rule.h"
+#include "drt_pair_rule.h"
 #include "drt_owned.h"
 
 #include <algorithm>
@@ -115,7 +116,7 @@ struct drt_context
     uint64_t  pool_blocks = 0;          /* blocks in d_records */
     uint32_t  worst_blocks_per_path = 0; /* what a path of max_depth vertices takes (table block included) */
     double    est_blocks_per_path = 0.0; /* measured on a sample of the tile when the context is created */
-    struct Batch { uint32_t first_sample, n_samples; uint64_t seq; uint32_t row0, rows, hits_sample_offset, stride; const uint32_t *list; uint64_t list_len; }; /* rows == 0: the whole tile; list: the pixels of an adaptive round */
+    struct Batch { PairSpan span; uint64_t seq; }; /* (drt_pair_rule.h) */
     std::vector<Batch> inflight;         /* kernel pairs enqueued since the last synchronisation (redone if the pool ran out) */
     uint64_t  next_seq = 1;
     uint64_t  redone_batches = 0, pool_peak = 0;
@@ -148,7 +149,10 @@ struct drt_context
     size_t trace_lds = 0, shade_lds = 0;
     bool trace_stash = false; /* camera launches run the stash form, drt_trace_kernel, with TRACE_STASH_BYTES of LDS behind trace_lds; else drt_trace_direct_kernel */
     int    trace_grid_cap = 0, shade_grid_cap = 0;
-    uint32_t trace_chunk_override = 0, shade_subs_override = ~0u, tail_period_override = 0; /* DRT_TRACE_CHUNK, DRT_SHADE_SUBS tuning knobs */
+    uint32_t trace_chunk_override = 0; /* DRT_TRACE_CHUNK tuning knob */
+    ShadeOverrides shade_overrides;    /* DRT_SHADE_CHUNK, DRT_SHADE_SUBS, DRT_TAIL_PERIOD tuning knobs (drt_pair_rule.h) */
+    uint32_t debug_shade_mode = 0;     /* DRT_DEBUG_SHADE_MODE timing probe: 1 main pass only, 2 tail pass only */
+    bool     debug_tail_phase_a_off = false; /* DRT_DEBUG_TAIL_PHASE_A_OFF timing probe: the tail pass is left its film update only */
     uint32_t shade_sets = 1, tail_first = 0, tail_count = 0;
     uint64_t n_pix = 0;
 
@@ -1074,8 +1078,7 @@ static size_t pixels_bytes(const drt_context *ctx)
     return (size_t)ctx->n_pix * (ctx->xyz_mode ? (size_t)XYZ_FILM_WORDS : (size_t)ctx->dsc.S + 1) * 8;
 }
 
-static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0,
-                         const uint32_t *list = nullptr, uint64_t list_len = 0, uint32_t col0 = 0, uint32_t cols = 0);
+static int enqueue_trace(drt_context *ctx, const TraceTile &tile, const PairSpan &span);
 
 /* waves of the trace-stage kernel that takes record blocks, for a launch of n_paths */
 static uint64_t trace_waves(const drt_context *ctx, uint64_t n_paths)
@@ -1302,8 +1305,11 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         ctx->shade_grid_cap = std::max(1, ctx->shade_grid_cap - n);
     }
     if (const char *e = getenv("DRT_TRACE_CHUNK")) ctx->trace_chunk_override = (uint32_t)std::min(1 << 20, std::max(64, atoi(e) / 64 * 64));
-    if (const char *e = getenv("DRT_TAIL_PERIOD")) ctx->tail_period_override = (uint32_t)std::max(0, atoi(e));
-    if (const char *e = getenv("DRT_SHADE_SUBS")) ctx->shade_subs_override = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = getenv("DRT_TAIL_PERIOD")) ctx->shade_overrides.tail_period = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = getenv("DRT_SHADE_SUBS")) ctx->shade_overrides.subs = (uint32_t)std::max(0, atoi(e));
+    if (const char *e = getenv("DRT_SHADE_CHUNK")) ctx->shade_overrides.chunk = (uint32_t)atoi(e); /* (shade_queue clamps it) */
+    if (const char *e = getenv("DRT_DEBUG_SHADE_MODE")) ctx->debug_shade_mode = (uint32_t)atoi(e);
+    if (const char *e = getenv("DRT_DEBUG_TAIL_PHASE_A_OFF")) ctx->debug_tail_phase_a_off = atoi(e) != 0;
     /*
      * The record pool and the launch size. A launch of N paths needs about N * b blocks, b = blocks per path on THIS tile of
      * THIS scene (0.9 on the Cornell frame, where a worst-case path would take 4): b is measured here, once, on a sample of the
@@ -1332,22 +1338,11 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
          * tile's average on the Cornell frame, in launches of 0.4 times the paths -- so b below stays blocks per TILE path, and the pool
          * serves windowed and whole-tile launches of the same samples alike */
         const bool win = window_in_use(ctx);
+        const PairWindow pw = {win, ctx->wx0, ctx->wx1, ctx->wy0, ctx->wy1};
         const uint64_t live_px = win ? (uint64_t)(ctx->wx1 - ctx->wx0) * (ctx->wy1 - ctx->wy0) : npx;
-        const uint32_t k = (uint32_t)std::max<uint64_t>(1, live_px / (128u << 10));
-        drt_params pp = ctx->params;
-        if (win && live_px > 0)
-        {
-            pp.x0 += ctx->wx0;
-            pp.tile_w = ctx->wx1 - ctx->wx0;
-            pp.y0 += ctx->wy0 * ctx->params.row_stride;
-            pp.tile_h = ctx->wy1 - ctx->wy0;
-        }
-        pp.tile_h = (pp.tile_h + k - 1) / k;
-        pp.row_stride = ctx->params.row_stride * k;
-        const uint64_t n_sample = (uint64_t)pp.tile_w * pp.tile_h;
-        ctx->n_pix = n_sample;
+        const TraceTile sample = pool_sample_tile(ctx->params, pw, pool_sample_step(live_px));
+        const uint64_t n_sample = sample.n_pix;
         ctx->pool_blocks = blocks_worst_case(ctx, n_sample);
-        ctx->n_pix = npx;
         HIP_TRY(ctx->d_records.need(ctx->pool_blocks * ctx->block_words));
         HIP_TRY(ctx->d_headers.need(n_sample * REC_HEADER_WORDS));
         if (ctx->bvh_pipeline)
@@ -1355,16 +1350,7 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
             HIP_TRY(ctx->d_primary.need(n_sample));
             HIP_TRY(ctx->d_queue.need(n_sample));
         }
-        const drt_params keep = ctx->params;
-        const uint64_t keep_pix = ctx->n_pix;
-        ctx->params = pp;
-        ctx->params.flags &= ~(uint32_t)DRT_FLAG_RECORD_HITS;
-        ctx->n_pix = n_sample;
-        ctx->batch_spp = 1;
-        rc = enqueue_trace(ctx, keep.first_sample, 1, 0);
-        ctx->params = keep;
-        ctx->n_pix = keep_pix;
-        if (rc) return rc;
+        if ((rc = enqueue_trace(ctx, sample, PairSpan::whole_tile(ctx->params.first_sample, 1, 0)))) return rc;
         unsigned long long used = 0; /* blocks handed to paths (the cursor also counts the waves' part-used chunks) */
         HIP_TRY(hipMemcpyAsync(&used, ctx->d_counters + DRT_PAIR_COUNTERS + 5, sizeof(used), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1570,18 +1556,19 @@ static WindowParams window_params(const drt_context *ctx)
     return wp;
 }
 
+static PairWindow pair_window(const drt_context *ctx) { return {ctx->win_open, ctx->wx0, ctx->wx1, ctx->wy0, ctx->wy1}; }
+
 /* While the window is open: the window's part of tile rows [row0, row0 + rows) (rows == 0: of the whole tile) into the staging film
  * (to_stage), or back. Dense pairs of those rows go in between. */
 static int window_copy(drt_context *ctx, bool to_stage, uint32_t row0 = 0, uint32_t rows = 0)
 {
     if (!ctx->win_open) return 0;
     WindowParams wp = window_params(ctx);
-    if (rows == 0) { row0 = 0; rows = ctx->params.tile_h; }
-    const uint32_t lo = std::max(row0, wp.wy0), hi = std::min(row0 + rows, wp.wy1);
-    if (hi <= lo || wp.wx1 <= wp.wx0) return 0;
-    const uint64_t stage0 = (uint64_t)(lo - wp.wy0) * (wp.wx1 - wp.wx0); /* the rows' first pixel in the staging film */
-    wp.wy0 = lo; wp.wy1 = hi;
-    const uint64_t pix = (uint64_t)(wp.wx1 - wp.wx0) * (hi - lo);
+    const WindowRows r = window_rows(row0, rows, ctx->params.tile_h, pair_window(ctx));
+    if (r.nothing) return 0;
+    const uint64_t stage0 = r.stage0; /* the rows' first pixel in the staging film */
+    wp.wy0 = r.lo; wp.wy1 = r.hi;
+    const uint64_t pix = (uint64_t)(wp.wx1 - wp.wx0) * (r.hi - r.lo);
     double *const film[3] = {ctx->d_pixels, ctx->d_avgs, ctx->d_vars};
     const uint32_t words[3] = {ctx->xyz_mode ? (uint32_t)XYZ_FILM_WORDS : wp.S + 1u, wp.S, wp.S};
     for (int f = 0; f < (ctx->xyz_mode ? 1 : 3); f += 1)
@@ -1652,33 +1639,27 @@ static int enqueue_window_fill(drt_context *ctx, uint32_t first_sample, uint32_t
 
 /* The trace stage of one kernel pair over samples [first_sample, first_sample + n) of every tile pixel: work queues and the
  * pool cursor reset, then drt_trace_kernel (scene in LDS) or drt_primary_kernel + drt_bounce_kernel (scene behind the hierarchy). */
-static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0, uint32_t rows, uint32_t stride,
-                         const uint32_t *list, uint64_t list_len, uint32_t col0, uint32_t cols)
+static int enqueue_trace(drt_context *ctx, const TraceTile &tile, const PairSpan &span)
 {
     const drt_params &p = ctx->params;
+    const uint32_t *const list = span.list;
     TraceParams tp{};
-    /* rows [row0, row0 + rows) of the tile (rows == 0: all of it): the kernels see a tile that starts there; headers, records and the
-     * staging buffers are indexed from the launch's first pixel */
-    const bool whole = rows == 0;
-    if (whole) { row0 = 0; rows = p.tile_h; }
-    /* columns [col0, col0 + cols) of those rows (cols == 0: all of them): a windowed pair's tile is the live window's part of the rows */
-    if (cols == 0) { col0 = 0; cols = p.tile_w; }
-    tp.width = p.width; tp.height = p.height; tp.x0 = p.x0 + col0; tp.y0 = p.y0 + row0 * p.row_stride;
-    tp.tile_w = cols; tp.tile_h = rows; tp.row_stride = p.row_stride;
-    tp.first_sample = first_sample;
-    tp.n_samples = n;
+    tp.width = p.width; tp.height = p.height; tp.x0 = tile.x0; tp.y0 = tile.y0;
+    tp.tile_w = tile.tile_w; tp.tile_h = tile.tile_h; tp.row_stride = tile.row_stride;
+    tp.first_sample = span.first_sample;
+    tp.n_samples = span.n_samples;
     tp.max_depth = p.max_depth;
     tp.pixel_scheme = p.pixel_scheme;
-    tp.record_hits = (p.flags & DRT_FLAG_RECORD_HITS) ? 1u : 0u;
+    tp.record_hits = tile.record_hits;
     tp.seed = p.seed;
-    tp.n_pix = list ? list_len : (whole && cols == p.tile_w) ? ctx->n_pix : (uint64_t)rows * cols; /* a list: its pixels, anywhere in the whole tile */
+    tp.n_pix = tile.n_pix;
     tp.pixel_list = list;
     tp.sample_base = list ? ctx->d_counts : nullptr;
-    tp.n_paths = tp.n_pix * n;
+    tp.n_paths = tp.n_pix * span.n_samples;
     tp.vertex_words = ctx->vertex_words;
     tp.block_words = ctx->block_words;
-    tp.hits_sample_offset = hits_sample_offset;
-    tp.batch = stride ? stride : ctx->batch_spp; /* sample slots per pixel in the header array (a launch over fewer rows may take more samples) */
+    tp.hits_sample_offset = span.hits_sample_offset;
+    tp.batch = tile.batch;
     tp.pool_blocks = (uint32_t)ctx->pool_blocks;
     tp.tail_stage = ctx->trace_tail ? ctx->d_tail_stage : nullptr;
     tp.tail_resume = tp.tail_stage ? ctx->d_tail_resume : nullptr;
@@ -1689,20 +1670,11 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
     tp.pool_cursor = work + 4;
     tp.overflow = (uint32_t *)(work + 5);
     HIP_TRY(hipMemsetAsync(work, 0, 5 * sizeof(unsigned long long), ctx->stream)); /* trace + shade work queues, bounce queue length, spare, pool cursor */
-    uint64_t blocks_needed = (tp.n_paths + TRACE_BLOCK - 1) / TRACE_BLOCK;
-    const int grid_cap = ctx->bvh_pipeline ? ctx->bounce_grid_cap : ctx->trace_grid_cap;
-    uint32_t grid = (uint32_t)std::min<uint64_t>(blocks_needed, (uint64_t)grid_cap);
-    /* work-queue granularity: about 16 draws per wave, so that the last draws finish together; 64..1024 path ids */
-    {
-        uint64_t waves = (uint64_t)grid * (TRACE_BLOCK / 64);
-        uint64_t c = tp.n_paths / (waves * 16) / 64 * 64;
-        tp.chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c, 64), ctx->bvh_pipeline ? 256 : 1024); /* queued paths all cost alike: small draws (config 5: 827 ms at 64-256, 855 at 1024) */
-        if (ctx->trace_chunk_override) tp.chunk = ctx->trace_chunk_override;
-    }
-    /* a bound ray table: the same launches through the ray-mode entry points, the table behind their arguments. A launch over rows
-     * [row0, ...) of the tile numbers its pixels from there; a list's pixels are numbered in the whole tile */
+    const uint32_t grid = trace_grid(tp.n_paths, TRACE_BLOCK, (uint32_t)(ctx->bvh_pipeline ? ctx->bounce_grid_cap : ctx->trace_grid_cap));
+    tp.chunk = trace_chunk(tp.n_paths, grid, TRACE_BLOCK, ctx->bvh_pipeline, ctx->trace_chunk_override);
+    /* a bound ray table: the same launches through the ray-mode entry points, the table behind their arguments */
     DevRayTable rt = ctx->rt;
-    rt.t_offset = (list || whole) ? 0 : (uint64_t)row0 * p.tile_w;
+    rt.t_offset = tile.t_offset;
     const bool rays = ctx->rays_bound;
     if (ctx->bvh_pipeline)
     {
@@ -1743,8 +1715,7 @@ static int enqueue_trace(drt_context *ctx, uint32_t first_sample, uint32_t n, ui
 }
 
 /* One kernel pair: trace, shade + film, and the mark that tells the host whether the pair was complete. */
-static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uint32_t hits_sample_offset, uint32_t row0 = 0, uint32_t rows = 0, uint32_t stride = 0,
-                        const uint32_t *list = nullptr, uint64_t list_len = 0)
+static int enqueue_pair(drt_context *ctx, const PairSpan &span)
 {
     hipEvent_t ev[3];
     int rc = next_events(ctx, ev);
@@ -1753,123 +1724,61 @@ static int enqueue_pair(drt_context *ctx, uint32_t first_sample, uint32_t n, uin
     HIP_TRY(hipEventRecord(ev[0], ctx->stream));
     /* A windowed pair (between window_open and window_close): the kernels' tile is the live window's part of the pair's rows, their
      * film the staging film; the pair's other pixels are drt_window_fill_kernel's, below. Nothing live in these rows: no kernels. */
-    const bool windowed = ctx->win_open && !list;
-    const uint32_t t_row0 = rows ? row0 : 0u, t_rows = rows ? rows : ctx->params.tile_h; /* the pair's tile rows */
-    uint32_t l_row0 = t_row0, l_rows = t_rows, l_cols = ctx->params.tile_w;
-    if (windowed)
-    {
-        const uint32_t lo = std::max(t_row0, ctx->wy0), hi = std::min(t_row0 + t_rows, ctx->wy1);
-        l_row0 = lo;
-        l_rows = hi > lo ? hi - lo : 0u;
-        l_cols = ctx->wx1 - ctx->wx0;
-    }
-    const bool nothing = windowed && (l_rows == 0u || l_cols == 0u);
-    if (!windowed && (rc = pool_floor(ctx))) return rc;
-    if (windowed) { if (!nothing && (rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, l_row0, l_rows, stride, nullptr, 0, ctx->wx0, l_cols))) return rc; }
-    else if ((rc = enqueue_trace(ctx, first_sample, n, hits_sample_offset, row0, rows, stride, list, list_len))) return rc;
-    const uint64_t n_pix = list ? list_len : windowed ? (uint64_t)l_rows * l_cols : rows ? (uint64_t)rows * ctx->params.tile_w : ctx->n_pix; /* pixels of this launch */
-    const uint64_t pix0 = (rows && !list) ? (uint64_t)row0 * ctx->params.tile_w : 0;                  /* its first pixel in the tile */
+    const PairGeometry g = pair_geometry(span, ctx->params.tile_w, ctx->params.tile_h, pair_window(ctx));
+    if (!g.windowed && (rc = pool_floor(ctx))) return rc;
+    if (!g.nothing && (rc = enqueue_trace(ctx, pair_trace_tile(ctx->params, ctx->n_pix, ctx->batch_spp, span, g), span))) return rc;
     HIP_TRY(hipEventRecord(ev[1], ctx->stream));
 
     unsigned long long *work = ctx->d_counters + DRT_NUM_COUNTERS;
     ShadeParams sp{};
-    sp.n_pix = n_pix;
-    sp.n_samples = n;
-    sp.first_sample = first_sample;
+    sp.n_pix = g.n_pix;
+    sp.n_samples = span.n_samples;
+    sp.first_sample = span.first_sample;
     sp.vertex_words = ctx->vertex_words;
     sp.vertex_shift = ctx->vertex_shift;
     sp.block_words = ctx->block_words;
     sp.overflow = (const uint32_t *)(work + 5);
     sp.n_lights = ctx->dsc.n_lights;
-    sp.batch = stride ? stride : ctx->batch_spp;
+    sp.batch = span.stride ? span.stride : ctx->batch_spp;
     sp.tail_first = ctx->tail_first;
     sp.tail_count = ctx->tail_count;
     sp.tail_stage = ctx->d_tail_stage;
     sp.tail_resume = ctx->d_tail_resume;
     sp.light0_em_spd = ctx->light0_em_spd;
     sp.no_fixed_lists = ctx->no_fixed_lists ? 1u : 0u;
-    sp.tail_staged = (ctx->tail_all_staged && ctx->d_tail_stage) ? 1u : 0u;
-    sp.pixel_list = list;
-    sp.sample_base = list ? ctx->d_counts : nullptr;
-    if (const char *e = getenv("DRT_DEBUG_SHADE_MODE")) sp.mode = (uint32_t)atoi(e); /* timing probe: 1 main pass only, 2 tail pass only */
-    if (const char *e = getenv("DRT_DEBUG_TAIL_PHASE_A_OFF")) sp.tail_staged = (uint32_t)atoi(e) ? 1u : sp.tail_staged;
+    sp.tail_staged = ((ctx->tail_all_staged && ctx->d_tail_stage) || ctx->debug_tail_phase_a_off) ? 1u : 0u;
+    sp.pixel_list = span.list;
+    sp.sample_base = span.list ? ctx->d_counts : nullptr;
+    sp.mode = ctx->debug_shade_mode;
     sp.cmf_rw = ctx->cmf_rw; sp.cmf_x = ctx->cmf_x; sp.cmf_y = ctx->cmf_y; sp.cmf_z = ctx->cmf_z;
-    sp.chunk = ctx->tail_count ? 64u / ctx->tail_count : SHADE_PIXEL_CHUNK;
-    if (ctx->tail_count && !sp.tail_staged)
-    {
-        /* A group's tail-pass item is the longest item of the queue: the replay of every path of its pixels that the trace kernel did
-         * not carry, 1-4 ms where glass fills them -- the floor under a small launch. Its lane groups take PATHS, not pixels, so a group
-         * of fewer pixels is replayed by the same 64 / R lane groups in that much less time, and only the short film phase runs with
-         * lanes to spare. Worth it where a wave gets fewer than two such items (64 rows x 1024 px x 256 spp: shade 6.8 -> 6.1 ms with
-         * half the pixels per group, 8 rows: 3.9 -> 1.6 with a quarter); the whole frame loses (80.2 -> 82.7: more, emptier film phases). */
-        const uint64_t tail_items = (n_pix + sp.chunk - 1) / sp.chunk, waves_ = (uint64_t)ctx->shade_grid_cap * SHADE_WAVES;
-        if (2 * tail_items < waves_) sp.chunk = std::max(1u, sp.chunk / 4);
-        else if (tail_items < 2 * waves_) sp.chunk = std::max(1u, sp.chunk / 2);
-    }
-    if (const char *e = getenv("DRT_SHADE_CHUNK")) sp.chunk = std::max(1u, std::min(ctx->tail_count ? 64u / ctx->tail_count : SHADE_PIXEL_CHUNK, (uint32_t)atoi(e))); /* tuning knob */
-    uint64_t groups = (n_pix + sp.chunk - 1) / sp.chunk;
-    const bool inline_tail = ctx->tail_count != 0;
-    /* work items: a group's main pass in pieces of sub_pixels pixels (+ its tail pass as an item of its own) when the
-     * groups alone are too few to keep the last round of the persistent waves short */
-    {
-        const uint64_t waves = (uint64_t)ctx->shade_grid_cap * SHADE_WAVES;
-        uint32_t subs = ctx->shade_subs_override;
-        if (subs == ~0u)
-        {
-            /* pixels per main-pass item: small enough for >= 64 items per wave (short last round), large enough for
-             * >= 256 paths per item (the queue is one atomic counter) */
-            uint64_t p_balance = n_pix / (waves * 64);
-            uint64_t p_atomic = (256 + n - 1) / n;
-            uint32_t P = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(std::max(p_balance, p_atomic), 1), sp.chunk);
-            subs = (sp.chunk + P - 1) / P;
-            if (subs == 1 && !inline_tail) subs = 0;
-        }
-        subs = std::min(subs, sp.chunk);
-        if (subs == 0 || (subs == 1 && !inline_tail) || groups * (uint64_t)(sp.chunk + 1) >= 0xFFFFFFFFull)
-        {
-            sp.sub_pixels = sp.chunk;
-            sp.items_per_group = 1;
-        }
-        else
-        {
-            sp.sub_pixels = (sp.chunk + subs - 1) / subs;
-            sp.items_per_group = (sp.chunk + sp.sub_pixels - 1) / sp.sub_pixels + (inline_tail ? 1 : 0);
-        }
-        if (groups * sp.items_per_group >= 0xFFFFFFFFull) return fail(-1, "tile too large for the shade work queue");
-        sp.n_items = (uint32_t)(groups * sp.items_per_group);
-        if (inline_tail && sp.items_per_group > 1)
-        {
-            uint32_t mains = sp.items_per_group - 1;
-            /* tail items (the longest ones, about a millisecond each) evenly through the queue when every wave gets many of them; when a
-             * wave gets only a few (a rank's share of a frame, a row block of the one-shot call), they go out in the first third of the
-             * queue and the launch ends on main-pass pieces only (64 rows x 1024 px x 256 spp: shade 7.0 -> 6.2 ms with the tails in the
-             * first 1/6 to 1/2 of the queue, 7.8 when spread over all of it; the whole frame does not care: 79.9-80.1 ms at any setting) */
-            sp.tail_period_mains = (groups >= 8 * waves) ? mains : std::max<uint32_t>(1, mains / 3);
-            if (ctx->tail_period_override) sp.tail_period_mains = std::min(mains, ctx->tail_period_override);
-        }
-    }
-    uint32_t sgrid = (uint32_t)std::min<uint64_t>(((uint64_t)sp.n_items + SHADE_WAVES - 1) / SHADE_WAVES, (uint64_t)ctx->shade_grid_cap);
+    const ShadeQueue q = shade_queue(g.n_pix, span.n_samples, ctx->tail_count, sp.tail_staged, (uint32_t)ctx->shade_grid_cap, SHADE_WAVES, SHADE_PIXEL_CHUNK,
+                                     ctx->shade_overrides);
+    if (q.too_large) return fail(-1, "tile too large for the shade work queue");
+    sp.chunk = q.chunk;
+    sp.sub_pixels = q.sub_pixels;
+    sp.items_per_group = q.items_per_group;
+    sp.n_items = q.n_items;
+    sp.tail_period_mains = q.tail_period_mains;
     const size_t S_ = ctx->dsc.S;
     const size_t film_words = ctx->xyz_mode ? (size_t)XYZ_FILM_WORDS : S_ + 1;
-    const uint64_t stage0 = windowed ? (uint64_t)(l_row0 - std::min(l_row0, ctx->wy0)) * l_cols : 0; /* the launch's first pixel in the staging film */
-    double *const film[3] = {windowed ? ctx->d_win_film[0] + stage0 * film_words : ctx->d_pixels + pix0 * film_words,
-                             windowed ? (ctx->xyz_mode ? nullptr : ctx->d_win_film[1] + stage0 * S_) : ctx->d_avgs ? ctx->d_avgs + pix0 * S_ : nullptr,
-                             windowed ? (ctx->xyz_mode ? nullptr : ctx->d_win_film[2] + stage0 * S_) : ctx->d_vars ? ctx->d_vars + pix0 * S_ : nullptr};
-    if (!nothing)
+    double *const film[3] = {g.windowed ? ctx->d_win_film[0] + g.stage0 * film_words : ctx->d_pixels + g.pix0 * film_words,
+                             g.windowed ? (ctx->xyz_mode ? nullptr : ctx->d_win_film[1] + g.stage0 * S_) : ctx->d_avgs ? ctx->d_avgs + g.pix0 * S_ : nullptr,
+                             g.windowed ? (ctx->xyz_mode ? nullptr : ctx->d_win_film[2] + g.stage0 * S_) : ctx->d_vars ? ctx->d_vars + g.pix0 * S_ : nullptr};
+    if (!g.nothing)
     {
-        rc = launch_shade(ctx, sgrid, sp, film);
+        rc = launch_shade(ctx, q.grid, sp, film);
         if (rc) return rc;
         HIP_TRY(hipGetLastError());
     }
-    if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, pix0))) return rc;
-    if (windowed && (rc = enqueue_window_fill(ctx, first_sample, n, t_row0, t_rows))) return rc;
+    if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, g.pix0))) return rc;
+    if (g.windowed && (rc = enqueue_window_fill(ctx, span.first_sample, span.n_samples, g.t_row0, g.t_rows))) return rc;
     const uint64_t seq = ctx->next_seq++;
     hipLaunchKernelGGL(drt_mark_pair_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_counters, (unsigned long long)seq);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev[2], ctx->stream));
     ctx->ev_paths.resize(ctx->ev_used / 3, 0.0);
-    ctx->ev_paths[ctx->ev_used / 3 - 1] = (double)(windowed ? (uint64_t)t_rows * ctx->params.tile_w : n_pix) * (double)n; /* (a windowed pair renders all its rows' pixels) */
-    ctx->inflight.push_back({first_sample, n, seq, row0, rows, hits_sample_offset, stride, list, list_len});
+    ctx->ev_paths[ctx->ev_used / 3 - 1] = (double)g.counted_paths;
+    ctx->inflight.push_back({span, seq});
     return 0;
 }
 
@@ -1889,7 +1798,7 @@ static int redo_batches(drt_context *ctx, uint64_t last_good_seq)
      * behind it, fills included, did nothing; the staging film went back as the last complete pair left it). A render call that
      * synchronises does so before it has staged anything, so the film is whole here, whether the window is open already or not. */
     bool lists = false; /* (pixel-list pairs write the film itself: no staging film around them) */
-    for (const auto &b : todo) lists = lists || b.list != nullptr;
+    for (const auto &b : todo) lists = lists || b.span.list != nullptr;
     const bool was_open = ctx->win_open;
     int rc = 0;
     if (lists) window_close(ctx);
@@ -1899,11 +1808,10 @@ static int redo_batches(drt_context *ctx, uint64_t last_good_seq)
     for (const auto &b : todo)
     {
         ctx->redone_batches += 1;
-        for (uint32_t done = 0; done < b.n_samples; done += safe)
+        for (uint32_t done = 0; done < b.span.n_samples; done += safe)
         {
-            /* (the hit log is indexed by sample offset within the caller's drt_render call: the batch remembers its own) */
-            rc = enqueue_pair(ctx, b.first_sample + done, std::min(safe, b.n_samples - done), b.hits_sample_offset + done, b.row0, b.rows, 0,
-                              b.list, b.list_len);
+            /* (the hit log is indexed by sample offset within the caller's drt_render call: the span remembers its own) */
+            rc = enqueue_pair(ctx, b.span.narrowed(done, std::min(safe, b.span.n_samples - done)));
             if (rc) break;
         }
         if (rc) break;
@@ -1923,27 +1831,20 @@ static int redo_batches(drt_context *ctx, uint64_t last_good_seq)
 }
 
 /* Samples [first_sample, first_sample + num_samples) of the tile in n_blocks row blocks, each with ALL the samples before the next
- * block starts: a pair then covers fewer pixels and more samples of each (the record pool holds the same number of paths), and the
- * film -- read and written once per pair, 3328 bytes a pixel -- is touched that much less often. Samples per pair: five eighths of
- * what the pool's size would allow, because it is sized from the tile's AVERAGE path and the rows of an image that hold its objects
- * run above that (a block that runs out anyway is rendered again: redo_batches). done[k], if asked for, is recorded behind block k. */
+ * block starts, so that the film -- read and written once per pair, 3328 bytes a pixel -- is touched that much less often. Samples per
+ * pair: row_block_fit, in pairs of equal size (drt_pair_rule.h); a block that runs out of records anyway is rendered again
+ * (redo_batches). done[k], if asked for, is recorded behind block k. */
 static int enqueue_blocks(drt_context *ctx, uint32_t first_sample, uint32_t num_samples, uint32_t n_blocks, std::vector<Event> *done)
 {
     const uint32_t H = ctx->params.tile_h, W = ctx->params.tile_w;
-    const uint32_t per = (H + n_blocks - 1) / n_blocks;
-    const uint32_t fit = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint32_t>(num_samples, 4096), ctx->n_pix * (uint64_t)ctx->batch_spp * 5 / 8 / ((uint64_t)per * W)));
-    /* ... in pairs of equal size: 256 samples where 125 fit go out as 86 + 85 + 85, not 125 + 125 + 6 (a launch of 6 samples fills the chip for a moment only) */
-    const uint32_t n_pairs = (num_samples + fit - 1) / fit;
-    const uint32_t n_blk = n_pairs ? (num_samples + n_pairs - 1) / n_pairs : 1u;
+    const uint32_t per = row_block_rows(H, n_blocks);
+    const EqualSplit split = equal_split(num_samples, row_block_fit(num_samples, ctx->n_pix, ctx->batch_spp, per, W));
     for (uint32_t r0 = 0; r0 < H; r0 += per)
     {
         const uint32_t rows = std::min(per, H - r0);
         int rc = window_copy(ctx, true, r0, rows); /* (an open live window: the block's part of it, there and back around the block's pairs) */
-        for (uint32_t at = 0; at < num_samples && !rc; at += n_blk)
-        {
-            const uint32_t n = std::min(n_blk, num_samples - at);
-            rc = enqueue_pair(ctx, first_sample + at, n, 0, r0, rows, n);
-        }
+        for (uint32_t i = 0, at = 0; i < split.n_pairs && !rc; at += split.size(i), i += 1)
+            rc = enqueue_pair(ctx, PairSpan::row_block(first_sample + at, split.size(i), r0, rows));
         const int rc_back = window_copy(ctx, false, r0, rows);
         if (rc || rc_back) return rc ? rc : rc_back;
         if (done)
@@ -2002,22 +1903,16 @@ static int render_pairs(drt_context *ctx, uint32_t first_sample, uint32_t num_sa
         int rc = drt_synchronize(ctx);
         if (rc) return rc;
     }
-    /* More samples than one pair takes over the whole tile, on a tile so large that a pair takes few samples of each pixel: row blocks,
-     * so that the film is passed over fewer times (config 5, 4096^2 at 16 samples a pair: 208 bytes of film per path; in blocks
-     * 1141 -> 1196 Mpaths/s). Where a pair takes 32 samples or more the film is a small part of the traffic and the smaller launches
-     * cost more than they save (1024^2, 64 a pair: 1493 -> 1452). Not with the hit log on, which is laid out by sample of the whole tile. */
-    if (!(p.flags & DRT_FLAG_RECORD_HITS) && num_samples > ctx->batch_spp && ctx->batch_spp < 32 && p.tile_h >= 64 && !getenv("DRT_NO_ROW_BLOCKS"))
+    /* Row blocks where row_block_count (drt_pair_rule.h) says they pay. Not with the hit log on, which is laid out by sample of the whole tile. */
+    if (!(p.flags & DRT_FLAG_RECORD_HITS) && !getenv("DRT_NO_ROW_BLOCKS"))
     {
-        const uint64_t want = ((uint64_t)num_samples * 8 + (uint64_t)ctx->batch_spp * 5 - 1) / ((uint64_t)ctx->batch_spp * 5); /* blocks for one pair each */
-        const uint32_t n_blocks = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(want, 16), p.tile_h / 16);
+        const uint32_t n_blocks = row_block_count(num_samples, ctx->batch_spp, p.tile_h);
         if (n_blocks > 1) return enqueue_blocks(ctx, first_sample, num_samples, n_blocks, nullptr);
     }
-    /* (pairs of equal size here too: 100 samples where 64 fit are 50 + 50) */
-    const uint32_t n_pairs = (num_samples + ctx->batch_spp - 1) / ctx->batch_spp;
-    const uint32_t each = n_pairs ? (num_samples + n_pairs - 1) / n_pairs : 1u;
+    const EqualSplit split = equal_split(num_samples, ctx->batch_spp);
     int rc = window_copy(ctx, true);
-    for (uint32_t done = 0; done < num_samples && !rc; done += each)
-        rc = enqueue_pair(ctx, first_sample + done, std::min(each, num_samples - done), done);
+    for (uint32_t i = 0, done = 0; i < split.n_pairs && !rc; done += split.size(i), i += 1)
+        rc = enqueue_pair(ctx, PairSpan::whole_tile(first_sample + done, split.size(i), done));
     const int rc_back = window_copy(ctx, false);
     return rc ? rc : rc_back;
 }
@@ -2371,19 +2266,6 @@ static int adaptive_begin(drt_context *ctx, const drt_adaptive *a)
     return enqueue_converge(ctx);
 }
 
-/* the kernel pairs of a round that renders k samples of each of n_in listed pixels: m samples and P pixels per pair. A pair takes up
- * to five eighths of the paths the record pool is sized for and at most 4096 samples of a pixel; pairs of equal size */
-struct RoundPairs { uint32_t m; uint64_t P; };
-static RoundPairs round_pairs(const drt_context *ctx, uint32_t k, uint64_t n_in)
-{
-    const uint64_t budget = std::max<uint64_t>(1, ctx->n_pix * (uint64_t)ctx->batch_spp * 5 / 8);
-    const uint32_t m_fit = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(k, budget), 4096);
-    const uint32_t n_sp = (k + m_fit - 1) / m_fit, m = (k + n_sp - 1) / n_sp;   /* samples per pair */
-    const uint64_t p_fit = std::max<uint64_t>(1, budget / m);
-    const uint64_t n_pp = (n_in + p_fit - 1) / p_fit, P = (n_in + n_pp - 1) / n_pp; /* pixels per pair */
-    return {m, P};
-}
-
 /* a later round: the next k samples of the ad.active pixels of list d_alist[cur] -- each from the count it holds, d_counts -- in kernel
  * pairs over ranges of the list. k: min(step, max_spp - n) while all active pixels hold n samples, step otherwise (the contract). A pair
  * takes up to five eighths of the paths the record pool is sized for (the pixels still active are the ones with the long paths: a
@@ -2395,7 +2277,7 @@ static int adaptive_enqueue_round(drt_context *ctx)
     ad.n_in = ad.active;
     ad.k = ad.same ? std::min(ad.a.step, ad.a.max_spp - ad.n) : ad.a.step;
     if (ad.same) ad.n += ad.k;
-    const RoundPairs rp = round_pairs(ctx, ad.k, ad.n_in);
+    const RoundPairs rp = round_pairs(ctx->n_pix, ctx->batch_spp, ad.k, ad.n_in);
     const uint32_t m = rp.m;
     const uint64_t P = rp.P;
     const uint32_t *list = ctx->d_alist[ad.cur];
@@ -2405,7 +2287,7 @@ static int adaptive_enqueue_round(drt_context *ctx)
         for (uint32_t at = 0; at < ad.k; at += m)
         {
             const uint32_t ns = std::min(m, ad.k - at);
-            int rc = enqueue_pair(ctx, at, ns, 0, 0, 0, ns, list + off, len);
+            int rc = enqueue_pair(ctx, PairSpan::list_range(at, ns, list + off, len));
             if (rc) return rc;
         }
     }
@@ -2662,7 +2544,7 @@ extern "C" int drt_render_tile(const drt_scene *scene, const drt_camera *camera,
          * renders again from there, and the film is fetched whole.) */
         uint32_t n_blocks = 8; /* 1024^2 x 256 spp, wall: 226 ms in one piece, 219 / 214 / 206 ms in 2 / 4 / 8 blocks (kernels 187 -> 197 ms: smaller launches) */
         if (getenv("DRT_ONESHOT_BLOCKS")) n_blocks = (uint32_t)std::max(1, atoi(getenv("DRT_ONESHOT_BLOCKS")));
-        const uint32_t per = (ctx->params.tile_h + n_blocks - 1) / n_blocks; /* rows per block */
+        const uint32_t per = row_block_rows(ctx->params.tile_h, n_blocks); /* rows per block */
         const bool blocks_ok = params->spp != 0 && n_blocks > 1 && !(params->flags & DRT_FLAG_RECORD_HITS) && ctx->params.tile_h >= 16 * n_blocks &&
                                (uint64_t)ctx->params.tile_w * ctx->params.tile_h >= (1u << 18);
         std::vector<Event> block_done;
@@ -3246,7 +3128,7 @@ static int map_enqueue_round(drt_context *ctx)
     ctx->sm_bits &= ctx->sm_bits - 1u;
     ad.n_in = ad.active;
     ad.k = 1u << b;
-    const RoundPairs rp = round_pairs(ctx, ad.k, ad.n_in);
+    const RoundPairs rp = round_pairs(ctx->n_pix, ctx->batch_spp, ad.k, ad.n_in);
     const uint32_t *list = ctx->d_alist[ad.cur];
     for (uint64_t off = 0; off < ad.n_in; off += rp.P)
     {
@@ -3258,7 +3140,7 @@ static int map_enqueue_round(drt_context *ctx)
              * the round's until its select runs, so pairs redone here start where they started */
             if (ctx->ev_used >= 3 * 256 && (rc = drt_synchronize(ctx))) return rc;
             const uint32_t ns = std::min(rp.m, ad.k - at);
-            if ((rc = enqueue_pair(ctx, at, ns, 0, 0, 0, ns, list + off, len))) return rc;
+            if ((rc = enqueue_pair(ctx, PairSpan::list_range(at, ns, list + off, len)))) return rc;
         }
     }
     return map_enqueue_select(ctx, lowest_bit(ctx->sm_bits));

@@ -8,7 +8,8 @@ DRT_MODE_XYZ folds the spectrum per kernel pair, which the oracle does not resta
 bit with the window off and with a fresh context, and its XYZ with the oracle's to 1e-9 relative, the bound tests/test_gpu_parity.py
 holds that mode to. drt_render_tile goes out in row blocks only from 2^18 pixels on: at 64 x 48 the one-shot case runs the plain
 path, and test_one_shot_call_in_row_blocks, the one case above 96 x 96 (512 x 512, 2 M paths), is the row blocks' own. Row blocks of
-drt_render at the small size: the batch_spp = 2 case."""
+drt_render at the small size: the batch_spp = 2 case; with a record pool that runs out under them: test_tiny_pool_redoes_windowed_row_blocks,
+at the 96 x 200, 23 samples and depth 7 of tests/test_gpu_parity.py's row-block case."""
 import contextlib
 import os
 
@@ -206,6 +207,22 @@ def test_tiny_pool_redoes_windowed_pairs():
     assert on[3].redone_launches >= 1, "the pool of %d blocks did not run out (peak %d)" % (on[3].record_pool_blocks, on[3].record_pool_peak)
 
 
+def test_tiny_pool_redoes_windowed_row_blocks():
+    """The three at once: a window that is a proper part of the tile, a drt_render call that goes out in row blocks (the shape of
+    test_render_in_row_blocks_is_the_same_film: 12 blocks of 17 rows, 12 + 11 samples each) and a record pool that runs out, so that
+    pairs over a block's rows are rendered again as windowed pairs -- the rows window_copy stages, the rows the pair's kernels see and
+    the rows the fill pass takes must be the same rows."""
+    bundle = W.load("cornell_plane_light.scn", 96, 200)
+    p = pydrt.make_params(96, 200, spp=23, max_depth=7, seed=2, batch_spp=3)
+    win = pydrt.live_window_of(bundle, p)
+    assert win != W.whole_tile(p) and win[0] < win[1] and win[2] < win[3], win
+    on = run(bundle, p, calls=((0, 23),), want_window=win, env={"DRT_POOL_BLOCKS": "1"})
+    opx, oav, ova, _, ost = cases.oracle_render_device_pow(bundle, p, num_threads=16)
+    assert_same(on, ((opx, oav, ova), cases.stat_counts(ost)), "against the oracle")
+    assert on[3].paths == 96 * 200 * 23
+    assert on[3].redone_launches > 0, "the pool of %d blocks did not run out (peak %d)" % (on[3].record_pool_blocks, on[3].record_pool_peak)
+
+
 def test_one_shot_call():
     bundle = W.load("cornell_plane_light.scn", 64, 48)
     p = params_of(64, 48)
@@ -219,7 +236,7 @@ def test_one_shot_call():
 
 
 def test_one_shot_call_in_row_blocks():
-    """drt_render_tile goes out in row blocks from 2^18 tile pixels on (the one case above the 96 x 96 of the others): each block stages
+    """drt_render_tile goes out in row blocks from 2^18 tile pixels on (the one case far above the 96 x 96 of the others): each block stages
     and returns its own part of the window, and its film rows are fetched when its event fires. With the window against without it;
     the oracle holds three bands of rows (above the window, across its upper edge, through its middle)."""
     size = 512
