@@ -24,6 +24,13 @@
 
 #define BVH_LDS_STACK BVH_STACK /* levels: the builder refuses deeper trees */
 
+/* How the bounce kernel's draws form their quotient (drt_rng, drt_device.h): by the division. With the short form anywhere it draws
+ * -- its light samples, its direction samplers, the camera rays of its ray-table twin -- it spills 136 scalar registers against a
+ * ceiling of 130 (tests/test_kernel_spill_budget.py). The value drawn is the same either way. Every draw of the kernel goes through
+ * bounce_rng or passes BOUNCE_DRAW_BY_RECIPROCAL on. */
+#define BOUNCE_DRAW_BY_RECIPROCAL false
+__device__ __forceinline__ double bounce_rng(uint64_t &state, uint32_t &draws) { return drt_rng<BOUNCE_DRAW_BY_RECIPROCAL>(state, draws); }
+
 struct PrimaryHit
 {
     int32_t index, pad;
@@ -490,7 +497,7 @@ __device__ __forceinline__ void bounce_paths(
                 uint32_t camera_draws = 0; /* counted by the primary kernel */
                 V3 ro, rd;
                 if (RAYS) (void)table_ray(rt, tp.width, path_tile_pixel<LIST>(tp, ps), ps.x, ps.y, ps.sample, ro, rd);
-                else camera_ray(cam, tp.pixel_scheme, ps.x, ps.y, rs, camera_draws, ro, rd);
+                else camera_ray<BOUNCE_DRAW_BY_RECIPROCAL>(cam, tp.pixel_scheme, ps.x, ps.y, rs, camera_draws, ro, rd);
                 hdr = headers + ps.slot * REC_HEADER_WORDS;
                 const PrimaryHit ph = primary[ps.slot];
                 hit_point_from_scan(sv, sc, ip, v_sum(ro, v_mul(rd, DRT_VIS_FUDGE)), rd, ph.min_dist, ph.index);
@@ -534,8 +541,8 @@ __device__ __forceinline__ void bounce_paths(
             }
             else if (ltype == DRT_GEO_SPHERE)
             {
-                double u = drt_rng(rs, n_draws);
-                double v = drt_rng(rs, n_draws);
+                double u = bounce_rng(rs, n_draws);
+                double v = bounce_rng(rs, n_draws);
                 double r = __builtin_sqrt(1.0 - u * u);
                 double t = (2.0 * DRT_PI) * v;
                 double st, ct;
@@ -545,8 +552,8 @@ __device__ __forceinline__ void bounce_paths(
             }
             else if (ltype == DRT_GEO_PLANE)
             {
-                double u = drt_rng(rs, n_draws);
-                double v = drt_rng(rs, n_draws);
+                double u = bounce_rng(rs, n_draws);
+                double v = bounce_rng(rs, n_draws);
                 V3 lu = v3(sv.lights[LF_UX * sv.n_lights + l], sv.lights[LF_UY * sv.n_lights + l], sv.lights[LF_UZ * sv.n_lights + l]);
                 V3 lv = v3(sv.lights[LF_VX * sv.n_lights + l], sv.lights[LF_VY * sv.n_lights + l], sv.lights[LF_VZ * sv.n_lights + l]);
                 light_position = v_sum(v_sum(lpos, v_mul(lu, u)), v_mul(lv, v));
@@ -629,7 +636,7 @@ __device__ __forceinline__ void bounce_paths(
             uint64_t *vrec = records + (uint64_t)blk * tp.block_words + (uint64_t)(shaded & (REC_BLOCK_VERTICES - 1u)) * tp.vertex_words;
             V3 in;
             double dir_pdf;
-            sample_direction_by_material(sc, sv, ip, rs, n_draws, in, dir_pdf);
+            sample_direction_by_material<BOUNCE_DRAW_BY_RECIPROCAL>(sc, sv, ip, rs, n_draws, in, dir_pdf);
             EvalCoef e = eval_coefficients_by_material(sc, sv, ip, in);
             vrec[0] = mat.bdsf_packed;
             vrec[1] = (uint64_t)mat.num_bdsfs | ((uint64_t)(e.flags | mat.vertex_flags) << 8) | ((uint64_t)((uint32_t)mat.diffuse_spd & 0xFFFFu) << 16) |

@@ -20,6 +20,15 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "drt_const_rule.h"
+
+#ifndef DRT_DRAW_BY_RECIPROCAL
+#define DRT_DRAW_BY_RECIPROCAL 1 /* 0: drt_rng ends in the division (today's text, for an A/B from the same tree) */
+#endif
+
+#ifndef DRT_GLASS_CONSTANTS
+#define DRT_GLASS_CONSTANTS 1 /* 0: every glass vertex divides its media's indices out itself (today's text, for an A/B from the same tree) */
+#endif
 
 #define DRT_PI 3.14159265358979323846
 #define DRT_VIS_FUDGE 0.0001 /* src/daily_ray_trace.c:237 */
@@ -44,6 +53,56 @@ __device__ __forceinline__ V3 v_mul(V3 v, double f) { return v3(f * v.x, f * v.y
 __device__ __forceinline__ V3 v_div(V3 v, double f) { return v3(v.x / f, v.y / f, v.z / f); }
 __device__ __forceinline__ double v_length(V3 v) { return __builtin_sqrt(v_dot(v, v)); }
 __device__ __forceinline__ V3 v_normalise(V3 v) { return v_div(v, v_length(v)); }
+
+/* v_div with ONE reciprocal. The compiler expands x / f on gfx950 into
+ *     d = div_scale(f, f, x)                      the denominator, scaled away from the ends of the exponent range
+ *     r = rcp(d), two Newton steps on it          e = fma(-d, r, 1), r = fma(r, e, r), twice
+ *     n = div_scale(x, f, x)                      the numerator, scaled to match; sets the flag div_fmas reads
+ *     q = n * r,  t = fma(-d, q, n),  q = div_fmas(t, r, q),  div_fixup(q, f, x)
+ * and does so three times for the three components, sharing nothing: d depends on the numerator as well (a zero numerator, a very
+ * small one, a quotient that would overflow or underflow each pick another scale or none). Here the three d
+ * are computed as there and compared bit for bit. Where they are equal, r and its Newton steps are the very operations on the very
+ * operands the three divisions would have run, so they run once; what belongs to a numerator (n, its flag, q, t, div_fmas,
+ * div_fixup) stays per component. A wave in which any active lane has three d that differ takes the three plain divisions. So the
+ * result is x / f, y / f, z / f bit for bit for every input: equal d means an equal chain, unequal d means `/` itself. Equal NaN
+ * scales (a zero vector over anything, anything over zero) count as equal -- they are the same bits, and div_fixup alone decides
+ * those quotients. Held to `/` on the device by tests/test_gpu_shared_division.py.
+ * In a wave that shares: two v_rcp_f64 (quarter rate) and eight fma less per vector, for two v_cmp and a scalar branch. A wave that does
+ * not share pays the comparison on top of its three divisions; how often that happens is the scene's (a zero or very small component in
+ * any active lane) and has not been counted; what the form is worth is what the A/B of this step alone gave (profiles/NOTES.md). */
+#ifndef DRT_SHARED_RCP_DIV
+#define DRT_SHARED_RCP_DIV 1 /* 0: v_div_shared is v_div (today's text, for an A/B from the same tree) */
+#endif
+__device__ __forceinline__ double drt_div_with_rcp(double x, double f, double d, double r)
+{
+    bool flag;
+    const double n = __builtin_amdgcn_div_scale(x, f, true, &flag);
+    double q = n * r;
+    const double t = __builtin_fma(-d, q, n);
+    q = __builtin_amdgcn_div_fmas(t, r, q, flag);
+    return __builtin_amdgcn_div_fixup(q, f, x);
+}
+__device__ __forceinline__ V3 v_div_shared(V3 v, double f)
+{
+#if DRT_SHARED_RCP_DIV
+    bool unused;
+    const double dx = __builtin_amdgcn_div_scale(v.x, f, false, &unused);
+    const double dy = __builtin_amdgcn_div_scale(v.y, f, false, &unused);
+    const double dz = __builtin_amdgcn_div_scale(v.z, f, false, &unused);
+    const long long bx = __double_as_longlong(dx);
+    if (__any(bx != __double_as_longlong(dy) || bx != __double_as_longlong(dz))) return v_div(v, f);
+    double r = __builtin_amdgcn_rcp(dx);
+    double e = __builtin_fma(-dx, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    e = __builtin_fma(-dx, r, 1.0);
+    r = __builtin_fma(r, e, r);
+    return v3(drt_div_with_rcp(v.x, f, dx, r), drt_div_with_rcp(v.y, f, dx, r), drt_div_with_rcp(v.z, f, dx, r));
+#else
+    return v_div(v, f);
+#endif
+}
+/* v_normalise through v_div_shared: the same bits. The trace kernels' normalisations take it. */
+__device__ __forceinline__ V3 v_normalise_shared(V3 v) { return v_div_shared(v, v_length(v)); }
 __device__ __forceinline__ V3 v_reverse(V3 v) { return v3(-v.x, -v.y, -v.z); }
 
 /* vec3_reflect, src/geometry.c:85-90 */
@@ -53,11 +112,10 @@ __device__ __forceinline__ V3 v_reflect(V3 v, V3 n)
     return v_sub(v, v_mul(n, f));
 }
 
-/* vec3_transmit, src/geometry.c:92-106 (NaN on total internal reflection, as in the reference) */
-__device__ __forceinline__ V3 v_transmit(V3 v, V3 n, double ir, double tr)
+/* vec3_transmit, src/geometry.c:92-106 (NaN on total internal reflection, as in the reference), from rel_ref = ir / tr on */
+__device__ __forceinline__ V3 v_transmit_rel(V3 v, V3 n, double rel_ref)
 {
     double vn_dot = v_dot(v, n);
-    double rel_ref = ir / tr;
     V3 m = v_mul(n, vn_dot);
     v = v_sub(m, v);
     V3 perpend = v_reverse(v_mul(v, rel_ref));
@@ -65,6 +123,7 @@ __device__ __forceinline__ V3 v_transmit(V3 v, V3 n, double ir, double tr)
     V3 parallel = v_mul(n, perpend_dot);
     return v_sum(perpend, parallel);
 }
+__device__ __forceinline__ V3 v_transmit(V3 v, V3 n, double ir, double tr) { return v_transmit_rel(v, n, ir / tr); }
 
 __device__ __forceinline__ V3 m_vmul(const M33 &m, V3 v)
 {
@@ -115,7 +174,10 @@ __device__ __forceinline__ uint64_t drt_splitmix64(uint64_t k)
     z ^= z >> 31;
     return z ? z : 1ull;
 }
-/* rng(): rand()/RAND_MAX with rand() := state>>33, RAND_MAX := 2^31-1; range [0,1] inclusive */
+/* rng(): rand()/RAND_MAX with rand() := state>>33, RAND_MAX := 2^31-1; range [0,1] inclusive.
+ * BY_RECIPROCAL chooses how the quotient is formed, never its value. The hierarchy's bounce kernel asks for the division: with the
+ * short form it spills 136 scalar registers against a budget of 130 (tests/test_kernel_spill_budget.py). */
+template <bool BY_RECIPROCAL = (DRT_DRAW_BY_RECIPROCAL != 0)>
 __device__ __forceinline__ double drt_rng(uint64_t &state, uint32_t &draws)
 {
     uint64_t x = state;
@@ -124,6 +186,7 @@ __device__ __forceinline__ double drt_rng(uint64_t &state, uint32_t &draws)
     x ^= x << 17;
     state = x;
     draws += 1;
+    if (BY_RECIPROCAL) return drt_draw_quotient((uint32_t)(x >> 33)); /* the same quotient, correctly rounded, in two operations (drt_const_rule.h) */
     return (double)(uint32_t)(x >> 33) / 2147483647.0;
 }
 
@@ -155,10 +218,11 @@ __device__ __forceinline__ void drt_sincos(double t, double &s, double &c)
 }
 
 /* uniform_sample_sphere, src/rng.c:14-23 */
+template <bool BY_RECIPROCAL = (DRT_DRAW_BY_RECIPROCAL != 0)>
 __device__ __forceinline__ V3 uniform_sample_sphere(uint64_t &rs, uint32_t &draws)
 {
-    double u = drt_rng(rs, draws);
-    double v = drt_rng(rs, draws);
+    double u = drt_rng<BY_RECIPROCAL>(rs, draws);
+    double v = drt_rng<BY_RECIPROCAL>(rs, draws);
     double r = __builtin_sqrt(1.0 - u * u);
     double t = (2.0 * DRT_PI) * v;
     double st, ct;
@@ -167,10 +231,11 @@ __device__ __forceinline__ V3 uniform_sample_sphere(uint64_t &rs, uint32_t &draw
 }
 
 /* uniform_sample_disc, src/rng.c:25-51 */
+template <bool BY_RECIPROCAL = (DRT_DRAW_BY_RECIPROCAL != 0)>
 __device__ __forceinline__ V3 uniform_sample_disc(uint64_t &rs, uint32_t &draws)
 {
-    double r_x = drt_rng(rs, draws);
-    double r_y = drt_rng(rs, draws);
+    double r_x = drt_rng<BY_RECIPROCAL>(rs, draws);
+    double r_y = drt_rng<BY_RECIPROCAL>(rs, draws);
     double o_x = 2.0 * r_x - 1.0;
     double o_y = 2.0 * r_y - 1.0;
     if (o_x == 0.0 && o_y == 0.0) return v3(0.0, 0.0, 0.0);
@@ -307,10 +372,9 @@ __device__ __forceinline__ double drt_pow_shininess(double x, double y)
 
 /* ---- Fresnel terms, one wavelength (the loop bodies of src/bdsf.c:44-101) --------------------- */
 
-/* fs_dielectric_reflectance body; ts_cos squares the already squared sine (quirk Q2) */
-__device__ __forceinline__ double dielectric_reflectance(double ir, double tr, double inc_cos, double inc_sin_sq)
+/* fs_dielectric_reflectance body from rel = ir / tr on; ts_cos squares the already squared sine (quirk Q2) */
+__device__ __forceinline__ double dielectric_reflectance_rel(double rel, double ir, double tr, double inc_cos, double inc_sin_sq)
 {
-    double rel = ir / tr;
     double ts_sin_sq = rel * rel * inc_sin_sq;
     if (ts_sin_sq >= 1.0) return 1.0;
     double ts_cos = __builtin_sqrt(1.0 - ts_sin_sq * ts_sin_sq);
@@ -323,6 +387,10 @@ __device__ __forceinline__ double dielectric_reflectance(double ir, double tr, d
     par *= par;
     per *= per;
     return 0.5 * (par + per);
+}
+__device__ __forceinline__ double dielectric_reflectance(double ir, double tr, double inc_cos, double inc_sin_sq)
+{
+    return dielectric_reflectance_rel(ir / tr, ir, tr, inc_cos, inc_sin_sq);
 }
 
 /* fs_conductor_reflectance body */

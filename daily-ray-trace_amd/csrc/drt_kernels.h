@@ -95,6 +95,9 @@ struct DevMaterial
     int32_t  emission_spd, diffuse_spd, glossy_spd, mirror_spd, refract_spd, extinct_spd;
     double   shininess, roughness;
     double   refract_i0, refract_i1; /* refract_spd at the two samples around trans_wl (value_at_wl) */
+    DrtGlassConst glass; /* drt_const_rule.h, from refract_i0 / refract_i1 of this material and the base material. Zeros in device memory:
+                            the LDS-scene trace kernels fill it in their own LDS copy of the table at every launch (SceneView.glass_ready),
+                            so it cannot go stale when a spectrum, a material or the base material is updated */
     uint32_t bdsfs[DRT_MAX_BDSFS];
     uint64_t bdsf_packed; /* bdsfs[] as 4-bit fields */
     uint32_t vertex_flags; /* FLAG_PLASTIC when the list is exactly {bp_diffuse_bdsf, bp_glossy_bdsf} */
@@ -318,6 +321,7 @@ struct SceneView /* pointers into LDS (or HBM when the scene does not fit) */
     const BvhNode     *bvh_nodes;
     const BvhLeafPrim *bvh_leaf;
     const double      *rows = nullptr; /* LDS scenes: the surface table again, one SR_STRIDE-word row per surface, for the scans */
+    bool               glass_ready = false; /* mats[].glass holds the glass constants (the trace kernels' LDS copy) */
     uint32_t           n_surf, n_lights;
 };
 
@@ -543,11 +547,11 @@ __device__ __forceinline__ void bvh_children(const BvhNode &n, const Ray32 &r, f
     }
 }
 
-/* points_mutually_visible, src/daily_ray_trace.c:238-270 */
+/* points_mutually_visible, src/daily_ray_trace.c:238-270; `dir` gives the caller the shadow ray's direction, normalise(p1 - p0) */
 template <bool ROWS = false>
-__device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 p0, V3 p1 DRT_SCAN_STATS_PARAM)
+__device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 p0, V3 p1, V3 &dir DRT_SCAN_STATS_PARAM)
 {
-    V3 dir = v_normalise(v_sub(p1, p0));
+    dir = v_normalise_shared(v_sub(p1, p0));
     V3 o = v_sum(p0, v_mul(dir, DRT_VIS_FUDGE));
     double vis_dist = v_length(v_sub(p1, o)) - DRT_VIS_FUDGE;
     bool visible = true;
@@ -562,6 +566,12 @@ __device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 
         if (!__any(visible)) break;
     }
     return visible;
+}
+template <bool ROWS = false>
+__device__ __forceinline__ bool points_mutually_visible(const SceneView &sv, V3 p0, V3 p1 DRT_SCAN_STATS_PARAM)
+{
+    V3 dir;
+    return points_mutually_visible<ROWS>(sv, p0, p1, dir DRT_SCAN_STATS_ARG(scan_stats));
 }
 
 struct HitPoint /* scene_point, src/daily_ray_trace.h:113-125 */
@@ -622,7 +632,7 @@ __device__ __forceinline__ void find_ray_intersection(const SceneView &sv, const
         uint32_t type = sv.surf_type[index];
         uint32_t smat = sv.surf_mat[index];
         ip.position = v_sum(ro, v_mul(rd, min_dist));
-        if (type == DRT_GEO_SPHERE) ip.normal = v_normalise(v_sub(ip.position, sf3(sv, SF_PX, index)));
+        if (type == DRT_GEO_SPHERE) ip.normal = v_normalise_shared(v_sub(ip.position, sf3(sv, SF_PX, index)));
         else ip.normal = sf3(sv, SF_NX, index);
         ip.out = v_reverse(rd);
         ip.on_dot = v_dot(ip.normal, ip.out);
@@ -702,9 +712,18 @@ __device__ __forceinline__ VertexDirs vertex_dirs(const DevScene &sc, const Scen
     if (dirs_need_refl(mat)) vd.refl = v_reflect(w, ip.normal);
     if (dirs_need_trans(mat))
     {
-        double ir = refract_at_trans_wl(sc, sv.mats[incident_mat_of(sc, ip)]);
-        double tr = refract_at_trans_wl(sc, sv.mats[transmit_mat_of(sc, ip)]);
-        vd.trans = v_transmit(w, ip.normal, ir, tr);
+        /* rel_ref = ir / tr of vec3_transmit: tabulated where the media are the pair (base material, this one) either way round;
+         * a vertex met from inside a second object divides */
+        const uint32_t im = incident_mat_of(sc, ip), tm = transmit_mat_of(sc, ip);
+        const bool p_out = im == sc.base_mat && tm == ip.surface_mat, p_in = im == ip.surface_mat && tm == sc.base_mat;
+        double rel;
+        if (DRT_GLASS_CONSTANTS && sv.glass_ready)
+        {
+            rel = p_out ? mat.glass.rel_out[2] : mat.glass.rel_in[2];
+            if (!(p_out || p_in)) rel = sv.mats[im].glass.at_wl / sv.mats[tm].glass.at_wl; /* the indices at trans_wl are every material's */
+        }
+        else rel = refract_at_trans_wl(sc, sv.mats[im]) / refract_at_trans_wl(sc, sv.mats[tm]);
+        vd.trans = v_transmit_rel(w, ip.normal, rel);
     }
     return vd;
 }
@@ -727,7 +746,7 @@ __device__ __forceinline__ EvalCoef eval_coefficients(const SceneView &sv, const
     double n_half = 0.0;
     if (needs & (NEED_GLOSSY | NEED_CT)) /* :113-114, :176-177 */
     {
-        half = v_normalise(v_sum(ip.out, in));
+        half = v_normalise_shared(v_sum(ip.out, in));
         n_half = v_dot(ip.normal, half);
     }
     if (needs & NEED_GLOSSY) e.spec = drt_pow_shininess((0.0 > n_half) ? 0.0 : n_half, mat.shininess); /* :115 */
@@ -778,8 +797,16 @@ __device__ __forceinline__ void sample_direction(const DevScene &sc, const Scene
         const DevMaterial &tm = sv.mats[transmit_mat_of(sc, ip)];
         /* value_at_wl(reflectance spectrum, 630) needs the Fresnel term at the two bracketing samples */
         double inc_sin_sq = 1.0 - ip.on_dot * ip.on_dot;
-        double r0 = dielectric_reflectance(im.refract_i0, tm.refract_i0, ip.on_dot, inc_sin_sq);
-        double r1 = dielectric_reflectance(im.refract_i1, tm.refract_i1, ip.on_dot, inc_sin_sq);
+        const uint32_t imi = incident_mat_of(sc, ip), tmi = transmit_mat_of(sc, ip);
+        const bool p_out = imi == sc.base_mat && tmi == ip.surface_mat, p_in = imi == ip.surface_mat && tmi == sc.base_mat;
+        double rel0 = p_out ? mat.glass.rel_out[0] : mat.glass.rel_in[0], rel1 = p_out ? mat.glass.rel_out[1] : mat.glass.rel_in[1];
+        if (!(DRT_GLASS_CONSTANTS && sv.glass_ready && (p_out || p_in)))
+        {
+            rel0 = im.refract_i0 / tm.refract_i0;
+            rel1 = im.refract_i1 / tm.refract_i1;
+        }
+        double r0 = dielectric_reflectance_rel(rel0, im.refract_i0, tm.refract_i0, ip.on_dot, inc_sin_sq);
+        double r1 = dielectric_reflectance_rel(rel1, im.refract_i1, tm.refract_i1, ip.on_dot, inc_sin_sq);
         double rd = drt_lerp(sc.trans_wl, sc.trans_w0, sc.trans_w1, r0, r1);
         double f = drt_rng(rs, draws);
         const bool reflect = f < rd;
@@ -903,7 +930,9 @@ __device__ __forceinline__ EvalCoef eval_coefficients_by_material(const DevScene
     return e;
 }
 
-/* Direction samplers, src/bdsf.c:188-292; they return the reciprocal pdf */
+/* Direction samplers, src/bdsf.c:188-292; they return the reciprocal pdf. DRAW_BY_RECIPROCAL is drt_rng's choice (drt_device.h) for
+ * every draw in here: the one caller names it once. */
+template <bool DRAW_BY_RECIPROCAL>
 __device__ __forceinline__ void sample_direction_by_material(const DevScene &sc, const SceneView &sv, const HitPoint &ip, uint64_t &rs,
                                                  uint32_t &draws, V3 &dir, double &recip_pdf)
 {
@@ -916,7 +945,7 @@ __device__ __forceinline__ void sample_direction_by_material(const DevScene &sc,
             V3 q;
             for (;;)
             {
-                q = uniform_sample_disc(rs, draws);
+                q = uniform_sample_disc<DRAW_BY_RECIPROCAL>(rs, draws);
                 if (v_dot(q, q) < 1.0) break;
             }
             q.z = __builtin_sqrt(1.0 - v_dot(q, q));
@@ -927,7 +956,7 @@ __device__ __forceinline__ void sample_direction_by_material(const DevScene &sc,
         }
         case DRT_DIRF_uniform_sample_hemisphere: /* :191-198 */
         {
-            V3 s = uniform_sample_sphere(rs, draws);
+            V3 s = uniform_sample_sphere<DRAW_BY_RECIPROCAL>(rs, draws);
             M33 r = rotation_between(zaxis, ip.normal);
             dir = m_vmul(r, s);
             recip_pdf = 2.0 * DRT_PI;
@@ -958,7 +987,7 @@ __device__ __forceinline__ void sample_direction_by_material(const DevScene &sc,
             double rd = drt_lerp(sc.trans_wl, sc.trans_w0, sc.trans_w1, r0, r1);
             double ir = refract_at_trans_wl(sc, im);
             double tr = refract_at_trans_wl(sc, tm);
-            double f = drt_rng(rs, draws);
+            double f = drt_rng<DRAW_BY_RECIPROCAL>(rs, draws);
             V3 w = v_reverse(ip.out);
             if (f < rd)
             {
@@ -976,8 +1005,8 @@ __device__ __forceinline__ void sample_direction_by_material(const DevScene &sc,
         {
             do
             {
-                double f = drt_rng(rs, draws);
-                double g = drt_rng(rs, draws);
+                double f = drt_rng<DRAW_BY_RECIPROCAL>(rs, draws);
+                double g = drt_rng<DRAW_BY_RECIPROCAL>(rs, draws);
                 double phi_mn = (2.0 * DRT_PI) * g;
                 double tan_mn = (mat.roughness * __builtin_sqrt(f)) / __builtin_sqrt(1.0 - f);
                 double cos_mn = 1.0 / __builtin_sqrt(1.0 + tan_mn * tan_mn);
@@ -1015,13 +1044,14 @@ __device__ __forceinline__ void store_coef(uint64_t *w, const EvalCoef &e)
     w[3] = (uint64_t)__double_as_longlong(e.ct_coef);
 }
 
-/* Camera ray: sample_pixel_point + sample_scene's ray set-up, src/daily_ray_trace.c:550-607 */
+/* Camera ray: sample_pixel_point + sample_scene's ray set-up, src/daily_ray_trace.c:550-607 (BY_RECIPROCAL: drt_rng's, drt_device.h) */
+template <bool BY_RECIPROCAL = (DRT_DRAW_BY_RECIPROCAL != 0)>
 __device__ __forceinline__ void camera_ray(const DevCamera &cam, uint32_t scheme, uint32_t x, uint32_t y, uint64_t &rs,
                                            uint32_t &draws, V3 &ro, V3 &rd)
 {
     double px = 0.0, py = 0.0;
     if (scheme == DRT_FILM_SAMPLE_CENTER) { px = 0.5; py = 0.5; }
-    else if (scheme == DRT_FILM_SAMPLE_RANDOM) { px = drt_rng(rs, draws); py = drt_rng(rs, draws); }
+    else if (scheme == DRT_FILM_SAMPLE_RANDOM) { px = drt_rng<BY_RECIPROCAL>(rs, draws); py = drt_rng<BY_RECIPROCAL>(rs, draws); }
     double film_x = ((double)x + px) * cam.pixel_width;
     double film_y = ((double)y + py) * cam.pixel_height;
     V3 bottom = v_mul(cam.up, film_y);
@@ -1033,7 +1063,7 @@ __device__ __forceinline__ void camera_ray(const DevCamera &cam, uint32_t scheme
         focus_dir = v_mul(focus_dir, cam.focal_depth / v_dot(focus_dir, cam.forward));
         V3 focus_point = v_sum(pixel_point, focus_dir);
         M33 r = rotation_between(v3(0.0, 0.0, 1.0), cam.forward);
-        V3 disc_point = v_mul(uniform_sample_disc(rs, draws), cam.aperture_radius);
+        V3 disc_point = v_mul(uniform_sample_disc<BY_RECIPROCAL>(rs, draws), cam.aperture_radius);
         V3 lens_point = m_vmul(r, disc_point);
         ro = v_sum(cam.aperture_position, lens_point);
         rd = v_normalise(v_sub(focus_point, ro));
@@ -1282,6 +1312,15 @@ __device__ __forceinline__ void trace_paths_form(DevScene k_sc, DevCamera k_cam,
         uint64_t *dst = (uint64_t *)l_mats;
         for (uint32_t k = threadIdx.x; k < sc.n_mat * (uint32_t)(sizeof(DevMaterial) / 8); k += TRACE_BLOCK) dst[k] = src[k];
         __syncthreads();
+#if DRT_GLASS_CONSTANTS
+        /* the glass constants of every material, once per workgroup, from the table just staged: a thread writes only its own
+         * material's `glass` and reads only refract_i0 / refract_i1, which nobody writes */
+        for (uint32_t k = threadIdx.x; k < sc.n_mat; k += TRACE_BLOCK)
+            l_mats[k].glass = drt_glass_constants(sc.trans_wl, sc.trans_w0, sc.trans_w1, l_mats[sc.base_mat].refract_i0, l_mats[sc.base_mat].refract_i1,
+                                                  l_mats[k].refract_i0, l_mats[k].refract_i1);
+        __syncthreads();
+        sv.glass_ready = true;
+#endif
         sv.surf = l_surf;
         sv.lights = l_lights;
         sv.surf_type = l_u32;
@@ -1750,12 +1789,16 @@ __device__ __forceinline__ void trace_paths_form(DevScene k_sc, DevCamera k_cam,
                         V3 lv = v3(sv.lights[LF_VX * sv.n_lights + l], sv.lights[LF_VY * sv.n_lights + l], sv.lights[LF_VZ * sv.n_lights + l]);
                         light_position = v_sum(v_sum(lpos, v_mul(lu, u)), v_mul(lv, v));
                     }
-                    bool visible = points_mutually_visible<SCENE_IN_LDS>(sv, ip.position, light_position DRT_SCAN_STATS_ARG(bs + 18));
+                    V3 shadow_dir;
+                    bool visible = points_mutually_visible<SCENE_IN_LDS>(sv, ip.position, light_position, shadow_dir DRT_SCAN_STATS_ARG(bs + 18));
                     uint64_t *lrec = vrec + REC_VERTEX_WORDS + (uint64_t)l * REC_LIGHT_WORDS;
                     uint32_t lflags = 0;
                     if (visible)
                     {
-                        V3 incoming = v_normalise(v_sub(light_position, ip.position));
+                        /* normalise(light_position - ip.position): the shadow ray's direction, the same expression on the same
+                         * operands. Taken from the visibility test instead of written out again: the wave-uniform branch inside
+                         * v_div_shared keeps the compiler from merging two copies as it merged two plain v_normalise. */
+                        V3 incoming = shadow_dir;
                         EvalCoef e = eval_coefficients(sv, ip, vd, incoming);
                         lflags = e.flags | FLAG_VISIBLE;
                         if (l == 0 && shaded < 8u) vis0_mask |= 1u << shaded;
@@ -3574,6 +3617,53 @@ __global__ void drt_unit_kernel(int func, const double *__restrict__ in, uint32_
             break;
         }
         default: break;
+    }
+}
+
+/* Division self-test (see drt_selftest_division in include/drt_hip.h): the forms that replace a `/` of the path loop, beside that
+ * `/` on the same operands, one record per thread. v_div_shared decides per WAVE, so a record's answer says which way its wave went. */
+enum
+{
+    DRT_DIVISION_SHARED = 0, /* in: v[3] f              out: v_div_shared(v, f)[3], v.x / f, v.y / f, v.z / f, 1 = this record's three scaled
+                                                             denominators are equal, 1 = its wave shared the reciprocal */
+    DRT_DIVISION_DRAW,       /* in: rng state (u64 bits) out: drt_rng(state), (state' >> 33) / 2147483647.0, state' (bits) */
+    DRT_DIVISION_COUNT
+};
+#define DRT_DIVISION_SHARED_IN 4
+#define DRT_DIVISION_SHARED_OUT 8
+#define DRT_DIVISION_DRAW_IN 1
+#define DRT_DIVISION_DRAW_OUT 3
+
+__global__ void drt_division_kernel(int func, const double *__restrict__ in, uint32_t in_stride, double *__restrict__ out, uint32_t out_stride,
+                                    uint64_t n)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *a = in + i * in_stride;
+    double *o = out + i * out_stride;
+    if (func == DRT_DIVISION_SHARED)
+    {
+        const V3 v = v3(a[0], a[1], a[2]);
+        const double f = a[3];
+        const V3 s = v_div_shared(v, f);
+        const V3 p = v_div(v, f);
+        bool unused;
+        const long long bx = __double_as_longlong(__builtin_amdgcn_div_scale(v.x, f, false, &unused));
+        const long long by = __double_as_longlong(__builtin_amdgcn_div_scale(v.y, f, false, &unused));
+        const long long bz = __double_as_longlong(__builtin_amdgcn_div_scale(v.z, f, false, &unused));
+        const bool differ = bx != by || bx != bz;
+        o[0] = s.x; o[1] = s.y; o[2] = s.z;
+        o[3] = p.x; o[4] = p.y; o[5] = p.z;
+        o[6] = differ ? 0.0 : 1.0;
+        o[7] = (DRT_SHARED_RCP_DIV && !__any(differ)) ? 1.0 : 0.0;
+    }
+    else if (func == DRT_DIVISION_DRAW)
+    {
+        uint64_t rs = (uint64_t)__double_as_longlong(a[0]);
+        uint32_t draws = 0;
+        o[0] = drt_rng(rs, draws);
+        o[1] = (double)(uint32_t)(rs >> 33) / 2147483647.0;
+        o[2] = __longlong_as_double((long long)rs);
     }
 }
 

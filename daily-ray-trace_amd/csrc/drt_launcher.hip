@@ -5679,6 +5679,31 @@ extern "C" int drt_selftest_unit(int device, int func, const double *in, uint32_
     return 0;
 }
 
+extern "C" int drt_selftest_division(int device, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n)
+{
+    g_last_error.clear();
+    if (func < 0 || func >= DRT_DIVISION_COUNT) return fail(-1, "unknown division function %d", func);
+    if (!in || !out) return fail(-1, "null argument");
+    /* as in drt_selftest_unit: narrower records would make the kernel read or write past its buffers */
+    static const uint32_t need_in[DRT_DIVISION_COUNT] = {DRT_DIVISION_SHARED_IN, DRT_DIVISION_DRAW_IN};
+    static const uint32_t need_out[DRT_DIVISION_COUNT] = {DRT_DIVISION_SHARED_OUT, DRT_DIVISION_DRAW_OUT};
+    if (in_stride < need_in[func] || out_stride < need_out[func])
+        return fail(-1, "division function %d needs %u doubles in and %u out per record", func, need_in[func], need_out[func]);
+    if (n == 0) return 0;
+    if (n > BUILD_SELFTEST_MAX) return fail(-1, "drt_selftest_division: %llu records, more than %u", (unsigned long long)n, BUILD_SELFTEST_MAX);
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> din, dout;
+    HIP_TRY(din.need(n * in_stride));
+    HIP_TRY(dout.need(n * out_stride));
+    HIP_TRY(hipMemcpy(din, in, n * in_stride * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dout, 0, n * out_stride * 8));
+    hipLaunchKernelGGL(drt_division_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, func, din, in_stride, dout, out_stride, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout, n * out_stride * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 /* Fresnel kind of a BDSF: 0 none, 1 dielectric, 2 conductor (build_device_scene's fresnel_kind, one function) */
 static int bdsf_fresnel_kind(uint32_t b)
 {

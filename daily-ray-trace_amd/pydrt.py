@@ -769,6 +769,9 @@ def hip_lib():
             L.drt_selftest_build_topology.argtypes = [C.c_int, u64p, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), u32p, u32p]
         if hasattr(L, "drt_selftest_live_resources"):  # (as drt_selftest_path_ids above)
             L.drt_selftest_live_resources.argtypes = [C.POINTER(C.c_uint64)]
+        if hasattr(L, "drt_selftest_division"):  # (as drt_selftest_path_ids above)
+            L.drt_selftest_division.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.c_uint32,
+                                                C.c_uint64]
         _hip = L
     return _hip
 
@@ -797,7 +800,7 @@ HIP_SYMBOLS = ["drt_shade_instantiation",
                "drt_bind_depth_cuts", "drt_read_depth_film", "drt_depth_film_device_ptrs", "drt_read_depth_xyz", "drt_read_depth_bgra",
                "drt_group_bind_depth_cuts", "drt_group_read_depth_film",
                "drt_render_sample_map", "drt_group_render_sample_map",
-               "drt_live_window_of", "drt_live_window"]
+               "drt_live_window_of", "drt_live_window", "drt_selftest_division"]
 
 MAX_DEPTH_CUTS = 8  # DRT_MAX_DEPTH_CUTS
 
@@ -1510,6 +1513,23 @@ def selftest_unit(func, records, device=0):
     m = _UNIT_OUT[func]
     out = np.zeros((n, m), dtype=np.float64)
     _check(hip_lib().drt_selftest_unit(device, func, _ptr(rec, C.c_double), k, _ptr(out, C.c_double), m, n), "drt_selftest_unit")
+    return out
+
+
+DIVISION_SHARED, DIVISION_DRAW = 0, 1
+_DIVISION_OUT = {DIVISION_SHARED: 8, DIVISION_DRAW: 3}
+
+
+def selftest_division(func, records, device=0):
+    """A form that replaces a `/` of the path loop beside that `/`, over `records` ([n][k] doubles, layouts in include/drt_hip.h).
+    Record i runs on thread i: 64 consecutive records share a wave. Returns [n][m]."""
+    rec = np.ascontiguousarray(records, dtype=np.float64)
+    if rec.ndim == 1:
+        rec = rec.reshape(-1, 1)
+    n, k = rec.shape
+    m = _DIVISION_OUT[func]
+    out = np.zeros((n, m), dtype=np.float64)
+    _check(hip_lib().drt_selftest_division(device, func, _ptr(rec, C.c_double), k, _ptr(out, C.c_double), m, n), "drt_selftest_division")
     return out
 
 

@@ -792,6 +792,15 @@ int drt_selftest_path_ids(int device, const uint64_t *bases, uint32_t n_draws, c
  *                                                          in o[3] d[3] c[3] r E limit         out 1 = "certainly missed" else 0, func 0's t */
 int drt_selftest_unit(int device, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
 
+/* Division self-test, records as in drt_selftest_unit: the forms that stand where the path loop had a `/` (csrc/drt_device.h,
+ * csrc/drt_const_rule.h), beside that `/` on the same operands. Thread i of the launch runs record i, 64 consecutive records to a
+ * wave: v_div_shared chooses per wave, so the caller decides by the order of the records which of them meet in one. func:
+ *   0 v_div_shared        in v[3] f                 out v_div_shared(v, f)[3], v.x / f, v.y / f, v.z / f,
+ *                                                       1 = the record's three scaled denominators are equal bit for bit (else 0),
+ *                                                       1 = the record's wave shared the reciprocal (else 0: three plain divisions)
+ *   1 drt_rng             in rng state (u64 bits)   out the draw, (state' >> 33) / 2147483647.0 by `/`, state' (u64 bits) */
+int drt_selftest_division(int device, int func, const double *in, uint32_t in_stride, double *out, uint32_t out_stride, uint64_t n);
+
 /* Material-layer self-test: runs n records (`in_stride` doubles in, `out_stride` doubles out per record) against the device scene of
  * ctx -- its materials, pair rows, diffuse * (1/PI) rows and refractive indices at trans_wl are the ones drt_create built -- through
  * the very __device__ functions the trace and shade kernels call, in their order. A record is a surface point:
