@@ -15,6 +15,7 @@
 #include "drt_build_kernels.h"
 #include "drt_material_kernels.h"
 #include "drt_depth_kernels.h"
+#include "drt_sensor_kernels.h"
 #include "drt_window_kernels.h"
 #include "drt_window_rule.h"
 #include "drt_pair_rule.h"
@@ -261,6 +262,9 @@ struct drt_context
     uint32_t  n_cuts = 0, cut_depth[DRT_MAX_DEPTH_CUTS] = {};
     struct CutFilms { DevBuf<double> pixels[DRT_MAX_DEPTH_CUTS], avgs[DRT_MAX_DEPTH_CUTS], vars[DRT_MAX_DEPTH_CUTS]; } cuts;
     int       depth_grid_cap = 1;
+    /* sensor film (drt_bind_sensor; drt_sensor_kernels.h): n curves of S values, and one film of n channels laid out as the main film */
+    uint32_t  n_sensor = 0;
+    struct SensorFilm { DevBuf<double> curves, pixels, avgs, vars; bool spds_in_lds = false; int grid_cap = 1; } sensor;
     /* sample maps (drt_render_sample_map; drt_sample_map_kernels.h): the call's remainders, host targets on their way to the adopt
      * kernel, the report and its pinned copy -- a set of its own, whole or absent like the adaptive one it is used with */
     DevBuf<uint32_t> d_sm_rem, d_sm_targets, d_sm_report;
@@ -1025,6 +1029,41 @@ static int launch_depth_cuts(drt_context *ctx, const ShadeParams &sp, uint64_t p
     return 0;
 }
 
+/* The sensor pass of one kernel pair (a sensor bound): drt_sensor_kernel over the pair's pixels and samples, behind its shade kernel.
+ * Its queue is the cut pass's word, +3 of the pair's work words: cuts and a sensor are never bound together. */
+static const void *sensor_kernel(bool lds) { return lds ? (const void *)drt_sensor_kernel<true> : (const void *)drt_sensor_kernel<false>; }
+static size_t sensor_lds_bytes(const drt_context *ctx, uint32_t n, bool lds) { return ((lds ? (size_t)ctx->dsc.n_spd : 0) + n) * ctx->dsc.S * 8; }
+
+static int launch_sensor(drt_context *ctx, const ShadeParams &sp, uint64_t pix0)
+{
+    const size_t S = ctx->dsc.S, n = ctx->n_sensor;
+    SensorParams np{};
+    np.n_pix = sp.n_pix;
+    np.n_samples = sp.n_samples;
+    np.first_sample = sp.first_sample;
+    np.vertex_words = sp.vertex_words;
+    np.block_words = sp.block_words;
+    np.n_lights = sp.n_lights;
+    np.batch = sp.batch;
+    np.overflow = sp.overflow;
+    np.n_sets = (uint32_t)((S + 63) / 64);
+    np.max_depth = ctx->params.max_depth;
+    np.n_channels = ctx->n_sensor;
+    if (sp.n_pix >= 0xFFFFFFFFull) return fail(-1, "tile too large for the sensor work queue");
+    np.n_items = (uint32_t)sp.n_pix;
+    np.curves = ctx->sensor.curves;
+    np.pixels = ctx->sensor.pixels + pix0 * (n + 1);
+    np.avgs = ctx->sensor.avgs + pix0 * n;
+    np.vars = ctx->sensor.vars + pix0 * n;
+    const uint64_t *records = ctx->d_records, *headers = ctx->d_headers;
+    unsigned long long *queue = ctx->d_counters + DRT_NUM_COUNTERS + 3;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((sp.n_pix + SENSOR_WAVES - 1) / SENSOR_WAVES, (uint64_t)ctx->sensor.grid_cap);
+    void *args[] = {&ctx->dsc, &np, &records, &headers, &queue};
+    HIP_TRY(hipLaunchKernel(sensor_kernel(ctx->sensor.spds_in_lds), dim3(grid), dim3(SENSOR_BLOCK), args,
+                            sensor_lds_bytes(ctx, ctx->n_sensor, ctx->sensor.spds_in_lds), ctx->stream));
+    return 0;
+}
+
 template <int NSETS, bool XYZ>
 static int shade_occupancy_mode(drt_context *ctx, int *per_cu)
 {
@@ -1166,7 +1205,7 @@ static void window_refresh(drt_context *ctx)
 static bool window_in_use(drt_context *ctx)
 {
     window_refresh(ctx);
-    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0;
+    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0 && ctx->n_sensor == 0;
 }
 
 static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camera *camera, const drt_params *params)
@@ -1771,6 +1810,7 @@ static int enqueue_pair(drt_context *ctx, const PairSpan &span)
         HIP_TRY(hipGetLastError());
     }
     if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, g.pix0))) return rc;
+    if (ctx->n_sensor && (rc = launch_sensor(ctx, sp, g.pix0))) return rc;
     if (g.windowed && (rc = enqueue_window_fill(ctx, span.first_sample, span.n_samples, g.t_row0, g.t_rows))) return rc;
     const uint64_t seq = ctx->next_seq++;
     hipLaunchKernelGGL(drt_mark_pair_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_counters, (unsigned long long)seq);
@@ -1976,6 +2016,13 @@ extern "C" int drt_reset_film(drt_context *ctx)
         HIP_TRY(hipMemsetAsync(ctx->cuts.avgs[c], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
         HIP_TRY(hipMemsetAsync(ctx->cuts.vars[c], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
     }
+    if (ctx->n_sensor)
+    {
+        const size_t n = ctx->n_sensor;
+        HIP_TRY(hipMemsetAsync(ctx->sensor.pixels, 0, (size_t)ctx->n_pix * (n + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->sensor.avgs, 0, (size_t)ctx->n_pix * n * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->sensor.vars, 0, (size_t)ctx->n_pix * n * 8, ctx->stream));
+    }
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->film_used = ctx->adaptive_done = false;
@@ -2159,6 +2206,7 @@ static int adaptive_check(drt_context *ctx, const drt_adaptive *a, bool held = f
 {
     if (!ctx || !a) return fail(-1, "null argument");
     if (ctx->n_cuts) return fail(-4, "adaptive sampling with depth cuts bound is not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
+    if (ctx->n_sensor) return fail(-4, "adaptive sampling with a sensor bound is not supported: drt_bind_sensor(ctx, NULL, 0) first");
     if (ctx->xyz_mode) return fail(-4, "adaptive sampling needs the spectral film (DRT_MODE_XYZ keeps no variance)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "adaptive sampling does not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (!held && ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
@@ -2969,6 +3017,7 @@ static int map_check(const drt_context *ctx, const drt_sample_map *m, bool group
     if (m->flags & ~(DRT_MAP_DEVICE | DRT_MAP_ADD)) return fail(-1, "flags %u: DRT_MAP_DEVICE and DRT_MAP_ADD are defined", m->flags);
     if (group && (m->flags & DRT_MAP_DEVICE)) return fail(-1, "a group takes the map from host memory (DRT_MAP_DEVICE is per context)");
     if (ctx->n_cuts) return fail(-4, "sample maps with depth cuts bound are not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
+    if (ctx->n_sensor) return fail(-4, "sample maps with a sensor bound are not supported: drt_bind_sensor(ctx, NULL, 0) first");
     if (ctx->xyz_mode) return fail(-4, "sample maps need the spectral film (the DRT_MODE_XYZ film keeps no filter sum per pixel)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "sample maps do not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (ctx->n_pix > 0xFFFFFFFFull) return fail(-1, "sample maps list pixels in 32 bits: the tile has %llu", (unsigned long long)ctx->n_pix);
@@ -3290,6 +3339,7 @@ static int depth_cuts_check(const drt_context *ctx, const uint32_t *depths, uint
             return fail(-1, "%s: cut %u has depth %u, not in 1..max_depth = %u", name, c, depths[c], ctx->params.max_depth);
         if (c > 0 && depths[c] <= depths[c - 1]) return fail(-1, "%s: the depths are not strictly ascending (cut %u: %u after %u)", name, c, depths[c], depths[c - 1]);
     }
+    if (ctx->n_sensor) return fail(-4, "%s: a sensor is bound, and the two passes share a work queue: drt_bind_sensor(ctx, NULL, 0) first", name);
     if (ctx->xyz_mode) return fail(-4, "%s: the cut films are spectral films: DRT_MODE_XYZ keeps none", name);
     if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render: drt_reset_film first", name);
     if (ctx->film_used) return fail(-7, "%s: the film already holds samples the cut films would lack: drt_reset_film first", name);
@@ -3448,6 +3498,172 @@ extern "C" int drt_group_read_depth_film(drt_group *g, uint32_t cut, double *pix
             if (!c) continue;
             HIP_TRY(hipSetDevice(c->device));
             const double *dev = f == 0 ? c->cuts.pixels[cut].get() : f == 1 ? c->cuts.avgs[cut].get() : c->cuts.vars[cut].get();
+            HIP_TRY(hipMemcpy2D((char *)host[f] + k * row_bytes, n * row_bytes, dev, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
+        }
+    }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Sensor films (the kernel in drt_sensor_kernels.h)                          */
+
+/* what a bind is refused for, before any device call; n == 0 (the unbind) passes on any context */
+static int sensor_check(const drt_context *ctx, const double *curves, uint32_t n, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (n == 0) return 0;
+    if (n > DRT_MAX_SENSOR_CHANNELS) return fail(-1, "%s: %u channels, at most %u", name, n, (unsigned)DRT_MAX_SENSOR_CHANNELS);
+    if (!curves) return fail(-1, "%s: null curves", name);
+    const size_t S = ctx->dsc.S;
+    for (size_t i = 0; i < (size_t)n * S; i += 1)
+        if (!std::isfinite(curves[i])) return fail(-1, "%s: curve %zu is not finite at wavelength %zu", name, i / S, i % S);
+    if (ctx->xyz_mode) return fail(-4, "%s: the sensor film is made from the spectral film's samples: DRT_MODE_XYZ keeps none", name);
+    if (ctx->n_cuts) return fail(-4, "%s: depth cuts are bound, and the two passes share a work queue: drt_bind_depth_cuts(ctx, NULL, 0) first", name);
+    if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render or a sample map: drt_reset_film first", name);
+    if (ctx->film_used) return fail(-7, "%s: the film already holds samples the sensor film would lack: drt_reset_film first", name);
+    return 0;
+}
+
+/* the curves and a zero-filled film of n channels for ctx, into `out`; the context is not touched */
+static int sensor_alloc(drt_context *ctx, const double *curves, uint32_t n, drt_context::SensorFilm *out)
+{
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t S = ctx->dsc.S, n_pix = ctx->n_pix;
+    hipError_t e = out->curves.need((size_t)n * S);
+    if (e == hipSuccess) e = out->pixels.need(n_pix * (n + 1));
+    if (e == hipSuccess) e = out->avgs.need(n_pix * n);
+    if (e == hipSuccess) e = out->vars.need(n_pix * n);
+    if (e != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail(-3, "drt_bind_sensor: no memory for a sensor film of %u channels (%zu bytes): %s", n, n_pix * (3 * (size_t)n + 1) * 8, hipGetErrorString(e));
+    }
+    HIP_TRY(hipMemcpyAsync(out->curves, curves, (size_t)n * S * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(out->pixels, 0, n_pix * (n + 1) * 8, ctx->stream));
+    HIP_TRY(hipMemsetAsync(out->avgs, 0, n_pix * n * 8, ctx->stream));
+    HIP_TRY(hipMemsetAsync(out->vars, 0, n_pix * n * 8, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* `curves` is the caller's, and pageable */
+    /* the SPD table beside the curves in LDS where the main pass keeps it there and both fit the 64 KiB a block may ask for */
+    out->spds_in_lds = ctx->spds_in_lds && sensor_lds_bytes(ctx, n, true) <= 65536;
+    if (sensor_lds_bytes(ctx, n, out->spds_in_lds) > 65536)
+        return fail(-4, "drt_bind_sensor: %u curves of %zu wavelengths do not fit the kernel's 64 KiB of LDS", n, S);
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sensor_kernel(out->spds_in_lds), SENSOR_BLOCK, sensor_lds_bytes(ctx, n, out->spds_in_lds)));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
+    out->grid_cap = std::max(1, prop.multiProcessorCount * std::max(1, per_cu));
+    return 0;
+}
+
+/* the stream idle, then the new film in place of the old (n == 0: none) */
+static int sensor_commit(drt_context *ctx, uint32_t n, drt_context::SensorFilm *film)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->sensor = std::move(*film);
+    ctx->n_sensor = n;
+    return 0;
+}
+
+extern "C" int drt_bind_sensor(drt_context *ctx, const double *curves, uint32_t n)
+{
+    g_last_error.clear();
+    int rc = sensor_check(ctx, curves, n, "drt_bind_sensor");
+    if (rc) return rc;
+    drt_context::SensorFilm film;
+    if ((rc = sensor_alloc(ctx, curves, n, &film))) return rc;
+    return sensor_commit(ctx, n, &film);
+}
+
+static int sensor_bound(const drt_context *ctx, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (ctx->n_sensor == 0) return fail(-4, "%s: no sensor is bound (drt_bind_sensor)", name);
+    return 0;
+}
+
+extern "C" int drt_sensor_film_device_ptrs(drt_context *ctx, void **d_pixels, void **d_avgs, void **d_vars)
+{
+    int rc = sensor_bound(ctx, "drt_sensor_film_device_ptrs");
+    if (rc) return rc;
+    if (d_pixels) *d_pixels = ctx->sensor.pixels.get();
+    if (d_avgs) *d_avgs = ctx->sensor.avgs.get();
+    if (d_vars) *d_vars = ctx->sensor.vars.get();
+    return 0;
+}
+
+extern "C" int drt_read_sensor_film(drt_context *ctx, double *pixels, double *avgs, double *vars)
+{
+    int rc = sensor_bound(ctx, "drt_read_sensor_film");
+    if (rc) return rc;
+    if ((rc = drt_synchronize(ctx))) return rc;
+    const size_t n = ctx->n_sensor;
+    if (pixels) HIP_TRY(hipMemcpy(pixels, ctx->sensor.pixels, (size_t)ctx->n_pix * (n + 1) * 8, hipMemcpyDeviceToHost));
+    if (avgs) HIP_TRY(hipMemcpy(avgs, ctx->sensor.avgs, (size_t)ctx->n_pix * n * 8, hipMemcpyDeviceToHost));
+    if (vars) HIP_TRY(hipMemcpy(vars, ctx->sensor.vars, (size_t)ctx->n_pix * n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_sensor_bgra(drt_context *ctx, int which, const double *matrix, uint8_t *bgra)
+{
+    int rc = sensor_bound(ctx, "drt_read_sensor_bgra");
+    if (rc) return rc;
+    if (!matrix || !bgra) return fail(-1, "drt_read_sensor_bgra: null argument");
+    if (which < 0 || which > 1) return fail(-1, "which = %d: 0 sum / filter, 1 mean", which);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = drt_synchronize(ctx))) return rc;
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
+    SensorMatrix m{};
+    for (uint32_t i = 0; i < 3 * ctx->n_sensor; i += 1) m.m[i / ctx->n_sensor][i % ctx->n_sensor] = matrix[i];
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_sensor_bgra_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->n_pix, ctx->n_sensor,
+                       which == 0 ? ctx->sensor.pixels.get() : ctx->sensor.avgs.get(), which, m, ctx->d_bgra.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_group_bind_sensor(drt_group *g, const double *curves, uint32_t n)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_bind_sensor: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = sensor_check(c, curves, n, "drt_group_bind_sensor"))) return rc;
+    std::vector<drt_context::SensorFilm> films(g->ctx.size());
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = sensor_alloc(g->ctx[k], curves, n, &films[k]))) return rc; /* (what was allocated so far is released with `films`) */
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = sensor_commit(g->ctx[k], n, &films[k]))) return rc;
+    return 0;
+}
+
+extern "C" int drt_group_read_sensor_film(drt_group *g, double *pixels, double *avgs, double *vars)
+{
+    if (!g) return fail(-1, "drt_group_read_sensor_film: null group");
+    int rc = 0;
+    uint32_t ch = 0;
+    for (drt_context *c : g->ctx)
+    {
+        if (c && (rc = sensor_bound(c, "drt_group_read_sensor_film"))) return rc;
+        if (c) ch = c->n_sensor;
+    }
+    if ((rc = drt_group_synchronize(g))) return rc;
+    /* as group_move_rows: device k holds rows k, k + n, ... of the tile */
+    const size_t n = g->ctx.size();
+    double *host[3] = {pixels, avgs, vars};
+    for (int f = 0; f < 3; f += 1)
+    {
+        if (!host[f]) continue;
+        const size_t row_bytes = (size_t)g->tile_w * (f == 0 ? (size_t)ch + 1 : (size_t)ch) * 8;
+        for (size_t k = 0; k < n; k += 1)
+        {
+            drt_context *c = g->ctx[k];
+            if (!c) continue;
+            HIP_TRY(hipSetDevice(c->device));
+            const double *dev = f == 0 ? c->sensor.pixels.get() : f == 1 ? c->sensor.avgs.get() : c->sensor.vars.get();
             HIP_TRY(hipMemcpy2D((char *)host[f] + k * row_bytes, n * row_bytes, dev, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
         }
     }

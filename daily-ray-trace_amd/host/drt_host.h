@@ -81,7 +81,7 @@ typedef struct
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
  * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK,
- * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS. */
+ * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_REGIONS, DRT_SENSOR. */
 #define DRT_HOST_MAX_PICKS 64
 #define DRT_HOST_MAX_LEVELS 64
 #define DRT_HOST_MAX_REGIONS 64
@@ -151,6 +151,13 @@ typedef struct
      * checkpoints or resuming, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS or DRT_PROJECTION. 0 regions: off */
     uint32_t n_regions;
     uint32_t regions[DRT_HOST_MAX_REGIONS][5]; /* x, y, w, h, spp */
+    /* DRT_SENSOR="r.csv,g.csv,b.csv": a sensor film (drt_group_bind_sensor) of one channel per file, DRT_MAX_SENSOR_CHANNELS at most,
+     * every curve resampled on the render's grid by drt_host_csv_to_spectrum: the three standard outputs again with n channels as
+     * <output_spd>.sensor.spd, <average_spd>.sensor.spd and <variance_spd>.sensor.spd, and with exactly three curves the picture
+     * <output_spd>.sensor.bmp through the identity matrix; every other output stays byte for byte what it is without it. Not combined
+     * with adaptive sampling, checkpoints or resuming, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS or DRT_REGIONS. 0 curves: off */
+    uint32_t n_sensor;
+    char     sensor_csv[DRT_MAX_SENSOR_CHANNELS][256];
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u

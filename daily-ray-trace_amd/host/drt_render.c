@@ -95,6 +95,12 @@ static int depth_path(char dst[64], const char *src, u32 depth, const char *ext)
     return snprintf(dst, 64, "%s.depth%u%s", src, depth, ext) < 64 ? 0 : -1;
 }
 
+/* DRT_SENSOR: "<src>.sensor<ext>" into a config field; -1 when it does not fit */
+static int sensor_path(char dst[64], const char *src, const char *ext)
+{
+    return snprintf(dst, 64, "%s.sensor%s", src, ext) < 64 ? 0 : -1;
+}
+
 /* Frame k of DRT_LIGHT_LEVELS: `rows` gets the scene's rows [*first_row, *first_row + *count) -- from the first to the last row an emissive
  * material names as its emission -- with every such row times `level` (one multiplication per sample) and the rows between as they are.
  * No emissive material: *count = 0. */
@@ -350,8 +356,22 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     u32 n_devices = 1;
     if (opt && opt->all_devices) { devices = NULL; n_devices = 0; }
     else if (opt && opt->n_devices) { devices = opt->devices; n_devices = opt->n_devices; }
-    drt_group *ctx = drt_group_create(scene, drt_host_camera_data(hs), &p, devices, n_devices);
-    if (!ctx) rc = -1;
+    /* DRT_SENSOR: every curve on the render's grid, before the first device call */
+    const u32 n_sensor = opt ? opt->n_sensor : 0;
+    f64 *sensor_curves = NULL;
+    if (n_sensor)
+    {
+        sensor_curves = (f64 *)calloc((size_t)n_sensor * S, sizeof(f64));
+        if (!sensor_curves) rc = -3;
+        for (u32 k = 0; !rc && k < n_sensor; k += 1)
+            if (!drt_host_csv_to_spectrum(opt->sensor_csv[k], scene->min_wavelength, scene->wavelength_interval, S, sensor_curves + (size_t)k * S))
+            {
+                fprintf(stderr, "render_image: DRT_SENSOR: cannot read %s\n", opt->sensor_csv[k]);
+                rc = -1;
+            }
+    }
+    drt_group *ctx = rc ? NULL : drt_group_create(scene, drt_host_camera_data(hs), &p, devices, n_devices);
+    if (!ctx && !rc) rc = -1;
     if (!rc && !(opt && opt->quiet) && drt_group_size(ctx) > 1) printf("Rendering on %u devices\n", drt_group_size(ctx));
     /* DRT_PROJECTION: the first rays from a table, bound while the film is still without samples (a resumed film is written after it) */
     if (!rc && opt && opt->projection)
@@ -375,6 +395,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     }
     /* DRT_DEPTH_CUTS: the cut films, bound while the film is still without samples */
     if (!rc && opt && opt->n_depth_cuts) rc = drt_group_bind_depth_cuts(ctx, opt->depth_cuts, opt->n_depth_cuts);
+    /* DRT_SENSOR: the sensor film, bound while the film is still without samples */
+    if (!rc && n_sensor) rc = drt_group_bind_sensor(ctx, sensor_curves, n_sensor);
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc && opt && opt->adaptive && (opt->adaptive_checkpoint_rounds || opt->adaptive_resume))
     {
@@ -527,6 +549,52 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         free(cut_avgs);
         free(cut_pixels);
     }
+    /* DRT_SENSOR: the sensor film through the standard writer with n channels for S (the variance normalised as the standard output's
+     * is) under the outputs' names with .sensor behind them; with three curves the picture of sum / filter through the identity matrix */
+    if (!rc && n_sensor)
+    {
+        f64 *sn_pixels = (f64 *)malloc(num_pixels * (n_sensor + 1) * sizeof(f64));
+        f64 *sn_avgs = (f64 *)malloc(num_pixels * n_sensor * sizeof(f64)), *sn_vars = (f64 *)malloc(num_pixels * n_sensor * sizeof(f64));
+        if (!sn_pixels || !sn_avgs || !sn_vars) rc = -3;
+        if (!rc) rc = drt_group_read_sensor_film(ctx, sn_pixels, sn_avgs, sn_vars);
+        if (!rc)
+        {
+            config_arguments cc = *config;
+            char bmp[64];
+            if (sensor_path(cc.output_spd, config->output_spd, ".spd") || sensor_path(cc.average_spd, config->average_spd, ".spd") ||
+                sensor_path(cc.variance_spd, config->variance_spd, ".spd") || sensor_path(bmp, config->output_spd, ".bmp") ||
+                drt_host_write_outputs(&cc, width, height, n_sensor, scene->min_wavelength, scene->wavelength_interval, sn_pixels, sn_avgs, sn_vars, 0, done, seed))
+                cut_bad = -1;
+            else if (n_sensor == 3)
+            {
+                /* drt_read_sensor_bgra's rule with the identity matrix: 1 * v, then + 0 * v for the other two, in order */
+                u8 *fb = (u8 *)malloc(num_pixels * 4);
+                if (!fb) cut_bad = -1;
+                for (u64 i = 0; fb && i < num_pixels; i += 1)
+                    for (int r = 0; r < 3; r += 1)
+                    {
+                        f64 f = 0.0;
+                        for (int k = 0; k < 3; k += 1)
+                        {
+                            const f64 t = (k == r ? 1.0 : 0.0) * (sn_pixels[i * 4 + k] / sn_pixels[i * 4 + 3]);
+                            f = k == 0 ? t : f + t;
+                        }
+                        f = (f < 0.0) ? 0.0 : f;
+                        f = (f > 1.0) ? 1.0 : f;
+                        fb[i * 4 + 2 - r] = (f == f) ? (u8)(f * 255.0) : (u8)0;
+                        fb[i * 4 + 3] = 255;
+                    }
+                if (fb && drt_host_write_bmp_bgra(bmp, width, height, fb) != 0) cut_bad = -1;
+                free(fb);
+            }
+            if (cut_bad) fprintf(stderr, "render_image: could not write the outputs of the sensor film\n");
+            else if (!opt->quiet) printf("Sensor film: %u channels, %s\n", n_sensor, cc.output_spd);
+        }
+        free(sn_vars);
+        free(sn_avgs);
+        free(sn_pixels);
+    }
+    free(sensor_curves);
     /* the denoised film, while the devices still hold the scene's tables (the film itself is not changed) */
     f64 *dn_mean = NULL, *dn_var = NULL;
     if (!rc && opt && opt->denoise)
@@ -1083,6 +1151,41 @@ static int regions_options(const config_arguments *config, drt_host_options *opt
     return 0;
 }
 
+/* DRT_SENSOR="a.csv,b.csv,..." (one curve per file, DRT_MAX_SENSOR_CHANNELS at most): parsed and checked here, before any device call,
+ * after the options it cannot be combined with. The curves themselves are resampled once the scene has given the grid. */
+static int sensor_options(const config_arguments *config, drt_host_options *opt)
+{
+    opt->n_sensor = 0;
+    const char *e = getenv("DRT_SENSOR");
+    if (!e) return 0;
+    static const char *const others[] = { "DRT_ADAPTIVE_ERROR", "DRT_CHECKPOINT_SPP", "DRT_RESUME", "DRT_TURNTABLE", "DRT_LIGHT_LEVELS", "DRT_DEPTH_CUTS", "DRT_REGIONS" };
+    for (size_t k = 0; k < sizeof(others) / sizeof(others[0]); k += 1)
+        if (getenv(others[k])) { fprintf(stderr, "render_image: DRT_SENSOR cannot be combined with %s: that render keeps no sensor film\n", others[k]); return -1; }
+    for (const char *c = e;;)
+    {
+        const char *end = strchr(c, ',');
+        const size_t len = end ? (size_t)(end - c) : strlen(c);
+        if (len == 0) { fprintf(stderr, "render_image: DRT_SENSOR=\"%s\": an empty entry (one CSV file per curve, separated by commas)\n", e); return -1; }
+        if (opt->n_sensor == DRT_MAX_SENSOR_CHANNELS) { fprintf(stderr, "render_image: DRT_SENSOR: %d curves at most\n", DRT_MAX_SENSOR_CHANNELS); return -1; }
+        if (len >= sizeof(opt->sensor_csv[0])) { fprintf(stderr, "render_image: DRT_SENSOR: a file name of %zu characters, %d at most\n", len, (int)sizeof(opt->sensor_csv[0]) - 1); return -1; }
+        char *path = opt->sensor_csv[opt->n_sensor];
+        memcpy(path, c, len);
+        path[len] = 0;
+        FILE *f = fopen(path, "rb");
+        const int first = f ? fgetc(f) : EOF; /* (a directory opens, and cannot be read) */
+        if (f) fclose(f);
+        if (first == EOF) { fprintf(stderr, "render_image: DRT_SENSOR: cannot read %s\n", path); return -1; }
+        opt->n_sensor += 1;
+        if (!end) break;
+        c = end + 1;
+    }
+    char path[64];
+    if (sensor_path(path, config->output_spd, ".spd") || sensor_path(path, config->average_spd, ".spd") ||
+        sensor_path(path, config->variance_spd, ".spd") || sensor_path(path, config->output_spd, ".bmp"))
+    { fprintf(stderr, "render_image: DRT_SENSOR: an output name with .sensor.spd behind it is longer than 63 characters\n"); return -1; }
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -1117,5 +1220,6 @@ void render_image(config_arguments *config)
     if (light_levels_options(&opt) != 0) exit(-1);
     if (depth_cuts_options(config, &opt) != 0) exit(-1);
     if (regions_options(config, &opt) != 0) exit(-1);
+    if (sensor_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

@@ -743,6 +743,14 @@ def hip_lib():
             L.drt_read_depth_bgra.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
             L.drt_group_bind_depth_cuts.argtypes = [C.c_void_p, u32p, C.c_uint32]
             L.drt_group_read_depth_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
+        if hasattr(L, "drt_bind_sensor"):  # (as drt_selftest_path_ids below)
+            vpp = C.POINTER(C.c_void_p)
+            L.drt_bind_sensor.argtypes = [C.c_void_p, f64p, C.c_uint32]
+            L.drt_read_sensor_film.argtypes = [C.c_void_p, f64p, f64p, f64p]
+            L.drt_sensor_film_device_ptrs.argtypes = [C.c_void_p, vpp, vpp, vpp]
+            L.drt_read_sensor_bgra.argtypes = [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_uint8)]
+            L.drt_group_bind_sensor.argtypes = [C.c_void_p, f64p, C.c_uint32]
+            L.drt_group_read_sensor_film.argtypes = [C.c_void_p, f64p, f64p, f64p]
         if hasattr(L, "drt_rebuild_hierarchy"):
             L.drt_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
@@ -799,6 +807,8 @@ HIP_SYMBOLS = ["drt_shade_instantiation",
                "drt_update_spectra", "drt_update_materials", "drt_group_update_spectra", "drt_group_update_materials",
                "drt_bind_depth_cuts", "drt_read_depth_film", "drt_depth_film_device_ptrs", "drt_read_depth_xyz", "drt_read_depth_bgra",
                "drt_group_bind_depth_cuts", "drt_group_read_depth_film",
+               "drt_bind_sensor", "drt_read_sensor_film", "drt_sensor_film_device_ptrs", "drt_read_sensor_bgra",
+               "drt_group_bind_sensor", "drt_group_read_sensor_film",
                "drt_render_sample_map", "drt_group_render_sample_map",
                "drt_live_window_of", "drt_live_window", "drt_selftest_division"]
 
@@ -811,6 +821,40 @@ def _depth_array(depths):
     if any(d < 0 or d > 0xFFFFFFFF for d in depths):
         raise ValueError("bind_depth_cuts: depths are unsigned 32-bit numbers")
     return ((C.c_uint32 * len(depths))(*depths) if depths else None), len(depths)
+
+
+MAX_SENSOR_CHANNELS = 8  # DRT_MAX_SENSOR_CHANNELS
+
+
+def _sensor_curves(curves, S):
+    """the (float64 array [n][S] or None, n) of drt_bind_sensor: None or no rows unbinds. The count and the values are the library's
+    to refuse (drt_last_error says which); the shape is checked here, because the library cannot see it."""
+    if curves is None:
+        return None, 0
+    a = np.ascontiguousarray(curves, dtype=np.float64)
+    if a.ndim == 1 and a.size == 0:
+        return None, 0
+    if a.ndim != 2 or a.shape[1] != S:
+        raise ValueError("bind_sensor: curves of shape %s, need [n][%d] (one value per wavelength of the render's grid)" % (a.shape, S))
+    if a.shape[0] == 0:
+        return None, 0
+    return a, int(a.shape[0])
+
+
+def _sensor_matrix(matrix, n):
+    m = np.ascontiguousarray(matrix, dtype=np.float64)
+    if m.shape != (3, n):
+        raise ValueError("read_sensor_bgra: a matrix of shape %s, need (3, %d): the bound channels to R, G, B" % (m.shape, n))
+    return m
+
+
+def observer_curves(bundle):
+    """The CIE observer as sensor curves [3][S]: row k is cmf_k[s] * rw[s], one multiply each -- the weights drt_read_xyz gives a
+    wavelength before its normalisation."""
+    spds = bundle.spds()
+    sc = bundle.scene
+    rw = spds[int(sc.cmf_rw)]
+    return np.stack([spds[int(sc.cmf_x)] * rw, spds[int(sc.cmf_y)] * rw, spds[int(sc.cmf_z)] * rw])
 
 
 def depth_layers(means):
@@ -951,6 +995,37 @@ class Renderer:
         """read_bgra of cut film `cut`"""
         out = np.empty((self.n_pixels, 4), dtype=np.uint8)
         _check(self.L.drt_read_depth_bgra(self.ctx, int(cut), int(which), _ptr(out, C.c_uint8)), "drt_read_depth_bgra")
+        return out
+
+    def bind_sensor(self, curves):
+        """drt_bind_sensor: a sensor film of one channel per curve ([n][S], at most MAX_SENSOR_CHANNELS) beside the main film, on a
+        film without samples. None or an empty sequence unbinds."""
+        arr, n = _sensor_curves(curves, self.S)
+        _check(self.L.drt_bind_sensor(self.ctx, None if arr is None else _ptr(arr, C.c_double), n), "drt_bind_sensor")
+        self.n_sensor = n
+
+    def read_sensor_film(self):
+        """(pixels [P][n + 1], means [P][n], variances [P][n]) of the sensor film"""
+        n = getattr(self, "n_sensor", 0)
+        px = np.empty((self.n_pixels, n + 1), dtype=np.float64)
+        av = np.empty((self.n_pixels, n), dtype=np.float64)
+        va = np.empty((self.n_pixels, n), dtype=np.float64)
+        _check(self.L.drt_read_sensor_film(self.ctx, _ptr(px, C.c_double), _ptr(av, C.c_double), _ptr(va, C.c_double)), "drt_read_sensor_film")
+        return px, av, va
+
+    def sensor_film_device_ptrs(self):
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self.L.drt_sensor_film_device_ptrs(self.ctx, C.byref(a), C.byref(b), C.byref(c)), "drt_sensor_film_device_ptrs")
+        return a.value, b.value, c.value
+
+    def read_sensor_bgra(self, which, matrix):
+        """BMP pixel bytes [n][4] = B, G, R, 255 of the sensor film's sum / filter (0) or mean (1) through the 3 x n matrix"""
+        n = getattr(self, "n_sensor", 0)
+        if n == 0:
+            _check(self.L.drt_read_sensor_bgra(self.ctx, int(which), None, None), "drt_read_sensor_bgra")
+        m = _sensor_matrix(matrix, n)
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_sensor_bgra(self.ctx, int(which), _ptr(m, C.c_double), _ptr(out, C.c_uint8)), "drt_read_sensor_bgra")
         return out
 
     def read_hit_indices(self, num_samples):
@@ -1383,6 +1458,21 @@ class Group:
         f64p = C.POINTER(C.c_double)
         _check(self.L.drt_group_read_depth_film(self.g, int(cut), px.ctypes.data_as(f64p), av.ctypes.data_as(f64p), va.ctypes.data_as(f64p)),
                "drt_group_read_depth_film")
+        return px, av, va
+
+    def bind_sensor(self, curves):
+        """drt_group_bind_sensor: as Renderer.bind_sensor, every context checked and every film allocated before any is changed"""
+        arr, n = _sensor_curves(curves, self.S)
+        _check(self.L.drt_group_bind_sensor(self.g, None if arr is None else _ptr(arr, C.c_double), n), "drt_group_bind_sensor")
+        self.n_sensor = n
+
+    def read_sensor_film(self):
+        """drt_group_read_sensor_film: the sensor film of the whole tile, in image order"""
+        n = getattr(self, "n_sensor", 0)
+        px = np.empty((self.n_pixels, n + 1)); av = np.empty((self.n_pixels, n)); va = np.empty((self.n_pixels, n))
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.drt_group_read_sensor_film(self.g, px.ctypes.data_as(f64p), av.ctypes.data_as(f64p), va.ctypes.data_as(f64p)),
+               "drt_group_read_sensor_film")
         return px, av, va
 
     def reset_film(self):

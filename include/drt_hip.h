@@ -188,7 +188,7 @@ typedef struct drt_stats
     uint64_t shadow_scans;      /* points_mutually_visible calls             */
     uint64_t rng_draws;
     double   trace_ms;          /* path-geometry kernel, HIP-event time      */
-    double   shade_ms;          /* spectral shade + film kernel; while depth cuts are bound (drt_bind_depth_cuts), the cut pass too */
+    double   shade_ms;          /* spectral shade + film kernel; while depth cuts or a sensor are bound (drt_bind_depth_cuts, drt_bind_sensor), that pass too */
     double   total_ms;
     /* the pool of vertex records (four vertices per block): its size, the most a launch has used, and how many launches had to be
      * rendered again in worst-case-sized pieces because the pool ran out (0 unless the tile's paths grew after the context measured them) */
@@ -379,7 +379,8 @@ int drt_group_render_adaptive_continue(drt_group *g, drt_adaptive *a, uint32_t m
  * drt_render_mattes with n_samples = 0 (under their own count rules), drt_render_adaptive_continue (under its own rules) and another
  * drt_render_sample_map work; drt_render and drt_write_film are refused until drt_reset_film. A map that asks for nothing succeeds
  * with 0 rounds and leaves the same state.
- * Refused (nonzero, drt_last_error, nothing rendered, no film bit changed): a null pointer, undefined flag bits, bound depth cuts,
+ * Refused (nonzero, drt_last_error, nothing rendered, no film bit changed): a null pointer, undefined flag bits, bound depth cuts, a bound
+ * sensor,
  * DRT_MODE_XYZ, DRT_FLAG_RECORD_HITS, a tile of more than 2^32 - 1 pixels, a filter sum that is not a whole number in [0, 2^32) and a
  * DRT_MAP_ADD overflow (either message names the first such tile pixel), and a failed allocation.
  * The group form takes host memory only (DRT_MAP_DEVICE is refused): the whole tile in image order, every device its own rows. All
@@ -650,6 +651,45 @@ int drt_group_bind_depth_cuts(drt_group *g, const uint32_t *depths, uint32_t n);
 int drt_group_read_depth_film(drt_group *g, uint32_t cut, double *pixels, double *avgs, double *vars);
 
 /*
+ * Sensor films: beside the spectral film, the film some other sensor records -- up to DRT_MAX_SENSOR_CHANNELS channels, each the
+ * sample's spectrum weighted by a caller-given curve and summed PER SAMPLE, so that every channel has a running mean and a variance
+ * of its own (one path carries all wavelengths, so a channel's variance cannot be made from the film's per-wavelength variances).
+ * DESIGN.md section 5l.
+ *
+ * The rule, for pixel p, sample number m (absolute: first_sample + s), the sample's contribution c[0..S) -- what the film update of
+ * src/daily_ray_trace.c:732 takes, vignette included -- and the curves R[k][0..S); `+ - * /` only, nothing contracted:
+ *   1. for each wavelength set j = 0 .. ceil(S/64) - 1: q[i] = R[k][64j+i] * c[64j+i] where 64j+i < S, and +0.0 elsewhere (i = 0..63);
+ *   2. six times q = q[0::2] + q[1::2]; then t_j = q[0];
+ *   3. v_k = t_0, then v_k = v_k + t_j for j = 1, 2, ... in order;
+ *   4. v_k through the film update (:732-743): sum_k += v_k, the running mean and the variance accumulator with the divisor
+ *      (double)(m + 1), the filter column += 1.0.
+ *
+ * The sensor film has the main film's three buffers with n channels where that has S wavelengths: [tile_h*tile_w][n+1] sum + filter,
+ * [..][n] mean, [..][n] variance; owned by the context, zero-filled at the bind and by drt_reset_film, released at the unbind and by
+ * drt_destroy. From the bind on every sample drt_render adds to the film is added to the sensor film too; a launch whose record pool
+ * ran out leaves it untouched and is rendered again with the rest.
+ */
+#define DRT_MAX_SENSOR_CHANNELS 8
+/* Bind the context to n curves of S values each (n == 0: unbind, the films are released). Refused, with the reason in
+ * drt_last_error() and the context as it was: n > DRT_MAX_SENSOR_CHANNELS, null curves with n > 0, a curve value that is not finite,
+ * DRT_MODE_XYZ, a film that holds samples, an adaptive render or a sample map (drt_reset_film first), bound depth cuts, an allocation
+ * failure. While a sensor is bound drt_bind_depth_cuts, drt_render_adaptive, drt_render_adaptive_continue and drt_render_sample_map
+ * are refused. */
+int drt_bind_sensor(drt_context *ctx, const double *curves /* [n][S] */, uint32_t n);
+/* Copy the sensor film to host buffers (any may be NULL). Synchronises. */
+int drt_read_sensor_film(drt_context *ctx, double *pixels /* [P][n+1] */, double *avgs /* [P][n] */, double *vars /* [P][n] */);
+/* Device pointers of the sensor film's buffers; valid until the next bind, unbind or drt_destroy. */
+int drt_sensor_film_device_ptrs(drt_context *ctx, void **d_pixels, void **d_avgs, void **d_vars);
+/* The sensor film as BMP pixel bytes. which: 0 = sum / filter, 1 = mean. Row r of the 3 x n matrix takes the channels to R, G, B
+ * (m[r][0] * v_0, then + m[r][k] * v_k in order); then clamp to [0, 1], x 255, truncate (a NaN gives 0), stored B, G, R, 255.
+ * Synchronises before it converts. */
+int drt_read_sensor_bgra(drt_context *ctx, int which, const double *matrix /* [3][n] */, uint8_t *bgra);
+/* Every context is checked, and every device's film allocated, before any context is changed. */
+int drt_group_bind_sensor(drt_group *g, const double *curves, uint32_t n);
+/* The sensor film of the whole tile, in image order, as drt_group_read_depth_film. */
+int drt_group_read_sensor_film(drt_group *g, double *pixels, double *avgs, double *vars);
+
+/*
  * Scene updates: move the camera and the surfaces of a live context, where the only way used to be drt_destroy + drt_create (the
  * pool freed and allocated again, the pool measurement rendered again, the hierarchy built again). DESIGN.md section 5g.
  *
@@ -891,7 +931,7 @@ int drt_read_hierarchy(drt_context *ctx, void *nodes, uint32_t n_nodes, uint32_t
  * per kernel pair, what its samples -- all worth +0 -- leave on the film, and its paths are counted in drt_stats as the reference
  * counts them (a path, one closest-hit scan, the pixel's draws). Films, statistics and draw counts are bit for bit what they are
  * without it; DRT_NO_LIVE_WINDOW=1, read by drt_create, turns it off. Not used with DRT_FLAG_RECORD_HITS, pixel lists (adaptive
- * rounds, sample maps), a bound ray table or bound depth cuts.
+ * rounds, sample maps), a bound ray table, bound depth cuts or a bound sensor.
  */
 /* Host only, like drt_bvh_stats: the rule on the scene and camera as given. */
 int drt_live_window_of(const drt_scene *scene, const drt_camera *camera, const drt_params *params, uint32_t out[4]);
