@@ -333,7 +333,56 @@ __device__ __forceinline__ uint32_t media_index(bool swapped, bool incident, uin
  * hi + lo with |lo| <= ulp(hi) / 2, every product is exact to 2^-104, so after the <= 20 products of an exponent below 1024 the
  * result rounds to the double nearest x^y except within ~2^-98 of a rounding boundary -- at least as close to libm's pow (which the
  * reference calls and which is not correctly rounded either) as the general-purpose pow it replaces here (within 2 ulp of glibc's,
- * tests/test_gpu_parity.py), at about half the instructions. Any other exponent goes to pow(). */
+ * tests/test_gpu_parity.py), at about half the instructions. Any other exponent goes to pow().
+ *
+ * The wave-uniform form (DRT_POW_UNIFORM, default 1; with 0 the function is the plain loop alone and compiles to the assembly it
+ * had before this form existed, for an A/B from one tree). Written plainly, the loop is if-converted: every iteration EXECUTES the
+ * product and the square (7 f64 operations each) and keeps or drops each with v_cndmask -- about 30 vector instructions per
+ * iteration whatever the exponent's bit is, about 210 for shininess 100, of which 3 products and 6 squares (63 operations) are
+ * wanted. The exponent is a material constant and in every shipped scene the same on every lane that gets here, so: the first
+ * active lane's exponent is read into a scalar register (readfirstlane), the lanes that hold that exponent walk its bits with
+ * SCALAR branches (s_bitcmp / s_cmp / s_cbranch_scc around bare f64 products: no select, no discarded product), and the lanes with
+ * another exponent run the plain loop under their own mask, as before.
+ *   Same value, bit for bit. A lane's result depends on its own x and exponent only. For a lane whose exponent k equals the scalar
+ * k0, the scalar loop tests the same bits of the same integer in the same order as the plain loop tests them on k, so it runs
+ * drt_dd_mul exactly where the plain loop KEEPS its product and drt_dd_sqr exactly where it keeps its square -- the first product
+ * into (1, 0) included -- on the same operands in the same order; whatever else the plain loop computes, a select throws away.
+ * drt_dd_mul and drt_dd_sqr are the plain loop's two bodies, statement for statement (the plain loop keeps its own text so that
+ * the switch at 0 is the old function to the letter), and -ffp-contract=off leaves both as written: the same IEEE operations,
+ * each rounded once. A lane with another exponent runs the plain loop as it always did; the iterations that loop adds for a
+ * longer exponent on another lane keep nothing. tests/test_gpu_glossy_power.py holds every wave shape to the exact rule.
+ *   Three things the compiler has to be told, all found on the gfx950 listing. (1) Inside `if (k == kf)` it knows the two are equal
+ * and puts the VECTOR k in the scalar's place, which makes the loop lane-wise again: so the loop counts on k0, a copy of kf taken
+ * through an empty asm with a scalar constraint, of which the compiler knows nothing -- the comparison is on kf, the loop on k0.
+ * (An asm on the compared value itself does not help: the substitution follows the comparison. One inside the branch fails with
+ * "illegal VGPR to SGPR copy".) (2) The empty asm behind each product keeps it inside its branch: the products are speculatable,
+ * and hoisted they would be selected again. (3) Register use is the plain form's in every kernel the spill budget names
+ * (tests/test_kernel_spill_budget.py), so no kernel needs the plain loop behind a template flag. */
+#ifndef DRT_POW_UNIFORM
+#define DRT_POW_UNIFORM 1
+#endif
+
+/* (rh + rl) * (bh + bl) */
+__device__ __forceinline__ void drt_dd_mul(double &rh, double &rl, double bh, double bl)
+{
+    const double p = rh * bh;
+    double e = __builtin_fma(rh, bh, -p);
+    e = __builtin_fma(rh, bl, e);
+    e = __builtin_fma(rl, bh, e);
+    rh = p + e;
+    rl = e - (rh - p);
+}
+
+/* (bh + bl)^2 */
+__device__ __forceinline__ void drt_dd_sqr(double &bh, double &bl)
+{
+    const double p = bh * bh;
+    double e = __builtin_fma(bh, bh, -p);
+    e = __builtin_fma(bh + bh, bl, e);
+    bh = p + e;
+    bl = e - (bh - p);
+}
+
 __device__ __forceinline__ double drt_pow_shininess(double x, double y)
 {
     const uint32_t n = (uint32_t)y;
@@ -345,6 +394,29 @@ __device__ __forceinline__ double drt_pow_shininess(double x, double y)
      * which the one vector-memory counter then made it wait for. The same integer either way. */
     double yk = y;
     asm volatile("" : "+v"(yk));
+#if DRT_POW_UNIFORM
+    const uint32_t kf = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)yk); /* the first lane's among the lanes that got here */
+    uint32_t k0 = kf; /* the copy the loop counts on: a scalar the compiler knows nothing about */
+    asm volatile("" : "+s"(k0));
+    if ((uint32_t)yk == kf)
+    {
+        for (; k0 != 0u; k0 >>= 1)
+        {
+            if (k0 & 1u)
+            {
+                drt_dd_mul(rh, rl, bh, bl);
+                asm volatile("" : "+v"(rh), "+v"(rl));
+            }
+            if (k0 > 1u)
+            {
+                drt_dd_sqr(bh, bl);
+                asm volatile("" : "+v"(bh), "+v"(bl));
+            }
+        }
+        return rh + rl;
+    }
+#endif
+    /* the plain loop: every lane tests its own exponent; it runs while any of its lanes has a bit left */
     for (uint32_t k = (uint32_t)yk; __any(k != 0u); k >>= 1)
     {
         if (k & 1u)
