@@ -16,6 +16,7 @@
 #include "drt_material_kernels.h"
 #include "drt_depth_kernels.h"
 #include "drt_sensor_kernels.h"
+#include "drt_bucket_kernels.h"
 #include "drt_window_kernels.h"
 #include "drt_window_rule.h"
 #include "drt_pair_rule.h"
@@ -265,6 +266,15 @@ struct drt_context
     /* sensor film (drt_bind_sensor; drt_sensor_kernels.h): n curves of S values, and one film of n channels laid out as the main film */
     uint32_t  n_sensor = 0;
     struct SensorFilm { DevBuf<double> curves, pixels, avgs, vars; bool spds_in_lds = false; int grid_cap = 1; } sensor;
+    /* bucket films (drt_bind_buckets; drt_bucket_kernels.h): one film per bucket, laid out as the main film; the samples drt_render has
+     * added since the bind or the last reset (only uniform renders are allowed while bound, so one count holds for every pixel); the
+     * resolve's two [n_pix][S] results, the film they were made from, and the estimate with a filter column of 1 for drt_film_xyz_kernel */
+    uint32_t  n_buckets = 0;
+    struct BucketFilms { DevBuf<double> pixels[DRT_MAX_BUCKETS], avgs[DRT_MAX_BUCKETS], vars[DRT_MAX_BUCKETS]; int grid_cap = 1; } buckets;
+    uint64_t  bk_samples = 0;
+    DevBuf<double> d_bk_estimate, d_bk_error, d_bk_packed;
+    bool      bk_valid = false;
+    uint64_t  bk_gen = 0;                  /* film_gen at the last drt_resolve_buckets */
     /* sample maps (drt_render_sample_map; drt_sample_map_kernels.h): the call's remainders, host targets on their way to the adopt
      * kernel, the report and its pinned copy -- a set of its own, whole or absent like the adaptive one it is used with */
     DevBuf<uint32_t> d_sm_rem, d_sm_targets, d_sm_report;
@@ -1034,6 +1044,55 @@ static int launch_depth_cuts(drt_context *ctx, const ShadeParams &sp, uint64_t p
 static const void *sensor_kernel(bool lds) { return lds ? (const void *)drt_sensor_kernel<true> : (const void *)drt_sensor_kernel<false>; }
 static size_t sensor_lds_bytes(const drt_context *ctx, uint32_t n, bool lds) { return ((lds ? (size_t)ctx->dsc.n_spd : 0) + n) * ctx->dsc.S * 8; }
 
+/* The bucket pass of one kernel pair (buckets bound): drt_bucket_kernel over the pair's pixels and samples, behind its shade kernel.
+ * Its queue is the cut pass's word, +3 of the pair's work words: of cuts, a sensor and buckets only one is ever bound. */
+template <int NB>
+static const void *bucket_kernel(bool lds) { return lds ? (const void *)drt_bucket_kernel<NB, true> : (const void *)drt_bucket_kernel<NB, false>; }
+static const void *bucket_kernel(uint32_t n, bool lds)
+{
+    switch (n)
+    {
+        case 1: return bucket_kernel<1>(lds);
+        case 2: return bucket_kernel<2>(lds);
+        case 3: return bucket_kernel<3>(lds);
+        case 4: return bucket_kernel<4>(lds);
+        case 5: return bucket_kernel<5>(lds);
+        case 6: return bucket_kernel<6>(lds);
+        case 7: return bucket_kernel<7>(lds);
+        default: return bucket_kernel<8>(lds);
+    }
+}
+
+static int launch_buckets(drt_context *ctx, const ShadeParams &sp, uint64_t pix0)
+{
+    const size_t S = ctx->dsc.S;
+    BucketParams bp{};
+    bp.n_pix = sp.n_pix;
+    bp.n_samples = sp.n_samples;
+    bp.first_sample = sp.first_sample;
+    bp.vertex_words = sp.vertex_words;
+    bp.block_words = sp.block_words;
+    bp.n_lights = sp.n_lights;
+    bp.batch = sp.batch;
+    bp.overflow = sp.overflow;
+    bp.n_sets = (uint32_t)((S + 63) / 64);
+    bp.max_depth = ctx->params.max_depth;
+    if (sp.n_pix * bp.n_sets >= 0xFFFFFFFFull) return fail(-1, "tile too large for the bucket work queue");
+    bp.n_items = (uint32_t)(sp.n_pix * bp.n_sets);
+    for (uint32_t b = 0; b < ctx->n_buckets; b += 1)
+    {
+        bp.pixels[b] = ctx->buckets.pixels[b] + pix0 * (S + 1);
+        bp.avgs[b] = ctx->buckets.avgs[b] + pix0 * S;
+        bp.vars[b] = ctx->buckets.vars[b] + pix0 * S;
+    }
+    const uint64_t *records = ctx->d_records, *headers = ctx->d_headers;
+    unsigned long long *queue = ctx->d_counters + DRT_NUM_COUNTERS + 3;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)bp.n_items + BUCKET_WAVES - 1) / BUCKET_WAVES, (uint64_t)ctx->buckets.grid_cap);
+    void *args[] = {&ctx->dsc, &bp, &records, &headers, &queue};
+    HIP_TRY(hipLaunchKernel(bucket_kernel(ctx->n_buckets, ctx->spds_in_lds), dim3(grid), dim3(BUCKET_BLOCK), args, depth_lds_bytes(ctx), ctx->stream));
+    return 0;
+}
+
 static int launch_sensor(drt_context *ctx, const ShadeParams &sp, uint64_t pix0)
 {
     const size_t S = ctx->dsc.S, n = ctx->n_sensor;
@@ -1205,7 +1264,7 @@ static void window_refresh(drt_context *ctx)
 static bool window_in_use(drt_context *ctx)
 {
     window_refresh(ctx);
-    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0 && ctx->n_sensor == 0;
+    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0 && ctx->n_sensor == 0 && ctx->n_buckets == 0;
 }
 
 static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camera *camera, const drt_params *params)
@@ -1811,6 +1870,7 @@ static int enqueue_pair(drt_context *ctx, const PairSpan &span)
     }
     if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, g.pix0))) return rc;
     if (ctx->n_sensor && (rc = launch_sensor(ctx, sp, g.pix0))) return rc;
+    if (ctx->n_buckets && (rc = launch_buckets(ctx, sp, g.pix0))) return rc;
     if (g.windowed && (rc = enqueue_window_fill(ctx, span.first_sample, span.n_samples, g.t_row0, g.t_rows))) return rc;
     const uint64_t seq = ctx->next_seq++;
     hipLaunchKernelGGL(drt_mark_pair_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_counters, (unsigned long long)seq);
@@ -1904,7 +1964,9 @@ extern "C" int drt_render(drt_context *ctx, uint32_t first_sample, uint32_t num_
     if (!ctx) return fail(-1, "null context");
     if (ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
     ctx->film_used = true;
-    return render_impl(ctx, first_sample, num_samples);
+    const int rc = render_impl(ctx, first_sample, num_samples);
+    if (!rc && ctx->n_buckets) ctx->bk_samples += num_samples;
+    return rc;
 }
 
 static int render_pairs(drt_context *ctx, uint32_t first_sample, uint32_t num_samples);
@@ -2023,6 +2085,13 @@ extern "C" int drt_reset_film(drt_context *ctx)
         HIP_TRY(hipMemsetAsync(ctx->sensor.avgs, 0, (size_t)ctx->n_pix * n * 8, ctx->stream));
         HIP_TRY(hipMemsetAsync(ctx->sensor.vars, 0, (size_t)ctx->n_pix * n * 8, ctx->stream));
     }
+    for (uint32_t b = 0; b < ctx->n_buckets; b += 1)
+    {
+        HIP_TRY(hipMemsetAsync(ctx->buckets.pixels[b], 0, (size_t)ctx->n_pix * (S + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->buckets.avgs[b], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->buckets.vars[b], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+    }
+    ctx->bk_samples = 0;
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->film_used = ctx->adaptive_done = false;
@@ -2207,6 +2276,7 @@ static int adaptive_check(drt_context *ctx, const drt_adaptive *a, bool held = f
     if (!ctx || !a) return fail(-1, "null argument");
     if (ctx->n_cuts) return fail(-4, "adaptive sampling with depth cuts bound is not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
     if (ctx->n_sensor) return fail(-4, "adaptive sampling with a sensor bound is not supported: drt_bind_sensor(ctx, NULL, 0) first");
+    if (ctx->n_buckets) return fail(-4, "adaptive sampling with buckets bound is not supported: drt_bind_buckets(ctx, 0) first");
     if (ctx->xyz_mode) return fail(-4, "adaptive sampling needs the spectral film (DRT_MODE_XYZ keeps no variance)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "adaptive sampling does not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (!held && ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
@@ -3018,6 +3088,7 @@ static int map_check(const drt_context *ctx, const drt_sample_map *m, bool group
     if (group && (m->flags & DRT_MAP_DEVICE)) return fail(-1, "a group takes the map from host memory (DRT_MAP_DEVICE is per context)");
     if (ctx->n_cuts) return fail(-4, "sample maps with depth cuts bound are not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
     if (ctx->n_sensor) return fail(-4, "sample maps with a sensor bound are not supported: drt_bind_sensor(ctx, NULL, 0) first");
+    if (ctx->n_buckets) return fail(-4, "sample maps with buckets bound are not supported: drt_bind_buckets(ctx, 0) first");
     if (ctx->xyz_mode) return fail(-4, "sample maps need the spectral film (the DRT_MODE_XYZ film keeps no filter sum per pixel)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "sample maps do not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (ctx->n_pix > 0xFFFFFFFFull) return fail(-1, "sample maps list pixels in 32 bits: the tile has %llu", (unsigned long long)ctx->n_pix);
@@ -3340,6 +3411,7 @@ static int depth_cuts_check(const drt_context *ctx, const uint32_t *depths, uint
         if (c > 0 && depths[c] <= depths[c - 1]) return fail(-1, "%s: the depths are not strictly ascending (cut %u: %u after %u)", name, c, depths[c], depths[c - 1]);
     }
     if (ctx->n_sensor) return fail(-4, "%s: a sensor is bound, and the two passes share a work queue: drt_bind_sensor(ctx, NULL, 0) first", name);
+    if (ctx->n_buckets) return fail(-4, "%s: buckets are bound, and the two passes share a work queue: drt_bind_buckets(ctx, 0) first", name);
     if (ctx->xyz_mode) return fail(-4, "%s: the cut films are spectral films: DRT_MODE_XYZ keeps none", name);
     if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render: drt_reset_film first", name);
     if (ctx->film_used) return fail(-7, "%s: the film already holds samples the cut films would lack: drt_reset_film first", name);
@@ -3519,6 +3591,7 @@ static int sensor_check(const drt_context *ctx, const double *curves, uint32_t n
         if (!std::isfinite(curves[i])) return fail(-1, "%s: curve %zu is not finite at wavelength %zu", name, i / S, i % S);
     if (ctx->xyz_mode) return fail(-4, "%s: the sensor film is made from the spectral film's samples: DRT_MODE_XYZ keeps none", name);
     if (ctx->n_cuts) return fail(-4, "%s: depth cuts are bound, and the two passes share a work queue: drt_bind_depth_cuts(ctx, NULL, 0) first", name);
+    if (ctx->n_buckets) return fail(-4, "%s: buckets are bound, and the two passes share a work queue: drt_bind_buckets(ctx, 0) first", name);
     if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render or a sample map: drt_reset_film first", name);
     if (ctx->film_used) return fail(-7, "%s: the film already holds samples the sensor film would lack: drt_reset_film first", name);
     return 0;
@@ -3667,6 +3740,316 @@ extern "C" int drt_group_read_sensor_film(drt_group *g, double *pixels, double *
             HIP_TRY(hipMemcpy2D((char *)host[f] + k * row_bytes, n * row_bytes, dev, row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
         }
     }
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Bucket films (the kernels in drt_bucket_kernels.h)                         */
+
+/* what a bind is refused for, before any device call; n == 0 (the unbind) passes on any context */
+static int buckets_check(const drt_context *ctx, uint32_t n, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (n == 0) return 0;
+    if (n > DRT_MAX_BUCKETS) return fail(-1, "%s: %u buckets, at most %u", name, n, (unsigned)DRT_MAX_BUCKETS);
+    if (ctx->xyz_mode) return fail(-4, "%s: the bucket films are spectral films: DRT_MODE_XYZ keeps none", name);
+    if (ctx->n_cuts) return fail(-4, "%s: depth cuts are bound, and the two passes share a work queue: drt_bind_depth_cuts(ctx, NULL, 0) first", name);
+    if (ctx->n_sensor) return fail(-4, "%s: a sensor is bound, and the two passes share a work queue: drt_bind_sensor(ctx, NULL, 0) first", name);
+    if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render or a sample map: drt_reset_film first", name);
+    if (ctx->film_used) return fail(-7, "%s: the film already holds samples the bucket films would lack: drt_reset_film first", name);
+    return 0;
+}
+
+/* n zero-filled bucket films for ctx, into `out`; the context is not touched */
+static int buckets_alloc(drt_context *ctx, uint32_t n, drt_context::BucketFilms *out)
+{
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t S = ctx->dsc.S, n_pix = ctx->n_pix;
+    for (uint32_t b = 0; b < n; b += 1)
+    {
+        hipError_t e = out->pixels[b].need(n_pix * (S + 1));
+        if (e == hipSuccess) e = out->avgs[b].need(n_pix * S);
+        if (e == hipSuccess) e = out->vars[b].need(n_pix * S);
+        if (e != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(-3, "drt_bind_buckets: no memory for bucket film %u of %u (%zu bytes each): %s", b, n, n_pix * (3 * S + 1) * 8, hipGetErrorString(e));
+        }
+        HIP_TRY(hipMemsetAsync(out->pixels[b], 0, n_pix * (S + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(out->avgs[b], 0, n_pix * S * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(out->vars[b], 0, n_pix * S * 8, ctx->stream));
+    }
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bucket_kernel(n, ctx->spds_in_lds), BUCKET_BLOCK, depth_lds_bytes(ctx)));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
+    out->grid_cap = std::max(1, prop.multiProcessorCount * std::max(1, per_cu));
+    return 0;
+}
+
+/* the stream idle, then the new films in place of the old (n == 0: none); an earlier resolve's results go with the old films */
+static int buckets_commit(drt_context *ctx, uint32_t n, drt_context::BucketFilms *films)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->buckets = std::move(*films);
+    ctx->n_buckets = n;
+    ctx->bk_samples = 0;
+    ctx->bk_valid = false;
+    ctx->d_bk_estimate = DevBuf<double>();
+    ctx->d_bk_error = DevBuf<double>();
+    ctx->d_bk_packed = DevBuf<double>();
+    return 0;
+}
+
+extern "C" int drt_bind_buckets(drt_context *ctx, uint32_t n)
+{
+    g_last_error.clear();
+    int rc = buckets_check(ctx, n, "drt_bind_buckets");
+    if (rc) return rc;
+    drt_context::BucketFilms films;
+    if ((rc = buckets_alloc(ctx, n, &films))) return rc;
+    return buckets_commit(ctx, n, &films);
+}
+
+static int bucket_index(const drt_context *ctx, uint32_t b, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (ctx->n_buckets == 0) return fail(-4, "%s: no buckets are bound (drt_bind_buckets)", name);
+    if (b >= ctx->n_buckets) return fail(-1, "%s: bucket %u of %u", name, b, ctx->n_buckets);
+    return 0;
+}
+
+extern "C" int drt_bucket_film_device_ptrs(drt_context *ctx, uint32_t b, void **d_pixels, void **d_avgs, void **d_vars)
+{
+    int rc = bucket_index(ctx, b, "drt_bucket_film_device_ptrs");
+    if (rc) return rc;
+    if ((rc = drt_synchronize(ctx))) return rc; /* (a launch that ran out of records is rendered again before anyone reads the films) */
+    if (d_pixels) *d_pixels = ctx->buckets.pixels[b].get();
+    if (d_avgs) *d_avgs = ctx->buckets.avgs[b].get();
+    if (d_vars) *d_vars = ctx->buckets.vars[b].get();
+    return 0;
+}
+
+extern "C" int drt_read_bucket_film(drt_context *ctx, uint32_t b, double *pixels, double *avgs, double *vars)
+{
+    int rc = bucket_index(ctx, b, "drt_read_bucket_film");
+    if (rc) return rc;
+    if ((rc = drt_synchronize(ctx))) return rc;
+    const size_t S = ctx->dsc.S;
+    if (pixels) HIP_TRY(hipMemcpy(pixels, ctx->buckets.pixels[b], (size_t)ctx->n_pix * (S + 1) * 8, hipMemcpyDeviceToHost));
+    if (avgs) HIP_TRY(hipMemcpy(avgs, ctx->buckets.avgs[b], (size_t)ctx->n_pix * S * 8, hipMemcpyDeviceToHost));
+    if (vars) HIP_TRY(hipMemcpy(vars, ctx->buckets.vars[b], (size_t)ctx->n_pix * S * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* what a resolve is refused for, before any device call */
+static int resolve_check(const drt_context *ctx, uint32_t trim, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (ctx->n_buckets == 0) return fail(-4, "%s: no buckets are bound (drt_bind_buckets)", name);
+    if (ctx->n_buckets < 2) return fail(-4, "%s: one bucket has no scatter to resolve: bind at least 2", name);
+    if (2ull * trim >= ctx->n_buckets) return fail(-1, "%s: trim = %u leaves nothing of %u buckets (2 * trim < n)", name, trim, ctx->n_buckets);
+    if (ctx->bk_samples < ctx->n_buckets)
+        return fail(-7, "%s: the film holds %llu samples, fewer than its %u buckets: some bucket is empty", name, (unsigned long long)ctx->bk_samples, ctx->n_buckets);
+    return 0;
+}
+
+template <int NB>
+static void launch_resolve(drt_context *ctx, uint64_t n_values, const BucketMeans &means, uint32_t trim)
+{
+    hipLaunchKernelGGL(drt_bucket_resolve_kernel<NB>, dim3((uint32_t)((n_values + 255) / 256)), dim3(256), 0, ctx->stream, n_values, means, trim,
+                       ctx->d_bk_estimate.get(), ctx->d_bk_error.get());
+}
+
+static int resolve_enqueue(drt_context *ctx, uint32_t trim)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = drt_synchronize(ctx); /* the complete films first (see drt_read_xyz) */
+    if (rc) return rc;
+    const uint64_t n_values = ctx->n_pix * (uint64_t)ctx->dsc.S;
+    if ((n_values + 255) / 256 > 0x7FFFFFFFull) return fail(-1, "drt_resolve_buckets: tile too large for one launch");
+    ctx->bk_valid = false;
+    hipError_t e = ctx->d_bk_estimate.need(n_values);
+    if (e == hipSuccess) e = ctx->d_bk_error.need(n_values);
+    if (e != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return fail(-3, "drt_resolve_buckets: no memory for the estimate and the error (%llu bytes each): %s", (unsigned long long)n_values * 8, hipGetErrorString(e));
+    }
+    BucketMeans means{};
+    for (uint32_t b = 0; b < ctx->n_buckets; b += 1) means.avgs[b] = ctx->buckets.avgs[b].get();
+    switch (ctx->n_buckets)
+    {
+        case 2: launch_resolve<2>(ctx, n_values, means, trim); break;
+        case 3: launch_resolve<3>(ctx, n_values, means, trim); break;
+        case 4: launch_resolve<4>(ctx, n_values, means, trim); break;
+        case 5: launch_resolve<5>(ctx, n_values, means, trim); break;
+        case 6: launch_resolve<6>(ctx, n_values, means, trim); break;
+        case 7: launch_resolve<7>(ctx, n_values, means, trim); break;
+        default: launch_resolve<8>(ctx, n_values, means, trim); break;
+    }
+    HIP_TRY(hipGetLastError());
+    ctx->bk_valid = true;
+    ctx->bk_gen = ctx->film_gen;
+    return 0;
+}
+
+extern "C" int drt_resolve_buckets(drt_context *ctx, uint32_t trim)
+{
+    g_last_error.clear();
+    int rc = resolve_check(ctx, trim, "drt_resolve_buckets");
+    if (rc) return rc;
+    return resolve_enqueue(ctx, trim);
+}
+
+static int resolve_current(const drt_context *ctx, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (ctx->n_buckets == 0) return fail(-4, "%s: no buckets are bound (drt_bind_buckets)", name);
+    if (!ctx->bk_valid) return fail(-7, "%s: nothing is resolved yet: drt_resolve_buckets first", name);
+    if (ctx->bk_gen != ctx->film_gen) return fail(-7, "%s: the film has changed since the last resolve: drt_resolve_buckets again", name);
+    return 0;
+}
+
+extern "C" int drt_bucket_resolve_device_ptrs(drt_context *ctx, void **d_estimate, void **d_error)
+{
+    int rc = resolve_current(ctx, "drt_bucket_resolve_device_ptrs");
+    if (rc) return rc;
+    if (d_estimate) *d_estimate = ctx->d_bk_estimate.get();
+    if (d_error) *d_error = ctx->d_bk_error.get();
+    return 0;
+}
+
+extern "C" int drt_read_bucket_resolve(drt_context *ctx, double *estimate, double *error)
+{
+    int rc = resolve_current(ctx, "drt_read_bucket_resolve");
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t bytes = (size_t)ctx->n_pix * ctx->dsc.S * 8;
+    if (estimate) HIP_TRY(hipMemcpy(estimate, ctx->d_bk_estimate, bytes, hipMemcpyDeviceToHost));
+    if (error) HIP_TRY(hipMemcpy(error, ctx->d_bk_error, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* drt_film_xyz_kernel reads [n_pix][S + 1] and divides by the last column: the estimate with a column of 1.0 (x / 1.0 is x) */
+extern "C" int drt_read_bucket_resolve_xyz(drt_context *ctx, double *xyz)
+{
+    int rc = resolve_current(ctx, "drt_read_bucket_resolve_xyz");
+    if (rc) return rc;
+    if (!xyz) return fail(-1, "drt_read_bucket_resolve_xyz: null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t S = ctx->dsc.S;
+    HIP_TRY(ctx->d_xyz.need((size_t)ctx->n_pix * 3));
+    HIP_TRY(ctx->d_bk_packed.need((size_t)ctx->n_pix * (S + 1)));
+    const uint64_t n_values = ctx->n_pix * (uint64_t)(S + 1);
+    hipLaunchKernelGGL(drt_bucket_pack_kernel, dim3((uint32_t)((n_values + 255) / 256)), dim3(256), 0, ctx->stream, n_values, (uint32_t)S,
+                       (const double *)ctx->d_bk_estimate.get(), ctx->d_bk_packed.get());
+    HIP_TRY(hipGetLastError());
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_film_xyz_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z,
+                       ctx->interval, ctx->n_pix, (const double *)ctx->d_bk_packed.get(), ctx->d_xyz);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(xyz, ctx->d_xyz, (size_t)ctx->n_pix * 3 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_bucket_resolve_bgra(drt_context *ctx, uint8_t *bgra)
+{
+    int rc = resolve_current(ctx, "drt_read_bucket_resolve_bgra");
+    if (rc) return rc;
+    if (!bgra) return fail(-1, "drt_read_bucket_resolve_bgra: null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_film_bgra_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z,
+                       ctx->interval, ctx->n_pix, (const double *)ctx->d_bk_estimate.get(), 1, ctx->d_bgra);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_group_bind_buckets(drt_group *g, uint32_t n)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_bind_buckets: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = buckets_check(c, n, "drt_group_bind_buckets"))) return rc;
+    std::vector<drt_context::BucketFilms> films(g->ctx.size());
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = buckets_alloc(g->ctx[k], n, &films[k]))) return rc; /* (what was allocated so far is released with `films`) */
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = buckets_commit(g->ctx[k], n, &films[k]))) return rc;
+    return 0;
+}
+
+/* as group_move_rows: device k of n holds rows k, k + n, ... of the tile; dev(c): that context's buffer, rows of row_bytes bytes */
+template <typename F>
+static int group_gather_bucket_rows(drt_group *g, double *host, size_t row_bytes, F dev)
+{
+    const size_t n = g->ctx.size();
+    for (size_t k = 0; k < n; k += 1)
+    {
+        drt_context *c = g->ctx[k];
+        if (!c) continue;
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipMemcpy2D((char *)host + k * row_bytes, n * row_bytes, dev(c), row_bytes, row_bytes, g->rows[k], hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+extern "C" int drt_group_read_bucket_film(drt_group *g, uint32_t b, double *pixels, double *avgs, double *vars)
+{
+    if (!g) return fail(-1, "drt_group_read_bucket_film: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = bucket_index(c, b, "drt_group_read_bucket_film"))) return rc;
+    if ((rc = drt_group_synchronize(g))) return rc;
+    double *host[3] = {pixels, avgs, vars};
+    for (int f = 0; f < 3; f += 1)
+    {
+        if (!host[f]) continue;
+        const size_t row_bytes = (size_t)g->tile_w * (f == 0 ? (size_t)g->S + 1 : (size_t)g->S) * 8;
+        rc = group_gather_bucket_rows(g, host[f], row_bytes, [&](drt_context *c) -> const double * {
+            return f == 0 ? c->buckets.pixels[b].get() : f == 1 ? c->buckets.avgs[b].get() : c->buckets.vars[b].get();
+        });
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+extern "C" int drt_group_resolve_buckets(drt_group *g, uint32_t trim)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_resolve_buckets: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = resolve_check(c, trim, "drt_group_resolve_buckets"))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = resolve_enqueue(c, trim))) return rc;
+    return 0;
+}
+
+extern "C" int drt_group_read_bucket_resolve(drt_group *g, double *estimate, double *error)
+{
+    if (!g) return fail(-1, "drt_group_read_bucket_resolve: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = resolve_current(c, "drt_group_read_bucket_resolve"))) return rc;
+    for (drt_context *c : g->ctx)
+        if (c)
+        {
+            HIP_TRY(hipSetDevice(c->device));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+        }
+    const size_t row_bytes = (size_t)g->tile_w * (size_t)g->S * 8;
+    if (estimate && (rc = group_gather_bucket_rows(g, estimate, row_bytes, [](drt_context *c) -> const double * { return c->d_bk_estimate.get(); }))) return rc;
+    if (error && (rc = group_gather_bucket_rows(g, error, row_bytes, [](drt_context *c) -> const double * { return c->d_bk_error.get(); }))) return rc;
     return 0;
 }
 

@@ -81,7 +81,7 @@ typedef struct
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
  * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK,
- * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_REGIONS, DRT_SENSOR. */
+ * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_REGIONS, DRT_SENSOR, DRT_BUCKETS. */
 #define DRT_HOST_MAX_PICKS 64
 #define DRT_HOST_MAX_LEVELS 64
 #define DRT_HOST_MAX_REGIONS 64
@@ -158,6 +158,13 @@ typedef struct
      * with adaptive sampling, checkpoints or resuming, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS or DRT_REGIONS. 0 curves: off */
     uint32_t n_sensor;
     char     sensor_csv[DRT_MAX_SENSOR_CHANNELS][256];
+    /* DRT_BUCKETS="n[,trim]": bucket films (drt_group_bind_buckets) of n buckets, DRT_MAX_BUCKETS at most: per bucket b the three standard
+     * .spd outputs again as <output_spd>.bucket<b>.spd, <average_spd>.bucket<b>.spd and <variance_spd>.bucket<b>.spd, and with n >= 2 the
+     * resolve (drt_group_resolve_buckets with `trim`; the median's, (n - 1) / 2, when none is given): the estimate as
+     * <average_spd>.robust.spd, the error as <variance_spd>.robust.spd, both under the average file's header, and the picture of the
+     * estimate <output_spd>.robust.bmp; every other output stays byte for byte what it is without it. Not combined with adaptive
+     * sampling, checkpoints or resuming, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_SENSOR or DRT_REGIONS. 0 buckets: off */
+    uint32_t n_buckets, bucket_trim;
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u

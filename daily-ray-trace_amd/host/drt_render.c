@@ -101,6 +101,16 @@ static int sensor_path(char dst[64], const char *src, const char *ext)
     return snprintf(dst, 64, "%s.sensor%s", src, ext) < 64 ? 0 : -1;
 }
 
+/* DRT_BUCKETS: "<src>.bucket<b><ext>" and "<src>.robust<ext>" into a config field; -1 when it does not fit */
+static int bucket_path(char dst[64], const char *src, u32 b, const char *ext)
+{
+    return snprintf(dst, 64, "%s.bucket%u%s", src, b, ext) < 64 ? 0 : -1;
+}
+static int robust_path(char dst[64], const char *src, const char *ext)
+{
+    return snprintf(dst, 64, "%s.robust%s", src, ext) < 64 ? 0 : -1;
+}
+
 /* Frame k of DRT_LIGHT_LEVELS: `rows` gets the scene's rows [*first_row, *first_row + *count) -- from the first to the last row an emissive
  * material names as its emission -- with every such row times `level` (one multiplication per sample) and the rows between as they are.
  * No emissive material: *count = 0. */
@@ -397,6 +407,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     if (!rc && opt && opt->n_depth_cuts) rc = drt_group_bind_depth_cuts(ctx, opt->depth_cuts, opt->n_depth_cuts);
     /* DRT_SENSOR: the sensor film, bound while the film is still without samples */
     if (!rc && n_sensor) rc = drt_group_bind_sensor(ctx, sensor_curves, n_sensor);
+    /* DRT_BUCKETS: the bucket films, bound while the film is still without samples */
+    if (!rc && opt && opt->n_buckets) rc = drt_group_bind_buckets(ctx, opt->n_buckets);
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc && opt && opt->adaptive && (opt->adaptive_checkpoint_rounds || opt->adaptive_resume))
     {
@@ -595,6 +607,50 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         free(sn_pixels);
     }
     free(sensor_curves);
+    /* DRT_BUCKETS: every bucket film through the standard writer (the variance normalised as the standard output's is) under the outputs'
+     * names with .bucket<b> behind them; with two buckets or more the resolve: estimate and error under the average file's header, and
+     * the estimate's picture by the .spd -> .bmp post-process */
+    if (!rc && opt && opt->n_buckets)
+    {
+        const u32 n_buckets = opt->n_buckets;
+        f64 *bk_pixels = (f64 *)malloc(num_pixels * (S + 1) * sizeof(f64));
+        f64 *bk_avgs = (f64 *)malloc(num_pixels * S * sizeof(f64)), *bk_vars = (f64 *)malloc(num_pixels * S * sizeof(f64));
+        f64 *cmf = (f64 *)malloc((size_t)4 * S * sizeof(f64));
+        if (!bk_pixels || !bk_avgs || !bk_vars || !cmf) rc = -3;
+        if (!rc)
+        {
+            const u32 rows[4] = { scene->cmf_rw, scene->cmf_x, scene->cmf_y, scene->cmf_z };
+            for (int r = 0; r < 4; r += 1) memcpy(cmf + (size_t)r * S, scene->spds + (size_t)rows[r] * S, (size_t)S * sizeof(f64));
+        }
+        for (u32 b = 0; !rc && !cut_bad && b < n_buckets; b += 1)
+        {
+            config_arguments cc = *config;
+            if ((rc = drt_group_read_bucket_film(ctx, b, bk_pixels, bk_avgs, bk_vars))) break;
+            /* the filter column says how many of the samples fell into this bucket */
+            if (bucket_path(cc.output_spd, config->output_spd, b, ".spd") || bucket_path(cc.average_spd, config->average_spd, b, ".spd") ||
+                bucket_path(cc.variance_spd, config->variance_spd, b, ".spd") ||
+                drt_host_write_outputs(&cc, width, height, S, scene->min_wavelength, scene->wavelength_interval, bk_pixels, bk_avgs, bk_vars, 0,
+                                       (done - b + n_buckets - 1) / n_buckets, seed))
+                cut_bad = -1;
+        }
+        if (!rc && !cut_bad && n_buckets >= 2)
+        {
+            char est[64], err[64], bmp[64];
+            if (!(rc = drt_group_resolve_buckets(ctx, opt->bucket_trim)) && !(rc = drt_group_read_bucket_resolve(ctx, bk_avgs, bk_vars)))
+            {
+                if (robust_path(est, config->average_spd, ".spd") || robust_path(err, config->variance_spd, ".spd") || robust_path(bmp, config->output_spd, ".bmp") ||
+                    publish_spd(est, width, height, S, scene->min_wavelength, scene->wavelength_interval, bk_avgs) ||
+                    publish_spd(err, width, height, S, scene->min_wavelength, scene->wavelength_interval, bk_vars) || drt_host_spd_file_to_bmp(est, bmp, cmf))
+                    cut_bad = -1;
+            }
+        }
+        if (cut_bad) fprintf(stderr, "render_image: could not write the outputs of the bucket films\n");
+        else if (!rc && !opt->quiet) printf("Bucket films: %u buckets, trim %u\n", n_buckets, opt->bucket_trim);
+        free(cmf);
+        free(bk_vars);
+        free(bk_avgs);
+        free(bk_pixels);
+    }
     /* the denoised film, while the devices still hold the scene's tables (the film itself is not changed) */
     f64 *dn_mean = NULL, *dn_var = NULL;
     if (!rc && opt && opt->denoise)
@@ -1186,6 +1242,49 @@ static int sensor_options(const config_arguments *config, drt_host_options *opt)
     return 0;
 }
 
+/* DRT_BUCKETS="n[,trim]" (whole numbers; 1 <= n <= DRT_MAX_BUCKETS; 2 * trim < n; no trim with n = 1, which has nothing to resolve):
+ * parsed and checked here, before any device call. Without a trim the median's: (n - 1) / 2. */
+static int buckets_options(const config_arguments *config, drt_host_options *opt)
+{
+    opt->n_buckets = opt->bucket_trim = 0;
+    const char *e = getenv("DRT_BUCKETS");
+    if (!e) return 0;
+    static const char *const others[] = { "DRT_ADAPTIVE_ERROR", "DRT_CHECKPOINT_SPP", "DRT_RESUME", "DRT_TURNTABLE", "DRT_LIGHT_LEVELS", "DRT_DEPTH_CUTS", "DRT_SENSOR", "DRT_REGIONS" };
+    for (size_t k = 0; k < sizeof(others) / sizeof(others[0]); k += 1)
+        if (getenv(others[k])) { fprintf(stderr, "render_image: DRT_BUCKETS cannot be combined with %s: that render keeps no bucket films\n", others[k]); return -1; }
+    unsigned long long v[2] = { 0, 0 };
+    int n_values = 0, ok = 1;
+    const char *c = e;
+    for (; ok && n_values < 2; n_values += 1)
+    {
+        char *stop = NULL;
+        ok = *c >= '0' && *c <= '9';
+        if (!ok) break;
+        v[n_values] = strtoull(c, &stop, 10);
+        ok = v[n_values] <= 0xFFFFFFFFull && stop - c <= 10;
+        c = stop;
+        if (!ok || *c != ',') { n_values += 1; break; }
+        c += 1;
+        if (n_values == 1) ok = 0; /* a second comma */
+    }
+    if (!ok || *c || n_values == 0)
+    { fprintf(stderr, "render_image: DRT_BUCKETS=\"%s\": n or n,trim in whole numbers\n", e); return -1; }
+    if (v[0] == 0 || v[0] > DRT_MAX_BUCKETS) { fprintf(stderr, "render_image: DRT_BUCKETS: %llu buckets: from 1 to %d\n", v[0], DRT_MAX_BUCKETS); return -1; }
+    if (n_values == 2 && v[0] == 1) { fprintf(stderr, "render_image: DRT_BUCKETS: one bucket has nothing to resolve, and so no trim\n"); return -1; }
+    if (n_values == 2 && 2 * v[1] >= v[0])
+    { fprintf(stderr, "render_image: DRT_BUCKETS: a trim of %llu leaves nothing of %llu buckets (2 * trim < n)\n", v[1], v[0]); return -1; }
+    if (config->num_pixel_samples < v[0])
+    { fprintf(stderr, "render_image: DRT_BUCKETS: %llu buckets of num_pixel_samples = %u samples: some bucket would stay empty\n", v[0], config->num_pixel_samples); return -1; }
+    char path[64];
+    if (bucket_path(path, config->output_spd, (u32)v[0] - 1, ".spd") || bucket_path(path, config->average_spd, (u32)v[0] - 1, ".spd") ||
+        bucket_path(path, config->variance_spd, (u32)v[0] - 1, ".spd") || robust_path(path, config->average_spd, ".spd") ||
+        robust_path(path, config->variance_spd, ".spd") || robust_path(path, config->output_spd, ".bmp"))
+    { fprintf(stderr, "render_image: DRT_BUCKETS: an output name with .bucket%u.spd or .robust.spd behind it is longer than 63 characters\n", (u32)v[0] - 1); return -1; }
+    opt->n_buckets = (u32)v[0];
+    opt->bucket_trim = n_values == 2 ? (u32)v[1] : ((u32)v[0] - 1) / 2;
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -1221,5 +1320,6 @@ void render_image(config_arguments *config)
     if (depth_cuts_options(config, &opt) != 0) exit(-1);
     if (regions_options(config, &opt) != 0) exit(-1);
     if (sensor_options(config, &opt) != 0) exit(-1);
+    if (buckets_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

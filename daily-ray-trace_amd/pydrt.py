@@ -751,6 +751,20 @@ def hip_lib():
             L.drt_read_sensor_bgra.argtypes = [C.c_void_p, C.c_int, f64p, C.POINTER(C.c_uint8)]
             L.drt_group_bind_sensor.argtypes = [C.c_void_p, f64p, C.c_uint32]
             L.drt_group_read_sensor_film.argtypes = [C.c_void_p, f64p, f64p, f64p]
+        if hasattr(L, "drt_bind_buckets"):  # (as drt_selftest_path_ids below)
+            vpp, u8p = C.POINTER(C.c_void_p), C.POINTER(C.c_uint8)
+            L.drt_bind_buckets.argtypes = [C.c_void_p, C.c_uint32]
+            L.drt_read_bucket_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
+            L.drt_bucket_film_device_ptrs.argtypes = [C.c_void_p, C.c_uint32, vpp, vpp, vpp]
+            L.drt_resolve_buckets.argtypes = [C.c_void_p, C.c_uint32]
+            L.drt_read_bucket_resolve.argtypes = [C.c_void_p, f64p, f64p]
+            L.drt_bucket_resolve_device_ptrs.argtypes = [C.c_void_p, vpp, vpp]
+            L.drt_read_bucket_resolve_xyz.argtypes = [C.c_void_p, f64p]
+            L.drt_read_bucket_resolve_bgra.argtypes = [C.c_void_p, u8p]
+            L.drt_group_bind_buckets.argtypes = [C.c_void_p, C.c_uint32]
+            L.drt_group_read_bucket_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
+            L.drt_group_resolve_buckets.argtypes = [C.c_void_p, C.c_uint32]
+            L.drt_group_read_bucket_resolve.argtypes = [C.c_void_p, f64p, f64p]
         if hasattr(L, "drt_rebuild_hierarchy"):
             L.drt_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
@@ -809,6 +823,9 @@ HIP_SYMBOLS = ["drt_shade_instantiation",
                "drt_group_bind_depth_cuts", "drt_group_read_depth_film",
                "drt_bind_sensor", "drt_read_sensor_film", "drt_sensor_film_device_ptrs", "drt_read_sensor_bgra",
                "drt_group_bind_sensor", "drt_group_read_sensor_film",
+               "drt_bind_buckets", "drt_read_bucket_film", "drt_bucket_film_device_ptrs", "drt_resolve_buckets", "drt_read_bucket_resolve",
+               "drt_bucket_resolve_device_ptrs", "drt_read_bucket_resolve_xyz", "drt_read_bucket_resolve_bgra",
+               "drt_group_bind_buckets", "drt_group_read_bucket_film", "drt_group_resolve_buckets", "drt_group_read_bucket_resolve",
                "drt_render_sample_map", "drt_group_render_sample_map",
                "drt_live_window_of", "drt_live_window", "drt_selftest_division"]
 
@@ -846,6 +863,32 @@ def _sensor_matrix(matrix, n):
     if m.shape != (3, n):
         raise ValueError("read_sensor_bgra: a matrix of shape %s, need (3, %d): the bound channels to R, G, B" % (m.shape, n))
     return m
+
+
+MAX_BUCKETS = 8  # DRT_MAX_BUCKETS
+
+
+def _u32(value, what):
+    """an unsigned 32-bit argument: what ctypes would wrap around silently is refused here; the range proper is the library's to refuse"""
+    v = int(value)
+    if v < 0 or v > 0xFFFFFFFF:
+        raise ValueError("%s = %d: an unsigned 32-bit number" % (what, v))
+    return v
+
+
+def bucket_pair(means):
+    """The half-buffer pair dual-buffer denoisers take, from bucket means [n][...] (n >= 2): the plain mean of the even buckets
+    (0, 2, ...) and of the odd ones (1, 3, ...), each summed in bucket order and divided by its count. Pure numpy."""
+    m = np.asarray(means, dtype=np.float64)
+    if m.ndim < 1 or m.shape[0] < 2:
+        raise ValueError("bucket_pair: means of shape %s, need [n][...] with n >= 2 buckets" % (m.shape,))
+    out = []
+    for half in (m[0::2], m[1::2]):
+        acc = half[0].copy()
+        for k in range(1, half.shape[0]):
+            acc = acc + half[k]
+        out.append(acc / float(half.shape[0]))
+    return out[0], out[1]
 
 
 def observer_curves(bundle):
@@ -995,6 +1038,61 @@ class Renderer:
         """read_bgra of cut film `cut`"""
         out = np.empty((self.n_pixels, 4), dtype=np.uint8)
         _check(self.L.drt_read_depth_bgra(self.ctx, int(cut), int(which), _ptr(out, C.c_uint8)), "drt_read_depth_bgra")
+        return out
+
+    def bind_buckets(self, n):
+        """drt_bind_buckets: n films (at most MAX_BUCKETS) beside the main film, sample m in film m % n as its sample m // n, on a film
+        that holds no samples; 0 or None unbinds"""
+        n = _u32(0 if n is None else n, "bind_buckets: n")
+        _check(self.L.drt_bind_buckets(self.ctx, n), "drt_bind_buckets")
+        self.n_buckets = n
+
+    def read_bucket_film(self, b):
+        """(pixels [P][S+1], means [P][S], variances [P][S]) of bucket b's film"""
+        b = _u32(b, "read_bucket_film: b")
+        if not getattr(self, "n_buckets", 0) or b >= self.n_buckets:
+            _check(self.L.drt_read_bucket_film(self.ctx, b, None, None, None), "drt_read_bucket_film")  # (says which, touches nothing)
+        S, n = self.S, self.n_pixels
+        px, av, va = np.empty((n, S + 1)), np.empty((n, S)), np.empty((n, S))
+        _check(self.L.drt_read_bucket_film(self.ctx, b, _ptr(px, C.c_double), _ptr(av, C.c_double), _ptr(va, C.c_double)), "drt_read_bucket_film")
+        return px, av, va
+
+    def bucket_film_device_ptrs(self, b):
+        a, bb, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self.L.drt_bucket_film_device_ptrs(self.ctx, _u32(b, "bucket_film_device_ptrs: b"), C.byref(a), C.byref(bb), C.byref(c)),
+               "drt_bucket_film_device_ptrs")
+        return a.value, bb.value, c.value
+
+    def resolve_buckets(self, trim=None):
+        """drt_resolve_buckets: the trimmed mean of the sorted bucket means and the squared standard error across buckets, on the device.
+        trim None: the median's, (n - 1) // 2"""
+        n = getattr(self, "n_buckets", 0)
+        t = max(n - 1, 0) // 2 if trim is None else _u32(trim, "resolve_buckets: trim")
+        _check(self.L.drt_resolve_buckets(self.ctx, t), "drt_resolve_buckets")
+
+    def read_bucket_resolve(self):
+        """(estimate [P][S], error [P][S]) of the last resolve_buckets"""
+        _check(self.L.drt_read_bucket_resolve(self.ctx, None, None), "drt_read_bucket_resolve")  # (refused before anything is allocated)
+        S, n = self.S, self.n_pixels
+        est, err = np.empty((n, S)), np.empty((n, S))
+        _check(self.L.drt_read_bucket_resolve(self.ctx, _ptr(est, C.c_double), _ptr(err, C.c_double)), "drt_read_bucket_resolve")
+        return est, err
+
+    def bucket_resolve_device_ptrs(self):
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(self.L.drt_bucket_resolve_device_ptrs(self.ctx, C.byref(a), C.byref(b)), "drt_bucket_resolve_device_ptrs")
+        return a.value, b.value
+
+    def read_bucket_resolve_xyz(self):
+        """[P][3]: drt_read_xyz's conversion of the estimate"""
+        out = np.empty((self.n_pixels, 3))
+        _check(self.L.drt_read_bucket_resolve_xyz(self.ctx, _ptr(out, C.c_double)), "drt_read_bucket_resolve_xyz")
+        return out
+
+    def read_bucket_resolve_bgra(self):
+        """BMP pixel bytes [P][4] = B, G, R, 255 of the estimate, as read_bgra of the means"""
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_bucket_resolve_bgra(self.ctx, _ptr(out, C.c_uint8)), "drt_read_bucket_resolve_bgra")
         return out
 
     def bind_sensor(self, curves):
@@ -1459,6 +1557,37 @@ class Group:
         _check(self.L.drt_group_read_depth_film(self.g, int(cut), px.ctypes.data_as(f64p), av.ctypes.data_as(f64p), va.ctypes.data_as(f64p)),
                "drt_group_read_depth_film")
         return px, av, va
+
+    def bind_buckets(self, n):
+        """drt_group_bind_buckets: as Renderer.bind_buckets, every context checked and every film allocated before any is changed"""
+        n = _u32(0 if n is None else n, "bind_buckets: n")
+        _check(self.L.drt_group_bind_buckets(self.g, n), "drt_group_bind_buckets")
+        self.n_buckets = n
+
+    def read_bucket_film(self, b):
+        """drt_group_read_bucket_film: bucket b's film of the whole tile, in image order"""
+        b = _u32(b, "read_bucket_film: b")
+        if not getattr(self, "n_buckets", 0) or b >= self.n_buckets:
+            _check(self.L.drt_group_read_bucket_film(self.g, b, None, None, None), "drt_group_read_bucket_film")
+        px, av, va = np.empty((self.n_pixels, self.S + 1)), np.empty((self.n_pixels, self.S)), np.empty((self.n_pixels, self.S))
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.drt_group_read_bucket_film(self.g, b, px.ctypes.data_as(f64p), av.ctypes.data_as(f64p), va.ctypes.data_as(f64p)),
+               "drt_group_read_bucket_film")
+        return px, av, va
+
+    def resolve_buckets(self, trim=None):
+        """drt_group_resolve_buckets: as Renderer.resolve_buckets on every device, every context checked before any resolves"""
+        n = getattr(self, "n_buckets", 0)
+        t = max(n - 1, 0) // 2 if trim is None else _u32(trim, "resolve_buckets: trim")
+        _check(self.L.drt_group_resolve_buckets(self.g, t), "drt_group_resolve_buckets")
+
+    def read_bucket_resolve(self):
+        """drt_group_read_bucket_resolve: (estimate, error) of the whole tile, in image order"""
+        _check(self.L.drt_group_read_bucket_resolve(self.g, None, None), "drt_group_read_bucket_resolve")
+        est, err = np.empty((self.n_pixels, self.S)), np.empty((self.n_pixels, self.S))
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.drt_group_read_bucket_resolve(self.g, est.ctypes.data_as(f64p), err.ctypes.data_as(f64p)), "drt_group_read_bucket_resolve")
+        return est, err
 
     def bind_sensor(self, curves):
         """drt_group_bind_sensor: as Renderer.bind_sensor, every context checked and every film allocated before any is changed"""

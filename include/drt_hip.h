@@ -188,7 +188,7 @@ typedef struct drt_stats
     uint64_t shadow_scans;      /* points_mutually_visible calls             */
     uint64_t rng_draws;
     double   trace_ms;          /* path-geometry kernel, HIP-event time      */
-    double   shade_ms;          /* spectral shade + film kernel; while depth cuts or a sensor are bound (drt_bind_depth_cuts, drt_bind_sensor), that pass too */
+    double   shade_ms;          /* spectral shade + film kernel; while depth cuts, a sensor or buckets are bound (drt_bind_depth_cuts, drt_bind_sensor, drt_bind_buckets), that pass too */
     double   total_ms;
     /* the pool of vertex records (four vertices per block): its size, the most a launch has used, and how many launches had to be
      * rendered again in worst-case-sized pieces because the pool ran out (0 unless the tile's paths grew after the context measured them) */
@@ -690,6 +690,60 @@ int drt_group_bind_sensor(drt_group *g, const double *curves, uint32_t n);
 int drt_group_read_sensor_film(drt_group *g, double *pixels, double *avgs, double *vars);
 
 /*
+ * Bucket films: the render's samples dealt out in turn to n films ("half buffers" at n = 2, the buckets of a median of means
+ * otherwise), and a robust resolve over the n running means. The scatter of the n means estimates the error of their mean without
+ * the film's own variance, and still does after a filter has been applied to each; the trimmed mean of the sorted means leaves
+ * fireflies out. DESIGN.md section 5m.
+ *
+ * The rule, `+ - * /` and `<` only, nothing contracted. Sample number m (absolute: first_sample + s) belongs to bucket b = m % n as
+ * that bucket's sample number j = m / n. Its contribution c[0..S) -- what the film update of src/daily_ray_trace.c:732 takes,
+ * vignette included -- goes through the film update (:732-743) of bucket b's film only, with the divisor (double)(j + 1); that
+ * film's filter column += 1.0. The samples of a bucket are applied in ascending m, also across several drt_render calls. With n = 1
+ * the bucket film is the main film, bit for bit.
+ *
+ * The resolve, for trim count t, 0 <= 2 t < n, n >= 2, per pixel and wavelength over the buckets' running means x_0 .. x_{n-1}:
+ *   1. mu = x_0, then mu = mu + x_b for b = 1 .. n-1 in order, then mu = mu / (double)n;
+ *   2. d_b = x_b - mu; q = d_0 * d_0, then q = q + d_b * d_b in order; error = q / (double)(n * (n - 1)): the squared standard error
+ *      of the mean across buckets, whatever t is;
+ *   3. y = x sorted by odd-even transposition: for round r = 0 .. n-1, for i = r % 2, r % 2 + 2, ... < n - 1: when y[i+1] < y[i] the
+ *      two change places. A comparison with a NaN is false, and so is -0 < +0: the network fixes where those end up;
+ *   4. e = y[t], then e = e + y[i] for i = t+1 .. n-1-t in order; estimate = e / (double)(n - 2 t). t = 0: the mean in sorted order;
+ *      t = (n-1)/2, n odd: the median; t = n/2 - 1, n even: the mean of the two middle values.
+ *
+ * Every bucket film has the main film's three buffers and layout: [tile_h*tile_w][S+1] sum + filter, [..][S] mean, [..][S] variance,
+ * owned by the context, zero-filled at the bind and by drt_reset_film, released at the unbind and by drt_destroy. From the bind on
+ * every sample drt_render adds to the film is added to its bucket's film too; a launch whose record pool ran out leaves them
+ * untouched and is rendered again with the rest.
+ */
+#define DRT_MAX_BUCKETS 8
+/* Bind the context to n buckets (n == 0: unbind, the films are released). Refused, with the reason in drt_last_error() and the
+ * context as it was: n > DRT_MAX_BUCKETS, DRT_MODE_XYZ, a film that holds samples, an adaptive render or a sample map (drt_reset_film
+ * first), bound depth cuts or a bound sensor, an allocation failure. While buckets are bound drt_bind_depth_cuts, drt_bind_sensor,
+ * drt_render_adaptive, drt_render_adaptive_continue and drt_render_sample_map are refused. */
+int drt_bind_buckets(drt_context *ctx, uint32_t n);
+/* Copy bucket b's film (0 .. n-1) to host buffers (any may be NULL). Synchronises. */
+int drt_read_bucket_film(drt_context *ctx, uint32_t b, double *pixels, double *avgs, double *vars);
+/* Device pointers of bucket b's buffers; valid until the next bind, unbind or drt_destroy. Synchronises. */
+int drt_bucket_film_device_ptrs(drt_context *ctx, uint32_t b, void **d_pixels, void **d_avgs, void **d_vars);
+/* Run the resolve on the context's stream into two context-owned [P][S] buffers. Refused: nothing bound, n < 2, 2 * trim >= n, a
+ * film of fewer than n samples (some bucket would be empty). */
+int drt_resolve_buckets(drt_context *ctx, uint32_t trim);
+/* The last resolve's results (either may be NULL), and their device addresses. Refused before any resolve, and after a render or a
+ * reset that came later than the last resolve. */
+int drt_read_bucket_resolve(drt_context *ctx, double *estimate /* [P][S] */, double *error /* [P][S] */);
+int drt_bucket_resolve_device_ptrs(drt_context *ctx, void **d_estimate, void **d_error);
+/* drt_read_xyz and drt_read_bgra's kernels with the estimate in the means' place (the picture is that of which = 1). */
+int drt_read_bucket_resolve_xyz(drt_context *ctx, double *xyz);
+int drt_read_bucket_resolve_bgra(drt_context *ctx, uint8_t *bgra);
+/* Every context is checked, and every device's films allocated, before any context is changed. */
+int drt_group_bind_buckets(drt_group *g, uint32_t n);
+/* Bucket b's film of the whole tile, in image order, as drt_group_read_depth_film. */
+int drt_group_read_bucket_film(drt_group *g, uint32_t b, double *pixels, double *avgs, double *vars);
+/* Every context is checked before any resolves; the results of the whole tile, in image order. */
+int drt_group_resolve_buckets(drt_group *g, uint32_t trim);
+int drt_group_read_bucket_resolve(drt_group *g, double *estimate, double *error);
+
+/*
  * Scene updates: move the camera and the surfaces of a live context, where the only way used to be drt_destroy + drt_create (the
  * pool freed and allocated again, the pool measurement rendered again, the hierarchy built again). DESIGN.md section 5g.
  *
@@ -931,7 +985,7 @@ int drt_read_hierarchy(drt_context *ctx, void *nodes, uint32_t n_nodes, uint32_t
  * per kernel pair, what its samples -- all worth +0 -- leave on the film, and its paths are counted in drt_stats as the reference
  * counts them (a path, one closest-hit scan, the pixel's draws). Films, statistics and draw counts are bit for bit what they are
  * without it; DRT_NO_LIVE_WINDOW=1, read by drt_create, turns it off. Not used with DRT_FLAG_RECORD_HITS, pixel lists (adaptive
- * rounds, sample maps), a bound ray table, bound depth cuts or a bound sensor.
+ * rounds, sample maps), a bound ray table, bound depth cuts, a bound sensor or bound buckets.
  */
 /* Host only, like drt_bvh_stats: the rule on the scene and camera as given. */
 int drt_live_window_of(const drt_scene *scene, const drt_camera *camera, const drt_params *params, uint32_t out[4]);
