@@ -17,6 +17,7 @@
 #include "drt_depth_kernels.h"
 #include "drt_sensor_kernels.h"
 #include "drt_bucket_kernels.h"
+#include "drt_lobe_kernels.h"
 #include "drt_window_kernels.h"
 #include "drt_window_rule.h"
 #include "drt_pair_rule.h"
@@ -275,6 +276,10 @@ struct drt_context
     DevBuf<double> d_bk_estimate, d_bk_error, d_bk_packed;
     bool      bk_valid = false;
     uint64_t  bk_gen = 0;                  /* film_gen at the last drt_resolve_buckets */
+    /* lobe films (drt_bind_lobes; drt_lobe_kernels.h): one film per lobe film, laid out as the main film, and the map that routes them */
+    uint32_t  n_lobes = 0;
+    drt_lobe_map lobe_map{};
+    struct LobeFilms { DevBuf<double> pixels[DRT_MAX_LOBE_FILMS], avgs[DRT_MAX_LOBE_FILMS], vars[DRT_MAX_LOBE_FILMS]; int grid_cap = 1; } lobes;
     /* sample maps (drt_render_sample_map; drt_sample_map_kernels.h): the call's remainders, host targets on their way to the adopt
      * kernel, the report and its pinned copy -- a set of its own, whole or absent like the adaptive one it is used with */
     DevBuf<uint32_t> d_sm_rem, d_sm_targets, d_sm_report;
@@ -1093,6 +1098,66 @@ static int launch_buckets(drt_context *ctx, const ShadeParams &sp, uint64_t pix0
     return 0;
 }
 
+/* The lobe pass of one kernel pair (lobes bound): drt_lobe_kernel over the pair's pixels and samples, behind its shade kernel. Its
+ * queue is the cut pass's word, +3 of the pair's work words: of cuts, a sensor, buckets and lobes only one is ever bound. */
+template <int NF>
+static const void *lobe_kernel(bool lds) { return lds ? (const void *)drt_lobe_kernel<NF, true> : (const void *)drt_lobe_kernel<NF, false>; }
+static const void *lobe_kernel(uint32_t n, bool lds)
+{
+    switch (n)
+    {
+        case 1: return lobe_kernel<1>(lds);
+        case 2: return lobe_kernel<2>(lds);
+        case 3: return lobe_kernel<3>(lds);
+        case 4: return lobe_kernel<4>(lds);
+        case 5: return lobe_kernel<5>(lds);
+        case 6: return lobe_kernel<6>(lds);
+        case 7: return lobe_kernel<7>(lds);
+        default: return lobe_kernel<8>(lds);
+    }
+}
+
+/* a map row as the kernel takes it: byte f is the film of function f */
+static uint64_t lobe_row(const uint8_t *row)
+{
+    uint64_t w = 0;
+    for (uint32_t f = 0; f < (uint32_t)DRT_NUM_BDSFS; f += 1) w |= (uint64_t)row[f] << (8 * f);
+    return w;
+}
+
+static int launch_lobes(drt_context *ctx, const ShadeParams &sp, uint64_t pix0)
+{
+    const size_t S = ctx->dsc.S;
+    LobeParams lp{};
+    lp.n_pix = sp.n_pix;
+    lp.n_samples = sp.n_samples;
+    lp.first_sample = sp.first_sample;
+    lp.vertex_words = sp.vertex_words;
+    lp.block_words = sp.block_words;
+    lp.n_lights = sp.n_lights;
+    lp.batch = sp.batch;
+    lp.overflow = sp.overflow;
+    lp.n_sets = (uint32_t)((S + 63) / 64);
+    lp.max_depth = ctx->params.max_depth;
+    lp.emission = ctx->lobe_map.emission;
+    lp.direct = lobe_row(ctx->lobe_map.direct);
+    lp.indirect = lobe_row(ctx->lobe_map.indirect);
+    if (sp.n_pix * lp.n_sets >= 0xFFFFFFFFull) return fail(-1, "tile too large for the lobe work queue");
+    lp.n_items = (uint32_t)(sp.n_pix * lp.n_sets);
+    for (uint32_t c = 0; c < ctx->n_lobes; c += 1)
+    {
+        lp.pixels[c] = ctx->lobes.pixels[c] + pix0 * (S + 1);
+        lp.avgs[c] = ctx->lobes.avgs[c] + pix0 * S;
+        lp.vars[c] = ctx->lobes.vars[c] + pix0 * S;
+    }
+    const uint64_t *records = ctx->d_records, *headers = ctx->d_headers;
+    unsigned long long *queue = ctx->d_counters + DRT_NUM_COUNTERS + 3;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)lp.n_items + LOBE_WAVES - 1) / LOBE_WAVES, (uint64_t)ctx->lobes.grid_cap);
+    void *args[] = {&ctx->dsc, &lp, &records, &headers, &queue};
+    HIP_TRY(hipLaunchKernel(lobe_kernel(ctx->n_lobes, ctx->spds_in_lds), dim3(grid), dim3(LOBE_BLOCK), args, depth_lds_bytes(ctx), ctx->stream));
+    return 0;
+}
+
 static int launch_sensor(drt_context *ctx, const ShadeParams &sp, uint64_t pix0)
 {
     const size_t S = ctx->dsc.S, n = ctx->n_sensor;
@@ -1264,7 +1329,7 @@ static void window_refresh(drt_context *ctx)
 static bool window_in_use(drt_context *ctx)
 {
     window_refresh(ctx);
-    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0 && ctx->n_sensor == 0 && ctx->n_buckets == 0;
+    return ctx->win_part && !(ctx->params.flags & DRT_FLAG_RECORD_HITS) && !ctx->rays_bound && ctx->n_cuts == 0 && ctx->n_sensor == 0 && ctx->n_buckets == 0 && ctx->n_lobes == 0;
 }
 
 static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camera *camera, const drt_params *params)
@@ -1871,6 +1936,7 @@ static int enqueue_pair(drt_context *ctx, const PairSpan &span)
     if (ctx->n_cuts && (rc = launch_depth_cuts(ctx, sp, g.pix0))) return rc;
     if (ctx->n_sensor && (rc = launch_sensor(ctx, sp, g.pix0))) return rc;
     if (ctx->n_buckets && (rc = launch_buckets(ctx, sp, g.pix0))) return rc;
+    if (ctx->n_lobes && (rc = launch_lobes(ctx, sp, g.pix0))) return rc;
     if (g.windowed && (rc = enqueue_window_fill(ctx, span.first_sample, span.n_samples, g.t_row0, g.t_rows))) return rc;
     const uint64_t seq = ctx->next_seq++;
     hipLaunchKernelGGL(drt_mark_pair_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_counters, (unsigned long long)seq);
@@ -2092,6 +2158,12 @@ extern "C" int drt_reset_film(drt_context *ctx)
         HIP_TRY(hipMemsetAsync(ctx->buckets.vars[b], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
     }
     ctx->bk_samples = 0;
+    for (uint32_t c = 0; c < ctx->n_lobes; c += 1)
+    {
+        HIP_TRY(hipMemsetAsync(ctx->lobes.pixels[c], 0, (size_t)ctx->n_pix * (S + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->lobes.avgs[c], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->lobes.vars[c], 0, (size_t)ctx->n_pix * S * 8, ctx->stream));
+    }
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, DRT_COUNTER_WORDS * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->film_used = ctx->adaptive_done = false;
@@ -2277,6 +2349,7 @@ static int adaptive_check(drt_context *ctx, const drt_adaptive *a, bool held = f
     if (ctx->n_cuts) return fail(-4, "adaptive sampling with depth cuts bound is not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
     if (ctx->n_sensor) return fail(-4, "adaptive sampling with a sensor bound is not supported: drt_bind_sensor(ctx, NULL, 0) first");
     if (ctx->n_buckets) return fail(-4, "adaptive sampling with buckets bound is not supported: drt_bind_buckets(ctx, 0) first");
+    if (ctx->n_lobes) return fail(-4, "adaptive sampling with lobes bound is not supported: drt_bind_lobes(ctx, 0, NULL) first");
     if (ctx->xyz_mode) return fail(-4, "adaptive sampling needs the spectral film (DRT_MODE_XYZ keeps no variance)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "adaptive sampling does not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (!held && ctx->adaptive_done) return fail(-7, "the film holds an adaptive render: drt_reset_film first");
@@ -3089,6 +3162,7 @@ static int map_check(const drt_context *ctx, const drt_sample_map *m, bool group
     if (ctx->n_cuts) return fail(-4, "sample maps with depth cuts bound are not supported: drt_bind_depth_cuts(ctx, NULL, 0) first");
     if (ctx->n_sensor) return fail(-4, "sample maps with a sensor bound are not supported: drt_bind_sensor(ctx, NULL, 0) first");
     if (ctx->n_buckets) return fail(-4, "sample maps with buckets bound are not supported: drt_bind_buckets(ctx, 0) first");
+    if (ctx->n_lobes) return fail(-4, "sample maps with lobes bound are not supported: drt_bind_lobes(ctx, 0, NULL) first");
     if (ctx->xyz_mode) return fail(-4, "sample maps need the spectral film (the DRT_MODE_XYZ film keeps no filter sum per pixel)");
     if (ctx->params.flags & DRT_FLAG_RECORD_HITS) return fail(-4, "sample maps do not record hit indices (DRT_FLAG_RECORD_HITS)");
     if (ctx->n_pix > 0xFFFFFFFFull) return fail(-1, "sample maps list pixels in 32 bits: the tile has %llu", (unsigned long long)ctx->n_pix);
@@ -3412,6 +3486,7 @@ static int depth_cuts_check(const drt_context *ctx, const uint32_t *depths, uint
     }
     if (ctx->n_sensor) return fail(-4, "%s: a sensor is bound, and the two passes share a work queue: drt_bind_sensor(ctx, NULL, 0) first", name);
     if (ctx->n_buckets) return fail(-4, "%s: buckets are bound, and the two passes share a work queue: drt_bind_buckets(ctx, 0) first", name);
+    if (ctx->n_lobes) return fail(-4, "%s: lobes are bound, and the two passes share a work queue: drt_bind_lobes(ctx, 0, NULL) first", name);
     if (ctx->xyz_mode) return fail(-4, "%s: the cut films are spectral films: DRT_MODE_XYZ keeps none", name);
     if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render: drt_reset_film first", name);
     if (ctx->film_used) return fail(-7, "%s: the film already holds samples the cut films would lack: drt_reset_film first", name);
@@ -3592,6 +3667,7 @@ static int sensor_check(const drt_context *ctx, const double *curves, uint32_t n
     if (ctx->xyz_mode) return fail(-4, "%s: the sensor film is made from the spectral film's samples: DRT_MODE_XYZ keeps none", name);
     if (ctx->n_cuts) return fail(-4, "%s: depth cuts are bound, and the two passes share a work queue: drt_bind_depth_cuts(ctx, NULL, 0) first", name);
     if (ctx->n_buckets) return fail(-4, "%s: buckets are bound, and the two passes share a work queue: drt_bind_buckets(ctx, 0) first", name);
+    if (ctx->n_lobes) return fail(-4, "%s: lobes are bound, and the two passes share a work queue: drt_bind_lobes(ctx, 0, NULL) first", name);
     if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render or a sample map: drt_reset_film first", name);
     if (ctx->film_used) return fail(-7, "%s: the film already holds samples the sensor film would lack: drt_reset_film first", name);
     return 0;
@@ -3755,6 +3831,7 @@ static int buckets_check(const drt_context *ctx, uint32_t n, const char *name)
     if (ctx->xyz_mode) return fail(-4, "%s: the bucket films are spectral films: DRT_MODE_XYZ keeps none", name);
     if (ctx->n_cuts) return fail(-4, "%s: depth cuts are bound, and the two passes share a work queue: drt_bind_depth_cuts(ctx, NULL, 0) first", name);
     if (ctx->n_sensor) return fail(-4, "%s: a sensor is bound, and the two passes share a work queue: drt_bind_sensor(ctx, NULL, 0) first", name);
+    if (ctx->n_lobes) return fail(-4, "%s: lobes are bound, and the two passes share a work queue: drt_bind_lobes(ctx, 0, NULL) first", name);
     if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render or a sample map: drt_reset_film first", name);
     if (ctx->film_used) return fail(-7, "%s: the film already holds samples the bucket films would lack: drt_reset_film first", name);
     return 0;
@@ -4050,6 +4127,184 @@ extern "C" int drt_group_read_bucket_resolve(drt_group *g, double *estimate, dou
     const size_t row_bytes = (size_t)g->tile_w * (size_t)g->S * 8;
     if (estimate && (rc = group_gather_bucket_rows(g, estimate, row_bytes, [](drt_context *c) -> const double * { return c->d_bk_estimate.get(); }))) return rc;
     if (error && (rc = group_gather_bucket_rows(g, error, row_bytes, [](drt_context *c) -> const double * { return c->d_bk_error.get(); }))) return rc;
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* Lobe films (the kernel in drt_lobe_kernels.h)                              */
+
+/* what a bind is refused for, before any device call; n == 0 (the unbind) passes on any context */
+static int lobes_check(const drt_context *ctx, uint32_t n, const drt_lobe_map *map, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (n == 0) return 0;
+    if (n > DRT_MAX_LOBE_FILMS) return fail(-1, "%s: %u films, at most %u", name, n, (unsigned)DRT_MAX_LOBE_FILMS);
+    if (!map) return fail(-1, "%s: null map", name);
+    if (map->emission >= n && map->emission != DRT_LOBE_NONE) return fail(-1, "%s: the map sends emission to film %u of %u", name, (unsigned)map->emission, n);
+    for (uint32_t f = 0; f < (uint32_t)DRT_NUM_BDSFS; f += 1)
+    {
+        if (map->direct[f] >= n && map->direct[f] != DRT_LOBE_NONE)
+            return fail(-1, "%s: the map sends the direct light of function %u to film %u of %u", name, f, (unsigned)map->direct[f], n);
+        if (map->indirect[f] >= n && map->indirect[f] != DRT_LOBE_NONE)
+            return fail(-1, "%s: the map sends the indirect light of function %u to film %u of %u", name, f, (unsigned)map->indirect[f], n);
+    }
+    if (ctx->xyz_mode) return fail(-4, "%s: the lobe films are spectral films: DRT_MODE_XYZ keeps none", name);
+    if (ctx->n_cuts) return fail(-4, "%s: depth cuts are bound, and the two passes share a work queue: drt_bind_depth_cuts(ctx, NULL, 0) first", name);
+    if (ctx->n_sensor) return fail(-4, "%s: a sensor is bound, and the two passes share a work queue: drt_bind_sensor(ctx, NULL, 0) first", name);
+    if (ctx->n_buckets) return fail(-4, "%s: buckets are bound, and the two passes share a work queue: drt_bind_buckets(ctx, 0) first", name);
+    if (ctx->adaptive_done) return fail(-7, "%s: the film holds an adaptive render or a sample map: drt_reset_film first", name);
+    if (ctx->film_used) return fail(-7, "%s: the film already holds samples the lobe films would lack: drt_reset_film first", name);
+    return 0;
+}
+
+/* n zero-filled lobe films for ctx, into `out`; the context is not touched */
+static int lobes_alloc(drt_context *ctx, uint32_t n, drt_context::LobeFilms *out)
+{
+    if (n == 0) return 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const size_t S = ctx->dsc.S, n_pix = ctx->n_pix;
+    for (uint32_t c = 0; c < n; c += 1)
+    {
+        hipError_t e = out->pixels[c].need(n_pix * (S + 1));
+        if (e == hipSuccess) e = out->avgs[c].need(n_pix * S);
+        if (e == hipSuccess) e = out->vars[c].need(n_pix * S);
+        if (e != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(-3, "drt_bind_lobes: no memory for lobe film %u of %u (%zu bytes each): %s", c, n, n_pix * (3 * S + 1) * 8, hipGetErrorString(e));
+        }
+        HIP_TRY(hipMemsetAsync(out->pixels[c], 0, n_pix * (S + 1) * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(out->avgs[c], 0, n_pix * S * 8, ctx->stream));
+        HIP_TRY(hipMemsetAsync(out->vars[c], 0, n_pix * S * 8, ctx->stream));
+    }
+    int per_cu = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lobe_kernel(n, ctx->spds_in_lds), LOBE_BLOCK, depth_lds_bytes(ctx)));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, ctx->device));
+    out->grid_cap = std::max(1, prop.multiProcessorCount * std::max(1, per_cu));
+    return 0;
+}
+
+/* the stream idle, then the new films and the map in place of the old (n == 0: none) */
+static int lobes_commit(drt_context *ctx, uint32_t n, const drt_lobe_map *map, drt_context::LobeFilms *films)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->lobes = std::move(*films);
+    ctx->n_lobes = n;
+    ctx->lobe_map = n ? *map : drt_lobe_map{};
+    return 0;
+}
+
+extern "C" int drt_bind_lobes(drt_context *ctx, uint32_t n, const drt_lobe_map *map)
+{
+    g_last_error.clear();
+    int rc = lobes_check(ctx, n, map, "drt_bind_lobes");
+    if (rc) return rc;
+    drt_context::LobeFilms films;
+    if ((rc = lobes_alloc(ctx, n, &films))) return rc;
+    return lobes_commit(ctx, n, map, &films);
+}
+
+static int lobe_index(const drt_context *ctx, uint32_t c, const char *name)
+{
+    if (!ctx) return fail(-1, "%s: null context", name);
+    if (ctx->n_lobes == 0) return fail(-4, "%s: no lobes are bound (drt_bind_lobes)", name);
+    if (c >= ctx->n_lobes) return fail(-1, "%s: film %u of %u", name, c, ctx->n_lobes);
+    return 0;
+}
+
+extern "C" int drt_lobe_film_device_ptrs(drt_context *ctx, uint32_t c, void **d_pixels, void **d_avgs, void **d_vars)
+{
+    int rc = lobe_index(ctx, c, "drt_lobe_film_device_ptrs");
+    if (rc) return rc;
+    if ((rc = drt_synchronize(ctx))) return rc; /* (a launch that ran out of records is rendered again before anyone reads the films) */
+    if (d_pixels) *d_pixels = ctx->lobes.pixels[c].get();
+    if (d_avgs) *d_avgs = ctx->lobes.avgs[c].get();
+    if (d_vars) *d_vars = ctx->lobes.vars[c].get();
+    return 0;
+}
+
+extern "C" int drt_read_lobe_film(drt_context *ctx, uint32_t c, double *pixels, double *avgs, double *vars)
+{
+    int rc = lobe_index(ctx, c, "drt_read_lobe_film");
+    if (rc) return rc;
+    if ((rc = drt_synchronize(ctx))) return rc;
+    const size_t S = ctx->dsc.S;
+    if (pixels) HIP_TRY(hipMemcpy(pixels, ctx->lobes.pixels[c], (size_t)ctx->n_pix * (S + 1) * 8, hipMemcpyDeviceToHost));
+    if (avgs) HIP_TRY(hipMemcpy(avgs, ctx->lobes.avgs[c], (size_t)ctx->n_pix * S * 8, hipMemcpyDeviceToHost));
+    if (vars) HIP_TRY(hipMemcpy(vars, ctx->lobes.vars[c], (size_t)ctx->n_pix * S * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_lobe_xyz(drt_context *ctx, uint32_t c, double *xyz)
+{
+    int rc = lobe_index(ctx, c, "drt_read_lobe_xyz");
+    if (rc) return rc;
+    if (!xyz) return fail(-1, "drt_read_lobe_xyz: null argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = drt_synchronize(ctx))) return rc; /* the complete films first (see drt_read_xyz) */
+    HIP_TRY(ctx->d_xyz.need((size_t)ctx->n_pix * 3));
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_film_xyz_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z,
+                       ctx->interval, ctx->n_pix, ctx->lobes.pixels[c].get(), ctx->d_xyz);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(xyz, ctx->d_xyz, (size_t)ctx->n_pix * 3 * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_read_lobe_bgra(drt_context *ctx, uint32_t c, int which, uint8_t *bgra)
+{
+    int rc = lobe_index(ctx, c, "drt_read_lobe_bgra");
+    if (rc) return rc;
+    if (!bgra) return fail(-1, "drt_read_lobe_bgra: null argument");
+    if (which < 0 || which > 2) return fail(-1, "which = %d: 0 sum, 1 mean, 2 variance", which);
+    HIP_TRY(hipSetDevice(ctx->device));
+    if ((rc = drt_synchronize(ctx))) return rc;
+    HIP_TRY(ctx->d_bgra.need((size_t)ctx->n_pix * 4));
+    const double *film = which == 0 ? ctx->lobes.pixels[c].get() : which == 1 ? ctx->lobes.avgs[c].get() : ctx->lobes.vars[c].get();
+    const uint32_t grid = (uint32_t)((ctx->n_pix + 255) / 256);
+    hipLaunchKernelGGL(drt_film_bgra_kernel, dim3(grid), dim3(256), 0, ctx->stream, ctx->dsc, ctx->cmf_rw, ctx->cmf_x, ctx->cmf_y, ctx->cmf_z,
+                       ctx->interval, ctx->n_pix, film, which, ctx->d_bgra);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(bgra, ctx->d_bgra, (size_t)ctx->n_pix * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int drt_group_bind_lobes(drt_group *g, uint32_t n, const drt_lobe_map *map)
+{
+    g_last_error.clear();
+    if (!g) return fail(-1, "drt_group_bind_lobes: null group");
+    int rc = 0;
+    for (drt_context *c : g->ctx)
+        if (c && (rc = lobes_check(c, n, map, "drt_group_bind_lobes"))) return rc;
+    std::vector<drt_context::LobeFilms> films(g->ctx.size());
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = lobes_alloc(g->ctx[k], n, &films[k]))) return rc; /* (what was allocated so far is released with `films`) */
+    for (size_t k = 0; k < g->ctx.size(); k += 1)
+        if (g->ctx[k] && (rc = lobes_commit(g->ctx[k], n, map, &films[k]))) return rc;
+    return 0;
+}
+
+extern "C" int drt_group_read_lobe_film(drt_group *g, uint32_t c, double *pixels, double *avgs, double *vars)
+{
+    if (!g) return fail(-1, "drt_group_read_lobe_film: null group");
+    int rc = 0;
+    for (drt_context *x : g->ctx)
+        if (x && (rc = lobe_index(x, c, "drt_group_read_lobe_film"))) return rc;
+    if ((rc = drt_group_synchronize(g))) return rc;
+    double *host[3] = {pixels, avgs, vars};
+    for (int f = 0; f < 3; f += 1)
+    {
+        if (!host[f]) continue;
+        const size_t row_bytes = (size_t)g->tile_w * (f == 0 ? (size_t)g->S + 1 : (size_t)g->S) * 8;
+        rc = group_gather_bucket_rows(g, host[f], row_bytes, [&](drt_context *x) -> const double * {
+            return f == 0 ? x->lobes.pixels[c].get() : f == 1 ? x->lobes.avgs[c].get() : x->lobes.vars[c].get();
+        });
+        if (rc) return rc;
+    }
     return 0;
 }
 

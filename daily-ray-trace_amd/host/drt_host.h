@@ -81,7 +81,7 @@ typedef struct
  * read from the environment by render_image(): DRT_DEVICE, DRT_DEVICES, DRT_SEED, DRT_BATCH_SPP, DRT_CHECKPOINT_SPP, DRT_RESUME,
  * DRT_ADAPTIVE_ERROR, DRT_ADAPTIVE_MIN_SPP, DRT_ADAPTIVE_STEP, DRT_ADAPTIVE_FLOOR, DRT_ADAPTIVE_CHECKPOINT_ROUNDS, DRT_ADAPTIVE_RESUME,
  * DRT_DENOISE_K, DRT_DENOISE_RADIUS, DRT_DENOISE_PATCH, DRT_DENOISE_ALPHA, DRT_DENOISE_SPD, DRT_DENOISE_VAR_SPD, DRT_FEATURES*, DRT_MATTES, DRT_PICK,
- * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_REGIONS, DRT_SENSOR, DRT_BUCKETS. */
+ * DRT_PROJECTION, DRT_ORTHO_WIDTH, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_REGIONS, DRT_SENSOR, DRT_BUCKETS, DRT_LOBES. */
 #define DRT_HOST_MAX_PICKS 64
 #define DRT_HOST_MAX_LEVELS 64
 #define DRT_HOST_MAX_REGIONS 64
@@ -165,6 +165,13 @@ typedef struct
      * estimate <output_spd>.robust.bmp; every other output stays byte for byte what it is without it. Not combined with adaptive
      * sampling, checkpoints or resuming, DRT_TURNTABLE, DRT_LIGHT_LEVELS, DRT_DEPTH_CUTS, DRT_SENSOR or DRT_REGIONS. 0 buckets: off */
     uint32_t n_buckets, bucket_trim;
+    /* DRT_LOBES=standard|functions: lobe films (drt_group_bind_lobes) with that preset's map: per film k the three standard .spd outputs
+     * again as <output_spd>.lobe<k>.spd, <average_spd>.lobe<k>.spd and <variance_spd>.lobe<k>.spd, the picture of its mean
+     * <output_spd>.lobe<k>.bmp, and <output_spd>.lobes.txt, one line "<k> <name>" per film; every other output stays byte for byte what
+     * it is without it. Not combined with DRT_BUCKETS or anything DRT_BUCKETS is not combined with. 0 films: off */
+    uint32_t n_lobes;
+    drt_lobe_map lobe_map;
+    const char *const *lobe_names;
 } drt_host_options;
 #define DRT_HOST_PROJECTION_EQUIRECT 1u
 #define DRT_HOST_PROJECTION_ORTHO 2u

@@ -111,6 +111,16 @@ static int robust_path(char dst[64], const char *src, const char *ext)
     return snprintf(dst, 64, "%s.robust%s", src, ext) < 64 ? 0 : -1;
 }
 
+/* DRT_LOBES: "<src>.lobe<k><ext>" and "<src>.lobes.txt" into a config field; -1 when it does not fit */
+static int lobe_path(char dst[64], const char *src, u32 k, const char *ext)
+{
+    return snprintf(dst, 64, "%s.lobe%u%s", src, k, ext) < 64 ? 0 : -1;
+}
+static int lobes_txt_path(char dst[64], const char *src)
+{
+    return snprintf(dst, 64, "%s.lobes.txt", src) < 64 ? 0 : -1;
+}
+
 /* Frame k of DRT_LIGHT_LEVELS: `rows` gets the scene's rows [*first_row, *first_row + *count) -- from the first to the last row an emissive
  * material names as its emission -- with every such row times `level` (one multiplication per sample) and the rows between as they are.
  * No emissive material: *count = 0. */
@@ -409,6 +419,8 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
     if (!rc && n_sensor) rc = drt_group_bind_sensor(ctx, sensor_curves, n_sensor);
     /* DRT_BUCKETS: the bucket films, bound while the film is still without samples */
     if (!rc && opt && opt->n_buckets) rc = drt_group_bind_buckets(ctx, opt->n_buckets);
+    /* DRT_LOBES: the lobe films, bound while the film is still without samples */
+    if (!rc && opt && opt->n_lobes) rc = drt_group_bind_lobes(ctx, opt->n_lobes, &opt->lobe_map);
     if (!rc && done) rc = drt_group_write_film(ctx, dst_pixels, dst_avgs, dst_vars);
     if (!rc && opt && opt->adaptive && (opt->adaptive_checkpoint_rounds || opt->adaptive_resume))
     {
@@ -650,6 +662,49 @@ int render_image_ex(config_arguments *config, const drt_host_options *opt, drt_s
         free(bk_vars);
         free(bk_avgs);
         free(bk_pixels);
+    }
+    /* DRT_LOBES: every lobe film through the standard writer (the variance normalised as the standard output's is) under the outputs'
+     * names with .lobe<k> behind them, the picture of its mean by the .spd -> .bmp post-process, and the list of the films' names */
+    if (!rc && opt && opt->n_lobes)
+    {
+        const u32 n_lobes = opt->n_lobes;
+        f64 *lb_pixels = (f64 *)malloc(num_pixels * (S + 1) * sizeof(f64));
+        f64 *lb_avgs = (f64 *)malloc(num_pixels * S * sizeof(f64)), *lb_vars = (f64 *)malloc(num_pixels * S * sizeof(f64));
+        f64 *cmf = (f64 *)malloc((size_t)4 * S * sizeof(f64));
+        if (!lb_pixels || !lb_avgs || !lb_vars || !cmf) rc = -3;
+        if (!rc)
+        {
+            const u32 rows[4] = { scene->cmf_rw, scene->cmf_x, scene->cmf_y, scene->cmf_z };
+            for (int r = 0; r < 4; r += 1) memcpy(cmf + (size_t)r * S, scene->spds + (size_t)rows[r] * S, (size_t)S * sizeof(f64));
+        }
+        for (u32 k = 0; !rc && !cut_bad && k < n_lobes; k += 1)
+        {
+            config_arguments cc = *config;
+            char bmp[64];
+            if ((rc = drt_group_read_lobe_film(ctx, k, lb_pixels, lb_avgs, lb_vars))) break;
+            if (lobe_path(cc.output_spd, config->output_spd, k, ".spd") || lobe_path(cc.average_spd, config->average_spd, k, ".spd") ||
+                lobe_path(cc.variance_spd, config->variance_spd, k, ".spd") || lobe_path(bmp, config->output_spd, k, ".bmp") ||
+                drt_host_write_outputs(&cc, width, height, S, scene->min_wavelength, scene->wavelength_interval, lb_pixels, lb_avgs, lb_vars, 0, done, seed) ||
+                drt_host_spd_file_to_bmp(cc.average_spd, bmp, cmf))
+                cut_bad = -1;
+        }
+        if (!rc && !cut_bad)
+        {
+            char txt[64];
+            FILE *f = lobes_txt_path(txt, config->output_spd) ? NULL : fopen(txt, "w");
+            if (!f) cut_bad = -1;
+            else
+            {
+                for (u32 k = 0; k < n_lobes; k += 1) fprintf(f, "%u %s\n", k, opt->lobe_names[k]);
+                if (fclose(f)) cut_bad = -1;
+            }
+        }
+        if (cut_bad) fprintf(stderr, "render_image: could not write the outputs of the lobe films\n");
+        else if (!rc && !opt->quiet) printf("Lobe films: %u films\n", n_lobes);
+        free(cmf);
+        free(lb_vars);
+        free(lb_avgs);
+        free(lb_pixels);
     }
     /* the denoised film, while the devices still hold the scene's tables (the film itself is not changed) */
     f64 *dn_mean = NULL, *dn_var = NULL;
@@ -1285,6 +1340,56 @@ static int buckets_options(const config_arguments *config, drt_host_options *opt
     return 0;
 }
 
+/* DRT_LOBES=standard|functions: a preset of lobe films, checked here, before any device call. The maps are those of pydrt.LOBE_PRESETS:
+ * "functions" -- emission, then one film per scattering function in bdsf_list.h's order, direct and indirect together; "standard" --
+ * emission; diffuse direct, indirect; glossy (bp_glossy, ct_conductor) direct, indirect; specular (mirror, fs_conductor, dielectric
+ * reflectance); transmission. */
+static int lobes_options(const config_arguments *config, drt_host_options *opt)
+{
+    static const char *const functions_names[] = { "emission", "bp_diffuse", "bp_glossy", "mirror", "fs_conductor", "fs_dielectric_reflectance",
+                                                   "fs_dielectric_transmittance", "ct_conductor" };
+    static const char *const standard_names[] = { "emission", "diffuse_direct", "diffuse_indirect", "glossy_direct", "glossy_indirect", "specular", "transmission" };
+    opt->n_lobes = 0;
+    opt->lobe_names = NULL;
+    memset(&opt->lobe_map, 0, sizeof(opt->lobe_map));
+    const char *e = getenv("DRT_LOBES");
+    if (!e) return 0;
+    static const char *const others[] = { "DRT_ADAPTIVE_ERROR", "DRT_CHECKPOINT_SPP", "DRT_RESUME", "DRT_TURNTABLE", "DRT_LIGHT_LEVELS", "DRT_DEPTH_CUTS", "DRT_SENSOR", "DRT_REGIONS", "DRT_BUCKETS" };
+    for (size_t k = 0; k < sizeof(others) / sizeof(others[0]); k += 1)
+        if (getenv(others[k])) { fprintf(stderr, "render_image: DRT_LOBES cannot be combined with %s: that render keeps no lobe films\n", others[k]); return -1; }
+    drt_lobe_map m;
+    memset(&m, 0, sizeof(m));
+    u32 n = 0;
+    if (strcmp(e, "functions") == 0)
+    {
+        n = 8;
+        m.emission = 0;
+        for (u32 f = 0; f < DRT_NUM_BDSFS; f += 1) m.direct[f] = m.indirect[f] = (uint8_t)(1 + f);
+        opt->lobe_names = functions_names;
+    }
+    else if (strcmp(e, "standard") == 0)
+    {
+        n = 7;
+        m.emission = 0;
+        m.direct[DRT_BDSF_bp_diffuse_bdsf] = 1; m.indirect[DRT_BDSF_bp_diffuse_bdsf] = 2;
+        m.direct[DRT_BDSF_bp_glossy_bdsf] = m.direct[DRT_BDSF_ct_conductor_bdsf] = 3;
+        m.indirect[DRT_BDSF_bp_glossy_bdsf] = m.indirect[DRT_BDSF_ct_conductor_bdsf] = 4;
+        m.direct[DRT_BDSF_mirror_bdsf] = m.indirect[DRT_BDSF_mirror_bdsf] = 5;
+        m.direct[DRT_BDSF_fs_conductor_bdsf] = m.indirect[DRT_BDSF_fs_conductor_bdsf] = 5;
+        m.direct[DRT_BDSF_fs_dielectric_reflectance_bdsf] = m.indirect[DRT_BDSF_fs_dielectric_reflectance_bdsf] = 5;
+        m.direct[DRT_BDSF_fs_dielectric_transmittance_bdsf] = m.indirect[DRT_BDSF_fs_dielectric_transmittance_bdsf] = 6;
+        opt->lobe_names = standard_names;
+    }
+    else { fprintf(stderr, "render_image: DRT_LOBES=\"%s\": standard or functions\n", e); return -1; }
+    char path[64];
+    if (lobe_path(path, config->output_spd, n - 1, ".spd") || lobe_path(path, config->average_spd, n - 1, ".spd") ||
+        lobe_path(path, config->variance_spd, n - 1, ".spd") || lobe_path(path, config->output_spd, n - 1, ".bmp") || lobes_txt_path(path, config->output_spd))
+    { fprintf(stderr, "render_image: DRT_LOBES: an output name with .lobe%u.spd or .lobes.txt behind it is longer than 63 characters\n", n - 1); return -1; }
+    opt->n_lobes = n;
+    opt->lobe_map = m;
+    return 0;
+}
+
 void render_image(config_arguments *config)
 {
     drt_host_options opt;
@@ -1321,5 +1426,6 @@ void render_image(config_arguments *config)
     if (regions_options(config, &opt) != 0) exit(-1);
     if (sensor_options(config, &opt) != 0) exit(-1);
     if (buckets_options(config, &opt) != 0) exit(-1);
+    if (lobes_options(config, &opt) != 0) exit(-1);
     if (render_image_ex(config, &opt, NULL) != 0) exit(-1);
 }

@@ -765,6 +765,15 @@ def hip_lib():
             L.drt_group_read_bucket_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
             L.drt_group_resolve_buckets.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_group_read_bucket_resolve.argtypes = [C.c_void_p, f64p, f64p]
+        if hasattr(L, "drt_bind_lobes"):  # (as drt_selftest_path_ids below)
+            vpp, u8p, mapp = C.POINTER(C.c_void_p), C.POINTER(C.c_uint8), C.POINTER(LobeMap)
+            L.drt_bind_lobes.argtypes = [C.c_void_p, C.c_uint32, mapp]
+            L.drt_read_lobe_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
+            L.drt_lobe_film_device_ptrs.argtypes = [C.c_void_p, C.c_uint32, vpp, vpp, vpp]
+            L.drt_read_lobe_xyz.argtypes = [C.c_void_p, C.c_uint32, f64p]
+            L.drt_read_lobe_bgra.argtypes = [C.c_void_p, C.c_uint32, C.c_int, u8p]
+            L.drt_group_bind_lobes.argtypes = [C.c_void_p, C.c_uint32, mapp]
+            L.drt_group_read_lobe_film.argtypes = [C.c_void_p, C.c_uint32, f64p, f64p, f64p]
         if hasattr(L, "drt_rebuild_hierarchy"):
             L.drt_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
             L.drt_group_rebuild_hierarchy.argtypes = [C.c_void_p, C.c_uint32]
@@ -826,6 +835,8 @@ HIP_SYMBOLS = ["drt_shade_instantiation",
                "drt_bind_buckets", "drt_read_bucket_film", "drt_bucket_film_device_ptrs", "drt_resolve_buckets", "drt_read_bucket_resolve",
                "drt_bucket_resolve_device_ptrs", "drt_read_bucket_resolve_xyz", "drt_read_bucket_resolve_bgra",
                "drt_group_bind_buckets", "drt_group_read_bucket_film", "drt_group_resolve_buckets", "drt_group_read_bucket_resolve",
+               "drt_bind_lobes", "drt_read_lobe_film", "drt_lobe_film_device_ptrs", "drt_read_lobe_xyz", "drt_read_lobe_bgra",
+               "drt_group_bind_lobes", "drt_group_read_lobe_film",
                "drt_render_sample_map", "drt_group_render_sample_map",
                "drt_live_window_of", "drt_live_window", "drt_selftest_division"]
 
@@ -889,6 +900,88 @@ def bucket_pair(means):
             acc = acc + half[k]
         out.append(acc / float(half.shape[0]))
     return out[0], out[1]
+
+
+MAX_LOBE_FILMS = 8  # DRT_MAX_LOBE_FILMS
+LOBE_NONE = 0xFF    # DRT_LOBE_NONE
+
+
+class LobeMap(C.Structure):
+    """drt_lobe_map"""
+    _fields_ = [("emission", C.c_uint8), ("direct", C.c_uint8 * len(BDSF_NAMES)), ("indirect", C.c_uint8 * len(BDSF_NAMES)), ("pad_", C.c_uint8)]
+
+
+def _lobe_film(value, what):
+    v = int(value)
+    if v != LOBE_NONE and not 0 <= v < MAX_LOBE_FILMS:
+        raise ValueError("%s = %d: a film 0 .. %d or LOBE_NONE" % (what, v, MAX_LOBE_FILMS - 1))
+    return v
+
+
+def _lobe_row(row, default, what):
+    out = [default] * len(BDSF_NAMES)
+    for name, film in dict(row or {}).items():
+        key = name if name in BDSF else str(name) + "_bdsf"
+        if key not in BDSF:
+            raise ValueError("%s: unknown scattering function %r (one of %s)" % (what, name, ", ".join(BDSF_NAMES)))
+        out[BDSF[key]] = _lobe_film(film, "%s[%s]" % (what, name))
+    return out
+
+
+def lobe_map(emission=None, direct=None, indirect=None, default=LOBE_NONE):
+    """A drt_lobe_map: the film of emission seen by the camera ray, and {function name: film} for the light sampled at the first vertex
+    (direct) and for everything behind it (indirect). Names are those of BDSF_NAMES, with or without the _bdsf ending; what is not
+    named goes to `default`. The film count a map needs is lobe_map_films(map)."""
+    default = _lobe_film(default, "lobe_map: default")
+    m = LobeMap()
+    m.emission = default if emission is None else _lobe_film(emission, "lobe_map: emission")
+    for k, v in enumerate(_lobe_row(direct, default, "lobe_map: direct")):
+        m.direct[k] = v
+    for k, v in enumerate(_lobe_row(indirect, default, "lobe_map: indirect")):
+        m.indirect[k] = v
+    return m
+
+
+def lobe_map_entries(m):
+    """the 15 entries of a map: emission, direct[7], indirect[7]"""
+    return [int(m.emission)] + [int(v) for v in m.direct] + [int(v) for v in m.indirect]
+
+
+def lobe_map_films(m):
+    """the smallest film count the map can be bound with: its highest film + 1 (at least 1)"""
+    used = [v for v in lobe_map_entries(m) if v != LOBE_NONE]
+    return max(used) + 1 if used else 1
+
+
+def _lobe_presets():
+    both = lambda films: dict(direct=films, indirect=films)
+    functions = lobe_map(emission=0, **both({n: 1 + i for i, n in enumerate(BDSF_NAMES)}))
+    d = {"bp_diffuse_bdsf": 1, "bp_glossy_bdsf": 3, "ct_conductor_bdsf": 3, "mirror_bdsf": 5, "fs_conductor_bdsf": 5,
+         "fs_dielectric_reflectance_bdsf": 5, "fs_dielectric_transmittance_bdsf": 6}
+    i = {"bp_diffuse_bdsf": 2, "bp_glossy_bdsf": 4, "ct_conductor_bdsf": 4, "mirror_bdsf": 5, "fs_conductor_bdsf": 5,
+         "fs_dielectric_reflectance_bdsf": 5, "fs_dielectric_transmittance_bdsf": 6}
+    return {"functions": (functions, ["emission"] + [n[:-len("_bdsf")] for n in BDSF_NAMES]),
+            "standard": (lobe_map(emission=0, direct=d, indirect=i),
+                         ["emission", "diffuse_direct", "diffuse_indirect", "glossy_direct", "glossy_indirect", "specular", "transmission"])}
+
+
+# name -> (map, film names): "functions" is emission plus one film per scattering function, direct and indirect together;
+# "standard" the usual layer set -- emission, diffuse and glossy each direct and indirect, specular, transmission
+LOBE_PRESETS = _lobe_presets()
+
+
+def _lobe_bind_args(map_or_preset, n):
+    """(n, map) for a bind: a preset's name, a LobeMap (n: its highest film + 1 unless given), or None / 0 to unbind"""
+    if map_or_preset is None or (isinstance(map_or_preset, int) and map_or_preset == 0):
+        return 0, None
+    if isinstance(map_or_preset, str):
+        if map_or_preset not in LOBE_PRESETS:
+            raise ValueError("bind_lobes: unknown preset %r (one of %s)" % (map_or_preset, ", ".join(sorted(LOBE_PRESETS))))
+        m, names = LOBE_PRESETS[map_or_preset]
+        return (len(names) if n is None else _u32(n, "bind_lobes: n")), m
+    if not isinstance(map_or_preset, LobeMap):
+        raise TypeError("bind_lobes: a preset's name, a pydrt.lobe_map(...) or None, not %s" % type(map_or_preset).__name__)
+    return (lobe_map_films(map_or_preset) if n is None else _u32(n, "bind_lobes: n")), map_or_preset
 
 
 def observer_curves(bundle):
@@ -1093,6 +1186,41 @@ class Renderer:
         """BMP pixel bytes [P][4] = B, G, R, 255 of the estimate, as read_bgra of the means"""
         out = np.empty((self.n_pixels, 4), dtype=np.uint8)
         _check(self.L.drt_read_bucket_resolve_bgra(self.ctx, _ptr(out, C.c_uint8)), "drt_read_bucket_resolve_bgra")
+        return out
+
+    def bind_lobes(self, map_or_preset, n=None):
+        """drt_bind_lobes: n films beside the main film that split it by the first vertex's scattering lobe, on a film that holds no
+        samples. map_or_preset: a name of LOBE_PRESETS, or a pydrt.lobe_map(...) (n: its highest film + 1 unless given); None unbinds"""
+        n, m = _lobe_bind_args(map_or_preset, n)
+        _check(self.L.drt_bind_lobes(self.ctx, n, C.byref(m) if m is not None else None), "drt_bind_lobes")
+        self.n_lobes = n
+
+    def read_lobe_film(self, c):
+        """(pixels [P][S+1], means [P][S], variances [P][S]) of lobe film c"""
+        c = _u32(c, "read_lobe_film: c")
+        if not getattr(self, "n_lobes", 0) or c >= self.n_lobes:
+            _check(self.L.drt_read_lobe_film(self.ctx, c, None, None, None), "drt_read_lobe_film")  # (says which, touches nothing)
+        S, n = self.S, self.n_pixels
+        px, av, va = np.empty((n, S + 1)), np.empty((n, S)), np.empty((n, S))
+        _check(self.L.drt_read_lobe_film(self.ctx, c, _ptr(px, C.c_double), _ptr(av, C.c_double), _ptr(va, C.c_double)), "drt_read_lobe_film")
+        return px, av, va
+
+    def lobe_film_device_ptrs(self, c):
+        a, b, d = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(self.L.drt_lobe_film_device_ptrs(self.ctx, _u32(c, "lobe_film_device_ptrs: c"), C.byref(a), C.byref(b), C.byref(d)),
+               "drt_lobe_film_device_ptrs")
+        return a.value, b.value, d.value
+
+    def read_lobe_xyz(self, c):
+        """[P][3]: drt_read_xyz's conversion of lobe film c"""
+        out = np.empty((self.n_pixels, 3))
+        _check(self.L.drt_read_lobe_xyz(self.ctx, _u32(c, "read_lobe_xyz: c"), _ptr(out, C.c_double)), "drt_read_lobe_xyz")
+        return out
+
+    def read_lobe_bgra(self, c, which=1):
+        """BMP pixel bytes [P][4] = B, G, R, 255 of lobe film c, as read_bgra"""
+        out = np.empty((self.n_pixels, 4), dtype=np.uint8)
+        _check(self.L.drt_read_lobe_bgra(self.ctx, _u32(c, "read_lobe_bgra: c"), int(which), _ptr(out, C.c_uint8)), "drt_read_lobe_bgra")
         return out
 
     def bind_sensor(self, curves):
@@ -1588,6 +1716,23 @@ class Group:
         f64p = C.POINTER(C.c_double)
         _check(self.L.drt_group_read_bucket_resolve(self.g, est.ctypes.data_as(f64p), err.ctypes.data_as(f64p)), "drt_group_read_bucket_resolve")
         return est, err
+
+    def bind_lobes(self, map_or_preset, n=None):
+        """drt_group_bind_lobes: as Renderer.bind_lobes, every context checked and every film allocated before any is changed"""
+        n, m = _lobe_bind_args(map_or_preset, n)
+        _check(self.L.drt_group_bind_lobes(self.g, n, C.byref(m) if m is not None else None), "drt_group_bind_lobes")
+        self.n_lobes = n
+
+    def read_lobe_film(self, c):
+        """drt_group_read_lobe_film: lobe film c of the whole tile, in image order"""
+        c = _u32(c, "read_lobe_film: c")
+        if not getattr(self, "n_lobes", 0) or c >= self.n_lobes:
+            _check(self.L.drt_group_read_lobe_film(self.g, c, None, None, None), "drt_group_read_lobe_film")
+        px, av, va = np.empty((self.n_pixels, self.S + 1)), np.empty((self.n_pixels, self.S)), np.empty((self.n_pixels, self.S))
+        f64p = C.POINTER(C.c_double)
+        _check(self.L.drt_group_read_lobe_film(self.g, c, px.ctypes.data_as(f64p), av.ctypes.data_as(f64p), va.ctypes.data_as(f64p)),
+               "drt_group_read_lobe_film")
+        return px, av, va
 
     def bind_sensor(self, curves):
         """drt_group_bind_sensor: as Renderer.bind_sensor, every context checked and every film allocated before any is changed"""

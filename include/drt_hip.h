@@ -188,7 +188,7 @@ typedef struct drt_stats
     uint64_t shadow_scans;      /* points_mutually_visible calls             */
     uint64_t rng_draws;
     double   trace_ms;          /* path-geometry kernel, HIP-event time      */
-    double   shade_ms;          /* spectral shade + film kernel; while depth cuts, a sensor or buckets are bound (drt_bind_depth_cuts, drt_bind_sensor, drt_bind_buckets), that pass too */
+    double   shade_ms;          /* spectral shade + film kernel; while depth cuts, a sensor, buckets or lobes are bound (drt_bind_depth_cuts, drt_bind_sensor, drt_bind_buckets, drt_bind_lobes), that pass too */
     double   total_ms;
     /* the pool of vertex records (four vertices per block): its size, the most a launch has used, and how many launches had to be
      * rendered again in worst-case-sized pieces because the pool ran out (0 unless the tile's paths grew after the context measured them) */
@@ -744,6 +744,60 @@ int drt_group_resolve_buckets(drt_group *g, uint32_t trim);
 int drt_group_read_bucket_resolve(drt_group *g, double *estimate, double *error);
 
 /*
+ * Lobe films: the film split by what the first surface did with the light -- by the entry of vertex 0's own BDSF list whose addend
+ * carries it, light sampled at vertex 0 (direct) and everything behind vertex 0 (indirect) apart -- and by emission the camera ray
+ * itself ends on. These are the layers a compositor grades separately and a denoiser filters with different bandwidths. The film is
+ * linear in the first vertex's BDSF addends (bdsf(), src/daily_ray_trace.c:215-229, and the light fold, :323-327, are linear per
+ * addend), so the layers add up to the main film up to rounding. DESIGN.md section 5n.
+ *
+ * The rule, `+ - *` and the film update's `/` only, nothing contracted. For one sample, with f_i the i-th entry of vertex 0's list:
+ *   - the addend a_i(args) is the value of the dispatcher's bdsf_result after entry i: the function's value, or, when its direction
+ *     test fails, the value carried over from the entry before it (quirk Q1) -- 0.0 when nothing came before. It belongs to entry i's
+ *     function even when it is a carried value: under this definition the films add up to the main film. On a reflected glass sample
+ *     the reflectance film and the transmittance film both receive R, as the main film receives R + R;
+ *   - R^c_K(args), for film c and map row K (direct or indirect): 0.0, then R = a_i + R over the positions i with K[f_i] == c, in
+ *     list order;
+ *   - C^c: 0.0, then for each visible light l in order C = C + R^c_direct(light l), C = C * em_l, C = C * c_l -- for every film;
+ *   - vertex 0: dst^c = 0.0 + 1.0 * C^c and T^c = 1.0 * (R^c_indirect(sample) * dir_pdf);
+ *   - vertex v >= 1: C_v and R_v are the main film's, shared by all films: dst^c = dst^c + T^c * C_v, T^c = T^c * (R_v * dir_pdf_v);
+ *   - the end of the path, with n_shaded < max_depth and the path ending on an emitter: value^c = dst^c + T^c * spd(emitter) for every
+ *     film when n_shaded >= 1; when n_shaded == 0, value = 0.0 + 1.0 * spd(emitter) for film `emission` and 0.0 for the others;
+ *   - value^c * vignette goes through the film update (:732-743) of film c, the divisor the sample's own number + 1, the filter
+ *     column += 1.0. Every film takes every sample, zeros included: each is a film of the main film's layout and count, and its
+ *     variance is the layer's own.
+ * A map that sends all 15 entries to film 0 gives the main film, bit for bit.
+ *
+ * Every lobe film has the main film's three buffers and layout, owned by the context, zero-filled at the bind and by drt_reset_film,
+ * released at the unbind and by drt_destroy. A launch whose record pool ran out leaves them untouched and is rendered again with the
+ * rest.
+ */
+#define DRT_MAX_LOBE_FILMS 8
+#define DRT_LOBE_NONE 0xFFu            /* this part goes to no film */
+typedef struct drt_lobe_map {
+    uint8_t emission;                  /* a camera ray that ends on an emitter (no shaded vertex, term == 1) */
+    uint8_t direct[DRT_NUM_BDSFS];     /* light sampled at vertex 0, by the listed function whose addend carries it */
+    uint8_t indirect[DRT_NUM_BDSFS];   /* everything behind vertex 0, by the function whose addend carries the continuation */
+    uint8_t pad_;
+} drt_lobe_map;
+/* Bind the context to n films and a map (n == 0: unbind, the films are released, the map is not read). Refused, with the reason in
+ * drt_last_error() and the context as it was: n > DRT_MAX_LOBE_FILMS, a NULL map, a map entry >= n that is not DRT_LOBE_NONE,
+ * DRT_MODE_XYZ, a film that holds samples, an adaptive render or a sample map (drt_reset_film first), bound depth cuts, a bound sensor
+ * or bound buckets, an allocation failure. While lobes are bound drt_bind_depth_cuts, drt_bind_sensor, drt_bind_buckets,
+ * drt_render_adaptive, drt_render_adaptive_continue and drt_render_sample_map are refused, and the live window is not used. */
+int drt_bind_lobes(drt_context *ctx, uint32_t n, const drt_lobe_map *map);
+/* Copy film c (0 .. n-1) to host buffers (any may be NULL). Synchronises. */
+int drt_read_lobe_film(drt_context *ctx, uint32_t c, double *pixels, double *avgs, double *vars);
+/* Device pointers of film c's buffers; valid until the next bind, unbind or drt_destroy. Synchronises. */
+int drt_lobe_film_device_ptrs(drt_context *ctx, uint32_t c, void **d_pixels, void **d_avgs, void **d_vars);
+/* drt_read_xyz and drt_read_bgra's kernels on film c (`which` as drt_read_bgra: 0 the sums, 1 the means, 2 the variances). */
+int drt_read_lobe_xyz(drt_context *ctx, uint32_t c, double *xyz);
+int drt_read_lobe_bgra(drt_context *ctx, uint32_t c, int which, uint8_t *bgra);
+/* Every context is checked, and every device's films allocated, before any context is changed. */
+int drt_group_bind_lobes(drt_group *g, uint32_t n, const drt_lobe_map *map);
+/* Film c of the whole tile, in image order, as drt_group_read_depth_film. */
+int drt_group_read_lobe_film(drt_group *g, uint32_t c, double *pixels, double *avgs, double *vars);
+
+/*
  * Scene updates: move the camera and the surfaces of a live context, where the only way used to be drt_destroy + drt_create (the
  * pool freed and allocated again, the pool measurement rendered again, the hierarchy built again). DESIGN.md section 5g.
  *
@@ -985,7 +1039,7 @@ int drt_read_hierarchy(drt_context *ctx, void *nodes, uint32_t n_nodes, uint32_t
  * per kernel pair, what its samples -- all worth +0 -- leave on the film, and its paths are counted in drt_stats as the reference
  * counts them (a path, one closest-hit scan, the pixel's draws). Films, statistics and draw counts are bit for bit what they are
  * without it; DRT_NO_LIVE_WINDOW=1, read by drt_create, turns it off. Not used with DRT_FLAG_RECORD_HITS, pixel lists (adaptive
- * rounds, sample maps), a bound ray table, bound depth cuts, a bound sensor or bound buckets.
+ * rounds, sample maps), a bound ray table, bound depth cuts, a bound sensor, bound buckets or bound lobes.
  */
 /* Host only, like drt_bvh_stats: the rule on the scene and camera as given. */
 int drt_live_window_of(const drt_scene *scene, const drt_camera *camera, const drt_params *params, uint32_t out[4]);
