@@ -2141,6 +2141,40 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t l)
     return (uint64_t)lo | ((uint64_t)hi << 32);
 }
 
+/* a word every lane holds alike (a broadcast LDS read), to the scalar side */
+__device__ __forceinline__ uint64_t first64(uint64_t v)
+{
+    uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
+/* v, through a copy the compiler cannot see through where AGAIN: what is derived from the result is derived where it is used, not hoisted
+ * with everything else that follows from v (shade_pixels: the lane number, per work item) */
+template <bool AGAIN>
+__device__ __forceinline__ uint32_t made_again(uint32_t v)
+{
+    if constexpr (AGAIN) asm volatile("" : "+v"(v));
+    return v;
+}
+
+/* A word for the scalar side, wherever the instantiation keeps it: FROM_LDS, the word every lane reads at `at` (a broadcast read);
+ * otherwise lane l of the register v. (Functions, not lambdas of the kernel's body: the form that does not read LDS then compiles
+ * to what readlane64 alone does.) */
+template <bool FROM_LDS>
+__device__ __forceinline__ uint64_t lifted_word(const uint64_t *at, uint64_t v, uint32_t l)
+{
+    if constexpr (FROM_LDS) return first64(*at);
+    else return readlane64(v, l);
+}
+/* the same word as a multiplicand: FROM_LDS, it stays in the vector register the read left it in */
+template <bool FROM_LDS>
+__device__ __forceinline__ double lifted_double(const uint64_t *at, uint64_t v, uint32_t l)
+{
+    if constexpr (FROM_LDS) return word_as_double(*at);
+    else return word_as_double(readlane64(v, l));
+}
+
 /* where vertex v of a path lives, from the header's block words (see the record layout above) */
 __device__ __forceinline__ const uint64_t *path_vertex(const uint64_t *__restrict__ pool, uint32_t block_words, uint32_t vw, uint64_t h2, uint64_t h3, uint32_t v)
 {
@@ -2275,6 +2309,24 @@ __device__ __forceinline__ double bdsf_at_wavelength(uint64_t list_arg, uint32_t
 #define TAIL_WINDOW_ENTRIES 112u /* headers of a window: three words each (words 0, 1, 2), and a 16-bit task list entry */
 #define TAIL_WINDOW_WORDS (3u * TAIL_WINDOW_ENTRIES + TAIL_WINDOW_ENTRIES / 4u) /* 2.9 KB */
 #define SHADE_WAVE_LDS_WORDS ((2u * 64u * SHADE_PREFETCH_REGS) > TAIL_WINDOW_WORDS ? (2u * 64u * SHADE_PREFETCH_REGS) : TAIL_WINDOW_WORDS)
+/* The closed instantiation's second form of the main pass (shade_pixels, CLOSED_LDS; the entry point drt_shade_kernel_closed_lds, compiled
+ * unless DRT_SHADE_CLOSED_LDS_HEADERS is 0): the window's header words 0-2 live in the wave's LDS region instead of eight vector
+ * registers, word 3 is fetched for the one path that reaches vertex 8, and the arrived record prefetch goes straight to ONE slot, so
+ * the registers it arrived in take the next prefetch -- no second copy as the source of v_readlane lifts. Region, in 64-bit words:
+ * [0, 128) the record slot, [128, 192) word 0 of the window's 64 samples, [192, 256) their word 1, [256, 320) their word 2. 2560 bytes a
+ * wave, so that five workgroups of SHADE_WAVES waves and a table of up to 39 rows of 69 fit a CU's LDS (drt_shade_lds_rule.h); the tail
+ * pass, in the same region at other times, takes windows of 96 headers there. */
+#ifndef DRT_SHADE_CLOSED_LDS_HEADERS
+#define DRT_SHADE_CLOSED_LDS_HEADERS 1
+#endif
+#define SHADE_CLOSED_SLOT_WORDS (64u * SHADE_PREFETCH_REGS)
+#define SHADE_CLOSED_HDR01_AT SHADE_CLOSED_SLOT_WORDS
+#define SHADE_CLOSED_HDR2_AT (SHADE_CLOSED_HDR01_AT + 128u)
+#define SHADE_CLOSED_TAIL_ENTRIES 96u
+#define SHADE_CLOSED_WAVE_LDS_WORDS (SHADE_CLOSED_HDR2_AT + 64u)
+static_assert(3u * SHADE_CLOSED_TAIL_ENTRIES + SHADE_CLOSED_TAIL_ENTRIES / 4u <= SHADE_CLOSED_WAVE_LDS_WORDS, "the tail pass's window fits the closed form's region");
+/* a wave's region by form: what the kernel strides by and the launcher allocates */
+#define SHADE_WAVE_LDS_WORDS_FOR(closed_lds) ((closed_lds) ? SHADE_CLOSED_WAVE_LDS_WORDS : SHADE_WAVE_LDS_WORDS)
 
 #define XYZ_FILM_WORDS 8 /* XYZ film mode, per pixel: X, Y, Z numerators of the main pass, filter sum, X, Y, Z of the tail pass, unused */
 
@@ -2289,7 +2341,7 @@ template <bool SPDS_IN_LDS, bool XYZ, bool SIMPLE, bool LIST = false>
 __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const ShadeParams &sp, const double *lds, uint64_t *wave_lds, const uint64_t *__restrict__ records,
                                                  const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                                  double *__restrict__ film_avgs, double *__restrict__ film_vars, uint64_t chunk_base,
-                                                 uint64_t chunk_end, uint32_t lane, const bool closed)
+                                                 uint64_t chunk_end, uint32_t lane, const bool closed, const bool closed_lds = false)
 {
     const uint32_t S = sc.S;
     const uint32_t vw = sp.vertex_words;
@@ -2322,8 +2374,9 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
      * lanes are waiting for.
      */
     const uint32_t n_groups = 64u / R;                 /* lane groups = the pixels of a full chunk */
-    const uint32_t win = TAIL_WINDOW_ENTRIES / n_groups; /* samples per window */
-    uint16_t *task_list = (uint16_t *)(wave_lds + 3u * TAIL_WINDOW_ENTRIES);
+    const uint32_t entries = closed_lds ? SHADE_CLOSED_TAIL_ENTRIES : TAIL_WINDOW_ENTRIES; /* (a constant where this is inlined) */
+    const uint32_t win = entries / n_groups; /* samples per window */
+    uint16_t *task_list = (uint16_t *)(wave_lds + 3u * entries);
     const uint32_t leader = g * R;                     /* the group's first lane */
     const bool in_group = g < n_groups;
     uint32_t v = 0, n_shaded = 0;
@@ -2645,7 +2698,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
  * fixed_vertex's four (the launcher checks, closed_lists()): the general list does not exist, neither in the main pass nor in the tail
  * pass's general step -- its loop, its switch and the registers they hold are not compiled. Same operations in the same order: what
  * is left is the very code the general instantiation runs for these lists (tests/test_gpu_closed_lists.py flips DRT_NO_CLOSED_SHADE). */
-template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE, bool LIST, bool CLOSED>
+template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE, bool LIST, bool CLOSED, bool CLOSED_LDS = false>
 __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadeParams &sp, const uint64_t *__restrict__ records,
                                              const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                              double *__restrict__ film_avgs, double *__restrict__ film_vars,
@@ -2662,9 +2715,11 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
         for (uint32_t k = threadIdx.x; k < spd_words; k += SHADE_BLOCK) lds[k] = sc.spds[k];
         __syncthreads();
     }
-    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lane_k = threadIdx.x & 63u;
     /* behind the SPD table: two record slots per wave (see the sample loop) */
-    uint64_t *rec_lds = (uint64_t *)(lds + (SPDS_IN_LDS ? (size_t)sc.n_spd * S : 0)) + (size_t)(threadIdx.x >> 6) * SHADE_WAVE_LDS_WORDS;
+    static_assert(!CLOSED_LDS || CLOSED, "the form with headers in LDS is a closed form");
+    constexpr bool LDS_HDR = CLOSED_LDS; /* headers and one record slot in LDS (see DRT_SHADE_CLOSED_LDS_HEADERS) */
+    uint64_t *rec_lds = (uint64_t *)(lds + (SPDS_IN_LDS ? (size_t)sc.n_spd * S : 0)) + (size_t)(threadIdx.x >> 6) * SHADE_WAVE_LDS_WORDS_FOR(LDS_HDR);
     const uint32_t vw = sp.vertex_words;                 /* power of two >= 16 */
     const uint32_t vpr = vw <= 64 ? 64u / vw : 0u;       /* vertices per 64-word register (0: records wider than a register) */
     const uint32_t n_fast_regs = vpr * SHADE_PREFETCH_REGS;
@@ -2674,7 +2729,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
 #pragma unroll
     for (int k = 0; k < NSETS; k += 1)
     {
-        const uint32_t lam = 64u * k + lane;
+        const uint32_t lam = 64u * k + lane_k;
         lam_c[k] = lam < S ? lam : 0; /* lanes past the table read row element 0 and are never stored */
     }
 
@@ -2684,9 +2739,15 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
         /* draw the next work item (wave-uniform): part of a pixel group's main pass, its tail pass, or both */
         const ShadeParams &qc = shade_const().sp; /* the queue's parameters, read here only */
         uint32_t item = 0;
-        if (lane == 0) item = (uint32_t)atomicAdd(work_counter, 1ull);
+        if (lane_k == 0) item = (uint32_t)atomicAdd(work_counter, 1ull);
         item = (uint32_t)__builtin_amdgcn_readfirstlane((int)item);
         if (item >= qc.n_items) break;
+        /* The lane number and what follows from it. LDS_HDR: made again for every item, and once more for its tail pass, from a copy the
+         * compiler cannot see through. Left alone it makes every lane-dependent value of BOTH passes -- offsets into the table, the
+         * slot and the film rows, the tail pass's pixel and wavelength -- once above this loop and holds them in vector registers
+         * through every item of either kind: thirteen registers that the main pass alone (83) and the tail pass alone (83) do not need. */
+        const uint32_t lane = made_again<LDS_HDR>(lane_k);
+        if constexpr (LDS_HDR) lam_c[0] = lane < S ? lane : 0; /* (one wavelength set) */
         /* split queue: a group's tail pass is the longest item, so the tail items are dealt out early -- one at the head of
          * every period of 1 + tail_period_mains items, between main-pass pieces so that latency-bound tail waves and
          * arithmetic-bound main waves share the SIMDs -- and the launch ends on main-pass pieces only */
@@ -2779,7 +2840,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
             h0 = h[0];
             h1 = h[1];
             h2 = h[2];
-            h3 = h[3];
+            if (!LDS_HDR) h3 = h[3];
         }
         /* the window's samples that are worth +-0 whatever the wavelength: no vertex, ended on nothing that emits, and a finite vignette
          * (0 x vignette must be a zero: a NaN or an infinity has to go through the arithmetic) -- one ballot over the headers */
@@ -2791,9 +2852,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
          * vertices laid end to end. A block is four vertices, 64 words or more, so a register never straddles blocks: one block
          * number per register, from the header (scalar), and consecutive lanes read consecutive words. Only the header's own
          * blocks are prefetched; deeper vertices are fetched when they are replayed. */
-        auto prefetch = [&](uint32_t sa, uint32_t nw, uint64_t *dst) {
-            if (nw == 0u) return; /* three paths in five have no shaded vertex: nothing to fetch, and what the registers hold is never read */
-            const uint64_t b2 = readlane64(h2, sa);
+        auto prefetch_blocks = [&](uint64_t b2, uint32_t nw, uint64_t *dst) __attribute__((always_inline)) { /* b2: the path's header word 2 */
 #pragma unroll
             for (int k = 0; k < SHADE_PREFETCH_REGS; k += 1)
             {
@@ -2803,24 +2862,79 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 dst[k] = (64u * k + lane < nw) ? base[lane] : 0;
             }
         };
+        auto prefetch = [&](uint32_t sa, uint32_t nw, uint64_t *dst) {
+            if (nw == 0u) return; /* three paths in five have no shaded vertex: nothing to fetch, and what the registers hold is never read */
+            prefetch_blocks(readlane64(h2, sa), nw, dst);
+        };
         /* ring of prefetched records: ring[0] = the sample being replayed, ring[d] = d samples ahead. Memory
          * latency (~2 us) is several samples of replay, so the loads run SHADE_PREFETCH_DEPTH samples ahead. */
         uint64_t ring[SHADE_PREFETCH_DEPTH + 1][SHADE_PREFETCH_REGS];
+        /* LDS_HDR: the window's headers go to the wave's region, and the sample loop runs on four words read a sample ahead --
+         * issued before a sample's film update, so they travel while it runs and no register holds them across a vertex body:
+         * hs_v / vig_v = words 0 and 1 of the sample about to be replayed, nx0_v / nx2_v = words 0 and 2 of the one after it (whose
+         * records that sample's iteration requests). ring[1] alone is used: the records in flight. */
+        const uint64_t *hdr01 = rec_lds + SHADE_CLOSED_HDR01_AT, *hdr2 = rec_lds + SHADE_CLOSED_HDR2_AT;
+        uint64_t hs_v = 0, vig_v = 0, nx0_v = 0, nx2_v = 0;
+        auto fetch_headers = [&](uint32_t t) { /* what sample t's iteration reads at its top (past the window: words nobody reads) */
+            const uint32_t a = t & 63u, b = (t + 1u) & 63u;
+            hs_v = hdr01[a];
+            vig_v = hdr01[64u + a];
+            nx0_v = hdr01[b];
+            nx2_v = hdr2[b];
+        };
+        if constexpr (LDS_HDR)
+        {
+            static_assert(SHADE_PREFETCH_DEPTH == 1, "one sample ahead");
+            __builtin_amdgcn_wave_barrier(); /* the reads of the window before, or of a tail pass, are in order before these writes (one wave, in-order LDS) */
+            uint64_t *hw = rec_lds + SHADE_CLOSED_HDR01_AT;
+            hw[lane] = h0; /* (lanes past the window: zeros, a path without a vertex) */
+            hw[64u + lane] = h1;
+            hw[128u + lane] = h2;
+            __builtin_amdgcn_wave_barrier();
+            fetch_headers(0u);
+            const uint64_t head0 = first64(hs_v);
+            const uint32_t nw = (uint32_t)(head0 & 0xFFFFu) * vw;
+            if (nw != 0u) prefetch_blocks(first64(hdr2[0]), nw, ring[1]);
+        }
+        else
+        {
 #pragma unroll
         for (int d = 0; d < SHADE_PREFETCH_DEPTH; d += 1)
         {
             const uint32_t nw = ((uint32_t)d < n_win) ? (uint32_t)(readlane64(h0, d) & 0xFFFFu) * vw : 0u;
             prefetch((uint32_t)d < n_win ? (uint32_t)d : 0u, nw, ring[d + 1]);
         }
+        }
         for (uint32_t s = 0; s < n_win; s += 1)
         {
-            const uint64_t hs = readlane64(h0, s);
-            const double vignette = word_as_double(readlane64(h1, s));
+            const uint64_t hs = LDS_HDR ? first64(hs_v) : readlane64(h0, s);
+            const uint64_t vig_w = LDS_HDR ? vig_v : readlane64(h1, s); /* LDS_HDR: stays in a vector register, it is only ever a multiplicand */
+            const double vignette = word_as_double(vig_w);
             const uint32_t n_shaded = (uint32_t)(hs & 0xFFFFu);
             const uint32_t term = (uint32_t)(hs >> 16) & HDR_TERM_MASK;
             const uint32_t term_spd = (uint32_t)(hs >> 32) & 0xFFFFu;
             const uint32_t plastic_mask = (uint32_t)(hs >> 48); /* bit v: vertex v has the two-lobe plastic list */
             const uint32_t vis0_mask = (uint32_t)(hs >> 24) & 0xFFu; /* bit v (< 8): light 0 visible from vertex v */
+            uint64_t w1_first = 0; /* LDS_HDR: word 1 of vertex 0 (its SPD indices), lifted before the registers take the next prefetch */
+            if constexpr (LDS_HDR)
+            {
+                /* This sample's records (requested a sample ago) go from the registers they arrived in to the wave's one slot -- the
+                 * reads of the sample before are in order before these writes -- and the same registers take the next sample's.
+                 * Every word of a record then comes from the slot: multiplicands as broadcast reads, fields for the scalar side
+                 * through v_readfirstlane (the words of vertex 0's leading plastic run: from the registers, here). */
+                if (n_shaded != 0u)
+                {
+                    w1_first = readlane64(ring[1][0], 1u);
+                    uint64_t *slot_now = rec_lds;
+#pragma unroll
+                    for (int k = 0; k < SHADE_PREFETCH_REGS; k += 1) slot_now[64u * k + lane] = ring[1][k];
+                }
+                const uint64_t next0 = first64(nx0_v);
+                const uint32_t nw = (s + 1u < n_win) ? (uint32_t)(next0 & 0xFFFFu) * vw : 0u;
+                if (nw != 0u) prefetch_blocks(first64(nx2_v), nw, ring[1]);
+            }
+            else
+            {
             /* rotate the ring, then start the load for the sample SHADE_PREFETCH_DEPTH ahead */
 #pragma unroll
             for (int d = 0; d < SHADE_PREFETCH_DEPTH; d += 1)
@@ -2831,7 +2945,10 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 const uint32_t nw = (sa < n_win) ? (uint32_t)(readlane64(h0, sa) & 0xFFFFu) * vw : 0u;
                 prefetch(sa < n_win ? sa : 0u, nw, ring[SHADE_PREFETCH_DEPTH]);
             }
+            }
             const uint64_t *cur = ring[0];
+            if constexpr (!LDS_HDR)
+            {
             /* This sample's records (requested a sample ago) also go to this wave's LDS slot s & 1: the coefficient words of a
              * plastic vertex are then read back as broadcast LDS loads -- one instruction per 64-bit word, result in a vector
              * register where the f64 operations want it -- instead of two v_readlane each. */
@@ -2841,9 +2958,17 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
 #pragma unroll
                 for (int k = 0; k < SHADE_PREFETCH_REGS; k += 1) slot_now[64u * k + lane] = ring[0][k];
             }
-            const uint64_t *rec_words = rec_lds + (s & 1u) * (64u * SHADE_PREFETCH_REGS);
+            }
+            const uint64_t *rec_words = rec_lds + (LDS_HDR ? 0u : (s & 1u) * (64u * SHADE_PREFETCH_REGS));
             /* nothing gathered, nothing emitted, into a pixel that is all +0: the film update would change no bit */
-            if (DARK && dark && ((worthless >> s) & 1ull) != 0ull) continue;
+            if (DARK && dark && ((worthless >> s) & 1ull) != 0ull)
+            {
+                if constexpr (LDS_HDR) fetch_headers(s + 1u);
+                continue;
+            }
+            /* LDS_HDR: this path's header words 2 and 3 where a deep vertex asks for them -- word 2 from the wave's region, word 3 (the
+             * blocks of vertices 8 and up) from the header itself, as the tail pass's deep_blocks does */
+            const uint64_t *head3_at = headers + ((pix * sp.batch + s0 + s) * REC_HEADER_WORDS + 3);
 
             double throughput[NSETS], dst[NSETS];
 #pragma unroll
@@ -2894,10 +3019,25 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 /* the vertices the first prefetch register holds, then those of the second: the word with the SPD indices comes out of
                  * ONE register by v_readlane, no choosing between two */
                 const uint32_t run0 = run < vpr ? run : vpr;
+                if constexpr (LDS_HDR)
+                {
+                    /* the word with the SPD indices: vertex 0's was lifted from the arrived registers, the next vertex's is read from the
+                     * slot while this one is replayed (past the run: a word of the slot nobody uses) */
+                    uint64_t w1 = w1_first;
+                    for (uint32_t v = 0; v < run; v += 1)
+                    {
+                        const uint64_t w1_next = rec_words[((v + 1u) * vw + 1u) & (SHADE_CLOSED_SLOT_WORDS - 1u)];
+                        run_vertex(w1, rec_words + v * vw, ((vis0_mask >> v) & 1u) != 0u);
+                        w1 = first64(w1_next);
+                    }
+                }
+                else
+                {
                 for (uint32_t v = 0; v < run0; v += 1)
                     run_vertex(readlane64(cur[0], v * vw + 1u), rec_words + v * vw, ((vis0_mask >> v) & 1u) != 0u);
                 for (uint32_t v = run0; v < run; v += 1)
                     run_vertex(readlane64(cur[SHADE_PREFETCH_REGS > 1 ? 1 : 0], (v - vpr) * vw + 1u), rec_words + v * vw, ((vis0_mask >> v) & 1u) != 0u);
+                }
                 v_first = run;
                 /* Beyond the prefetched records (vertices 8 and up: long paths in closed scenes), when everything so far was a run: the
                  * path's further blocks one at a time -- four vertices by ONE coalesced load, which takes the place of vertices 0-3
@@ -2905,14 +3045,14 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                  * round trip per block instead of one per vertex, and none of the general loop's work. */
                 if (run == n_fast && n_shaded > run && vw * REC_BLOCK_VERTICES == 64u)
                 {
-                    const uint64_t h3s = readlane64(h3, s);
+                    const uint64_t h3s = lifted_word<LDS_HDR>(head3_at, h3, s);
                     for (uint32_t b = n_fast / REC_BLOCK_VERTICES; b * REC_BLOCK_VERTICES < n_shaded && b < 4u; b += 1) /* plastic_mask covers 16 vertices */
                     {
                         uint32_t id = (uint32_t)h3s;
-                        if (b == 1u) id = (uint32_t)(readlane64(h2, s) >> 32);
+                        if (b == 1u) id = (uint32_t)(lifted_word<LDS_HDR>(hdr2 + s, h2, s) >> 32);
                         if (b >= REC_HEADER_BLOCKS) id = ((const uint32_t *)(records + (uint64_t)(uint32_t)(h3s >> 32) * sp.block_words))[b - REC_HEADER_BLOCKS];
                         const uint64_t blockw = records[(uint64_t)id * sp.block_words + lane];
-                        uint64_t *slot = rec_lds + (s & 1u) * (64u * SHADE_PREFETCH_REGS);
+                        uint64_t *slot = rec_lds + (LDS_HDR ? 0u : (s & 1u) * (64u * SHADE_PREFETCH_REGS));
                         slot[lane] = blockw;
                         const uint32_t v_lo = b * REC_BLOCK_VERTICES;
                         const uint32_t v_hi = n_shaded < v_lo + REC_BLOCK_VERTICES ? n_shaded : v_lo + REC_BLOCK_VERTICES;
@@ -2934,7 +3074,17 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 /* the register (and the lane offset in it) that holds this vertex's record */
                 uint64_t src;
                 uint32_t lane0;
-                if (v < n_fast)
+                uint32_t vbase = 0; /* LDS_HDR: where the vertex's words are in the slot */
+                if constexpr (LDS_HDR)
+                {
+                    /* every word comes from the slot: a prefetched vertex lies there, a deeper one (or a record wider than a register) is
+                     * fetched now, its first 64 words taking the place of the slot's -- vertices that are done */
+                    lane0 = 0;
+                    src = 0;
+                    if (v < n_fast) vbase = v * vw;
+                    else rec_lds[lane] = (lane < vw) ? path_vertex(records, sp.block_words, vw, lifted_word<LDS_HDR>(hdr2 + s, h2, s), lifted_word<LDS_HDR>(head3_at, h3, s), v)[lane] : 0;
+                }
+                else if (v < n_fast)
                 {
                     const uint32_t sel = v / vpr;
                     lane0 = (v - sel * vpr) * vw;
@@ -2945,8 +3095,9 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 {
                     /* deep path or a record wider than a register: fetch the first 64 words of the vertex now */
                     lane0 = 0;
-                    src = (lane < vw) ? path_vertex(records, sp.block_words, vw, readlane64(h2, s), readlane64(h3, s), v)[lane] : 0;
+                    src = (lane < vw) ? path_vertex(records, sp.block_words, vw, lifted_word<LDS_HDR>(hdr2 + s, h2, s), lifted_word<LDS_HDR>(head3_at, h3, s), v)[lane] : 0;
                 }
+                const uint64_t *vslot = rec_words + vbase; /* LDS_HDR: the vertex's words in the slot */
                 const double *table = SPDS_IN_LDS ? (const double *)lds : sc.spds;
                 double contribution[NSETS];
 #pragma unroll
@@ -2993,11 +3144,11 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                             if (off + REC_LIGHT_WORDS <= 64 || v < n_fast)
                             {
 #pragma unroll
-                                for (int k = 0; k < 4; k += 1) lw[k] = readlane64(src, lane0 + off + k);
+                                for (int k = 0; k < 4; k += 1) lw[k] = lifted_word<LDS_HDR>(vslot + off + k, src, lane0 + off + k);
                             }
                             else
                             {
-                                const uint64_t *lp = path_vertex(records, sp.block_words, vw, readlane64(h2, s), readlane64(h3, s), v) + off;
+                                const uint64_t *lp = path_vertex(records, sp.block_words, vw, lifted_word<LDS_HDR>(hdr2 + s, h2, s), lifted_word<LDS_HDR>(head3_at, h3, s), v) + off;
 #pragma unroll
                                 for (int k = 0; k < 4; k += 1) lw[k] = readlane64(lp[k], 0);
                             }
@@ -3026,20 +3177,20 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 };
                 if (v < 16u && ((plastic_mask >> v) & 1u))
                 {
-                    const uint64_t w1p = readlane64(src, lane0 + 1);
+                    const uint64_t w1p = lifted_word<LDS_HDR>(vslot + 1, src, lane0 + 1);
                     if (v < n_fast)
                     {
                         const uint64_t *vwords = rec_words + v * vw;
                         plastic_vertex(w1p, word_as_double(vwords[4]), word_as_double(vwords[5]), word_as_double(vwords[6]));
                         continue;
                     }
-                    const double dir_pdf_p = word_as_double(readlane64(src, lane0 + 4));
-                    const double s_a_in_p = word_as_double(readlane64(src, lane0 + 5)), s_spec_p = word_as_double(readlane64(src, lane0 + 6));
+                    const double dir_pdf_p = lifted_double<LDS_HDR>(vslot + 4, src, lane0 + 4);
+                    const double s_a_in_p = lifted_double<LDS_HDR>(vslot + 5, src, lane0 + 5), s_spec_p = lifted_double<LDS_HDR>(vslot + 6, src, lane0 + 6);
                     plastic_vertex(w1p, dir_pdf_p, s_a_in_p, s_spec_p);
                     continue;
                 }
-                const uint64_t list = readlane64(src, lane0 + 0);
-                const uint64_t w1 = readlane64(src, lane0 + 1);
+                const uint64_t list = lifted_word<LDS_HDR>(vslot + 0, src, lane0 + 0);
+                const uint64_t w1 = lifted_word<LDS_HDR>(vslot + 1, src, lane0 + 1);
                 const uint32_t num_bdsfs = (uint32_t)(w1 & 0xFFu);
                 const uint32_t sflags = (uint32_t)(w1 >> 8) & 0xFFu;
                 /* The specular lists, straight-line: bdsf_at_wavelength's fixed-list form, so no loop and no switch per evaluation, and
@@ -3057,8 +3208,8 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                     const bool fresnel = !SIMPLE && kind != 0u;
                     constexpr bool GGX_BODY = CLOSED; /* the general instantiations keep the general loop for the rough conductor */
                     const bool rough = GGX_BODY && kind == 3u;
-                    const bool in_lds = v < n_fast;
-                    const uint64_t *vwords = rec_words + v * vw;
+                    const bool in_lds = LDS_HDR || v < n_fast;
+                    const uint64_t *vwords = rec_words + (LDS_HDR ? vbase : v * vw);
                     uint32_t i_r0 = (uint32_t)(w1 >> 48) & 0xFFFFu, i_r1 = 0, i_r2 = 0; /* the mirror's one row, or the three Fresnel rows */
                     bool paired = false;
                     double on_dot = 0.0; /* the cosine the Fresnel term is taken at: on_dot, or the rough conductor's mn_dot */
@@ -3068,8 +3219,8 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                     for (int k = 0; k < NSETS; k += 1) r1[k] = r2[k] = 0.0;
                     if (fresnel)
                     {
-                        fresnel_rows(readlane64(src, lane0 + 2), i_r0, i_r1, i_r2, paired);
-                        if (!rough) on_dot = in_lds ? word_as_double(vwords[3]) : word_as_double(readlane64(src, lane0 + 3));
+                        fresnel_rows(lifted_word<LDS_HDR>(vslot + 2, src, lane0 + 2), i_r0, i_r1, i_r2, paired);
+                        if (!rough) on_dot = in_lds ? word_as_double(vwords[3]) : lifted_double<LDS_HDR>(vslot + 3, src, lane0 + 3);
 #pragma unroll
                         for (int k = 0; k < NSETS; k += 1)
                         {
@@ -3097,18 +3248,18 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                         double c;
                         if (off + REC_LIGHT_WORDS <= 64 || v < n_fast)
                         {
-                            lw0 = readlane64(src, lane0 + off);
-                            c = in_lds ? word_as_double(vwords[off + 1u]) : word_as_double(readlane64(src, lane0 + off + 1u));
+                            lw0 = lifted_word<LDS_HDR>(vslot + off, src, lane0 + off);
+                            c = in_lds ? word_as_double(vwords[off + 1u]) : lifted_double<LDS_HDR>(vslot + off + 1u, src, lane0 + off + 1u);
                             if (rough)
                             {
-                                on_dot = in_lds ? word_as_double(vwords[off + 4u]) : word_as_double(readlane64(src, lane0 + off + 4u));
-                                ct = in_lds ? word_as_double(vwords[off + 5u]) : word_as_double(readlane64(src, lane0 + off + 5u));
+                                on_dot = in_lds ? word_as_double(vwords[off + 4u]) : lifted_double<LDS_HDR>(vslot + off + 4u, src, lane0 + off + 4u);
+                                ct = in_lds ? word_as_double(vwords[off + 5u]) : lifted_double<LDS_HDR>(vslot + off + 5u, src, lane0 + off + 5u);
                             }
                         }
                         else
                         {
                             /* light block beyond the register: uniform loads straight from the record */
-                            const uint64_t *lp = path_vertex(records, sp.block_words, vw, readlane64(h2, s), readlane64(h3, s), v) + off;
+                            const uint64_t *lp = path_vertex(records, sp.block_words, vw, lifted_word<LDS_HDR>(hdr2 + s, h2, s), lifted_word<LDS_HDR>(head3_at, h3, s), v) + off;
                             lw0 = readlane64(lp[0], 0);
                             c = word_as_double(lp[1]);
                             if (rough)
@@ -3131,15 +3282,15 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                     }
                     if (rough) /* the sampled direction's mn_dot and ct_coef */
                     {
-                        on_dot = in_lds ? word_as_double(vwords[7]) : word_as_double(readlane64(src, lane0 + 7));
-                        ct = in_lds ? word_as_double(vwords[8]) : word_as_double(readlane64(src, lane0 + 8));
+                        on_dot = in_lds ? word_as_double(vwords[7]) : lifted_double<LDS_HDR>(vslot + 7, src, lane0 + 7);
+                        ct = in_lds ? word_as_double(vwords[8]) : lifted_double<LDS_HDR>(vslot + 8, src, lane0 + 8);
                     }
 #pragma unroll
                     for (int k = 0; k < NSETS; k += 1)
                     {
                         dst[k] = dst[k] + throughput[k] * contribution[k]; /* :461-462 */
                         double reflectance = eval(k, sflags);
-                        const double dir_pdf = in_lds ? word_as_double(vwords[4]) : word_as_double(readlane64(src, lane0 + 4));
+                        const double dir_pdf = in_lds ? word_as_double(vwords[4]) : lifted_double<LDS_HDR>(vslot + 4, src, lane0 + 4);
                         reflectance = reflectance * dir_pdf;         /* :468 */
                         throughput[k] = throughput[k] * reflectance; /* :469 */
                     }
@@ -3148,7 +3299,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                 {
                     /* every list of the scene is covered: a plastic vertex beyond the header's 16 flags, or one of the four fixed kinds */
                     if (sflags & FLAG_PLASTIC)
-                        plastic_vertex(w1, word_as_double(readlane64(src, lane0 + 4)), word_as_double(readlane64(src, lane0 + 5)), word_as_double(readlane64(src, lane0 + 6)));
+                        plastic_vertex(w1, lifted_double<LDS_HDR>(vslot + 4, src, lane0 + 4), lifted_double<LDS_HDR>(vslot + 5, src, lane0 + 5), lifted_double<LDS_HDR>(vslot + 6, src, lane0 + 6));
                     else
                         fixed_vertex(list == DRT_LIST_MIRROR ? 0u : list == DRT_LIST_GLASS ? 1u : list == DRT_LIST_CONDUCTOR ? 2u : 3u);
                     continue;
@@ -3165,15 +3316,15 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                         continue;
                     }
                 }
-                const uint64_t w2 = readlane64(src, lane0 + 2);
-                const double on_dot = word_as_double(readlane64(src, lane0 + 3));
-                const double dir_pdf = word_as_double(readlane64(src, lane0 + 4));
+                const uint64_t w2 = lifted_word<LDS_HDR>(vslot + 2, src, lane0 + 2);
+                const double on_dot = lifted_double<LDS_HDR>(vslot + 3, src, lane0 + 3);
+                const double dir_pdf = lifted_double<LDS_HDR>(vslot + 4, src, lane0 + 4);
                 const uint32_t i_diffuse = (uint32_t)(w1 >> 16) & 0xFFFFu, i_glossy = (uint32_t)(w1 >> 32) & 0xFFFFu;
                 const uint32_t i_mirror = (uint32_t)(w1 >> 48) & 0xFFFFu;
                 uint32_t i_ir, i_tr, i_te; /* or the pair's rows in their place */
                 bool paired;               /* wave-uniform: the record word came through v_readlane */
                 fresnel_rows(w2, i_ir, i_tr, i_te, paired);
-                const double s_a_in = word_as_double(readlane64(src, lane0 + 5)), s_spec = word_as_double(readlane64(src, lane0 + 6));
+                const double s_a_in = lifted_double<LDS_HDR>(vslot + 5, src, lane0 + 5), s_spec = lifted_double<LDS_HDR>(vslot + 6, src, lane0 + 6);
 
                 if (sflags & FLAG_PLASTIC) /* a plastic vertex beyond the header's 16 flags */
                 {
@@ -3198,12 +3349,12 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                     if (off + REC_LIGHT_WORDS <= 64 || v < n_fast)
                     {
 #pragma unroll
-                        for (int k = 0; k < REC_LIGHT_WORDS; k += 1) lw[k] = readlane64(src, lane0 + off + k);
+                        for (int k = 0; k < REC_LIGHT_WORDS; k += 1) lw[k] = lifted_word<LDS_HDR>(vslot + off + k, src, lane0 + off + k);
                     }
                     else
                     {
                         /* light block beyond the register: uniform loads straight from the record */
-                        const uint64_t *lp = path_vertex(records, sp.block_words, vw, readlane64(h2, s), readlane64(h3, s), v) + off;
+                        const uint64_t *lp = path_vertex(records, sp.block_words, vw, lifted_word<LDS_HDR>(hdr2 + s, h2, s), lifted_word<LDS_HDR>(head3_at, h3, s), v) + off;
 #pragma unroll
                         for (int k = 0; k < REC_LIGHT_WORDS; k += 1) lw[k] = readlane64(lp[k], 0);
                     }
@@ -3222,7 +3373,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                         contribution[k] = contribution[k] * c;                                /* :326-327 */
                     }
                 }
-                const double s_mn = word_as_double(readlane64(src, lane0 + 7)), s_ct = word_as_double(readlane64(src, lane0 + 8));
+                const double s_mn = lifted_double<LDS_HDR>(vslot + 7, src, lane0 + 7), s_ct = lifted_double<LDS_HDR>(vslot + 8, src, lane0 + 8);
 #pragma unroll
                 for (int k = 0; k < NSETS; k += 1)
                 {
@@ -3233,6 +3384,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
                     throughput[k] = throughput[k] * reflectance; /* :469 */
                 }
             }
+            if constexpr (LDS_HDR) fetch_headers(s + 1u); /* the next sample's header words travel while the film update runs */
             const double denom = (double)(first + s0 + s + 1);
             if (DARK) dark = false; /* (a sample that gets this far may leave something in the accumulators) */
 #pragma unroll
@@ -3307,7 +3459,11 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
         }
       }
 
-        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, lane, CLOSED);
+        if constexpr (LDS_HDR)
+        {
+            __builtin_amdgcn_wave_barrier(); /* the main pass's reads of the region are in order before the tail pass's writes */
+        }
+        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, made_again<LDS_HDR>(lane), CLOSED, LDS_HDR);
     }
 }
 
@@ -3336,6 +3492,25 @@ __global__ __launch_bounds__(SHADE_BLOCK, DRT_SHADE_WAVES_CLOSED) void drt_shade
 {
     shade_pixels<1, true, false, DARK, false, false, true>(sc, sp, records, headers, film_pixels, film_avgs, film_vars, work_counter);
 }
+
+/* The closed instantiation with the window's headers and one record slot in LDS (shade_pixels, CLOSED_LDS): the kernel a closed context
+ * launches where five workgroups fit a compute unit's LDS beside the table (drt_shade_lds_rule.h; the launcher, shade_closed_lds()).
+ * Five waves: 92 registers (93 without DARK), nothing spilled; shade 66.3 -> 55.1 ms on the headline. drt_shade_kernel_closed above
+ * stays what it was, instruction for instruction: what runs where five workgroups do not fit, and with DRT_NO_CLOSED_LDS=1 -- the A/B
+ * against this kernel from one library. (It never had a fifth wave resident when forced to five: its LDS allows four workgroups.) */
+#ifndef DRT_SHADE_WAVES_CLOSED_LDS
+#define DRT_SHADE_WAVES_CLOSED_LDS 5
+#endif
+#if DRT_SHADE_CLOSED_LDS_HEADERS
+template <bool DARK>
+__global__ __launch_bounds__(SHADE_BLOCK, DRT_SHADE_WAVES_CLOSED_LDS) void drt_shade_kernel_closed_lds(DevScene sc, ShadeParams sp, const uint64_t *__restrict__ records,
+                                                                 const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
+                                                                 double *__restrict__ film_avgs, double *__restrict__ film_vars,
+                                                                 unsigned long long *__restrict__ work_counter)
+{
+    shade_pixels<1, true, false, DARK, false, false, true, true>(sc, sp, records, headers, film_pixels, film_avgs, film_vars, work_counter);
+}
+#endif
 
 /* spectrum_to_xyz over the film (src/daily_ray_trace.c:15-23, src/spectrum.c:49-70): one thread per
  * pixel so the sums run in the reference's order. */

@@ -21,6 +21,7 @@
 #include "drt_window_kernels.h"
 #include "drt_window_rule.h"
 #include "drt_pair_rule.h"
+#include "drt_shade_lds_rule.h"
 #include "drt_owned.h"
 
 #include <algorithm>
@@ -150,6 +151,8 @@ struct drt_context
 
     bool   scene_in_lds = true, spds_in_lds = true, use_bvh = false;
     size_t trace_lds = 0, shade_lds = 0;
+    size_t shade_lds_closed = 0; /* dynamic LDS of drt_shade_kernel_closed_lds, whose waves have a region of their own size (shade_lds: every other shade kernel) */
+    bool   closed_lds = false;   /* a closed context launches drt_shade_kernel_closed_lds: five of its workgroups fit a compute unit's LDS, and DRT_NO_CLOSED_LDS was not set when the context was created */
     bool trace_stash = false; /* camera launches run the stash form, drt_trace_kernel, with TRACE_STASH_BYTES of LDS behind trace_lds; else drt_trace_direct_kernel */
     int    trace_grid_cap = 0, shade_grid_cap = 0;
     uint32_t trace_chunk_override = 0; /* DRT_TRACE_CHUNK tuning knob */
@@ -929,16 +932,27 @@ static bool shade_closed(const drt_context *ctx)
     return ctx->closed_lists && !ctx->no_closed_shade && !ctx->no_fixed_lists && !shade_simple(ctx) && ctx->spds_in_lds && ctx->shade_sets == 1 && !ctx->xyz_mode;
 }
 
+/* ... and of the closed kernel's two forms the one with headers and one record slot in LDS, five waves per SIMD (create_impl decides) */
+static bool shade_closed_lds(const drt_context *ctx) { return DRT_SHADE_CLOSED_LDS_HEADERS != 0 && ctx->closed_lds && shade_closed(ctx); }
+
 template <int NSETS, bool XYZ, bool LIST>
 static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams &sp, double *const film[3])
 {
     if (NSETS == 1 && !XYZ && !LIST && shade_closed(ctx))
     {
-#define DRT_LAUNCH_CLOSED(DARK)                                                                                                                    \
-    hipLaunchKernelGGL((drt_shade_kernel_closed<DARK>), dim3(grid), dim3(SHADE_BLOCK), ctx->shade_lds, ctx->stream, ctx->dsc, sp, ctx->d_records, \
+#define DRT_LAUNCH_CLOSED(KERNEL, DARK, LDS_BYTES)                                                                                                 \
+    hipLaunchKernelGGL((KERNEL<DARK>), dim3(grid), dim3(SHADE_BLOCK), LDS_BYTES, ctx->stream, ctx->dsc, sp, ctx->d_records, \
                        ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
-        if (shade_dark(ctx, sp)) DRT_LAUNCH_CLOSED(true);
-        else DRT_LAUNCH_CLOSED(false);
+#if DRT_SHADE_CLOSED_LDS_HEADERS
+        if (shade_closed_lds(ctx))
+        {
+            if (shade_dark(ctx, sp)) DRT_LAUNCH_CLOSED(drt_shade_kernel_closed_lds, true, ctx->shade_lds_closed);
+            else DRT_LAUNCH_CLOSED(drt_shade_kernel_closed_lds, false, ctx->shade_lds_closed);
+            return 0;
+        }
+#endif
+        if (shade_dark(ctx, sp)) DRT_LAUNCH_CLOSED(drt_shade_kernel_closed, true, ctx->shade_lds);
+        else DRT_LAUNCH_CLOSED(drt_shade_kernel_closed, false, ctx->shade_lds);
 #undef DRT_LAUNCH_CLOSED
         return 0;
     }
@@ -1192,8 +1206,14 @@ template <int NSETS, bool XYZ>
 static int shade_occupancy_mode(drt_context *ctx, int *per_cu)
 {
     /* (the DARK instantiations have the same registers and LDS) */
-    /* (a closed context's adaptive rounds launch the general LIST instantiation on the same grid cap: both are bound at four waves;
-     * were the bounds to differ, blocks beyond what is resident would only queue behind the persistent ones and find the work gone) */
+    /* (a closed context's adaptive rounds launch the general LIST instantiation on the same grid cap, with its own LDS size: the closed
+     * kernel is bound at five waves, the general one at four, so a workgroup in five of such a round only queues behind the
+     * persistent ones and finds the work gone) */
+#if DRT_SHADE_CLOSED_LDS_HEADERS
+    if (NSETS == 1 && !XYZ && shade_closed_lds(ctx))
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, drt_shade_kernel_closed_lds<true>, SHADE_BLOCK, ctx->shade_lds_closed));
+    else
+#endif
     if (NSETS == 1 && !XYZ && shade_closed(ctx))
         HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, drt_shade_kernel_closed<true>, SHADE_BLOCK, ctx->shade_lds));
     else if (NSETS == 1 && shade_simple(ctx))
@@ -1442,9 +1462,15 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         ctx->bounce_grid_cap = prop.multiProcessorCount * std::max(1, b_cu);
     }
     /* shade kernel LDS: SPD tables + two record buffers per wave */
-    ctx->shade_lds = ctx->spds_in_lds ? (size_t)ctx->dsc.n_spd * S * 8 : 0;
-    ctx->shade_lds += (size_t)SHADE_WAVES * SHADE_WAVE_LDS_WORDS * 8; /* a wave's own region: two record slots in the main pass (the coefficient words of plastic
-                                                                          vertices are read back from them), a window of headers in the tail pass */
+    /* (drt_shade_lds_rule.h) a wave's own region: two record slots in the main pass (the coefficient words of plastic vertices are read
+     * back from them), a window of headers in the tail pass; the closed instantiation's: one slot and the window's headers */
+    const ShadeLdsPlan lds_general = shade_lds_plan(ctx->dsc.n_spd, S, ctx->spds_in_lds, SHADE_WAVES, SHADE_WAVE_LDS_WORDS_FOR(false), DRT_SHADE_WAVES_PER_SIMD);
+    const ShadeLdsPlan lds_closed = shade_lds_plan(ctx->dsc.n_spd, S, ctx->spds_in_lds, SHADE_WAVES, SHADE_WAVE_LDS_WORDS_FOR(true), DRT_SHADE_WAVES_CLOSED_LDS);
+    ctx->shade_lds = lds_general.group_bytes;
+    ctx->shade_lds_closed = lds_closed.group_bytes;
+    /* the form with headers in LDS is there for its fifth wave: where five workgroups do not fit beside the table, the closed kernel
+     * with the headers in registers runs, as it does with DRT_NO_CLOSED_LDS=1 (the A/B of the two from one library) */
+    ctx->closed_lds = lds_closed.groups >= DRT_SHADE_WAVES_CLOSED_LDS * SHADE_SIMDS_PER_CU / SHADE_WAVES && getenv("DRT_NO_CLOSED_LDS") == nullptr;
     int s_per_cu = 0;
     shade_sets(S, &ctx->shade_sets, &ctx->tail_first, &ctx->tail_count);
     switch (ctx->shade_sets)
@@ -1455,6 +1481,10 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         default: rc = shade_occupancy<4>(ctx, &s_per_cu); break;
     }
     if (rc) return rc;
+    const int s_query = s_per_cu; /* what the runtime's occupancy query said */
+    /* the closed kernel's grid never counts on more resident workgroups than the LDS rule allows (its register bound asks for one
+     * more than the other instantiations': that one must also fit) */
+    if (shade_closed_lds(ctx)) s_per_cu = std::min(s_per_cu, (int)lds_closed.groups);
     if (s_per_cu < 1) s_per_cu = 1;
     if (const char *e = getenv("DRT_SHADE_BLOCKS_PER_CU")) s_per_cu = std::max(1, atoi(e)); /* tuning knob */
     ctx->shade_grid_cap = prop.multiProcessorCount * s_per_cu;
@@ -1600,8 +1630,10 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     if (ctx->tail_count && ctx->tail_resume) HIP_TRY(ctx->d_tail_resume.need((size_t)npx * batch * ctx->tail_count));
     if (const char *e = getenv("DRT_DARK_SKIP")) ctx->dark_skip = ctx->dark_skip_win = atoi(e) != 0; /* A/B switch of the parity tests: same film either way */
     if (getenv("DRT_VERBOSE"))
-        fprintf(stderr, "drt: %d CUs, trace %d blocks/CU (lds %zu), shade %d blocks/CU (lds %zu), batch %u, %.3f blocks/path measured (worst %u), pool %.2f GB\n",
-                prop.multiProcessorCount, per_cu, ctx->trace_lds, s_per_cu, ctx->shade_lds, ctx->batch_spp, ctx->est_blocks_per_path,
+        fprintf(stderr, "drt: %d CUs, trace %d blocks/CU (lds %zu), shade %d blocks/CU (%s, occupancy query %d, lds %zu; LDS rule: general %u, closed %u of %zu bytes), batch %u, %.3f blocks/path measured (worst %u), pool %.2f GB\n",
+                prop.multiProcessorCount, per_cu, ctx->trace_lds, s_per_cu, shade_closed_lds(ctx) ? "closed, headers in LDS" : shade_closed(ctx) ? "closed" : "general", s_query,
+                shade_closed_lds(ctx) ? ctx->shade_lds_closed : ctx->shade_lds, lds_general.groups_by_lds, lds_closed.groups_by_lds, lds_closed.group_bytes,
+                ctx->batch_spp, ctx->est_blocks_per_path,
                 ctx->worst_blocks_per_path, (double)(ctx->pool_blocks * block_bytes) / 1e9);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return 0;
@@ -2333,6 +2365,12 @@ extern "C" int drt_shade_instantiation(const drt_context *ctx)
     if (!ctx) return -1;
     if (shade_closed(ctx)) return DRT_SHADE_CLOSED;
     return shade_simple(ctx) ? DRT_SHADE_SIMPLE : DRT_SHADE_GENERAL;
+}
+
+extern "C" int drt_shade_closed_lds(const drt_context *ctx)
+{
+    if (!ctx) return -1;
+    return shade_closed_lds(ctx) ? 1 : 0;
 }
 
 /*

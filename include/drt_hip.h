@@ -267,6 +267,9 @@ uint32_t drt_batch_spp(drt_context *ctx);
 #define DRT_SHADE_SIMPLE 1
 #define DRT_SHADE_CLOSED 2
 int drt_shade_instantiation(const drt_context *ctx);
+/* 1: the context's dense launches run the closed instantiation's form with window headers in LDS, five waves per SIMD
+ * (drt_shade_kernel_closed_lds); 0: any other kernel; -1: null context */
+int drt_shade_closed_lds(const drt_context *ctx);
 
 /*
  * One-shot form matching the reference's loop: host buffers, caller-owned,

@@ -51,11 +51,13 @@ GROUPS = {"features": ("drt_feature_kernel", "drt_feature_bvh_kernel", "drt_feat
 _NOT_VALU = ("v_nop", "v_interp")
 
 
-def device_asm(extra=()):
-    """The gfx950 assembly of csrc/drt_launcher.hip as text."""
+def device_asm(extra=(), source=None):
+    """The gfx950 assembly of csrc/drt_launcher.hip as text; `source`: of that file instead (one that includes the kernels' headers and
+    instantiates a few of them compiles in seconds where the whole library takes minutes)."""
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "drt.s")
-        cmd = [HIPCC] + FLAGS + ["--cuda-device-only", "-S", "-gline-tables-only", os.path.join(PKG, "csrc", "drt_launcher.hip"), "-o", out] + list(extra)
+        src = source or os.path.join(PKG, "csrc", "drt_launcher.hip")
+        cmd = [HIPCC] + FLAGS + ["-I" + os.path.join(PKG, "csrc"), "--cuda-device-only", "-S", "-gline-tables-only", src, "-o", out] + list(extra)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])
@@ -183,9 +185,9 @@ def _wait_stats(body):
     return loops, main
 
 
-def kernel_stats(extra=(), asm=None):
+def kernel_stats(extra=(), asm=None, source=None):
     """{demangled kernel name: figures}; see the module's docstring for what they are."""
-    asm = asm if asm is not None else device_asm(extra)
+    asm = asm if asm is not None else device_asm(extra, source)
     meta = _metadata(asm)
     lines = asm.splitlines()
     names = _demangle(list(meta))
