@@ -2337,11 +2337,15 @@ static_assert(3u * SHADE_CLOSED_TAIL_ENTRIES + SHADE_CLOSED_TAIL_ENTRIES / 4u <=
  * arithmetic in the same order. It is a work item of the shade kernel's queue, sharing the SIMDs with main-pass waves
  * (as a kernel of its own, at 4 to 8 waves per SIMD, it was 12-27 ms slower: measured).
  */
+/* (a member of ShadeTail<LEAN>: LEAN is the six-wave closed kernel's leaner cursor, see below; every other instantiation is ShadeTail<false>) */
+template <bool LEAN>
+struct ShadeTail
+{
 template <bool SPDS_IN_LDS, bool XYZ, bool SIMPLE, bool LIST = false>
 __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const ShadeParams &sp, const double *lds, uint64_t *wave_lds, const uint64_t *__restrict__ records,
                                                  const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                                  double *__restrict__ film_avgs, double *__restrict__ film_vars, uint64_t chunk_base,
-                                                 uint64_t chunk_end, uint32_t lane, const bool closed, const bool closed_lds = false)
+                                                 uint64_t chunk_end, uint32_t lane, const bool closed, const bool closed_lds = false) const
 {
     const uint32_t S = sc.S;
     const uint32_t vw = sp.vertex_words;
@@ -2386,7 +2390,13 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
     uint64_t slot = 0; /* the path's header / staging slot: pixel * batch + sample */
     const uint64_t *vcur = records; /* the record of vertex v */
     const bool one_light = sp.n_lights == 1u;
-    const double em0 = spd_at(table, S, one_light ? sp.light0_em_spd : 0u, lam); /* light 0's emission at this lane's wavelength */
+    const double em0_held = LEAN ? 0.0 : spd_at(table, S, one_light ? sp.light0_em_spd : 0u, lam); /* light 0's emission at this lane's wavelength */
+    /* LEAN (the six-wave form, where a path's cursor has fewer registers): what the window's entry in the wave's region still holds is
+     * read from there where it is used -- the vignette when the path closes, block word 2 at a block's end -- and light 0's emission
+     * from the table at every lit vertex; the cursor keeps the entry's index e_cur in their place. Same values, same operations. */
+    uint32_t e_cur = 0;
+#define TAIL_EM0 (LEAN ? spd_at(table, S, one_light ? sp.light0_em_spd : 0u, made_again<LEAN>(lam)) : em0_held)
+#define TAIL_PH2 (LEAN ? wave_lds[e_cur * 3u + 2u] : ph2)
     /* header word 3 (the blocks of vertices 8 and up) is fetched when a path gets that far */
     auto deep_blocks = [&](uint32_t vertex) -> uint64_t { return vertex >= 2u * REC_BLOCK_VERTICES ? headers[slot * REC_HEADER_WORDS + 3] : 0ull; };
     for (uint32_t s0 = sp.tail_staged ? sp.n_samples : 0u; s0 < sp.n_samples; s0 += win) /* tail_staged: nothing to replay, drt_trace_kernel<true, true> staged every sample */
@@ -2452,8 +2462,12 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     const uint32_t ge = e / n_win, off = e - ge * n_win;
                     slot = (chunk_base + ge) * (uint64_t)sp.batch + s0 + off;
                     ph0 = w[0];
+                    if constexpr (LEAN) e_cur = e;
+                    else
+                    {
                     vignette = word_as_double(w[1]);
                     ph2 = w[2];
+                    }
                     n_shaded = (uint32_t)(ph0 & 0xFFFFu);
                     /* the vertex to start from: 0, or the one at which the trace kernel stopped carrying this path's tail wavelengths. What
                      * it had by then is the same operations in the same order as the steps below, so the replay takes it over: throughput
@@ -2469,9 +2483,9 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                         const double *at = sp.tail_stage + (slot * R + j);
                         dst = at[0];
                         throughput = at[shade_const().sp.tail_resume - sp.tail_stage];
-                        vcur = path_vertex(records, sp.block_words, vw, ph2, deep_blocks(k), k);
+                        vcur = path_vertex(records, sp.block_words, vw, LEAN ? w[2] : ph2, deep_blocks(k), k);
                     }
-                    else vcur = records + (uint64_t)(uint32_t)ph2 * sp.block_words; /* vertex 0 opens the header's first block */
+                    else vcur = records + (uint64_t)(uint32_t)(LEAN ? w[2] : ph2) * sp.block_words; /* vertex 0 opens the header's first block */
                     busy = true;
                 }
                 next_task += (uint32_t)__popcll(want);
@@ -2504,7 +2518,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                             double reflectance = diffuse_pi * a_in + 0.0;
                             reflectance = (glossy * spec) * a_in + reflectance;
                             contribution = contribution + reflectance;
-                            contribution = contribution * em0;
+                            contribution = contribution * TAIL_EM0;
                             contribution = contribution * c;
                         }
                     }
@@ -2519,7 +2533,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                         double reflectance = diffuse_pi * a_in + 0.0;
                         reflectance = (glossy * spec) * a_in + reflectance;
                         double lit = 0.0 + reflectance;
-                        lit = lit * em0;
+                        lit = lit * TAIL_EM0;
                         lit = lit * c;
                         contribution = ((uint32_t)(lw0 >> 16) & FLAG_VISIBLE) ? lit : 0.0;
                     }
@@ -2542,7 +2556,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     reflectance = reflectance * dir_pdf;
                     throughput = throughput * reflectance;
                     v += 1;
-                    if (v < n_shaded) vcur = (v & (REC_BLOCK_VERTICES - 1u)) != 0u ? vcur + vw : path_vertex(records, sp.block_words, vw, ph2, deep_blocks(v), v); /* the next record: the one behind, or a new block */
+                    if (v < n_shaded) vcur = (v & (REC_BLOCK_VERTICES - 1u)) != 0u ? vcur + vw : path_vertex(records, sp.block_words, vw, TAIL_PH2, deep_blocks(v), v); /* the next record: the one behind, or a new block */
                 }
             }
             else if (n_general > 0)
@@ -2552,7 +2566,7 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                     /* any BDSF list (also plastic vertices beyond the header's 16 flags) */
                     const uint64_t *vrec = vcur;
                     const uint64_t list = vrec[0], w1 = vrec[1], w2 = vrec[2];
-                    const double on_dot = word_as_double(vrec[3]), dir_pdf = word_as_double(vrec[4]);
+                    const double on_dot = word_as_double(vrec[3]), dir_pdf = LEAN ? 0.0 : word_as_double(vrec[4]); /* (LEAN: fetched behind the lights, below) */
                     const uint32_t num_bdsfs = (uint32_t)(w1 & 0xFFu);
                     const uint32_t sflags = (uint32_t)(w1 >> 8) & 0xFFu;
                     const uint32_t i_diffuse = (uint32_t)(w1 >> 16) & 0xFFFFu, i_glossy = (uint32_t)(w1 >> 32) & 0xFFFFu;
@@ -2584,8 +2598,11 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                             contribution = contribution * word_as_double(lrec[1]);
                         }
                         dst = dst + throughput * contribution;
+                        double dir_pdf_late = 0.0; /* LEAN: not held across the lights' evaluations; it travels during the last one */
+                        if constexpr (LEAN) dir_pdf_late = word_as_double(vrec[4]);
                         double reflectance = eval(sflags, vrec + 5);
-                        reflectance = reflectance * dir_pdf;
+                        if constexpr (LEAN) reflectance = reflectance * dir_pdf_late;
+                        else reflectance = reflectance * dir_pdf;
                         throughput = throughput * reflectance;
                     };
                     const bool glass = !SIMPLE && num_bdsfs == 2u && list == DRT_LIST_GLASS;
@@ -2616,14 +2633,14 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
                                                               word_as_double(a[2]), word_as_double(a[3]), flags, paired);
                         });
                     v += 1;
-                    if (v < n_shaded) vcur = (v & (REC_BLOCK_VERTICES - 1u)) != 0u ? vcur + vw : path_vertex(records, sp.block_words, vw, ph2, deep_blocks(v), v); /* the next record: the one behind, or a new block */
+                    if (v < n_shaded) vcur = (v & (REC_BLOCK_VERTICES - 1u)) != 0u ? vcur + vw : path_vertex(records, sp.block_words, vw, TAIL_PH2, deep_blocks(v), v); /* the next record: the one behind, or a new block */
                 }
             }
             if (busy && v >= n_shaded)
             {
                 /* the path's last vertex is done: close the sample, :452-457 and :615 */
                 if (((uint32_t)(ph0 >> 16) & HDR_TERM_MASK) == 1u) dst = dst + throughput * spd_at(table, S, (uint32_t)(ph0 >> 32) & 0xFFFFu, lam);
-                sp.tail_stage[slot * R + j] = dst * vignette;
+                sp.tail_stage[slot * R + j] = dst * (LEAN ? word_as_double(wave_lds[e_cur * 3u + 1u]) : vignette);
                 busy = false;
             }
         }
@@ -2633,9 +2650,16 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
      * film rows' indices) are made at the kernel's entry and held in vector register pairs through every main-pass item, where
      * there is none to spare */
     uint32_t j_b = j;
+    uint32_t g_b = g;
+    if constexpr (LEAN)
+    {
+        /* ... and made again from the lane number: g's and j's registers are not held through phase A's general step either */
+        const uint32_t lane_b = made_again<true>(lane);
+        g_b = lane_b / R;
+        j_b = lane_b - g_b * R;
+    }
     asm volatile("" : "+v"(j_b));
     const uint32_t lam_b = sp.tail_first + j_b;
-    uint32_t g_b = g;
     asm volatile("" : "+v"(g_b));
     const uint64_t pix_b = chunk_base + g_b;
     const uint64_t pix_f = LIST ? (act ? (uint64_t)sp.pixel_list[pix_b] : 0u) : pix_b; /* its film row */
@@ -2691,14 +2715,17 @@ __device__ __forceinline__ void shade_tail_group(const DevScene &sc, const Shade
         pa[lam_b] = f_avg;
         pv[lam_b] = f_var;
     }
+#undef TAIL_EM0
+#undef TAIL_PH2
 }
+};
 
 
 /* The kernel's body, shared by its two entry points below. CLOSED: every BDSF list of the scene is the two-lobe plastic or one of
  * fixed_vertex's four (the launcher checks, closed_lists()): the general list does not exist, neither in the main pass nor in the tail
  * pass's general step -- its loop, its switch and the registers they hold are not compiled. Same operations in the same order: what
  * is left is the very code the general instantiation runs for these lists (tests/test_gpu_closed_lists.py flips DRT_NO_CLOSED_SHADE). */
-template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE, bool LIST, bool CLOSED, bool CLOSED_LDS = false>
+template <int NSETS, bool SPDS_IN_LDS, bool XYZ, bool DARK, bool SIMPLE, bool LIST, bool CLOSED, bool CLOSED_LDS = false, uint32_t BLOCK = SHADE_BLOCK>
 __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadeParams &sp, const uint64_t *__restrict__ records,
                                              const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
                                              double *__restrict__ film_avgs, double *__restrict__ film_vars,
@@ -2712,13 +2739,16 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
     {
         /* the SPD block [n_spd][S] is contiguous: coalesced copy */
         const uint32_t spd_words = sc.n_spd * S;
-        for (uint32_t k = threadIdx.x; k < spd_words; k += SHADE_BLOCK) lds[k] = sc.spds[k];
+        for (uint32_t k = threadIdx.x; k < spd_words; k += BLOCK) lds[k] = sc.spds[k];
         __syncthreads();
     }
     const uint32_t lane_k = threadIdx.x & 63u;
     /* behind the SPD table: two record slots per wave (see the sample loop) */
     static_assert(!CLOSED_LDS || CLOSED, "the form with headers in LDS is a closed form");
     constexpr bool LDS_HDR = CLOSED_LDS; /* headers and one record slot in LDS (see DRT_SHADE_CLOSED_LDS_HEADERS) */
+    /* the six-wave form (drt_shade_kernel_closed_lds6): a pixel's film rows are wave-uniform addresses, kept on the scalar side, and the
+     * lane's offset into them is made where a row is read or written -- not three 64-bit vector addresses held across the pixel's samples */
+    constexpr bool FILM_SCALAR = LDS_HDR && BLOCK != SHADE_BLOCK;
     uint64_t *rec_lds = (uint64_t *)(lds + (SPDS_IN_LDS ? (size_t)sc.n_spd * S : 0)) + (size_t)(threadIdx.x >> 6) * SHADE_WAVE_LDS_WORDS_FOR(LDS_HDR);
     const uint32_t vw = sp.vertex_words;                 /* power of two >= 16 */
     const uint32_t vpr = vw <= 64 ? 64u / vw : 0u;       /* vertices per 64-word register (0: records wider than a register) */
@@ -2809,6 +2839,14 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
         {
             const uint32_t lam = 64u * k + lane;
             const bool active = lam < S_main;
+            if constexpr (FILM_SCALAR)
+            {
+                const uint32_t at = made_again<true>(lane) * 8u;
+                f_sum[k] = active ? *(const double *)((const char *)px + at) : 0.0;
+                f_avg[k] = active ? *(const double *)((const char *)pa + at) : 0.0;
+                f_var[k] = active ? *(const double *)((const char *)pv + at) : 0.0;
+                continue;
+            }
             f_sum[k] = (active && !XYZ) ? px[lam] : 0.0;
             f_avg[k] = (active && !XYZ) ? pa[lam] : 0.0;
             f_var[k] = (active && !XYZ) ? pv[lam] : 0.0;
@@ -3448,6 +3486,17 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
             for (int k = 0; k < NSETS; k += 1)
             {
                 const uint32_t lam = 64u * k + lane;
+                if constexpr (FILM_SCALAR)
+                {
+                    const uint32_t at = made_again<true>(lane) * 8u;
+                    if (lam < S_main)
+                    {
+                        *(double *)((char *)px + at) = f_sum[k];
+                        *(double *)((char *)pa + at) = f_avg[k];
+                        *(double *)((char *)pv + at) = f_var[k];
+                    }
+                    continue;
+                }
                 if (lam < S_main)
                 {
                     px[lam] = f_sum[k];
@@ -3463,7 +3512,7 @@ __device__ __forceinline__ void shade_pixels(const DevScene &sc, const ShadePara
         {
             __builtin_amdgcn_wave_barrier(); /* the main pass's reads of the region are in order before the tail pass's writes */
         }
-        if (tail_item && sp.mode != 1u) shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, made_again<LDS_HDR>(lane), CLOSED, LDS_HDR);
+        if (tail_item && sp.mode != 1u) ShadeTail<FILM_SCALAR>{}.template shade_tail_group<SPDS_IN_LDS, XYZ, SIMPLE, LIST>(sc, sp, (const double *)lds, rec_lds, records, headers, film_pixels, film_avgs, film_vars, chunk_base, chunk_end, made_again<LDS_HDR>(lane), CLOSED, LDS_HDR);
     }
 }
 
@@ -3509,6 +3558,31 @@ __global__ __launch_bounds__(SHADE_BLOCK, DRT_SHADE_WAVES_CLOSED_LDS) void drt_s
                                                                  unsigned long long *__restrict__ work_counter)
 {
     shade_pixels<1, true, false, DARK, false, false, true, true>(sc, sp, records, headers, film_pixels, film_avgs, film_vars, work_counter);
+}
+
+/* The same form at six waves per SIMD (shade_pixels, CLOSED_LDS, BLOCK = 512): the kernel a closed context's dense launches run where
+ * the runtime grants three of its workgroups per compute unit (the launcher, shade_closed_lds6(); DRT_CLOSED_WAVES=5 keeps the kernel
+ * above -- the A/B from one library). Two things held the form at five. LDS: every workgroup stages the table, and a sixth workgroup
+ * of four waves does not fit beside five copies of 38 rows; eight waves behind ONE copy do, three workgroups to a compute unit
+ * (drt_shade_lds_rule.h). Work items are drawn per wave, so the queue does not see the workgroup's size. Registers: at the bound of 80
+ * the body above spilled 14-16 dwords. The main pass's six were the pixel's three film-row addresses, wave-uniform bases plus the lane
+ * -- here they stay scalar and the lane's offset is made at the read and at the write (FILM_SCALAR). The tail pass's ten went with a
+ * leaner cursor (ShadeTail<true>): vignette, block word 2 and light 0's emission are read back from LDS where they are used, a
+ * general vertex's dir_pdf is fetched behind its lights, phase B makes its indices again from the lane. 79 registers (80 with DARK),
+ * nothing spilled, no scratch. Same operations in the same order: same films, bit for bit (tests/test_gpu_shade_six_waves.py).
+ * The two kernels above compile to the instructions they had. Measurements: DESIGN.md sections 4 and 7. */
+#define SHADE_BLOCK_CLOSED_LDS6 512
+#define SHADE_WAVES_CLOSED_LDS6 (SHADE_BLOCK_CLOSED_LDS6 / 64)
+#ifndef DRT_SHADE_WAVES_CLOSED_LDS6
+#define DRT_SHADE_WAVES_CLOSED_LDS6 6
+#endif
+template <bool DARK>
+__global__ __launch_bounds__(SHADE_BLOCK_CLOSED_LDS6, DRT_SHADE_WAVES_CLOSED_LDS6) void drt_shade_kernel_closed_lds6(DevScene sc, ShadeParams sp, const uint64_t *__restrict__ records,
+                                                                 const uint64_t *__restrict__ headers, double *__restrict__ film_pixels,
+                                                                 double *__restrict__ film_avgs, double *__restrict__ film_vars,
+                                                                 unsigned long long *__restrict__ work_counter)
+{
+    shade_pixels<1, true, false, DARK, false, false, true, true, SHADE_BLOCK_CLOSED_LDS6>(sc, sp, records, headers, film_pixels, film_avgs, film_vars, work_counter);
 }
 #endif
 

@@ -154,6 +154,10 @@ struct drt_context
     size_t shade_lds_closed = 0; /* dynamic LDS of drt_shade_kernel_closed_lds, whose waves have a region of their own size (shade_lds: every other shade kernel) */
     bool   closed_lds = false;   /* a closed context launches drt_shade_kernel_closed_lds: five of its workgroups fit a compute unit's LDS, and DRT_NO_CLOSED_LDS was not set when the context was created */
     bool trace_stash = false; /* camera launches run the stash form, drt_trace_kernel, with TRACE_STASH_BYTES of LDS behind trace_lds; else drt_trace_direct_kernel */
+    size_t shade_lds_closed6 = 0; /* dynamic LDS of drt_shade_kernel_closed_lds6: one table and eight wave regions */
+    bool   closed_lds6 = false;   /* a closed context's dense launches run drt_shade_kernel_closed_lds6, six waves per SIMD: the occupancy query gave three of its 512-lane
+                                     workgroups per compute unit, and DRT_CLOSED_WAVES did not ask for fewer when the context was created */
+    int    shade_grid_cap6 = 0;   /* ... and their persistent grid (shade_grid_cap: every other shade launch, the context's adaptive rounds among them) */
     int    trace_grid_cap = 0, shade_grid_cap = 0;
     uint32_t trace_chunk_override = 0; /* DRT_TRACE_CHUNK tuning knob */
     ShadeOverrides shade_overrides;    /* DRT_SHADE_CHUNK, DRT_SHADE_SUBS, DRT_TAIL_PERIOD tuning knobs (drt_pair_rule.h) */
@@ -934,6 +938,11 @@ static bool shade_closed(const drt_context *ctx)
 
 /* ... and of the closed kernel's two forms the one with headers and one record slot in LDS, five waves per SIMD (create_impl decides) */
 static bool shade_closed_lds(const drt_context *ctx) { return DRT_SHADE_CLOSED_LDS_HEADERS != 0 && ctx->closed_lds && shade_closed(ctx); }
+/* ... and of that form the one in workgroups of 512 lanes with one table for eight waves, six waves per SIMD (create_impl decides) */
+static bool shade_closed_lds6(const drt_context *ctx) { return ctx->closed_lds6 && shade_closed_lds(ctx); }
+/* a shade launch's workgroup, in waves, and the cap of its persistent grid (`list`: an adaptive round, the general LIST instantiation) */
+static uint32_t shade_launch_waves(const drt_context *ctx, bool list) { return !list && shade_closed_lds6(ctx) ? SHADE_WAVES_CLOSED_LDS6 : SHADE_WAVES; }
+static uint32_t shade_launch_grid_cap(const drt_context *ctx, bool list) { return (uint32_t)(!list && shade_closed_lds6(ctx) ? ctx->shade_grid_cap6 : ctx->shade_grid_cap); }
 
 template <int NSETS, bool XYZ, bool LIST>
 static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams &sp, double *const film[3])
@@ -944,6 +953,16 @@ static int launch_shade_mode(drt_context *ctx, uint32_t grid, const ShadeParams 
     hipLaunchKernelGGL((KERNEL<DARK>), dim3(grid), dim3(SHADE_BLOCK), LDS_BYTES, ctx->stream, ctx->dsc, sp, ctx->d_records, \
                        ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
 #if DRT_SHADE_CLOSED_LDS_HEADERS
+        if (shade_closed_lds6(ctx))
+        {
+#define DRT_LAUNCH_CLOSED6(DARK)                                                                                                                   \
+    hipLaunchKernelGGL((drt_shade_kernel_closed_lds6<DARK>), dim3(grid), dim3(SHADE_BLOCK_CLOSED_LDS6), ctx->shade_lds_closed6, ctx->stream, ctx->dsc, sp, \
+                       ctx->d_records, ctx->d_headers, film[0], film[1], film[2], ctx->d_counters + DRT_NUM_COUNTERS + 1)
+            if (shade_dark(ctx, sp)) DRT_LAUNCH_CLOSED6(true);
+            else DRT_LAUNCH_CLOSED6(false);
+#undef DRT_LAUNCH_CLOSED6
+            return 0;
+        }
         if (shade_closed_lds(ctx))
         {
             if (shade_dark(ctx, sp)) DRT_LAUNCH_CLOSED(drt_shade_kernel_closed_lds, true, ctx->shade_lds_closed);
@@ -1471,6 +1490,15 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     /* the form with headers in LDS is there for its fifth wave: where five workgroups do not fit beside the table, the closed kernel
      * with the headers in registers runs, as it does with DRT_NO_CLOSED_LDS=1 (the A/B of the two from one library) */
     ctx->closed_lds = lds_closed.groups >= DRT_SHADE_WAVES_CLOSED_LDS * SHADE_SIMDS_PER_CU / SHADE_WAVES && getenv("DRT_NO_CLOSED_LDS") == nullptr;
+    /* Six waves: every workgroup holds the table, so a sixth workgroup of four waves never fits beside a table of 38 rows -- three
+     * workgroups of eight waves with one table each do. The runtime is asked, and the form runs only where it answers three (asked
+     * below, once the context's instantiation is known); DRT_CLOSED_WAVES=5 (or 4) keeps the five-wave kernel: the A/B from one library. */
+    static_assert(SHADE_WAVES_CLOSED_LDS6 == SHADE_LDS_SIX_BLOCK_WAVES && DRT_SHADE_WAVES_CLOSED_LDS6 == SHADE_LDS_SIX_WAVES_PER_SIMD, "the rule's shape is the kernel's");
+    const ShadeLdsPlan lds_closed6 = shade_lds_plan_six(ctx->dsc.n_spd, S, ctx->spds_in_lds, SHADE_WAVE_LDS_WORDS_FOR(true));
+    ctx->shade_lds_closed6 = lds_closed6.group_bytes;
+    const uint32_t groups6 = SHADE_LDS_SIX_GROUPS;
+    int closed_waves_asked = DRT_SHADE_WAVES_CLOSED_LDS6;
+    if (const char *e = getenv("DRT_CLOSED_WAVES")) closed_waves_asked = atoi(e);
     int s_per_cu = 0;
     shade_sets(S, &ctx->shade_sets, &ctx->tail_first, &ctx->tail_count);
     switch (ctx->shade_sets)
@@ -1486,6 +1514,16 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
      * more than the other instantiations': that one must also fit) */
     if (shade_closed_lds(ctx)) s_per_cu = std::min(s_per_cu, (int)lds_closed.groups);
     if (s_per_cu < 1) s_per_cu = 1;
+    int s6_query = -1; /* the query's answer for the six-wave kernel (-1: not asked) */
+#if DRT_SHADE_CLOSED_LDS_HEADERS
+    if (shade_closed_lds(ctx) && closed_waves_asked >= DRT_SHADE_WAVES_CLOSED_LDS6 && shade_lds_six_fits(lds_closed6))
+    {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&s6_query, drt_shade_kernel_closed_lds6<true>, SHADE_BLOCK_CLOSED_LDS6, ctx->shade_lds_closed6));
+        ctx->closed_lds6 = s6_query == (int)groups6; /* (more cannot be: the kernel's register bound; fewer: five waves of the other form are better) */
+    }
+#endif
+    ctx->shade_grid_cap6 = prop.multiProcessorCount * (int)groups6;
+    if (const char *e = getenv("DRT_SHADE_BLOCKS_PER_CU")) ctx->shade_grid_cap6 = prop.multiProcessorCount * std::min((int)groups6, std::max(1, atoi(e)));
     if (const char *e = getenv("DRT_SHADE_BLOCKS_PER_CU")) s_per_cu = std::max(1, atoi(e)); /* tuning knob */
     ctx->shade_grid_cap = prop.multiProcessorCount * s_per_cu;
     /* Both grids are persistent and fill every wave slot of the chip, so a kernel of another stream -- a collective's,
@@ -1496,6 +1534,7 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
         int n = std::max(0, atoi(e));
         ctx->trace_grid_cap = std::max(1, ctx->trace_grid_cap - n);
         ctx->shade_grid_cap = std::max(1, ctx->shade_grid_cap - n);
+        ctx->shade_grid_cap6 = std::max(1, ctx->shade_grid_cap6 - n);
     }
     if (const char *e = getenv("DRT_TRACE_CHUNK")) ctx->trace_chunk_override = (uint32_t)std::min(1 << 20, std::max(64, atoi(e) / 64 * 64));
     if (const char *e = getenv("DRT_TAIL_PERIOD")) ctx->shade_overrides.tail_period = (uint32_t)std::max(0, atoi(e));
@@ -1629,6 +1668,11 @@ static int create_impl(drt_context *ctx, const drt_scene *scene, const drt_camer
     if (ctx->tail_count) HIP_TRY(ctx->d_tail_stage.need((size_t)npx * batch * ctx->tail_count));
     if (ctx->tail_count && ctx->tail_resume) HIP_TRY(ctx->d_tail_resume.need((size_t)npx * batch * ctx->tail_count));
     if (const char *e = getenv("DRT_DARK_SKIP")) ctx->dark_skip = ctx->dark_skip_win = atoi(e) != 0; /* A/B switch of the parity tests: same film either way */
+    if (getenv("DRT_VERBOSE"))
+        fprintf(stderr, "drt: shade kernel %s; six waves: %s, occupancy query %d workgroups of %d lanes per CU, lds %zu (LDS rule: %u), grid cap %d\n",
+                shade_closed_lds6(ctx) ? "drt_shade_kernel_closed_lds6" : shade_closed_lds(ctx) ? "drt_shade_kernel_closed_lds" : shade_closed(ctx) ? "drt_shade_kernel_closed" : "drt_shade_kernel",
+                shade_closed_lds6(ctx) ? "chosen" : s6_query >= 0 ? "refused by the query" : "not asked", s6_query, SHADE_BLOCK_CLOSED_LDS6, ctx->shade_lds_closed6,
+                lds_closed6.groups, ctx->shade_grid_cap6);
     if (getenv("DRT_VERBOSE"))
         fprintf(stderr, "drt: %d CUs, trace %d blocks/CU (lds %zu), shade %d blocks/CU (%s, occupancy query %d, lds %zu; LDS rule: general %u, closed %u of %zu bytes), batch %u, %.3f blocks/path measured (worst %u), pool %.2f GB\n",
                 prop.multiProcessorCount, per_cu, ctx->trace_lds, s_per_cu, shade_closed_lds(ctx) ? "closed, headers in LDS" : shade_closed(ctx) ? "closed" : "general", s_query,
@@ -1946,7 +1990,8 @@ static int enqueue_pair(drt_context *ctx, const PairSpan &span)
     sp.sample_base = span.list ? ctx->d_counts : nullptr;
     sp.mode = ctx->debug_shade_mode;
     sp.cmf_rw = ctx->cmf_rw; sp.cmf_x = ctx->cmf_x; sp.cmf_y = ctx->cmf_y; sp.cmf_z = ctx->cmf_z;
-    const ShadeQueue q = shade_queue(g.n_pix, span.n_samples, ctx->tail_count, sp.tail_staged, (uint32_t)ctx->shade_grid_cap, SHADE_WAVES, SHADE_PIXEL_CHUNK,
+    const ShadeQueue q = shade_queue(g.n_pix, span.n_samples, ctx->tail_count, sp.tail_staged, shade_launch_grid_cap(ctx, span.list != nullptr),
+                                     shade_launch_waves(ctx, span.list != nullptr), SHADE_PIXEL_CHUNK,
                                      ctx->shade_overrides);
     if (q.too_large) return fail(-1, "tile too large for the shade work queue");
     sp.chunk = q.chunk;
@@ -2371,6 +2416,13 @@ extern "C" int drt_shade_closed_lds(const drt_context *ctx)
 {
     if (!ctx) return -1;
     return shade_closed_lds(ctx) ? 1 : 0;
+}
+
+extern "C" int drt_shade_closed_waves(const drt_context *ctx)
+{
+    if (!ctx) return -1;
+    if (!shade_closed(ctx)) return 0;
+    return shade_closed_lds6(ctx) ? DRT_SHADE_WAVES_CLOSED_LDS6 : shade_closed_lds(ctx) ? DRT_SHADE_WAVES_CLOSED_LDS : DRT_SHADE_WAVES_CLOSED;
 }
 
 /*

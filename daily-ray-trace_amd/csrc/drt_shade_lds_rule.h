@@ -10,6 +10,11 @@
  * workgroups also fit the LDS: the headline scene's table is 38 rows of 69 (20 976 bytes), and with the 2 912-byte regions of the
  * general instantiations a workgroup is 32 624 bytes -- five of them are 163 120 bytes, inside 160 KiB only if LDS were handed out to
  * the byte. It is handed out in granules; with them four workgroups fit, whatever the registers allow.
+ *
+ * A sixth wave per SIMD as a sixth workgroup of four waves is out of reach for that table: 163 840 / 6 is 26 880 bytes in granules, and
+ * the table alone takes 20 976. The table is the same in every workgroup, so the six-wave form has workgroups of eight waves that
+ * share one copy: shade_lds_plan_six() -- 20 976 + 8 x 2 560 = 41 456 bytes, 33 granules, and three such workgroups (24 waves, six per
+ * SIMD) are 126 720 bytes.
  */
 #ifndef DRT_SHADE_LDS_RULE_H
 #define DRT_SHADE_LDS_RULE_H
@@ -50,5 +55,18 @@ static inline ShadeLdsPlan shade_lds_plan(uint32_t n_spd, uint32_t S, bool spds_
     p.waves_per_simd = p.groups * block_waves / SHADE_SIMDS_PER_CU;
     return p;
 }
+
+/* The six-wave shape: workgroups of SHADE_LDS_SIX_BLOCK_WAVES waves behind one table, SHADE_LDS_SIX_GROUPS of them on a compute unit. */
+#define SHADE_LDS_SIX_BLOCK_WAVES 8u
+#define SHADE_LDS_SIX_WAVES_PER_SIMD 6u
+#define SHADE_LDS_SIX_GROUPS (SHADE_LDS_SIX_WAVES_PER_SIMD * SHADE_SIMDS_PER_CU / SHADE_LDS_SIX_BLOCK_WAVES) /* 3 */
+
+static inline ShadeLdsPlan shade_lds_plan_six(uint32_t n_spd, uint32_t S, bool spds_in_lds, uint32_t wave_words)
+{
+    return shade_lds_plan(n_spd, S, spds_in_lds, SHADE_LDS_SIX_BLOCK_WAVES, wave_words, SHADE_LDS_SIX_WAVES_PER_SIMD);
+}
+
+/* whether the shape keeps its six waves per SIMD beside this table (the launcher then still asks the runtime) */
+static inline bool shade_lds_six_fits(const ShadeLdsPlan &p) { return p.groups >= SHADE_LDS_SIX_GROUPS; }
 
 #endif

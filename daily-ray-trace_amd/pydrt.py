@@ -725,6 +725,9 @@ def hip_lib():
         if hasattr(L, "drt_shade_closed_lds"):
             L.drt_shade_closed_lds.argtypes = [C.c_void_p]
             L.drt_shade_closed_lds.restype = C.c_int
+        if hasattr(L, "drt_shade_closed_waves"):
+            L.drt_shade_closed_waves.argtypes = [C.c_void_p]
+            L.drt_shade_closed_waves.restype = C.c_int
         if hasattr(L, "drt_update_surfaces"):
             L.drt_set_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
             L.drt_update_surfaces.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -812,7 +815,7 @@ def hip_lib():
 
 SHADE_INSTANTIATIONS = ("general", "simple", "closed")  # DRT_SHADE_GENERAL, DRT_SHADE_SIMPLE, DRT_SHADE_CLOSED
 
-HIP_SYMBOLS = ["drt_shade_instantiation", "drt_shade_closed_lds",
+HIP_SYMBOLS = ["drt_shade_instantiation", "drt_shade_closed_lds", "drt_shade_closed_waves",
                "drt_last_error", "drt_device_count", "drt_create", "drt_destroy", "drt_bind_film", "drt_set_stream",
                "drt_render", "drt_synchronize", "drt_reset_film", "drt_film_device_ptrs", "drt_read_film", "drt_write_film",
                "drt_read_xyz", "drt_read_bgra", "drt_read_hit_indices", "drt_get_stats", "drt_batch_spp", "drt_render_tile", "drt_selftest_arith",
@@ -1273,6 +1276,11 @@ class Renderer:
     def shade_closed_lds(self):
         """whether the closed instantiation runs in its form with window headers in LDS, five waves per SIMD (drt_shade_closed_lds)"""
         return int(self.L.drt_shade_closed_lds(self.ctx)) == 1
+
+    def shade_closed_waves(self):
+        """waves per SIMD of the closed kernel a context's dense launches run: 6 (drt_shade_kernel_closed_lds6, workgroups of 512 lanes),
+        5 (drt_shade_kernel_closed_lds), 4 (drt_shade_kernel_closed); 0: not the closed instantiation (drt_shade_closed_waves)"""
+        return int(self.L.drt_shade_closed_waves(self.ctx))
 
     def stats(self):
         st = Stats()

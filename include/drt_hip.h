@@ -270,6 +270,9 @@ int drt_shade_instantiation(const drt_context *ctx);
 /* 1: the context's dense launches run the closed instantiation's form with window headers in LDS, five waves per SIMD
  * (drt_shade_kernel_closed_lds); 0: any other kernel; -1: null context */
 int drt_shade_closed_lds(const drt_context *ctx);
+/* waves per SIMD of the closed kernel the context's dense launches run: 6 (drt_shade_kernel_closed_lds6: 512-lane workgroups, one SPD
+ * table for eight waves; DRT_CLOSED_WAVES=5 at creation keeps the five-wave kernel), 5, 4; 0: another instantiation; -1: null context */
+int drt_shade_closed_waves(const drt_context *ctx);
 
 /*
  * One-shot form matching the reference's loop: host buffers, caller-owned,

@@ -2,7 +2,7 @@
 """Per-kernel register / spill / scratch / occupancy figures of libdrt_hip.so's kernels, from the compiler's own output: the device
 assembly of csrc/drt_launcher.hip (the Makefile's flags plus -S -gline-tables-only) and the kernel metadata at its end. Extra
 arguments are passed on (e.g. -DSHADE_PREFETCH_DEPTH=3).   python3 tools/kernel_resources.py [filter substring | group] [--loops] [--waits] [--asm=FILE] [-D...]
-A filter that names a group (GROUPS below: `features`, `mattes`, `rays`, `rayfilm`, `trace`, `update`, `build`, `material`) stands for the group's kernels.
+A filter that names a group (GROUPS below: `features`, `mattes`, `rays`, `rayfilm`, `closed`, `trace`, `update`, `build`, `material`) stands for the group's kernels.
 
 Columns: VGPRs, SGPRs, `sspill` / `vspill` = the metadata's .sgpr_spill_count / .vgpr_spill_count, scratch bytes per lane, static
 LDS, occupancy (waves per SIMD, from the VGPR count), `valu` = vector ALU instructions in the kernel's text, `lanemv` = how many of
@@ -37,6 +37,8 @@ GROUPS = {"features": ("drt_feature_kernel", "drt_feature_bvh_kernel", "drt_feat
           # the ray-mode entry points of the render path (drt_bind_rays) and the camera twins they share their bodies with
           "rayfilm": ("drt_trace_rays_kernel", "drt_primary_rays_kernel", "drt_bounce_rays_kernel", "drt_trace_kernel", "drt_primary_kernel",
                       "drt_bounce_kernel"),
+          # the closed shade kernel's three forms: four waves, five (headers in LDS), six (512-lane workgroups)
+          "closed": ("drt_shade_kernel_closed<", "drt_shade_kernel_closed_lds<", "drt_shade_kernel_closed_lds6<"),
           # the trace kernel's two forms: drt_trace_kernel starts paths from its ray stash, drt_trace_direct_kernel in the idle lane
           "trace": ("drt_trace_kernel", "drt_trace_direct_kernel"),
           # scene updates (drt_update_surfaces, drt_set_camera)
